@@ -8,19 +8,28 @@ across GPUs with no data-path collective).
 
 Serving-loop shape of the timed region: POOL distinct batches stay resident in HBM; step s copies batch
 s % POOL into the static input buffers of the captured HIP graph of stream s % inflight (device-to-device,
-on that stream) and replays it -- so consecutive steps see different data.  The K-step region demanded by
-the driver contract (barrier + synchronize on both sides, max over ranks) is REPEATED until at least
---min-time seconds have been timed; `ms_per_step` / `value` are the median region, every region is listed.
-`value_tied_inputs`: the same loop on batches whose first cloud contains duplicated points, so its FPS
-arg-maxima tie and the real second-level FPS pass (not the prefix shortcut) is priced.
+on that stream) and replays it -- so consecutive steps see different data.  The timed region is --steps
+steps (barrier + synchronize on both sides, max over ranks); `ms_per_step` is its time / --steps and
+`value` the frames/s it sustained.
 
-    python bench.py --gpus 1 --steps 50 --warmup 10
+A plain run does only that: set-up, --warmup steps, the timed region, --dump-outputs if given, the line.
+--full adds everything else, as before: the K-step region is REPEATED until at least --min-time seconds
+have been timed (`ms_per_step` / `value` are then the median region, every region is listed),
+`value_tied_inputs` (the same loop on batches whose first cloud contains duplicated points, so its FPS
+arg-maxima tie and the real second-level FPS pass, not the prefix shortcut, is priced), the single-stream
+and eager reference points, the replay check, and these extra objects:
+  roofline      dominant hand-written kernel, timed live with HIP events on the launching stream
+  train / stress / latency_b1   secondary legs in child processes (scripts/bench_legs.py)
+  cpu_baseline  the reference's CPU path (port, oracle/cpu_reference.py) on this box's host cores
+
+    python bench.py --gpus 1 --steps 50 --warmup 10 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
            --master-port 29500 bench.py --gpus 8 --steps 50 --warmup 10
 
-Prints ONE JSON line (rank 0).  Extra objects:
-  roofline      dominant hand-written kernel, timed live with HIP events on the launching stream
-  cpu_baseline  the reference's CPU path (port, oracle/cpu_reference.py) on this box's host cores
+Prints ONE JSON line (rank 0).
+--dump-outputs DIR: rank 0 writes what the forward of the last timed step returned (pred_kp, canon_pose, ...) as
+DIR/<name>.npy (float32; float64 for other dtypes), at most DUMP_LIMIT_BYTES in all.  The inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -219,6 +228,36 @@ def make_pool(rank, batch, npoints, dev, tied=False):
     return pool
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def host_outputs(d, prefix=""):
+    """{dotted name: float32 / float64 numpy array} of every tensor in a forward's (nested) output dict, copied to the host."""
+    out = {}
+    for k in sorted(d):
+        v = d[k]
+        if isinstance(v, dict):
+            out.update(host_outputs(v, prefix + k + "."))
+        elif torch.is_tensor(v):
+            t = v.detach().cpu()
+            ok32 = t.dtype in (torch.float32, torch.float16, torch.bfloat16)
+            out[prefix + k] = t.to(torch.float32 if ok32 else torch.float64).numpy()
+    return out
+
+
+def dump_outputs(arrays, path):
+    """DIR/<name>.npy per array; above DUMP_LIMIT_BYTES in all, each array is cut to the same fixed, seeded share of its
+    elements (flat indices in ascending order)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES:
+            k = max(1, int(a.size * DUMP_LIMIT_BYTES / total))
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, k, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -226,8 +265,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=64, help="clouds per GPU per step (BASELINE configs[1])")
     ap.add_argument("--npoints", type=int, default=1024)
-    ap.add_argument("--min-time", type=float, default=6.0, help="repeat the K-step timed region until this many seconds are timed "
-                    "(default 6 s: longer than the 5-s tick of an external GPU-busy sampler)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: repeated regions (--min-time), tied inputs, "
+                    "single-stream / eager points, per-kernel roofline, replay check, secondary legs, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy")
+    ap.add_argument("--min-time", type=float, default=6.0, help="with --full: repeat the K-step timed region until this many "
+                    "seconds are timed (default 6 s: longer than the 5-s tick of an external GPU-busy sampler)")
     ap.add_argument("--train-steps", type=int, default=20, help="steps of the training leg (configs[2] per GPU, 32 x 1024, whole step "
                     "as HIP graphs; WORLD_SIZE > 1: data parallel with a flat-gradient RCCL all-reduce) appended after the headline "
                     "regions; 0 = skip")
@@ -245,6 +287,7 @@ def main():
                     "i %% inflight (each stream has its own captured graph and buffers), so one batch's FPS / small "
                     "kernels overlap another batch's GEMMs")
     args = ap.parse_args()
+    full = args.full
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -276,8 +319,8 @@ def main():
 
     model = build_model(dev, elide=not args.no_elide)
     pool = make_pool(rank, args.batch, args.npoints, dev)          # seeded per rank, resident in HBM
-    tied_pool = make_pool(rank, args.batch, args.npoints, dev, tied=True)
-    timer = KernelTimer()
+    tied_pool = make_pool(rank, args.batch, args.npoints, dev, tied=True) if full else None
+    timer = KernelTimer() if full else None
 
     def sync_all():
         torch.cuda.synchronize()
@@ -301,12 +344,13 @@ def main():
         eager_ms = None
         if use_graph:
             # one forward = ~50 short kernels: capture it once per stream, replay it per step (no host launch cost)
-            sync_all()
-            t0 = time.perf_counter()
-            for i in range(5):
-                model(pool[i % POOL][0], dict(FLAGS))
-            torch.cuda.synchronize()
-            eager_ms = (time.perf_counter() - t0) / 5 * 1e3
+            if full:
+                sync_all()
+                t0 = time.perf_counter()
+                for i in range(5):
+                    model(pool[i % POOL][0], dict(FLAGS))
+                torch.cuda.synchronize()
+                eager_ms = (time.perf_counter() - t0) / 5 * 1e3
             from hotrack_amd import ext
             import hotrack_amd
             hotrack_amd.streams_in_flight(ninf)  # warns once when the hardware-queue setting would serialise the streams
@@ -327,18 +371,20 @@ def main():
                     slots[i][1].copy_(src_flat, non_blocking=True)
                     graphs[i].replay()
             g_single = None
-            if ninf > 1:  # the single-stream reference point replays a graph captured with every CU available to the SA grids
+            if full and ninf > 1:  # the single-stream reference point replays a graph captured with every CU available to the SA grids
                 ext.sa_set_compute_units(0)
                 g_single = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g_single):
                     out_single = model(slots[0][0], dict(FLAGS))
                 ext.sa_set_compute_units(sa_cus)
 
+        last = [None]  # the output dict of the most recent step
+
         def make_step(n, src):
             counter = [0]
             if not use_graph:
                 def step():
-                    outs[0] = model(src[counter[0] % POOL][0], dict(FLAGS))
+                    outs[0] = last[0] = model(src[counter[0] % POOL][0], dict(FLAGS))
                     counter[0] += 1
                 return step
 
@@ -350,10 +396,12 @@ def main():
                     with torch.cuda.stream(gstreams[0]):
                         slots[0][1].copy_(src[s % POOL][1], non_blocking=True)
                         g_single.replay()
+                    last[0] = out_single
                     return
                 # the serving loop's hand-over: this step's batch goes into the graph's static inputs (one device-to-device
                 # copy of the batch's flat buffer), on the graph's stream
                 replay_slot(i, src[s % POOL][1])
+                last[0] = outs[i]
             return step
 
         local_regions = []  # this rank's own wall time of every headline region (per-rank frames/s spread at N > 1)
@@ -379,41 +427,45 @@ def main():
         for _ in range(args.warmup):
             step()
         single_ms = None
-        if use_graph and ninf > 1:  # informational: the same K steps strictly one after another on one stream
+        if full and use_graph and ninf > 1:  # informational: the same K steps strictly one after another on one stream
             one = make_step(1, pool)
             sync_all()  # a graph must never be replayed while an earlier replay of it is still running
             for _ in range(3):
                 one()
             single_ms = timed_region(one) / args.steps * 1e3
         local_regions.clear()
-        regions = repeat_regions(step, args.min_time)   # ---- THE timed regions: K steps each, barrier + sync on both sides
+        # ---- THE timed regions: K steps each, barrier + sync on both sides (a plain run: exactly one)
+        regions = repeat_regions(step, args.min_time if full else 0.0)
         headline_local = sorted(local_regions)[len(local_regions) // 2]
-        tied_step = make_step(ninf, tied_pool)
-        sync_all()
-        for _ in range(3):
-            tied_step()
-        tied_regions = repeat_regions(tied_step, min(args.min_time, 0.3))
-        sync_all()
-        # separate short eager pass for the per-kernel HIP-event timing (events perturb the async pipeline)
-        timed_passes = min(args.steps, 20)
-        timer.start()
-        for i in range(timed_passes):
-            model(pool[i % POOL][0], dict(FLAGS))
-        torch.cuda.synchronize()
-        timer.stop()
-        # ---- what the replays computed: every resident batch through every stream's graph against the eager forward of that
-        # batch, at the headline size (a wrong-but-finite replay must not print a headline)
-        replay_check = None
-        if use_graph:
-            eager_kp = [model(pool[r][0], dict(FLAGS))["pred_kp"].clone() for r in range(POOL)]
-            worst = 0.0
-            for i in range(ninf):
-                for r in range(POOL):
-                    replay_slot(i, pool[r][1])
-                    gstreams[i].synchronize()
-                    worst = max(worst, float((outs[i]["pred_kp"] - eager_kp[r]).abs().max()))
-            assert worst <= 1e-5, f"graph replay differs from the eager forward of the same batch by {worst}"
-            replay_check = {"max_abs_diff_pred_kp": worst, "batches": POOL, "streams": ninf, "tolerance": 1e-5}
+        if args.dump_outputs and rank == 0:  # the region ended with a synchronize: last[0] holds the last timed step's outputs
+            dump_outputs(host_outputs(last[0]), args.dump_outputs)
+        tied_regions, timed_passes, replay_check = None, 0, None
+        if full:
+            tied_step = make_step(ninf, tied_pool)
+            sync_all()
+            for _ in range(3):
+                tied_step()
+            tied_regions = repeat_regions(tied_step, min(args.min_time, 0.3))
+            sync_all()
+            # separate short eager pass for the per-kernel HIP-event timing (events perturb the async pipeline)
+            timed_passes = min(args.steps, 20)
+            timer.start()
+            for i in range(timed_passes):
+                model(pool[i % POOL][0], dict(FLAGS))
+            torch.cuda.synchronize()
+            timer.stop()
+            # ---- what the replays computed: every resident batch through every stream's graph against the eager forward of that
+            # batch, at the headline size (a wrong-but-finite replay must not print a headline)
+            if use_graph:
+                eager_kp = [model(pool[r][0], dict(FLAGS))["pred_kp"].clone() for r in range(POOL)]
+                worst = 0.0
+                for i in range(ninf):
+                    for r in range(POOL):
+                        replay_slot(i, pool[r][1])
+                        gstreams[i].synchronize()
+                        worst = max(worst, float((outs[i]["pred_kp"] - eager_kp[r]).abs().max()))
+                assert worst <= 1e-5, f"graph replay differs from the eager forward of the same batch by {worst}"
+                replay_check = {"max_abs_diff_pred_kp": worst, "batches": POOL, "streams": ninf, "tolerance": 1e-5}
     assert all(torch.isfinite(o["pred_kp"]).all() for o in outs if o is not None)
 
     # ---- secondary legs, all OUTSIDE the headline regions and each in a CHILD process (scripts/bench_legs.py): an exception, a
@@ -425,19 +477,21 @@ def main():
     per_rank = None
     legs = {}
     torch.cuda.synchronize()
-    sys.path.insert(0, os.path.join(ROOT, "scripts"))
-    import bench_legs
+    no_legs = args.no_legs or not full
+    if not no_legs:
+        sys.path.insert(0, os.path.join(ROOT, "scripts"))
+        import bench_legs
     backend_world = dist.get_world_size() if world > 1 else 1
     assert backend_world == args.gpus, f"backend sees {backend_world} ranks, --gpus {args.gpus}"
-    if world > 1:
+    if full and world > 1:
         t = torch.tensor([args.batch * args.steps / headline_local], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
         gathered = [torch.zeros_like(t) for _ in range(world)]
         dist.all_gather(gathered, t)
         per_rank = [round(float(g), 1) for g in gathered]
-    if use_graph and not args.no_legs:
+    if use_graph and not no_legs:
         del graphs, slots, g_single
         torch.cuda.empty_cache()
-    if not args.no_legs and args.train_steps > 0:
+    if not no_legs and args.train_steps > 0:
         if world > 1:
             import socket
             port = torch.zeros(1, dtype=torch.int64, device=dev if backend == "nccl" else "cpu")
@@ -464,7 +518,7 @@ def main():
             legs["train"] = got
         else:
             legs["train"] = bench_legs.run_child(bench_legs.leg_cmd("train", args.train_steps, 5, 32), 420)
-    if not args.no_legs and world == 1:
+    if not no_legs and world == 1:
         legs["stress"] = bench_legs.run_child(bench_legs.leg_cmd("stress"), 300)
         legs["latency_b1"] = bench_legs.run_child(bench_legs.leg_cmd("latency"), 300)
     if world > 1:
@@ -476,8 +530,30 @@ def main():
         dt = med
         frames_per_region = args.batch * world * args.steps
         fps = frames_per_region / dt
-        tied_fps = frames_per_region / sorted(tied_regions)[len(tied_regions) // 2]
         alg_bytes = ALG_BYTES_PER_FRAME_1024 if args.npoints == 1024 else None
+        res = {
+            "metric": "HandTrackNet point-cloud frames/sec (N=%d)" % args.npoints, "value": round(fps, 2), "unit": "frames/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "timed_region_s": round(sum(regions), 4), "timed_regions": len(regions),
+            "region_ms_per_step": {"min": round(min(regions) / args.steps * 1e3, 4), "median": round(med / args.steps * 1e3, 4),
+                                   "max": round(max(regions) / args.steps * 1e3, 4)},
+            "config": {"workload": "HandTrackNet forward, batch=%d synthetic %d-pt clouds per GPU (BASELINE configs[1])"
+                                   % (args.batch, args.npoints),
+                       "per_gpu_batch": args.batch, "global_batch": args.batch * world, "npoints": args.npoints,
+                       "parallelism": "dp%d (independent batches, no collective)" % world, "world_size": world,
+                       "resident_batches_rotated": POOL,
+                       "dead_attention_elided": not args.no_elide, "fused_sa_kernels": fused_on,
+                       "launch": "hipGraph replay" if use_graph else "eager", "batches_in_flight": ninf,
+                       "hip_hw_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "4")),
+                       "sa_compute_units": (sa_cus or 256) if use_graph else 256,
+                       "weights": "deterministic random init (no checkpoint available offline)"},
+            "frame_alg_bytes": alg_bytes,
+            "frame_hbm_frac": None if alg_bytes is None else round(alg_bytes * fps / world / 1e9 / HBM_PEAK_GBS, 6),
+        }
+        if not full:
+            print(json.dumps(res), flush=True)
+            return
         # dominant hand-written kernel = largest (mean launch time x launches per step) among the hooked kernels
         ks = timer.summary(timed_passes)
         per_kernel = sorted(({"key": k, "sec": v[0], "per_step": v[1]} for k, v in ks.items()),
@@ -509,34 +585,13 @@ def main():
                                               "MI355X_MICROARCH.md)" % os.path.basename(src))
         except (OSError, KeyError, ValueError, IndexError):
             pass
-        res = {
-            "metric": "HandTrackNet point-cloud frames/sec (N=%d)" % args.npoints, "value": round(fps, 2), "unit": "frames/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "timed_region_s": round(sum(regions), 4), "timed_regions": len(regions),
-            "region_ms_per_step": {"min": round(min(regions) / args.steps * 1e3, 4), "median": round(med / args.steps * 1e3, 4),
-                                   "max": round(max(regions) / args.steps * 1e3, 4)},
-            "value_tied_inputs": round(tied_fps, 2),
-            "config": {"workload": "HandTrackNet forward, batch=%d synthetic %d-pt clouds per GPU (BASELINE configs[1])"
-                                   % (args.batch, args.npoints),
-                       "per_gpu_batch": args.batch, "global_batch": args.batch * world, "npoints": args.npoints,
-                       "parallelism": "dp%d (independent batches, no collective)" % world, "world_size": world,
-                       "resident_batches_rotated": POOL,
-                       "tied_inputs": "cloud 0 of every batch has 64 duplicated points: FPS arg-maxima tie, the second-level FPS "
-                                      "runs its real pass for that cloud (value_tied_inputs, %d regions)" % len(tied_regions),
-                       "dead_attention_elided": not args.no_elide, "fused_sa_kernels": fused_on,
-                       "launch": "hipGraph replay" if use_graph else "eager", "batches_in_flight": ninf,
-                       "hip_hw_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "4")),
-                       "sa_compute_units": (sa_cus or 256) if use_graph else 256,
-                       "single_stream_ms_per_step": None if single_ms is None else round(single_ms, 4),
-                       "eager_ms_per_step": None if eager_ms is None else round(eager_ms, 4),
-                       "weights": "deterministic random init (no checkpoint available offline)"},
-            "frame_alg_bytes": alg_bytes,
-            "frame_hbm_frac": None if alg_bytes is None else round(alg_bytes * fps / world / 1e9 / HBM_PEAK_GBS, 6),
-            "roofline": roof,
-            "kernels": other,
-            "replay_check": replay_check,
-        }
+        res["value_tied_inputs"] = round(frames_per_region / sorted(tied_regions)[len(tied_regions) // 2], 2)
+        res["config"].update({
+            "tied_inputs": "cloud 0 of every batch has 64 duplicated points: FPS arg-maxima tie, the second-level FPS runs its real "
+                           "pass for that cloud (value_tied_inputs, %d regions)" % len(tied_regions),
+            "single_stream_ms_per_step": None if single_ms is None else round(single_ms, 4),
+            "eager_ms_per_step": None if eager_ms is None else round(eager_ms, 4)})
+        res.update({"roofline": roof, "kernels": other, "replay_check": replay_check})
         from hotrack_amd import gemm_tuning
         res["gemm_table"] = gemm_tuning.status()["gemm_table"]
         res["config"]["gemm_table_detail"] = gemm_tuning.status()["detail"]

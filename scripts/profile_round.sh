@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage (GPU box, repo root): scripts/profile_round.sh rNN   -> gpurun_out/rNN_* (copy what is to be judged into profiles/)
-#   rNN_bench.json               the default `python bench.py` line
-#   rNN_bench_kernel_stats.csv   rocprofv3 --kernel-trace --stats of `python bench.py --no-cpu-baseline`
+#   rNN_bench.json               the `python bench.py --full` line
+#   rNN_bench_kernel_stats.csv   rocprofv3 --kernel-trace --stats of `python bench.py --full --no-cpu-baseline`
 #   rNN_bench_kernel_by_grid.csv the same trace per (kernel, grid)
 #   rNN_pmc_traffic.json         FETCH_SIZE / WRITE_SIZE (separate --pmc passes, --kernel-trace only) -> HBM bytes per launch
 #   rNN_pmc_mfma.txt             MfmaUtil of the SA kernels (SQ_VALU_MFMA_BUSY_CYCLES, GRBM_GUI_ACTIVE: separate passes)
@@ -10,9 +10,9 @@ tag=$1
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out
 mkdir -p $O
-cd $R && python bench.py > $O/${tag}_bench.json 2> $O/${tag}_bench.err
+cd $R && python bench.py --full > $O/${tag}_bench.json 2> $O/${tag}_bench.err
 cd /tmp && export TMPDIR=/tmp
-rm -rf /tmp/prof_stats && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats -o b -- python $R/bench.py --no-cpu-baseline > $O/${tag}_stats.log 2>&1
+rm -rf /tmp/prof_stats && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats -o b -- python $R/bench.py --full --no-cpu-baseline > $O/${tag}_stats.log 2>&1
 cp $(find /tmp/prof_stats -name "*kernel_stats.csv" | head -1) $O/${tag}_bench_kernel_stats.csv
 python $R/scripts/kernel_trace_by_grid.py $(find /tmp/prof_stats -name "*kernel_trace.csv" | head -1) > $O/${tag}_bench_kernel_by_grid.csv
 for c in FETCH_SIZE WRITE_SIZE SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE; do

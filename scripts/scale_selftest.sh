@@ -9,11 +9,11 @@ R=$(cd "$(dirname "$0")/.." && pwd)
 cd "$R"
 Ns=${@:-2 4}
 export HOTRACK_DATA_ROOT=${HOTRACK_DATA_ROOT:-/tmp/hotrack_selftest}
-one=$(python bench.py --gpus 1 --steps 5 --warmup 2 --min-time 0.2 --no-cpu-baseline | grep '^{')
+one=$(python bench.py --full --gpus 1 --steps 5 --warmup 2 --min-time 0.2 --no-cpu-baseline | grep '^{')
 for N in $Ns; do
   port=$((29600 + N))
   line=$(PN2_BENCH_BACKEND=gloo PN2_BENCH_LEG_TIMEOUT=240 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 \
-         --master-port $port bench.py --gpus $N --steps 5 --warmup 2 --min-time 0.2 --train-steps 5 --no-cpu-baseline | grep '^{')
+         --master-port $port bench.py --full --gpus $N --steps 5 --warmup 2 --min-time 0.2 --train-steps 5 --no-cpu-baseline | grep '^{')
   python - "$N" "$line" "$one" <<'PY'
 import json, sys
 n, d, one = int(sys.argv[1]), json.loads(sys.argv[2]), json.loads(sys.argv[3])
@@ -36,7 +36,7 @@ done
 # a training leg that dies on ONE rank (its peers then wait for it until the leg's timeout): the headline must survive, the
 # line must carry train.error, and the process group of the parents must still shut down cleanly (exit code 0)
 line=$(PN2_BENCH_BACKEND=gloo PN2_BENCH_FAIL_TRAIN_LEG=1 PN2_BENCH_LEG_TIMEOUT=90 python -m torch.distributed.run --nnodes=1 \
-       --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29650 bench.py --gpus 2 --steps 5 --warmup 2 --min-time 0.2 \
+       --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29650 bench.py --full --gpus 2 --steps 5 --warmup 2 --min-time 0.2 \
        --train-steps 5 --no-cpu-baseline | grep '^{')
 python - "$line" <<'PY'
 import json, sys

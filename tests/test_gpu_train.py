@@ -325,7 +325,7 @@ def test_bn_relu_max_matches_unfused(G, K, C, ties):
     assert torch.equal(a[4], b_[4]) and torch.equal(a[5], b_[5])
 
 
-def test_graph_captured_data_parallel_step_two_ranks_one_gpu():
+def test_graph_captured_data_parallel_step_two_ranks_one_gpu(tmp_path):
     """Trainer's "flat" data-parallel mode under torch.distributed.run: forward+backward HIP graph | one all-reduce of the flat
     gradient buffer | optimiser HIP graph.  Two ranks share this GPU over gloo (RCCL refuses two ranks on one device; the
     collective call site is the same), launched the way the driver launches bench.py."""
@@ -335,7 +335,7 @@ def test_graph_captured_data_parallel_step_two_ranks_one_gpu():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
-    env = dict(os.environ, PN2_DIST_BACKEND="gloo", HOTRACK_DATA_ROOT="/tmp/hotrack_test_dp")
+    env = dict(os.environ, PN2_DIST_BACKEND="gloo", HOTRACK_DATA_ROOT=str(tmp_path))
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                           "--master-port", str(port), os.path.join(ROOT, "scripts", "bench_train.py"), "--steps", "6", "--warmup", "4",
                           "--batch", "8", "--graph"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
