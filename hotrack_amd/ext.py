@@ -702,3 +702,75 @@ def copy_multi(dsts, srcs) -> None:
             for j in range(k):
                 D[j], S[j], Bn[j] = dsts[i0 + j].data_ptr(), srcs[i0 + j].data_ptr(), dsts[i0 + j].numel() * dsts[i0 + j].element_size()
             _native._check(_lib.pn2x_copy_multi(k, D, S, Bn, _native._stream(dsts[0])), "copy_multi")
+
+
+# ---- the per-point chain fp1 -> conv1 -> q layer-1 over the rows the kNN lists name (include/pn2_ext.h: pn2x_row_chain) ----
+_lib.pn2x_row_lists.argtypes = [_ci] * 5 + [_vp] * 5
+_lib.pn2x_row_lists.restype = _ci
+_lib.pn2x_row_chain_supported.argtypes = [_ci] * 4
+_lib.pn2x_row_chain_supported.restype = _ci
+_lib.pn2x_row_chain.argtypes = [_ci, _ci, _vp, _ci, _vp, _vp] + [_vp] * 7 + [_vp, _ci, _ci, _vp]
+_lib.pn2x_row_chain.restype = _ci
+ROW_CHAIN_MAX_B = 1024
+
+
+def row_lists(gi: torch.Tensor, gi_small, n: int):
+    """Per-cloud lists of the distinct points the kNN index lists name: gi (B,J,KL) int32, gi_small (B,J,KS) int32 (or None: every
+    row of gi counts as small).  -> list (B,n) int32 (rows named by gi_small ascending, then the rest of
+    gi's rows ascending; entries past the count are not written) and counts (B,2) int32 [small, all]."""
+    if gi.dim() != 3 or gi.dtype != torch.int32 or not gi.is_cuda:
+        raise TypeError("row_lists: gi must be a (B,J,K) int32 GPU tensor")
+    gi = gi.contiguous()
+    B, J, KL = gi.shape
+    if gi_small is not None:
+        if gi_small.dim() != 3 or gi_small.shape[:2] != (B, J) or gi_small.dtype != torch.int32 or gi_small.device != gi.device:
+            raise ValueError("row_lists: gi_small must be (B,J,K2) int32 on gi's device")
+        gi_small = gi_small.contiguous()
+    KS = gi_small.shape[2] if gi_small is not None else KL
+    lst = torch.empty((B, n), dtype=torch.int32, device=gi.device)
+    counts = torch.empty((B, 2), dtype=torch.int32, device=gi.device)
+    with torch.cuda.device(gi.device):
+        _native._check(_native._call(_lib.pn2x_row_lists, "row_lists_kernel", None, B, n, J, KL, KS, gi.data_ptr(),
+                                     None if gi_small is None else gi_small.data_ptr(), lst.data_ptr(), counts.data_ptr(),
+                                     _native._stream(gi)), "row_lists")
+    return lst, counts
+
+
+def row_chain_supported(c_in: int, c_h: int, c_conv: int, c_q: int) -> bool:
+    return bool(_lib.pn2x_row_chain_supported(c_in, c_h, c_conv, c_q))
+
+
+def row_chain_pack(W: torch.Tensor) -> torch.Tensor:
+    """(n_out, k) weights -> the kernel's operand layout: k zero-padded to a multiple of 16, then [n-tile][k-group][lane][4] with
+    lane = 16 * (k quad inside the group) + (row inside the n-tile) (include/pn2_ext.h: pn2x_row_chain)."""
+    n_out, k = W.shape
+    kp = (k + 15) // 16 * 16
+    Wp = torch.zeros((n_out, kp), dtype=torch.float32, device=W.device)
+    Wp[:, :k] = W
+    return Wp.view(n_out // 16, 16, kp // 16, 4, 4).permute(0, 2, 3, 1, 4).contiguous()
+
+
+def row_chain(x: torch.Tensor, lst: torch.Tensor, counts: torch.Tensor, wa, ba, wb, bb, wc, bc, wq, out: torch.Tensor = None,
+              grid: int = 0) -> torch.Tensor:
+    """out[b, p, :512] for every listed point p of cloud b (pn2x_row_chain): x (B,N,>=132) [interp | xyz | pad] rows (last dim
+    contiguous, row stride a multiple of 4), lst / counts from row_lists, the four weight matrices packed by row_chain_pack
+    (wa: fp1 layer 1 as (128, 131) [features | xyz]; wb (128,128); wc (384,128); wq (512,384)) and the biases of the first three.
+    Rows / columns no list asks for are left as they are in `out` (B,N,>=512)."""
+    if x.dim() != 3 or not x.is_cuda or x.dtype != torch.float32 or x.stride(2) != 1 or x.stride(0) != x.shape[1] * x.stride(1):
+        raise TypeError("row_chain: x must be a (B,N,C) float32 GPU tensor with contiguous rows")
+    B, N, _ = x.shape
+    f32 = torch.float32
+    if out is None:
+        out = torch.empty((B, N, 512), dtype=f32, device=x.device)
+    if out.shape[:2] != (B, N) or out.shape[2] < 512 or out.stride(2) != 1 or out.stride(0) != N * out.stride(1) or out.dtype != f32:
+        raise ValueError("row_chain: out must be (B,N,>=512) float32 with contiguous rows")
+    if lst.shape != (B, N) or counts.shape != (B, 2) or lst.dtype != torch.int32 or counts.dtype != torch.int32:
+        raise ValueError("row_chain: list (B,N) / counts (B,2) int32 from row_lists")
+    with torch.cuda.device(x.device):
+        _native._check(_native._call(_lib.pn2x_row_chain, "row_chain_kernel", None, B, N, x.data_ptr(), x.stride(1), lst.data_ptr(),
+                                     counts.data_ptr(), _native._ptr(wa, "wa", f32, 128 * 144), _native._ptr(ba, "ba", f32, 128),
+                                     _native._ptr(wb, "wb", f32, 128 * 128), _native._ptr(bb, "bb", f32, 128),
+                                     _native._ptr(wc, "wc", f32, 384 * 128), _native._ptr(bc, "bc", f32, 384),
+                                     _native._ptr(wq, "wq", f32, 512 * 384), out.data_ptr(), out.stride(1), int(grid),
+                                     _native._stream(x)), "row_chain")
+    return out

@@ -285,6 +285,30 @@ int pn2x_sa_mlp_max_pair_supported(int k0, int k1, int c1, int c2, int c3);
 int pn2x_sa_mlp_max_pair(int b, int c1, int c2, int c3, const pn2x_sa_problem *p0, const pn2x_sa_problem *p1, void *stream);
 
 /*
+ * Per-point layers over the rows a kNN list names (hotrack_amd/csrc/row_chain.hip).
+ *
+ * pn2x_row_lists: for each cloud b, the distinct points named by gi (b, j, k_large) and gi_small (b, j, k_small) -- or, with
+ * gi_small NULL, by the first k_small entries of every gi list.  list (b, n): the points named by a small list in ascending
+ * order, then the points named only by a large list in ascending order (entries past the count are not written);
+ * counts (b, 2): [points named by a small list, points named by any list].  One workgroup per cloud, n <= 16384.
+ *
+ * pn2x_row_chain: for every listed point p of cloud b (r = b * n + p),
+ *     h1 = relu(Wa [x[r, 0:128] | x[r, 128:131]] + ba)   h2 = relu(Wb h1 + bb)   c = relu(Wc h2 + bc)   out[r, :] = Wq c
+ * with Wa (128, 131), Wb (128, 128), Wc (384, 128), Wq (512, 384) BatchNorm-folded: columns [0, 256) of out are written for the
+ * points named by a small list, columns [256, 512) for every listed point; nothing else is written.  The weights come in
+ * the kernel's operand layout (hotrack_amd/ext.py: row_chain_pack: k padded to a multiple of 16, [n/16][k/16][64][4]).
+ * x rows ldx >= 132 floats apart (x[r, 131] is ignored), out rows ldo >= 512 apart; both multiples of 4 floats, 16-byte
+ * aligned.  The counts are read on the device (no host sync; capturable).  grid: persistent workgroups, 0 = one per compute
+ * unit.  b <= 1024 (PN2_ERANGE otherwise).  Exact fp32 (v_mfma_f32_16x16x4_f32), summation order differs from a GEMM library.
+ */
+int pn2x_row_lists(int b, int n, int j, int k_large, int k_small, const int *gi, const int *gi_small, int *list, int *counts,
+                   void *stream);
+int pn2x_row_chain_supported(int c_in, int c_h, int c_conv, int c_q);
+int pn2x_row_chain(int b, int n, const float *x, int ldx, const int *list, const int *counts, const float *wa, const float *ba,
+                   const float *wb, const float *bb, const float *wc, const float *bc, const float *wq, float *out, int ldo,
+                   int grid, void *stream);
+
+/*
  * ---- training-mode building blocks on point-major activations (hotrack_amd/csrc/train_ops.hip) --------------------------
  * The reference trains every grouped MLP as Conv2d(1x1) + BatchNorm2d + ReLU on channel-major (B, C, S, K) tensors
  * (pointnet_utils.py:399-403, :460-462, :504-506, :577-581).  A 1x1 convolution is a GEMM over all R = B*S*K positions

@@ -50,6 +50,7 @@ class FastEval:
         self._consts = {}
         self._idents = {}
         self.two_level_fps = True  # level-2 sampling via the prefix property (ext.fps_two_level)
+        self.row_chain = True  # large batches: fp1 -> conv1 -> q layer 1 over the kNN-listed rows only (ext.row_chain)
 
     def _palm_idx(self, device):
         key = ("palm", str(device))
@@ -164,6 +165,20 @@ class FastEval:
                 q[(name, i)] = dict(wx=W1[:, C:C + 3].contiguous(), b1=b1, l2=l2, l3=l3, K=mod.nsample_list[i],
                                     wc=W1[:, C + 3:] if W1.shape[1] > C + 3 else None)
         P["q"] = q
+        # fp1 (both layers), conv1 and the four scales' layer-1 feature product as ONE launch over the rows some keypoint's kNN
+        # list names (ext.row_chain): weights in the kernel's operand layout, the small-K scale's columns first
+        P["row_chain"] = None
+        Ks = [q[("q1", i)]["K"] for i in range(2)]
+        Wc = P["conv1"][0]
+        if (len(fp1) == 2 and c_in == P["fp2"][-1][0].shape[0] and Ks[0] != Ks[1] and fp1[0][0].shape[1] == c_in + 3
+                and ext.row_chain_supported(c_in, fp1[0][0].shape[0], Wc.shape[0], 4 * wq[0].shape[0])
+                and fp1[1][0].shape == (c_in, c_in) and Wc.shape[1] == c_in and C == Wc.shape[0]):
+            i_s = Ks.index(min(Ks))
+            order = (i_s, 1 - i_s)
+            wqc = torch.cat([torch.cat([wq[i], wq[2 + i]], dim=0) for i in order], dim=0)
+            P["row_chain"] = dict(order=order, wa=ext.row_chain_pack(fp1[0][0]), ba=fp1[0][1].contiguous(),
+                                  wb=ext.row_chain_pack(fp1[1][0]), bb=fp1[1][1].contiguous(),
+                                  wc=ext.row_chain_pack(Wc), bc=P["conv1"][1].contiguous(), wq=ext.row_chain_pack(wqc))
         # Layer 1 of a keypoint branch is linear in the per-point feature, so it is a GEMM over POINTS for branches
         # whose J*K neighbour slots outnumber the points (K = 64: 1344 slots > 1024 points) and a GEMM over the
         # GATHERED slots for the small ones (K = 16: 336 rows instead of 1024).  Branch order inside each block:
@@ -191,13 +206,6 @@ class FastEval:
         key = ("perm", B, str(perm.device))
         if key not in self._idents:
             self._idents[key] = perm.reshape(1, -1).to(torch.int32).expand(B, -1).contiguous()
-        return self._idents[key]
-
-    def _ident(self, B, J, K, dev):
-        """(B, J, K) int32 identity neighbour index for slot-major gathered rows (row j*K + k of each cloud)."""
-        key = (B, J, K, str(dev))
-        if key not in self._idents:
-            self._idents[key] = torch.arange(J * K, dtype=torch.int32, device=dev).view(1, J, K).expand(B, J, K).contiguous()
         return self._idents[key]
 
     @staticmethod
@@ -343,17 +351,6 @@ class FastEval:
         # ---- fp1: interpolate l1 -> l0, [interp | xyz] (weights permuted to match) -> MLP; conv1 ----------
         assert c_i == l1_out.shape[2]
         ext.three_nn_interpolate_pm(xyz2, l1_xyz, l1_out, fp1_in[:, :, :c_i])
-        f = P["fp1_fused"]
-        if f is not None:  # both fp1 layers in one launch (pn2x_mlp2_rows): rows [interp | xyz | pad] -> 128 -> 128
-            x = ext.mlp2_rows(fp1_in.view(B * N, c_i + 4), f["w2"], f["b2"], f["w3"], f["b3"], w2e=f["w2e"])
-        else:
-            x = fp1_in.view(B * N, c_i + 4)[:, :c_i + 3]
-            for W, b in P["fp1"]:
-                x = _lin_relu(x, W, b)
-        src2 = _lin_relu(x, *P["conv1"])  # (B*N, C) per-point backbone features
-        C = src2.shape[1]
-
-        # ---- q1 / q2: kNN (16 / 64) neighbourhoods of the 21 keypoints ------------------------------------
         q = P["q"]
         # kNN lists are sorted by (distance, index): the K=16 list is the prefix of the K=64 list -> one search
         Ks = [q[("q1", i)]["K"] for i in range(2)]
@@ -364,29 +361,34 @@ class FastEval:
             gi, gi_small = ext.knn_indices(kmax, xyz1, xyz2, k2=kmin) if kmin < kmax else (ext.knn_indices(kmax, xyz1, xyz2), None)
         c_q = q[("q1", 0)]["l3"][0].shape[0]
         c1q = q[("q1", 0)]["l2"][0].shape[1]
-        src3 = src2.view(B, N, C)
-        # per scale i: neighbour index, feature rows the layer-1 GEMM runs over, the coordinates that go with them
+        rc = P["row_chain"]
+        # per scale i: neighbour index, the per-point layer-1 feature term (a column block), the coordinates that go with them
         plan = []
-        # few slots and a batch large enough that the GEMM, not the launch count, is what costs (measured: pays from B ~ 32)
-        gathered = [J * K * 2 <= N and B * N >= 32768 for K in Ks]
-        over_points = [i for i, gth in enumerate(gathered) if not gth]
-        a_all = None
-        if len(over_points) > 1:  # small batch: the scales' per-point GEMMs read the same rows -> one GEMM, column blocks per scale
-            a_all = _lin(src2, self._wcat(tuple(over_points))).view(B, N, -1)
-        for i, K in enumerate(Ks):
-            W = self._wcat(i)  # (2*c1q, C): layer-1 feature weights of q1 | q2 at this scale
-            if gathered[i]:  # gather the J*K feature rows, then the GEMM (slot-major rows, identity index)
-                flat = (gi_small if K == kmin and gi_small is not None else gi[:, :, :K].contiguous()).view(B, J * K)
-                a = _lin(ext.gather_rows(src3, flat).view(B * J * K, C), W).view(B, J * K, -1)
-                plan.append((self._ident(B, J, K, dev), a, ext.gather_rows(xyz2, flat)))
+        if self.row_chain and rc is not None and B * N >= 32768 and B <= ext.ROW_CHAIN_MAX_B and gi_small is not None:
+            # a batch large enough that the dense work, not the launch count, is what costs: the q branches read the per-point
+            # features only through their kNN lists (about 2/3 of a cloud's points for K = 64, 1/4 for K = 16), so fp1, conv1 and
+            # the layer-1 feature product of all four scales run over the listed rows only, in one launch (rows named by a
+            # K = 16 list get the columns of both scales, the others only the K = 64 scale's)
+            lst, counts = ext.row_lists(gi, gi_small, N)
+            a_all = torch.empty((B, N, 4 * c1q), **f32)
+            ext.row_chain(fp1_in, lst, counts, rc["wa"], rc["ba"], rc["wb"], rc["bb"], rc["wc"], rc["bc"], rc["wq"], out=a_all)
+            for i, K in enumerate(Ks):
+                j = rc["order"].index(i)
+                plan.append((gi_small if K == kmin else gi, a_all[:, :, 2 * c1q * j:2 * c1q * (j + 1)], xyz2))
+        else:
+            f = P["fp1_fused"]
+            if f is not None:  # both fp1 layers in one launch (pn2x_mlp2_rows): rows [interp | xyz | pad] -> 128 -> 128
+                x = ext.mlp2_rows(fp1_in.view(B * N, c_i + 4), f["w2"], f["b2"], f["w3"], f["b3"], w2e=f["w2e"])
             else:
+                x = fp1_in.view(B * N, c_i + 4)[:, :c_i + 3]
+                for W, b in P["fp1"]:
+                    x = _lin_relu(x, W, b)
+            src2 = _lin_relu(x, *P["conv1"])  # (B*N, C) per-point backbone features
+            # both scales' per-point GEMMs read the same rows -> one GEMM, a column block per scale
+            a_all = _lin(src2, self._wcat((0, 1))).view(B, N, -1)
+            for i, K in enumerate(Ks):
                 idx = gi if K == kmax else (gi_small if K == kmin and gi_small is not None else gi[:, :, :K].contiguous())
-                if a_all is not None:
-                    j = over_points.index(i)
-                    a = a_all[:, :, j * W.shape[0]:(j + 1) * W.shape[0]]
-                else:
-                    a = _lin(src2, W).view(B, N, -1)
-                plan.append((idx, a, xyz2))
+                plan.append((idx, a_all[:, :, 2 * c1q * i:2 * c1q * (i + 1)], xyz2))
         f11 = torch.empty((B, J, 2 * c_q), **f32)
         self._q_scales(ext, "q1", plan, q, xyz1, c1q, 0, None, f11, c_q)
         Wr, br, perm = P["r1"]
