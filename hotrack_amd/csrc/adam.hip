@@ -108,15 +108,8 @@ __global__ void adam_advance_kernel(float *__restrict__ steps, int n) {
 }  // namespace adam
 }  // namespace pn2
 
-// One Adam step over n tensors (fp32, contiguous).  p / g / m / v / step: host arrays of n device pointers (step: one fp32
-// counter per tensor, torch's `state['step']` of a capturable optimiser); numel: host array of n element counts.
-extern "C" int pn2x_adam_multi(int n, void *const *p, const void *const *g, void *const *m, void *const *v, void *const *step,
-                               const long *numel, double lr, double beta1, double beta2, double eps, double weight_decay, void *stream) {
-    return pn2x_adam_multi2(n, p, g, m, v, step, numel, lr, beta1, beta2, eps, weight_decay, 1, stream);
-}
-
 // All step counters of an optimiser in ONE contiguous buffer (views of it as the per-parameter `step` tensors): advanced by one
-// launch after the update kernels (pn2x_adam_multi2 with advance = 0) instead of one launch per 64 tensors.
+// launch after the update kernels (pn2x_adam_multi with advance = 0) instead of one launch per 64 tensors.
 extern "C" int pn2x_adam_advance(float *steps, int n, void *stream) {
     if (n < 0) return PN2_EINVAL;
     if (n == 0) return PN2_OK;
@@ -125,7 +118,10 @@ extern "C" int pn2x_adam_advance(float *steps, int n, void *stream) {
     return pn2::check_launch();
 }
 
-extern "C" int pn2x_adam_multi2(int n, void *const *p, const void *const *g, void *const *m, void *const *v, void *const *step,
+// One Adam step over n tensors (fp32, contiguous).  p / g / m / v / step: host arrays of n device pointers (step: one fp32
+// counter per tensor, torch's `state['step']` of a capturable optimiser); numel: host array of n element counts.  advance = 0:
+// the counters are not advanced here (pn2x_adam_advance does it for all of them in one launch).
+extern "C" int pn2x_adam_multi(int n, void *const *p, const void *const *g, void *const *m, void *const *v, void *const *step,
                                 const long *numel, double lr, double beta1, double beta2, double eps, double weight_decay, int advance,
                                 void *stream) {
     using namespace pn2;

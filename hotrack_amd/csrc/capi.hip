@@ -50,7 +50,7 @@ static inline bool fits_int(long v) { return v >= 0 && v <= 2147483647L; }
 
 extern "C" {
 
-int pn2_abi_version(void) { return 1; }
+int pn2_abi_version(void) { return 2; }
 
 int pn2_last_hip_error(void) { return g_last_hip_error; }
 
@@ -140,15 +140,7 @@ int pn2_ball_query(int b, int n, int m, float radius, int nsample, const float *
     return ball_query_dispatch(b, n, m, radius, nsample, new_xyz, xyz, idx, (hipStream_t)stream, nullptr, nullptr, nullptr, 0);
 }
 
-int pn2x_ball_query_picks2(int b, int n, int m, float radius, int nsample, const float *xyz, const int *picks, float *new_xyz,
-                           int *idx, float *new_xyz_copy, int copy_ld, void *stream);
-
 int pn2x_ball_query_picks(int b, int n, int m, float radius, int nsample, const float *xyz, const int *picks, float *new_xyz,
-                          int *idx, void *stream) {
-    return pn2x_ball_query_picks2(b, n, m, radius, nsample, xyz, picks, new_xyz, idx, nullptr, 0, stream);
-}
-
-int pn2x_ball_query_picks2(int b, int n, int m, float radius, int nsample, const float *xyz, const int *picks, float *new_xyz,
                            int *idx, float *new_xyz_copy, int copy_ld, void *stream) {
     PN2_REQ(!new_xyz_copy || copy_ld >= 3, PN2_EINVAL);
     PN2_REQ(b >= 0 && n >= 1 && m >= 0 && nsample >= 1, PN2_EINVAL);

@@ -446,7 +446,7 @@ hand_frame_kernel(int xb, int num, int n, int j, const float *__restrict__ tmpl_
             c[0] = v0; c[1] = v1; c[2] = v2;
         }
     }
-    if (nonfinite) {  // per-cloud flag for pn2x_pose_head2: a frame with a non-finite input yields NaN keypoints (as the
+    if (nonfinite) {  // per-cloud flag for pn2x_pose_head: a frame with a non-finite input yields NaN keypoints (as the
         bad = __syncthreads_or(bad);  // reference, where the NaN spreads through sampling / grouping / the global max-pool)
         if (threadIdx.x == 0) nonfinite[b] = bad;
     }
@@ -471,13 +471,8 @@ extern "C" int pn2x_kabsch_backward(int b, int xb, int num, const float *x, cons
     return pn2::check_launch();
 }
 
-extern "C" int pn2x_hand_losses(int b, int pb, const float *pred_hf, const float *init_hf, const float *gt_kp, const float *pred_kp,
-                                const float *R, const float *t, float scale, const float *palm, float *out, float *saved, void *stream) {
-    return pn2x_hand_losses2(b, pb, pred_hf, init_hf, gt_kp, pred_kp, R, t, scale, palm, out, saved, nullptr, stream);
-}
-
 // weights (9) != NULL: out has TEN entries, out[9] = sum_i weights[i] out[i]
-extern "C" int pn2x_hand_losses2(int b, int pb, const float *pred_hf, const float *init_hf, const float *gt_kp, const float *pred_kp,
+extern "C" int pn2x_hand_losses(int b, int pb, const float *pred_hf, const float *init_hf, const float *gt_kp, const float *pred_kp,
                                  const float *R, const float *t, float scale, const float *palm, float *out, float *saved,
                                  const float *weights, void *stream) {
     if (b < 1 || !(pb == 1 || pb == b) || !(scale > 0.f)) return PN2_EINVAL;
@@ -487,13 +482,8 @@ extern "C" int pn2x_hand_losses2(int b, int pb, const float *pred_hf, const floa
     return pn2::check_launch();
 }
 
-extern "C" int pn2x_hand_losses_backward(int b, int pb, const float *pred_hf, float scale, const float *palm, const float *saved,
-                                         const float *grad3, float *d_pred_hf, void *stream) {
-    return pn2x_hand_losses_backward2(b, pb, pred_hf, scale, palm, saved, grad3, nullptr, nullptr, d_pred_hf, stream);
-}
-
 // dL/d out[i] = grad3[i] (grad3 may be NULL) + grad_total[0] * weights[i] (grad_total may be NULL; weights as given to the forward)
-extern "C" int pn2x_hand_losses_backward2(int b, int pb, const float *pred_hf, float scale, const float *palm, const float *saved,
+extern "C" int pn2x_hand_losses_backward(int b, int pb, const float *pred_hf, float scale, const float *palm, const float *saved,
                                           const float *grad3, const float *grad_total, const float *weights, float *d_pred_hf,
                                           void *stream) {
     if (b < 1 || !(pb == 1 || pb == b) || !(scale > 0.f)) return PN2_EINVAL;
@@ -503,26 +493,7 @@ extern "C" int pn2x_hand_losses_backward2(int b, int pb, const float *pred_hf, f
     return pn2::check_launch();
 }
 
-extern "C" int pn2x_hand_frame3(int b, int xb, int num, int n, int j, const float *palm_template, const float *kp,
-                                const int *palm_idx, const float *points, float scale, float *R, float *t, float *xyz2,
-                                float *xyz1, float *xyz2_copy, int copy_ld, int *nonfinite, void *stream);
-extern "C" int pn2x_hand_frame2(int b, int xb, int num, int n, int j, const float *palm_template, const float *kp,
-                                const int *palm_idx, const float *points, float scale, float *R, float *t, float *xyz2,
-                                float *xyz1, float *xyz2_copy, int copy_ld, void *stream);
-
 extern "C" int pn2x_hand_frame(int b, int xb, int num, int n, int j, const float *palm_template, const float *kp,
-                               const int *palm_idx, const float *points, float scale, float *R, float *t, float *xyz2,
-                               float *xyz1, void *stream) {
-    return pn2x_hand_frame2(b, xb, num, n, j, palm_template, kp, palm_idx, points, scale, R, t, xyz2, xyz1, nullptr, 0, stream);
-}
-
-extern "C" int pn2x_hand_frame2(int b, int xb, int num, int n, int j, const float *palm_template, const float *kp,
-                                const int *palm_idx, const float *points, float scale, float *R, float *t, float *xyz2,
-                                float *xyz1, float *xyz2_copy, int copy_ld, void *stream) {
-    return pn2x_hand_frame3(b, xb, num, n, j, palm_template, kp, palm_idx, points, scale, R, t, xyz2, xyz1, xyz2_copy, copy_ld, nullptr, stream);
-}
-
-extern "C" int pn2x_hand_frame3(int b, int xb, int num, int n, int j, const float *palm_template, const float *kp,
                                 const int *palm_idx, const float *points, float scale, float *R, float *t, float *xyz2,
                                 float *xyz1, float *xyz2_copy, int copy_ld, int *nonfinite, void *stream) {
     if (xyz2_copy && copy_ld < 3) return PN2_EINVAL;

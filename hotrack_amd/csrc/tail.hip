@@ -90,7 +90,7 @@ pose_head_kernel(int tokens, int j, int c, const float *__restrict__ h, const fl
     if (lane == 0) {
         const int b = tok / j;
         float px = a0 + bias[0] + xyz1[3 * tok], py = a1 + bias[1] + xyz1[3 * tok + 1], pz = a2 + bias[2] + xyz1[3 * tok + 2];
-        if (nonfinite && nonfinite[b]) px = py = pz = __builtin_nanf("");  // flagged by pn2x_hand_frame3: non-finite input frame
+        if (nonfinite && nonfinite[b]) px = py = pz = __builtin_nanf("");  // flagged by pn2x_hand_frame: non-finite input frame
         kp_hand[3 * tok] = px; kp_hand[3 * tok + 1] = py; kp_hand[3 * tok + 2] = pz;
         const float *Rb = R + 9 * b, *tb = t + 3 * b;
         // row vector times R^T: out_i = sum_k p_k R[i][k]
@@ -122,11 +122,6 @@ extern "C" int pn2x_add_layernorm(long rows, int c, const float *x, const float 
 }
 
 extern "C" int pn2x_pose_head(int b, int j, int c, const float *h, const float *w, const float *bias, const float *xyz1,
-                              const float *R, const float *t, float scale, float *kp_hand, float *kp_cam, void *stream) {
-    return pn2x_pose_head2(b, j, c, h, w, bias, xyz1, R, t, scale, kp_hand, kp_cam, nullptr, stream);
-}
-
-extern "C" int pn2x_pose_head2(int b, int j, int c, const float *h, const float *w, const float *bias, const float *xyz1,
                                const float *R, const float *t, float scale, float *kp_hand, float *kp_cam, const int *nonfinite,
                                void *stream) {
     if (b < 0 || j < 1 || c < 1) return PN2_EINVAL;

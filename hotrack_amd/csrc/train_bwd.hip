@@ -932,17 +932,6 @@ extern "C" int pn2x_tg_bwd_partials(long rows, int c_out, int c_in) {
     return grid_of(rows, s) * s.ks_w;
 }
 
-extern "C" int pn2x_tg_bwd(long rows, int n, int k, int gmode, const float *g, int ldg, const int *arg, int kmax, const float *yi,
-                           int ldyi, const float *mean_i, const float *invstd_i, const float *gamma_i, const float *beta_i,
-                           const double *sums_bwd_i, const float *w, int ldw,
-                           const float *yp, int ldyp, const float *mean_p, const float *invstd_p, const float *gamma_p,
-                           const float *beta_p, float *gp, int ldgp, double *sums_bwd_p, float *partial, long partial_floats,
-                           float *dw, void *stream) {
-    return pn2x_tg_bwd_slice(rows, n, k, gmode, g, ldg, arg, ldg, kmax, yi, ldyi, mean_i, invstd_i, gamma_i, beta_i, sums_bwd_i, n, w, ldw, yp,
-                             ldyp, mean_p, invstd_p, gamma_p, beta_p, gp, ldgp, sums_bwd_p, partial, partial_floats, dw, nullptr, 0, 0,
-                             stream);
-}
-
 // One column slice [c0, c0 + n) of a layer with sums_ld >= n channels: the caller passes g / yi / the per-channel vectors / sums_bwd_i /
 // w / dw already offset to the slice; arg (gmode 2) has its own row stride ldarg (g may be a column block of a wider tensor).  g_add (row stride ldga, may alias gp): the data-gradient partial of earlier slices; raw_out: leave
 // mask and sums to a later slice.

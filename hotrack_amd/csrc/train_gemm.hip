@@ -814,18 +814,9 @@ extern "C" long pn2x_tg_wgrad_partial_floats(long rows, int n, int k) {
     return (long)splits * kg * n * k;
 }
 
-extern "C" int pn2x_tg_wgrad(long rows, int n, int k, int gmode, const float *g, int ldg, const int *arg, int kmax, const float *yi,
-                             int ldyi, const float *mean_i, const float *invstd_i, const float *gamma_i, const float *beta_i,
-                             const double *sums_bwd_i, const float *yp, int ldyp, const float *mean_p, const float *invstd_p,
-                             const float *gamma_p, const float *beta_p, float *partial, long partial_floats, float *dw,
-                             float *dgamma, float *dbeta, float *dbias, void *stream) {
-    return pn2x_tg_wgrad2(rows, n, k, gmode, g, ldg, arg, kmax, yi, ldyi, mean_i, invstd_i, gamma_i, beta_i, sums_bwd_i, yp, ldyp, mean_p,
-                          invstd_p, gamma_p, beta_p, partial, partial_floats, dw, dgamma, dbeta, dbias, nullptr, stream);
-}
-
 // n_partials != NULL: only the partial tiles are written (and dw zeroed); *n_partials receives their count for a later
 // pn2x_tg_reduce_multi over several layers.
-extern "C" int pn2x_tg_wgrad2(long rows, int n, int k, int gmode, const float *g, int ldg, const int *arg, int kmax, const float *yi,
+extern "C" int pn2x_tg_wgrad(long rows, int n, int k, int gmode, const float *g, int ldg, const int *arg, int kmax, const float *yi,
                               int ldyi, const float *mean_i, const float *invstd_i, const float *gamma_i, const float *beta_i,
                               const double *sums_bwd_i, const float *yp, int ldyp, const float *mean_p, const float *invstd_p,
                               const float *gamma_p, const float *beta_p, float *partial, long partial_floats, float *dw,
@@ -864,15 +855,9 @@ extern "C" int pn2x_tg_wgrad2(long rows, int n, int k, int gmode, const float *g
     return check_launch();
 }
 
-extern "C" int pn2x_tg_reduce_multi(int count, const float *const *partial, const int *n_partials, const int *numel, float *const *dw,
-                                    const double *const *sums_bwd, const int *channels, float *const *dgamma, float *const *dbeta,
-                                    float *const *dbias, void *stream) {
-    return pn2x_tg_reduce_multi2(count, partial, n_partials, numel, dw, sums_bwd, channels, nullptr, dgamma, dbeta, dbias, stream);
-}
-
 // sums_ld (may be NULL: = channels): entry j is a column slice of a layer with sums_ld[j] channels (sums_bwd[j], dgamma[j], dbeta[j],
 // dbias[j], dw[j] already offset to the slice)
-extern "C" int pn2x_tg_reduce_multi2(int count, const float *const *partial, const int *n_partials, const int *numel, float *const *dw,
+extern "C" int pn2x_tg_reduce_multi(int count, const float *const *partial, const int *n_partials, const int *numel, float *const *dw,
                                      const double *const *sums_bwd, const int *channels, const int *sums_ld, float *const *dgamma,
                                      float *const *dbeta, float *const *dbias, void *stream) {
     if (count < 0) return PN2_EINVAL;

@@ -1093,12 +1093,6 @@ extern "C" int pn2x_bn_relu_bwd(long rows, int c, const float *dh, int ldd, cons
 // (train_gemm.hip): the top layer of a stack needs only the reduction (its dY is computed on load by the fused GEMMs),
 // the first layer only the apply step (its pre-masked gradient and sums come from the dgrad epilogue of layer 2).
 extern "C" int pn2x_bn_bwd_reduce(long rows, int c, const float *dh, int ldd, const int *arg, int k, const float *y, int ldy,
-                                  const float *mean, const float *invstd, const float *gamma, const float *beta, int relu, double *sums,
-                                  void *stream) {
-    return pn2x_bn_bwd_reduce_g(rows, c, dh, ldd, arg, k, y, ldy, mean, invstd, gamma, beta, relu, sums, nullptr, 0, stream);
-}
-
-extern "C" int pn2x_bn_bwd_reduce_g(long rows, int c, const float *dh, int ldd, const int *arg, int k, const float *y, int ldy,
                                     const float *mean, const float *invstd, const float *gamma, const float *beta, int relu, double *sums,
                                     float *g_out, int ldg, void *stream) {
     using namespace pn2;
@@ -1427,22 +1421,9 @@ extern "C" int pn2x_bn_relu_max_ld(long groups, int k, int c, const float *y, in
     return check_launch();
 }
 
-// pn2x_bn_relu_max for two problems (the two neighbourhood sizes of a module) in ONE launch where both take the split kernel (few
+// pn2x_bn_relu_max_ld for two problems (the two neighbourhood sizes of a module) in ONE launch where both take the split kernel (few
 // groups: rows of a group over several lanes); two calls otherwise.  Same results.
 extern "C" int pn2x_bn_relu_max_pair(long groups_a, int k_a, int c_a, const float *y_a, int ldy_a, const double *sums_a, const float *gamma_a,
-                                     const float *beta_a, const float *conv_bias_a, float eps_a, float momentum_a, float *running_mean_a,
-                                     float *running_var_a, long long *nbt_a, float *save_mean_a, float *save_invstd_a, float *out_a, int *arg_a,
-                                     long groups_b, int k_b, int c_b, const float *y_b, int ldy_b, const double *sums_b, const float *gamma_b,
-                                     const float *beta_b, const float *conv_bias_b, float eps_b, float momentum_b, float *running_mean_b,
-                                     float *running_var_b, long long *nbt_b, float *save_mean_b, float *save_invstd_b, float *out_b, int *arg_b,
-                                     void *stream) {
-    return pn2x_bn_relu_max_pair_ld(groups_a, k_a, c_a, y_a, ldy_a, sums_a, gamma_a, beta_a, conv_bias_a, eps_a, momentum_a, running_mean_a,
-                                    running_var_a, nbt_a, save_mean_a, save_invstd_a, out_a, c_a, arg_a, groups_b, k_b, c_b, y_b, ldy_b, sums_b,
-                                    gamma_b, beta_b, conv_bias_b, eps_b, momentum_b, running_mean_b, running_var_b, nbt_b, save_mean_b,
-                                    save_invstd_b, out_b, c_b, arg_b, stream);
-}
-
-extern "C" int pn2x_bn_relu_max_pair_ld(long groups_a, int k_a, int c_a, const float *y_a, int ldy_a, const double *sums_a, const float *gamma_a,
                                         const float *beta_a, const float *conv_bias_a, float eps_a, float momentum_a, float *running_mean_a,
                                         float *running_var_a, long long *nbt_a, float *save_mean_a, float *save_invstd_a, float *out_a, int ldo_a,
                                         int *arg_a, long groups_b, int k_b, int c_b, const float *y_b, int ldy_b, const double *sums_b,
@@ -1534,12 +1515,6 @@ extern "C" int pn2x_three_interpolate_pm_grad(int b, int c, int m, int n, const 
 }
 
 extern "C" int pn2x_sa_layer1(int b, int n, int s, int k, int c1, const float *a1f, int a1f_ld, const float *xyz, const float *cxyz,
-                              const float *wx, const float *cadd, int cadd_ld, const int *idx, float *out, float *rel_out,
-                              void *stream) {
-    return pn2x_sa_layer1_ld(b, n, s, k, c1, a1f, a1f_ld, xyz, cxyz, wx, 3, cadd, cadd_ld, idx, out, rel_out, stream);
-}
-
-extern "C" int pn2x_sa_layer1_ld(int b, int n, int s, int k, int c1, const float *a1f, int a1f_ld, const float *xyz, const float *cxyz,
                                  const float *wx, int wx_ld, const float *cadd, int cadd_ld, const int *idx, float *out, float *rel_out,
                                  void *stream) {
     using namespace pn2;
@@ -1556,7 +1531,7 @@ extern "C" int pn2x_sa_layer1_ld(int b, int n, int s, int k, int c1, const float
     return check_launch();
 }
 
-// pn2x_sa_layer1_ld that also accumulates the BatchNorm statistics of its output into `sums` (pn2x_bn_sums_doubles(c1) doubles, zeroed
+// pn2x_sa_layer1 that also accumulates the BatchNorm statistics of its output into `sums` (pn2x_bn_sums_doubles(c1) doubles, zeroed
 // by the caller; the layout pn2x_bn_stats writes): in the same launch when the channel quads divide the workgroup, by a
 // pn2x_bn_stats launch behind it otherwise.
 namespace pn2 {
@@ -1584,7 +1559,7 @@ static int sa_layer1_stats_args(int b, int n, int s, int k, int c1, const float 
 }
 }  // namespace pn2
 
-// pn2x_sa_layer1_ld that also accumulates the BatchNorm statistics of its output into `sums` (pn2x_bn_sums_doubles(c1) doubles, zeroed
+// pn2x_sa_layer1 that also accumulates the BatchNorm statistics of its output into `sums` (pn2x_bn_sums_doubles(c1) doubles, zeroed
 // by the caller; the layout pn2x_bn_stats writes): in the same launch when the channel quads divide the workgroup, by a
 // pn2x_bn_stats launch behind it otherwise.
 extern "C" int pn2x_sa_layer1_stats(int b, int n, int s, int k, int c1, const float *a1f, int a1f_ld, const float *xyz, const float *cxyz,
@@ -1595,7 +1570,7 @@ extern "C" int pn2x_sa_layer1_stats(int b, int n, int s, int k, int c1, const fl
     unsigned nbx = 0;
     const int rc0 = sa_layer1_stats_args(b, n, s, k, c1, a1f, a1f_ld, xyz, cxyz, wx, wx_ld, cadd, cadd_ld, idx, out, rel_out, sums, a, nbx);
     if (rc0 == 1) {
-        const int rc = pn2x_sa_layer1_ld(b, n, s, k, c1, a1f, a1f_ld, xyz, cxyz, wx, wx_ld, cadd, cadd_ld, idx, out, rel_out, stream);
+        const int rc = pn2x_sa_layer1(b, n, s, k, c1, a1f, a1f_ld, xyz, cxyz, wx, wx_ld, cadd, cadd_ld, idx, out, rel_out, stream);
         if (rc != PN2_OK || b == 0 || s == 0) return rc;
         return pn2x_bn_stats((long)b * s * k, c1, out, c1, sums, stream);
     }

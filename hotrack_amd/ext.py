@@ -262,7 +262,6 @@ _lib.pn2x_three_nn_interpolate_pm.argtypes = [_ci, _ci, _ci, _ci, _vp, _vp, _vp,
 _lib.pn2x_three_nn_interpolate_pm.restype = _ci
 _lib.pn2x_three_nn_interpolate_pm_supported.argtypes = [_ci] * 6
 _lib.pn2x_three_nn_interpolate_pm_supported.restype = _ci
-NN_INTERP_FUSED = True  # (module attribute: tests / A-B runs set it False for the two-launch chain)
 
 
 def three_nn_interpolate_pm(unknown: torch.Tensor, known: torch.Tensor, points: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
@@ -273,7 +272,7 @@ def three_nn_interpolate_pm(unknown: torch.Tensor, known: torch.Tensor, points: 
     pp, ldp = _rows(points, "points", C)
     po, ldo = _rows(out, "out", C)
     f32 = torch.float32
-    if (NN_INTERP_FUSED and _lib.pn2x_three_nn_interpolate_pm_supported(B, n, m, C, ldp, ldo) and pp % 16 == 0 and po % 16 == 0):
+    if _lib.pn2x_three_nn_interpolate_pm_supported(B, n, m, C, ldp, ldo) and pp % 16 == 0 and po % 16 == 0:
         with torch.cuda.device(points.device):
             _native._check(_native._call(_lib.pn2x_three_nn_interpolate_pm, "three_nn_interp_kernel", None, B, n, m, C,
                                          _native._ptr(unknown, "unknown", f32, B * n * 3), _native._ptr(known, "known", f32, B * m * 3),
@@ -333,12 +332,8 @@ def max_rows(x: torch.Tensor) -> torch.Tensor:
     return out
 
 
-_lib.pn2x_hand_frame.argtypes = [_ci] * 5 + [_vp] * 4 + [ctypes.c_float] + [_vp] * 5
+_lib.pn2x_hand_frame.argtypes = [_ci] * 5 + [_vp] * 4 + [ctypes.c_float] + [_vp] * 5 + [_ci, _vp, _vp]
 _lib.pn2x_hand_frame.restype = _ci
-_lib.pn2x_hand_frame2.argtypes = [_ci] * 5 + [_vp] * 4 + [ctypes.c_float] + [_vp] * 5 + [_ci, _vp]
-_lib.pn2x_hand_frame2.restype = _ci
-_lib.pn2x_hand_frame3.argtypes = [_ci] * 5 + [_vp] * 4 + [ctypes.c_float] + [_vp] * 5 + [_ci, _vp, _vp]
-_lib.pn2x_hand_frame3.restype = _ci
 
 
 def _xyz_cols(t: torch.Tensor, name: str, B: int, R: int):
@@ -367,7 +362,7 @@ def hand_frame(palm_template: torch.Tensor, kp: torch.Tensor, palm_idx: torch.Te
     xyz1 = torch.empty((B, J, 3), dtype=f32, device=points.device)
     pc, ldc = (None, 0) if xyz2_copy is None else _xyz_cols(xyz2_copy, "xyz2_copy", B, N)
     with torch.cuda.device(points.device):
-        _native._check(_lib.pn2x_hand_frame3(B, xb, num, N, J, _native._ptr(palm_template, "palm_template", f32, xb * num * 3),
+        _native._check(_lib.pn2x_hand_frame(B, xb, num, N, J, _native._ptr(palm_template, "palm_template", f32, xb * num * 3),
                                              _native._ptr(kp, "kp", f32, B * J * 3), _native._ptr(palm_idx, "palm_idx", torch.int32, num),
                                              _native._ptr(points, "points", f32, B * N * 3), float(scale), R.data_ptr(), t.data_ptr(),
                                              xyz2.data_ptr(), xyz1.data_ptr(), pc, ldc,
@@ -379,8 +374,8 @@ def hand_frame(palm_template: torch.Tensor, kp: torch.Tensor, palm_idx: torch.Te
 _cf = ctypes.c_float
 _lib.pn2x_add_layernorm.argtypes = [_cl, _ci, _vp, _vp, _vp, _vp, _vp, _cf, _vp, _vp, _cf, _vp, _vp]
 _lib.pn2x_add_layernorm.restype = _ci
-_lib.pn2x_pose_head2.argtypes = [_ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _cf, _vp, _vp, _vp, _vp]
-_lib.pn2x_pose_head2.restype = _ci
+_lib.pn2x_pose_head.argtypes = [_ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _cf, _vp, _vp, _vp, _vp]
+_lib.pn2x_pose_head.restype = _ci
 
 
 def add_layernorm(x: torch.Tensor, ln1, y: torch.Tensor = None, bias: torch.Tensor = None, ln2=None) -> torch.Tensor:
@@ -418,7 +413,7 @@ def pose_head(h: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, xyz1: torch.
     kp_hand = torch.empty((B, J, 3), dtype=f32, device=h.device)
     kp_cam = torch.empty((B, J, 3), dtype=f32, device=h.device)
     with torch.cuda.device(h.device):
-        _native._check(_lib.pn2x_pose_head2(B, J, C, *ptrs, float(scale), kp_hand.data_ptr(), kp_cam.data_ptr(),
+        _native._check(_lib.pn2x_pose_head(B, J, C, *ptrs, float(scale), kp_hand.data_ptr(), kp_cam.data_ptr(),
                                             None if nonfinite is None else _native._ptr(nonfinite, "nonfinite", torch.int32, B),
                                             _native._stream(h)), "pose_head")
     return kp_hand, kp_cam
@@ -521,8 +516,8 @@ _lib.pn2x_furthest_point_sampling_prefix.argtypes = [_ci, _ci, _ci, _vp, _vp, _c
 _lib.pn2x_furthest_point_sampling_prefix.restype = _ci
 
 
-_lib.pn2x_ball_query_picks2.argtypes = [_ci, _ci, _ci, ctypes.c_float, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _vp]
-_lib.pn2x_ball_query_picks2.restype = _ci
+_lib.pn2x_ball_query_picks.argtypes = [_ci, _ci, _ci, ctypes.c_float, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _vp]
+_lib.pn2x_ball_query_picks.restype = _ci
 
 
 def ball_query_picks(radius: float, nsample: int, xyz: torch.Tensor, picks: torch.Tensor, xyz_copy: torch.Tensor = None):
@@ -537,7 +532,7 @@ def ball_query_picks(radius: float, nsample: int, xyz: torch.Tensor, picks: torc
     new_xyz = torch.empty((B, S, 3), dtype=torch.float32, device=xyz.device)
     pc, ldc = (None, 0) if xyz_copy is None else _xyz_cols(xyz_copy, "xyz_copy", B, S)
     with torch.cuda.device(xyz.device):
-        _native._check(_lib.pn2x_ball_query_picks2(B, N, S, float(radius), nsample, px, pp, new_xyz.data_ptr(), idx.data_ptr(),
+        _native._check(_lib.pn2x_ball_query_picks(B, N, S, float(radius), nsample, px, pp, new_xyz.data_ptr(), idx.data_ptr(),
                                                    pc, ldc, _native._stream(xyz)), "ball_query_picks")
     return idx, new_xyz
 
@@ -616,14 +611,10 @@ def fps_two_level(xyz: torch.Tensor, m1: int, m2: int, query=None, knn=None):
     return res + (lists if lists is not None else knn_alone(),)
 
 
-_lib.pn2x_hand_losses.argtypes = [_ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, _vp]
+_lib.pn2x_hand_losses.argtypes = [_ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, _vp, _vp]
 _lib.pn2x_hand_losses.restype = _ci
-_lib.pn2x_hand_losses_backward.argtypes = [_ci, _ci, _vp, ctypes.c_float, _vp, _vp, _vp, _vp, _vp]
+_lib.pn2x_hand_losses_backward.argtypes = [_ci, _ci, _vp, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
 _lib.pn2x_hand_losses_backward.restype = _ci
-_lib.pn2x_hand_losses2.argtypes = _lib.pn2x_hand_losses.argtypes[:-1] + [_vp, _vp]
-_lib.pn2x_hand_losses2.restype = _ci
-_lib.pn2x_hand_losses_backward2.argtypes = [_ci, _ci, _vp, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
-_lib.pn2x_hand_losses_backward2.restype = _ci
 HAND_LOSS_NAMES = ("hand_pred_kp_loss", "hand_pred_r_loss", "hand_pred_t_loss", "hand_pred_kp_diff", "hand_init_kp_diff",
                    "hand_init_r_diff", "hand_init_t_diff", "hand_pred_r_diff", "hand_pred_t_diff")
 
@@ -649,7 +640,7 @@ class HandLosses(torch.autograd.Function):
         saved = torch.empty((B, 87), dtype=f32, device=pred_hf.device)
         wptr = None if weights is None else _native._ptr(weights, "weights", f32, 9)
         with torch.cuda.device(pred_hf.device):
-            _native._check(_lib.pn2x_hand_losses2(B, palm.shape[0], _native._ptr(pred_hf, "pred_hf", f32, B * 63), _native._ptr(args[0], "init_hf", f32, B * 63),
+            _native._check(_lib.pn2x_hand_losses(B, palm.shape[0], _native._ptr(pred_hf, "pred_hf", f32, B * 63), _native._ptr(args[0], "init_hf", f32, B * 63),
                                                   _native._ptr(args[1], "gt_kp", f32, B * 63), _native._ptr(args[2], "pred_kp", f32, B * 63),
                                                   _native._ptr(args[3], "R", f32, B * 9), _native._ptr(args[4], "t", f32, B * 3), float(scale),
                                                   _native._ptr(palm, "palm", f32, palm.shape[0] * 18), out.data_ptr(), saved.data_ptr(), wptr,
@@ -672,13 +663,14 @@ class HandLosses(torch.autograd.Function):
         gt = None if grad_total is None else grad_total.contiguous().float()
         d = torch.empty_like(pred_hf)
         with torch.cuda.device(pred_hf.device):
-            _native._check(_lib.pn2x_hand_losses_backward2(B, palm.shape[0], pred_hf.data_ptr(), ctx.scale, palm.data_ptr(), saved.data_ptr(),
+            _native._check(_lib.pn2x_hand_losses_backward(B, palm.shape[0], pred_hf.data_ptr(), ctx.scale, palm.data_ptr(), saved.data_ptr(),
                                                            None if g3 is None else g3.data_ptr(), None if gt is None else gt.data_ptr(),
                                                            None if weights is None else weights.data_ptr(), d.data_ptr(),
                                                            _native._stream(pred_hf)), "hand_losses_backward")
         return d, None, None, None, None, None, None, None, None
 
 
+_lib.pn2x_copy_multi_max.argtypes = []
 _lib.pn2x_copy_multi_max.restype = _ci
 _lib.pn2x_copy_multi.argtypes = [_ci, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_long), _vp]
 _lib.pn2x_copy_multi.restype = _ci

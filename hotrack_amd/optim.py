@@ -18,10 +18,8 @@ from . import pointnet2_hip as _native
 _lib = _native._lib
 _vp = ctypes.c_void_p
 _lib.pn2x_adam_multi.argtypes = [ctypes.c_int, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
-                                 ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_long)] + [ctypes.c_double] * 5 + [_vp]
+                                 ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_long)] + [ctypes.c_double] * 5 + [ctypes.c_int, _vp]
 _lib.pn2x_adam_multi.restype = ctypes.c_int
-_lib.pn2x_adam_multi2.argtypes = _lib.pn2x_adam_multi.argtypes[:-1] + [ctypes.c_int, _vp]
-_lib.pn2x_adam_multi2.restype = ctypes.c_int
 _lib.pn2x_adam_advance.argtypes = [_vp, ctypes.c_int, _vp]
 _lib.pn2x_adam_advance.restype = ctypes.c_int
 
@@ -105,7 +103,7 @@ class FusedAdam(torch.optim.Optimizer):
             lr = group["lr"]
             lr = float(lr.item()) if torch.is_tensor(lr) else float(lr)
             with torch.cuda.device(ps[0].device):
-                _native._check(_lib.pn2x_adam_multi2(n, P, G, M, V, S, N, lr, float(b1), float(b2), float(group["eps"]),
+                _native._check(_lib.pn2x_adam_multi(n, P, G, M, V, S, N, lr, float(b1), float(b2), float(group["eps"]),
                                                      float(group["weight_decay"]), 0, _native._stream(ps[0])), "adam_multi")
             stepped += [self.state[p]["step"] for p in ps]
         self._advance(stepped)

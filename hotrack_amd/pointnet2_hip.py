@@ -55,7 +55,9 @@ for _name, _args in _SIGS.items():
     _fn.restype = _ci
 _lib.pn2_strerror.restype = ctypes.c_char_p
 _lib.pn2_strerror.argtypes = [_ci]
+_lib.pn2_abi_version.argtypes = []
 _lib.pn2_abi_version.restype = _ci
+_lib.pn2_last_hip_error.argtypes = []
 _lib.pn2_last_hip_error.restype = _ci
 
 _lib.pn2x_ball_query_grid_scratch_words.argtypes = [_ci, _ci]

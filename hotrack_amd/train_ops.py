@@ -26,9 +26,7 @@ _lib.pn2x_bn_relu_apply.argtypes = [_cl, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _cf,
 _lib.pn2x_bn_relu_bwd.argtypes = [_cl, _ci, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _vp, _ci, _vp, _vp, _vp, _vp]
 _lib.pn2x_scatter_add_rows.argtypes = [_ci, _ci, _ci, _ci, _vp, _ci, _vp, _vp, _ci, _vp]
 _lib.pn2x_three_interpolate_pm_grad.argtypes = [_ci, _ci, _ci, _ci, _vp, _ci, _vp, _vp, _vp, _ci, _vp]
-_lib.pn2x_sa_layer1.argtypes = [_ci] * 5 + [_vp, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _vp]
-_lib.pn2x_sa_layer1_ld.argtypes = [_ci] * 5 + [_vp, _ci, _vp, _vp, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp]
-_lib.pn2x_sa_layer1_ld.restype = _ci
+_lib.pn2x_sa_layer1.argtypes = [_ci] * 5 + [_vp, _ci, _vp, _vp, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp]
 _lib.pn2x_sa_layer1_stats.argtypes = [_ci] * 5 + [_vp, _ci, _vp, _vp, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _vp]
 _lib.pn2x_sa_layer1_stats.restype = _ci
 _lib.pn2x_bn_sums_doubles.argtypes = [_ci]
@@ -311,7 +309,7 @@ class _SaLayer1(torch.autograd.Function):
                     if sm is not None:
                         _native._check(_lib.pn2x_sa_layer1_stats(*args, sm.data_ptr(), st), "sa_layer1_stats")
                     else:
-                        _native._check(_lib.pn2x_sa_layer1_ld(*args, st), "sa_layer1")
+                        _native._check(_lib.pn2x_sa_layer1(*args, st), "sa_layer1")
         ctx.aux = aux
         if aux is not None:
             aux["rel"], aux["dwx"] = list(rels), {}

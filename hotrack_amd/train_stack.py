@@ -42,20 +42,13 @@ _lib.pn2x_tg_dgrad.argtypes = [_cl, _ci, _ci] + _DY + [_vp, _ci, _vp, _ci, _vp, 
 _lib.pn2x_tg_dgrad.restype = _ci
 _lib.pn2x_tg_wgrad_partial_floats.argtypes = [_cl, _ci, _ci]
 _lib.pn2x_tg_wgrad_partial_floats.restype = _cl
-_lib.pn2x_tg_wgrad.argtypes = [_cl, _ci, _ci] + _DY + [_vp, _ci, _vp, _vp, _vp, _vp, _vp, _cl, _vp, _vp, _vp, _vp, _vp]
+_lib.pn2x_tg_wgrad.argtypes = [_cl, _ci, _ci] + _DY + [_vp, _ci, _vp, _vp, _vp, _vp, _vp, _cl, _vp, _vp, _vp, _vp,
+                                                         ctypes.POINTER(_ci), _vp]
 _lib.pn2x_tg_wgrad.restype = _ci
-_lib.pn2x_tg_wgrad2.argtypes = _lib.pn2x_tg_wgrad.argtypes[:-1] + [ctypes.POINTER(_ci), _vp]
-_lib.pn2x_tg_wgrad2.restype = _ci
-_lib.pn2x_tg_reduce_multi.argtypes = [_ci, ctypes.POINTER(_vp), ctypes.POINTER(_ci), ctypes.POINTER(_ci), ctypes.POINTER(_vp),
-                                      ctypes.POINTER(_vp), ctypes.POINTER(_ci), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
-                                      ctypes.POINTER(_vp), _vp]
-_lib.pn2x_tg_reduce_multi.restype = _ci
 _lib.pn2x_tg_bwd_supported.argtypes = [_ci, _ci]
 _lib.pn2x_tg_bwd_supported.restype = _ci
 _lib.pn2x_tg_bwd_partials.argtypes = [_cl, _ci, _ci]
 _lib.pn2x_tg_bwd_partials.restype = _ci
-_lib.pn2x_tg_bwd.argtypes = [_cl, _ci, _ci, _ci, _vp, _ci, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _vp, _vp, _vp,
-                             _vp, _vp, _ci, _vp, _vp, _cl, _vp, _vp]
 _lib.pn2x_tg_bwd_slice.argtypes = [_cl, _ci, _ci, _ci, _vp, _ci, _vp, _ci, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _vp, _ci, _vp, _vp,
                                    _vp, _vp, _vp, _ci, _vp, _vp, _cl, _vp, _vp, _ci, _ci, _vp]
 _lib.pn2x_tg_bwd_slice.restype = _ci
@@ -68,10 +61,10 @@ _lib.pn2x_tg_fwd2_pair.restype = _ci
 _lib.pn2x_tg_bwd_slice_pair.argtypes = _lib.pn2x_tg_bwd_slice.argtypes[:-1] * 2 + [ctypes.POINTER(_ci), _vp]
 _lib.pn2x_tg_bwd_slice_pair.restype = _ci
 PAIR_LAUNCH = _os.environ.get("HOTRACK_STACK_PAIR_LAUNCH", "1") != "0"  # one launch for equal-shaped layers of two sibling stacks
-_lib.pn2x_tg_reduce_multi2.argtypes = [_ci, ctypes.POINTER(_vp), ctypes.POINTER(_ci), ctypes.POINTER(_ci), ctypes.POINTER(_vp),
-                                       ctypes.POINTER(_vp), ctypes.POINTER(_ci), ctypes.POINTER(_ci), ctypes.POINTER(_vp),
-                                       ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp]
-_lib.pn2x_tg_reduce_multi2.restype = _ci
+_lib.pn2x_tg_reduce_multi.argtypes = [_ci, ctypes.POINTER(_vp), ctypes.POINTER(_ci), ctypes.POINTER(_ci), ctypes.POINTER(_vp),
+                                      ctypes.POINTER(_vp), ctypes.POINTER(_ci), ctypes.POINTER(_ci), ctypes.POINTER(_vp),
+                                      ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp]
+_lib.pn2x_tg_reduce_multi.restype = _ci
 
 
 def _bwd_slices(c_in: int, c_out: int):
@@ -87,7 +80,6 @@ def _bwd_slices(c_in: int, c_out: int):
 
 _lib.pn2x_bn_bwd_reduce_routed.argtypes = [_cl, _ci, _ci, _vp, _ci, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp]
 _lib.pn2x_bn_bwd_reduce_routed.restype = _ci
-_lib.pn2x_tg_bwd.restype = _ci
 _lib.pn2x_tg_bwd_set_variant.argtypes = [_ci]
 _lib.pn2x_tg_bwd_set_variant.restype = _ci
 
@@ -98,10 +90,8 @@ def set_bwd_kernel_variant(v2: bool) -> None:
     _native._check(_lib.pn2x_tg_bwd_set_variant(1 if v2 else 0), "tg_bwd_set_variant")
 FUSED_BWD = True  # data + weight gradient of a layer in one kernel (train_bwd.hip); False: the two-kernel backward (tests compare)
 ROUTE_ON_LOAD = True  # max-pooled top: sums from the arg-max rows, routed on load
-_lib.pn2x_bn_bwd_reduce.argtypes = [_cl, _ci, _vp, _ci, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _vp]
+_lib.pn2x_bn_bwd_reduce.argtypes = [_cl, _ci, _vp, _ci, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _vp, _ci, _vp]
 _lib.pn2x_bn_bwd_reduce.restype = _ci
-_lib.pn2x_bn_bwd_reduce_g.argtypes = [_cl, _ci, _vp, _ci, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _vp, _ci, _vp]
-_lib.pn2x_bn_bwd_reduce_g.restype = _ci
 ROUTE_DENSE = True  # max-routed top gradient materialised once by the reduction (where ROUTE_ON_LOAD does not apply)
 # The weight gradients are not read before the optimiser: the backward writes only partial tiles and ONE launch at the end of
 # the pass (autograd's final callbacks) sums the tiles of every layer of every stack.  Off (HOTRACK_STACK_DEFER_REDUCE=0, or
@@ -224,6 +214,7 @@ def _dpar(gamma, beta, bias, n, dev):
     return out
 
 
+_lib.pn2x_wgrad_multi_max.argtypes = []
 _lib.pn2x_wgrad_multi_max.restype = _ci
 _lib.pn2x_wgrad_multi_scratch_floats.argtypes = [_ci, ctypes.POINTER(_ci), ctypes.POINTER(_ci), ctypes.POINTER(_ci)]
 _lib.pn2x_wgrad_multi_scratch_floats.restype = _cl
@@ -289,20 +280,18 @@ def _reduce_items(items):
     if any(it[5] != st for it in items):
         raise RuntimeError("train_stack: deferred reductions recorded on different streams")
     with torch.cuda.device(items[0][2].device):
-        _native._check(_lib.pn2x_tg_reduce_multi2(n, part, P, numel, dw, sm, ch, sld, dg, db, dbi, st), "tg_reduce_multi")
+        _native._check(_lib.pn2x_tg_reduce_multi(n, part, P, numel, dw, sm, ch, sld, dg, db, dbi, st), "tg_reduce_multi")
 
 
 _lib.pn2x_bn_bwd_apply_rel.argtypes = [_cl, _ci, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _cl, _vp, _vp]
 _lib.pn2x_bn_bwd_apply_rel.restype = _ci
 _lib.pn2x_bn_bwd_reduce_routed_pair.argtypes = _lib.pn2x_bn_bwd_reduce_routed.argtypes[:-1] * 2 + [_vp]
 _lib.pn2x_bn_bwd_reduce_routed_pair.restype = _ci
-_lib.pn2x_bn_relu_max_pair.argtypes = _t._lib.pn2x_bn_relu_max.argtypes[:-1] * 2 + [_vp]
-_lib.pn2x_bn_relu_max_pair.restype = _ci
 _MAX_LD = _t._lib.pn2x_bn_relu_max.argtypes[:-2] + [_ci, _vp]  # (..., out, ldo, arg): the output rows ldo floats apart
 _lib.pn2x_bn_relu_max_ld.argtypes = _MAX_LD + [_vp]
 _lib.pn2x_bn_relu_max_ld.restype = _ci
-_lib.pn2x_bn_relu_max_pair_ld.argtypes = _MAX_LD * 2 + [_vp]
-_lib.pn2x_bn_relu_max_pair_ld.restype = _ci
+_lib.pn2x_bn_relu_max_pair.argtypes = _MAX_LD * 2 + [_vp]
+_lib.pn2x_bn_relu_max_pair.restype = _ci
 _lib.pn2x_bn_bwd_apply_rel_pair.argtypes = _lib.pn2x_bn_bwd_apply_rel.argtypes[:-1] * 2 + [_vp]
 _lib.pn2x_bn_bwd_apply_rel_pair.restype = _ci
 _lib.pn2x_bn_bwd_apply_rel_scratch_floats.argtypes = [_cl, _ci]
@@ -470,7 +459,7 @@ class _Bwd:
                 # GEMMs of the top layer read that instead of routing through arg-max on every load (their slowest variant)
                 g_dense = torch.empty((R, Cl), dtype=_f32, device=dev)
             if not routed:
-                _native._check(_lib.pn2x_bn_bwd_reduce_g(R, Cl, dout.data_ptr(), Cl, _p(arg), K if K else 1, yl.data_ptr(), yl.stride(0),
+                _native._check(_lib.pn2x_bn_bwd_reduce(R, Cl, dout.data_ptr(), Cl, _p(arg), K if K else 1, yl.data_ptr(), yl.stride(0),
                                                          svl[0].data_ptr(), svl[1].data_ptr(), gam(L - 1).data_ptr(),
                                                          bet(L - 1).data_ptr(), 1, sums[L - 1].data_ptr(), _p(g_dense), Cl, st),
                                "bn_bwd_reduce")
@@ -517,7 +506,7 @@ class _Bwd:
                 pf = int(_lib.pn2x_tg_wgrad_partial_floats(R, N, Kc))
                 partial = torch.empty(pf, dtype=_f32, device=dev)
                 np_ = _ci(0)
-                _native._check(_lib.pn2x_tg_wgrad2(R, N, Kc, *dy_args, yp.data_ptr(), yp.stride(0), svp[0].data_ptr(), svp[1].data_ptr(),
+                _native._check(_lib.pn2x_tg_wgrad(R, N, Kc, *dy_args, yp.data_ptr(), yp.stride(0), svp[0].data_ptr(), svp[1].data_ptr(),
                                                    gam(i - 1).data_ptr(), bet(i - 1).data_ptr(), partial.data_ptr(), pf, dw.data_ptr(),
                                                    dpar[0].data_ptr(), dpar[1].data_ptr(), dpar[2].data_ptr(),
                                                    ctypes.byref(np_) if defer else None, st), "tg_wgrad")
@@ -602,7 +591,7 @@ def _issue_pair(a, b):
             _native._check(_lib.pn2x_bn_bwd_apply_rel_pair(*a[1], *b[1], st), "bn_bwd_apply_rel_pair")
             return None, None
         if kind == "max":
-            _native._check(_lib.pn2x_bn_relu_max_pair_ld(*a[1], *b[1], st), "bn_relu_max_pair")
+            _native._check(_lib.pn2x_bn_relu_max_pair(*a[1], *b[1], st), "bn_relu_max_pair")
             return None, None
         if kind == "routed":
             _native._check(_lib.pn2x_bn_bwd_reduce_routed_pair(*a[1], *b[1], st), "bn_bwd_reduce_routed_pair")

@@ -40,21 +40,15 @@ int pn2x_kabsch_backward(int b, int xb, int num, const float *x, const float *y,
  * (reference hand_network.py:100,118-119 + hand_utils.py:30-31,42-66: ransac_rt with a CPU SVD, torch.cat,
  * transpose, matmul, divide).  points (b,n,3), kp (b,j,3), palm_template (xb,num,3) with xb in {1,b};
  * outputs R (b,3,3), t (b,3,1), xyz2 (b,n,3), xyz1 (b,j,3), all point-major.
+ * xyz2_copy (or NULL): a second copy of xyz2 into three columns of a wider row buffer (row stride copy_ld floats).
+ * nonfinite (device int32, b entries, or NULL): per-cloud flag, 1 when the cloud, the keypoints or the fit of cloud b contain
+ * a NaN / Inf.  Handed to pn2x_pose_head, it turns that frame's predicted keypoints into NaN: the fused inference kernels
+ * drop NaNs in their ReLU / max-pool maxima (built -fno-honor-nans), whereas in the reference a non-finite input point
+ * spreads through sampling, grouping and the global max-pool to every output of its frame.
  */
 int pn2x_hand_frame(int b, int xb, int num, int n, int j, const float *palm_template, const float *kp,
                     const int *palm_idx, const float *points, float scale, float *R, float *t, float *xyz2,
-                    float *xyz1, void *stream);
-/* ... and a second copy of xyz2 into three columns of a wider row buffer (row stride copy_ld floats), or NULL. */
-int pn2x_hand_frame2(int b, int xb, int num, int n, int j, const float *palm_template, const float *kp,
-                     const int *palm_idx, const float *points, float scale, float *R, float *t, float *xyz2,
-                     float *xyz1, float *xyz2_copy, int copy_ld, void *stream);
-/* ... and a per-cloud flag nonfinite[b] (device int32, b entries, or NULL): 1 when the cloud, the keypoints or the fit of
- * cloud b contain a NaN / Inf.  Handed to pn2x_pose_head2, it turns that frame's predicted keypoints into NaN: the
- * fused inference kernels drop NaNs in their ReLU / max-pool maxima (built -fno-honor-nans), whereas in the reference a
- * non-finite input point spreads through sampling, grouping and the global max-pool to every output of its frame. */
-int pn2x_hand_frame3(int b, int xb, int num, int n, int j, const float *palm_template, const float *kp,
-                     const int *palm_idx, const float *points, float scale, float *R, float *t, float *xyz2,
-                     float *xyz1, float *xyz2_copy, int copy_ld, int *nonfinite, void *stream);
+                    float *xyz1, float *xyz2_copy, int copy_ld, int *nonfinite, void *stream);
 
 /*
  * Fused grouped MLP + max of one set-abstraction scale, eval mode (BatchNorm folded into the
@@ -155,7 +149,7 @@ int pn2x_fps_radii_knn(int b, int n, int m, const float *xyz, int *idx, float *r
                        int *knn_idx, int *knn_idx2, void *stream);
 int pn2x_fps_prefix_ties(int b, int n, int m1, int m2, const float *xyz, const int *idx1, const float *radii, int *flags, void *stream);
 /*
- * pn2x_ball_query_picks_ties: pn2x_ball_query_picks2 (ball query around the picks (b, m) of a sampling run + their coordinates) AND
+ * pn2x_ball_query_picks_ties: pn2x_ball_query_picks (ball query around the picks (b, m) of a sampling run + their coordinates) AND
  * pn2x_fps_prefix_ties (was an arg-max among the first m2 picks tied?  radii (b, m) from the sampling run, flags as above) in ONE
  * launch -- both consume the picks and nothing of each other.  Same outputs as the two calls.  PN2_ERANGE unless
  * pn2x_ball_query_picks_ties_supported(b, n, m, m2): small batches (b n <= 16384, the tracking loop), m2 <= 1024.
@@ -177,13 +171,11 @@ int pn2x_knn_indices(int b, int n, int m, int k, int k2, const float *unknown, c
  * pn2_ball_query whose centroids are given as indices into the cloud itself (picks (b, m) int32, values in [0, n):
  * the output of FPS), which is how PointNet++ always calls it (pointnet_utils.py:379-382: sample, gather, query).
  * Also writes the centroids' coordinates new_xyz (b, m, 3) = xyz[picks], so the gather launch disappears.
+ * new_xyz_copy (or NULL): a second copy of the coordinates into three columns of a wider row buffer (row stride copy_ld
+ * floats; the consumer's [feat | xyz] GEMM input, so the reference's torch.cat of pointnet_utils.py:493 is not needed).
  */
 int pn2x_ball_query_picks(int b, int n, int m, float radius, int nsample, const float *xyz, const int *picks, float *new_xyz,
-                          int *idx, void *stream);
-/* ... and a second copy of the coordinates into three columns of a wider row buffer (row stride copy_ld floats; the
- * consumer's [feat | xyz] GEMM input, so the reference's torch.cat of pointnet_utils.py:493 is not needed), or NULL. */
-int pn2x_ball_query_picks2(int b, int n, int m, float radius, int nsample, const float *xyz, const int *picks, float *new_xyz,
-                           int *idx, float *new_xyz_copy, int copy_ld, void *stream);
+                          int *idx, float *new_xyz_copy, int copy_ld, void *stream);
 
 /*
  * pn2_ball_query through a cell grid (csrc/ball_query_grid.hip): identical output for every input -- the same hit test on
@@ -235,13 +227,11 @@ int pn2x_add_layernorm(long rows, int c, const float *x, const float *y, const f
 /*
  * Head of HandTrackNet (hand_network.py:141-147): delta = h W^T + bias (W (3, c): the last Conv1d), kp_hand = delta +
  * xyz1, kp_cam = (kp_hand R^T) * scale + t.  h (b*j, c) token-major; xyz1, kp_hand, kp_cam (b, j, 3); R (b,3,3); t (b,3,1).
+ * nonfinite: the per-cloud flags of pn2x_hand_frame (or NULL): flagged frames get NaN keypoints in both frames.
  */
 int pn2x_pose_head(int b, int j, int c, const float *h, const float *w, const float *bias, const float *xyz1,
-                   const float *R, const float *t, float scale, float *kp_hand, float *kp_cam, void *stream);
-/* ... with the per-cloud flags of pn2x_hand_frame3 (or NULL): flagged frames get NaN keypoints in both frames. */
-int pn2x_pose_head2(int b, int j, int c, const float *h, const float *w, const float *bias, const float *xyz1,
-                    const float *R, const float *t, float scale, float *kp_hand, float *kp_cam, const int *nonfinite,
-                    void *stream);
+                   const float *R, const float *t, float scale, float *kp_hand, float *kp_cam, const int *nonfinite,
+                   void *stream);
 
 /*
  * Both scales of a keypoint-query module (reference PointNetSetAbstractionMsg_GivenCenterPoints, pointnet_utils.py:536-590:
@@ -345,14 +335,12 @@ int pn2x_bn_relu_bwd(long rows, int c, const float *dh, int ldd, const float *y,
  * [feat_j | xyz_j - c_s | centre_feat_s] (reference pointnet_utils.py:389-399, :566-577): the same linear split as
  * pn2x_sa_mlp_max (a1f / wx / cadd, each optional, see above), bias omitted because BatchNorm follows.
  *   out (b, s*k, c1) point-major; rel_out (b, s*k, 3) or NULL receives xyz_j - c_s (the backward's d(wx) operand).
+ * The (c1, 3) weight block wx is read in place from a wider matrix: rows wx_ld >= 3 floats apart (a column block of the
+ * layer's [feature | xyz | centre] weight; no contiguous copy per step).
  */
 int pn2x_sa_layer1(int b, int n, int s, int k, int c1, const float *a1f, int a1f_ld, const float *xyz, const float *cxyz,
-                   const float *wx, const float *cadd, int cadd_ld, const int *idx, float *out, float *rel_out, void *stream);
-/* the same with the (c1, 3) weight block taken in place from a wider matrix: rows wx_ld floats apart (a column block of the
- * layer's [feature | xyz | centre] weight; no contiguous copy per step) */
-int pn2x_sa_layer1_ld(int b, int n, int s, int k, int c1, const float *a1f, int a1f_ld, const float *xyz, const float *cxyz,
-                      const float *wx, int wx_ld, const float *cadd, int cadd_ld, const int *idx, float *out, float *rel_out,
-                      void *stream);
+                   const float *wx, int wx_ld, const float *cadd, int cadd_ld, const int *idx, float *out, float *rel_out,
+                   void *stream);
 /* the same, also accumulating the BatchNorm statistics of `out` into sums (pn2x_bn_sums_doubles(c1) doubles, zeroed by the caller,
  * as pn2x_bn_stats would): the layer that follows is a train-mode BatchNorm (pointnet_utils.py:399-401), and its separate
  * statistics pass over the (b s k, c1) tensor -- one launch per scale and step -- is saved */
@@ -423,26 +411,20 @@ int pn2x_scatter_cm(int t, int b, int c, int n_dst, int m_src, const float *grad
 int pn2x_bn_relu_max(long groups, int k, int c, const float *y, int ldy, const double *sums, const float *gamma, const float *beta,
                      const float *conv_bias, float eps, float momentum, float *running_mean, float *running_var,
                      long long *num_batches_tracked, float *save_mean, float *save_invstd, float *out, int *arg, void *stream);
-/* two problems (the two neighbourhood sizes of a module) in ONE launch where both take the few-groups kernel; two calls otherwise */
-int pn2x_bn_relu_max_pair(long groups_a, int k_a, int c_a, const float *y_a, int ldy_a, const double *sums_a, const float *gamma_a,
-                          const float *beta_a, const float *conv_bias_a, float eps_a, float momentum_a, float *running_mean_a,
-                          float *running_var_a, long long *nbt_a, float *save_mean_a, float *save_invstd_a, float *out_a, int *arg_a,
-                          long groups_b, int k_b, int c_b, const float *y_b, int ldy_b, const double *sums_b, const float *gamma_b,
-                          const float *beta_b, const float *conv_bias_b, float eps_b, float momentum_b, float *running_mean_b,
-                          float *running_var_b, long long *nbt_b, float *save_mean_b, float *save_invstd_b, float *out_b, int *arg_b,
-                          void *stream);
 /* the same with the output rows ldo floats apart (`out` = a column block of a wider buffer: the scales of a multi-scale module,
  * reference pointnet_utils.py:405-409 / :583-590 `torch.cat(new_points_list, dim=1)`, write the halves of one tensor) */
 int pn2x_bn_relu_max_ld(long groups, int k, int c, const float *y, int ldy, const double *sums, const float *gamma, const float *beta,
                         const float *conv_bias, float eps, float momentum, float *running_mean, float *running_var,
                         long long *num_batches_tracked, float *save_mean, float *save_invstd, float *out, int ldo, int *arg, void *stream);
-int pn2x_bn_relu_max_pair_ld(long groups_a, int k_a, int c_a, const float *y_a, int ldy_a, const double *sums_a, const float *gamma_a,
-                             const float *beta_a, const float *conv_bias_a, float eps_a, float momentum_a, float *running_mean_a,
-                             float *running_var_a, long long *nbt_a, float *save_mean_a, float *save_invstd_a, float *out_a, int ldo_a,
-                             int *arg_a, long groups_b, int k_b, int c_b, const float *y_b, int ldy_b, const double *sums_b,
-                             const float *gamma_b, const float *beta_b, const float *conv_bias_b, float eps_b, float momentum_b,
-                             float *running_mean_b, float *running_var_b, long long *nbt_b, float *save_mean_b, float *save_invstd_b,
-                             float *out_b, int ldo_b, int *arg_b, void *stream);
+/* pn2x_bn_relu_max_ld for two problems (the two neighbourhood sizes of a module) in ONE launch where both take the few-groups
+ * kernel; two calls otherwise */
+int pn2x_bn_relu_max_pair(long groups_a, int k_a, int c_a, const float *y_a, int ldy_a, const double *sums_a, const float *gamma_a,
+                          const float *beta_a, const float *conv_bias_a, float eps_a, float momentum_a, float *running_mean_a,
+                          float *running_var_a, long long *nbt_a, float *save_mean_a, float *save_invstd_a, float *out_a, int ldo_a,
+                          int *arg_a, long groups_b, int k_b, int c_b, const float *y_b, int ldy_b, const double *sums_b,
+                          const float *gamma_b, const float *beta_b, const float *conv_bias_b, float eps_b, float momentum_b,
+                          float *running_mean_b, float *running_var_b, long long *nbt_b, float *save_mean_b, float *save_invstd_b,
+                          float *out_b, int ldo_b, int *arg_b, void *stream);
 int pn2x_bn_relu_max_bwd(long groups, int k, int c, const float *dout, const int *arg, const float *y, int ldy, const float *mean,
                          const float *invstd, const float *gamma, const float *beta, double *sums, float *dy, int ldo, float *dgamma,
                          float *dbeta, float *dbias, void *stream);
@@ -451,19 +433,17 @@ int pn2x_bn_relu_max_bwd(long groups, int k, int c, const float *dout, const int
  * The two launches of pn2x_bn_relu_bwd / pn2x_bn_relu_max_bwd as separate entries (used by the fused training stacks below).
  * pn2x_bn_bwd_reduce: sums += [sum_r g, sum_r g xhat] with g = dh . [relu(bn(y)) > 0] (relu != 0) -- or, with arg != NULL,
  *   dh = d(max over k consecutive rows) (rows / k x c, row stride ldd, arg (rows / k, c) with the same row stride c) routed
- *   to the recorded arg-max row and ReLU-masked.
+ *   to the recorded arg-max row and ReLU-masked; for this max-routed form the routed + masked gradient itself is also written
+ *   densely to g_out (rows x c, row stride ldg) unless g_out is NULL: the fused GEMMs of the layer below then read a plain
+ *   gradient instead of routing it on every load.
  * pn2x_bn_bwd_apply: dy = gamma invstd (g' - sum(g)/R - xhat sum(g xhat)/R) with g' = g . mask when relu != 0, g as given
  *   (already masked) when relu == 0; also writes dgamma, dbeta (and zeros to dbias) from the sums.
  */
 int pn2x_bn_bwd_reduce(long rows, int c, const float *dh, int ldd, const int *arg, int k, const float *y, int ldy, const float *mean,
-                       const float *invstd, const float *gamma, const float *beta, int relu, double *sums, void *stream);
-/* ... and, for the max-routed form (arg != NULL), the routed + masked gradient itself written densely to g_out (rows x c, row
- * stride ldg) or NULL: the fused GEMMs of the layer below then read a plain gradient instead of routing it on every load. */
-int pn2x_bn_bwd_reduce_g(long rows, int c, const float *dh, int ldd, const int *arg, int k, const float *y, int ldy, const float *mean,
-                         const float *invstd, const float *gamma, const float *beta, int relu, double *sums, float *g_out, int ldg,
-                         void *stream);
+                       const float *invstd, const float *gamma, const float *beta, int relu, double *sums, float *g_out, int ldg,
+                       void *stream);
 /* The same sums for a max-routed top layer from its arg-max rows only (groups x c gathered reads of y instead of rows x c):
- * dout (groups x c, row stride ldd: may be a column block of a wider gradient), arg (groups x c, row stride lda), y ((groups * k) x c).  The layer below then routes on load (pn2x_tg_bwd, gmode 2). */
+ * dout (groups x c, row stride ldd: may be a column block of a wider gradient), arg (groups x c, row stride lda), y ((groups * k) x c).  The layer below then routes on load (pn2x_tg_bwd_slice, gmode 2). */
 int pn2x_bn_bwd_reduce_routed(long groups, int k, int c, const float *dout, int ldd, const int *arg, int lda, const float *y, int ldy,
                               const float *mean, const float *invstd, const float *gamma, const float *beta, double *sums, void *stream);
 /* two problems of the same channel count in one launch (two launches when the counts differ); same results */
@@ -516,6 +496,9 @@ int pn2x_bn_bwd_apply_rel_pair(long rows_a, int c_a, const float *g_a, int ldg_a
  *                and sums_bwd_i (complete: from pn2x_bn_bwd_reduce for the top layer, from the dgrad of layer i+1 otherwise).
  * pn2x_tg_wgrad  dw (n x k) = dY_i^T relu(BN_p(y_p)) (both operands computed on load), reduced over row splits through
  *                `partial` (>= pn2x_tg_wgrad_partial_floats(rows, n, k) floats); also dgamma_i, dbeta_i (and zeros to dbias_i).
+ *                n_partials != NULL: the reduction is deferred -- only the partial tiles are written (dw zeroed) and their
+ *                count returned in *n_partials; pn2x_tg_reduce_multi then sums the partial tiles of SEVERAL layers in one
+ *                launch (the weight gradients are not needed before the optimiser step).
  * pn2x_tg_supported(c_in, c_out): c_in % 4 == 0, c_in <= 512, c_out a multiple of 32 (for wgrad also c_in % 32 == 0).
  */
 int pn2x_tg_supported(int c_in, int c_out);
@@ -531,7 +514,8 @@ long pn2x_tg_wgrad_partial_floats(long rows, int n, int k);
 int pn2x_tg_wgrad(long rows, int n, int k, int gmode, const float *g, int ldg, const int *arg, int kmax, const float *yi, int ldyi,
                   const float *mean_i, const float *invstd_i, const float *gamma_i, const float *beta_i, const double *sums_bwd_i,
                   const float *yp, int ldyp, const float *mean_p, const float *invstd_p, const float *gamma_p, const float *beta_p,
-                  float *partial, long partial_floats, float *dw, float *dgamma, float *dbeta, float *dbias, void *stream);
+                  float *partial, long partial_floats, float *dw, float *dgamma, float *dbeta, float *dbias, int *n_partials,
+                  void *stream);
 
 /*
  * The loss / metric dictionary of HandTrackNet.compute_loss (reference hand_network.py:159-221, training mode without MANO
@@ -539,19 +523,15 @@ int pn2x_tg_wgrad(long rows, int n, int k, int gmode, const float *g, int ldg, c
  * pred_hf / init_hf (b,3,21) channel-major hand-frame keypoints, gt_kp / pred_kp (b,21,3) camera frame, R (b,3,3) / t (b,3) /
  * scale: the canonical pose, palm (pb,6,3) with pb in {1,b}: the palm template.  out[9] =
  *   {hand_pred_kp_loss, hand_pred_r_loss, hand_pred_t_loss, hand_pred_kp_diff, hand_init_kp_diff, hand_init_r_diff,
- *    hand_init_t_diff, hand_pred_r_diff, hand_pred_t_diff};  saved (b, 87) floats for the backward.
- * backward: d_pred_hf (b,3,21) = d(grad3[0] out[0] + grad3[1] out[1] + grad3[2] out[2]) / d pred_hf, grad3 on the device.
+ *    hand_init_t_diff, hand_pred_r_diff, hand_pred_t_diff};  saved (b, 87) floats for the backward.  weights (9, or NULL): the
+ * caller's weighted total folded in -- out then has ten entries, out[9] = sum_i weights[i] out[i].
+ * backward: d_pred_hf (b,3,21) = d(grad3[0] out[0] + grad3[1] out[1] + grad3[2] out[2] + grad_total[0] out[9]) / d pred_hf;
+ * grad3 (3) and grad_total (1) on the device, either may be NULL (not both); weights as given to the forward.
  */
-int pn2x_hand_losses(int b, int pb, const float *pred_hf, const float *init_hf, const float *gt_kp, const float *pred_kp,
-                     const float *R, const float *t, float scale, const float *palm, float *out, float *saved, void *stream);
-int pn2x_hand_losses_backward(int b, int pb, const float *pred_hf, float scale, const float *palm, const float *saved,
-                              const float *grad3, float *d_pred_hf, void *stream);
-/* ... with the caller's weighted total folded in: weights (9) -> out has ten entries, out[9] = sum_i weights[i] out[i]; the backward
- * takes dL/d out[0..2] (grad3, may be NULL) and / or dL/d out[9] (grad_total, one float on the device, may be NULL). */
-int pn2x_hand_losses2(int b, int pb, const float *pred_hf, const float *init_hf, const float *gt_kp, const float *pred_kp, const float *R,
-                      const float *t, float scale, const float *palm, float *out, float *saved, const float *weights, void *stream);
-int pn2x_hand_losses_backward2(int b, int pb, const float *pred_hf, float scale, const float *palm, const float *saved, const float *grad3,
-                               const float *grad_total, const float *weights, float *d_pred_hf, void *stream);
+int pn2x_hand_losses(int b, int pb, const float *pred_hf, const float *init_hf, const float *gt_kp, const float *pred_kp, const float *R,
+                     const float *t, float scale, const float *palm, float *out, float *saved, const float *weights, void *stream);
+int pn2x_hand_losses_backward(int b, int pb, const float *pred_hf, float scale, const float *palm, const float *saved, const float *grad3,
+                              const float *grad_total, const float *weights, float *d_pred_hf, void *stream);
 
 /*
  * The 21-token tail in TRAINING mode (csrc/tail_train.hip; reference transformer.py:65-67, hand_network.py:139-147 with
@@ -589,30 +569,19 @@ int pn2x_tail_pose_head_bwd(int b, int j, int c, const float *h, const float *w,
  * One Adam step over n fp32 tensors (csrc/adam.hip): torch.optim.Adam semantics (L2 weight decay added to the gradient, bias
  * corrections from the per-tensor `step` counters, no amsgrad -- reference trainer.py:49-52), the arithmetic of torch's fused
  * kernel.  p / g / m / v / step: HOST arrays of n device pointers (m = exp_avg, v = exp_avg_sq, step = one fp32 counter per
- * tensor, advanced by this call); numel: host array of n element counts.  The tensor table travels in the kernel arguments.
+ * tensor); numel: host array of n element counts.  The tensor table travels in the kernel arguments.  advance != 0: this call
+ * advances the counters; advance = 0: they are left alone (the caller keeps them in one contiguous buffer and advances them all
+ * with pn2x_adam_advance AFTER every pn2x_adam_multi of the step: the update kernels read the old values).
  */
-int pn2x_adam_multi(int n, void *const *p, const void *const *g, void *const *m, void *const *v, void *const *step,
-                    const long *numel, double lr, double beta1, double beta2, double eps, double weight_decay, void *stream);
-/* advance = 0: the counters are left alone (the caller keeps them in one contiguous buffer and advances them all with
- * pn2x_adam_advance AFTER every pn2x_adam_multi2 of the step: the update kernels read the old values) */
-int pn2x_adam_multi2(int n, void *const *p, const void *const *g, void *const *m, void *const *v, void *const *step, const long *numel,
-                     double lr, double beta1, double beta2, double eps, double weight_decay, int advance, void *stream);
+int pn2x_adam_multi(int n, void *const *p, const void *const *g, void *const *m, void *const *v, void *const *step, const long *numel,
+                    double lr, double beta1, double beta2, double eps, double weight_decay, int advance, void *stream);
 int pn2x_adam_advance(float *steps, int n, void *stream);
-/* pn2x_tg_wgrad with the reduction deferred: n_partials != NULL -> only the partial tiles are written (dw zeroed) and their count
- * returned; pn2x_tg_reduce_multi then sums the partial tiles of SEVERAL layers (host arrays of `count` entries) and emits their
- * dgamma / dbeta (/ zero dbias) in one launch -- the weight gradients are not needed before the optimiser step. */
-int pn2x_tg_wgrad2(long rows, int n, int k, int gmode, const float *g, int ldg, const int *arg, int kmax, const float *yi, int ldyi,
-                   const float *mean_i, const float *invstd_i, const float *gamma_i, const float *beta_i, const double *sums_bwd_i,
-                   const float *yp, int ldyp, const float *mean_p, const float *invstd_p, const float *gamma_p, const float *beta_p,
-                   float *partial, long partial_floats, float *dw, float *dgamma, float *dbeta, float *dbias, int *n_partials,
-                   void *stream);
+/* The deferred reduction of pn2x_tg_wgrad (n_partials != NULL) for SEVERAL layers (host arrays of `count` entries): sums their
+ * partial tiles and emits their dgamma / dbeta (/ zero dbias) in one launch.  Entries may be column slices of a wider layer:
+ * sums_ld[j] = channels of the whole layer (sums_ld NULL: = channels[j]). */
 int pn2x_tg_reduce_multi(int count, const float *const *partial, const int *n_partials, const int *numel, float *const *dw,
-                         const double *const *sums_bwd, const int *channels, float *const *dgamma, float *const *dbeta,
-                         float *const *dbias, void *stream);
-/* ... with entries that are column slices of a wider layer: sums_ld[j] = channels of the whole layer (NULL: = channels[j]) */
-int pn2x_tg_reduce_multi2(int count, const float *const *partial, const int *n_partials, const int *numel, float *const *dw,
-                          const double *const *sums_bwd, const int *channels, const int *sums_ld, float *const *dgamma,
-                          float *const *dbeta, float *const *dbias, void *stream);
+                         const double *const *sums_bwd, const int *channels, const int *sums_ld, float *const *dgamma,
+                         float *const *dbeta, float *const *dbias, void *stream);
 /* pn2x_tg_fwd with a different schedule for 64- / 128-channel inputs (csrc/train_fwd.hip: W_i resident in LDS, 64-row tiles whose
  * normalised operand is built once, one 32 x 32 output block per wave).  Same arguments and results (up to summation order). */
 int pn2x_tg_fwd2_supported(int c_in, int c_out);
@@ -622,13 +591,13 @@ int pn2x_tg_fwd2(long rows, int k, int n, const float *x, int ldx, const float *
                  void *stream);
 
 /* The whole backward of fused layer i in one kernel (csrc/train_bwd.hip): g_{i-1} (gp, with the ReLU mask and the
- * BatchNorm-backward sums of layer i-1, as pn2x_tg_dgrad) AND the weight-gradient partial tiles (as pn2x_tg_wgrad2 with
+ * BatchNorm-backward sums of layer i-1, as pn2x_tg_dgrad) AND the weight-gradient partial tiles (as pn2x_tg_wgrad with
  * n_partials) from one pass over g_i, Y_i and Y_{i-1}.  gmode 0: g pre-masked (rows x n); gmode 1: g dense, ReLU-masked from Y_i on load; gmode 2: g = d(max over kmax
  * rows) ((rows / kmax) x n) routed on load through arg (same shape / stride) and ReLU-masked from Y_i.  n = channels of layer i, k = channels of layer
  * i-1; w (n x k).  pn2x_tg_bwd_supported(k, n): k in {32, 64, 128} and the instantiated n; pn2x_tg_bwd_partials = the number
- * of (n x k) partial tiles written (partial_floats >= that * n * k), to be summed by pn2x_tg_reduce_multi.  dw is zeroed. */
-/* pn2x_tg_bwd_slice: one column slice [c0, c0 + n) of a layer with sums_ld channels (all layer-i pointers offset to the slice by the
- * caller).  A wider layer runs as consecutive slices: raw_out = 1 leaves the unmasked partial data gradient in gp, the next slice
+ * of (n x k) partial tiles written (partial_floats >= that * n * k), to be summed by pn2x_tg_reduce_multi.  dw is zeroed.
+ * pn2x_tg_bwd_slice runs one column slice [c0, c0 + n) of a layer with sums_ld channels (all layer-i pointers offset to the slice by the
+ * caller; a whole layer is the one slice c0 = 0, sums_ld = n, ldarg = ldg, g_add = NULL, raw_out = 0).  A wider layer runs as consecutive slices: raw_out = 1 leaves the unmasked partial data gradient in gp, the next slice
  * passes it as g_add (may alias gp) and the last one applies the mask and accumulates the sums.  gmode 1: dense g, masked from Y_i. */
 int pn2x_tg_bwd_slice(long rows, int n, int k, int gmode, const float *g, int ldg, const int *arg, int ldarg, int kmax, const float *yi, int ldyi,
                       const float *mean_i, const float *invstd_i, const float *gamma_i, const float *beta_i, const double *sums_bwd_i,
@@ -666,11 +635,6 @@ int pn2x_tg_bwd_partials(long rows, int c_out, int c_in);
  * every shape, 1 (default, or HOTRACK_TGB2) the new one where instantiated.  Process-wide: switch between whole backward passes
  * only (tests, A/B benches) -- the number of partial tiles a launch writes depends on it. */
 int pn2x_tg_bwd_set_variant(int v2);
-int pn2x_tg_bwd(long rows, int n, int k, int gmode, const float *g, int ldg, const int *arg, int kmax, const float *yi, int ldyi,
-                const float *mean_i, const float *invstd_i, const float *gamma_i, const float *beta_i, const double *sums_bwd_i,
-                const float *w, int ldw, const float *yp,
-                int ldyp, const float *mean_p, const float *invstd_p, const float *gamma_p, const float *beta_p, float *gp, int ldgp,
-                double *sums_bwd_p, float *partial, long partial_floats, float *dw, void *stream);
 
 /* The weight gradients of `count` plain linear layers in one grouped launch (csrc/train_wgrad.hip):
  *   dw[p] (n[p] x k[p], row stride lddw[p]) = g[p]^T (rows[p] x n[p], row stride ldg[p]) . x[p] (rows[p] x k[p], row stride ldx[p])

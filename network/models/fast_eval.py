@@ -49,7 +49,6 @@ class FastEval:
         self.P = None
         self._consts = {}
         self._idents = {}
-        self.two_level_fps = True  # level-2 sampling via the prefix property (ext.fps_two_level)
         self.row_chain = True  # large batches: fp1 -> conv1 -> q layer 1 over the kNN-listed rows only (ext.row_chain)
 
     def _palm_idx(self, device):
@@ -165,41 +164,29 @@ class FastEval:
                 q[(name, i)] = dict(wx=W1[:, C:C + 3].contiguous(), b1=b1, l2=l2, l3=l3, K=mod.nsample_list[i],
                                     wc=W1[:, C + 3:] if W1.shape[1] > C + 3 else None)
         P["q"] = q
-        # fp1 (both layers), conv1 and the four scales' layer-1 feature product as ONE launch over the rows some keypoint's kNN
-        # list names (ext.row_chain): weights in the kernel's operand layout, the small-K scale's columns first
-        P["row_chain"] = None
+        # Layer 1 of a keypoint branch is linear in the per-point feature: the feature term of all four branches is ONE product
+        # with the stacked weight [q1 scale i | q2 scale i] per scale i, the small-K scale first (column block j of the product
+        # belongs to scale wq_order[j])
         Ks = [q[("q1", i)]["K"] for i in range(2)]
+        i_s = Ks.index(min(Ks))
+        P["wq_order"] = (i_s, 1 - i_s)
+        P["wq"] = torch.cat([torch.cat([wq[i], wq[2 + i]], dim=0) for i in P["wq_order"]], dim=0)
+        # fp1 (both layers), conv1 and that product as ONE launch over the rows some keypoint's kNN list names (ext.row_chain):
+        # weights in the kernel's operand layout
+        P["row_chain"] = None
         Wc = P["conv1"][0]
         if (len(fp1) == 2 and c_in == P["fp2"][-1][0].shape[0] and Ks[0] != Ks[1] and fp1[0][0].shape[1] == c_in + 3
                 and ext.row_chain_supported(c_in, fp1[0][0].shape[0], Wc.shape[0], 4 * wq[0].shape[0])
                 and fp1[1][0].shape == (c_in, c_in) and Wc.shape[1] == c_in and C == Wc.shape[0]):
-            i_s = Ks.index(min(Ks))
-            order = (i_s, 1 - i_s)
-            wqc = torch.cat([torch.cat([wq[i], wq[2 + i]], dim=0) for i in order], dim=0)
-            P["row_chain"] = dict(order=order, wa=ext.row_chain_pack(fp1[0][0]), ba=fp1[0][1].contiguous(),
+            P["row_chain"] = dict(wa=ext.row_chain_pack(fp1[0][0]), ba=fp1[0][1].contiguous(),
                                   wb=ext.row_chain_pack(fp1[1][0]), bb=fp1[1][1].contiguous(),
-                                  wc=ext.row_chain_pack(Wc), bc=P["conv1"][1].contiguous(), wq=ext.row_chain_pack(wqc))
-        # Layer 1 of a keypoint branch is linear in the per-point feature, so it is a GEMM over POINTS for branches
-        # whose J*K neighbour slots outnumber the points (K = 64: 1344 slots > 1024 points) and a GEMM over the
-        # GATHERED slots for the small ones (K = 16: 336 rows instead of 1024).  Branch order inside each block:
-        # (q1, i), (q2, i) for the i's of that kind.
-        P["wq"] = wq  # per branch, order q1s0, q1s1, q2s0, q2s1
+                                  wc=ext.row_chain_pack(Wc), bc=P["conv1"][1].contiguous(), wq=ext.row_chain_pack(P["wq"]))
         P["wc2"] = torch.cat([q[("q2", 0)]["wc"], q[("q2", 1)]["wc"]], dim=0).contiguous()  # (2*128, C)
         P["head_w"] = net.final_mlp[2].weight.detach().squeeze(-1).contiguous()  # (3, 256)
         P["r1"] = (net.r1.linear.weight.detach().squeeze(-1), net.r1.linear.bias.detach(), net.r1._perm.t().contiguous())
         P["r2"] = (net.r2.linear.weight.detach().squeeze(-1), net.r2.linear.bias.detach(), net.r2._perm.t().contiguous())
         self.P, self._key = P, key
         return P
-
-    def _wcat(self, i):
-        """Cache of the per-scale layer-1 feature weights [q1 scale i | q2 scale i] (lives in P: rebuilt with the parameters)."""
-        c = self.P.setdefault("_wcat", {})
-        if i not in c:
-            if isinstance(i, tuple):  # several scales stacked (one GEMM over the points for all of them)
-                c[i] = torch.cat([self._wcat(j) for j in i], dim=0).contiguous()
-            else:
-                c[i] = torch.cat([self.P["wq"][i], self.P["wq"][2 + i]], dim=0).contiguous()
-        return c[i]
 
     def _perm_idx(self, perm, B):
         """(B, J*re) int32 row indices of rearrange_module's token gather (perm (J, re)), cached per batch size."""
@@ -241,7 +228,6 @@ class FastEval:
 
     def _geometry(self, input, flag_dict):
         from hotrack_amd import ext
-        from hotrack_amd import pointnet2_utils as ops
         net = self.net
         P = self.prepare()
         if P is None:
@@ -279,20 +265,14 @@ class FastEval:
         # ---- sa1: 1024 -> 256 centroids, r = 0.1, K = 32, MLP [3 -> 32 -> 32 -> 64] ------------------
         p = P["sa1"]
         S1, K1 = bh.sa1.npoint, bh.sa1.nsample_list[0]
-        # both sampling levels at once: level 2 (FPS over level 1's samples) is level 1's prefix unless an arg-max tied
-        if self.two_level_fps:
-            # sampling level 1 -> ball query level 1 (which also emits the centroids' coordinates) -> tie check ->
-            # sampling level 2 (a no-op launch unless an arg-max tied): no gather launches
-            # ... and the keypoints' kNN lists (sorted by (distance, index): the K = 16 list is the prefix of the K = 64 list) ride
-            # in the launch of sampling level 1, which keeps one compute unit per cloud busy and nothing else
-            qK = [P["q"][("q1", i)]["K"] for i in range(2)]
-            knn_req = (xyz1, max(qK), min(qK) if min(qK) < max(qK) else 0)
-            _, l1_xyz, i_l2, idx1, knn_lists = ext.fps_two_level(xyz2, S1, bh.sa2.npoint, query=(bh.sa1.radius_list[0], K1), knn=knn_req)
-        else:
-            knn_lists = None
-            l1_xyz = ext.gather_rows(xyz2, ops.furthest_point_sample(xyz2, S1))
-            i_l2 = ops.furthest_point_sample(l1_xyz, bh.sa2.npoint)
-            idx1 = ops.ball_query(bh.sa1.radius_list[0], K1, xyz2, l1_xyz)
+        # both sampling levels at once: level 2 (FPS over level 1's samples) is level 1's prefix unless an arg-max tied.
+        # Sampling level 1 -> ball query level 1 (which also emits the centroids' coordinates) -> tie check ->
+        # sampling level 2 (a no-op launch unless an arg-max tied): no gather launches
+        # ... and the keypoints' kNN lists (sorted by (distance, index): the K = 16 list is the prefix of the K = 64 list) ride
+        # in the launch of sampling level 1, which keeps one compute unit per cloud busy and nothing else
+        qK = [P["q"][("q1", i)]["K"] for i in range(2)]
+        knn_req = (xyz1, max(qK), min(qK) if min(qK) < max(qK) else 0)
+        _, l1_xyz, i_l2, idx1, knn_lists = ext.fps_two_level(xyz2, S1, bh.sa2.npoint, query=(bh.sa1.radius_list[0], K1), knn=knn_req)
         return dict(P=P, pts=pts, B=B, N=N, J=J, c_i=c_i, fp1_in=fp1_in, nonfinite=nonfinite, R=R, t=t, xyz2=xyz2, xyz1=xyz1,
                     canon=canon, S1=S1, K1=K1, l1_xyz=l1_xyz, i_l2=i_l2, idx1=idx1, knn_lists=knn_lists)
 
@@ -352,18 +332,13 @@ class FastEval:
         assert c_i == l1_out.shape[2]
         ext.three_nn_interpolate_pm(xyz2, l1_xyz, l1_out, fp1_in[:, :, :c_i])
         q = P["q"]
-        # kNN lists are sorted by (distance, index): the K=16 list is the prefix of the K=64 list -> one search
+        # kNN lists are sorted by (distance, index): the K=16 list is the prefix of the K=64 list -> one search (_geometry)
         Ks = [q[("q1", i)]["K"] for i in range(2)]
         kmin, kmax = min(Ks), max(Ks)
-        if knn_lists is not None:
-            gi, gi_small = knn_lists
-        else:
-            gi, gi_small = ext.knn_indices(kmax, xyz1, xyz2, k2=kmin) if kmin < kmax else (ext.knn_indices(kmax, xyz1, xyz2), None)
+        gi, gi_small = knn_lists
         c_q = q[("q1", 0)]["l3"][0].shape[0]
         c1q = q[("q1", 0)]["l2"][0].shape[1]
         rc = P["row_chain"]
-        # per scale i: neighbour index, the per-point layer-1 feature term (a column block), the coordinates that go with them
-        plan = []
         if self.row_chain and rc is not None and B * N >= 32768 and B <= ext.ROW_CHAIN_MAX_B and gi_small is not None:
             # a batch large enough that the dense work, not the launch count, is what costs: the q branches read the per-point
             # features only through their kNN lists (about 2/3 of a cloud's points for K = 64, 1/4 for K = 16), so fp1, conv1 and
@@ -372,9 +347,6 @@ class FastEval:
             lst, counts = ext.row_lists(gi, gi_small, N)
             a_all = torch.empty((B, N, 4 * c1q), **f32)
             ext.row_chain(fp1_in, lst, counts, rc["wa"], rc["ba"], rc["wb"], rc["bb"], rc["wc"], rc["bc"], rc["wq"], out=a_all)
-            for i, K in enumerate(Ks):
-                j = rc["order"].index(i)
-                plan.append((gi_small if K == kmin else gi, a_all[:, :, 2 * c1q * j:2 * c1q * (j + 1)], xyz2))
         else:
             f = P["fp1_fused"]
             if f is not None:  # both fp1 layers in one launch (pn2x_mlp2_rows): rows [interp | xyz | pad] -> 128 -> 128
@@ -385,10 +357,13 @@ class FastEval:
                     x = _lin_relu(x, W, b)
             src2 = _lin_relu(x, *P["conv1"])  # (B*N, C) per-point backbone features
             # both scales' per-point GEMMs read the same rows -> one GEMM, a column block per scale
-            a_all = _lin(src2, self._wcat((0, 1))).view(B, N, -1)
-            for i, K in enumerate(Ks):
-                idx = gi if K == kmax else (gi_small if K == kmin and gi_small is not None else gi[:, :, :K].contiguous())
-                plan.append((idx, a_all[:, :, 2 * c1q * i:2 * c1q * (i + 1)], xyz2))
+            a_all = _lin(src2, P["wq"]).view(B, N, -1)
+        # per scale i: neighbour index, the per-point layer-1 feature term (a column block), the coordinates that go with them
+        plan = []
+        for i, K in enumerate(Ks):
+            j = P["wq_order"].index(i)
+            idx = gi if K == kmax else (gi_small if K == kmin and gi_small is not None else gi[:, :, :K].contiguous())
+            plan.append((idx, a_all[:, :, 2 * c1q * j:2 * c1q * (j + 1)], xyz2))
         f11 = torch.empty((B, J, 2 * c_q), **f32)
         self._q_scales(ext, "q1", plan, q, xyz1, c1q, 0, None, f11, c_q)
         Wr, br, perm = P["r1"]

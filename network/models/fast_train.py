@@ -17,16 +17,8 @@ The module path (pointnet_utils.py in this directory) remains the general fallba
 """
 from __future__ import annotations
 
-import os
-
 import torch
 import torch.nn.functional as F
-
-
-# ONE switch for "weight gradients of plain linear layers deferred to the grouped end-of-pass launch" (hotrack_amd.linear_dw):
-# FastTrain, the rearrange modules and FastTail all read it here (three separate reads of the environment let a
-# programmatic change switch the path only partly).  HOTRACK_DEFER_WGRAD=0, or fast_train.DEFER_WGRAD = False before a forward.
-DEFER_WGRAD = os.environ.get("HOTRACK_DEFER_WGRAD", "1") != "0"
 
 
 def _w2d(conv):
@@ -53,49 +45,18 @@ class _SplitCols(torch.autograd.Function):
         return (torch.cat(parts, dim=1),) + (None,) * len(ctx.sizes)
 
 
-def _split_first_layer(w, D, has_center):
-    """w (C1, D + 3 [+ Dc]) -> (feature block | None, xyz block, centre block | None)."""
-    sizes = ([D] if D else []) + [3] + ([w.shape[1] - D - 3] if has_center else [])
-    parts = list(_SplitCols.apply(w, *sizes))
-    wf = parts.pop(0) if D else None
-    wx = parts.pop(0)
-    wc = parts.pop(0) if has_center else None
-    return wf, wx, wc
-
-
-class _Linear2Shared(torch.autograd.Function):
-    """(x W1^T, x W2^T) for two weight matrices applied to the SAME rows (the per-point halves of layer 1 of the two keypoint
-    query modules both read the backbone features).  As two independent linears autograd sums their two input gradients with
-    a separate pass over (B*N, C) (23 us at 32 x 1024 x 384); here the second product accumulates into the first (addmm)."""
-
-    @staticmethod
-    def forward(ctx, x, w1, w2):
-        ctx.save_for_backward(x, w1, w2)
-        return torch.mm(x, w1.t()), torch.mm(x, w2.t())
-
-    @staticmethod
-    def backward(ctx, g1, g2):
-        x, w1, w2 = ctx.saved_tensors
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.mm(g1, w1)
-            dx.addmm_(g2, w2)
-        dw1 = torch.mm(g1.t(), x) if ctx.needs_input_grad[1] else None
-        dw2 = torch.mm(g2.t(), x) if ctx.needs_input_grad[2] else None
-        return dx, dw1, dw2
+def _split_first_layer(w, has_center):
+    """First-layer weight of a module without per-point features, w (C1, 3 [+ Dc]) -> (None, xyz block, centre block | None)."""
+    sizes = [3] + ([w.shape[1] - 3] if has_center else [])
+    parts = _SplitCols.apply(w, *sizes)
+    return None, parts[0], parts[1] if has_center else None
 
 
 class FastTrain:
     def __init__(self, net):
         self.net = net
         self.ws = None
-        import os
-        self.use_fused_stacks = os.environ.get("HOTRACK_FUSED_STACKS", "1") != "0"  # 0: round-2 path (library GEMMs + streaming BN)
         self.small_stack_rows = 4096  # stacks with at most this many rows run as unfused layers (8192 lost at batch 64: DESIGN.md 5b)
-
-    @property
-    def defer_wgrad(self) -> bool:
-        return DEFER_WGRAD  # False: every weight gradient a library GEMM inside the pass
 
     @staticmethod
     def supported(net) -> bool:
@@ -119,8 +80,8 @@ class FastTrain:
         # few rows (the group-all sa3 and the two coarse feature-propagation stacks: 4096 - 8192 rows at 32 clouds): a fused layer
         # is a latency chain of 32 - 64 workgroups per launch, and since the weight gradients of plain linears left the pass
         # (linear_dw) the unfused form has only the small input-gradient GEMM on the critical path
-        small = self.defer_wgrad and x2d.shape[0] <= self.small_stack_rows
-        if self.use_fused_stacks and len(convs) > 1 and not small:
+        small = x2d.shape[0] <= self.small_stack_rows
+        if len(convs) > 1 and not small:
             from hotrack_amd import train_stack
             widths = [c.weight.shape[0] for c in convs]
             if train_stack.stack_supported(widths[0], widths[1:]):
@@ -134,13 +95,12 @@ class FastTrain:
             x2d = bn_relu_max(y, max_over, bn, self.ws, conv.bias) if (max_over and i == last) else bn_relu(y, bn, self.ws, conv.bias)
         return x2d
 
-    def _linear(self, x2d, conv, bias=None):
-        """x2d . W^T (+ bias) for a Linear / 1x1 convolution module's weight; the weight gradient is computed by the grouped
-        end-of-pass launch (hotrack_amd.linear_dw) unless HOTRACK_DEFER_WGRAD=0."""
-        if self.defer_wgrad:
-            from hotrack_amd.linear_dw import linear
-            return linear(x2d, conv.weight, bias)
-        return F.linear(x2d, _w2d(conv), bias)
+    @staticmethod
+    def _linear(x2d, conv):
+        """x2d . W^T for a 1x1 convolution module's weight; the weight gradient is computed by the grouped end-of-pass launch
+        (hotrack_amd.linear_dw)."""
+        from hotrack_amd.linear_dw import linear
+        return linear(x2d, conv.weight, None)
 
     def _per_point(self, feat2d, mods, D, stash=None):
         """Per module (first-layer blocks [(None, xyz block, centre block | None) per scale], feat2d . W_f^T): the per-point halves of
@@ -152,42 +112,27 @@ class FastTrain:
         # input gradient of the per-point product is one GEMM (hotrack_amd.linear_dw._PerPoint)
         return [([(None, wx, wc) for wx, wc in b], a, (share, m)) for m, (b, a) in enumerate(zip(blocks, a1f))]
 
-    @staticmethod
-    def _first_layer_blocks(mod, D, has_center):
-        """Per scale (feature block | None, xyz block, centre block | None) of the first-layer weights, and the feature blocks of
-        all scales stacked (the weight of the per-point GEMM)."""
-        w1 = [_split_first_layer(_w2d(convs[0]), D, has_center) for convs in mod.conv_blocks]
-        wf = None
-        if D:
-            wf = w1[0][0] if len(w1) == 1 else torch.cat([w[0] for w in w1], dim=0)
-        return w1, wf
-
     def _sa_scales(self, mod, xyz, cxyz, feat2d, idxs, center2d=None, pre=None, invs=None, feat_stash=None):
         """All scales of one SA module.  xyz (B,N,3), cxyz (B,S,3), feat2d (B*N, D)|None, center2d (B*S, D2)|None ->
-        (B, S, sum C3) point-major.  pre = (w1, a1f2d): the first-layer blocks and the per-point product feat2d wf^T computed by
-        the caller (_Linear2Shared)."""
+        (B, S, sum C3) point-major.  pre = (w1, a1f2d, share): the first-layer blocks, the per-point product feat2d wf^T and where
+        its gradient goes, computed by the caller (_per_point)."""
         from hotrack_amd.train_ops import sa_layer1
         B, N, _ = xyz.shape
         S = cxyz.shape[1]
-        D = 0 if feat2d is None else feat2d.shape[1]
-        a1f = cadd = None
-        a1f_share = None
+        a1f = cadd = a1f_share = None
         if pre is not None:
-            w1, a1f2d = pre[:2]
-            a1f_share = pre[2] if len(pre) > 2 else None
+            w1, a1f2d, a1f_share = pre
             a1f = a1f2d.view(B, N, -1)
-        elif D and self.defer_wgrad:
-            (w1, a1f2d, _), = self._per_point(feat2d, [mod], D, stash=feat_stash)
+        elif feat2d is not None:
+            (w1, a1f2d, _), = self._per_point(feat2d, [mod], feat2d.shape[1], stash=feat_stash)
             a1f = a1f2d.view(B, N, -1)
-        else:
-            w1, wf = self._first_layer_blocks(mod, D, center2d is not None)
-            if D:
-                a1f = F.linear(feat2d, wf).view(B, N, -1)
+        else:  # no per-point features (sa1): xyz [+ centre] blocks only
+            w1 = [_split_first_layer(_w2d(convs[0]), center2d is not None) for convs in mod.conv_blocks]
         if center2d is not None:
             wc = w1[0][2] if len(w1) == 1 else torch.cat([w[2] for w in w1], dim=0)
             cadd = F.linear(center2d, wc).view(B, S, -1)
-        aux = {} if self.use_fused_stacks else None  # relative coordinates -> the stacks, d(W_xyz) <- the stacks (train_ops.sa_layer1)
-        if aux is not None and a1f_share is not None and a1f_share[0] is not None:
+        aux = {}  # relative coordinates -> the stacks, d(W_xyz) <- the stacks (train_ops.sa_layer1)
+        if a1f_share is not None and a1f_share[0] is not None:
             aux["a1f_share"] = a1f_share
         y1s = sa_layer1(a1f, cadd, xyz, cxyz, idxs, [w[1] for w in w1], invs=invs, aux=aux,
                         ws=self.ws)
@@ -199,14 +144,12 @@ class FastTrain:
             for i, y1 in enumerate(y1s):
                 K = idxs[i].shape[2]
                 h = self._stack(y1.view(B * S * K, -1), mod.conv_blocks[i], mod.bn_blocks[i], first_done=True, max_over=K,
-                                aux=None if aux is None else (aux, i))
+                                aux=(aux, i))
                 outs.append(h.view(B, S, -1))
         return outs[0] if len(outs) == 1 else torch.cat(outs, dim=2)
 
     def _pair_stacks(self, mod, y1s, idxs, aux):
         """The two scales of a module as ONE pair of fused stacks when their layer widths agree and the kernels cover them."""
-        if not self.use_fused_stacks:
-            return None
         from hotrack_amd import train_stack
         widths = [[c.weight.shape[0] for c in convs] for convs in mod.conv_blocks]
         if widths[0] != widths[1] or len(widths[0]) < 2 or not train_stack.stack_supported(widths[0][0], widths[0][1:]):
@@ -218,8 +161,7 @@ class FastTrain:
             layers += [train_stack.Layer(c.weight, bn, c.bias) for c, bn in zip(convs[1:], bns[1:])]
             stacks.append((y1.view(-1, y1.shape[-1]), layers, idxs[i].shape[2]))
         (ya, la, ka), (yb, lb, kb) = stacks
-        return train_stack.mlp_stack_pair(ya, yb, la, lb, self.ws, ka, kb, aux_a=None if aux is None else (aux, 0),
-                                          aux_b=None if aux is None else (aux, 1), cat=True)
+        return train_stack.mlp_stack_pair(ya, yb, la, lb, self.ws, ka, kb, aux_a=(aux, 0), aux_b=(aux, 1), cat=True)
 
     def _fp(self, mod, xyz1, xyz2, points1, points2, extra=None, nn3=None):
         """xyz1 (B,N,3), xyz2 (B,S,3), points1 (B,N,D1)|None, points2 (B,S,D2) -> (B*N, D') rows.
@@ -237,15 +179,12 @@ class FastTrain:
         if extra is not None:
             convs.append(extra[0])
             bns.append(extra[1])
-        if self.defer_wgrad and self.use_fused_stacks:
-            # layer 1 over [skip | interpolated] as the sum of its column blocks' products: no concatenation forward, no copy of a
-            # gradient slice backward; a broadcast per-cloud feature (fp3: the global feature) is multiplied once per cloud
-            from hotrack_amd.linear_dw import linear_blocks
-            blocks = [] if points1 is None else [points1.reshape(B * N, -1)]
-            blocks.append((points2.reshape(B, -1), N) if xyz2.shape[1] == 1 else interp.reshape(B * N, -1))
-            return self._stack(linear_blocks(blocks, convs[0].weight), convs, bns, first_done=True)
-        x = interp if points1 is None else torch.cat([points1, interp], dim=2)
-        return self._stack(x.reshape(B * N, -1), convs, bns)
+        # layer 1 over [skip | interpolated] as the sum of its column blocks' products: no concatenation forward, no copy of a
+        # gradient slice backward; a broadcast per-cloud feature (fp3: the global feature) is multiplied once per cloud
+        from hotrack_amd.linear_dw import linear_blocks
+        blocks = [] if points1 is None else [points1.reshape(B * N, -1)]
+        blocks.append((points2.reshape(B, -1), N) if xyz2.shape[1] == 1 else interp.reshape(B * N, -1))
+        return self._stack(linear_blocks(blocks, convs[0].weight), convs, bns, first_done=True)
 
     # ------------------------------------------------------------------------------------------------------------------
     def geometry(self, xyz: torch.Tensor, kp: torch.Tensor, with_inverse: bool = True) -> dict:
@@ -310,18 +249,14 @@ class FastTrain:
         from hotrack_amd.linear_dw import GradStash, tap
         # l1_feat / l2_feat each feed the next level AND a skip connection: the later consumer reads them through tap(), the
         # earlier one's product sums both input gradients (linear_dw: no element-wise add launch in the backward)
-        st1, st2 = (GradStash(), GradStash()) if (self.defer_wgrad and self.use_fused_stacks) else (None, None)
+        st1, st2 = GradStash(), GradStash()
         l1_feat = self._sa_scales(bh.sa1, xyz, l1_xyz, None, [geo["idx1"]])                            # (B,S1,64)
         l2_feat = self._sa_scales(bh.sa2, l1_xyz, l2_xyz, l1_feat.reshape(B * S1, -1), [geo["idx2"]],
                                   invs=None if geo["inv2"] is None else [geo["inv2"]], feat_stash=st1)  # (B,S2,128)
         # group-all: [xyz | feat], centre = origin (not subtracted)
-        if self.defer_wgrad and self.use_fused_stacks:
-            from hotrack_amd.linear_dw import linear_blocks
-            y1 = linear_blocks([l2_xyz.reshape(B * S2, 3), l2_feat.reshape(B * S2, -1)], bh.sa3.mlp_convs[0].weight, stashes=[None, st2])
-            l3 = self._stack(y1, bh.sa3.mlp_convs, bh.sa3.mlp_bns, first_done=True, max_over=S2).view(B, 1, -1)  # (B,1,512)
-        else:
-            x = torch.cat([l2_xyz, l2_feat], dim=2).view(B * S2, -1)
-            l3 = self._stack(x, bh.sa3.mlp_convs, bh.sa3.mlp_bns, max_over=S2).view(B, 1, -1)
+        from hotrack_amd.linear_dw import linear_blocks
+        y1 = linear_blocks([l2_xyz.reshape(B * S2, 3), l2_feat.reshape(B * S2, -1)], bh.sa3.mlp_convs[0].weight, stashes=[None, st2])
+        l3 = self._stack(y1, bh.sa3.mlp_convs, bh.sa3.mlp_bns, first_done=True, max_over=S2).view(B, 1, -1)  # (B,1,512)
         l2_out = self._fp(bh.fp3, l2_xyz, l2_xyz[:, :1], tap(l2_feat, st2), l3).view(B, S2, -1)
         l1_out = self._fp(bh.fp2, l1_xyz, l2_xyz, tap(l1_feat, st1), l2_out, nn3=geo["fp2"]).view(B, S1, -1)
         # fp1 (skip = xyz) and the backbone's conv1 / bn1 as one stack [131 -> 128 -> 128 -> C]
@@ -331,14 +266,8 @@ class FastTrain:
 
         # ---- q1 -> r1 -> q2 -> r2 around the J keypoints; one kNN search for both neighbourhood sizes ------------------
         idxs, invs = geo["knn"], geo["knn_inv"]
-        # the per-point halves of both modules' first layers read src2: one Function, one input gradient (_Linear2Shared)
-        if self.defer_wgrad:
-            (w1_q1, a1f_q1, sh_q1), (w1_q2, a1f_q2, sh_q2) = self._per_point(src2, [net.q1, net.q2], C)
-        else:
-            sh_q1 = sh_q2 = None
-            w1_q1, wf_q1 = self._first_layer_blocks(net.q1, C, False)
-            w1_q2, wf_q2 = self._first_layer_blocks(net.q2, C, True)
-            a1f_q1, a1f_q2 = _Linear2Shared.apply(src2, wf_q1, wf_q2)
+        # the per-point halves of both modules' first layers read src2: one Function, one input gradient (linear_dw._PerPoint)
+        (w1_q1, a1f_q1, sh_q1), (w1_q2, a1f_q2, sh_q2) = self._per_point(src2, [net.q1, net.q2], C)
         # both modules gather through the same neighbour lists: inverted once (geometry) for the two backward scatters
         f11 = self._sa_scales(net.q1, xyz, kp, src2, idxs, pre=(w1_q1, a1f_q1, sh_q1), invs=invs)             # (B,J,C)
         f12 = self._rearrange(net.r1, f11)                                                                 # (B*J, C)
@@ -361,10 +290,8 @@ class FastTrain:
             g = gather_rows(tok, cache[0], cache[1])  # (B, J*re, C); backward: one segment-sum launch
         else:
             g = tok.index_select(1, cache[0][0].long())
-        if DEFER_WGRAD:
-            from hotrack_amd.linear_dw import linear
-            return linear(g.view(B * J, mod.re * C), mod.linear.weight, mod.linear.bias)
-        return F.linear(g.view(B * J, mod.re * C), mod.linear.weight.squeeze(-1), mod.linear.bias)
+        from hotrack_amd.linear_dw import linear
+        return linear(g.view(B * J, mod.re * C), mod.linear.weight, mod.linear.bias)
 
 
 class FastTail:
@@ -444,13 +371,8 @@ class FastTail:
         seed_used = torch.empty(1, dtype=torch.int64, device=dev)
         grads = T.TailGrads(dev, 14 * C + 2 * H + Hf + 3 * Hf + 3)
         pd = lambda m: float(m.p) if m.training else 0.0
-        if DEFER_WGRAD:
-            from hotrack_amd.linear_dw import GradStash, linear as lin, tap
-            sa, sb = GradStash(), GradStash()  # h / h2 feed their block's first product AND its residual: one input gradient each
-        else:
-            lin = lambda x, w, stash=None: F.linear(x, w.view(w.shape[0], -1))
-            tap = lambda x, stash: x
-            sa = sb = None
+        from hotrack_amd.linear_dw import GradStash, linear as lin, tap
+        sa, sb = GradStash(), GradStash()  # h / h2 feed their block's first product AND its residual: one input gradient each
         h = T.ln(rows, s11.norm1, c11.norm1, grads, seed_dev=self.seed, seed_out=seed_used)
         d = T.relu_dropout(lin(h, c11.linear1.weight, stash=sa), c11.linear1.bias, pd(c11.dropout2), 1, seed_used, grads)
         h2 = T.ln(tap(h, sa), c11.norm2, c3.norm1, grads, y=lin(d, c11.linear2.weight), bias=c11.linear2.bias, p=pd(c11.dropout3), site=2, seed_in=seed_used)

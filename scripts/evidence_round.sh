@@ -14,7 +14,6 @@ python scripts/bench_ops.py --out $O/${tag}_bench_ops.json > /dev/null 2>&1 || p
 python scripts/bench_stress.py --out $O/${tag}_stress.json > $O/${tag}_stress.log 2>&1
 python scripts/bench_latency.py > $O/${tag}_bench_latency.json 2>/dev/null
 python scripts/bench_train.py --graph > $O/${tag}_bench_train_graph.json 2>/dev/null
-HOTRACK_FUSED_STACKS=0 python scripts/bench_train.py --graph > $O/${tag}_bench_train_graph_unfused_stacks.json 2>/dev/null
 python scripts/bench_train.py > $O/${tag}_bench_train_eager.json 2>/dev/null
 python scripts/probes/tg_bench.py --iters 10 > $O/${tag}_tg_bench.json 2>/dev/null
 cd /tmp && export TMPDIR=/tmp

@@ -16,6 +16,77 @@ def _declared(header):
     return sorted(set(re.findall(r"\b(pn2[xs]?_[a-z0-9_]+)\s*\(", src)))
 
 
+def _prototypes():
+    """{name: [parameter declarations]} of every entry the three headers declare (comments stripped)."""
+    out = {}
+    for header in ("pn2_hip.h", "pn2_ext.h", "pn2_sdf.h"):
+        src = open(os.path.join(ROOT, "include", header)).read()
+        src = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", src, flags=re.S))
+        for m in re.finditer(r"\b(pn2[xs]?_\w+)\s*\(([^()]*)\)\s*;", src):
+            params = [p.strip() for p in m.group(2).split(",")]
+            out[m.group(1)] = [] if params in ([""], ["void"]) else params
+    return out
+
+
+def _called_entries():
+    """Entries the Python bindings call: `lib.<name>(...)` directly, or `lib.<name>` handed to pointnet2_hip._call."""
+    called = set()
+    for base in ("hotrack_amd", "network"):
+        for dp, _, files in os.walk(os.path.join(ROOT, base)):
+            for f in files:
+                if f.endswith(".py"):
+                    called |= set(re.findall(r"lib\.(pn2[xs]?_\w+)\s*[(,]", open(os.path.join(dp, f)).read()))
+    return called
+
+
+def test_every_extension_entry_has_a_caller():
+    """An entry that nothing calls is dead ABI surface: every pn2x_* the extension header declares is called by the bindings."""
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "pn2_ext.h")).read(), flags=re.S)
+    declared = set(re.findall(r"\b(pn2x_\w+)\s*\(", src))
+    assert declared
+    assert sorted(declared - _called_entries()) == []
+
+
+def test_bound_argtypes_match_the_header_prototypes():
+    """Every entry the bindings call has argtypes, and each list matches the header prototype element by element (int, long,
+    float, double or pointer) -- a renamed or re-signatured entry cannot slip through with a stale table."""
+    import importlib
+    for m in ("pointnet2_hip", "ext", "train_ops", "train_stack", "linear_dw", "tail_train", "optim", "sdf"):
+        importlib.import_module("hotrack_amd." + m)
+    from hotrack_amd.pointnet2_hip import _lib
+    c = ctypes
+
+    def c_kind(param):
+        if "*" in param:
+            return "pointer"
+        words = re.sub(r"\b(const|unsigned)\b", "", param).split()[:-1]  # type words without the parameter name
+        return {"int": "int", "long": "long", "float": "float", "double": "double"}[words[0]]
+
+    def py_kind(t):
+        if t in (c.c_int, c.c_int32):
+            return "int"
+        if t in (c.c_long, c.c_longlong, c.c_int64):
+            return "long"
+        if t in (c.c_float, c.c_double):
+            return {c.c_float: "float", c.c_double: "double"}[t]
+        if t in (c.c_void_p, c.c_char_p) or issubclass(t, c._Pointer):
+            return "pointer"
+        raise AssertionError(t)
+
+    protos = _prototypes()
+    bad = []
+    for name in sorted(_called_entries()):
+        assert name in protos, f"{name} is called but no header declares it"
+        at = getattr(_lib, name).argtypes
+        if at is None:
+            bad.append(f"{name}: no argtypes")
+            continue
+        want, got = [c_kind(p) for p in protos[name]], [py_kind(t) for t in at]
+        if want != got:
+            bad.append(f"{name}: header {want} != argtypes {got}")
+    assert not bad, "\n".join(bad)
+
+
 def test_headers_declare_the_reference_surface():
     names = _declared("pn2_hip.h")
     for n in ("pn2_ball_query", "pn2_group_points", "pn2_group_points_grad", "pn2_gather_points", "pn2_gather_points_grad",
@@ -29,7 +100,7 @@ def test_library_exports_every_declared_symbol(hip_lib_path):
         for name in _declared(header):
             assert hasattr(lib, name), f"{name} declared in {header} but not exported"
     lib.pn2_abi_version.restype = ctypes.c_int
-    assert lib.pn2_abi_version() >= 1
+    assert lib.pn2_abi_version() == 2  # 2: the superseded pn2x_* shims removed, their successors renamed
     lib.pn2_strerror.restype = ctypes.c_char_p
     assert b"NULL" in lib.pn2_strerror(-2)
 

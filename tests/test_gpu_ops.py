@@ -376,7 +376,7 @@ def test_ball_query_picks_matches_gather_then_query():
 
 
 def test_ball_query_tie_check_colaunch_equals_separate_launches(monkeypatch):
-    """pn2x_ball_query_picks_ties == pn2x_ball_query_picks2 + pn2x_fps_prefix_ties: neighbour lists, centroid coordinates and (through
+    """pn2x_ball_query_picks_ties == pn2x_ball_query_picks + pn2x_fps_prefix_ties: neighbour lists, centroid coordinates and (through
     the second sampling level they steer) the tie flags, on tie-free and tied clouds, one and two centroids per wave."""
     from _cases import cloud
     from hotrack_amd import ext, pointnet2_utils as ops
