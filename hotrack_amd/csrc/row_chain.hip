@@ -18,16 +18,18 @@
 // Work split: the persistent grid divides the GLOBAL row work (both lists of all clouds, small-K rows weighted 31 : 20 by
 // their FLOPs) into equal contiguous shares of 16-row groups; a workgroup runs its share as tiles of up to 64 rows.
 // Per tile, all four layers on the fp32 matrix cores (v_mfma_f32_16x16x4_f32, exact fp32) with the activations in LDS
-// and the weights streamed from L2 straight into registers (pre-arranged by the caller so that one wave's 16-byte loads
-// cover 1 KiB contiguously).  Transposed products (D^T = W X^T) make every lane own four consecutive output channels of
-// one row: the results go to LDS / HBM as 16-byte stores.
+// and the weights streamed from L2 straight into registers (the shared core and its layouts: mfma_rows.h).
 #include "pn2_common.h"
+#include "mfma_rows.h"
 #include "../../include/pn2_ext.h"
 
 namespace pn2 {
 namespace rchain {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using mrows::f32x4;
+using mrows::init_bias;
+using mrows::mm;
+using mrows::relu_to_lds;
 
 constexpr int CH = 128, CC = 384, CQ = 512;  // fp1 width, conv1 width, the four scales' layer-1 width
 constexpr int KX = 144;                      // fp1 layer 1: 128 features + 3 coordinates, zero-padded to 9 k-groups of 16
@@ -44,63 +46,6 @@ struct ChainArgs {
     const float *wa, *ba, *wb, *bb, *wc, *bc, *wq;
     float *out;
 };
-
-// acc[nt][mt] += W[tile nt] . X[rows of m-tile mt]^T over KG k-groups of 16.  wp: packed weights of the first n-tile
-// ([n-tile][k-group][lane][4], KG k-groups per n-tile); xs: LDS rows, ld floats apart.  Lane l supplies, in k-step s of a
-// k-group, W[n0 + l%16][16 kg + 4 (l/16) + s] and X[m0 + l%16][16 kg + 4 (l/16) + s]: one 16-byte load of each per k-group.
-template <int NT, int MT, int KG, int LD>
-__device__ __forceinline__ void mm(f32x4 (&acc)[NT][MT], const float *__restrict__ wp, const float *xs, int lane) {
-    const f32x4 *w4 = reinterpret_cast<const f32x4 *>(wp) + lane;
-    const float *xr = xs + (lane & 15) * LD + 4 * (lane >> 4);
-    f32x4 w[2][NT], x[2][MT];
-    auto load = [&](int kg, int slot) {
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) w[slot][nt] = w4[(nt * KG + kg) * 64];
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) x[slot][mt] = *reinterpret_cast<const f32x4 *>(xr + mt * 16 * LD + 16 * kg);
-    };
-    auto step = [&](int slot) {
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt)
-                    acc[nt][mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[slot][nt][s], x[slot][mt][s], acc[nt][mt], 0, 0, 0);
-    };
-    load(0, 0);
-    int kg = 0;
-#pragma unroll 1
-    for (; kg + 2 <= KG; kg += 2) {
-        load(kg + 1, 1);
-        step(0);
-        if (kg + 2 < KG) load(kg + 2, 0);
-        step(1);
-    }
-    if constexpr (KG & 1) step(0);
-}
-
-template <int NT, int MT>
-__device__ __forceinline__ void init_bias(f32x4 (&acc)[NT][MT], const float *__restrict__ bias, int nt0, int lane) {
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        const f32x4 b = *reinterpret_cast<const f32x4 *>(bias + (nt0 + nt) * 16 + 4 * (lane >> 4));
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) acc[nt][mt] = b;
-    }
-}
-
-template <int NT, int MT>
-__device__ __forceinline__ void relu_to_lds(const f32x4 (&acc)[NT][MT], float *dst, int ld, int nt0, int lane) {
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-            const f32x4 v = acc[nt][mt];
-            *reinterpret_cast<f32x4 *>(dst + (mt * 16 + (lane & 15)) * ld + (nt0 + nt) * 16 + 4 * (lane >> 4)) =
-                (f32x4){fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)};
-        }
-}
 
 struct Smem {
     int *rows;       // [64] global row (b * N + point) of each tile row, -1 past the end

@@ -766,3 +766,78 @@ def row_chain(x: torch.Tensor, lst: torch.Tensor, counts: torch.Tensor, wa, ba, 
                                      _native._ptr(wq, "wq", f32, 512 * 384), out.data_ptr(), out.stride(1), int(grid),
                                      _native._stream(x)), "row_chain")
     return out
+
+
+# ---- sa3 and fp3 as row-tiled layer chains on the large-batch route (include/pn2_ext.h: pn2x_sa3_chain, pn2x_fp3_chain) ----
+_lib.pn2x_sa3_chain_supported.argtypes = [_ci] * 5
+_lib.pn2x_sa3_chain_supported.restype = _ci
+_lib.pn2x_sa3_chain.argtypes = [_ci, _ci, _vp, _ci] + [_vp] * 7 + [_vp]
+_lib.pn2x_sa3_chain.restype = _ci
+_lib.pn2x_fp3_chain_supported.argtypes = [_ci] * 5
+_lib.pn2x_fp3_chain_supported.restype = _ci
+_lib.pn2x_fp3_chain.argtypes = [_ci, _ci, _vp, _ci] + [_vp] * 6 + [_vp, _ci, _vp]
+_lib.pn2x_fp3_chain.restype = _ci
+MID_CHAIN_TILE = 32  # rows per tile of pn2x_sa3_chain / pn2x_fp3_chain; each tile writes one partial maximum row
+
+
+def sa3_chain_supported(s: int, c_in: int, c1: int, c2: int, c3: int) -> bool:
+    return bool(_lib.pn2x_sa3_chain_supported(s, c_in, c1, c2, c3))
+
+
+def fp3_chain_supported(s: int, c_l2: int, c_l3: int, c1: int, c2: int) -> bool:
+    return bool(_lib.pn2x_fp3_chain_supported(s, c_l2, c_l3, c1, c2))
+
+
+def _chain_rows(x: torch.Tensor, name: str, min_cols: int):
+    if x.dim() != 3 or not x.is_cuda or x.dtype != torch.float32 or x.stride(2) != 1 or x.shape[2] < min_cols or \
+            x.stride(0) != x.shape[1] * x.stride(1):
+        raise TypeError(f"{name}: expected a (B,S,>={min_cols}) float32 GPU tensor with contiguous rows, got {tuple(x.shape)} {x.stride()}")
+    return x.shape[0], x.shape[1]
+
+
+def sa3_chain(x: torch.Tensor, w1, b1, w2, b2, w3, b3, part: torch.Tensor = None) -> torch.Tensor:
+    """Per-tile maxima of sa3 (pn2x_sa3_chain): x (B,S,>=132) [l2_feat | l2_xyz | pad] rows, weights packed by row_chain_pack
+    (w1: (128, 131) [features | xyz]; w2 (128,128); w3 (512,128)) with their biases.  -> part (B, S/32, 512); the max over
+    its last-but-one axis is sa3's output."""
+    B, S = _chain_rows(x, "sa3_chain", 132)
+    T = MID_CHAIN_TILE
+    if S % T:
+        raise ValueError(f"sa3_chain: S = {S} is not a multiple of {T}")
+    f32 = torch.float32
+    if part is None:
+        part = torch.empty((B, S // T, 512), dtype=f32, device=x.device)
+    if tuple(part.shape) != (B, S // T, 512) or not part.is_contiguous() or part.dtype != f32:
+        raise ValueError(f"sa3_chain: part must be a contiguous (B, S/{T}, 512) float32 tensor")
+    with torch.cuda.device(x.device):
+        _native._check(_native._call(_lib.pn2x_sa3_chain, "sa3_chain_kernel", None, B, S, x.data_ptr(), x.stride(1),
+                                     _native._ptr(w1, "w1", f32, 128 * 144), _native._ptr(b1, "b1", f32, 128),
+                                     _native._ptr(w2, "w2", f32, 128 * 128), _native._ptr(b2, "b2", f32, 128),
+                                     _native._ptr(w3, "w3", f32, 512 * 128), _native._ptr(b3, "b3", f32, 512), part.data_ptr(),
+                                     _native._stream(x)), "sa3_chain")
+    return part
+
+
+def fp3_chain(x: torch.Tensor, part: torch.Tensor, wgt, bg, wa, wf, bf, out: torch.Tensor = None) -> torch.Tensor:
+    """fp3 over the level-2 rows (pn2x_fp3_chain): out[b, r] = relu(Wf relu(Wa x[b, r, :128] + Wg l3[b] + bg) + bf) with
+    l3[b] = part[b].max(0) (part from sa3_chain).  x (B,S,>=128) rows with contiguous columns; wgt = Wg^T (512, 256)
+    contiguous; wa (256, 128) and wf (256, 256) packed by row_chain_pack.  out (B,S,>=256)."""
+    B, S = _chain_rows(x, "fp3_chain", 128)
+    T = MID_CHAIN_TILE
+    if S % T:
+        raise ValueError(f"fp3_chain: S = {S} is not a multiple of {T}")
+    f32 = torch.float32
+    if out is None:
+        out = torch.empty((B, S, 256), dtype=f32, device=x.device)
+    _chain_rows(out, "fp3_chain: out", 256)
+    if out.shape[:2] != (B, S):
+        raise ValueError("fp3_chain: out must be (B,S,>=256)")
+    if tuple(part.shape) != (B, S // T, 512) or not part.is_contiguous() or part.dtype != f32:
+        raise ValueError(f"fp3_chain: part must be a contiguous (B, S/{T}, 512) float32 tensor")
+    if tuple(wgt.shape) != (512, 256):
+        raise ValueError("fp3_chain: wgt must be Wg^T, (512, 256)")
+    with torch.cuda.device(x.device):
+        _native._check(_native._call(_lib.pn2x_fp3_chain, "fp3_chain_kernel", None, B, S, x.data_ptr(), x.stride(1), part.data_ptr(),
+                                     _native._ptr(wgt, "wgt", f32, 512 * 256), _native._ptr(bg, "bg", f32, 256),
+                                     _native._ptr(wa, "wa", f32, 256 * 128), _native._ptr(wf, "wf", f32, 256 * 256),
+                                     _native._ptr(bf, "bf", f32, 256), out.data_ptr(), out.stride(1), _native._stream(x)), "fp3_chain")
+    return out

@@ -299,6 +299,35 @@ int pn2x_row_chain(int b, int n, const float *x, int ldx, const int *list, const
                    int grid, void *stream);
 
 /*
+ * sa3 and fp3 of the backbone over the b * s level-2 rows, as row-tiled layer chains (hotrack_amd/csrc/mid_chain.hip).
+ * A workgroup runs one tile of 32 rows of one cloud (r = c * s + i for cloud c, row i); s must be a multiple of 32.
+ * Weights are BatchNorm-folded and come in the kernels' operand layout (hotrack_amd/ext.py: row_chain_pack: k padded to a
+ * multiple of 16, [n/16][k/16][64][4]); biases plain.  Row strides are multiples of 4 floats, every pointer 16-byte aligned.
+ * Exact fp32 (v_mfma_f32_16x16x4_f32); summation order differs from a GEMM library.  No atomics: results do not depend on
+ * the order in which tiles run.  No host sync (capturable).  Errors: PN2_EINVAL for a bad size, stride, s % 32 != 0 or
+ * a misaligned pointer, PN2_ERANGE for b * s >= 2^31, PN2_ENULL for a NULL pointer; b == 0 returns PN2_OK and touches
+ * nothing.  Arguments are checked before any device work.
+ *
+ * pn2x_sa3_chain: for tile t (rows 32 t .. 32 t + 31),
+ *     h1 = relu(W1 [x[r, 0:128] | x[r, 128:131]] + b1)   h2 = relu(W2 h1 + b2)   part[t, :] = max over the tile's rows r of
+ *     relu(W3 h2 + b3)
+ * with W1 (128, 131), W2 (128, 128), W3 (512, 128).  x rows ldx >= 132 floats apart (x[r, 131] is ignored); part is
+ * contiguous (b * s / 32, 512) = (b, s / 32, 512): the max over a cloud's s / 32 rows of part is its sa3 output.
+ *
+ * pn2x_fp3_chain: for every row r of cloud c,
+ *     l3 = max over part[c, :, :]   g = Wg l3 + bg   h = relu(Wa x[r, 0:128] + g)   out[r, 0:256] = relu(Wf h + bf)
+ * with wgt = Wg^T (512, 256) contiguous (plain layout), Wa (256, 128) and Wf (256, 256) packed.  x rows ldx >= 128 floats
+ * apart, out rows ldo >= 256 apart; columns [0, 256) of the b * s out rows are written, nothing else.  Each tile computes
+ * its cloud's g itself (the two launches do not wait on each other's workgroups).
+ */
+int pn2x_sa3_chain_supported(int s, int c_in, int c1, int c2, int c3);
+int pn2x_sa3_chain(int b, int s, const float *x, int ldx, const float *w1, const float *b1, const float *w2, const float *b2,
+                   const float *w3, const float *b3, float *part, void *stream);
+int pn2x_fp3_chain_supported(int s, int c_l2, int c_l3, int c1, int c2);
+int pn2x_fp3_chain(int b, int s, const float *x, int ldx, const float *part, const float *wgt, const float *bg, const float *wa,
+                   const float *wf, const float *bf, float *out, int ldo, void *stream);
+
+/*
  * ---- training-mode building blocks on point-major activations (hotrack_amd/csrc/train_ops.hip) --------------------------
  * The reference trains every grouped MLP as Conv2d(1x1) + BatchNorm2d + ReLU on channel-major (B, C, S, K) tensors
  * (pointnet_utils.py:399-403, :460-462, :504-506, :577-581).  A 1x1 convolution is a GEMM over all R = B*S*K positions

@@ -181,12 +181,31 @@ class FastEval:
             P["row_chain"] = dict(wa=ext.row_chain_pack(fp1[0][0]), ba=fp1[0][1].contiguous(),
                                   wb=ext.row_chain_pack(fp1[1][0]), bb=fp1[1][1].contiguous(),
                                   wc=ext.row_chain_pack(Wc), bc=P["conv1"][1].contiguous(), wq=ext.row_chain_pack(P["wq"]))
+        # sa3 and fp3 as two row-tiled chains over the level-2 rows (ext.sa3_chain / ext.fp3_chain): weights in the kernels' operand
+        # layout, fp3's per-cloud half transposed for the tiles' own g product
+        P["mid_chain"] = None
+        S2 = bh.sa2.npoint
+        pf = P["fp3"]
+        if (len(sa3) == 3 and len(pf["rest"]) == 1 and sa3[0][0].shape[1] == c_l2 + 3
+                and ext.sa3_chain_supported(S2, c_l2, sa3[0][0].shape[0], sa3[1][0].shape[0], sa3[2][0].shape[0])
+                and sa3[1][0].shape[1] == sa3[0][0].shape[0] and sa3[2][0].shape[1] == sa3[1][0].shape[0]
+                and ext.fp3_chain_supported(S2, pf["wa"].shape[1], pf["wb"].shape[1], pf["wa"].shape[0], pf["rest"][0][0].shape[0])
+                and pf["wb"].shape[1] == sa3[2][0].shape[0] and pf["rest"][0][0].shape[1] == pf["wa"].shape[0]):
+            P["mid_chain"] = dict(sa3=[t for W, b in sa3 for t in (ext.row_chain_pack(W), b.contiguous())],
+                                  wgt=pf["wb"].t().contiguous(), bg=pf["b"].contiguous(), wa=ext.row_chain_pack(pf["wa"]),
+                                  wf=ext.row_chain_pack(pf["rest"][0][0]), bf=pf["rest"][0][1].contiguous())
         P["wc2"] = torch.cat([q[("q2", 0)]["wc"], q[("q2", 1)]["wc"]], dim=0).contiguous()  # (2*128, C)
         P["head_w"] = net.final_mlp[2].weight.detach().squeeze(-1).contiguous()  # (3, 256)
         P["r1"] = (net.r1.linear.weight.detach().squeeze(-1), net.r1.linear.bias.detach(), net.r1._perm.t().contiguous())
         P["r2"] = (net.r2.linear.weight.detach().squeeze(-1), net.r2.linear.bias.detach(), net.r2._perm.t().contiguous())
         self.P, self._key = P, key
         return P
+
+    def _large_batch(self, B, N) -> bool:
+        """A batch large enough that the dense work, not the launch count, is what costs: the row-tiled chains (ext.row_chain,
+        ext.sa3_chain / ext.fp3_chain) replace the library GEMMs.  FastEval.row_chain = False forces the library route."""
+        from hotrack_amd import ext
+        return self.row_chain and B * N >= 32768 and B <= ext.ROW_CHAIN_MAX_B
 
     def _perm_idx(self, perm, B):
         """(B, J*re) int32 row indices of rearrange_module's token gather (perm (J, re)), cached per batch size."""
@@ -302,24 +321,32 @@ class FastEval:
         l2_feat = sa3_in[:, :, :c_l2]
         ext.sa_mlp_max(idx2, *p["l2"], *p["l3"], a1f=a1f, xyz=l1_xyz, cxyz=l2_xyz, wx=p["wx"], b1=p["b1"], out=l2_feat)
 
-        # ---- sa3: group-all [feat | xyz] (weights permuted to match) -> MLP -> max over the 128 points -----------
-        x = sa3_in.view(B * S2, c_l2 + 4)[:, :c_l2 + 3]
-        for W, b in P["sa3"]:
-            x = _lin_relu(x, W, b)
-        l3 = ext.max_rows(x.view(B, S2, -1))  # (B,512)
-
-        # ---- fp3: S == 1 -> the global feature is broadcast; first layer split so it is applied once per cloud
-        p = P["fp3"]
-        g = _lin(l3, p["wb"], p["b"])  # (B,256) per-cloud half, bias included
-        if B == 1:  # one cloud: the per-cloud half IS the layer's bias vector (one launch less in the tracking loop; same operations)
-            h = _lin_relu(sa3_in.view(S2, c_l2 + 4)[:, :c_l2], p["wa"], g.view(-1)).view(B, S2, -1)
+        large = self._large_batch(B, N)
+        mc = P["mid_chain"]
+        if large and mc is not None:
+            # ---- sa3 + fp3 as two row-tiled chains over the level-2 rows (tiles of 32 rows of one cloud): sa3's tiles write
+            # their partial maxima, fp3's tiles take their cloud's max, its per-cloud half g and both fp3 layers -----------
+            part = ext.sa3_chain(sa3_in, *mc["sa3"])
+            l2_out = ext.fp3_chain(sa3_in, part, mc["wgt"], mc["bg"], mc["wa"], mc["wf"], mc["bf"])
         else:
-            h = _lin(sa3_in.view(B * S2, c_l2 + 4)[:, :c_l2], p["wa"]).view(B, S2, -1)
-            ext.bias_act_pm_(h, g, rows_per_bias=S2, relu=True)
-        x = h.view(B * S2, -1)
-        for W, b in p["rest"]:
-            x = _lin_relu(x, W, b)
-        l2_out = x.view(B, S2, -1)
+            # ---- sa3: group-all [feat | xyz] (weights permuted to match) -> MLP -> max over the 128 points -----------
+            x = sa3_in.view(B * S2, c_l2 + 4)[:, :c_l2 + 3]
+            for W, b in P["sa3"]:
+                x = _lin_relu(x, W, b)
+            l3 = ext.max_rows(x.view(B, S2, -1))  # (B,512)
+
+            # ---- fp3: S == 1 -> the global feature is broadcast; first layer split so it is applied once per cloud
+            p = P["fp3"]
+            g = _lin(l3, p["wb"], p["b"])  # (B,256) per-cloud half, bias included
+            if B == 1:  # one cloud: the per-cloud half IS the layer's bias vector (one launch less in the tracking loop; same operations)
+                h = _lin_relu(sa3_in.view(S2, c_l2 + 4)[:, :c_l2], p["wa"], g.view(-1)).view(B, S2, -1)
+            else:
+                h = _lin(sa3_in.view(B * S2, c_l2 + 4)[:, :c_l2], p["wa"]).view(B, S2, -1)
+                ext.bias_act_pm_(h, g, rows_per_bias=S2, relu=True)
+            x = h.view(B * S2, -1)
+            for W, b in p["rest"]:
+                x = _lin_relu(x, W, b)
+            l2_out = x.view(B, S2, -1)
 
         # ---- fp2: interpolate l2 -> l1, [l1_feat | interp] -> MLP ---------------------------------------
         ext.three_nn_interpolate_pm(l1_xyz, l2_xyz, l2_out, fp2_in[:, :, c_l1:])  # search + blend: one launch
@@ -339,9 +366,8 @@ class FastEval:
         c_q = q[("q1", 0)]["l3"][0].shape[0]
         c1q = q[("q1", 0)]["l2"][0].shape[1]
         rc = P["row_chain"]
-        if self.row_chain and rc is not None and B * N >= 32768 and B <= ext.ROW_CHAIN_MAX_B and gi_small is not None:
-            # a batch large enough that the dense work, not the launch count, is what costs: the q branches read the per-point
-            # features only through their kNN lists (about 2/3 of a cloud's points for K = 64, 1/4 for K = 16), so fp1, conv1 and
+        if large and rc is not None and gi_small is not None:
+            # the q branches read the per-point features only through their kNN lists (about 2/3 of a cloud's points for K = 64, 1/4 for K = 16), so fp1, conv1 and
             # the layer-1 feature product of all four scales run over the listed rows only, in one launch (rows named by a
             # K = 16 list get the columns of both scales, the others only the K = 64 scale's)
             lst, counts = ext.row_lists(gi, gi_small, N)
