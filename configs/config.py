@@ -62,8 +62,8 @@ def get_config(args, save=True):
         cfg["device"] = torch.device("cuda", local % torch.cuda.device_count())  # (% only matters for the shared-GPU self-test)
     else:
         cfg["device"] = "cpu"
-    if cfg.get("hand_model") == "synthetic":  # the same instance poses the synthetic sequences and drives the optimiser
-        from models.hand_model import SyntheticLBSHand
-        cfg["hand_model"] = SyntheticLBSHand()
+    if cfg.get("hand_model") in ("synthetic", "synthetic_shaped"):  # the same instance poses the synthetic sequences and
+        from models.hand_model import SyntheticLBSHand                 # drives the optimisers
+        cfg["hand_model"] = SyntheticLBSHand(num_betas=10 if cfg["hand_model"] == "synthetic_shaped" else 0)
     print("Running on ", cfg["device"])
     return cfg

@@ -70,7 +70,8 @@ class SyntheticSequences(Dataset):
 def get_dataloader(cfg, mode="train", shuffle=False, num_workers=0, distributed=False, length=None):
     syn = cfg["data_cfg"].get("synthetic", {})
     if cfg.get("track") == "hand_IKNet" and cfg.get("use_optimization") and cfg.get("hand_model") is not None:
-        ds = SyntheticHandObjectSequences(cfg, syn.get("test_sequences", 2), syn.get("sequence_frames", 20) if length is None else length)
+        ds = SyntheticHandObjectSequences(cfg, syn.get("test_sequences", 2), syn.get("sequence_frames", 20) if length is None else length,
+                                          hand_beta=syn.get("hand_beta"))
         return torch.utils.data.DataLoader(ds, batch_size=1, shuffle=False, collate_fn=lambda b: b[0])
     if cfg.get("track") == "obj_opt":
         ds = SyntheticObjectSequences(cfg, syn.get("test_sequences", 2), syn.get("sequence_frames", 30) if length is None else length)
@@ -165,11 +166,17 @@ class SyntheticHandObjectSequences(Dataset):
     branch, reference track_network.py:142-156, :203-211): a hand (cfg['hand_model'], models/hand_model.HandModel) grasping the
     synthetic capsule.  Per frame: hand_points sampled on the posed hand's vertices (+ sensor noise), gt / jittered keypoints,
     gt_hand_pose (palm template of the model's rest pose, rotation, translation), gt_obj_pose, projection, the silhouette's
-    background mask; frame 0 also carries the object's SDF volume."""
+    background mask; frame 0 also carries the object's SDF volume.
 
-    def __init__(self, cfg, num_sequences: int, frames: int, res: int = 151, stride: float = 0.003):
+    hand_beta: the hand's true shape code beta* for a hand model with a shape space -- None (the zero shape: the data of a
+    model without one), a (num_betas,) vector for every sequence, or a float sigma: beta* ~ N(0, sigma^2) per sequence, drawn
+    from the sequence's seed.  With a shape, the palm template and every frame come from the shaped hand and gt_hand_pose
+    carries `mano_beta` (1, num_betas)."""
+
+    def __init__(self, cfg, num_sequences: int, frames: int, res: int = 151, stride: float = 0.003, hand_beta=None):
         self.cfg, self.ns, self.nf, self.res, self.stride = cfg, num_sequences, frames, res, stride
         self.hand = cfg["hand_model"]
+        self.hand_beta = hand_beta
         self._vol = None
 
     def __len__(self):
@@ -190,8 +197,14 @@ class SyntheticHandObjectSequences(Dataset):
         background = torch.from_numpy(~((xx - u) ** 2 + (yy - v) ** 2 < 110 ** 2))
         import copy
         hm = copy.deepcopy(self.hand).cpu()  # (the optimiser's instance lives on the GPU: nn.Module.cpu() moves in place)
+        shape = {}
+        if self.hand_beta is not None and getattr(hm, "num_betas", 0) > 0:
+            hb = self.hand_beta
+            beta = (np.random.default_rng(60_000 + s).normal(0, float(hb), hm.num_betas) if np.ndim(hb) == 0
+                    else np.asarray(hb, np.float64).reshape(hm.num_betas))
+            shape = {"th_betas": f(beta)[None]}
         with torch.no_grad():
-            _, rest_kp = hm.forward(th_pose_coeffs=torch.zeros(1, 3 + hm.num_pose), th_trans=torch.zeros(1, 3))
+            _, rest_kp = hm.forward(th_pose_coeffs=torch.zeros(1, 3 + hm.num_pose), th_trans=torch.zeros(1, 3), **shape)
         palm = rest_kp[:, PALM]
         seq = []
         for k in range(self.nf):
@@ -204,12 +217,12 @@ class SyntheticHandObjectSequences(Dataset):
             ang = np.arccos(np.clip((np.trace(R) - 1) / 2, -1, 1))
             ax = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]]) / (2 * np.sin(ang) + 1e-12)
             with torch.no_grad():
-                verts, kp = hm.forward(th_pose_coeffs=torch.cat([f(ax * ang)[None], f(theta)[None]], 1), th_trans=f(t)[None])
+                verts, kp = hm.forward(th_pose_coeffs=torch.cat([f(ax * ang)[None], f(theta)[None]], 1), th_trans=f(t)[None], **shape)
             pick = rng.integers(0, verts.shape[1], n)
             pts = verts[0, pick].numpy() + rng.normal(0, 0.0015, (n, 3))
             fr = {"hand_points": f(pts).unsqueeze(0), "gt_hand_kp": kp.clone(), "jittered_hand_kp": kp + f(rng.normal(0, jitter, (1, 21, 3))),
                   "gt_hand_pose": {"palm_template": palm.clone(), "rotation": f(R).reshape(1, 3, 3), "translation": f(t).reshape(1, 3, 1),
-                                   "mano_pose": f(theta)[None]},
+                                   "mano_pose": f(theta)[None], **({"mano_beta": shape["th_betas"].clone()} if shape else {})},
                   "gt_obj_pose": {"rotation": f(R_obj).reshape(1, 3, 3), "translation": f(t_obj).reshape(1, 3, 1)},
                   "projection": {kk: [vv] for kk, vv in proj.items()}, "background_mask": background,
                   "category": [self.cfg["obj_category"][0]], "file_name": [f"synthetic_handobj_{s:03d}/{k:04d}"]}

@@ -841,3 +841,40 @@ def fp3_chain(x: torch.Tensor, part: torch.Tensor, wgt, bg, wa, wf, bf, out: tor
                                      _native._ptr(wa, "wa", f32, 256 * 128), _native._ptr(wf, "wf", f32, 256 * 256),
                                      _native._ptr(bf, "bf", f32, 256), out.data_ptr(), out.stride(1), _native._stream(x)), "fp3_chain")
     return out
+
+
+# ---- hand shape-code search in one launch (include/pn2_ext.h: pn2x_hand_shape_opt) ---------------------------------------
+_lib.pn2x_hand_shape_opt_supported.argtypes = [_ci] * 3
+_lib.pn2x_hand_shape_opt_supported.restype = _ci
+_lib.pn2x_hand_shape_opt.argtypes = [_ci] * 4 + [_vp] * 5 + [ctypes.c_double, ctypes.c_double, _vp, _vp, _vp]
+_lib.pn2x_hand_shape_opt.restype = _ci
+
+
+def hand_shape_opt_supported(p: int, d: int, t: int) -> bool:
+    return bool(_lib.pn2x_hand_shape_opt_supported(p, d, t))
+
+
+def hand_shape_opt(k0: torch.Tensor, k: torch.Tensor, pre: torch.Tensor, targets: torch.Tensor, initial_scale: torch.Tensor,
+                   scaling_coefficient2: float, beta: float, iterations: int, out: torch.Tensor = None, trace: bool = False):
+    """The whole shape-code search of gf_optimize_hand_shape.optimize in one launch (pn2x_hand_shape_opt).  k0 (21,3) and
+    k (D,21,3): keypoints affine in the shape code (HandModel.shape_keypoint_basis); pre (P,D) pre-sampled particles, row 0
+    zero; targets (T,15) bone lengths; initial_scale (D).  -> (shape code (D,), trace (iterations, 3 + D) or None)."""
+    P, D = pre.shape
+    T = targets.shape[0]
+    f32 = torch.float32
+    if tuple(k.shape) != (D, 21, 3) or tuple(k0.shape) != (21, 3) or targets.dim() != 2 or targets.shape[1] != 15:
+        raise ValueError(f"hand_shape_opt: k0 {tuple(k0.shape)}, k {tuple(k.shape)}, pre {tuple(pre.shape)}, targets "
+                         f"{tuple(targets.shape)} do not fit together")
+    if not hand_shape_opt_supported(P, D, T):
+        raise ValueError(f"hand_shape_opt: P = {P}, D = {D}, T = {T} outside 1..8192, 1..16, 1..1024")
+    if out is None:
+        out = (torch.empty if iterations > 0 else torch.zeros)(D, dtype=f32, device=pre.device)
+    tr = torch.empty((iterations, 3 + D), dtype=f32, device=pre.device) if trace else None
+    with torch.cuda.device(pre.device):
+        _native._check(_native._call(_lib.pn2x_hand_shape_opt, "hand_shape_kernel", None, P, D, T, int(iterations),
+                                     _native._ptr(k0, "k0", f32, 63), _native._ptr(k, "k", f32, D * 63),
+                                     _native._ptr(pre, "pre", f32, P * D), _native._ptr(targets, "targets", f32, T * 15),
+                                     _native._ptr(initial_scale, "initial_scale", f32, D), float(scaling_coefficient2), float(beta),
+                                     _native._ptr(out, "out", f32, D), None if tr is None else tr.data_ptr(),
+                                     _native._stream(pre)), "hand_shape_opt")
+    return out, tr

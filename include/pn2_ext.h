@@ -328,6 +328,29 @@ int pn2x_fp3_chain(int b, int s, const float *x, int ldx, const float *part, con
                    const float *wf, const float *bf, float *out, int ldo, void *stream);
 
 /*
+ * Hand shape-code search (reference gf_optimize_hand_shape.optimize, network/models/optimization_hand.py:74-124) in one
+ * launch of one 1024-thread workgroup (hotrack_amd/csrc/hand_shape.hip).  The hand's keypoints at the fixed pose are the
+ * affine function kp(beta) = k0 + sum_d beta_d k[d] (k0 (21,3), k (d,21,3): HandModel.shape_keypoint_basis).  With h = 0,
+ * search = initial_scale (d), prev_search = search, prev_success = 1, each of `iterations` iterations does
+ *     sample[q] = pre[q] * search                                  pre (p, d), row 0 zero (the current estimate)
+ *     E[q]      = mean_t mean_b | |bone_b(h + sample[q])| - targets[t, b] |      bones / parents of kp2length, targets (t, 15)
+ *     w[q]      = (E[0] - E[q]) [E[q] < E[0]]    success = any(E[q] < E[0])
+ *     mean_E    = success ? sum w E / sum w : E[0]         mt = success ? sum_q w[q] sample[q] / sum w : 0      h += mt
+ *     sz        = |mt| + 1e-3    search = mean_E * scaling_coefficient2 * sz / ||sz|| + 1e-3
+ *     if (prev_success && success) search = beta search + (1 - beta) prev_search;  if (success) prev_search = search
+ *     prev_success = success
+ * and out (d) = h.  trace (iterations, 3 + d) or NULL: per iteration [E[0], mean_E, success (0/1), search after the update].
+ * fp32; every sum runs in a fixed order, no atomics: two runs give bitwise-equal results.  No host sync (capturable).
+ * 1 <= p <= 8192, 1 <= d <= 16, 1 <= t <= 1024 (pn2x_hand_shape_opt_supported).  Errors: PN2_EINVAL for p, d or t < 1 or
+ * iterations < 0, PN2_ERANGE beyond the limits or for iterations * (3 + d) >= 2^31, PN2_ENULL for a NULL pointer other
+ * than trace; iterations == 0 returns PN2_OK and touches nothing.  Arguments are checked before any device work.
+ */
+int pn2x_hand_shape_opt_supported(int p, int d, int t);
+int pn2x_hand_shape_opt(int p, int d, int t, int iterations, const float *k0, const float *k, const float *pre,
+                        const float *targets, const float *initial_scale, double scaling_coefficient2, double beta, float *out,
+                        float *trace, void *stream);
+
+/*
  * ---- training-mode building blocks on point-major activations (hotrack_amd/csrc/train_ops.hip) --------------------------
  * The reference trains every grouped MLP as Conv2d(1x1) + BatchNorm2d + ReLU on channel-major (B, C, S, K) tensors
  * (pointnet_utils.py:399-403, :460-462, :504-506, :577-581).  A 1x1 convolution is a GEMM over all R = B*S*K positions

@@ -36,6 +36,12 @@ class HandModel(nn.Module):
     num_verts: int
     num_pose: int
     contact_zones: dict
+    num_betas: int = 0  # dimensions of the shape code `th_betas` (MANO: 10); 0 = the model has no shape space
+
+    # A shape basis is accepted when it reproduces forward() to this many metres at shape codes as large as the shape search
+    # reaches (initial search size 5 x a few standard deviations of the pre-sampled particles).
+    BASIS_TOL = 1e-6
+    BASIS_CHECK_RANGE = 20.0
 
     def pca_comps2pose(self, ncomps: int, pca: torch.Tensor) -> torch.Tensor:
         raise NotImplementedError
@@ -43,14 +49,48 @@ class HandModel(nn.Module):
     def register_beta(self, th_betas=None):
         return None
 
+    def shape_keypoint_basis(self, pose_coeffs: torch.Tensor):
+        """Keypoints at the pose `pose_coeffs` (1, 3 + num_pose) as an affine function of the shape code,
+        kp(beta) = K0 + sum_d beta_d K[d]  ->  (K0 (21,3), K (num_betas,21,3)) float32 on the model's device, or None when the
+        model has no shape space or is not affine in beta there (the check: forward() at a few random beta in
+        [-BASIS_CHECK_RANGE, BASIS_CHECK_RANGE]^num_betas, tolerance BASIS_TOL).  A linear-blend-skinned hand with linear shape
+        blend directions (MANO, SyntheticLBSHand) is affine at a fixed pose: the rest joints and vertices are linear in beta
+        and the rotations do not depend on it.  Built and checked in float64, once per model and pose."""
+        D = int(self.num_betas)
+        if D <= 0:
+            return None
+        pose = pose_coeffs.detach().reshape(1, -1).to(torch.float64).cpu()
+        cache = self.__dict__.setdefault("_shape_basis_cache", {})
+        key = tuple(pose.flatten().tolist())
+        if key not in cache:
+            g = torch.Generator().manual_seed(1234)
+            betas = torch.cat([torch.zeros(1, D, dtype=torch.float64), torch.eye(D, dtype=torch.float64),
+                               (torch.rand(4, D, generator=g, dtype=torch.float64) * 2 - 1) * self.BASIS_CHECK_RANGE])
+            dev = next(iter(self.buffers()), pose).device
+            with torch.no_grad():
+                try:  # float64 where the model computes in the pose's dtype (SyntheticLBSHand), else its own precision
+                    _, kp = self.forward(th_pose_coeffs=pose.to(dev).expand(betas.shape[0], -1), th_betas=betas.to(dev))
+                except RuntimeError:
+                    _, kp = self.forward(th_pose_coeffs=pose.float().to(dev).expand(betas.shape[0], -1), th_betas=betas.float().to(dev))
+            kp = kp.cpu().double()
+            K0, K = kp[0], kp[1:D + 1] - kp[0]
+            pred = K0 + torch.einsum("rd,dkc->rkc", betas[D + 1:], K)
+            affine = bool((pred - kp[D + 1:]).abs().max() <= self.BASIS_TOL)
+            cache[key] = (K0.float().contiguous(), K.float().contiguous()) if affine else None
+        basis = cache[key]
+        if basis is None:
+            return None
+        dev = next(iter(self.buffers()), pose_coeffs).device
+        return basis[0].to(dev), basis[1].to(dev)
+
 
 class SyntheticLBSHand(HandModel):
     FINGERS = ((1, 2, 3, 4), (5, 6, 7, 8), (9, 10, 11, 12), (13, 14, 15, 16), (17, 18, 19, 20))  # thumb, index, middle, ring, pinky
 
-    def __init__(self, num_verts: int = 778, seed: int = 0):
+    def __init__(self, num_verts: int = 778, seed: int = 0, num_betas: int = 0):
         super().__init__()
         g = torch.Generator().manual_seed(seed)
-        self.num_verts, self.num_pose = num_verts, 45
+        self.num_verts, self.num_pose, self.num_betas = num_verts, 45, int(num_betas)
         # ---- rest skeleton (metres), wrist at the origin, fingers along +y, palm in the xy plane -------------------------
         rest = torch.zeros(21, 3)
         base_x = (-0.035, -0.02, 0.0, 0.018, 0.034)
@@ -110,6 +150,42 @@ class SyntheticLBSHand(HandModel):
         bone_of = torch.tensor(bone_of)
         tip_bone = {kp: bones.index((parents[kp], kp)) for kp in (8, 12, 16, 20, 4)}
         self.contact_zones = {i + 1: torch.nonzero(bone_of == tip_bone[kp]).flatten().tolist() for i, kp in enumerate((8, 12, 16, 20, 4))}
+        self.registered_beta = None
+        if self.num_betas > 0:
+            self._init_shape_space(g)
+
+    def _init_shape_space(self, g: torch.Generator):
+        """num_betas shape directions, drawn after (so without changing) everything above.  Direction d moves every bone
+        along its own axis by a random fraction of its length (a few per cent per unit of beta) plus a small random
+        sideways offset; the wrist stays at the origin.  The rest joints are a linear function of beta, and every vertex
+        moves rigidly with the end joint of its bone (palm vertices: with a random palm stretch), so the skinning offsets
+        rest[j] - rest[parent] and v_rest - j_k are linear in beta and the posed hand is affine in beta at a fixed pose."""
+        D, rest, par = self.num_betas, self.rest_joints, self.parents
+        stretch = torch.randn(D, 21, generator=g) * 0.03               # relative bone-length change per unit of beta
+        side = torch.randn(D, 21, 3, generator=g) * 0.0005             # metres per unit of beta
+        d_off = torch.zeros(D, 21, 3)
+        for j in range(1, 21):
+            d_off[:, j] = stretch[:, j, None] * (rest[j] - rest[par[j]]) + side[:, j]
+        d_joints = torch.zeros(D, 21, 3)
+        for chain in self.FINGERS:                                     # accumulate the offsets down each finger
+            for j in chain:
+                d_joints[:, j] = d_joints[:, par[j]] + d_off[:, j]
+        palm = torch.randn(D, 3, generator=g) * torch.tensor([0.02, 0.02, 0.005])
+        # a vertex follows its bone's end joint: v_rest - j_k changes only by the difference of the two end joints' motion
+        end = self.skin_idx[:, 1].clone()
+        is_palm = self.skin_w[:, 1] == 0
+        d_verts = d_joints[:, end]                                     # (D, V, 3)
+        d_verts[:, is_palm] = self.rest_verts[is_palm][None] * palm[:, None, :]
+        self.register_buffer("shape_joints", d_joints.contiguous())
+        self.register_buffer("shape_verts", d_verts.contiguous())
+
+    def register_beta(self, th_betas=None):
+        """The shape used by forward(..., use_registed_beta=True) (our_mano.py:211-216); ignored by a model without a shape
+        space."""
+        if self.num_betas == 0 or th_betas is None:
+            return None
+        self.registered_beta = torch.as_tensor(th_betas).reshape(1, self.num_betas).to(self.rest_joints)
+        return None
 
     def pca_comps2pose(self, ncomps: int, pca: torch.Tensor) -> torch.Tensor:
         return pca.mm(self.th_comps[:ncomps])
@@ -120,6 +196,15 @@ class SyntheticLBSHand(HandModel):
         Rg = rodrigues(th_pose_coeffs[:, :3])                                  # (P,3,3)
         Rl = rodrigues(th_pose_coeffs[:, 3:].reshape(P, 15, 3))                # (P,15,3,3)
         rest = self.rest_joints.to(dt)
+        rest_verts = self.rest_verts.to(dt)
+        if self.num_betas > 0:
+            if th_betas is None and use_registed_beta:
+                th_betas = self.registered_beta
+            if th_betas is not None:  # per-candidate rest pose: (P,21,3) joints, (P,V,3) vertices, linear in beta
+                b = th_betas.to(dt).reshape(-1, self.num_betas).expand(P, -1)
+                rest = rest + (b @ self.shape_joints.to(dt).reshape(self.num_betas, -1)).view(P, 21, 3)
+                rest_verts = rest_verts + (b @ self.shape_verts.to(dt).reshape(self.num_betas, -1)).view(P, -1, 3)
+        shaped = rest.dim() == 3
         R_w = [None] * 21
         t_w = [None] * 21
         R_w[0] = Rg
@@ -128,15 +213,18 @@ class SyntheticLBSHand(HandModel):
         for chain in self.FINGERS:
             for j in chain:
                 pa = self.parents[j]
-                off = (rest[j] - rest[pa]).view(1, 3, 1)
+                off = (rest[..., j, :] - rest[..., pa, :]).view(-1, 3, 1)
                 t_w[j] = t_w[pa] + (R_w[pa] @ off).squeeze(-1)
                 R_w[j] = R_w[pa] @ Rl[:, art_of[j]] if j in art_of else R_w[pa]
         R_w = torch.stack(R_w, dim=1)                                          # (P,21,3,3)
         t_w = torch.stack(t_w, dim=1)                                          # (P,21,3)
         # linear blend skinning: v = sum_k w_k (R_k (v_rest - j_k) + t_k)
-        rel = (self.rest_verts.to(dt)[:, None, :] - rest[self.skin_idx])       # (V,2,3)
+        if shaped:
+            rel = rest_verts[:, :, None, :] - rest[:, self.skin_idx]           # (P,V,2,3)
+        else:
+            rel = (rest_verts[:, None, :] - rest[self.skin_idx])[None]         # (1,V,2,3)
         Rk = R_w[:, self.skin_idx]                                             # (P,V,2,3,3)
-        vk = (Rk @ rel[None, :, :, :, None]).squeeze(-1) + t_w[:, self.skin_idx]
+        vk = (Rk @ rel[..., None]).squeeze(-1) + t_w[:, self.skin_idx]
         verts = (vk * self.skin_w.to(dt)[None, :, :, None]).sum(dim=2)         # (P,V,3)
         joints = t_w
         if th_trans is not None:

@@ -1,4 +1,4 @@
-"""Hand-pose particle optimiser (counterpart of the reference's gf_optimize_hand_pose,
+"""Hand-shape and hand-pose particle optimisers.  Hand-pose particle optimiser (counterpart of the reference's gf_optimize_hand_pose,
 network/models/optimization_hand.py:138-394): a gradient-free search over global rotation, translation and PCA pose
 coefficients of the hand -- 5120 candidate hands per iteration, 5 iterations per frame -- that trades keypoint fidelity
 against hand-object penetration, silhouette, temporal smoothness and fingertip attraction.
@@ -33,6 +33,125 @@ def world2point2D(xyz, fx, fy, cx, cy):
     x = xyz[..., 0] / xyz[..., 2] * fx + cx
     y = xyz[..., 1] / xyz[..., 2] * fy + cy
     return torch.stack([y, x], dim=-1).float()
+
+
+_BONE = [1, 2, 3, 5, 6, 7, 9, 10, 11, 13, 14, 15, 17, 18, 19]
+_PARENT = [0, 1, 2, 0, 5, 6, 0, 9, 10, 0, 13, 14, 0, 17, 18]
+
+
+def kp2length(kp):
+    """(B,21,3) keypoints -> (B,15) bone lengths, optimization_hand.py:24-28."""
+    return torch.norm(kp[:, _BONE] - kp[:, _PARENT], dim=-1)
+
+
+class gf_optimize_hand_shape:
+    """The hand's shape code from HandTrackNet's keypoints (reference gf_optimize_hand_shape, optimization_hand.py:30-124): a
+    gradient-free search over the model's num_betas shape dimensions -- `particle_size` candidate shapes per iteration,
+    `iteration` dependent iterations -- whose energy is the mean absolute difference between a candidate's 15 bone lengths
+    at the rest pose and the target lengths (the current prediction's, or with `use_old` those of every earlier call too).
+
+    Two routes, the same arithmetic:
+      * GPU: when the hand model is on the GPU and its keypoints are affine in the shape code at the rest pose
+        (HandModel.shape_keypoint_basis is not None), the whole search is ONE kernel launch (hotrack_amd.ext.hand_shape_opt,
+        csrc/hand_shape.hip): no hand-model evaluation, no host sync, graph-capturable;
+      * torch: the model's forward on all candidates every iteration, like the reference, with its two host branches on
+        `torch.any(better_mask)` turned into selections on the device.  Serves CPU tensors and models without an affine basis.
+    `trace` (the last call's per-iteration [energy[0], mean_energy, success, search_size after the update]) is kept when
+    `keep_trace` is set (tests)."""
+
+    def __init__(self, cfg=None, hand_model=None, device="cuda", particle_size=5120, seed=None):
+        cfg = cfg or {}
+        self.device = torch.device(cfg.get("device", device))
+        self.mano_layer_right = hand_model.to(self.device) if hand_model is not None else None
+        self.optimize_dim = int(hand_model.num_betas) if hand_model is not None else 10   # :32
+        self.particle_size = particle_size                                                 # :36
+        self.iteration = 20
+        self.beta = 0.9
+        self.scaling_coefficient2 = 2000
+        self.initial_scale = torch.ones(self.optimize_dim, device=self.device) * 5
+        # pre-sampled particles: N(0, I), the first one at the origin (= the current estimate), :45-49
+        g = torch.Generator().manual_seed(0 if seed is None else seed)
+        pre = torch.randn(self.particle_size, self.optimize_dim, generator=g)
+        pre[0] = 0
+        self.pre_sampled_particle = pre.to(self.device)
+        self.old_pred_length = None
+        self.keep_trace = False
+        self.trace = None
+
+    def evaluate(self, kp):
+        return (kp2length(kp).unsqueeze(1) - self.old_pred_length).abs().mean(dim=-1).mean(dim=-1)
+
+    def update_seach_size(self, energy, mean_transform):
+        s = mean_transform.abs() + 1e-3
+        return energy * self.scaling_coefficient2 * s / s.norm() + 1e-3
+
+    def set_init_para(self, pred_kp, use_old):
+        """:62-72; the history of use_old (mode 3) stays on the device, one row per call."""
+        self.hand_shape = torch.zeros((1, self.optimize_dim), device=self.device)
+        self.pred_length = kp2length(pred_kp.to(self.device).float()).unsqueeze(1)
+        if use_old and self.old_pred_length is not None:
+            self.old_pred_length = torch.cat([self.old_pred_length, self.pred_length], dim=1)
+        else:
+            self.old_pred_length = self.pred_length
+
+    def _rest_pose(self, n, device=None):
+        return torch.zeros((n, 3 + self.mano_layer_right.num_pose), device=device or self.device)
+
+    def keypoint_basis(self):
+        """The model's affine shape basis at the rest pose on this optimiser's device, or None (built once)."""
+        if "_basis" not in self.__dict__:
+            b = self.mano_layer_right.shape_keypoint_basis(self._rest_pose(1, "cpu"))
+            self._basis = None if b is None else (b[0].to(self.device).contiguous(), b[1].to(self.device).contiguous())
+        return self._basis
+
+    def use_kernel(self) -> bool:
+        return self.device.type == "cuda" and self.keypoint_basis() is not None
+
+    def optimize(self, pred_kp, use_old=False):
+        """pred_kp (1,21,3) -> the shape code (1, num_betas), :74-124."""
+        self.set_init_para(pred_kp, use_old)
+        if self.use_kernel():
+            from hotrack_amd import ext
+            k0, k = self.keypoint_basis()
+            targets = self.old_pred_length.reshape(-1, 15).contiguous()
+            h, tr = ext.hand_shape_opt(k0, k, self.pre_sampled_particle.float().contiguous(), targets,
+                                       self.initial_scale.float().contiguous(), self.scaling_coefficient2, self.beta, self.iteration,
+                                       trace=self.keep_trace)
+            self.hand_shape = h.reshape(1, -1)
+            self.trace = tr
+            return self.hand_shape
+        return self._optimize_torch()
+
+    def _optimize_torch(self):
+        dev, P = self.device, self.particle_size
+        search_size = self.initial_scale
+        prev_search_size = search_size
+        prev_success = torch.ones((), dtype=torch.bool, device=dev)
+        trace = []
+        pose, trans = self._rest_pose(P), torch.zeros((P, 3), device=dev)
+        for _ in range(self.iteration):
+            sample = self.pre_sampled_particle * search_size
+            _, kp = self.mano_layer_right.forward(th_pose_coeffs=pose, th_trans=trans, th_betas=self.hand_shape + sample)
+            energy = self.evaluate(kp)
+
+            origin_energy = energy[0]
+            better_mask = energy < origin_energy
+            weight = (origin_energy - energy) * better_mask
+            weight_sum = weight.sum()
+            success = better_mask.any()
+            mean_energy = torch.where(success, (energy * weight).sum() / weight_sum, energy[0])
+            mt = (sample * weight.unsqueeze(1)).sum(dim=0, keepdim=True) / weight_sum      # NaN when no success
+            mean_transform = torch.where(success, mt, torch.zeros_like(mt))
+            self.hand_shape = torch.where(success, self.hand_shape + mean_transform, self.hand_shape)
+
+            search_size = self.update_seach_size(mean_energy, mean_transform)
+            search_size = torch.where(prev_success & success, self.beta * search_size + (1 - self.beta) * prev_search_size, search_size)
+            prev_search_size = torch.where(success, search_size, prev_search_size)
+            prev_success = success
+            if self.keep_trace:
+                trace.append(torch.cat([torch.stack([origin_energy, mean_energy, success.float()]), search_size.reshape(-1)]))
+        self.trace = torch.stack(trace) if self.keep_trace else None
+        return self.hand_shape
 
 
 class gf_optimize_hand_pose:

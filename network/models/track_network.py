@@ -4,7 +4,8 @@ reference track_network.py:139-226, HandTrackNet-only branch :214-217).
 Frame t is initialised from frame t-1: the previous prediction, expressed relative to the previous
 cloud's centroid, is re-attached to the current cloud's centroid ("important for fast motion",
 :163,:217).  The palm template comes from the sequence's first frame (the reference builds it from a
-MANO layer, which needs licensed assets; the tracking logic is otherwise the same)."""
+MANO layer, which needs licensed assets; the tracking logic is otherwise the same) -- or, with hand shape estimation
+(`use_pred_hand_shape`), from the hand model's rest hand at the estimated shape code."""
 from __future__ import annotations
 
 import torch
@@ -36,6 +37,26 @@ class HandTrackModel(nn.Module):
         if self.use_optimization:
             from .optimization_hand import gf_optimize_hand_pose
             self.optimizer = gf_optimize_hand_pose(cfg, hand_model=hand_model, particle_size=int(cfg.get("hand_particles", 5120)))
+        # shape-code estimation from HandTrackNet's keypoints (reference track_network.py:130-134, :174-193):
+        # use_pred_hand_shape 1 = on frame 0, 2 = every 10 frames, 3 = every 10 frames over the bone lengths of all earlier
+        # calls.  It runs where the reference's IKNet branch runs here (use_optimization with a hand model) and needs a
+        # hand model with a shape space; otherwise the loop is unchanged and says why.
+        mode = cfg.get("use_pred_hand_shape", 0)
+        self.shape_mode = int(mode) if mode not in (None, False, True) else int(bool(mode))
+        if self.shape_mode not in (0, 1, 2, 3):
+            raise ValueError(f"use_pred_hand_shape: 0/False, 1, 2 or 3, got {mode!r}")
+        self.opt_shape = None
+        if self.shape_mode:
+            why = ("use_optimization is off or there is no hand model" if not self.use_optimization else
+                   "the hand model has no shape space (num_betas = 0)" if getattr(hand_model, "num_betas", 0) == 0 else None)
+            if why is None:
+                from .optimization_hand import gf_optimize_hand_shape
+                self.opt_shape = gf_optimize_hand_shape(cfg, hand_model=self.optimizer.mano_layer_right,
+                                                        particle_size=int(cfg.get("shape_particles", 5120)))
+                print(f"[Hand Tracking] hand shape estimation: use_pred_hand_shape = {self.shape_mode} "
+                      f"({'GPU kernel' if self.opt_shape.use_kernel() else 'torch route'})")
+            else:
+                print(f"[Hand Tracking] hand shape estimation skipped (use_pred_hand_shape = {self.shape_mode}): {why}")
 
     # A captured graph bakes in the pointers of the BN-folded weights FastEval built at capture time: anything that can
     # change the weights (checkpoint load, fine-tuning, .to()/.float()) drops the captured graphs.
@@ -89,15 +110,31 @@ class HandTrackModel(nn.Module):
         theta = prev_theta if prev_theta is not None else torch.zeros((1, hm.num_pose), device=pred_kp.device)
         with torch.no_grad():
             _, kp0 = hm.forward(th_pose_coeffs=torch.cat([torch.zeros((1, 3), device=pred_kp.device), theta], dim=1),
-                                th_trans=torch.zeros((1, 3), device=pred_kp.device))
+                                th_trans=torch.zeros((1, 3), device=pred_kp.device), use_registed_beta=True)
             R, t = ext.kabsch(kp0.contiguous(), pred_kp.contiguous())  # pred ~ R kp0 + t
         return theta, {"rotation": R.reshape(1, 3, 3), "translation": t.reshape(1, 3, 1)}
+
+    def _shaped_palm_template(self, shape_code):
+        """Palm keypoints of the rest hand with `shape_code` (1, num_betas) (reference handkp2palmkp of the shaped rest hand)."""
+        from .hand_utils import handkp2palmkp
+        hm = self.opt_shape.mano_layer_right
+        with torch.no_grad():
+            _, kp = hm.forward(th_pose_coeffs=torch.zeros((1, 3 + hm.num_pose), device=self.device),
+                               th_trans=torch.zeros((1, 3), device=self.device), th_betas=shape_code)
+        return handkp2palmkp(kp).float()
+
+    def _shape_due(self, i):
+        return (self.shape_mode == 1 and i == 0) or (self.shape_mode in (2, 3) and i % 10 == 0)
 
     def forward(self, input, flag_dict):
         flag_dict["track_flag"] = True
         assert flag_dict["test_flag"]
         flag_dict["opt_flag"] = self.use_optimization
-        palm_template = input[0]["gt_hand_pose"]["palm_template"].to(self.device).float()
+        if self.opt_shape is not None:  # the zero shape's rest hand until the first estimate (:150-152)
+            palm_template = self._shaped_palm_template(torch.zeros((1, self.opt_shape.optimize_dim), device=self.device))
+            shape_code = None
+        else:
+            palm_template = input[0]["gt_hand_pose"]["palm_template"].to(self.device).float()
         last_kp = None
         rets = []
         graph_ok = (self.use_graph and pointnet_utils.fused_backend() is not None and not self.training
@@ -110,7 +147,7 @@ class HandTrackModel(nn.Module):
                 raise RuntimeError("use_optimization: no SDF volume (decoding it from a DeepSDF latent needs the checkpoints); "
                                    "put 'sdf_volume' / 'voxel_scale' into the sequence's first frame")
         prev_theta = None
-        for data in input:
+        for i, data in enumerate(input):
             data["pred_palm_template"] = palm_template
             points = data["hand_points"].to(self.device, non_blocking=True).float()
             centre = points.mean(dim=-2, keepdim=True)
@@ -122,6 +159,12 @@ class HandTrackModel(nn.Module):
                 ret = self.handnet(data, flag_dict)
             if self.use_optimization:  # track_network.py:142-156 (IKNet's role: _pose_init), :203-211
                 ret["baseline_pred_kp"] = ret["pred_kp"].clone()
+                if self.opt_shape is not None:  # :174-193: the template takes effect from the next frame on
+                    if self._shape_due(i):
+                        shape_code = self.opt_shape.optimize(ret["baseline_pred_kp"], use_old=self.shape_mode == 3).clone()
+                        palm_template = self._shaped_palm_template(shape_code)
+                    data["pred_beta"] = shape_code
+                    ret["pred_beta"] = shape_code
                 theta0, pose0 = self._pose_init(ret["baseline_pred_kp"], prev_theta)
                 obj_pose = data["pred_obj_pose"] if (self.use_pred_obj_pose and "pred_obj_pose" in data) else data["gt_obj_pose"]
                 kp, theta, rot, trans = self.optimizer.optimize(theta0, pose0, ret["baseline_pred_kp"], last_kp, ret["pred_kp_vis_mask"],

@@ -73,10 +73,10 @@ class Trainer(nn.Module):
             # (track_network.py:214-217) -- and says so.
             hm = cfg.get("hand_model")
             if isinstance(hm, str):
-                if hm != "synthetic":
-                    raise ValueError("hand_model: 'synthetic' or a models.hand_model.HandModel instance")
+                if hm not in ("synthetic", "synthetic_shaped"):
+                    raise ValueError("hand_model: 'synthetic', 'synthetic_shaped' or a models.hand_model.HandModel instance")
                 from models.hand_model import SyntheticLBSHand
-                hm = SyntheticLBSHand()
+                hm = SyntheticLBSHand(num_betas=10 if hm == "synthetic_shaped" else 0)
                 cfg["hand_model"] = hm  # the synthetic sequences pose the same model
             if hm is not None and cfg.get("use_optimization", False):
                 self.log_string("track=hand_IKNet: HandTrackNet tracking + hand-pose particle optimisation (hand model: %s; "
