@@ -65,5 +65,8 @@ def get_config(args, save=True):
     if cfg.get("hand_model") in ("synthetic", "synthetic_shaped"):  # the same instance poses the synthetic sequences and
         from models.hand_model import SyntheticLBSHand                 # drives the optimisers
         cfg["hand_model"] = SyntheticLBSHand(num_betas=10 if cfg["hand_model"] == "synthetic_shaped" else 0)
+    if cfg.get("track") == "hand_IKNet":  # IKNet runs when its checkpoint and a hand model exist (recorded as cfg["use_iknet"])
+        from models.iknet import resolve_use_iknet
+        resolve_use_iknet(cfg)
     print("Running on ", cfg["device"])
     return cfg

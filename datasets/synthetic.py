@@ -67,9 +67,65 @@ class SyntheticSequences(Dataset):
         return seq
 
 
+class SyntheticIKFrames(Dataset):
+    """Independent frames for training IKNet (`network.type: iknet`, reference SingleFrameData items as IKNet.forward reads them,
+    hand_network.py:268-271): the hand model (models/hand_model.HandModel) posed at a seeded sample and
+      mano_pose (48): [global axis-angle | 45 joint axis-angles], the joints i.i.d. uniform in [-pose_range, pose_range] rad
+                      (default 0.5; SyntheticHandObjectSequences' grasp poses stay within +-0.2), the global rotation uniform
+                      over SO(3) (axis uniform on the sphere, angle with density (1 - cos) / pi);
+      translation     (0, 0, 0.5) m + uniform [-0.1, 0.1]^3 m;
+      mano_beta       (num_betas) ~ N(0, 1) when the model has a shape space;
+    gt_hand_kp = the model's keypoints, jittered_hand_kp = gt + N(0, rand_scale^2) (hand_jitter_cfg), palm_template = the palm
+    keypoints of the shaped rest hand.  Item i depends only on (base_seed + i)."""
+
+    def __init__(self, cfg, length: int, base_seed: int = 0, pose_range: float = 0.5):
+        self.hand = cfg.get("hand_model")
+        if self.hand is None or isinstance(self.hand, str):
+            from models.hand_model import SyntheticLBSHand
+            self.hand = SyntheticLBSHand(num_betas=10 if self.hand == "synthetic_shaped" else 0)
+        self.len, self.seed, self.pose_range = length, base_seed, pose_range
+        self.jitter = cfg["hand_jitter_cfg"]["rand_scale"]
+
+    def __len__(self):
+        return self.len
+
+    def __getitem__(self, i):
+        import copy
+        rng = np.random.default_rng(self.seed + i)
+        f = lambda a: torch.from_numpy(np.asarray(a, dtype=np.float32))
+        axis = rng.standard_normal(3)
+        axis /= np.linalg.norm(axis)
+        u = rng.uniform()
+        ang = 0.0  # angle of a uniform rotation: inverse CDF of (x - sin x) / pi, by bisection
+        lo, hi = 0.0, np.pi
+        for _ in range(40):
+            ang = 0.5 * (lo + hi)
+            lo, hi = (ang, hi) if (ang - np.sin(ang)) / np.pi < u else (lo, ang)
+        pose = np.concatenate([axis * ang, rng.uniform(-self.pose_range, self.pose_range, 45)])
+        trans = np.array([0.0, 0.0, 0.5]) + rng.uniform(-0.1, 0.1, 3)
+        hm = self.hand if not any(p.is_cuda for p in self.hand.buffers()) else copy.deepcopy(self.hand).cpu()
+        nb = int(getattr(hm, "num_betas", 0))
+        shape = {"th_betas": f(rng.standard_normal(nb))[None]} if nb else {}
+        with torch.no_grad():
+            _, kp = hm.forward(th_pose_coeffs=f(pose)[None], th_trans=f(trans)[None], **shape)
+            _, rest = hm.forward(th_pose_coeffs=torch.zeros(1, 48), th_trans=torch.zeros(1, 3), **shape)
+        gt = kp[0].float()
+        pose_d = {"palm_template": rest[0, PALM].float(), "mano_pose": f(pose)}
+        if nb:
+            pose_d["mano_beta"] = shape["th_betas"][0]
+        return {"gt_hand_kp": gt, "jittered_hand_kp": gt + f(rng.normal(0, self.jitter, (21, 3))), "gt_hand_pose": pose_d}
+
+
 def get_dataloader(cfg, mode="train", shuffle=False, num_workers=0, distributed=False, length=None):
     syn = cfg["data_cfg"].get("synthetic", {})
-    if cfg.get("track") == "hand_IKNet" and cfg.get("use_optimization") and cfg.get("hand_model") is not None:
+    if not cfg.get("track") and cfg.get("network", {}).get("type") == "iknet":
+        n = length or (syn.get("train_frames", 2048) if mode == "train" else max(cfg["batch_size"] * 4, 64))
+        ds = SyntheticIKFrames(cfg, n, base_seed=0 if mode == "train" else 1_000_000)
+        sampler = torch.utils.data.distributed.DistributedSampler(ds, shuffle=shuffle) if distributed else None
+        return torch.utils.data.DataLoader(ds, batch_size=cfg["batch_size"], shuffle=shuffle and sampler is None, sampler=sampler,
+                                           num_workers=num_workers, drop_last=(mode == "train"))
+    if (cfg.get("track") == "hand_IKNet" and (cfg.get("use_optimization") or cfg.get("use_iknet"))
+            and cfg.get("hand_model") is not None):
         ds = SyntheticHandObjectSequences(cfg, syn.get("test_sequences", 2), syn.get("sequence_frames", 20) if length is None else length,
                                           hand_beta=syn.get("hand_beta"))
         return torch.utils.data.DataLoader(ds, batch_size=1, shuffle=False, collate_fn=lambda b: b[0])

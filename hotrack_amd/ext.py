@@ -878,3 +878,41 @@ def hand_shape_opt(k0: torch.Tensor, k: torch.Tensor, pre: torch.Tensor, targets
                                      _native._ptr(out, "out", f32, D), None if tr is None else tr.data_ptr(),
                                      _native._stream(pre)), "hand_shape_opt")
     return out, tr
+
+
+# ---- IKNet eval forward for up to 16 rows (include/pn2_ext.h: pn2x_iknet_forward) -------------------------------------------
+_lib.pn2x_iknet_supported.argtypes = [_ci] * 5
+_lib.pn2x_iknet_supported.restype = _ci
+_lib.pn2x_iknet_work_floats.argtypes = []
+_lib.pn2x_iknet_work_floats.restype = _cl
+_lib.pn2x_iknet_forward.argtypes = [_ci, _ci] + [_vp] * 14
+_lib.pn2x_iknet_forward.restype = _ci
+IKNET_MAX_ROWS = 16
+
+
+def iknet_supported(m: int, k_in: int = 126, hidden: int = 1024, layers: int = 6, n_out: int = 60) -> bool:
+    return bool(_lib.pn2x_iknet_supported(m, k_in, hidden, layers, n_out))
+
+
+def iknet_forward(kp: torch.Tensor, R: torch.Tensor, t: torch.Tensor, w1, b1, wh, bh, wo, bo, camera: bool = False):
+    """The eval-mode IKNet forward (pn2x_iknet_forward): kp (M,21,3), R (M,3,3), t (M,3,1) of the palm fit; BatchNorm-folded
+    weights w1 (1024,128) (columns 126, 127 zero), b1 (1024), wh (5,1024,1024), bh (5,1024), wo (60,1024), bo (60).
+    -> (raw_quat (M,60), theta (M,45), kp_hf (M,3,21)).  camera: the 'camera' frame (kp * 5; R, t unused)."""
+    M = kp.shape[0]
+    if not iknet_supported(M):
+        raise ValueError(f"iknet_forward: {M} rows outside 1..{IKNET_MAX_ROWS}")
+    f32 = torch.float32
+    dev = kp.device
+    work = torch.empty(int(_lib.pn2x_iknet_work_floats()), dtype=f32, device=dev)
+    raw = torch.empty((M, 60), dtype=f32, device=dev)
+    theta = torch.empty((M, 45), dtype=f32, device=dev)
+    kp_hf = torch.empty((M, 3, 21), dtype=f32, device=dev)
+    with torch.cuda.device(dev):
+        _native._check(_native._call(_lib.pn2x_iknet_forward, "iknet_forward", None, M, 1 if camera else 0,
+                                     _native._ptr(kp, "kp", f32, M * 63), _native._ptr(R, "R", f32, M * 9),
+                                     _native._ptr(t, "t", f32, M * 3), _native._ptr(w1, "w1", f32, 1024 * 128),
+                                     _native._ptr(b1, "b1", f32, 1024), _native._ptr(wh, "wh", f32, 5 * 1024 * 1024),
+                                     _native._ptr(bh, "bh", f32, 5 * 1024), _native._ptr(wo, "wo", f32, 60 * 1024),
+                                     _native._ptr(bo, "bo", f32, 60), work.data_ptr(), kp_hf.data_ptr(), raw.data_ptr(),
+                                     theta.data_ptr(), _native._stream(kp)), "iknet_forward")
+    return raw, theta, kp_hf

@@ -351,6 +351,27 @@ int pn2x_hand_shape_opt(int p, int d, int t, int iterations, const float *k0, co
                         float *trace, void *stream);
 
 /*
+ * IKNet forward in eval mode (reference hand_network.py:264-322; hotrack_amd/csrc/iknet.hip) for m <= 16 rows, fp32:
+ *     kp_hf = R^T (kp - t) / 0.2  (frame 0, 'kp')   or   kp * 5  (frame 1, 'camera'; R and t are not read)
+ *     x     = [kp_hf | kp_hf - kp_hf[parent]]  coordinate-major (m, 126)
+ *     h     = relu(x W1^T + b1), then five times h = relu(h Wl^T + bl)      (BatchNorm folded into W / b by the caller)
+ *     raw_quat = h Wo^T + bo  (m, 60);  theta (m, 45) = per joint the axis-angle of raw_quat's quaternion [w, x, y, z]:
+ *                q / (|q| + 1e-8), sin = sqrt(max(1 - w^2, 0)), axis = xyz / max(sin, [sin < 1e-8]), angle = 2 acos(clamp(w))
+ * kp (m, 21, 3); R (m, 3, 3); t (m, 3, 1); w1 (1024, 128) with columns 126, 127 zero; b1 (1024); wh (5, 1024, 1024); bh (5, 1024);
+ * wo (60, 1024); bo (60); work: pn2x_iknet_work_floats() floats; kp_hf (m, 3, 21) or NULL; raw_quat (m, 60); theta (m, 45).
+ * w1, wh, wo and work 16-byte aligned.  Seven launches (one per layer), fixed summation order, no atomics: results are bitwise
+ * reproducible.  No host sync or allocation (capturable).  Errors, checked before any device work: PN2_EINVAL for m < 1, a
+ * frame other than 0 / 1 or a misaligned pointer; PN2_ERANGE for m > 16; PN2_ENULL for a NULL pointer (R, t: frame 0 only;
+ * kp_hf may be NULL).  pn2x_iknet_supported(m, k_in, hidden, layers, n_out): the sizes this entry covers (1..16, 126, 1024, 6,
+ * 60).
+ */
+int pn2x_iknet_supported(int m, int k_in, int hidden, int layers, int n_out);
+long pn2x_iknet_work_floats(void);
+int pn2x_iknet_forward(int m, int frame, const float *kp, const float *R, const float *t, const float *w1, const float *b1,
+                       const float *wh, const float *bh, const float *wo, const float *bo, float *work, float *kp_hf,
+                       float *raw_quat, float *theta, void *stream);
+
+/*
  * ---- training-mode building blocks on point-major activations (hotrack_amd/csrc/train_ops.hip) --------------------------
  * The reference trains every grouped MLP as Conv2d(1x1) + BatchNorm2d + ReLU on channel-major (B, C, S, K) tensors
  * (pointnet_utils.py:399-403, :460-462, :504-506, :577-581).  A 1x1 convolution is a GEMM over all R = B*S*K positions

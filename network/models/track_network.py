@@ -18,17 +18,24 @@ class HandTrackModel(nn.Module):
     """hand_model (models/hand_model.HandModel, e.g. a MANO layer with the reference's call signature): enables the
     hand-pose particle optimisation of the reference's `use_optimization` branch (track_network.py:142-156, :203-211) on
     top of the HandTrackNet tracking loop.  In the reference that branch sits behind IKNet, which supplies the initial
-    MANO pose code and global pose; IKNet needs the MANO assets and its checkpoint, so here those two inputs come from a
+    MANO pose code and global pose.  With `IKnet` (models/iknet.IKNet, needs a hand model) it does here too, and without the
+    optimisation IKNet's pose drives the hand model's keypoints (`pred_kp`); without an IKNet those two inputs come from a
     stand-in with the same role (`_pose_init`): the pose code of the previous frame's optimum and the rigid fit of the hand
     model's keypoints to HandTrackNet's prediction (device Kabsch).  Everything downstream -- visibility mask, candidate
     evaluation, update rule, what is fed to the next frame -- is the reference's."""
 
     def __init__(self, cfg, handnet, IKnet=None, hand_model=None):
         super().__init__()
-        if IKnet is not None:
-            raise NotImplementedError("IKNet needs the MANO assets and its checkpoint (out of scope)")
         self.device = cfg["device"]
         self.handnet = handnet(cfg)
+        # IKNet (models/iknet.py; reference track_network.py:165-211): HandTrackNet's keypoints -> MANO pose code + global pose,
+        # which seed the pose optimiser (use_optimization) or drive the hand model's keypoints (pred_kp) -- needs a hand model
+        self.IKnet = None
+        if IKnet is not None:
+            if hand_model is None:
+                raise ValueError("HandTrackModel: IKNet needs a hand model")
+            self.IKnet = IKnet if isinstance(IKnet, nn.Module) else IKnet(cfg, hand_model=hand_model)
+            print("[Hand Tracking] Use IKNet: True")
         self.use_graph = True  # GPU + fused backend: one captured HIP graph per (N, keypoints) shape, replayed per frame
         self._graphs = {}
         self.use_optimization = bool(cfg.get("use_optimization", False)) and hand_model is not None
@@ -103,6 +110,34 @@ class HandTrackModel(nn.Module):
         graph.replay()
         return {k: (v.clone() if torch.is_tensor(v) else {kk: vv.clone() for kk, vv in v.items()}) for k, v in out.items()}
 
+    def _iknet_step(self, kp, palm_template, graph_ok):
+        """IKNet on HandTrackNet's keypoints (1,21,3): (raw_quat, MANO_theta, canon_pose, init_kp_handframe).  On the kernel
+        route with graphs on it is a replay of a captured graph keyed by shape next to HandTrackNet's (same invalidation rules;
+        a change of IKNet's weights re-captures): the palm fit and seven launches, no host sync."""
+        ik = self.IKnet
+        if not (graph_ok and ik.kernel_route(kp)):
+            return ik.solve(kp, palm_template)
+        key = ("iknet", tuple(kp.shape), tuple(palm_template.shape))
+        folded = ik.folded_weights()
+        g = self._graphs.get(key)
+        if g is None or g[3] is not folded:
+            buf = (kp.clone(), palm_template.clone())
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                ik.solve(*buf)  # warm-up: constants, library handles
+            torch.cuda.current_stream().wait_stream(side)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                out = ik.solve(*buf)
+            g = self._graphs[key] = (graph, buf, out, folded)
+        graph, buf, out, _ = g
+        buf[0].copy_(kp, non_blocking=True)
+        buf[1].copy_(palm_template, non_blocking=True)
+        graph.replay()
+        raw, theta, canon, kp_hf = out
+        return raw.clone(), theta.clone(), {k: v.clone() for k, v in canon.items()}, kp_hf.clone()
+
     def _pose_init(self, pred_kp, prev_theta):
         """Stand-in for IKNet's two outputs (see the class docstring): MANO_theta (1,45) and global_pose."""
         from hotrack_amd import ext
@@ -139,8 +174,11 @@ class HandTrackModel(nn.Module):
         rets = []
         graph_ok = (self.use_graph and pointnet_utils.fused_backend() is not None and not self.training
                     and not torch.is_grad_enabled() and torch.device(self.device).type == "cuda")
-        if self.use_optimization:
+        # (IKNet's graph needs no fused HandTrackNet backend: its own kernels and the device Kabsch)
+        ik_graph_ok = (self.use_graph and not self.training and not torch.is_grad_enabled() and torch.device(self.device).type == "cuda")
+        if self.use_optimization or self.IKnet is not None:
             flag_dict["IKNet_flag"] = True  # HandTrackNet also returns the keypoint visibility mask (hand_network.py:149-155)
+        if self.use_optimization:
             if "sdf_volume" in input[0]:
                 self.optimizer.load_volume(input[0]["sdf_volume"], input[0].get("voxel_scale"))
             elif self.optimizer.sdf_volume is None:
@@ -157,24 +195,37 @@ class HandTrackModel(nn.Module):
                 ret = self._graph_step(points, data["jittered_hand_kp"].to(self.device).float(), palm_template, flag_dict)
             else:
                 ret = self.handnet(data, flag_dict)
-            if self.use_optimization:  # track_network.py:142-156 (IKNet's role: _pose_init), :203-211
+            if self.use_optimization or self.IKnet is not None:
                 ret["baseline_pred_kp"] = ret["pred_kp"].clone()
+            if self.use_optimization:  # track_network.py:142-156, :203-211
                 if self.opt_shape is not None:  # :174-193: the template takes effect from the next frame on
                     if self._shape_due(i):
                         shape_code = self.opt_shape.optimize(ret["baseline_pred_kp"], use_old=self.shape_mode == 3).clone()
                         palm_template = self._shaped_palm_template(shape_code)
                     data["pred_beta"] = shape_code
                     ret["pred_beta"] = shape_code
-                theta0, pose0 = self._pose_init(ret["baseline_pred_kp"], prev_theta)
+                if self.IKnet is not None:
+                    theta0, pose0 = self._iknet(ret, data, palm_template, ik_graph_ok)
+                else:  # (without IKNet: the stand-in for its two outputs)
+                    theta0, pose0 = self._pose_init(ret["baseline_pred_kp"], prev_theta)
                 obj_pose = data["pred_obj_pose"] if (self.use_pred_obj_pose and "pred_obj_pose" in data) else data["gt_obj_pose"]
                 kp, theta, rot, trans = self.optimizer.optimize(theta0, pose0, ret["baseline_pred_kp"], last_kp, ret["pred_kp_vis_mask"],
                                                                 obj_pose, data.get("pred_beta"), data["projection"], data["background_mask"])
                 ret["pred_kp"], ret["MANO_theta"] = kp, theta
                 ret["global_pose"] = {"rotation": rot.unsqueeze(0), "translation": trans.unsqueeze(-1)}
                 prev_theta = theta
+            elif self.IKnet is not None:  # track_network.py:196-200, hand_network.py:313-318
+                self._iknet(ret, data, palm_template, ik_graph_ok)
+                ret["pred_kp"] = self.IKnet.pose_keypoints(ret["raw_quat"], ret["global_pose"], data.get("pred_beta"))
             last_kp = (ret["pred_kp"] - centre).clone()
             rets.append(ret)
         return rets
+
+    def _iknet(self, ret, data, palm_template, graph_ok):
+        data["baseline_pred_kp"] = ret["baseline_pred_kp"]
+        raw, theta, canon, _ = self._iknet_step(ret["baseline_pred_kp"], palm_template, graph_ok)
+        ret["raw_quat"], ret["MANO_theta"], ret["global_pose"] = raw, theta, canon
+        return theta, canon
 
     def compute_loss(self, input, ret_dict_lst, flag_dict):
         total = {}

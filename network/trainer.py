@@ -22,6 +22,7 @@ import torch.nn.init as init
 from torch.optim import lr_scheduler
 
 from models.hand_network import HandTrackNet
+from models.iknet import IKNet, iknet_checkpoint, resolve_use_iknet
 from models.track_network import HandTrackModel, ObjTrackModel_Optimization
 
 
@@ -59,8 +60,8 @@ class Trainer(nn.Module):
         self.ckpt_dir = pjoin(cfg["experiment_dir"], "ckpt")
         os.makedirs(self.ckpt_dir, exist_ok=True)
         self.loss_weights = cfg["network"].get("loss_weight", {})
-        if cfg["network"]["type"] != "HandTrackNet":
-            raise NotImplementedError("only HandTrackNet is on this path (IKNet needs MANO assets)")
+        if cfg["network"]["type"] not in ("HandTrackNet", "iknet"):
+            raise NotImplementedError("network.type: HandTrackNet or iknet")
         self.optimizer = self.scheduler = None
         if cfg["track"] == "hand":
             self.model = HandTrackModel(cfg, handnet=HandTrackNet)
@@ -78,7 +79,12 @@ class Trainer(nn.Module):
                 from models.hand_model import SyntheticLBSHand
                 hm = SyntheticLBSHand(num_betas=10 if hm == "synthetic_shaped" else 0)
                 cfg["hand_model"] = hm  # the synthetic sequences pose the same model
-            if hm is not None and cfg.get("use_optimization", False):
+            if resolve_use_iknet(cfg):
+                self.log_string("track=hand_IKNet: HandTrackNet tracking + IKNet (%s; hand model: %s)" % (
+                    "hand-pose particle optimisation from IKNet's pose" if cfg.get("use_optimization", False) else
+                    "keypoints of the hand model driven by IKNet's pose", type(hm).__name__))
+                self.model = HandTrackModel(cfg, handnet=HandTrackNet, IKnet=IKNet, hand_model=hm)
+            elif hm is not None and cfg.get("use_optimization", False):
                 self.log_string("track=hand_IKNet: HandTrackNet tracking + hand-pose particle optimisation (hand model: %s; "
                                 "IKNet's initial pose from the previous frame + a rigid keypoint fit)" % type(hm).__name__)
                 self.model = HandTrackModel(cfg, handnet=HandTrackNet, hand_model=hm)
@@ -88,7 +94,7 @@ class Trainer(nn.Module):
         elif cfg["track"] == "obj_opt":
             self.model = ObjTrackModel_Optimization(cfg)
         elif not cfg["track"]:
-            self.model = HandTrackNet(cfg)
+            self.model = IKNet(cfg, hand_model=cfg.get("hand_model")) if cfg["network"]["type"] == "iknet" else HandTrackNet(cfg)
             params = [p for p in self.model.parameters() if p.requires_grad]
             # Whole-step HIP graph (forward + loss + backward + Adam in one replay): the training step is ~800 small
             # launches and host-bound (about 14 ms of Python / autograd dispatch against 10.4 ms of kernels), so
@@ -230,6 +236,11 @@ class Trainer(nn.Module):
             else:
                 sd = torch.load(name, map_location=self.device)["model"]
                 ckpt.update({"handnet." + k: v for k, v in sd.items()})
+            if getattr(self.model, "IKnet", None) is not None:  # reference trainer.py:218-227
+                name = iknet_checkpoint(self.cfg)
+                self.log_string(f"Load IKNet model from {name}")
+                sd = IKNet.drop_hand_model_keys(torch.load(name, map_location=self.device)["model"])
+                ckpt.update({"IKnet." + k: v for k, v in sd.items()})
         else:
             e = self.cfg.get("resume_epoch", -1)
             name = pjoin(self.ckpt_dir, f"model_{e:04d}.pt") if e and e > 0 else get_last_model(self.ckpt_dir)
