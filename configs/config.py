@@ -39,6 +39,9 @@ def get_config(args, save=True):
     for key, item in cli.items():
         if item is not None and key not in ("mode_name", "debug", "debug_save", "save", "num_workers", "synthetic_frames", "max_iters"):
             overwrite_config(cfg, key, key.split("/"), item)
+    if not isinstance(cfg.get("opt"), dict):
+        cfg["opt"] = {}
+    cfg["opt"].setdefault("fused_pose", False)  # hand-pose particle optimiser on the device-resident route (--fused_hand_pose)
     data_cfg = _load("data_config", cfg["data_config"])
     cfg["pointnet"] = {k: _load("pointnet_config", v) for k, v in cfg["pointnet_cfg"].items()}
 

@@ -1,0 +1,502 @@
+// hand_pose.hip -- the hand-pose particle optimiser (reference gf_optimize_hand_pose.evaluate / optimize,
+// optimization_hand.py:215-293, :335-394) on the device: per iteration one launch that evaluates every candidate hand and
+// one single-workgroup launch that applies the update.  No host sync, no atomics, no waits between workgroups.
+//
+// hand_pose_eval_kernel.  The hand model is a plain linear-blend-skinning table (HandModel.skinning_tables): a workgroup
+// stages, once, per vertex and weight the rest offset v_rest - j_k and the weight (one float4) plus the packed joint indices
+// into LDS; after that each of its four WAVES evaluates candidates on its own (candidate = wave, no workgroup barrier in
+// the candidate loop, so one wave's serial skeleton phase overlaps the other waves' vertex phase):
+//   skeleton: lane j owns joint j -- its pose block's angles, Rodrigues, then the kinematic chain level by level (the parent's
+//             transform comes by cross-lane read), 12 floats per joint into the wave's LDS slot;
+//   keypoint terms: lane j's distance to pred_kp / last_frame_kp, three wave sums;
+//   vertices: lane l skins vertices l, l + 64, ... (13 for 778), and per vertex transforms into the object frame, reads the
+//             nearest voxel with pn2s_nearest's arithmetic (sdf_device.h) and the silhouette pixel -- the two gathers of four
+//             vertices are issued before any is used;
+//   then wave reductions (max, five minima, an integer count) and lane 0 writes the candidate's terms.
+// Sums over lanes are xor butterflies, the vertex loop is in index order: a candidate's result does not depend on the grid.
+//
+// hand_pose_update_kernel.  One workgroup of 1024 threads: gate, energies, weights and the 20 weighted sums (thread-strided
+// in index order, a butterfly per wave, an in-order sum over the 16 waves -- as hand_shape.hip), then thread 0 applies the
+// reference's update with its host branches as selects and threads 64..108 the 45 joint angles.
+#include <hip/hip_fp16.h>
+
+#include "pn2_common.h"
+#include "sdf_device.h"
+#include "../../include/pn2_ext.h"
+
+namespace pn2 {
+namespace hpose {
+
+constexpr int MAXP = 8192, MAXV = 1024, NJ = 21, MAXK = 4, NC = 10, NPOSE = 45, ND = 6 + NC;
+// state (pn2_ext.h): rotation, translation, joint angles, search size, previous search size, previous success
+constexpr int S_R = 0, S_T = 9, S_THETA = 12, S_SEARCH = 57, S_PREV = 73, S_PREV_OK = 89;
+constexpr int TERMS = 4;  // per candidate: gate-independent energy, attraction term, penetration, 0
+constexpr int UT = 1024, UW = UT / 64, NV = 3 + 1 + ND;  // update: w, w E, [E < origin], w * [qw | sample]
+
+struct Frame {
+    int P, V, K;
+    const int *parents, *pose_block;
+    const float *rest_j, *rest_v;
+    const int *pack;
+    const float *skin_w, *comps;
+    float theta_scale;
+    const float *pre, *state, *pred_kp, *last_kp;
+    const unsigned char *vis;
+    const float *obj_r, *obj_t;
+    const void *vol;
+    int res;
+    float voxel_scale;
+    const unsigned char *mask;
+    int h, w;
+    float fx, fy, cx, cy;
+    float w_sil, w_pen, w_vis, w_invis, w_tmp, w_attr;
+    float *terms, *out_verts, *out_kp;
+};
+
+inline size_t eval_lds_bytes(int v, int k) { return (size_t)v * k * sizeof(float4) + (size_t)v * sizeof(int); }
+
+template <bool F16>
+__device__ __forceinline__ float vol_round(float x) {  // a value of the volume's dtype (products and sums stay in it)
+    if constexpr (F16) return __half2float(__float2half(x));
+    else return x;
+}
+
+__device__ __forceinline__ float wave_sum_xor(float v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+
+// [qw | pre[q] * search] of optimize() (:343-345): qw = sqrt(1 - x^2 - y^2 - z^2), NaN for a negative argument
+__device__ __forceinline__ void candidate_sample(const float *__restrict__ pre, int q, const float *search, float *s) {
+#pragma unroll
+    for (int k = 0; k < ND; ++k) s[1 + k] = pre[(size_t)q * ND + k] * search[k];
+    s[0] = sqrtf(1.0f - s[1] * s[1] - s[2] * s[2] - s[3] * s[3]);
+}
+
+// evaluate()'s last two lines (:284-293): the attraction term counts only when candidate 0 penetrates
+__device__ __forceinline__ float candidate_energy(const float *__restrict__ terms, int q, bool gate) {
+    const float base = terms[(size_t)q * TERMS], attr = terms[(size_t)q * TERMS + 1];
+    return gate ? base + attr : base;
+}
+
+// hand_model.rodrigues: I + sin K + (1 - cos) K K with K the cross-product matrix of aa / max(|aa|, 1e-12)
+__device__ __forceinline__ void rodrigues(float ax, float ay, float az, float *R) {
+    const float n = fmaxf(sqrtf(ax * ax + ay * ay + az * az), 1e-12f);
+    const float kx = ax / n, ky = ay / n, kz = az / n;
+    const float s = sinf(n), oc = 1.0f - cosf(n);
+    R[0] = 1.0f + oc * (-(kz * kz) - ky * ky);  R[1] = s * -kz + oc * (kx * ky);            R[2] = s * ky + oc * (kx * kz);
+    R[3] = s * kz + oc * (kx * ky);            R[4] = 1.0f + oc * (-(kz * kz) - kx * kx);  R[5] = s * -kx + oc * (ky * kz);
+    R[6] = s * -ky + oc * (kx * kz);           R[7] = s * kx + oc * (ky * kz);             R[8] = 1.0f + oc * (-(ky * ky) - kx * kx);
+}
+
+template <bool F16>
+__global__ void __launch_bounds__(256) hand_pose_eval_kernel(const Frame A) {
+    extern __shared__ float4 dyn[];
+    __shared__ float4 skel[4][NJ * 3];  // per wave and joint: R (9, row-major), t (3)
+    const int V = A.V, K = A.K, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    float4 *tab = dyn;                                  // (K, V): v_rest - j_k, w_k
+    int *pk = reinterpret_cast<int *>(dyn + (size_t)K * V);  // (V): joint indices 5 bits each, tip-region bits from bit 20
+
+    for (int i = tid; i < V; i += 256) {
+        const int p = A.pack[i];
+        pk[i] = p;
+        const float vx = A.rest_v[3 * i], vy = A.rest_v[3 * i + 1], vz = A.rest_v[3 * i + 2];
+#pragma unroll
+        for (int k = 0; k < MAXK; ++k)
+            if (k < K) {
+                const int jn = min((p >> (5 * k)) & 31, NJ - 1);
+                tab[k * V + i] = make_float4(vx - A.rest_j[3 * jn], vy - A.rest_j[3 * jn + 1], vz - A.rest_j[3 * jn + 2], A.skin_w[i * K + k]);
+            }
+    }
+
+    // ---- this lane's joint (lanes >= 21 carry joint 0's tables and are masked where it matters) ------------------------------
+    const bool is_joint = lane < NJ;
+    const int j = is_joint ? lane : 0;
+    const int pa = j == 0 ? 0 : min(max(A.parents[j], 0), j - 1);
+    int blk = A.pose_block[j];
+    if (blk < 0 || blk >= NPOSE / 3 || j == 0) blk = -1;
+    int depth = 0;
+    for (int s = 0, q = j; s < NJ; ++s)
+        if (q != 0) {
+            q = min(max(A.parents[q], 0), q - 1);
+            ++depth;
+        }
+    int maxdepth = depth;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) maxdepth = max(maxdepth, __shfl_xor(maxdepth, m, 64));
+    float off[3], pred[3], last[3] = {0.f, 0.f, 0.f}, cth[3] = {0.f, 0.f, 0.f}, cm[NC][3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        off[a] = A.rest_j[3 * j + a] - A.rest_j[3 * pa + a];
+        pred[a] = A.pred_kp[3 * j + a];
+        if (A.last_kp) last[a] = A.last_kp[3 * j + a];
+        if (blk >= 0) cth[a] = A.state[S_THETA + 3 * blk + a];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) cm[c][a] = blk >= 0 ? A.comps[c * NPOSE + 3 * blk + a] : 0.f;
+    }
+    const float visf = A.vis[j] ? 1.f : 0.f;
+    const unsigned long long vis_bits = __ballot(is_joint && A.vis[j]);
+    const int nvis = __popcll(vis_bits), ninv = NJ - nvis;
+    const float root[3] = {A.rest_j[0], A.rest_j[1], A.rest_j[2]};
+
+    float R0[9], t0[3], search[ND], oR[9], ot[3];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        R0[k] = A.state[S_R + k];
+        oR[k] = A.obj_r[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        t0[k] = A.state[S_T + k];
+        ot[k] = A.obj_t[k];
+    }
+#pragma unroll
+    for (int k = 0; k < ND; ++k) search[k] = A.state[S_SEARCH + k];
+    const float fw = (float)A.w, fh = (float)A.h;
+    float4 *sk = skel[wave];
+    __syncthreads();
+
+    for (int c0 = blockIdx.x * 4 + wave; c0 < A.P; c0 += gridDim.x * 4) {
+        const int c = __builtin_amdgcn_readfirstlane(c0);
+        float sp[1 + ND], S[9], Rg[9], tr[3];
+        candidate_sample(A.pre, c, search, sp);
+        quat_to_matrix(sp[0], sp[1], sp[2], sp[3], S);
+        mat3_mul(R0, S, Rg);  // curr_r @ quat2mat(q), used as the root's rotation
+#pragma unroll
+        for (int k = 0; k < 3; ++k) tr[k] = t0[k] + sp[4 + k];
+
+        // ---- skeleton -----------------------------------------------------------------------------------------------------------
+        float th[3], Rl[9], R[9], t[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            float acc = sp[7] * cm[0][a];
+#pragma unroll
+            for (int cc = 1; cc < NC; ++cc) acc = fmaf(sp[7 + cc], cm[cc][a], acc);
+            th[a] = cth[a] + acc * A.theta_scale;
+        }
+        rodrigues(th[0], th[1], th[2], Rl);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) R[k] = Rg[k];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) t[k] = root[k];
+        for (int lvl = 1; lvl <= maxdepth; ++lvl) {
+            float pR[9], pt[3];
+#pragma unroll
+            for (int k = 0; k < 9; ++k) pR[k] = __shfl(R[k], pa, 64);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) pt[k] = __shfl(t[k], pa, 64);
+            if (depth == lvl) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k)
+                    t[k] = pt[k] + fmaf(pR[3 * k + 2], off[2], fmaf(pR[3 * k + 1], off[1], pR[3 * k] * off[0]));
+                if (blk >= 0) mat3_mul(pR, Rl, R);
+                else {
+#pragma unroll
+                    for (int k = 0; k < 9; ++k) R[k] = pR[k];
+                }
+            }
+        }
+        __builtin_amdgcn_wave_barrier();  // the previous candidate's reads of this slot are issued before these writes
+        if (is_joint) {
+            sk[3 * j] = make_float4(R[0], R[1], R[2], R[3]);
+            sk[3 * j + 1] = make_float4(R[4], R[5], R[6], R[7]);
+            sk[3 * j + 2] = make_float4(R[8], t[0], t[1], t[2]);
+        }
+        __builtin_amdgcn_wave_barrier();
+
+        // ---- keypoint terms (:236-240, :259-262) -------------------------------------------------------------------------------
+        const float kx = t[0] + tr[0], ky = t[1] + tr[1], kz = t[2] + tr[2];
+        if (A.out_kp && is_joint) {
+            float *o = A.out_kp + ((size_t)c * NJ + j) * 3;
+            o[0] = kx; o[1] = ky; o[2] = kz;
+        }
+        float dx = kx - pred[0], dy = ky - pred[1], dz = kz - pred[2];
+        const float err = sqrtf(dx * dx + dy * dy + dz * dz);
+        dx = kx - last[0]; dy = ky - last[1]; dz = kz - last[2];
+        const float terr = sqrtf(dx * dx + dy * dy + dz * dz);
+        const float vis_sum = wave_sum_xor(is_joint ? err * visf : 0.f);
+        const float inv_sum = wave_sum_xor(is_joint ? err * (1.f - visf) : 0.f);
+        const float tmp_sum = wave_sum_xor(is_joint ? terr : 0.f);
+
+        // ---- vertices ------------------------------------------------------------------------------------------------------------
+        float pen = 0.f, fmin5[5];
+        int count = 0;
+#pragma unroll
+        for (int f = 0; f < 5; ++f) fmin5[f] = __builtin_inff();
+        constexpr int U = 4;
+        for (int v0 = lane; v0 < V; v0 += 64 * U) {
+            float sdf[U];
+            int bg[U], bits[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int vv = min(v0 + 64 * u, V - 1);  // slots past the end repeat the last vertex and are masked below
+                const int p = pk[vv];
+                bits[u] = p >> 20;
+                float x = 0.f, y = 0.f, z = 0.f;
+#pragma unroll
+                for (int k = 0; k < MAXK; ++k)
+                    if (k < K) {
+                        const float4 e = tab[k * V + vv];
+                        const int jn = min((p >> (5 * k)) & 31, NJ - 1);
+                        const float4 a = sk[3 * jn], b = sk[3 * jn + 1], d = sk[3 * jn + 2];
+                        const float qx = fmaf(a.z, e.z, fmaf(a.y, e.y, a.x * e.x)) + d.y;
+                        const float qy = fmaf(b.y, e.z, fmaf(b.x, e.y, a.w * e.x)) + d.z;
+                        const float qz = fmaf(d.x, e.z, fmaf(b.w, e.y, b.z * e.x)) + d.w;
+                        x = k == 0 ? qx * e.w : fmaf(qx, e.w, x);
+                        y = k == 0 ? qy * e.w : fmaf(qy, e.w, y);
+                        z = k == 0 ? qz * e.w : fmaf(qz, e.w, z);
+                    }
+                x += tr[0]; y += tr[1]; z += tr[2];
+                if (A.out_verts && v0 + 64 * u < V) {
+                    float *o = A.out_verts + ((size_t)c * V + vv) * 3;
+                    o[0] = x; o[1] = y; o[2] = z;
+                }
+                float ox, oy, oz;
+                to_object_frame(x, y, z, ot, oR, ox, oy, oz);
+                const int flat = nearest_voxel(ox, oy, oz, A.voxel_scale, A.res);
+                if constexpr (F16) sdf[u] = __half2float(reinterpret_cast<const __half *>(A.vol)[flat]);
+                else sdf[u] = reinterpret_cast<const float *>(A.vol)[flat];
+                // world2point2D (:13-21), .long() = truncation toward zero, clamp to the image (:242-246)
+                const float px = x / z * A.fx + A.cx, py = y / z * A.fy + A.cy;
+                const int row = min(max((int)fminf(fmaxf(py, -1.f), fh), 0), A.h - 1);
+                const int col = min(max((int)fminf(fmaxf(px, -1.f), fw), 0), A.w - 1);
+                bg[u] = A.mask[(size_t)row * A.w + col];
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (v0 + 64 * u >= V) continue;
+                const float s = sdf[u];
+                if (s < 0.f) pen = fmaxf(pen, -s);
+                const float tip = s > 0.f ? s : 0.f;  // sdf * (sdf > 0)
+#pragma unroll
+                for (int f = 0; f < 5; ++f)
+                    if ((bits[u] >> f) & 1) fmin5[f] = fminf(fmin5[f], tip);
+                count += bg[u] != 0;
+            }
+        }
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) {
+            pen = fmaxf(pen, __shfl_xor(pen, m, 64));
+            count += __shfl_xor(count, m, 64);
+#pragma unroll
+            for (int f = 0; f < 5; ++f) fmin5[f] = fminf(fmin5[f], __shfl_xor(fmin5[f], m, 64));
+        }
+
+        // ---- the candidate's terms, added in evaluate()'s order with torch's type promotion (:277-293) ----------------------------
+        if (lane == 0) {
+            float e = ((float)count / (float)V) * A.w_sil;
+            e = e + vol_round<F16>(pen * A.w_pen);
+            e = e + (vis_sum / (float)max(nvis, 1)) * A.w_vis;
+            e = e + (inv_sum / (float)max(ninv, 1)) * A.w_invis;
+            if (A.last_kp) e = e + (tmp_sum / (float)NJ) * A.w_tmp;
+            constexpr int tipkp[5] = {8, 12, 16, 20, 4};  // get_attraction_loss: fingers whose tip keypoint is invisible
+            float attr = 0.f;
+#pragma unroll
+            for (int f = 0; f < 5; ++f) attr = vol_round<F16>(attr + (((vis_bits >> tipkp[f]) & 1ull) ? fmin5[f] * 0.f : fmin5[f]));
+            float *o = A.terms + (size_t)c * TERMS;
+            o[0] = e;
+            o[1] = vol_round<F16>(attr * A.w_attr);
+            o[2] = pen;
+            o[3] = 0.f;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) hand_pose_energy_kernel(int P, const float *__restrict__ terms, float *__restrict__ energy) {
+    const bool gate = terms[2] != 0.f;
+    for (int q = blockIdx.x * 256 + threadIdx.x; q < P; q += gridDim.x * 256) energy[q] = candidate_energy(terms, q, gate);
+}
+
+__global__ void __launch_bounds__(UT) hand_pose_update_kernel(int P, const float *__restrict__ pre, const float *__restrict__ terms,
+                                                              const float *__restrict__ comps, float theta_scale, float c2, float beta,
+                                                              float one_minus_beta, float *__restrict__ state, float *__restrict__ trace) {
+    __shared__ float red[UW * NV], tot[NV];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const bool gate = terms[2] != 0.f;
+    const float origin = candidate_energy(terms, 0, gate);
+    float search[ND], acc[NV];
+#pragma unroll
+    for (int k = 0; k < ND; ++k) search[k] = state[S_SEARCH + k];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) acc[v] = 0.f;
+    for (int q = tid; q < P; q += UT) {
+        const float e = candidate_energy(terms, q, gate);
+        const bool better = e < origin;
+        const float w = (origin - e) * (better ? 1.f : 0.f);  // (origin_energy - energy) * better_mask, NaN and all (:351)
+        float s[1 + ND];
+        candidate_sample(pre, q, search, s);
+        acc[0] += w;
+        acc[1] += e * w;
+        acc[2] += better ? 1.f : 0.f;
+#pragma unroll
+        for (int k = 0; k < 1 + ND; ++k) acc[3 + k] += s[k] * w;
+    }
+#pragma unroll
+    for (int v = 0; v < NV; ++v) acc[v] = wave_sum_xor(acc[v]);
+    if (lane == 0) {
+#pragma unroll
+        for (int v = 0; v < NV; ++v) red[wave * NV + v] = acc[v];
+    }
+    __syncthreads();
+    if (tid < NV) {
+        float a = 0.f;
+        for (int w = 0; w < UW; ++w) a += red[w * NV + tid];
+        tot[tid] = a;
+    }
+    __syncthreads();
+    const float wsum = tot[0];
+    const bool success = tot[2] > 0.f;
+
+    if (tid >= 64 && tid < 64 + NPOSE && success) {  // curr_theta += (mt[7:] @ comps[:10]) * theta_scale (:363)
+        const int a = tid - 64;
+        float d = (tot[3 + 7] / wsum) * comps[a];
+#pragma unroll
+        for (int c = 1; c < NC; ++c) d = fmaf(tot[3 + 7 + c] / wsum, comps[c * NPOSE + a], d);
+        state[S_THETA + a] = state[S_THETA + a] + d * theta_scale;
+    }
+    if (tid != 0) return;
+
+    const float mean_e = success ? tot[1] / wsum : origin;
+    float mt[1 + ND];
+#pragma unroll
+    for (int k = 0; k < 1 + ND; ++k) mt[k] = tot[3 + k] / wsum;  // NaN without a better candidate: selected away below
+    const float qn = sqrtf(mt[0] * mt[0] + mt[1] * mt[1] + mt[2] * mt[2] + mt[3] * mt[3]);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) mt[k] /= qn;
+    if (success) {
+        float R0[9], S[9], Rn[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) R0[k] = state[S_R + k];
+        quat_to_matrix(mt[0], mt[1], mt[2], mt[3], S);
+        mat3_mul(R0, S, Rn);
+        // re-projection onto SO(3): Gram-Schmidt on the first two rows (rotation_from_ortho6d + transpose, :377-378)
+        float x[3] = {Rn[0], Rn[1], Rn[2]}, yr[3] = {Rn[3], Rn[4], Rn[5]}, z[3], y[3];
+        normalize3(x);
+        z[0] = x[1] * yr[2] - x[2] * yr[1]; z[1] = x[2] * yr[0] - x[0] * yr[2]; z[2] = x[0] * yr[1] - x[1] * yr[0];
+        normalize3(z);
+        y[0] = z[1] * x[2] - z[2] * x[1]; y[1] = z[2] * x[0] - z[0] * x[2]; y[2] = z[0] * x[1] - z[1] * x[0];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            state[S_R + k] = x[k];
+            state[S_R + 3 + k] = y[k];
+            state[S_R + 6 + k] = z[k];
+            state[S_T + k] = state[S_T + k] + mt[4 + k];
+        }
+    }
+    // update_seach_size on mean_transform[:, 1:] (:295-298) and its smoothing (:381-386)
+    float s[ND], nrm = 0.f;
+#pragma unroll
+    for (int k = 0; k < ND; ++k) {
+        s[k] = fabsf(success ? mt[1 + k] : 0.f) + 1e-3f;
+        nrm += s[k] * s[k];
+    }
+    nrm = sqrtf(nrm);
+    const bool both = state[S_PREV_OK] != 0.f && success;
+    if (trace) {
+        trace[0] = origin;
+        trace[1] = mean_e;
+        trace[2] = success ? 1.f : 0.f;
+    }
+#pragma unroll
+    for (int k = 0; k < ND; ++k) {
+        float ns = mean_e * c2 * s[k] / nrm + 1e-3f;
+        if (both) ns = beta * ns + one_minus_beta * state[S_PREV + k];
+        state[S_SEARCH + k] = ns;
+        if (success) state[S_PREV + k] = ns;
+        if (trace) trace[3 + k] = ns;
+    }
+    state[S_PREV_OK] = success ? 1.f : 0.f;
+}
+
+}  // namespace hpose
+}  // namespace pn2
+
+using namespace pn2;
+using namespace pn2::hpose;
+
+extern "C" int pn2x_hand_pose_opt_supported(int p, int v, int j, int k, int d_pose, int res) {
+    return (p >= 1 && p <= MAXP && v >= 1 && v <= MAXV && j == NJ && k >= 1 && k <= MAXK && d_pose == NC && res >= 1 &&
+            res <= 1024 && (res & 1) == 1) ? 1 : 0;
+}
+
+extern "C" long pn2x_hand_pose_opt_work_floats(int p) { return p < 0 ? (long)PN2_EINVAL : (long)TERMS * p; }
+
+static int eval_launch(const Frame &A, int f16, hipStream_t st) {
+    static PerDeviceOnce raised;
+    if (raised.first_use()) {
+        (void)hipFuncSetAttribute((const void *)hand_pose_eval_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)eval_lds_bytes(MAXV, MAXK));
+        (void)hipFuncSetAttribute((const void *)hand_pose_eval_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)eval_lds_bytes(MAXV, MAXK));
+    }
+    // a workgroup's four waves take a candidate each; the grid covers the compute units at most three times and the
+    // candidates are dealt evenly over it
+    const int wgs = (A.P + 3) / 4, cap = 3 * num_compute_units(), rounds = (wgs + cap - 1) / cap, grid = (wgs + rounds - 1) / rounds;
+    if (f16) hipLaunchKernelGGL(hand_pose_eval_kernel<true>, dim3(grid), dim3(256), eval_lds_bytes(A.V, A.K), st, A);
+    else hipLaunchKernelGGL(hand_pose_eval_kernel<false>, dim3(grid), dim3(256), eval_lds_bytes(A.V, A.K), st, A);
+    return PN2_OK;
+}
+
+#define HAND_POSE_MODEL_PARAMS                                                                                                    \
+    int p, int v, int j, int k, const int *parents, const int *pose_block, const float *rest_joints, const float *rest_verts,    \
+        const int *skin_pack, const float *skin_w, const float *comps, float theta_scale, const float *pre,                       \
+        const float *pred_kp, const float *last_kp, const unsigned char *vis_mask, const float *obj_r, const float *obj_t,        \
+        const void *vol, int vol_f16, int res, float voxel_scale, const unsigned char *mask, int h, int w, float fx, float fy,    \
+        float cx, float cy, float w_sil, float w_pen, float w_vis, float w_invis, float w_temporal, float w_attr
+
+static int fill_frame(Frame &A, HAND_POSE_MODEL_PARAMS) {
+    if (p < 1 || v < 1 || j < 1 || k < 1 || res < 1 || (res & 1) == 0 || !(voxel_scale > 0.f) || h < 1 || w < 1 ||
+        (vol_f16 != 0 && vol_f16 != 1))
+        return PN2_EINVAL;
+    if (!pn2x_hand_pose_opt_supported(p, v, j, k, NC, res) || (long)h * w >= (1L << 31)) return PN2_ERANGE;
+    if (!parents || !pose_block || !rest_joints || !rest_verts || !skin_pack || !skin_w || !comps || !pre || !pred_kp || !vis_mask ||
+        !obj_r || !obj_t || !vol || !mask)
+        return PN2_ENULL;
+    A.P = p; A.V = v; A.K = k;
+    A.parents = parents; A.pose_block = pose_block; A.rest_j = rest_joints; A.rest_v = rest_verts; A.pack = skin_pack;
+    A.skin_w = skin_w; A.comps = comps; A.theta_scale = theta_scale; A.pre = pre; A.pred_kp = pred_kp; A.last_kp = last_kp;
+    A.vis = vis_mask; A.obj_r = obj_r; A.obj_t = obj_t; A.vol = vol; A.res = res; A.voxel_scale = voxel_scale; A.mask = mask;
+    A.h = h; A.w = w; A.fx = fx; A.fy = fy; A.cx = cx; A.cy = cy;
+    A.w_sil = w_sil; A.w_pen = w_pen; A.w_vis = w_vis; A.w_invis = w_invis; A.w_tmp = w_temporal; A.w_attr = w_attr;
+    A.state = nullptr; A.terms = nullptr; A.out_verts = nullptr; A.out_kp = nullptr;
+    return PN2_OK;
+}
+
+#define HAND_POSE_MODEL_ARGS                                                                                                     \
+    p, v, j, k, parents, pose_block, rest_joints, rest_verts, skin_pack, skin_w, comps, theta_scale, pre, pred_kp, last_kp,     \
+        vis_mask, obj_r, obj_t, vol, vol_f16, res, voxel_scale, mask, h, w, fx, fy, cx, cy, w_sil, w_pen, w_vis, w_invis,        \
+        w_temporal, w_attr
+
+extern "C" int pn2x_hand_pose_energy(HAND_POSE_MODEL_PARAMS, const float *state, float *work, float *energy, float *out_verts,
+                                     float *out_kp, void *stream) {
+    Frame A;
+    const int rc = fill_frame(A, HAND_POSE_MODEL_ARGS);
+    if (rc != PN2_OK) return rc;
+    if (!state || !work || !energy) return PN2_ENULL;
+    A.state = state; A.terms = work; A.out_verts = out_verts; A.out_kp = out_kp;
+    hipStream_t st = (hipStream_t)stream;
+    eval_launch(A, vol_f16, st);
+    hipLaunchKernelGGL(hand_pose_energy_kernel, dim3((p + 255) / 256), dim3(256), 0, st, p, work, energy);
+    return check_launch();
+}
+
+extern "C" int pn2x_hand_pose_opt(HAND_POSE_MODEL_PARAMS, int iterations, double scaling_coefficient2, double beta, float *state,
+                                  float *work, float *trace, void *stream) {
+    Frame A;
+    const int rc = fill_frame(A, HAND_POSE_MODEL_ARGS);
+    if (rc != PN2_OK) return rc;
+    if (iterations < 0) return PN2_EINVAL;
+    if (iterations > 4096) return PN2_ERANGE;
+    if (iterations == 0) return PN2_OK;
+    if (!state || !work) return PN2_ENULL;
+    A.state = state; A.terms = work;
+    hipStream_t st = (hipStream_t)stream;
+    for (int it = 0; it < iterations; ++it) {
+        eval_launch(A, vol_f16, st);
+        hipLaunchKernelGGL(hand_pose_update_kernel, dim3(1), dim3(UT), 0, st, p, pre, work, comps, theta_scale,
+                           (float)scaling_coefficient2, (float)beta, (float)(1.0 - beta), state,
+                           trace ? trace + (size_t)it * (3 + ND) : nullptr);
+    }
+    return check_launch();
+}

@@ -10,6 +10,7 @@
 #include <hip/hip_fp16.h>
 
 #include "pn2_common.h"
+#include "sdf_device.h"
 #include "../../include/pn2_sdf.h"
 
 namespace pn2 {
@@ -24,11 +25,6 @@ template <int FMT>
 __device__ __forceinline__ float vol_at(const void *v, int i) {
     if constexpr (FMT & 1) return __half2float(reinterpret_cast<const __half *>(v)[i]);
     else return reinterpret_cast<const float *>(v)[i];
-}
-
-__device__ __forceinline__ float clampf(float v, float lo, float hi) {  // torch.clamp: min(max(v, lo), hi)
-    v = v < lo ? lo : v;
-    return v > hi ? hi : v;
 }
 
 // One point of gf_optimize_obj.Distance (optimization_obj.py:184-228), in three steps so that callers can issue
@@ -127,15 +123,6 @@ __device__ __forceinline__ float trilinear(const SdfVol &A, float vx, float vy, 
     return tri_blend(A, t, d);
 }
 
-// (p - t) @ R with the fixed chain o_j = fma(q2, R2j, fma(q1, R1j, q0*R0j)) (same chain in oracle/sdf_oracle.c).
-__device__ __forceinline__ void to_object_frame(float px, float py, float pz, const float *t, const float *R, float &ox,
-                                                float &oy, float &oz) {
-    const float q0 = px - t[0], q1 = py - t[1], q2 = pz - t[2];
-    ox = fmaf(q2, R[6], fmaf(q1, R[3], q0 * R[0]));
-    oy = fmaf(q2, R[7], fmaf(q1, R[4], q0 * R[1]));
-    oz = fmaf(q2, R[8], fmaf(q1, R[5], q0 * R[2]));
-}
-
 __device__ __forceinline__ float block_sum_256(float v, float *sm) {  // sm: >= 4 floats of LDS; all threads get the sum
 #pragma unroll
     for (int o = 32; o; o >>= 1) v += __shfl_down(v, o);
@@ -199,33 +186,11 @@ sdf_particle_energy_kernel(int n, const float *__restrict__ pcld, const float *_
 // [16 .. 16+p) per-particle sdf_energy.
 constexpr int W_SEARCH = 0, W_PREV = 6, W_PREV_OK = 12, W_PREV_SCALAR = 13, W_TICKET = 14, W_ENERGY = 16;
 
-__device__ __forceinline__ void quat_to_matrix(float w, float x, float y, float z, float *m) {  // rotations.py:105-113
-    m[0] = 1.0f - 2.0f * y * y - 2.0f * z * z;  m[1] = 2.0f * x * y - 2.0f * z * w;         m[2] = 2.0f * x * z + 2.0f * y * w;
-    m[3] = 2.0f * x * y + 2.0f * z * w;         m[4] = 1.0f - 2.0f * x * x - 2.0f * z * z;  m[5] = 2.0f * y * z - 2.0f * x * w;
-    m[6] = 2.0f * x * z - 2.0f * y * w;         m[7] = 2.0f * y * z + 2.0f * x * w;         m[8] = 1.0f - 2.0f * x * x - 2.0f * y * y;
-}
-
-__device__ __forceinline__ void mat3_mul(const float *a, const float *b, float *o) {  // o = a @ b, fixed fma chain
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) o[3 * i + j] = fmaf(a[3 * i + 2], b[6 + j], fmaf(a[3 * i + 1], b[3 + j], a[3 * i] * b[j]));
-}
-
 // sample = [qw, pre*search] (:259-261)
 __device__ __forceinline__ void particle_sample(const float *__restrict__ pre, int i, const float *search, float *s) {
 #pragma unroll
     for (int k = 0; k < 6; ++k) s[1 + k] = pre[6 * i + k] * search[k];
     s[0] = sqrtf(1.0f - s[1] * s[1] - s[2] * s[2] - s[3] * s[3]);
-}
-
-__device__ __forceinline__ void normalize3(float *v) {  // rotations.py:328-340
-    const float mag = sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-    if (mag > 1e-8f) {
-        v[0] /= mag; v[1] /= mag; v[2] /= mag;
-    } else {
-        v[0] = 1.0f; v[1] = 0.0f; v[2] = 0.0f;
-    }
 }
 
 struct OptArgs {
@@ -392,23 +357,7 @@ __global__ void __launch_bounds__(256) obj_optimize_kernel(const OptArgs A) {
 }
 
 // ---- gf_optimize_hand_pose.query_sdf (+ get_penetration_loss) (optimization_hand.py:252-268) -----------------------
-// torch's `tensor // scalar` on floats is c10::div_floor_floating: fmod, (a - mod) / b, sign fix-up, floor, and a
-// +1 if that floor fell below the rounding error -- for b > 0 and |a/b| < 2^22 that is exactly the mathematical
-// floor of the real quotient a/b (derivation in DESIGN.md section 8).  fmodf costs ~100 instructions and made this
-// kernel ALU-bound (39 us); the same integer comes from one correctly rounded division and one exact-sign FMA
-// remainder:  k = floor(RN(a/b));  r = fma(-k, b, a)  has the sign of the true remainder a - k*b (an FMA rounds
-// once and never rounds a non-zero value to zero, so its SIGN is exact -- its magnitude is not: a tiny negative a
-// gives r = b - tiny, which rounds to b, hence the second test looks at the sign of a - (k+1)*b instead of r >= b);
-// k is off by at most one, fixed by the two sign tests.  Beyond 2^22 both versions are far outside the clamp
-// range [-res/2, res/2] applied next, so the voxel index is identical for every finite input
-// (tests: bit-exact indices vs the literal restatement in oracle/sdf_oracle.c on adversarial k*b +- ulp inputs).
-__device__ __forceinline__ float div_floor(float a, float b) {
-    float k = floorf(a / b);
-    if (fmaf(-k, b, a) < 0.0f) k -= 1.0f;                  // a - k*b < 0: k is one too large
-    else if (fmaf(-(k + 1.0f), b, a) >= 0.0f) k += 1.0f;   // a - (k+1)*b >= 0: k is one too small
-    return k;
-}
-
+// (index arithmetic: div_floor / nearest_voxel in sdf_device.h, shared with hand_pose.hip)
 template <bool F16>
 __global__ void __launch_bounds__(256)
 sdf_nearest_kernel(int n, const float *__restrict__ hand, const float *__restrict__ obj_r, const float *__restrict__ obj_t,
@@ -421,8 +370,6 @@ sdf_nearest_kernel(int n, const float *__restrict__ hand, const float *__restric
     for (int k = 0; k < 9; ++k) R[k] = obj_r[k];
 #pragma unroll
     for (int k = 0; k < 3; ++k) t[k] = obj_t[k];
-    const int half = res / 2;
-    const float fh = (float)half;
     float pen = 0.0f;
     constexpr int U = 4;
     for (int j0 = threadIdx.x; j0 < n; j0 += 256 * U) {
@@ -434,10 +381,7 @@ sdf_nearest_kernel(int n, const float *__restrict__ hand, const float *__restric
             const size_t e = (size_t)b * n + min(j0 + 256 * u, n - 1);
             float ox, oy, oz;
             to_object_frame(hand[3 * e], hand[3 * e + 1], hand[3 * e + 2], t, R, ox, oy, oz);
-            const int ix = (int)clampf(div_floor(ox, voxel_scale), -fh, fh) + half;
-            const int iy = (int)clampf(div_floor(oy, voxel_scale), -fh, fh) + half;
-            const int iz = (int)clampf(div_floor(oz, voxel_scale), -fh, fh) + half;
-            flat[u] = (ix * res + iy) * res + iz;
+            flat[u] = nearest_voxel(ox, oy, oz, voxel_scale, res);
             if constexpr (F16) h[u] = reinterpret_cast<const __half *>(vol)[flat[u]];
             else v[u] = reinterpret_cast<const float *>(vol)[flat[u]];
         }

@@ -1,0 +1,74 @@
+// sdf_device.h -- device arithmetic shared by the particle optimisers' kernels (sdf.hip, hand_pose.hip): the object-frame
+// transform, torch's floor division and the nearest-voxel index of gf_optimize_hand_pose.query_sdf, and the small rotation
+// helpers of the pose updates.  One definition, so that a lookup fused into another kernel reads the same voxel as
+// pn2s_nearest for every input.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace pn2 {
+
+__device__ __forceinline__ float clampf(float v, float lo, float hi) {  // torch.clamp: min(max(v, lo), hi)
+    v = v < lo ? lo : v;
+    return v > hi ? hi : v;
+}
+
+// (p - t) @ R with the fixed chain o_j = fma(q2, R2j, fma(q1, R1j, q0*R0j)) (same chain in oracle/sdf_oracle.c).
+__device__ __forceinline__ void to_object_frame(float px, float py, float pz, const float *t, const float *R, float &ox,
+                                                float &oy, float &oz) {
+    const float q0 = px - t[0], q1 = py - t[1], q2 = pz - t[2];
+    ox = fmaf(q2, R[6], fmaf(q1, R[3], q0 * R[0]));
+    oy = fmaf(q2, R[7], fmaf(q1, R[4], q0 * R[1]));
+    oz = fmaf(q2, R[8], fmaf(q1, R[5], q0 * R[2]));
+}
+
+// torch's `tensor // scalar` on floats is c10::div_floor_floating: fmod, (a - mod) / b, sign fix-up, floor, and a
+// +1 if that floor fell below the rounding error -- for b > 0 and |a/b| < 2^22 that is exactly the mathematical
+// floor of the real quotient a/b (derivation in DESIGN.md section 8).  fmodf costs ~100 instructions and made this
+// kernel ALU-bound (39 us); the same integer comes from one correctly rounded division and one exact-sign FMA
+// remainder:  k = floor(RN(a/b));  r = fma(-k, b, a)  has the sign of the true remainder a - k*b (an FMA rounds
+// once and never rounds a non-zero value to zero, so its SIGN is exact -- its magnitude is not: a tiny negative a
+// gives r = b - tiny, which rounds to b, hence the second test looks at the sign of a - (k+1)*b instead of r >= b);
+// k is off by at most one, fixed by the two sign tests.  Beyond 2^22 both versions are far outside the clamp
+// range [-res/2, res/2] applied next, so the voxel index is identical for every finite input
+// (tests: bit-exact indices vs the literal restatement in oracle/sdf_oracle.c on adversarial k*b +- ulp inputs).
+__device__ __forceinline__ float div_floor(float a, float b) {
+    float k = floorf(a / b);
+    if (fmaf(-k, b, a) < 0.0f) k -= 1.0f;                  // a - k*b < 0: k is one too large
+    else if (fmaf(-(k + 1.0f), b, a) >= 0.0f) k += 1.0f;   // a - (k+1)*b >= 0: k is one too small
+    return k;
+}
+
+// Flat index of the voxel query_sdf reads for the object-frame point (ox, oy, oz) (optimization_hand.py:252-262): per axis
+// clamp(q // voxel_scale, -(res/2), res/2) + res/2, res odd.
+__device__ __forceinline__ int nearest_voxel(float ox, float oy, float oz, float voxel_scale, int res) {
+    const int half = res / 2;
+    const float fh = (float)half;
+    const int ix = (int)clampf(div_floor(ox, voxel_scale), -fh, fh) + half;
+    const int iy = (int)clampf(div_floor(oy, voxel_scale), -fh, fh) + half;
+    const int iz = (int)clampf(div_floor(oz, voxel_scale), -fh, fh) + half;
+    return (ix * res + iy) * res + iz;
+}
+
+__device__ __forceinline__ void quat_to_matrix(float w, float x, float y, float z, float *m) {  // rotations.py:105-113
+    m[0] = 1.0f - 2.0f * y * y - 2.0f * z * z;  m[1] = 2.0f * x * y - 2.0f * z * w;         m[2] = 2.0f * x * z + 2.0f * y * w;
+    m[3] = 2.0f * x * y + 2.0f * z * w;         m[4] = 1.0f - 2.0f * x * x - 2.0f * z * z;  m[5] = 2.0f * y * z - 2.0f * x * w;
+    m[6] = 2.0f * x * z - 2.0f * y * w;         m[7] = 2.0f * y * z + 2.0f * x * w;         m[8] = 1.0f - 2.0f * x * x - 2.0f * y * y;
+}
+
+__device__ __forceinline__ void mat3_mul(const float *a, const float *b, float *o) {  // o = a @ b, fixed fma chain
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) o[3 * i + j] = fmaf(a[3 * i + 2], b[6 + j], fmaf(a[3 * i + 1], b[3 + j], a[3 * i] * b[j]));
+}
+
+__device__ __forceinline__ void normalize3(float *v) {  // rotations.py:328-340
+    const float mag = sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+    if (mag > 1e-8f) {
+        v[0] /= mag; v[1] /= mag; v[2] /= mag;
+    } else {
+        v[0] = 1.0f; v[1] = 0.0f; v[2] = 0.0f;
+    }
+}
+
+}  // namespace pn2

@@ -916,3 +916,118 @@ def iknet_forward(kp: torch.Tensor, R: torch.Tensor, t: torch.Tensor, w1, b1, wh
                                      _native._ptr(bo, "bo", f32, 60), work.data_ptr(), kp_hf.data_ptr(), raw.data_ptr(),
                                      theta.data_ptr(), _native._stream(kp)), "iknet_forward")
     return raw, theta, kp_hf
+
+
+# ---- hand-pose particle optimiser on the device (include/pn2_ext.h: pn2x_hand_pose_energy / pn2x_hand_pose_opt) ---------------
+_cf, _cd = ctypes.c_float, ctypes.c_double
+_HAND_POSE_COMMON = ([_ci] * 4 + [_vp] * 7 + [_cf] + [_vp] * 7 + [_ci, _ci, _cf, _vp, _ci, _ci] + [_cf] * 10)
+_lib.pn2x_hand_pose_opt_supported.argtypes = [_ci] * 6
+_lib.pn2x_hand_pose_opt_supported.restype = _ci
+_lib.pn2x_hand_pose_opt_work_floats.argtypes = [_ci]
+_lib.pn2x_hand_pose_opt_work_floats.restype = _cl
+_lib.pn2x_hand_pose_energy.argtypes = _HAND_POSE_COMMON + [_vp] * 6
+_lib.pn2x_hand_pose_energy.restype = _ci
+_lib.pn2x_hand_pose_opt.argtypes = _HAND_POSE_COMMON + [_ci, _cd, _cd] + [_vp] * 4
+_lib.pn2x_hand_pose_opt.restype = _ci
+HAND_POSE_STATE_FLOATS = 90   # curr_r (9), curr_t (3), curr_theta (45), search (16), previous search (16), previous success
+HAND_POSE_TRACE_FLOATS = 19   # E[0], mean_E, success, search after the update (16)
+HAND_POSE_WEIGHTS = ("sil_loss", "penetrate_sum_loss", "vis_regu_loss", "invis_regu_loss", "temporal_smooth", "attraction_loss")
+
+
+def hand_pose_opt_supported(p: int, v: int, j: int, k: int, d_pose: int = 10, res: int = 151) -> bool:
+    return bool(_lib.pn2x_hand_pose_opt_supported(int(p), int(v), int(j), int(k), int(d_pose), int(res)))
+
+
+def hand_pose_model(tables: dict, device) -> dict:
+    """HandModel.skinning_tables() as the device arrays the hand-pose kernels read (built once per model and device):
+    int32 parents / pose_block, float32 rest and shape tables, skin_w, comps, and skin_pack = the K joint indices of a vertex
+    (5 bits each) with, from bit 20, the tip regions (fingers 0..4 of tips / finger_offsets) the vertex belongs to."""
+    f32, i32 = torch.float32, torch.int32
+    idx = tables["skin_idx"].long()
+    V, K = idx.shape
+    pack = torch.zeros(V, dtype=torch.long)
+    for k in range(K):
+        pack |= idx[:, k] << (5 * k)
+    offs = [int(o) for o in tables["finger_offsets"]]
+    for f in range(5):
+        pack[tables["tips"][offs[f]:offs[f + 1]].long().unique()] |= 1 << (20 + f)
+    m = {"V": V, "K": K, "J": int(tables["parents"].numel()),
+         "parents": tables["parents"].to(device, i32).contiguous(), "pose_block": tables["pose_block"].to(device, i32).contiguous(),
+         "rest_joints": tables["rest_joints"].to(device, f32).contiguous(), "rest_verts": tables["rest_verts"].to(device, f32).contiguous(),
+         "skin_pack": pack.to(device, i32).contiguous(), "skin_w": tables["skin_w"].to(device, f32).contiguous(),
+         "comps": tables["comps"].to(device, f32).contiguous(), "fingers_ok": all(offs[f + 1] > offs[f] for f in range(5))}
+    if "shape_joints" in tables:
+        D = tables["shape_joints"].shape[0]
+        m["shape_joints"] = tables["shape_joints"].to(device, f32).reshape(D, -1).contiguous()
+        m["shape_verts"] = tables["shape_verts"].to(device, f32).reshape(D, -1).contiguous()
+    return m
+
+
+def hand_pose_rest(model: dict, beta: torch.Tensor = None):
+    """The frame's shaped rest joints (J,3) and vertices (V,3): rest + beta @ shape_* (device ops, no host read)."""
+    if beta is None or "shape_joints" not in model:
+        return model["rest_joints"], model["rest_verts"]
+    b = beta.to(model["rest_joints"]).reshape(1, -1)
+    return ((model["rest_joints"] + (b @ model["shape_joints"]).view(-1, 3)).contiguous(),
+            (model["rest_verts"] + (b @ model["shape_verts"]).view(-1, 3)).contiguous())
+
+
+def _hand_pose_args(model, rest, theta_scale, pre, pred_kp, last_kp, vis_mask, obj_r, obj_t, volume, voxel_scale, mask, proj, weights):
+    f32, u8 = torch.float32, torch.uint8
+    V, K, J = model["V"], model["K"], model["J"]
+    if pre.dim() != 2 or pre.shape[1] != 16:
+        raise ValueError(f"hand_pose: pre {tuple(pre.shape)} is not (P, 16)")
+    P = pre.shape[0]
+    if volume.dim() != 3 or len(set(volume.shape)) != 1 or volume.dtype not in (torch.float16, f32):
+        raise ValueError(f"hand_pose: volume {tuple(volume.shape)} {volume.dtype} is not a cubic fp16 / fp32 volume")
+    res = volume.shape[0]
+    if mask.dim() != 2:
+        raise ValueError(f"hand_pose: mask {tuple(mask.shape)} is not (h, w)")
+    h, w = mask.shape
+    if not hand_pose_opt_supported(P, V, J, K, 10, res):
+        raise ValueError(f"hand_pose: P = {P}, V = {V}, J = {J}, K = {K}, res = {res} outside 1..8192, 1..1024, 21, 1..4, odd <= 1024")
+    rest_j, rest_v = rest
+    args = [P, V, J, K, _native._ptr(model["parents"], "parents", torch.int32, J), _native._ptr(model["pose_block"], "pose_block", torch.int32, J),
+            _native._ptr(rest_j, "rest_joints", f32, J * 3), _native._ptr(rest_v, "rest_verts", f32, V * 3),
+            _native._ptr(model["skin_pack"], "skin_pack", torch.int32, V), _native._ptr(model["skin_w"], "skin_w", f32, V * K),
+            _native._ptr(model["comps"], "comps", f32, 45 * 45), float(theta_scale), _native._ptr(pre, "pre", f32, P * 16),
+            _native._ptr(pred_kp, "pred_kp", f32, J * 3), None if last_kp is None else _native._ptr(last_kp, "last_kp", f32, J * 3),
+            _native._ptr(vis_mask, "vis_mask", u8, J), _native._ptr(obj_r, "obj_r", f32, 9), _native._ptr(obj_t, "obj_t", f32, 3),
+            _native._ptr(volume, "volume", volume.dtype, res ** 3), 1 if volume.dtype == torch.float16 else 0, res, float(voxel_scale),
+            _native._ptr(mask, "mask", u8, h * w), h, w, float(proj["fx"]), float(proj["fy"]), float(proj["cx"]), float(proj["cy"])]
+    return P, args + [float(weights[k]) for k in HAND_POSE_WEIGHTS]
+
+
+def hand_pose_energy(model, rest, theta_scale, pre, state, pred_kp, last_kp, vis_mask, obj_r, obj_t, volume, voxel_scale, mask, proj,
+                     weights, with_geometry: bool = False):
+    """One evaluation of all candidates at `state` (pn2x_hand_pose_energy): model = hand_pose_model(...), rest = hand_pose_rest(...),
+    pre (P,16), state (90,), pred_kp / last_kp (21,3) (last_kp may be None), vis_mask (21,) uint8, obj_r (3,3), obj_t (3,), volume
+    (res,res,res) fp16 / fp32, mask (h,w) uint8 (non-zero = background), proj {fx, fy, cx, cy}, weights {energy_weight names}.
+    -> (energy (P,), vertices (P,V,3) or None, keypoints (P,21,3) or None)."""
+    P, args = _hand_pose_args(model, rest, theta_scale, pre, pred_kp, last_kp, vis_mask, obj_r, obj_t, volume, voxel_scale, mask, proj, weights)
+    f32, dev = torch.float32, pre.device
+    work = torch.empty(int(_lib.pn2x_hand_pose_opt_work_floats(P)), dtype=f32, device=dev)
+    energy = torch.empty(P, dtype=f32, device=dev)
+    verts = torch.empty((P, model["V"], 3), dtype=f32, device=dev) if with_geometry else None
+    kp = torch.empty((P, model["J"], 3), dtype=f32, device=dev) if with_geometry else None
+    with torch.cuda.device(dev):
+        _native._check(_native._call(_lib.pn2x_hand_pose_energy, "hand_pose_energy", None, *args,
+                                     _native._ptr(state, "state", f32, HAND_POSE_STATE_FLOATS), work.data_ptr(), energy.data_ptr(),
+                                     None if verts is None else verts.data_ptr(), None if kp is None else kp.data_ptr(),
+                                     _native._stream(pre)), "hand_pose_energy")
+    return energy, verts, kp
+
+
+def hand_pose_opt(model, rest, theta_scale, pre, state, pred_kp, last_kp, vis_mask, obj_r, obj_t, volume, voxel_scale, mask, proj,
+                  weights, iterations: int, scaling_coefficient2: float, beta: float, trace: bool = False):
+    """`iterations` x (evaluate, update) of gf_optimize_hand_pose.optimize on the device (pn2x_hand_pose_opt), arguments as
+    hand_pose_energy; `state` (90,) is updated in place.  -> trace (iterations, 19) or None."""
+    P, args = _hand_pose_args(model, rest, theta_scale, pre, pred_kp, last_kp, vis_mask, obj_r, obj_t, volume, voxel_scale, mask, proj, weights)
+    f32, dev = torch.float32, pre.device
+    work = torch.empty(int(_lib.pn2x_hand_pose_opt_work_floats(P)), dtype=f32, device=dev)
+    tr = torch.empty((int(iterations), HAND_POSE_TRACE_FLOATS), dtype=f32, device=dev) if trace else None
+    with torch.cuda.device(dev):
+        _native._check(_native._call(_lib.pn2x_hand_pose_opt, "hand_pose_opt", None, *args, int(iterations), float(scaling_coefficient2),
+                                     float(beta), _native._ptr(state, "state", f32, HAND_POSE_STATE_FLOATS), work.data_ptr(),
+                                     None if tr is None else tr.data_ptr(), _native._stream(pre)), "hand_pose_opt")
+    return tr

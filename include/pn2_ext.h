@@ -351,6 +351,64 @@ int pn2x_hand_shape_opt(int p, int d, int t, int iterations, const float *k0, co
                         float *trace, void *stream);
 
 /*
+ * Hand-pose particle optimiser (reference gf_optimize_hand_pose.evaluate / optimize, network/models/optimization_hand.py:215-293,
+ * :335-394) on the device (hotrack_amd/csrc/hand_pose.hip): hand_pose_eval_kernel evaluates all p candidate hands in one
+ * launch, hand_pose_update_kernel (one workgroup) applies an iteration's update.
+ *
+ * The hand model is a linear-blend-skinning table (HandModel.skinning_tables) at the frame's shape:
+ *   parents (j) int32, parents[i] < i, joint 0 the root;  pose_block (j) int32: the 3-vector of the 45 joint angles that rotates
+ *   joint i, -1 for none;  rest_joints (j,3), rest_verts (v,3): rest + beta @ shape_*;  skin_w (v,k);  skin_pack (v) int32: bits
+ *   5i..5i+4 the joint of weight i < k, bits 20..24 the tip regions (fingers 0..4 of get_attraction_loss) the vertex belongs to;
+ *   comps (45,45), rows [0,10) used;  theta_scale (30).  Keypoints are the joint positions.
+ * state, 90 floats: [0,9) curr_r row-major, [9,12) curr_t, [12,57) curr_theta, [57,73) search size, [73,89) previous search
+ * size, [89] previous success (0 / 1).  Candidate q (pre (p,16), row 0 zero):
+ *     s = pre[q] * search;  quat = [sqrt(1 - s0^2 - s1^2 - s2^2), s0, s1, s2]  (NaN for a negative argument, as the reference)
+ *     root rotation = curr_r @ quat2mat(quat) (used as a matrix, not through axis-angle);  translation = curr_t + s[3:6];
+ *     joint angles = curr_theta + (s[6:16] @ comps[:10]) * theta_scale;  Rodrigues, kinematic chain, skinning (fp32)
+ *     per vertex: object frame and nearest voxel exactly as pn2s_nearest (obj_r (3,3), obj_t (3), vol res^3 fp16 / fp32, res odd);
+ *       penetration = max |sdf| [sdf < 0];  per finger min of sdf [sdf > 0] over its tip region;  silhouette pixel
+ *       (row, col) = trunc(y/z*fy+cy, x/z*fx+cx) clamped to the h x w byte image `mask` (non-zero = background), count / v
+ *     keypoints: visible / invisible mean distance to pred_kp (21,3) under vis_mask (21 bytes) with clamp(count, 1) denominators,
+ *       mean distance to last_kp (21,3), or no temporal term when last_kp is NULL
+ *     energy = sil w_sil + pen w_pen + vis w_vis + invis w_invis + temporal w_temporal + attraction w_attr, added in that order;
+ *       penetration, attraction and their products with the weights are rounded to the volume's type; the attraction term
+ *       counts for every candidate only if candidate 0 penetrates.
+ * work: pn2x_hand_pose_opt_work_floats(p) floats (per candidate: energy without attraction, attraction term, penetration, 0).
+ *
+ * pn2x_hand_pose_energy: one evaluation at `state` -> energy (p); out_verts (p,v,3) / out_kp (p,21,3) or NULL: the candidates'
+ * vertices and keypoints as the optimiser's device function computes them (tests, diagnostics).
+ * pn2x_hand_pose_opt: `iterations` x (evaluate, update); state in/out.  Update (:349-386, host branches as selects):
+ *     w = (E[0] - E) [E < E[0]];  success = any(E < E[0]);  mean_E = success ? sum w E / sum w : E[0];  mt = sum w [quat | s] / sum w;
+ *     mt[:4] /= |mt[:4]|;  on success curr_r = gram_schmidt_rows(curr_r @ quat2mat(mt[:4])), curr_t += mt[4:7],
+ *     curr_theta += (mt[7:] @ comps[:10]) * theta_scale;  sz = |success ? mt[1:] : 0| + 1e-3;
+ *     search = mean_E * scaling_coefficient2 * sz / ||sz|| + 1e-3;  if (previous success && success) search = beta search +
+ *     (1 - beta) previous search;  if (success) previous search = search;  previous success = success.
+ *   trace (iterations, 19) or NULL: per iteration [E[0], mean_E, success, search after the update].
+ * Sums run in a fixed order (xor butterflies inside a wave, waves in index order), no atomics, no waits between workgroups:
+ * two runs give bitwise-equal results.  No host sync or allocation (capturable).  Limits (pn2x_hand_pose_opt_supported): 1 <= p <=
+ * 8192, 1 <= v <= 1024, j == 21, 1 <= k <= 4, d_pose == 10 pose components, res odd and <= 1024.  Errors, checked before any
+ * device work: PN2_EINVAL for a size < 1, an even res, voxel_scale <= 0, vol_f16 not 0 / 1 or iterations < 0; PN2_ERANGE beyond
+ * the limits (or h * w >= 2^31, iterations > 4096); PN2_ENULL for a NULL pointer other than last_kp, out_verts, out_kp, trace;
+ * iterations == 0 returns PN2_OK and touches nothing.
+ */
+int pn2x_hand_pose_opt_supported(int p, int v, int j, int k, int d_pose, int res);
+long pn2x_hand_pose_opt_work_floats(int p);
+int pn2x_hand_pose_energy(int p, int v, int j, int k, const int *parents, const int *pose_block, const float *rest_joints,
+                          const float *rest_verts, const int *skin_pack, const float *skin_w, const float *comps, float theta_scale,
+                          const float *pre, const float *pred_kp, const float *last_kp, const unsigned char *vis_mask,
+                          const float *obj_r, const float *obj_t, const void *vol, int vol_f16, int res, float voxel_scale,
+                          const unsigned char *mask, int h, int w, float fx, float fy, float cx, float cy, float w_sil, float w_pen,
+                          float w_vis, float w_invis, float w_temporal, float w_attr, const float *state, float *work, float *energy,
+                          float *out_verts, float *out_kp, void *stream);
+int pn2x_hand_pose_opt(int p, int v, int j, int k, const int *parents, const int *pose_block, const float *rest_joints,
+                       const float *rest_verts, const int *skin_pack, const float *skin_w, const float *comps, float theta_scale,
+                       const float *pre, const float *pred_kp, const float *last_kp, const unsigned char *vis_mask,
+                       const float *obj_r, const float *obj_t, const void *vol, int vol_f16, int res, float voxel_scale,
+                       const unsigned char *mask, int h, int w, float fx, float fy, float cx, float cy, float w_sil, float w_pen,
+                       float w_vis, float w_invis, float w_temporal, float w_attr, int iterations, double scaling_coefficient2,
+                       double beta, float *state, float *work, float *trace, void *stream);
+
+/*
  * IKNet forward in eval mode (reference hand_network.py:264-322; hotrack_amd/csrc/iknet.hip) for m <= 16 rows, fp32:
  *     kp_hf = R^T (kp - t) / 0.2  (frame 0, 'kp')   or   kp * 5  (frame 1, 'camera'; R and t are not read)
  *     x     = [kp_hf | kp_hf - kp_hf[parent]]  coordinate-major (m, 126)

@@ -83,6 +83,97 @@ class HandModel(nn.Module):
         dev = next(iter(self.buffers()), pose_coeffs).device
         return basis[0].to(dev), basis[1].to(dev)
 
+    # Skinning tables are accepted when lbs_forward_from_tables reproduces forward() to this many metres (float64, a handful of
+    # seeded random poses: joint angles up to +-TABLES_CHECK_ANGLE rad, random global rotation, translation and shape code).
+    TABLES_TOL = 1e-6
+    TABLES_CHECK_ANGLE = 1.5
+
+    def _lbs_tables(self):
+        """The model's own claim to be a plain linear-blend-skinning hand: a dict with the entries skinning_tables() documents
+        (tensors on any device), or None.  skinning_tables() checks the claim against forward() before it hands it out."""
+        return None
+
+    def skinning_tables(self):
+        """The model as plain linear-blend-skinning tables (CPU tensors), or None when it is not such a model:
+          parents (J,) int64, topologically ordered, joint 0 the root;  pose_block (J,) int64: which 3-vector of the num_pose
+          pose dimensions rotates the joint (-1: no rotation of its own; the root takes the global rotation);
+          rest_joints (J,3), rest_verts (V,3), skin_idx (V,K) int64, skin_w (V,K), K <= 4;
+          shape_joints (D,J,3), shape_verts (D,V,3) when num_betas = D > 0 (else absent);
+          comps (num_pose, num_pose): the rows pca_comps2pose uses;
+          tips (T,) int64 and finger_offsets (6,) int64: the concatenated contact-zone vertex list of fingers 1..5 in the order
+          gf_optimize_hand_pose.set_hand_model builds it (finger i = tips[finger_offsets[i]:finger_offsets[i + 1]]).
+        Keypoints are the joint positions.  The tables are accepted only if lbs_forward_from_tables reproduces forward() in
+        float64 to TABLES_TOL at seeded random poses (and shape codes); a model with a pose-dependent corrective term (a MANO
+        layer with pose blend shapes) fails that check and returns None.  Built and checked once per model."""
+        if "_skinning_tables_cache" not in self.__dict__:
+            self.__dict__["_skinning_tables_cache"] = self._checked_tables()
+        return self.__dict__["_skinning_tables_cache"]
+
+    def _checked_tables(self):
+        t = self._lbs_tables()
+        if t is None:
+            return None
+        t = {k: (v.detach().cpu() if torch.is_tensor(v) else v) for k, v in t.items()}
+        J, K, D = t["parents"].numel(), t["skin_idx"].shape[1], int(self.num_betas)
+        if J > 21 or K > 4 or (D > 0) != ("shape_joints" in t) or any(int(t["parents"][j]) >= j for j in range(1, J)):
+            return None
+        zones = self.contact_zones
+        tips, offs = [], [0]
+        for i in range(5):
+            tips.extend(int(v) for v in zones[i + 1])
+            offs.append(len(tips))
+        t["tips"], t["finger_offsets"] = torch.tensor(tips, dtype=torch.long), torch.tensor(offs, dtype=torch.long)
+        g = torch.Generator().manual_seed(4321)
+        n, f64 = 6, torch.float64
+        pose = torch.cat([(torch.rand(n, 3, generator=g, dtype=f64) * 2 - 1) * 2.0,
+                          (torch.rand(n, self.num_pose, generator=g, dtype=f64) * 2 - 1) * self.TABLES_CHECK_ANGLE], dim=1)
+        trans = torch.rand(n, 3, generator=g, dtype=f64) - 0.5
+        beta = torch.randn(n, D, generator=g, dtype=f64) * 2 if D > 0 else None
+        dev = next(iter(self.buffers()), pose).device
+        with torch.no_grad():
+            want = None
+            for dt in (f64, torch.float32):  # float64 where the model computes in the pose's dtype, else its own precision
+                try:
+                    want = self.forward(th_pose_coeffs=pose.to(dev, dt), th_trans=trans.to(dev, dt),
+                                        th_betas=None if beta is None else beta.to(dev, dt))
+                    break
+                except RuntimeError:
+                    continue
+            if want is None:
+                return None
+            got = lbs_forward_from_tables(t, pose, trans, beta)
+        ok = all(tuple(a.shape) == tuple(b.shape) and bool((a.cpu().double() - b).abs().max() <= self.TABLES_TOL)
+                 for a, b in zip(want, got))
+        return t if ok else None
+
+
+def lbs_forward_from_tables(tables, pose, trans, beta=None):
+    """vertices (P,V,3), keypoints (P,J,3) of HandModel.skinning_tables() at pose (P, 3 + num_pose) = [global axis-angle | joint
+    angles], trans (P,3) and, for a model with a shape space, beta (P|1, D) -- in pose's dtype, on pose's device:
+        rest = rest_* + beta @ shape_*;  R_0 = rodrigues(pose[:, :3]), t_0 = rest_joints[0];
+        t_j = t_parent + R_parent (rest_j - rest_parent),  R_j = R_parent rodrigues(pose block pose_block[j]) (or R_parent);
+        v = sum_k w_k (R_k (rest_v - rest_k) + t_k) + trans;  keypoints = t_j + trans."""
+    dt, dev, P = pose.dtype, pose.device, pose.shape[0]
+    T = lambda k: tables[k].to(dev)
+    parents, block = [int(v) for v in tables["parents"]], [int(v) for v in tables["pose_block"]]
+    rest, verts = T("rest_joints").to(dt)[None], T("rest_verts").to(dt)[None]
+    if beta is not None and "shape_joints" in tables:
+        b = beta.to(dev, dt).reshape(-1, tables["shape_joints"].shape[0])
+        rest = rest + torch.einsum("pd,djc->pjc", b, T("shape_joints").to(dt))
+        verts = verts + torch.einsum("pd,dvc->pvc", b, T("shape_verts").to(dt))
+    Rl = rodrigues(pose[:, 3:].reshape(P, -1, 3))
+    R_w, t_w = [rodrigues(pose[:, :3])], [rest[:, 0].expand(P, 3)]
+    for j in range(1, len(parents)):
+        pa = parents[j]
+        t_w.append(t_w[pa] + (R_w[pa] @ (rest[:, j] - rest[:, pa])[..., None]).squeeze(-1))
+        R_w.append(R_w[pa] @ Rl[:, block[j]] if block[j] >= 0 else R_w[pa])
+    R_w, t_w = torch.stack(R_w, dim=1), torch.stack(t_w, dim=1)
+    idx, w = T("skin_idx"), T("skin_w").to(dt)
+    rel = verts[:, :, None, :] - rest[:, idx]                                   # (P|1, V, K, 3)
+    vk = (R_w[:, idx] @ rel[..., None]).squeeze(-1) + t_w[:, idx]
+    out = (vk * w[None, :, :, None]).sum(dim=2)
+    return out + trans[:, None, :], t_w + trans[:, None, :]
+
 
 class SyntheticLBSHand(HandModel):
     FINGERS = ((1, 2, 3, 4), (5, 6, 7, 8), (9, 10, 11, 12), (13, 14, 15, 16), (17, 18, 19, 20))  # thumb, index, middle, ring, pinky
@@ -189,6 +280,17 @@ class SyntheticLBSHand(HandModel):
 
     def pca_comps2pose(self, ncomps: int, pca: torch.Tensor) -> torch.Tensor:
         return pca.mm(self.th_comps[:ncomps])
+
+    def _lbs_tables(self):
+        block = [-1] * 21
+        for a, j in enumerate(self.art):
+            block[j] = a
+        t = {"parents": torch.tensor(self.parents, dtype=torch.long), "pose_block": torch.tensor(block, dtype=torch.long),
+             "rest_joints": self.rest_joints, "rest_verts": self.rest_verts, "skin_idx": self.skin_idx, "skin_w": self.skin_w,
+             "comps": self.th_comps}
+        if self.num_betas > 0:
+            t["shape_joints"], t["shape_verts"] = self.shape_joints, self.shape_verts
+        return t
 
     def forward(self, th_pose_coeffs, th_betas=None, th_trans=None, use_registed_beta=False, **_):
         P = th_pose_coeffs.shape[0]

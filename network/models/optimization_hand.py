@@ -18,6 +18,9 @@ What is different:
     `penetrate_sum_loss[0] != 0` every iteration (:359, :284); here both are torch.where selections on the device, so a frame
     is a fixed launch sequence (graph-capturable);
   * the silhouette mask is handed over by the caller (the reference reads a PNG per frame from the dataset folder, :316-331);
+  * with `opt.fused_pose` (off by default) the whole loop runs on the device: hotrack_amd/csrc/hand_pose.hip evaluates every
+    candidate in one launch per iteration (hand model as skinning tables, SDF, silhouette and keypoint terms fused) and a
+    second launch applies the update (`use_kernel`, `_optimize_fused`); the torch route below stays the default;
   * the object volume is handed over (`load_volume`) instead of being decoded from a DeepSDF latent (`load_obj`, :186-213:
     needs the checkpoints).
 """
@@ -165,6 +168,11 @@ class gf_optimize_hand_pose:
                                   {"penetrate_sum_loss": 1, "sil_loss": 0.1, "attraction_loss": 0.05, "vis_regu_loss": 10,
                                    "invis_regu_loss": 0, "temporal_smooth": 1})
         self.device = torch.device(cfg.get("device", device))
+        # the device-resident route (hotrack_amd/csrc/hand_pose.hip): opt-in, see use_kernel()
+        self.fused = bool((cfg.get("opt") or {}).get("fused_pose", False))
+        self._fused_said = False
+        self.keep_trace = False
+        self.trace = None
         self.theta_scale = 30
         self.beta = 0.9
         self.scaling_coefficient2 = 0.1
@@ -205,6 +213,68 @@ class gf_optimize_hand_pose:
     def set_obj_pose(self, init_obj_pose):  # the two lines of set_init_para that concern the object (:312-313)
         self.obj_r = init_obj_pose["rotation"].to(self.device).reshape(3, 3).float()
         self.obj_t = init_obj_pose["translation"].to(self.device).reshape(1, 1, 3).float()
+
+    # ---- the device-resident route --------------------------------------------------------------------------------------------
+    def _kernel_model(self):
+        """The hand model's skinning tables as device arrays (None when the model has no such tables), built once per model."""
+        hm = self.mano_layer_right
+        if self.__dict__.get("_kmodel_of") is not hm:
+            from hotrack_amd import ext
+            tables = hm.skinning_tables() if hasattr(hm, "skinning_tables") else None
+            self._kmodel = None if tables is None else ext.hand_pose_model(tables, self.device)
+            self._kmodel_of = hm
+        return self._kmodel
+
+    def _why_not_kernel(self):
+        if self.device.type != "cuda":
+            return f"the device is {self.device.type}"
+        if self.mano_layer_right is None or self._kernel_model() is None:
+            return "the hand model has no plain skinning tables (HandModel.skinning_tables() is None)"
+        if self.sdf_lookup is not None:
+            return "a test SDF lookup is injected (sdf_lookup)"
+        from hotrack_amd import ext
+        m = self._kernel_model()
+        if not (m["fingers_ok"] and self.optimize_dim == 16 and self.mano_layer_right.num_pose == 45 and
+                ext.hand_pose_opt_supported(self.particle_size, m["V"], m["J"], m["K"], self.ncomps, self.volume_size)):
+            return (f"the sizes are outside the kernel's limits (particles {self.particle_size}, vertices {m['V']}, joints {m['J']}, "
+                    f"weights per vertex {m['K']}, volume {self.volume_size})")
+        return None
+
+    def use_kernel(self) -> bool:
+        """True when optimize() runs on the device-resident route: `fused` is set (cfg['opt']['fused_pose']), the device is a
+        GPU, the hand model has skinning tables, no test SDF lookup is injected and the sizes are within the kernel's limits.
+        With `fused` set and a condition missing, the reason is logged once and the torch route runs."""
+        if not self.fused:
+            return False
+        why = self._why_not_kernel()
+        if why is not None and not self._fused_said:
+            self._fused_said = True
+            print(f"[Hand pose optimiser] fused_pose is set but the torch route runs: {why}")
+        return why is None
+
+    def _pack_state(self, search_size):
+        return torch.cat([self.curr_r.reshape(9).float(), self.curr_t.reshape(3).float(), self.curr_theta.reshape(45).float(),
+                          search_size.float(), search_size.float(), torch.ones(1, device=self.device)]).contiguous()
+
+    def _kernel_frame(self):
+        """This frame's inputs as the kernels read them, staged with device ops only."""
+        from hotrack_amd import ext
+        hm, m = self.mano_layer_right, self._kernel_model()
+        last = None if self.last_frame_kp is None else self.last_frame_kp.reshape(21, 3).float().contiguous()
+        return dict(model=m, rest=ext.hand_pose_rest(m, getattr(hm, "registered_beta", None)), theta_scale=self.theta_scale,
+                    pre=self.pre_sampled_particle.float().contiguous(), pred_kp=self.pred_kp.reshape(21, 3).float().contiguous(),
+                    last_kp=last, vis_mask=self.vis_mask.reshape(21).to(torch.uint8).contiguous(), obj_r=self.obj_r.contiguous(),
+                    obj_t=self.obj_t.reshape(3).contiguous(), volume=self.sdf_volume, voxel_scale=self.voxel_scale,
+                    mask=self.gt_background_mask.to(torch.bool).to(torch.uint8).contiguous(), proj=self.proj, weights=self.energy_weight)
+
+    def _optimize_fused(self):
+        """optimize()'s loop as `iteration` x (hand_pose_eval_kernel, hand_pose_update_kernel): no host sync (capturable)."""
+        from hotrack_amd import ext
+        state = self._pack_state(self.initial_scale)
+        self.trace = ext.hand_pose_opt(state=state, iterations=self.iteration, scaling_coefficient2=self.scaling_coefficient2,
+                                       beta=self.beta, trace=self.keep_trace, **self._kernel_frame())
+        self.curr_r, self.curr_t, self.curr_theta = state[0:9].view(1, 3, 3), state[9:12].view(1, 3, 1), state[12:57].view(1, 45)
+        self.search_size, self.prev_search_size, self.prev_success = state[57:73], state[73:89], state[89] != 0
 
     # ---- SDF part (one launch for lookup + penetration) --------------------------------------------------------------------
     sdf_lookup = None  # test hook: callable(optimiser, hand) -> (queried_sdf, penetration); None = hotrack_amd.sdf (GPU only)
@@ -303,10 +373,21 @@ class gf_optimize_hand_pose:
                  background_mask=None):
         """One frame: returns (final keypoints (1,21,3), MANO pose (1,45), rotation (3,3), translation (1,3)), :335-394."""
         self.set_init_para(init_mano, init_hand_pose, init_kp, last_frame_kp, vis_mask, init_obj_pose, hand_shape, projection, background_mask)
+        if self.use_kernel():
+            self._optimize_fused()
+        else:
+            self._optimize_torch()
+        curr_axisangle = quaternion_to_axis_angle(matrix_to_unit_quaternion(self.curr_r))
+        _, final_kp = self.mano_layer_right.forward(th_pose_coeffs=torch.cat([curr_axisangle, self.curr_theta], dim=-1),
+                                                    th_trans=self.curr_t.squeeze(-1), use_registed_beta=True)
+        return final_kp, self.curr_theta, self.curr_r.squeeze(0), self.curr_t.squeeze(-1)
+
+    def _optimize_torch(self):
         dev = self.device
         search_size = self.initial_scale
         prev_search_size = search_size
         prev_success = torch.ones((), dtype=torch.bool, device=dev)
+        trace = []
         for _ in range(self.iteration):
             sample_part = self.pre_sampled_particle * search_size
             sample_qw = torch.sqrt(1 - sample_part[:, 0] ** 2 - sample_part[:, 1] ** 2 - sample_part[:, 2] ** 2).unsqueeze(1)
@@ -339,8 +420,7 @@ class gf_optimize_hand_pose:
             search_size = torch.where(both, self.beta * search_size + (1 - self.beta) * prev_search_size, search_size)
             prev_search_size = torch.where(success, search_size, prev_search_size)
             prev_success = success
-
-        curr_axisangle = quaternion_to_axis_angle(matrix_to_unit_quaternion(self.curr_r))
-        _, final_kp = self.mano_layer_right.forward(th_pose_coeffs=torch.cat([curr_axisangle, self.curr_theta], dim=-1),
-                                                    th_trans=self.curr_t.squeeze(-1), use_registed_beta=True)
-        return final_kp, self.curr_theta, self.curr_r.squeeze(0), self.curr_t.squeeze(-1)
+            if self.keep_trace:
+                trace.append(torch.cat([torch.stack([origin_energy.float(), mean_energy.float(), success.float()]), search_size.reshape(-1)]))
+        self.search_size, self.prev_search_size, self.prev_success = search_size.reshape(-1), prev_search_size.reshape(-1), prev_success
+        self.trace = torch.stack(trace) if self.keep_trace else None

@@ -44,6 +44,9 @@ class HandTrackModel(nn.Module):
         if self.use_optimization:
             from .optimization_hand import gf_optimize_hand_pose
             self.optimizer = gf_optimize_hand_pose(cfg, hand_model=hand_model, particle_size=int(cfg.get("hand_particles", 5120)))
+            if self.optimizer.fused and self.optimizer.use_kernel():
+                print("[Hand Tracking] hand-pose optimisation on the device-resident route (opt.fused_pose): "
+                      "2 launches per iteration, no host sync")
         # shape-code estimation from HandTrackNet's keypoints (reference track_network.py:130-134, :174-193):
         # use_pred_hand_shape 1 = on frame 0, 2 = every 10 frames, 3 = every 10 frames over the bone lengths of all earlier
         # calls.  It runs where the reference's IKNet branch runs here (use_optimization with a hand model) and needs a

@@ -34,4 +34,8 @@ def add_args(parser):
                              "linear-blend-skinning stand-in of models/hand_model.py; 'synthetic_shaped' = the same with 10 shape "
                              "dimensions, for use_pred_hand_shape; a MANO layer is passed programmatically)")
     parser.add_argument("--hand_particles", type=int, default=None, help="candidate hands per optimiser iteration (reference: 5120)")
+    parser.add_argument("--fused_hand_pose", dest="opt/fused_pose", action="store_const", const=True, default=None,
+                        help="use_optimization: run the hand-pose particle optimiser on the device-resident route (two kernels per "
+                             "iteration, hotrack_amd/csrc/hand_pose.hip) instead of the torch route; needs a hand model with "
+                             "plain skinning tables")
     return parser
