@@ -174,11 +174,18 @@ def capsule_surface(rng, n, noise=0.0015):
     return p + rng.normal(0, noise, p.shape)
 
 
+def model_points(seed: int, n: int = 2048) -> torch.Tensor:
+    """(n,3) noise-free samples of the capsule surface in the object frame: the ground-truth cloud of the chamfer metrics
+    (`obj_model_points`; the reference samples the object's mesh, track_network.py:398).  A generator of its own, so the
+    sequences' other draws do not depend on it."""
+    return torch.from_numpy(capsule_surface(np.random.default_rng(seed), n, noise=0.0).astype(np.float32))
+
+
 class SyntheticObjectSequences(Dataset):
     """Sequences for `track: obj_opt` (reference SequenceData items as ObjTrackModel_Optimization.forward reads them,
     track_network.py:338-383): per frame obj_points (1,N,3) camera frame, gt_obj_pose, category / file_name / projection;
-    frame 0 also carries jittered_obj_pose (obj_jitter_cfg: r degrees, t metres) and -- in place of the DeepSDF latent the
-    reference decodes -- the object's SDF volume."""
+    frame 0 also carries jittered_obj_pose (obj_jitter_cfg: r degrees, t metres), -- in place of the DeepSDF latent the
+    reference decodes -- the object's SDF volume, and obj_model_points (2048,3): surface samples for the chamfer metrics."""
 
     def __init__(self, cfg, num_sequences: int, frames: int, res: int = 201, stride: float = 0.002):
         self.cfg, self.ns, self.nf = cfg, num_sequences, frames
@@ -211,6 +218,7 @@ class SyntheticObjectSequences(Dataset):
                 tj = t + rng.normal(0, float(jit.get("t", 0.03)) / 3, 3)
                 fr["jittered_obj_pose"] = {"rotation": f(Rj).reshape(1, 3, 3), "translation": f(tj).reshape(1, 3, 1)}
                 fr["sdf_volume"], fr["voxel_scale"] = self._vol, self.stride
+                fr["obj_model_points"] = model_points(70_000 + s)
             seq.append(fr)
             R = R @ _rot(w_axis, w)
             t = t + vel
@@ -222,7 +230,7 @@ class SyntheticHandObjectSequences(Dataset):
     branch, reference track_network.py:142-156, :203-211): a hand (cfg['hand_model'], models/hand_model.HandModel) grasping the
     synthetic capsule.  Per frame: hand_points sampled on the posed hand's vertices (+ sensor noise), gt / jittered keypoints,
     gt_hand_pose (palm template of the model's rest pose, rotation, translation), gt_obj_pose, projection, the silhouette's
-    background mask; frame 0 also carries the object's SDF volume.
+    background mask; frame 0 also carries the object's SDF volume and obj_model_points (2048,3) (surface samples, object frame).
 
     hand_beta: the hand's true shape code beta* for a hand model with a shape space -- None (the zero shape: the data of a
     model without one), a (num_betas,) vector for every sequence, or a float sigma: beta* ~ N(0, sigma^2) per sequence, drawn
@@ -284,5 +292,6 @@ class SyntheticHandObjectSequences(Dataset):
                   "category": [self.cfg["obj_category"][0]], "file_name": [f"synthetic_handobj_{s:03d}/{k:04d}"]}
             if k == 0:
                 fr["sdf_volume"], fr["voxel_scale"] = self._vol, self.stride
+                fr["obj_model_points"] = model_points(80_000 + s)
             seq.append(fr)
         return seq

@@ -1031,3 +1031,45 @@ def hand_pose_opt(model, rest, theta_scale, pre, state, pred_kp, last_kp, vis_ma
                                      float(beta), _native._ptr(state, "state", f32, HAND_POSE_STATE_FLOATS), work.data_ptr(),
                                      None if tr is None else tr.data_ptr(), _native._stream(pre)), "hand_pose_opt")
     return tr
+
+
+_lib.pn2x_posed_chamfer_partial_floats.argtypes = [_ci, _ci, _ci]
+_lib.pn2x_posed_chamfer_partial_floats.restype = ctypes.c_long
+_lib.pn2x_posed_chamfer.argtypes = [_ci, _ci, _ci] + [_vp] * 7 + [ctypes.c_long, _vp, _vp]
+_lib.pn2x_posed_chamfer.restype = _ci
+_lib.pn2x_obj_pose_metrics.argtypes = [_ci, _vp, _vp, _vp, _vp, _ci, _ci, _vp, _vp]
+_lib.pn2x_obj_pose_metrics.restype = _ci
+
+
+def posed_chamfer(A: torch.Tensor, B: torch.Tensor, Ra: torch.Tensor, ta: torch.Tensor, Rb: torch.Tensor, tb: torch.Tensor) -> torch.Tensor:
+    """Per-frame chamfer distance of two posed clouds (pn2x_posed_chamfer): A (N,3), B (M,3) in their model frames, Ra / Rb
+    (T,3,3), ta / tb (T,3) -> (T,) with out[f] = mean_i min_j |Ra_f a_i + ta_f - (Rb_f b_j + tb_f)| + mean_j min_i |...|.
+    Two launches for the whole sequence, no host sync (capturable)."""
+    f32 = torch.float32
+    N, M, T = A.shape[0], B.shape[0], Ra.shape[0]
+    if T > 0 and (N == 0 or M == 0):
+        raise ValueError(f"posed_chamfer: empty cloud (N = {N}, M = {M})")
+    args = [_native._ptr(A, "A", f32, N * 3), _native._ptr(B, "B", f32, M * 3), _native._ptr(Ra, "Ra", f32, T * 9),
+            _native._ptr(ta, "ta", f32, T * 3), _native._ptr(Rb, "Rb", f32, T * 9), _native._ptr(tb, "tb", f32, T * 3)]
+    need = int(_lib.pn2x_posed_chamfer_partial_floats(N, M, T))
+    partial = torch.empty(max(need, 1), dtype=f32, device=A.device)
+    out = torch.empty(T, dtype=f32, device=A.device)
+    with torch.cuda.device(A.device):
+        _native._check(_native._call(_lib.pn2x_posed_chamfer, "posed_chamfer", None, N, M, T, *args, partial.data_ptr(), need,
+                                     out.data_ptr(), _native._stream(A)), "posed_chamfer")
+    return out
+
+
+def obj_pose_metrics(gt_R: torch.Tensor, gt_t: torch.Tensor, pred_R: torch.Tensor, pred_t: torch.Tensor, axis: int,
+                     up_and_down_sym: bool) -> torch.Tensor:
+    """eval_part_full's per-frame terms (pn2x_obj_pose_metrics): rotations (T,3,3), translations (T,3) ->
+    (T,4) = [tdiff (m), rdiff (degrees), 5deg5cm, 10deg10cm].  One launch, no host sync."""
+    f32 = torch.float32
+    T = gt_R.shape[0]
+    out = torch.empty((T, 4), dtype=f32, device=gt_R.device)
+    with torch.cuda.device(gt_R.device):
+        _native._check(_native._call(_lib.pn2x_obj_pose_metrics, "obj_pose_metrics", None, T, _native._ptr(gt_R, "gt_R", f32, T * 9),
+                                     _native._ptr(gt_t, "gt_t", f32, T * 3), _native._ptr(pred_R, "pred_R", f32, T * 9),
+                                     _native._ptr(pred_t, "pred_t", f32, T * 3), int(axis), 1 if up_and_down_sym else 0,
+                                     out.data_ptr(), _native._stream(gt_R)), "obj_pose_metrics")
+    return out

@@ -796,6 +796,31 @@ int pn2x_ln_linear_small(int m, int k, int n, const float *xa, const float *ya, 
                          float eps1, const float *g2, const float *b2, float eps2, float *xout, const float *w, int ldw,
                          const float *bias, int relu, float *y, int ldy, void *stream);
 
+/*
+ * Per-sequence evaluation of the object trackers (csrc/seq_eval.hip): all t frames of a sequence per call, no host sync.
+ *
+ * pn2x_posed_chamfer: the reference's compute_chamfer (track_network.py:91-94) on the two clouds after its per-frame
+ * `matmul(cloud, R^T) + t` transforms (:431-433), for every frame at once.  a (n, 3) and b (m, 3) in their model frames;
+ * ra, rb (t, 3, 3) row-major and ta, tb (t, 3) the per-frame poses;
+ *   out[f] = mean_i min_j |(ra_f a_i + ta_f) - (rb_f b_j + tb_f)| + mean_j min_i |...|        (f < t; metres).
+ * The un-posed chamfer is the same call with t = 1 and identity poses.  Squared distances in the difference form, one square
+ * root per point; the (n x m) distance matrix is never stored.  partial: device scratch of at least
+ * pn2x_posed_chamfer_partial_floats(n, m, t) floats (PN2_ESCRATCH when smaller; -1 for a negative size): the per-workgroup
+ * sums, added in index order by a second launch -- no atomics, two calls give the same bits.  PN2_EINVAL for n, m or t < 0 and
+ * for an empty cloud with t > 0; t = 0 is a no-op; PN2_ERANGE beyond 65535 tiles of 512 points (n + m > ~33 million).
+ *
+ * pn2x_obj_pose_metrics: eval_part_full's per-frame terms (pose_utils/part_dof_utils.py:54-78, metrics.py:6-143) for t pose
+ * pairs: gt_r, pred_r (t, 3, 3), gt_t, pred_t (t, 3) -> out (t, 4) = {tdiff [m], rdiff [degrees], 5deg5cm, 10deg10cm}.
+ * axis / up_and_down_sym select rot_diff_rad's branch: axis 0..2 the angle between those columns (|cos| when up_and_down_sym),
+ * 3 the minimum over the identity and the three 180-degree flips, -1 over the identity and the xz flip, any other value the
+ * geodesic angle.  Cosines clamped to [-1, 1], thresholds inclusive (<=), as in the reference.
+ */
+long pn2x_posed_chamfer_partial_floats(int n, int m, int t);
+int pn2x_posed_chamfer(int n, int m, int t, const float *a, const float *b, const float *ra, const float *ta, const float *rb,
+                       const float *tb, float *partial, long partial_floats, float *out, void *stream);
+int pn2x_obj_pose_metrics(int t, const float *gt_r, const float *gt_t, const float *pred_r, const float *pred_t, int axis,
+                          int up_and_down_sym, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,6 +40,7 @@ class HandTrackModel(nn.Module):
         self._graphs = {}
         self.use_optimization = bool(cfg.get("use_optimization", False)) and hand_model is not None
         self.use_pred_obj_pose = bool(cfg.get("use_pred_obj_pose", False))
+        self.sym = cfg.get("obj_sym", -1)  # rot_diff_rad's symmetry mode for the obj_pred_* metrics (compute_loss)
         self.optimizer = None
         if self.use_optimization:
             from .optimization_hand import gf_optimize_hand_pose
@@ -231,12 +232,26 @@ class HandTrackModel(nn.Module):
         return theta, canon
 
     def compute_loss(self, input, ret_dict_lst, flag_dict):
+        """HandTrackNet's loss / metric dictionary averaged over the frames.  With `use_pred_obj_pose` and frames that carry
+        `pred_obj_pose`, also the reference's object-pose block (track_network.py:244-251): `obj_pred_tdiff_0`,
+        `obj_pred_rdiff_0`, `obj_pred_5deg5cm_0`, `obj_pred_10deg10cm_0` of the supplied object poses against gt_obj_pose
+        (eval_metrics.eval_part_full: one launch for the whole sequence, enqueued ahead of the single read-back)."""
         total = {}
         for data, ret in zip(input, ret_dict_lst):
             loss, _ = self.handnet.compute_loss(data, ret, flag_dict)
             for k, v in loss.items():
                 total[k] = total[k] + v if k in total else v  # stays on the device: one host sync per sequence
-        return {k: float(v) / len(input) for k, v in total.items()}, ret_dict_lst
+        obj = None
+        if self.use_pred_obj_pose and len(input) and all("pred_obj_pose" in d and "gt_obj_pose" in d for d in input):
+            from . import eval_metrics
+            err = eval_metrics.eval_part_full(_stack_poses([d["gt_obj_pose"] for d in input], self.device),
+                                              _stack_poses([d["pred_obj_pose"] for d in input], self.device), axis=int(self.sym),
+                                              up_and_down_sym=_up_and_down_sym(input[0]["gt_obj_pose"]))
+            obj = torch.stack([err[k] for k in eval_metrics.METRIC_KEYS])
+        out = {k: float(v) / len(input) for k, v in total.items()}
+        if obj is not None:
+            out.update({"obj_pred_" + k: v for k, v in zip(eval_metrics.METRIC_KEYS, obj.tolist())})
+        return out, ret_dict_lst
 
 
 class ObjTrackModel_Optimization(nn.Module):
@@ -287,10 +302,27 @@ class ObjTrackModel_Optimization(nn.Module):
         return rets
 
     def compute_loss(self, input, ret_dict_lst, flag_dict):
-        """Mean rotation / symmetry-axis (degrees) and translation (metres) error against gt_obj_pose.  (The reference
-        evaluates through pose_utils.part_dof_utils.eval_part_full plus a chamfer term on the reconstructed mesh, :385-440 --
-        mesh assets.)"""
+        """The reference's evaluation of a tracked sequence (track_network.py:385-434) next to this project's three figures,
+        every frame at once on the device (eval_metrics; hotrack_amd/csrc/seq_eval.hip) with one read-back per sequence:
+
+          obj_pred_r_diff / obj_pred_axis_diff / obj_pred_t_diff   mean geodesic rotation / object-z-axis (degrees) and
+                                                  translation (metres) error against gt_obj_pose;
+          tdiff_0, rdiff_0, 5deg5cm_0, 10deg10cm_0                 eval_part_full with axis = int(cfg['obj_sym']) (default -1) and
+                                                  up_and_down_sym from gt_obj_pose (default False).  An optional
+                                                  input[0]['eval_frame'] = {'rotation' (3,3), 'translation' (3,)} is the
+                                                  reference's HO3D / DexYCB change of evaluation frame (:417-425), applied to both
+                                                  poses; its per-instance table of such frames is not part of this project;
+          raw_obj_chamfer(mm), pred_obj_chamfer(mm)                when input[0] carries 'obj_model_points' ((N,3) samples of the
+                                                  ground-truth surface, object frame): chamfer distance to the predicted
+                                                  cloud (input[0]['obj_recon_points'], else the same points) un-posed, and under
+                                                  the ground-truth / predicted pose of each frame, averaged.  The reference
+                                                  samples a mesh file and the decoded reconstruction instead (mesh assets).  A
+                                                  cloud of more than 2048 points is cut to 2048 by this project's FPS operator
+                                                  (the reference: its Python FPS).  Without model points the two keys are
+                                                  absent and the log says so once."""
+        from . import eval_metrics
         r_err = t_err = a_err = 0.0
+        gRs, gts, Rs, ts = [], [], [], []
         for data, ret in zip(input, ret_dict_lst):
             gR = data["gt_obj_pose"]["rotation"].float().reshape(3, 3).to(self.device)
             gt = data["gt_obj_pose"]["translation"].float().reshape(3).to(self.device)
@@ -299,5 +331,61 @@ class ObjTrackModel_Optimization(nn.Module):
             r_err = r_err + torch.rad2deg(torch.arccos(cos.clamp(-1, 1)))
             a_err = a_err + torch.rad2deg(torch.arccos((R[:, 2] * gR[:, 2]).sum().clamp(-1, 1)))  # object z axis (revolution axis)
             t_err = t_err + (t - gt).norm()
+            gRs.append(gR)
+            gts.append(gt)
+            Rs.append(R.float())
+            ts.append(t.float())
         n = max(len(input), 1)
-        return {"obj_pred_r_diff": float(r_err) / n, "obj_pred_axis_diff": float(a_err) / n, "obj_pred_t_diff": float(t_err) / n}, ret_dict_lst
+        if not len(input):
+            return {"obj_pred_r_diff": 0.0, "obj_pred_axis_diff": 0.0, "obj_pred_t_diff": 0.0}, ret_dict_lst
+        gt_pose = {"rotation": torch.stack(gRs), "translation": torch.stack(gts)}
+        pred_pose = {"rotation": torch.stack(Rs), "translation": torch.stack(ts)}
+        ev_gt, ev_pred = gt_pose, pred_pose
+        if "eval_frame" in input[0]:
+            ev_gt, ev_pred = eval_metrics.to_eval_frame(gt_pose, input[0]["eval_frame"]), eval_metrics.to_eval_frame(pred_pose, input[0]["eval_frame"])
+        err = eval_metrics.eval_part_full(ev_gt, ev_pred, axis=int(self.sym), up_and_down_sym=_up_and_down_sym(input[0]["gt_obj_pose"]))
+        keys = ["obj_pred_r_diff", "obj_pred_axis_diff", "obj_pred_t_diff", *eval_metrics.METRIC_KEYS]
+        vals = [r_err, a_err, t_err, *[err[k] for k in eval_metrics.METRIC_KEYS]]
+        if "obj_model_points" in input[0]:
+            gt_cloud = self._eval_cloud(input[0]["obj_model_points"])
+            pred_cloud = self._eval_cloud(input[0]["obj_recon_points"]) if "obj_recon_points" in input[0] else gt_cloud
+            eye, zero = torch.eye(3, device=self.device).reshape(1, 3, 3), torch.zeros((1, 3), device=self.device)
+            raw = eval_metrics.posed_chamfer(gt_cloud, pred_cloud, eye, zero, eye, zero)[0] * 1000
+            posed = eval_metrics.posed_chamfer(gt_cloud, pred_cloud, gt_pose["rotation"], gt_pose["translation"], pred_pose["rotation"],
+                                               pred_pose["translation"]).mean() * 1000
+            keys += ["raw_obj_chamfer(mm)", "pred_obj_chamfer(mm)"]
+            vals += [raw, posed]
+        elif not ObjTrackModel_Optimization._said_no_points:
+            ObjTrackModel_Optimization._said_no_points = True
+            print("[Object Tracking] no 'obj_model_points' in the sequence's first frame: raw_obj_chamfer(mm) / pred_obj_chamfer(mm) are not reported")
+        host = torch.stack([torch.as_tensor(v, dtype=torch.float32, device=self.device).reshape(()) for v in vals]).tolist()  # the one read-back
+        out = dict(zip(keys, host))
+        for k in keys[:3]:
+            out[k] = out[k] / n
+        return out, ret_dict_lst
+
+    _said_no_points = False
+
+    def _eval_cloud(self, points):
+        """(N,3) fp32 cloud on the device, cut to 2048 points by farthest point sampling when larger (:400-402)."""
+        pts = torch.as_tensor(points).float().reshape(-1, 3).to(self.device).contiguous()
+        if pts.shape[0] > 2048:
+            from hotrack_amd import pointnet2_utils
+            idx = pointnet2_utils.furthest_point_sample(pts[None], 2048)
+            pts = pts[idx[0].long()].contiguous()
+        return pts
+
+
+def _stack_poses(poses, device):
+    """[{'rotation', 'translation'} per frame] -> {'rotation' (T,3,3), 'translation' (T,3)} fp32 on `device`."""
+    return {"rotation": torch.stack([p["rotation"].float().reshape(3, 3).to(device) for p in poses]),
+            "translation": torch.stack([p["translation"].float().reshape(3).to(device) for p in poses])}
+
+
+def _up_and_down_sym(gt_obj_pose) -> bool:
+    v = gt_obj_pose.get("up_and_down_sym", False)
+    if torch.is_tensor(v):
+        return bool(v.reshape(-1)[0]) if v.numel() else False
+    if isinstance(v, (list, tuple)):
+        return bool(v[0]) if len(v) else False
+    return bool(v)
