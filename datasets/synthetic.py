@@ -127,10 +127,13 @@ def get_dataloader(cfg, mode="train", shuffle=False, num_workers=0, distributed=
     if (cfg.get("track") == "hand_IKNet" and (cfg.get("use_optimization") or cfg.get("use_iknet"))
             and cfg.get("hand_model") is not None):
         ds = SyntheticHandObjectSequences(cfg, syn.get("test_sequences", 2), syn.get("sequence_frames", 20) if length is None else length,
-                                          hand_beta=syn.get("hand_beta"))
+                                          hand_beta=syn.get("hand_beta"), obj_as_mesh=bool(cfg.get("obj_as_mesh", False)),
+                                          obj_mesh_path=cfg.get("obj_mesh"))
         return torch.utils.data.DataLoader(ds, batch_size=1, shuffle=False, collate_fn=lambda b: b[0])
     if cfg.get("track") == "obj_opt":
-        ds = SyntheticObjectSequences(cfg, syn.get("test_sequences", 2), syn.get("sequence_frames", 30) if length is None else length)
+        ds = SyntheticObjectSequences(cfg, syn.get("test_sequences", 2), syn.get("sequence_frames", 30) if length is None else length,
+                                      obj_as_mesh=bool(cfg.get("obj_as_mesh", False)),
+                                          obj_mesh_path=cfg.get("obj_mesh"))
         return torch.utils.data.DataLoader(ds, batch_size=1, shuffle=False, collate_fn=lambda b: b[0])
     if cfg.get("track"):
         ds = SyntheticSequences(cfg, syn.get("test_sequences", 4),
@@ -156,6 +159,30 @@ def capsule_volume(res: int = 201, stride: float = 0.002) -> np.ndarray:
     ax = (np.arange(res) - res // 2) * float(stride)
     g = np.stack(np.meshgrid(ax, ax, ax, indexing="ij"), axis=-1)
     return np.clip(_capsule_sdf(g), -0.1, 0.1).astype(np.float16)
+
+
+def capsule_mesh(n_around: int = 64, n_cap: int = 16):
+    """(verts float32 (nv,3), faces int32 (nf,3)): a closed, outward-oriented tessellation of the same capsule with every
+    vertex on its surface -- n_around segments around z, n_cap latitude bands per hemispherical cap, one band for the cylinder
+    (whose generators are straight); 2 n_around (2 n_cap) faces."""
+    phi = np.arange(n_around) * 2 * np.pi / n_around
+    theta = np.arange(1, n_cap + 1) * (np.pi / 2) / n_cap   # polar angle of a cap's rings, the last one its equator
+    rings = [(0.07 + 0.04 * np.cos(th), 0.04 * np.sin(th)) for th in theta] + [(-0.07 - 0.04 * np.cos(th), 0.04 * np.sin(th)) for th in theta[::-1]]
+    verts = [[0.0, 0.0, 0.11]] + [[r * np.cos(a), r * np.sin(a), z] for z, r in rings for a in phi] + [[0.0, 0.0, -0.11]]
+    at = lambda ring, j: 1 + ring * n_around + j % n_around
+    last, bottom = len(rings) - 1, 1 + len(rings) * n_around
+    faces = []
+    for j in range(n_around):
+        faces.append((0, at(0, j), at(0, j + 1)))
+        for k in range(last):  # from ring k down to ring k + 1
+            faces += [(at(k, j), at(k + 1, j), at(k + 1, j + 1)), (at(k, j), at(k + 1, j + 1), at(k, j + 1))]
+        faces.append((at(last, j), bottom, at(last, j + 1)))
+    return np.asarray(verts, dtype=np.float32), np.asarray(faces, dtype=np.int32)
+
+
+def _mesh_entry():
+    v, f = capsule_mesh()
+    return {"vertices": torch.from_numpy(v), "faces": torch.from_numpy(f)}
 
 
 def _rot(axis, angle):
@@ -185,18 +212,29 @@ class SyntheticObjectSequences(Dataset):
     """Sequences for `track: obj_opt` (reference SequenceData items as ObjTrackModel_Optimization.forward reads them,
     track_network.py:338-383): per frame obj_points (1,N,3) camera frame, gt_obj_pose, category / file_name / projection;
     frame 0 also carries jittered_obj_pose (obj_jitter_cfg: r degrees, t metres), -- in place of the DeepSDF latent the
-    reference decodes -- the object's SDF volume, and obj_model_points (2048,3): surface samples for the chamfer metrics."""
+    reference decodes -- the object's SDF volume, and obj_model_points (2048,3): surface samples for the chamfer metrics.
+    obj_as_mesh: frame 0 carries `obj_mesh` ({'vertices', 'faces'}: capsule_mesh()) instead of `sdf_volume` and the tracker
+    builds the volume (models/mesh_sdf.py); every other entry and every random draw is unchanged.  obj_mesh_path: frame 0
+    carries that `obj_mesh_path` (an OBJ / PLY file, object frame, metres) instead: the clouds are tracked against its volume."""
 
-    def __init__(self, cfg, num_sequences: int, frames: int, res: int = 201, stride: float = 0.002):
+    def __init__(self, cfg, num_sequences: int, frames: int, res: int = 201, stride: float = 0.002, obj_as_mesh: bool = False,
+                 obj_mesh_path=None):
         self.cfg, self.ns, self.nf = cfg, num_sequences, frames
         self.res, self.stride = res, stride
         self._vol = None
+        self.obj_as_mesh, self.obj_mesh_path = bool(obj_as_mesh), obj_mesh_path
+        self._mesh = None
 
     def __len__(self):
         return self.ns
 
     def __getitem__(self, s):
-        if self._vol is None:
+        if self.obj_mesh_path is not None:
+            pass
+        elif self.obj_as_mesh:
+            if self._mesh is None:
+                self._mesh = _mesh_entry()
+        elif self._vol is None:
             self._vol = torch.from_numpy(capsule_volume(self.res, self.stride))
         rng = np.random.default_rng(40_000 + s)
         n = self.cfg["num_points"]
@@ -217,7 +255,9 @@ class SyntheticObjectSequences(Dataset):
                 Rj = R @ _rot(rng.standard_normal(3), ang)
                 tj = t + rng.normal(0, float(jit.get("t", 0.03)) / 3, 3)
                 fr["jittered_obj_pose"] = {"rotation": f(Rj).reshape(1, 3, 3), "translation": f(tj).reshape(1, 3, 1)}
-                fr["sdf_volume"], fr["voxel_scale"] = self._vol, self.stride
+                fr["voxel_scale"] = self.stride
+                fr.update({"obj_mesh_path": self.obj_mesh_path} if self.obj_mesh_path is not None else
+                          {"obj_mesh": self._mesh} if self.obj_as_mesh else {"sdf_volume": self._vol})
                 fr["obj_model_points"] = model_points(70_000 + s)
             seq.append(fr)
             R = R @ _rot(w_axis, w)
@@ -235,19 +275,30 @@ class SyntheticHandObjectSequences(Dataset):
     hand_beta: the hand's true shape code beta* for a hand model with a shape space -- None (the zero shape: the data of a
     model without one), a (num_betas,) vector for every sequence, or a float sigma: beta* ~ N(0, sigma^2) per sequence, drawn
     from the sequence's seed.  With a shape, the palm template and every frame come from the shaped hand and gt_hand_pose
-    carries `mano_beta` (1, num_betas)."""
+    carries `mano_beta` (1, num_betas).
 
-    def __init__(self, cfg, num_sequences: int, frames: int, res: int = 151, stride: float = 0.003, hand_beta=None):
+    obj_as_mesh / obj_mesh_path: as in SyntheticObjectSequences -- frame 0 carries `obj_mesh` / `obj_mesh_path` instead of
+    `sdf_volume`."""
+
+    def __init__(self, cfg, num_sequences: int, frames: int, res: int = 151, stride: float = 0.003, hand_beta=None,
+                 obj_as_mesh: bool = False, obj_mesh_path=None):
         self.cfg, self.ns, self.nf, self.res, self.stride = cfg, num_sequences, frames, res, stride
         self.hand = cfg["hand_model"]
         self.hand_beta = hand_beta
         self._vol = None
+        self.obj_as_mesh, self.obj_mesh_path = bool(obj_as_mesh), obj_mesh_path
+        self._mesh = None
 
     def __len__(self):
         return self.ns
 
     def __getitem__(self, s):
-        if self._vol is None:
+        if self.obj_mesh_path is not None:
+            pass
+        elif self.obj_as_mesh:
+            if self._mesh is None:
+                self._mesh = _mesh_entry()
+        elif self._vol is None:
             self._vol = torch.from_numpy(capsule_volume(self.res, self.stride))
         rng = np.random.default_rng(50_000 + s)
         n = self.cfg["num_points"]
@@ -291,7 +342,9 @@ class SyntheticHandObjectSequences(Dataset):
                   "projection": {kk: [vv] for kk, vv in proj.items()}, "background_mask": background,
                   "category": [self.cfg["obj_category"][0]], "file_name": [f"synthetic_handobj_{s:03d}/{k:04d}"]}
             if k == 0:
-                fr["sdf_volume"], fr["voxel_scale"] = self._vol, self.stride
+                fr["voxel_scale"] = self.stride
+                fr.update({"obj_mesh_path": self.obj_mesh_path} if self.obj_mesh_path is not None else
+                          {"obj_mesh": self._mesh} if self.obj_as_mesh else {"sdf_volume": self._vol})
                 fr["obj_model_points"] = model_points(80_000 + s)
             seq.append(fr)
         return seq

@@ -6,6 +6,7 @@ Mirrors, function for function, the reference methods it replaces:
   obj_optimize      the particle loop of gf_optimize_obj.optimize :253-301
   query_sdf         gf_optimize_hand_pose.query_sdf              network/models/optimization_hand.py:252-262
   penetration_loss  ... .get_penetration_loss(query_sdf(hand))   :264-268 (fused with the lookup)
+  mesh_signed_distance / mesh_sdf_volume   load_obj_oracle (mesh -> volume; kaolin there)   optimization_obj.py:163-182
 """
 from __future__ import annotations
 
@@ -161,3 +162,78 @@ def query_sdf(hand: torch.Tensor, obj_r: torch.Tensor, obj_t: torch.Tensor, sdf_
     if with_index:
         ret += (idx,)
     return ret[0] if len(ret) == 1 else ret
+
+
+# ---- mesh -> signed distance (hotrack_amd/csrc/mesh_sdf.hip) ------------------------------------------------------------------
+_cl = ctypes.c_long
+_lib.pn2s_mesh_sdf_work_floats.argtypes = [_ci]
+_lib.pn2s_mesh_sdf_work_floats.restype = _cl
+_lib.pn2s_mesh_sdf_points.argtypes = [_ci, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _cl, _vp]
+_lib.pn2s_mesh_sdf_points.restype = _ci
+_lib.pn2s_mesh_sdf_volume.argtypes = [_ci, _vp, _ci, _vp, _ci, _cf, _cf, _vp, _ci, _vp, _cl, _vp]
+_lib.pn2s_mesh_sdf_volume.restype = _ci
+
+
+def _mesh(verts: torch.Tensor, faces: torch.Tensor):
+    """Validate a mesh: verts (nv,3) float32, faces (nf,3) int32, contiguous, on one GPU -> (nv, verts pointer, nf, faces pointer)."""
+    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"verts must be (nv,3) and faces (nf,3), got {tuple(verts.shape)} and {tuple(faces.shape)}")
+    if verts.shape[0] == 0 or faces.shape[0] == 0:
+        raise ValueError("the mesh is empty")
+    nv, nf = verts.shape[0], faces.shape[0]
+    pv, pf = _native._ptr(verts, "verts", _f32, nv * 3), _native._ptr(faces, "faces", torch.int32, nf * 3)
+    if faces.device != verts.device:
+        raise RuntimeError(f"verts and faces are on different devices ({verts.device}, {faces.device})")
+    return nv, pv, nf, pf
+
+
+def _mesh_work(nf: int, device) -> torch.Tensor:
+    return torch.empty((_lib.pn2s_mesh_sdf_work_floats(nf),), dtype=_f32, device=device)
+
+
+def _mesh_faces_ok(work: torch.Tensor, what: str) -> None:
+    """The one read-back per call: the kernel's face-index check (include/pn2_sdf.h).  Raises before the caller sees the output."""
+    if int(work[:1].view(torch.int32).item()) != 0:
+        raise ValueError(f"{what}: a face index lies outside [0, number of vertices)")
+
+
+def mesh_signed_distance(points: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, return_winding: bool = False):
+    """Signed distance (M,) fp32 of points (M,3) to the triangle mesh (verts (nv,3) fp32, faces (nf,3) int32): exact
+    point-triangle minimum over all faces, negative where the generalised winding number exceeds 0.5; unclamped.
+    return_winding: also the winding numbers (M,).  Synchronises once (the face-index check)."""
+    nv, pv, nf, pf = _mesh(verts, faces)
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"points must be (M,3), got {tuple(points.shape)}")
+    m = points.shape[0]
+    pp = _native._ptr(points, "points", _f32, m * 3)
+    if points.device != verts.device:
+        raise RuntimeError(f"points and the mesh are on different devices ({points.device}, {verts.device})")
+    out = torch.empty((m,), dtype=_f32, device=verts.device)
+    wn = torch.empty((m,), dtype=_f32, device=verts.device) if return_winding else None
+    if m:
+        work = _mesh_work(nf, verts.device)
+        with torch.cuda.device(verts.device):
+            rc = _lib.pn2s_mesh_sdf_points(m, pp, nv, pv, nf, pf, out.data_ptr(), None if wn is None else wn.data_ptr(),
+                                           work.data_ptr(), work.numel(), _native._stream(verts))
+        _native._check(rc, "sdf.mesh_signed_distance")
+        _mesh_faces_ok(work, "sdf.mesh_signed_distance")
+    return (out, wn) if return_winding else out
+
+
+def mesh_sdf_volume(verts: torch.Tensor, faces: torch.Tensor, res: int = 201, voxel_scale: float = 0.002, clamp: float = 0.1,
+                    dtype: torch.dtype = torch.float16) -> torch.Tensor:
+    """(res,res,res) SDF volume of the mesh, indexed [ix,iy,iz] with voxel centre ((ix,iy,iz) - res//2) * voxel_scale (the grid
+    of the reference's volume_ind, optimization_obj.py:133-143), clamped to +-clamp and rounded once to `dtype` (float16, the
+    reference's storage type, or float32).  One build per object: synchronises once (the face-index check)."""
+    nv, pv, nf, pf = _mesh(verts, faces)
+    if dtype not in (torch.float16, torch.float32):
+        raise TypeError(f"dtype must be float16 or float32, got {dtype}")
+    res = int(res)
+    out = torch.empty((res, res, res) if res > 0 else (0,), dtype=dtype, device=verts.device)
+    work = _mesh_work(nf, verts.device)
+    with torch.cuda.device(verts.device):
+        rc = _lib.pn2s_mesh_sdf_volume(nv, pv, nf, pf, res, float(voxel_scale), float(clamp), out.data_ptr(), int(dtype == torch.float16),
+                                       work.data_ptr(), work.numel(), _native._stream(verts))
+    _native._check(rc, "sdf.mesh_sdf_volume")
+    _mesh_faces_ok(work, "sdf.mesh_sdf_volume")
+    return out

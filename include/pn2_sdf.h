@@ -90,6 +90,37 @@ int pn2s_obj_optimize_work_floats(int p);
 int pn2s_nearest(int b, int n, const float *hand, const float *obj_r, const float *obj_t, const void *vol,
                  int vol_f16, int res, float voxel_scale, int *out_idx, void *out_sdf, void *out_pen, void *stream);
 
+/*
+ * Signed distance to a triangle mesh -- the producer of the volumes above (optimization_obj.py:163-182, load_obj_oracle: "directly
+ * compute the SDF volume from a mesh if we assume the mesh is known"; the reference leaves it commented out because it needs
+ * kaolin).  verts (nv,3) fp32; faces (nf,3) int32 vertex indices, closed and outward oriented.
+ *   magnitude: the exact minimum over ALL triangles of the distance to the triangle's closest point (face, edge or vertex);
+ *              no triangle is culled;
+ *   sign:      generalised winding number w = (1/4pi) sum_f Omega_f, Omega_f = 2 atan2(a.(b x c), |a||b||c| + (a.b)|c| +
+ *              (b.c)|a| + (c.a)|b|), a, b, c = v - p (Van Oosterom-Strackee); negative (inside) iff w > 0.5.  Every query sums its
+ *              angles in face order: no atomics, two runs are bitwise equal;
+ *   degenerate triangles (a repeated vertex, three collinear vertices: |n|^2 <= 1e-12 |b-a|^2 |c-a|^2) contribute the distance
+ *              to their segment or point and exactly zero solid angle; no input produces a NaN.
+ * work: scratch of at least pn2s_mesh_sdf_work_floats(nf) floats, 16-byte aligned (the per-triangle records, built by a
+ *   prepare launch).  On return -- in stream order -- the int at work[0] is 1 if a face index lies outside [0, nv) and 0
+ *   otherwise.  Such a face is replaced by vertex 0, so nothing is read out of bounds, and the outputs must not be used: the caller
+ *   reads that one word back.  A volume is built once per object and outside any captured graph, so the one read-back costs
+ *   nothing that matters; a caller inside a capture leaves the word on the device.
+ * Limits: nv, nf <= 2^24, res <= 1023 (PN2_ERANGE beyond); PN2_ESCRATCH when work_floats is too small.
+ *
+ * pn2s_mesh_sdf_points: pts (m,3) -> out_sdf (m) signed and unclamped; out_wn (m) the winding numbers, or NULL.  m == 0 is a
+ *   no-op that reads nothing.
+ * pn2s_mesh_sdf_volume: res^3 voxels, element (ix,iy,iz) at (ix*res + iy)*res + iz with centre ((ix,iy,iz) - res/2) * stride
+ *   (fp32 product; res odd -- the grid pn2s_nearest indexes), the value clamped to [-clamp, clamp] (the reference: 0.1) and
+ *   rounded once to the output type (out_f16 = 1: IEEE binary16, 0: fp32).  Before clamping and rounding, the value is
+ *   bit-for-bit what pn2s_mesh_sdf_points returns at that centre.
+ */
+long pn2s_mesh_sdf_work_floats(int nf);
+int pn2s_mesh_sdf_points(int m, const float *pts, int nv, const float *verts, int nf, const int *faces, float *out_sdf,
+                         float *out_wn, float *work, long work_floats, void *stream);
+int pn2s_mesh_sdf_volume(int nv, const float *verts, int nf, const int *faces, int res, float stride, float clamp, void *out,
+                         int out_f16, float *work, long work_floats, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -185,9 +185,10 @@ class HandTrackModel(nn.Module):
         if self.use_optimization:
             if "sdf_volume" in input[0]:
                 self.optimizer.load_volume(input[0]["sdf_volume"], input[0].get("voxel_scale"))
-            elif self.optimizer.sdf_volume is None:
+            elif not _load_mesh_volume(self.optimizer, input[0], self.device) and self.optimizer.sdf_volume is None:
                 raise RuntimeError("use_optimization: no SDF volume (decoding it from a DeepSDF latent needs the checkpoints); "
-                                   "put 'sdf_volume' / 'voxel_scale' into the sequence's first frame")
+                                   "put 'sdf_volume' / 'voxel_scale', or the object's mesh as 'obj_mesh' ({'vertices', 'faces'}) "
+                                   "or 'obj_mesh_path', into the sequence's first frame")
         prev_theta = None
         for i, data in enumerate(input):
             data["pred_palm_template"] = palm_template
@@ -263,7 +264,9 @@ class ObjTrackModel_Optimization(nn.Module):
     poses evaluated by the fused SDF-lookup kernels with the pose update on the device (hotrack_amd/csrc/sdf.hip): the loop
     never synchronises with the host.  The reference decodes the volume from a DeepSDF latent per sequence
     (`load_obj_for_opt` + `optimizer.load_obj`, :342-346 -- needs the checkpoints); here the sequence hands the volume
-    over (`input[0]['sdf_volume']`, `['voxel_scale']`)."""
+    over (`input[0]['sdf_volume']`, `['voxel_scale']`) or hands over the object's triangle mesh (`input[0]['obj_mesh']` =
+    {'vertices', 'faces'} or `['obj_mesh_path']`), from which the volume is built once (models/mesh_sdf.py, the reference's
+    load_obj_oracle)."""
 
     def __init__(self, cfg):
         super().__init__()
@@ -280,9 +283,10 @@ class ObjTrackModel_Optimization(nn.Module):
         assert flag_dict["test_flag"]
         if "sdf_volume" in input[0]:
             self.optimizer.load_volume(input[0]["sdf_volume"], input[0].get("voxel_scale"))
-        elif self.optimizer.sdf_volume is None:
+        elif not _load_mesh_volume(self.optimizer, input[0], self.device) and self.optimizer.sdf_volume is None:
             raise RuntimeError("no SDF volume: decoding it from a DeepSDF latent needs the checkpoints (out of scope); "
-                               "put 'sdf_volume' / 'voxel_scale' into the sequence's first frame")
+                               "put 'sdf_volume' / 'voxel_scale', or the object's mesh as 'obj_mesh' ({'vertices', 'faces'}) or "
+                               "'obj_mesh_path', into the sequence's first frame")
         last = None
         rets = []
         for data in input:
@@ -318,8 +322,10 @@ class ObjTrackModel_Optimization(nn.Module):
                                                   the ground-truth / predicted pose of each frame, averaged.  The reference
                                                   samples a mesh file and the decoded reconstruction instead (mesh assets).  A
                                                   cloud of more than 2048 points is cut to 2048 by this project's FPS operator
-                                                  (the reference: its Python FPS).  Without model points the two keys are
-                                                  absent and the log says so once."""
+                                                  (the reference: its Python FPS).  Without model points but with a mesh
+                                                  ('obj_mesh' / 'obj_mesh_path') 2048 points are sampled from it
+                                                  (mesh_sdf.sample_surface, seed 0); with neither the two keys are absent and
+                                                  the log says so once."""
         from . import eval_metrics
         r_err = t_err = a_err = 0.0
         gRs, gts, Rs, ts = [], [], [], []
@@ -346,8 +352,14 @@ class ObjTrackModel_Optimization(nn.Module):
         err = eval_metrics.eval_part_full(ev_gt, ev_pred, axis=int(self.sym), up_and_down_sym=_up_and_down_sym(input[0]["gt_obj_pose"]))
         keys = ["obj_pred_r_diff", "obj_pred_axis_diff", "obj_pred_t_diff", *eval_metrics.METRIC_KEYS]
         vals = [r_err, a_err, t_err, *[err[k] for k in eval_metrics.METRIC_KEYS]]
-        if "obj_model_points" in input[0]:
-            gt_cloud = self._eval_cloud(input[0]["obj_model_points"])
+        model_points = input[0].get("obj_model_points")
+        if model_points is None:  # the reference's trimesh.sample.sample_surface(mesh, 2048) (:398)
+            from . import mesh_sdf
+            mesh = mesh_sdf.frame_mesh(input[0], self.device)
+            if mesh is not None:
+                model_points = mesh_sdf.sample_surface(mesh[1], mesh[2], 2048, seed=0)
+        if model_points is not None:
+            gt_cloud = self._eval_cloud(model_points)
             pred_cloud = self._eval_cloud(input[0]["obj_recon_points"]) if "obj_recon_points" in input[0] else gt_cloud
             eye, zero = torch.eye(3, device=self.device).reshape(1, 3, 3), torch.zeros((1, 3), device=self.device)
             raw = eval_metrics.posed_chamfer(gt_cloud, pred_cloud, eye, zero, eye, zero)[0] * 1000
@@ -357,7 +369,7 @@ class ObjTrackModel_Optimization(nn.Module):
             vals += [raw, posed]
         elif not ObjTrackModel_Optimization._said_no_points:
             ObjTrackModel_Optimization._said_no_points = True
-            print("[Object Tracking] no 'obj_model_points' in the sequence's first frame: raw_obj_chamfer(mm) / pred_obj_chamfer(mm) are not reported")
+            print("[Object Tracking] no 'obj_model_points' and no mesh in the sequence's first frame: raw_obj_chamfer(mm) / pred_obj_chamfer(mm) are not reported")
         host = torch.stack([torch.as_tensor(v, dtype=torch.float32, device=self.device).reshape(()) for v in vals]).tolist()  # the one read-back
         out = dict(zip(keys, host))
         for k in keys[:3]:
@@ -374,6 +386,19 @@ class ObjTrackModel_Optimization(nn.Module):
             idx = pointnet2_utils.furthest_point_sample(pts[None], 2048)
             pts = pts[idx[0].long()].contiguous()
         return pts
+
+
+def _load_mesh_volume(optimizer, frame0, device) -> bool:
+    """The reference's load_obj_oracle (optimization_obj.py:163-182): when the first frame carries the object's mesh
+    ('obj_mesh' or 'obj_mesh_path'), build its SDF volume at the optimiser's own volume_size and the frame's (else the
+    optimiser's) voxel_scale -- once per mesh, cached -- and load it.  False: the frame carries no mesh."""
+    from . import mesh_sdf
+    voxel_scale = float(frame0.get("voxel_scale", optimizer.voxel_scale))
+    vol = mesh_sdf.frame_volume(frame0, optimizer.volume_size, voxel_scale, device)
+    if vol is None:
+        return False
+    optimizer.load_volume(vol, voxel_scale)
+    return True
 
 
 def _stack_poses(poses, device):

@@ -38,4 +38,9 @@ def add_args(parser):
                         help="use_optimization: run the hand-pose particle optimiser on the device-resident route (two kernels per "
                              "iteration, hotrack_amd/csrc/hand_pose.hip) instead of the torch route; needs a hand model with "
                              "plain skinning tables")
+    parser.add_argument("--obj_mesh", type=str, default=None,
+                        help="track the synthetic sequences' clouds against an SDF volume built from this triangle mesh (OBJ or "
+                             "PLY, object frame, metres; models/mesh_sdf.py) instead of the analytic capsule volume")
+    parser.add_argument("--obj_as_mesh", action="store_const", const=True, default=None,
+                        help="the synthetic sequences carry the capsule as a triangle mesh and the tracker builds the volume")
     return parser
