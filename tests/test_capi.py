@@ -150,6 +150,63 @@ def test_argument_validation_without_gpu(hip_lib_path):
     assert lib.pn2x_sa_mlp_max(1, 64, 4, 16, 128, 128, 192, one, 1 << 23, one, one, one, one, None, 0, one, one, one, one, one, one, 768, 192, 1, None) == -3
 
 
+def test_sa_mlp_max_argument_validation_without_gpu(hip_lib_path):
+    """pn2x_sa_mlp_max / pn2x_sa_mlp_max_pair refuse every invalid argument before any launch: non-null fake pointers and exactly
+    one violation per call.  The *_supported queries answer 1 on exactly the combinations sa_fused.hip instantiates."""
+    lib = ctypes.CDLL(hip_lib_path)
+    vp, ci, cl = ctypes.c_void_p, ctypes.c_int, ctypes.c_long
+    lib.pn2x_sa_mlp_max.argtypes = [ci] * 7 + [vp, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, cl, ci, ci, vp]
+    p = vp(16)
+    good = dict(b=2, n=64, s=4, k=16, c1=128, c2=128, c3=192, a1f=p, a1f_ld=128, xyz=p, cxyz=p, wx=p, b1=p, cadd=p, cadd_ld=128, idx=p,
+                w2=p, b2=p, w3=p, b3=p, out=p, out_b=768, out_s=192, out_c=1, stream=None)
+
+    def call(**change):
+        assert set(change) <= set(good)
+        return lib.pn2x_sa_mlp_max(*{**good, **change}.values())
+
+    assert call(b=-1) == -1
+    assert call(k=0) == -1
+    assert call(s=0) == 0                                  # nothing to do
+    assert call(b=0) == 0
+    assert call(idx=None) == -2
+    assert call(a1f=None, xyz=None) == -2                  # layer 1 needs a per-point term
+    assert call(cxyz=None) == -2                           # xyz without the centroids
+    assert call(a1f_ld=124) == -1                          # a1f_ld < c1
+    assert call(a1f_ld=130) == -1                          # rows are read as 16-byte quads
+    assert call(cadd_ld=130) == -1
+    assert call(k=8) == -3
+    assert call(c1=64, c2=64, c3=64, out_b=256, out_s=64) == -3
+    assert call(a1f=vp(20)) == -1                          # not 16-byte aligned
+
+    class Problem(ctypes.Structure):                       # include/pn2_ext.h: pn2x_sa_problem
+        _fields_ = [("n", ci), ("s", ci), ("k", ci), ("a1f", vp), ("a1f_ld", ci), ("xyz", vp), ("cxyz", vp), ("wx", vp), ("b1", vp),
+                    ("cadd", vp), ("cadd_ld", ci), ("idx", vp), ("w2", vp), ("b2", vp), ("w3", vp), ("b3", vp), ("out", vp),
+                    ("out_b", cl), ("out_s", ci), ("out_c", ci)]
+
+    lib.pn2x_sa_mlp_max_pair.argtypes = [ci] * 4 + [ctypes.POINTER(Problem)] * 2 + [vp]
+
+    def problem(k):
+        return Problem(64, 21, k, 16, 128, 16, 16, 16, 16, 16, 128, 16, 16, 16, 16, 16, 16, 21 * 384, 384, 1)
+
+    p16, p32, p64 = problem(16), problem(32), problem(64)
+    assert lib.pn2x_sa_mlp_max_pair(2, 128, 128, 192, None, ctypes.byref(p64), None) == -2
+    assert lib.pn2x_sa_mlp_max_pair(2, 128, 128, 192, ctypes.byref(p16), None, None) == -2
+    assert lib.pn2x_sa_mlp_max_pair(-1, 128, 128, 192, ctypes.byref(p16), ctypes.byref(p64), None) == -1
+    assert lib.pn2x_sa_mlp_max_pair(2, 128, 128, 192, ctypes.byref(p32), ctypes.byref(p64), None) == -3
+    assert lib.pn2x_sa_mlp_max_pair(0, 128, 128, 192, ctypes.byref(p16), ctypes.byref(p64), None) == 0
+
+    widths = {(32, 32, 64), (64, 64, 128), (128, 128, 192)}
+    near = sorted(widths | {(32, 32, 32), (32, 64, 64), (64, 64, 64), (64, 64, 192), (64, 128, 128), (128, 128, 128), (128, 128, 256),
+                            (128, 192, 192), (192, 192, 192), (16, 16, 32), (32, 32, 128), (64, 32, 128), (128, 64, 192), (0, 0, 0)})
+    ks = (0, 1, 8, 15, 16, 17, 24, 31, 32, 33, 48, 63, 64, 65, 128)
+    for w in near:
+        for k in ks:
+            assert lib.pn2x_sa_mlp_max_supported(k, *w) == int(w in widths and k in (16, 32, 64)), (k, w)
+        for k0 in ks:
+            for k1 in ks:
+                assert lib.pn2x_sa_mlp_max_pair_supported(k0, k1, *w) == int(w == (128, 128, 192) and (k0, k1) in ((16, 64), (64, 16))), (k0, k1, w)
+
+
 def test_python_boundary_exports_reference_names():
     from hotrack_amd import pointnet2_hip, pointnet2_utils
     for n in pointnet2_hip.EXPORTED:
