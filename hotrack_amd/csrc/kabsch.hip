@@ -499,7 +499,8 @@ extern "C" int pn2x_hand_frame(int b, int xb, int num, int n, int j, const float
     if (xyz2_copy && copy_ld < 3) return PN2_EINVAL;
     if (b < 0 || num < 1 || num > 16 || n < 0 || j < 1 || !(xb == b || xb == 1) || !(scale > 0.f)) return PN2_EINVAL;
     if (b == 0) return PN2_OK;
-    if (!palm_template || !kp || !palm_idx || !points || !R || !t || !xyz2 || !xyz1) return PN2_ENULL;
+    // n == 0 (keypoints only): an empty cloud has no storage, points / xyz2 may be null and are never dereferenced
+    if (!palm_template || !kp || !palm_idx || !R || !t || !xyz1 || (n > 0 && (!points || !xyz2))) return PN2_ENULL;
     hipLaunchKernelGGL(pn2::hand_frame_kernel, dim3(b), dim3(256), 0, (hipStream_t)stream, xb, num, n, j, palm_template, kp,
                        palm_idx, points, scale, R, t, xyz2, xyz1, xyz2_copy, copy_ld, nonfinite);
     return pn2::check_launch();

@@ -39,7 +39,7 @@ int pn2x_kabsch_backward(int b, int xb, int num, const float *x, const float *y,
  *   xyz2[b,i,:] = R_b^T (points[b,i,:] - t_b) / scale      xyz1[b,k,:] = R_b^T (kp[b,k,:] - t_b) / scale
  * (reference hand_network.py:100,118-119 + hand_utils.py:30-31,42-66: ransac_rt with a CPU SVD, torch.cat,
  * transpose, matmul, divide).  points (b,n,3), kp (b,j,3), palm_template (xb,num,3) with xb in {1,b};
- * outputs R (b,3,3), t (b,3,1), xyz2 (b,n,3), xyz1 (b,j,3), all point-major.
+ * outputs R (b,3,3), t (b,3,1), xyz2 (b,n,3), xyz1 (b,j,3), all point-major.  n == 0: points and xyz2 may be NULL.
  * xyz2_copy (or NULL): a second copy of xyz2 into three columns of a wider row buffer (row stride copy_ld floats).
  * nonfinite (device int32, b entries, or NULL): per-cloud flag, 1 when the cloud, the keypoints or the fit of cloud b contain
  * a NaN / Inf.  Handed to pn2x_pose_head, it turns that frame's predicted keypoints into NaN: the fused inference kernels
