@@ -8,7 +8,9 @@
 //     mbcnt prefix-popcount appends the hits in ascending index order (the reference's
 //     serial scan order), and the wave leaves the scan as soon as nsample hits are found;
 //   * every element of the output row is written (hits, then first-hit padding, or zeros),
-//     so the caller does not have to pre-zero idx (pointnet2_utils.py:262).
+//     so the caller does not have to pre-zero idx (pointnet2_utils.py:262);
+//   * optionally the hit count of every centroid, min(hits, nsample) and 1 for a row without a hit (its list is all point 0:
+//     one slot of it gives the same max), for consumers that skip the padding (sa_fused.hip: the class walk).
 #include "pn2_common.h"
 #include "fps_tie.h"
 
@@ -23,7 +25,8 @@ template <int CPW, bool JOINT>  // centroids per wave; JOINT: they walk the cand
 __device__ __forceinline__ void ball_query_body(const int bx, const int by, int n, int m, float radius2, int nsample,
                                                 const float *__restrict__ new_xyz_all, const float *__restrict__ xyz_all,
                                                 int *__restrict__ idx_all, const int *__restrict__ picks_all,
-                                                float *__restrict__ new_xyz_out_all, float *__restrict__ new_xyz_copy, int copy_ld) {
+                                                float *__restrict__ new_xyz_out_all, float *__restrict__ new_xyz_copy, int copy_ld,
+                                                int *__restrict__ counts_all) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tile_cap = n < kBqTile ? n : kBqTile;
     float *sx = smem, *sy = smem + tile_cap, *sz = smem + 2 * tile_cap;
@@ -146,6 +149,7 @@ __device__ __forceinline__ void ball_query_body(const int bx, const int by, int 
         int *__restrict__ row = idx + (size_t)s * nsample;
         const int fill = cnt[c] > 0 ? first[c] : 0;
         for (int p = cnt[c] + lane; p < nsample; p += kWave) row[p] = fill;
+        if (counts_all && lane == 0) counts_all[(size_t)b * m + s] = cnt[c] < 1 ? 1 : (cnt[c] < nsample ? cnt[c] : nsample);
     }
 }
 
@@ -153,9 +157,9 @@ template <int CPW, bool JOINT>
 __global__ void __launch_bounds__(kBqThreads)
 ball_query_kernel(int n, int m, float radius2, int nsample, const float *__restrict__ new_xyz_all,
                   const float *__restrict__ xyz_all, int *__restrict__ idx_all, const int *__restrict__ picks_all,
-                  float *__restrict__ new_xyz_out_all, float *__restrict__ new_xyz_copy, int copy_ld) {
+                  float *__restrict__ new_xyz_out_all, float *__restrict__ new_xyz_copy, int copy_ld, int *__restrict__ counts_all) {
     ball_query_body<CPW, JOINT>((int)blockIdx.x, (int)blockIdx.y, n, m, radius2, nsample, new_xyz_all, xyz_all, idx_all, picks_all,
-                                new_xyz_out_all, new_xyz_copy, copy_ld);
+                                new_xyz_out_all, new_xyz_copy, copy_ld, counts_all);
 }
 
 // The level-1 ball query around the picks of a sampling run AND that run's tie check (fps_tie.h) in one launch: both need the
@@ -164,13 +168,14 @@ template <int CPW>
 __global__ void __launch_bounds__(kBqThreads)
 ball_tie_kernel(int nbx_ball, int nb_ball, int nbx_tie, int n, int m, float radius2, int nsample, const float *__restrict__ xyz_all,
                 int *__restrict__ idx_all, const int *__restrict__ picks_all, float *__restrict__ new_xyz_out_all,
-                float *__restrict__ new_xyz_copy, int copy_ld, int m2, const float *__restrict__ radii_all, int *__restrict__ flags) {
+                float *__restrict__ new_xyz_copy, int copy_ld, int m2, const float *__restrict__ radii_all, int *__restrict__ flags,
+                int *__restrict__ counts_all) {
     const int L = (int)blockIdx.x;
     if (L < nb_ball) {  // workgroup-uniform
         const int by = L / nbx_ball;
         // (new_xyz_all is unused with picks; a literal nullptr here crashes the inliner of this hipcc)
         ball_query_body<CPW, false>(L - by * nbx_ball, by, n, m, radius2, nsample, xyz_all, xyz_all, idx_all, picks_all, new_xyz_out_all,
-                                    new_xyz_copy, copy_ld);
+                                    new_xyz_copy, copy_ld, counts_all);
     } else {
         const int T = L - nb_ball, by = T / nbx_tie;
         fps_tie_body(T - by * nbx_tie, by, nbx_tie, n, m2, m, xyz_all, picks_all, radii_all, flags);
@@ -179,7 +184,7 @@ ball_tie_kernel(int nbx_ball, int nb_ball, int nbx_tie, int n, int m, float radi
 
 int ball_query_dispatch(int b, int n, int m, float radius, int nsample, const float *new_xyz,
                         const float *xyz, int *idx, hipStream_t st, const int *picks, float *new_xyz_out, float *new_xyz_copy,
-                        int copy_ld) {
+                        int copy_ld, int *counts) {
     if (b == 0 || m == 0) return PN2_OK;
     const float radius2 = radius * radius;  // fp32 product, ball_query_gpu.cu:23
     const int tile_cap = n < kBqTile ? n : kBqTile;
@@ -193,15 +198,15 @@ int ball_query_dispatch(int b, int n, int m, float radius, int nsample, const fl
     dim3 grid((m + per_block - 1) / per_block, b);
     const bool joint = cpw >= 2 && n >= 4096;
     if (cpw == 4 && joint)
-        hipLaunchKernelGGL((ball_query_kernel<4, true>), grid, dim3(kBqThreads), lds, st, n, m, radius2, nsample, new_xyz, xyz, idx, picks, new_xyz_out, new_xyz_copy, copy_ld);
+        hipLaunchKernelGGL((ball_query_kernel<4, true>), grid, dim3(kBqThreads), lds, st, n, m, radius2, nsample, new_xyz, xyz, idx, picks, new_xyz_out, new_xyz_copy, copy_ld, counts);
     else if (cpw == 4)
-        hipLaunchKernelGGL((ball_query_kernel<4, false>), grid, dim3(kBqThreads), lds, st, n, m, radius2, nsample, new_xyz, xyz, idx, picks, new_xyz_out, new_xyz_copy, copy_ld);
+        hipLaunchKernelGGL((ball_query_kernel<4, false>), grid, dim3(kBqThreads), lds, st, n, m, radius2, nsample, new_xyz, xyz, idx, picks, new_xyz_out, new_xyz_copy, copy_ld, counts);
     else if (cpw == 2 && joint)
-        hipLaunchKernelGGL((ball_query_kernel<2, true>), grid, dim3(kBqThreads), lds, st, n, m, radius2, nsample, new_xyz, xyz, idx, picks, new_xyz_out, new_xyz_copy, copy_ld);
+        hipLaunchKernelGGL((ball_query_kernel<2, true>), grid, dim3(kBqThreads), lds, st, n, m, radius2, nsample, new_xyz, xyz, idx, picks, new_xyz_out, new_xyz_copy, copy_ld, counts);
     else if (cpw == 2)
-        hipLaunchKernelGGL((ball_query_kernel<2, false>), grid, dim3(kBqThreads), lds, st, n, m, radius2, nsample, new_xyz, xyz, idx, picks, new_xyz_out, new_xyz_copy, copy_ld);
+        hipLaunchKernelGGL((ball_query_kernel<2, false>), grid, dim3(kBqThreads), lds, st, n, m, radius2, nsample, new_xyz, xyz, idx, picks, new_xyz_out, new_xyz_copy, copy_ld, counts);
     else
-        hipLaunchKernelGGL((ball_query_kernel<1, false>), grid, dim3(kBqThreads), lds, st, n, m, radius2, nsample, new_xyz, xyz, idx, picks, new_xyz_out, new_xyz_copy, copy_ld);
+        hipLaunchKernelGGL((ball_query_kernel<1, false>), grid, dim3(kBqThreads), lds, st, n, m, radius2, nsample, new_xyz, xyz, idx, picks, new_xyz_out, new_xyz_copy, copy_ld, counts);
     return check_launch();
 }
 
@@ -219,7 +224,7 @@ bool ball_tie_supported(long b, long n, long m, long m2) {
 }
 
 int ball_tie_dispatch(int b, int n, int m, float radius, int nsample, const float *xyz, int *idx, const int *picks, float *new_xyz_out,
-                      float *new_xyz_copy, int copy_ld, int m2, const float *radii, int *flags, hipStream_t st) {
+                      float *new_xyz_copy, int copy_ld, int m2, const float *radii, int *flags, hipStream_t st, int *counts) {
     if (!ball_tie_supported(b, n, m, m2)) return PN2_ERANGE;
     const float radius2 = radius * radius;
     const int tile_cap = n < kBqTile ? n : kBqTile;
@@ -228,7 +233,7 @@ int ball_tie_dispatch(int b, int n, int m, float radius, int nsample, const floa
     const int nbx_ball = (m + per_block - 1) / per_block, nbx_tie = (n + kTiePts - 1) / kTiePts;
     const long grid = (long)b * nbx_ball + (long)b * nbx_tie;
     hipLaunchKernelGGL(ball_tie_kernel<1>, dim3((unsigned)grid), dim3(kBqThreads), lds, st, nbx_ball, b * nbx_ball, nbx_tie, n, m, radius2, nsample,
-                       xyz, idx, picks, new_xyz_out, new_xyz_copy, copy_ld, m2, radii, flags);
+                       xyz, idx, picks, new_xyz_out, new_xyz_copy, copy_ld, m2, radii, flags, counts);
     return check_launch();
 }
 

@@ -15,14 +15,14 @@ int fps_tie_check(int b, int n, int m, int m1, const float *xyz, const int *idx,
 bool fps_knn_supported(int n, int nq, int k);
 bool ball_tie_supported(long b, long n, long m, long m2);
 int ball_tie_dispatch(int b, int n, int m, float radius, int nsample, const float *xyz, int *idx, const int *picks, float *new_xyz_out,
-                      float *new_xyz_copy, int copy_ld, int m2, const float *radii, int *flags, hipStream_t st);
+                      float *new_xyz_copy, int copy_ld, int m2, const float *radii, int *flags, hipStream_t st, int *counts);
 bool three_nn_interp_supported(long b, long n, long m, long c, long ldp, long ldo);
 int three_nn_interp_dispatch(int b, int n, int m, int c, const float *unknown, const float *known, const float *points, int ldp,
                              float *out, int ldo, hipStream_t st);
 int fps_knn_dispatch(int b, int n, int m, const float *xyz, int *idx, float *radii, int nq, int k, int k2, const float *query,
                      int *kidx, int *kidx2, hipStream_t st);
 int ball_query_dispatch(int b, int n, int m, float radius, int nsample, const float *new_xyz, const float *xyz,
-                        int *idx, hipStream_t st, const int *picks, float *new_xyz_out, float *new_xyz_copy, int copy_ld);
+                        int *idx, hipStream_t st, const int *picks, float *new_xyz_out, float *new_xyz_copy, int copy_ld, int *counts);
 int three_nn_dispatch(int b, int n, int m, const float *unknown, const float *known, float *dist2, int *idx,
                       hipStream_t st, bool weights);
 int interp_pm_dispatch(int b, int c, int m, int n, const float *points, int ldp, const int *idx, const float *weight,
@@ -137,11 +137,16 @@ int pn2_ball_query(int b, int n, int m, float radius, int nsample, const float *
             }
         }
     }
-    return ball_query_dispatch(b, n, m, radius, nsample, new_xyz, xyz, idx, (hipStream_t)stream, nullptr, nullptr, nullptr, 0);
+    return ball_query_dispatch(b, n, m, radius, nsample, new_xyz, xyz, idx, (hipStream_t)stream, nullptr, nullptr, nullptr, 0, nullptr);
 }
 
 int pn2x_ball_query_picks(int b, int n, int m, float radius, int nsample, const float *xyz, const int *picks, float *new_xyz,
                            int *idx, float *new_xyz_copy, int copy_ld, void *stream) {
+    return pn2x_ball_query_picks_counts(b, n, m, radius, nsample, xyz, picks, new_xyz, idx, new_xyz_copy, copy_ld, nullptr, stream);
+}
+
+int pn2x_ball_query_picks_counts(int b, int n, int m, float radius, int nsample, const float *xyz, const int *picks, float *new_xyz,
+                                  int *idx, float *new_xyz_copy, int copy_ld, int *counts, void *stream) {
     PN2_REQ(!new_xyz_copy || copy_ld >= 3, PN2_EINVAL);
     PN2_REQ(b >= 0 && n >= 1 && m >= 0 && nsample >= 1, PN2_EINVAL);
     PN2_REQ(radius == radius, PN2_EINVAL);
@@ -149,20 +154,27 @@ int pn2x_ball_query_picks(int b, int n, int m, float radius, int nsample, const 
     PN2_REQ(xyz && picks && new_xyz && idx, PN2_ENULL);
     PN2_REQ(b <= 65535, PN2_ERANGE);
     PN2_REQ(fits_int((long)n * 3) && fits_int((long)m * nsample), PN2_ERANGE);
-    return ball_query_dispatch(b, n, m, radius, nsample, nullptr, xyz, idx, (hipStream_t)stream, picks, new_xyz, new_xyz_copy, copy_ld);
+    return ball_query_dispatch(b, n, m, radius, nsample, nullptr, xyz, idx, (hipStream_t)stream, picks, new_xyz, new_xyz_copy, copy_ld, counts);
 }
 
 int pn2x_ball_query_picks_ties_supported(int b, int n, int m, int m2) { return ball_tie_supported(b, n, m, m2) ? 1 : 0; }
 
 int pn2x_ball_query_picks_ties(int b, int n, int m, float radius, int nsample, const float *xyz, const int *picks, float *new_xyz,
                                int *idx, float *new_xyz_copy, int copy_ld, int m2, const float *radii, int *flags, void *stream) {
+    return pn2x_ball_query_picks_ties_counts(b, n, m, radius, nsample, xyz, picks, new_xyz, idx, new_xyz_copy, copy_ld, m2, radii, flags,
+                                             nullptr, stream);
+}
+
+int pn2x_ball_query_picks_ties_counts(int b, int n, int m, float radius, int nsample, const float *xyz, const int *picks, float *new_xyz,
+                                      int *idx, float *new_xyz_copy, int copy_ld, int m2, const float *radii, int *flags, int *counts,
+                                      void *stream) {
     PN2_REQ(!new_xyz_copy || copy_ld >= 3, PN2_EINVAL);
     PN2_REQ(b >= 0 && n >= 1 && m >= 1 && nsample >= 1 && m2 >= 1 && m2 <= m, PN2_EINVAL);
     PN2_REQ(radius == radius, PN2_EINVAL);
     if (b == 0) return PN2_OK;
     PN2_REQ(xyz && picks && new_xyz && idx && radii && flags, PN2_ENULL);
     PN2_REQ(b <= 65535 && fits_int((long)n * 3) && fits_int((long)m * nsample), PN2_ERANGE);
-    return ball_tie_dispatch(b, n, m, radius, nsample, xyz, idx, picks, new_xyz, new_xyz_copy, copy_ld, m2, radii, flags, (hipStream_t)stream);
+    return ball_tie_dispatch(b, n, m, radius, nsample, xyz, idx, picks, new_xyz, new_xyz_copy, copy_ld, m2, radii, flags, (hipStream_t)stream, counts);
 }
 
 int pn2_group_points(int b, int c, int n, int npoints, int nsample, const float *points, const int *idx,

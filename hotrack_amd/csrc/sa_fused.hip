@@ -19,6 +19,13 @@
 // Tile geometry: 4 COMPUTE waves = WC channel groups x WP position groups (WC*WP = 4); a position
 // group owns 64 consecutive (s,k) positions = 64/K centroids (K in {16,32,64}); 4 LOAD waves prepare the next tile.
 //
+// Class walk (pn2x_sa_mlp_max_classes, sa_body with K = 0): ball-query lists pad their 32 slots with copies of the first hit, and
+// on the clouds this serves nine lists in ten hold at most 8 hits.  The walk gives a centroid only the first K' = 8, 16 or 32
+// slots of its row, the smallest that holds its hits: centroids sorted by K' on the device (sa_class_lists_kernel), a position
+// group = 64 / K' listed centroids, K' = 8 pooled with ONE cross-lane step.  It changes no bit of the result: every position's
+// MLP output is independent of the tile and row it sits in, the dropped slots are exact copies of slot 0, and the max over a
+// list is the max over its distinct entries (tests/test_gpu_sa_classes.py holds it to torch.equal with the fixed-K launch).
+//
 // What bounds it (profiles/r02_misc_measurements.md): on this part the fp32 matrix rate equals the packed-fp32 vector
 // rate, and next to a wave that streams fp32 MFMAs the SIMD issues almost nothing else -- VALU work does not hide under
 // the MFMAs, wherever it is placed and whatever the wave priorities.  A tile costs its 640 MFMAs x 32 cycles plus about
@@ -117,6 +124,13 @@ __device__ __forceinline__ f32x2 pk_fma_hi(f32x2 w, f32x2 d, f32x2 acc) {
     return r;
 }
 
+// max over lane rows {0, 1} and over {2, 3} of a wave64 (the first step of rows_max4): rows 0-1 get the first, rows 2-3 the second
+__device__ __forceinline__ float rows_max2(float v) {
+    const unsigned u = __builtin_bit_cast(unsigned, v);
+    auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);  // a[0]: rows {0,0,2,2}, a[1]: rows {1,1,3,3}
+    return fmax_raw(__builtin_bit_cast(float, (unsigned)a[0]), __builtin_bit_cast(float, (unsigned)a[1]));
+}
+
 struct SaArgs {
     int B, N, S, K, lgK;
     const float *a1f;   // (B,N,a1f_ld>=C1) point-major per-point feature term of layer 1, or nullptr
@@ -134,6 +148,8 @@ struct SaArgs {
     int out_s, out_c;
     int num_tiles, tiles_per_cloud;
     long long *trace;   // debug: per-phase s_memtime stamps of workgroup 0 (nullptr = off)
+    const int *cls_list;   // class walk (K = 0, see sa_body): (B*S, 4) records {centroid b*S + s, b*N, b, s}, class 32 first, then 16, then 8
+    const int *cls_sizes;  // class walk: the three class sizes [17..32 hits, 9..16, <= 8], read on the device
 };
 
 // Workgroup = 8 waves with fixed roles (wave specialisation):
@@ -151,7 +167,15 @@ struct SaArgs {
 // of a launch that serves two scales of a module at once -- sa_mlp_max_pair_kernel below).
 template <int C1, int C2, int C3, int WC, int RTC, int MINW, int NB1, int K, int MODE>
 __device__ __forceinline__ void sa_body(const SaArgs &A, const int wg, const int nwg) {
-    static_assert(K == 16 || K == 32 || K == 64, "K");
+    static_assert(K == 0 || K == 16 || K == 32 || K == 64, "K");
+    // K = 0 ("class walk", pn2x_sa_mlp_max_classes): the index rows are ball-query lists of 32 slots whose tail repeats the first
+    // hit, and a centroid is served with only the first K' = 8, 16 or 32 slots, the smallest that holds its hits.  The centroids
+    // come sorted by K' in a device-side list (sa_class_lists_kernel), a tile is still TM positions = TM / K' listed centroids,
+    // and the workgroup walks an equal contiguous share of [class-32 tiles | class-16 tiles | class-8 tiles], whose counts it
+    // reads from device memory.  NOT A BIT CHANGES: a position's MLP output does not depend on the tile or row it sits in (each
+    // row of an MFMA tile is its own dot products, in the same order), the dropped slots are copies of slot 0, and a max over
+    // a list equals the max over the list with its duplicates removed.
+    constexpr bool CLS = K == 0;
     // MODE 4 ("rows"): no neighbourhoods at all -- H1 = the input rows a1f[r, :] as they are, and every row of the layer-3
     // output is stored (no max-pool): a fused two-layer MLP over R = S*K plain rows (pn2x_mlp2_rows), same tile loop.
     // MODE 5: rows whose first layer has three more input columns x[r, C1 .. C1+2] (coordinates next to the features: the
@@ -165,7 +189,7 @@ __device__ __forceinline__ void sa_body(const SaArgs &A, const int wg, const int
     constexpr bool has_a1f = MODE >= 1, has_xyz = !ROWS, has_cadd = MODE == 2 || MODE == 3;
     const bool p_a1f = MODE == 3 ? A.a1f != nullptr : has_a1f, p_xyz = MODE == 3 ? A.xyz != nullptr : has_xyz;
     const bool p_cadd = MODE == 3 ? A.cadd != nullptr : has_cadd;
-    constexpr int lgK = K == 16 ? 4 : K == 32 ? 5 : 6;
+    constexpr int lgK = K == 16 ? 4 : K == 32 ? 5 : 6;  // (unused by the class walk: K' is a property of the tile)
     const int N = A.N, S = A.S;
     const float *__restrict__ W2 = A.w2, *__restrict__ b2 = A.b2, *__restrict__ W3 = A.w3, *__restrict__ b3 = A.b3;
     float *__restrict__ out = A.out;
@@ -223,10 +247,43 @@ __device__ __forceinline__ void sa_body(const SaArgs &A, const int wg, const int
     const int row0 = (lt / Q1) * RPT;
     // Tile cursor: tile = wg + i*nwg -> (cloud b, tile t inside the cloud), advanced incrementally (no division in
     // the loops).
-    const int cur_db = nwg / tiles_per_cloud, cur_dt = nwg - cur_db * tiles_per_cloud;
+    // The workgroup's tiles: first, first + step, ... < end.  Class walk: the three class sizes give the tiles per class, the
+    // sequence [class 32 | class 16 | class 8] is cut into nwg equal contiguous shares (every tile is TM positions through the
+    // same layers, so a centroid of class 32 / 16 / 8 weighs 1 : 1/2 : 1/4 and equal tile counts are equal cost), and a cursor is
+    // (tile, b = class 0 / 1 / 2 for K' = 32 / 16 / 8, t = tile inside the class).
+    int first = wg, step = nwg, end = num_tiles;
+    int cls_n0 = 0, cls_n1 = 0, cls_n2 = 0, cls_t0 = 0, cls_t1 = 0;
+    if constexpr (CLS) {
+        constexpr int lgTM = TM == 64 ? 6 : 7;
+        static_assert(TM == 64 || TM == 128, "class walk: tile of 64 or 128 positions");
+        cls_n0 = A.cls_sizes[0]; cls_n1 = A.cls_sizes[1]; cls_n2 = A.cls_sizes[2];
+        cls_t0 = (int)(((unsigned)cls_n0 * 32u + (TM - 1)) >> lgTM);
+        cls_t1 = (int)(((unsigned)cls_n1 * 16u + (TM - 1)) >> lgTM);
+        const unsigned total = (unsigned)cls_t0 + (unsigned)cls_t1 + (((unsigned)cls_n2 * 8u + (TM - 1)) >> lgTM);
+        const unsigned q = total / (unsigned)nwg, r = total - q * (unsigned)nwg;
+        first = (int)((unsigned)wg * q + ((unsigned)wg < r ? (unsigned)wg : r));
+        end = first + (int)q + ((unsigned)wg < r ? 1 : 0);
+        step = 1;
+    }
+    auto sel3 = [](int c, int v0, int v1, int v2) { return c == 0 ? v0 : c == 1 ? v1 : v2; };
+    const int cur_db = CLS ? 0 : nwg / tiles_per_cloud, cur_dt = CLS ? 0 : nwg - cur_db * tiles_per_cloud;
     struct Cursor { int tile, b, t; };
-    auto cursor_at = [&](int tile) { Cursor c; c.tile = tile; c.b = tile / tiles_per_cloud; c.t = tile - c.b * tiles_per_cloud; return c; };
+    auto cursor_at = [&](int tile) {
+        Cursor c;
+        c.tile = tile;
+        if constexpr (CLS) {
+            c.b = 0; c.t = tile;
+            if (c.t >= cls_t0) {
+                c.t -= cls_t0; c.b = 1;
+                if (c.t >= cls_t1) { c.t -= cls_t1; c.b = 2; }
+            }
+        } else {
+            c.b = tile / tiles_per_cloud; c.t = tile - c.b * tiles_per_cloud;
+        }
+        return c;
+    };
     auto cursor_next = [&](Cursor c) {
+        if constexpr (CLS) return cursor_at(c.tile + 1);
         c.tile += nwg; c.b += cur_db; c.t += cur_dt;
         if (c.t >= tiles_per_cloud) { c.t -= tiles_per_cloud; ++c.b; }
         return c;
@@ -246,7 +303,8 @@ __device__ __forceinline__ void sa_body(const SaArgs &A, const int wg, const int
     const unsigned cxyz_cloud = 12u * (unsigned)S, cadd_cloud = (unsigned)S * cadd_ldb;
     const rsrc_t ra_all = make_rsrc(A.a1f, p_a1f ? (unsigned)A.B * a1f_cloud : 0u);
     const rsrc_t rx_all = make_rsrc(A.xyz, p_xyz ? (unsigned)A.B * xyz_cloud : 0u);
-    struct HalfIdx { int jj[RPT], ss; };
+    struct HalfIdx { int jj[RPT], ss, bn; };  // bn (class walk): first row of the centroid's cloud, b * N
+    struct HalfCid { int cid, bn; };          // class walk: a position's list record {centroid b * S + s, b * N}
     struct HalfRows { float4 a[RPT], pj[RPT], c, cs, e; };  // pj / cs: (x, y, z, the following record's x -- unused); e: MODE 5
     auto load_idx = [&](const Cursor &cu, int h, HalfIdx &I) {
         const int b = cu.b < A.B ? cu.b : A.B - 1;
@@ -269,7 +327,52 @@ __device__ __forceinline__ void sa_body(const SaArgs &A, const int wg, const int
         }
         I.ss = (pos0 + row0) >> lgK;
     };
+    // Class walk: the position's centroid comes from the class list (slots past the class read record 0 through the bounds check:
+    // centroid 0, valid addresses, never stored), then the first K' slots of its 32-slot index row.  One more dependent load
+    // than the plain walk, so the LOAD loop runs the list reads one half tile further ahead than the index reads.
+    const rsrc_t ri_all = make_rsrc(A.idx, CLS ? 128u * (unsigned)A.B * (unsigned)S : 0u);
+    auto load_cid = [&](const Cursor &cu, int h, HalfCid &C) {
+        const int lgk = 5 - cu.b;
+        const int n_c = sel3(cu.b, cls_n0, cls_n1, cls_n2), off = sel3(cu.b, 0, cls_n0, cls_n0 + cls_n1);
+        const rsrc_t rl = make_rsrc(A.cls_list + 4 * (size_t)off, 16u * (unsigned)n_c);
+        const unsigned slot = (unsigned)(cu.t * TM + h * (TM / 2) + row0) >> lgk;
+        const i32x2 v = __builtin_bit_cast(i32x2, __builtin_amdgcn_raw_buffer_load_b64(rl, (int)(16u * slot), 0, 0));
+        C.cid = v.x; C.bn = v.y;
+    };
+    auto load_idx_cls = [&](const Cursor &cu, int h, const HalfCid &C, HalfIdx &I) {
+        const int lgk = 5 - cu.b;
+        const unsigned k0 = (unsigned)(cu.t * TM + h * (TM / 2) + row0) & ((1u << lgk) - 1u);
+        const unsigned voff = mad24(C.cid, 128u, 4u * k0);  // the index rows keep their stride of 32 slots
+        if constexpr (RPT == 4) {
+            const i32x4 v = __builtin_bit_cast(i32x4, __builtin_amdgcn_raw_buffer_load_b128(ri_all, (int)voff, 0, 0));
+            I.jj[0] = v.x; I.jj[1] = v.y; I.jj[2] = v.z; I.jj[3] = v.w;
+        } else if constexpr (RPT == 2) {
+            const i32x2 v = __builtin_bit_cast(i32x2, __builtin_amdgcn_raw_buffer_load_b64(ri_all, (int)voff, 0, 0));
+            I.jj[0] = v.x; I.jj[1] = v.y;
+        } else {
+            I.jj[0] = (int)__builtin_amdgcn_raw_buffer_load_b32(ri_all, (int)voff, 0, 0);
+        }
+        I.ss = C.cid;
+        I.bn = C.bn;
+    };
     auto load_rows = [&](const Cursor &cu, const HalfIdx &I, HalfRows &D) {
+        if constexpr (CLS) {  // every operand through a whole-tensor descriptor: rows b * N + j, centroids b * S + s
+            if (has_a1f) {
+#pragma unroll
+                for (int r = 0; r < RPT; ++r) D.a[r] = ld_b128(ra_all, mad24(I.jj[r] + I.bn, a1f_ldb, c4x16), 0);
+            }
+            if (has_cadd) {
+                const rsrc_t rd = make_rsrc(A.cadd, p_cadd ? (unsigned)A.B * cadd_cloud : 0u);
+                D.c = ld_b128(rd, mad24(I.ss, cadd_ldb, c4x16), 0);
+            }
+            if (has_xyz) {
+                const rsrc_t rc = make_rsrc(A.cxyz, p_xyz ? (unsigned)A.B * cxyz_cloud : 0u);
+#pragma unroll
+                for (int r = 0; r < RPT; ++r) D.pj[r] = ld_b128(rx_all, mul24(I.jj[r] + I.bn, 12u), 0);
+                D.cs = ld_b128(rc, mul24(I.ss, 12u), 0);
+            }
+            return;
+        }
         const int b = cu.b < A.B ? cu.b : A.B - 1;
         if (has_a1f) {
             const int so = ROWS ? 0 : (int)((unsigned)b * a1f_cloud);
@@ -349,7 +452,13 @@ __device__ __forceinline__ void sa_body(const SaArgs &A, const int wg, const int
     auto gather = [&](const Cursor &cu, float *__restrict__ H1, int h) {  // unpipelined: prologue only
         HalfIdx I;
         HalfRows D;
-        load_idx(cu, h, I);
+        if constexpr (CLS) {
+            HalfCid C;
+            load_cid(cu, h, C);
+            load_idx_cls(cu, h, C, I);
+        } else {
+            load_idx(cu, h, I);
+        }
         load_rows(cu, I, D);
         finish(D, H1, h);
     };
@@ -397,9 +506,9 @@ __device__ __forceinline__ void sa_body(const SaArgs &A, const int wg, const int
             }
         }
     } else {
-        Cursor cu = cursor_at(wg);
+        Cursor cu = cursor_at(first);
         for (int a = 0; a < NB1 - 1; ++a, cu = cursor_next(cu)) {  // prologue: the first NB1-1 tiles of this workgroup
-            if (cu.tile < num_tiles) {
+            if (cu.tile < end) {
                 gather(cu, H1ring + a * TM * LD1, 0);
                 gather(cu, H1ring + a * TM * LD1, 1);
             }
@@ -429,13 +538,24 @@ __device__ __forceinline__ void sa_body(const SaArgs &A, const int wg, const int
         // pipeline fill: rows of the first half and indices of the second half of the first tile this loop gathers
         HalfIdx I0, I1;
         HalfRows D0, D1;
-        Cursor nx = cursor_at(wg + (NB1 - 1) * nwg);  // the tile whose rows this iteration finishes
-        Cursor af = cursor_next(nx);                  // the one after it (indices / first rows in flight)
-        load_idx(nx, 0, I0);
-        load_idx(nx, 1, I1);
+        Cursor nx = cursor_at(first + (NB1 - 1) * step);  // the tile whose rows this iteration finishes
+        Cursor af = cursor_next(nx);                      // the one after it (indices / first rows in flight)
+        Cursor ag = cursor_next(af);                      // class walk: the one after that (list records in flight)
+        HalfCid G0, G1;
+        if constexpr (CLS) {
+            load_cid(nx, 0, G0);
+            load_cid(nx, 1, G1);
+            load_idx_cls(nx, 0, G0, I0);
+            load_idx_cls(nx, 1, G1, I1);
+            load_cid(af, 0, G0);
+            load_cid(af, 1, G1);
+        } else {
+            load_idx(nx, 0, I0);
+            load_idx(nx, 1, I1);
+        }
         load_rows(nx, I0, D0);
         int it = 0;
-        for (int tile = wg; tile < num_tiles; tile += nwg, ++it) {
+        for (int tile = first; tile < end; tile += step, ++it) {
             stamp(it, 0);
             float *H1n = H1ring + ((it + NB1 - 1) % NB1) * TM * LD1;  // last read by COMPUTE in iteration it-1
 #if !(SA_PROBE & 1)
@@ -443,11 +563,16 @@ __device__ __forceinline__ void sa_body(const SaArgs &A, const int wg, const int
 #endif
             stamp(it, 7);
 #if !(SA_PROBE & 4)
-            load_idx(af, 0, I0);      // indices two halves ahead
+            if constexpr (CLS) {
+                load_idx_cls(af, 0, G0, I0);
+                load_cid(ag, 0, G0);
+            } else {
+                load_idx(af, 0, I0);  // indices two halves ahead
+            }
 #endif
             stamp(it, 1);
 #if !(SA_PROBE & 2)
-            if (nx.tile < num_tiles) finish(D0, H1n, 0);
+            if (nx.tile < end) finish(D0, H1n, 0);
 #endif
             stamp(it, 2);
             __syncthreads();  // B1
@@ -456,17 +581,23 @@ __device__ __forceinline__ void sa_body(const SaArgs &A, const int wg, const int
             load_rows(af, I0, D0);    // half 0 of the following tile
 #endif
 #if !(SA_PROBE & 4)
-            load_idx(af, 1, I1);
+            if constexpr (CLS) {
+                load_idx_cls(af, 1, G1, I1);
+                load_cid(ag, 1, G1);
+            } else {
+                load_idx(af, 1, I1);
+            }
 #endif
             stamp(it, 4);
 #if !(SA_PROBE & 2)
-            if (nx.tile < num_tiles) finish(D1, H1n, 1);
+            if (nx.tile < end) finish(D1, H1n, 1);
 #endif
             stamp(it, 5);
             __syncthreads();  // B2
             stamp(it, 6);
             nx = af;
-            af = cursor_next(af);
+            af = CLS ? ag : cursor_next(af);
+            if constexpr (CLS) ag = cursor_next(ag);
         }
         return;
     }
@@ -474,9 +605,9 @@ __device__ __forceinline__ void sa_body(const SaArgs &A, const int wg, const int
     __builtin_amdgcn_s_setprio(SA_COMPUTE_PRIO);
 #endif
     int it = 0;
-    Cursor cc = cursor_at(wg);
+    Cursor cc = cursor_at(first);
     constexpr int NP = 4 / RTC, NQ2 = C1 / 16, NQ3 = C2 / 16;
-    constexpr int rstep = K >> 4;  // row tiles per centroid (K = 16 -> 1, 32 -> 2, 64 -> 4)
+    constexpr int rstep = CLS ? 4 : K >> 4;  // row tiles per centroid (K = 16 -> 1, 32 -> 2, 64 -> 4; class walk: see epilogue_cls)
     // one store per centroid: lane group g writes channel tile ct = g (the row maxima are in every lane group)
     const int oc_lane = (wc * NT3 + g) * 16 + li;
     const unsigned out_cloud = 4u * ((unsigned)(S - 1) * (unsigned)A.out_s + (unsigned)(C3 - 1) * (unsigned)A.out_c + 1u);
@@ -523,6 +654,52 @@ __device__ __forceinline__ void sa_body(const SaArgs &A, const int wg, const int
             }
         }
     };
+    // Class walk: the position group's 64 / K' centroids are list slots slot0 .. ; lane l holds the {b, s} of slot0 + (l & 7)
+    // (load_me, issued behind barrier B1 so that layer 3 covers it) and a storing lane fetches its centroid's pair with two
+    // ds_bpermute.  K' = 32 and 16 pool like the plain walk; K' = 8 stops after ONE cross-lane step (lane rows 0-1 = positions
+    // 0-7 of the row tile, rows 2-3 = positions 8-15: two centroids), and lane row g stores channel tile g & 1 of centroid g >> 1.
+    int me_b = 0, me_s = 0;
+    auto load_me = [&](const Cursor &cu) {
+        const int lgk = 5 - cu.b;
+        const int n_c = sel3(cu.b, cls_n0, cls_n1, cls_n2), off = sel3(cu.b, 0, cls_n0, cls_n0 + cls_n1);
+        const rsrc_t rl = make_rsrc(A.cls_list + 4 * (size_t)off, 16u * (unsigned)n_c);
+        const unsigned slot = ((unsigned)(cu.t * TM + wp * 64) >> lgk) + (unsigned)(lane & 7);
+        const i32x2 v = __builtin_bit_cast(i32x2, __builtin_amdgcn_raw_buffer_load_b64(rl, (int)(16u * slot + 8u), 0, 0));
+        me_b = v.x; me_s = v.y;
+    };
+    const unsigned out_all = 4u * ((unsigned)(A.B - 1) * (unsigned)A.out_b + (unsigned)(S - 1) * (unsigned)A.out_s + (unsigned)(C3 - 1) * (unsigned)A.out_c + 1u);
+    auto epilogue_cls = [&](const Cursor &cu) {
+        static_assert(!CLS || NT3 == 2, "class walk: a lane row stores one of two channel tiles");
+        const int lgk = 5 - cu.b;
+        const int n_c = sel3(cu.b, cls_n0, cls_n1, cls_n2);
+        const int slot0 = (int)((unsigned)(cu.t * TM + wp * 64) >> lgk);
+        const rsrc_t ro = make_rsrc(out, out_all);
+        auto store = [&](float v, int src, int ct, bool lane_ok) {  // src: the centroid's number inside the position group
+            const unsigned bb = (unsigned)__builtin_amdgcn_ds_bpermute(4 * src, me_b), ss = (unsigned)__builtin_amdgcn_ds_bpermute(4 * src, me_s);
+            const unsigned off = 4u * (bb * (unsigned)A.out_b + ss * (unsigned)A.out_s + (unsigned)((wc * NT3 + ct) * 16 + li) * (unsigned)A.out_c);
+            const bool ok = lane_ok && slot0 + src < n_c;
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, fmaxf(v, 0.f)), ro, (int)(ok ? off : 0xffffffffu), 0, 0);
+        };
+        if (lgk == 5) {
+#pragma unroll
+            for (int rt = 0; rt < 4; rt += 2) {
+                const float v0 = rows_max4(fmax_raw(m[rt][0], m[rt + 1][0])), v1 = rows_max4(fmax_raw(m[rt][NT3 - 1], m[rt + 1][NT3 - 1]));
+                store(g == 1 ? v1 : v0, rt >> 1, g & 1, g < 2);
+            }
+        } else if (lgk == 4) {
+#pragma unroll
+            for (int rt = 0; rt < 4; ++rt) {
+                const float v0 = rows_max4(m[rt][0]), v1 = rows_max4(m[rt][NT3 - 1]);
+                store(g == 1 ? v1 : v0, rt, g & 1, g < 2);
+            }
+        } else {
+#pragma unroll
+            for (int rt = 0; rt < 4; ++rt) {
+                const float v0 = rows_max2(m[rt][0]), v1 = rows_max2(m[rt][NT3 - 1]);
+                store((g & 1) ? v1 : v0, 2 * rt + (g >> 1), g & 1, true);
+            }
+        }
+    };
     auto frag2 = [&](const float *H1, int p, int tq, int rt) {
         return *reinterpret_cast<const float4 *>(H1 + (wp * 64 + (p * RTC + rt) * 16 + li) * LD1 + 4 * g + 16 * tq);
     };
@@ -533,7 +710,7 @@ __device__ __forceinline__ void sa_body(const SaArgs &A, const int wg, const int
     float4 an2[RTC];
 #pragma unroll
     for (int rt = 0; rt < RTC; ++rt) an2[rt] = frag2(H1ring, 0, 0, rt);
-    for (int tile = wg; tile < num_tiles; tile += nwg, ++it, cc = cursor_next(cc)) {
+    for (int tile = first; tile < end; tile += step, ++it, cc = cursor_next(cc)) {
         stamp(it, 0);
         const float *H1 = H1ring + (it % NB1) * TM * LD1;
         const float *H1next = H1ring + ((it + 1) % NB1) * TM * LD1;
@@ -597,7 +774,7 @@ __device__ __forceinline__ void sa_body(const SaArgs &A, const int wg, const int
                                 acc[p & 1][rt][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(w2r[ct][4 * tq + j], av, acc[p & 1][rt][ct], 0, 0, 0);
                         }
 #if SA_DEFER_EPILOGUE
-                    if (!ROWS && tq == 0 && p == 0) epilogue();  // the previous tile's max-pool + store (nothing is written when there was none)
+                    if (!ROWS && !CLS && tq == 0 && p == 0) epilogue();  // the previous tile's max-pool + store (nothing is written when there was none)
 #endif
 #if SA_OVERLAP_WRITEOUT
                     if (tq == 0 && p > 0) writeout2(p - 1);
@@ -615,6 +792,7 @@ __device__ __forceinline__ void sa_body(const SaArgs &A, const int wg, const int
         stamp(it, 2);
         __syncthreads();  // B1: H2 complete
         stamp(it, 3);
+        if constexpr (CLS) load_me(cc);
         {
             // ---- layer 3 + max over the 16 positions of every row tile ------------------------------------------
             auto frag3 = [&](int p, int tq, int rt) {
@@ -681,7 +859,9 @@ __device__ __forceinline__ void sa_body(const SaArgs &A, const int wg, const int
                 }
             }
             stamp(it, 4);
-            if constexpr (!ROWS) {
+            if constexpr (CLS) {
+                epilogue_cls(cc);
+            } else if constexpr (!ROWS) {
                 e_b = cc.b;
                 e_pos0 = cc.t * TM;
                 e_pending = true;
@@ -695,7 +875,7 @@ __device__ __forceinline__ void sa_body(const SaArgs &A, const int wg, const int
         stamp(it, 6);
     }
 #if SA_DEFER_EPILOGUE
-    if (!ROWS) epilogue();  // the last tile's (a workgroup without tiles writes nothing: e_pending is false)
+    if (!ROWS && !CLS) epilogue();  // the last tile's (a workgroup without tiles writes nothing: e_pending is false)
 #endif
 }
 
@@ -703,6 +883,13 @@ template <int C1, int C2, int C3, int WC, int RTC, int MINW, int NB1, int K, int
 __global__ void __launch_bounds__(512, MINW)
 sa_mlp_max_kernel(const SaArgs A, const int grid) {
     sa_body<C1, C2, C3, WC, RTC, MINW, NB1, K, MODE>(A, (int)__builtin_amdgcn_workgroup_id_x(), grid);
+}
+
+// The class walk (sa_body with K = 0) as a kernel of its own name: one persistent launch per level.
+template <int C1, int C2, int C3, int WC, int RTC, int MINW, int NB1, int MODE>
+__global__ void __launch_bounds__(512, MINW)
+sa_mlp_max_classes_kernel(const SaArgs A, const int grid) {
+    sa_body<C1, C2, C3, WC, RTC, MINW, NB1, 0, MODE>(A, (int)__builtin_amdgcn_workgroup_id_x(), grid);
 }
 
 // Both scales of a keypoint-query module (K0 and K1 neighbours, same layer widths) in ONE persistent grid: workgroups
@@ -758,6 +945,27 @@ static int launch_sa_km(int b, SaArgs a, hipStream_t st) {
     // (1344 tiles: 224 workgroups x 6 instead of 256 of which 64 run 6 and 192 run 5).
     const int rounds = (a.num_tiles + max_wg - 1) / max_wg;
     const int grid = (a.num_tiles + rounds - 1) / rounds;
+    hipLaunchKernelGGL(kfn, dim3(grid), dim3(512), lds, st, a, grid);
+    return check_launch();
+}
+
+// The class walk's launch: the tile count lives in device memory (the class sizes; nothing of it reaches the host, so the
+// launch can be captured and replayed on other inputs), hence no "equal rounds" sizing here: the grid is every workgroup the
+// compute units in use can hold -- capped by the tile count of all-full lists -- and the kernel cuts the tile sequence into
+// that many equal contiguous shares.
+template <int C1, int C2, int C3, int WC, int RTC, int MINW, int NB1, int MODE>
+static int launch_sa_classes(int b, SaArgs a, hipStream_t st) {
+    constexpr int WP = 4 / WC, TM = WP * 64;
+    a.B = b; a.K = 32; a.lgK = 5; a.tiles_per_cloud = 1; a.num_tiles = 0;
+    const size_t lds = (size_t)TM * (NB1 * (C1 + SA_PAD) + C2 + SA_PAD) * sizeof(float);
+    auto kfn = sa_mlp_max_classes_kernel<C1, C2, C3, WC, RTC, MINW, NB1, MODE>;
+    static PerDeviceOnce raised;
+    if (lds > 64 * 1024 && raised.first_use())
+        (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const int wg_per_cu = (int)((160 * 1024) / lds) < MINW / 2 ? (int)((160 * 1024) / lds) : MINW / 2;
+    const long max_wg = (long)sa_compute_units() * (wg_per_cu < 1 ? 1 : wg_per_cu);
+    const long most = ((long)b * a.S * 32 + TM - 1) / TM + 2;  // all lists full; + 2: the two class boundaries' short tiles
+    const int grid = (int)(most < max_wg ? most : max_wg);
     hipLaunchKernelGGL(kfn, dim3(grid), dim3(512), lds, st, a, grid);
     return check_launch();
 }
@@ -833,7 +1041,101 @@ static bool sa_ranges_ok(long b, long n, long s, long k, long a1f_ld, long cadd_
     return n < (1L << 24) && s < (1L << 24) && 4 * a1f_ld < (1L << 24) && 4 * cadd_ld < (1L << 24) &&
            4 * b * n * (a1f_ld > 3 ? a1f_ld : 3) <= lim && 4 * s * (cadd_ld > 3 ? cadd_ld : 3) <= lim && 4 * s * k <= lim;
 }
+
+// ---- class lists of the class walk ------------------------------------------------------------------------------------------
+// counts (M = B*S): hits of every centroid's ball query, 1 .. 32.  One workgroup: thread t owns the centroids [t * per, (t + 1) * per),
+// counts its three classes (17..32 hits | 9..16 | <= 8), a block scan of the per-thread counts places every centroid -- class 32
+// first, then 16, then 8, ascending id inside a class (no atomics: the order is a function of the counts alone) -- and every
+// centroid's record {b*S + s, b*N, b, s} goes to its place.  sizes[0..2] = the class sizes.
+constexpr int kClsThreads = 1024;
+__global__ __launch_bounds__(kClsThreads) void sa_class_lists_kernel(int M, int S, int N, const int *__restrict__ counts,
+                                                                      int *__restrict__ list, int *__restrict__ sizes) {
+    __shared__ int scan[3][kClsThreads];
+    const int tid = (int)threadIdx.x;
+    const int per = (M + kClsThreads - 1) / kClsThreads;
+    const long lo = (long)tid * per;
+    const int i0 = (int)(lo < M ? lo : M), i1 = i0 + per < M ? i0 + per : M;
+    int c0 = 0, c1 = 0, c2 = 0;
+    for (int i = i0; i < i1; ++i) {
+        const int k = counts[i];
+        c0 += k > 16 ? 1 : 0;
+        c1 += (k > 8 && k <= 16) ? 1 : 0;
+        c2 += k <= 8 ? 1 : 0;
+    }
+    int s0 = c0, s1 = c1, s2 = c2;  // inclusive scan
+    for (int d = 1; d < kClsThreads; d <<= 1) {
+        scan[0][tid] = s0; scan[1][tid] = s1; scan[2][tid] = s2;
+        __syncthreads();
+        if (tid >= d) { s0 += scan[0][tid - d]; s1 += scan[1][tid - d]; s2 += scan[2][tid - d]; }
+        __syncthreads();
+    }
+    scan[0][tid] = s0; scan[1][tid] = s1; scan[2][tid] = s2;
+    __syncthreads();
+    const int t0 = scan[0][kClsThreads - 1], t1 = scan[1][kClsThreads - 1], t2 = scan[2][kClsThreads - 1];
+    int p0 = s0 - c0, p1 = t0 + s1 - c1, p2 = t0 + t1 + s2 - c2;
+    int b = i0 / S, s = i0 - b * S;
+    int4 *__restrict__ dst = reinterpret_cast<int4 *>(list);
+    for (int i = i0; i < i1; ++i) {
+        const int k = counts[i];
+        const int4 rec = make_int4(i, b * N, b, s);
+        if (k > 16) dst[p0++] = rec;
+        else if (k > 8) dst[p1++] = rec;
+        else dst[p2++] = rec;
+        if (++s == S) { s = 0; ++b; }
+    }
+    if (tid == 0) { sizes[0] = t0; sizes[1] = t1; sizes[2] = t2; }
+}
 }  // namespace pn2
+
+extern "C" int pn2x_sa_class_lists(int b, int s, int n, const int *counts, int *list, int *sizes, void *stream) {
+    using namespace pn2;
+    if (b < 0 || s < 1 || n < 1) return PN2_EINVAL;
+    if ((long)b * s >= (1L << 24) || (long)b * n >= (1L << 24)) return PN2_ERANGE;  // the class walk's 24-bit row numbers
+    if (!sizes) return PN2_ENULL;
+    if (b > 0 && (!counts || !list)) return PN2_ENULL;
+    if ((uintptr_t)list % 16 != 0) return PN2_EINVAL;
+    hipLaunchKernelGGL(sa_class_lists_kernel, dim3(1), dim3(kClsThreads), 0, (hipStream_t)stream, b * s, s, n, counts, list, sizes);
+    return check_launch();
+}
+
+extern "C" int pn2x_sa_mlp_max_classes_supported(int k, int c1, int c2, int c3) {
+    return (k == 32 && ((c1 == 32 && c2 == 32 && c3 == 64) || (c1 == 64 && c2 == 64 && c3 == 128))) ? 1 : 0;
+}
+
+extern "C" int pn2x_sa_mlp_max_classes(int b, int n, int s, int k, int c1, int c2, int c3, const float *a1f, int a1f_ld,
+                                       const float *xyz, const float *cxyz, const float *wx, const float *b1, const float *cadd,
+                                       int cadd_ld, const int *idx, const int *cls_list, const int *cls_sizes,
+                                       const float *w2, const float *b2, const float *w3, const float *b3, float *out,
+                                       long out_b, int out_s, int out_c, void *stream) {
+    using namespace pn2;
+    if (b < 0 || n < 1 || s < 0 || k < 1) return PN2_EINVAL;
+    if (b == 0 || s == 0) return PN2_OK;
+    if (!idx || !cls_list || !cls_sizes || !w2 || !b2 || !w3 || !b3 || !out) return PN2_ENULL;
+    if (!a1f && !xyz) return PN2_ENULL;
+    if (xyz && (!cxyz || !wx)) return PN2_ENULL;
+    if ((a1f && (a1f_ld < c1 || a1f_ld % 4)) || (cadd && (cadd_ld < c1 || cadd_ld % 4))) return PN2_EINVAL;
+    if (!pn2x_sa_mlp_max_classes_supported(k, c1, c2, c3)) return PN2_ERANGE;
+    if (!sa_ranges_ok(b, n, s, k, a1f ? a1f_ld : 0, cadd ? cadd_ld : 0, c3, out_s, out_c)) return PN2_ERANGE;
+    // whole-tensor descriptors and 24-bit row numbers b*n + j, b*s + s' (sa_body, class walk)
+    const long lim = 0xffffffffL;
+    if (out_b < 0 || (long)b * n >= (1L << 24) || (long)b * s >= (1L << 24) || 128L * b * s > lim ||
+        4L * b * s * (cadd && cadd_ld > 3 ? cadd_ld : 3) > lim || 4 * ((b - 1) * out_b + (s - 1L) * out_s + (c3 - 1L) * out_c + 1) >= lim)
+        return PN2_ERANGE;
+    if (((uintptr_t)a1f | (uintptr_t)cadd | (uintptr_t)b1 | (uintptr_t)w2 | (uintptr_t)w3 | (uintptr_t)cls_list) % 16 != 0) return PN2_EINVAL;
+    SaArgs a;
+    a.B = b; a.N = n; a.S = s; a.K = k; a.lgK = 5;
+    a.a1f = a1f; a.a1f_ld = a1f_ld; a.cadd_ld = cadd_ld; a.xyz = xyz; a.cxyz = cxyz; a.wx = wx; a.b1 = b1; a.cadd = cadd; a.idx = idx;
+    a.w2 = w2; a.b2 = b2; a.w3 = w3; a.b3 = b3; a.w2e = nullptr; a.out = out; a.out_b = out_b; a.out_s = out_s; a.out_c = out_c;
+    a.num_tiles = 0; a.tiles_per_cloud = 1; a.trace = nullptr; a.cls_list = cls_list; a.cls_sizes = cls_sizes;
+    hipStream_t st = (hipStream_t)stream;
+    const bool fa = a1f != nullptr, fx = xyz != nullptr, fc = cadd != nullptr;
+    if (c1 == 32) {  // sa1: coordinates only; any other operand set through the instance that tests its operands at run time
+        if (!fa && fx && !fc) return launch_sa_classes<32, 32, 64, 2, 4, 4, SA_NB1, 0>(b, a, st);
+        return launch_sa_classes<32, 32, 64, 2, 4, 4, SA_NB1, 3>(b, a, st);
+    }
+    if (fa && fx && !fc) return launch_sa_classes<64, 64, 128, 4, 2, 4, SA_NB1, 1>(b, a, st);  // sa2: features + coordinates
+    return launch_sa_classes<64, 64, 128, 4, 2, 4, SA_NB1, 3>(b, a, st);
+}
 
 extern "C" int pn2x_sa_set_compute_units(int n) {
     if (n < 0) return PN2_EINVAL;
@@ -862,7 +1164,7 @@ extern "C" int pn2x_sa_mlp_max(int b, int n, int s, int k, int c1, int c2, int c
     a.B = b; a.N = n; a.S = s; a.K = k; a.lgK = 0;
     a.a1f = a1f; a.a1f_ld = a1f_ld; a.cadd_ld = cadd_ld; a.xyz = xyz; a.cxyz = cxyz; a.wx = wx; a.b1 = b1; a.cadd = cadd; a.idx = idx;
     a.w2 = w2; a.b2 = b2; a.w3 = w3; a.b3 = b3; a.w2e = nullptr; a.out = out; a.out_b = out_b; a.out_s = out_s; a.out_c = out_c;
-    a.num_tiles = 0; a.tiles_per_cloud = 0; a.trace = g_sa_trace;
+    a.num_tiles = 0; a.tiles_per_cloud = 0; a.trace = g_sa_trace; a.cls_list = nullptr; a.cls_sizes = nullptr;
     hipStream_t st = (hipStream_t)stream;
     if (c1 == 32 && c2 == 32 && c3 == 64) return launch_sa<32, 32, 64, 2, 4, 4, SA_NB1>(b, a, st);
     if (c1 == 64 && c2 == 64 && c3 == 128) return launch_sa<64, 64, 128, 4, 2, 4, SA_NB1>(b, a, st);
@@ -882,7 +1184,7 @@ static int fill_sa_args(int b, const pn2x_sa_problem &p, int c1, int c3, SaArgs 
     a.B = 0; a.N = p.n; a.S = p.s; a.K = p.k; a.lgK = 0;
     a.a1f = p.a1f; a.a1f_ld = p.a1f_ld; a.cadd_ld = p.cadd_ld; a.xyz = p.xyz; a.cxyz = p.cxyz; a.wx = p.wx; a.b1 = p.b1;
     a.cadd = p.cadd; a.idx = p.idx; a.w2 = p.w2; a.b2 = p.b2; a.w3 = p.w3; a.b3 = p.b3; a.w2e = nullptr; a.out = p.out; a.out_b = p.out_b;
-    a.out_s = p.out_s; a.out_c = p.out_c; a.num_tiles = 0; a.tiles_per_cloud = 0; a.trace = nullptr;
+    a.out_s = p.out_s; a.out_c = p.out_c; a.num_tiles = 0; a.tiles_per_cloud = 0; a.trace = nullptr; a.cls_list = nullptr; a.cls_sizes = nullptr;
     return PN2_OK;
 }
 }  // namespace pn2
@@ -927,7 +1229,7 @@ extern "C" int pn2x_mlp2_rows(long rows, int c1, int c2, int c3, const float *x,
     a.B = 1; a.N = (int)rows; a.K = 16; a.S = (int)((rows + 15) / 16); a.lgK = 4;
     a.a1f = x; a.a1f_ld = ldx; a.cadd_ld = 0; a.xyz = nullptr; a.cxyz = nullptr; a.wx = nullptr; a.b1 = nullptr; a.cadd = nullptr; a.idx = nullptr;
     a.w2 = w2; a.b2 = b2; a.w3 = w3; a.b3 = b3; a.w2e = w2e; a.out = out; a.out_b = 0; a.out_s = ldo; a.out_c = 1;
-    a.num_tiles = 0; a.tiles_per_cloud = 0; a.trace = nullptr;
+    a.num_tiles = 0; a.tiles_per_cloud = 0; a.trace = nullptr; a.cls_list = nullptr; a.cls_sizes = nullptr;
     if (w2e) return launch_sa_km<128, 128, 128, 4, 2, 2, SA_NB1, 16, 5>(1, a, (hipStream_t)stream);
     return launch_sa_km<128, 128, 128, 4, 2, 2, SA_NB1, 16, 4>(1, a, (hipStream_t)stream);
 }

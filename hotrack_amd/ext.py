@@ -105,6 +105,60 @@ def sa_mlp_max(idx: torch.Tensor, w2, b2, w3, b3, *, a1f=None, xyz=None, cxyz=No
     """Fused SA scale (include/pn2_ext.h: pn2x_sa_mlp_max).
     idx (B,S,K) int32; a1f (B,N,>=C1) rows; xyz (B,N,3); cxyz (B,S,3); wx (C1,3); b1 (C1); cadd (B,S,>=C1).
     Returns (B,C3,S), or (B,S,C3) if point_major; `out` may be a (B,S,C3) column block of a wider buffer."""
+    return _sa_mlp_max(idx, w2, b2, w3, b3, None, a1f, xyz, cxyz, wx, b1, cadd, out, point_major)
+
+
+_lib.pn2x_sa_mlp_max_classes.argtypes = [_ci] * 7 + [_vp, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _cl, _ci, _ci, _vp]
+_lib.pn2x_sa_mlp_max_classes.restype = _ci
+_lib.pn2x_sa_mlp_max_classes_supported.argtypes = [_ci] * 4
+_lib.pn2x_sa_mlp_max_classes_supported.restype = _ci
+_lib.pn2x_sa_class_lists.argtypes = [_ci, _ci, _ci, _vp, _vp, _vp, _vp]
+_lib.pn2x_sa_class_lists.restype = _ci
+
+
+def sa_mlp_max_classes_supported(k: int, c1: int, c2: int, c3: int) -> bool:
+    """Does pn2x_sa_mlp_max_classes (the fused SA scale that skips ball-query padding) cover this neighbourhood size and widths?"""
+    return bool(_lib.pn2x_sa_mlp_max_classes_supported(k, c1, c2, c3))
+
+
+def sa_class_partition(counts: torch.Tensor):
+    """The class rule of sa_class_lists as plain torch (any device; the statement the tests hold the kernel to): counts (B,S)
+    -> (ids (B*S,) int32: the centroids b*S + s with count 17..32 in ascending order, then those with 9..16, then those with
+    <= 8; sizes (3,) int32)."""
+    c = counts.reshape(-1)
+    ids = torch.arange(c.numel(), dtype=torch.int32, device=c.device)
+    masks = (c > 16, (c > 8) & (c <= 16), c <= 8)
+    return torch.cat([ids[m] for m in masks]), torch.stack([m.sum() for m in masks]).to(torch.int32)
+
+
+def sa_class_lists(counts: torch.Tensor, n: int):
+    """Class lists of the class walk from the ball query's hit counts (include/pn2_ext.h: pn2x_sa_class_lists): counts (B,S) int32
+    -> (lst (B*S,4) int32 records {b*S + s, b*n, b, s}, sizes (3,) int32), one launch, nothing synchronises with the host.
+    n: points per cloud of the level the index lists name."""
+    if not isinstance(counts, torch.Tensor) or counts.dim() != 2 or counts.dtype != torch.int32 or not counts.is_cuda:
+        raise TypeError("sa_class_lists: counts must be a (B,S) int32 GPU tensor")
+    if int(n) < 1:
+        raise ValueError("sa_class_lists: n >= 1")
+    B, S = counts.shape
+    pc = _native._ptr(counts, "counts", torch.int32, B * S)
+    lst = torch.empty((B * S, 4), dtype=torch.int32, device=counts.device)
+    sizes = torch.empty(3, dtype=torch.int32, device=counts.device)
+    with torch.cuda.device(counts.device):
+        _native._check(_native._call(_lib.pn2x_sa_class_lists, "sa_class_lists_kernel", None, B, S, int(n), pc, lst.data_ptr(),
+                                     sizes.data_ptr(), _native._stream(counts)), "sa_class_lists")
+    return lst, sizes
+
+
+def sa_mlp_max_classes(idx: torch.Tensor, classes, w2, b2, w3, b3, *, a1f=None, xyz=None, cxyz=None, wx=None, b1=None, cadd=None,
+                       out=None, point_major=False) -> torch.Tensor:
+    """sa_mlp_max over ball-query lists without their padding (include/pn2_ext.h: pn2x_sa_mlp_max_classes): idx (B,S,32) whose
+    slots past a centroid's hit count repeat slot 0, classes = sa_class_lists(counts, N).  Bit-identical to sa_mlp_max."""
+    if not (isinstance(classes, (tuple, list)) and len(classes) == 2):
+        raise TypeError("sa_mlp_max_classes: classes must be the (list, sizes) pair of sa_class_lists")
+    return _sa_mlp_max(idx, w2, b2, w3, b3, classes, a1f, xyz, cxyz, wx, b1, cadd, out, point_major)
+
+
+def _sa_mlp_max(idx, w2, b2, w3, b3, classes, a1f, xyz, cxyz, wx, b1, cadd, out, point_major):
     B, S, K = idx.shape
     C1, C2, C3 = w2.shape[1], w2.shape[0], w3.shape[0]
     f32 = torch.float32
@@ -125,6 +179,17 @@ def sa_mlp_max(idx: torch.Tensor, w2, b2, w3, b3, *, a1f=None, xyz=None, cxyz=No
     else:
         po, ld = _rows(out, "out", C3)
         ob, os_, oc = out.stride(0), ld, 1
+    if classes is not None:
+        lst, sizes = classes
+        pl = _native._ptr(lst, "classes list", torch.int32, B * S * 4)
+        ps = _native._ptr(sizes, "classes sizes", torch.int32, 3)
+        if lst.device != idx.device or sizes.device != idx.device:
+            raise ValueError("sa_mlp_max_classes: classes on another device than idx")
+        with torch.cuda.device(idx.device):
+            _native._check(_native._call(_lib.pn2x_sa_mlp_max_classes, "sa_mlp_max_classes_kernel", None, B, N, S, K, C1, C2, C3, pa, lda,
+                                         px, pcx, pwx, pb1, pc, ldc, pi, pl, ps, pw2, pb2, pw3, pb3, po, ob, os_, oc,
+                                         _native._stream(idx)), "sa_mlp_max_classes")
+        return out
     with torch.cuda.device(idx.device):
         _native._check(_native._call(_lib.pn2x_sa_mlp_max, "sa_mlp_max_kernel", None, B, N, S, K, C1, C2, C3, pa, lda, px, pcx,
                                      pwx, pb1, pc, ldc, pi, pw2, pb2, pw3, pb3, po, ob, os_, oc, _native._stream(idx)),
@@ -518,12 +583,16 @@ _lib.pn2x_furthest_point_sampling_prefix.restype = _ci
 
 _lib.pn2x_ball_query_picks.argtypes = [_ci, _ci, _ci, ctypes.c_float, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _vp]
 _lib.pn2x_ball_query_picks.restype = _ci
+_lib.pn2x_ball_query_picks_counts.argtypes = [_ci, _ci, _ci, ctypes.c_float, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _vp, _vp]
+_lib.pn2x_ball_query_picks_counts.restype = _ci
 
 
-def ball_query_picks(radius: float, nsample: int, xyz: torch.Tensor, picks: torch.Tensor, xyz_copy: torch.Tensor = None):
+def ball_query_picks(radius: float, nsample: int, xyz: torch.Tensor, picks: torch.Tensor, xyz_copy: torch.Tensor = None,
+                     counts: bool = False):
     """Ball query around the centroids xyz[picks] (picks (B,S) int32 from FPS) -> (idx (B,S,nsample) int32,
     new_xyz (B,S,3) = the centroids' coordinates): pointnet2_utils.ball_query + the gather before it, one launch.
-    xyz_copy: a (B,S,3) column block of a consumer's row buffer that receives a second copy of new_xyz."""
+    xyz_copy: a (B,S,3) column block of a consumer's row buffer that receives a second copy of new_xyz.
+    counts=True: a third value, (B,S) int32 = min(hits, nsample) per centroid, 1 where nothing was hit (same launch)."""
     B, N, _ = xyz.shape
     S = picks.shape[1]
     px = _native._ptr(xyz, "xyz", torch.float32, B * N * 3)
@@ -532,6 +601,11 @@ def ball_query_picks(radius: float, nsample: int, xyz: torch.Tensor, picks: torc
     new_xyz = torch.empty((B, S, 3), dtype=torch.float32, device=xyz.device)
     pc, ldc = (None, 0) if xyz_copy is None else _xyz_cols(xyz_copy, "xyz_copy", B, S)
     with torch.cuda.device(xyz.device):
+        if counts:
+            cnt = torch.empty((B, S), dtype=torch.int32, device=xyz.device)
+            _native._check(_lib.pn2x_ball_query_picks_counts(B, N, S, float(radius), nsample, px, pp, new_xyz.data_ptr(), idx.data_ptr(),
+                                                              pc, ldc, cnt.data_ptr(), _native._stream(xyz)), "ball_query_picks")
+            return idx, new_xyz, cnt
         _native._check(_lib.pn2x_ball_query_picks(B, N, S, float(radius), nsample, px, pp, new_xyz.data_ptr(), idx.data_ptr(),
                                                    pc, ldc, _native._stream(xyz)), "ball_query_picks")
     return idx, new_xyz
@@ -541,16 +615,19 @@ FPS_KNN_COLAUNCH = True  # (module attributes: tests compare the co-launches wit
 BALL_TIE_COLAUNCH = True
 _lib.pn2x_ball_query_picks_ties.argtypes = [_ci, _ci, _ci, ctypes.c_float, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _vp]
 _lib.pn2x_ball_query_picks_ties.restype = _ci
+_lib.pn2x_ball_query_picks_ties_counts.argtypes = [_ci, _ci, _ci, ctypes.c_float, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _vp]
+_lib.pn2x_ball_query_picks_ties_counts.restype = _ci
 _lib.pn2x_ball_query_picks_ties_supported.argtypes = [_ci] * 4
 _lib.pn2x_ball_query_picks_ties_supported.restype = _ci
 
 
-def fps_two_level(xyz: torch.Tensor, m1: int, m2: int, query=None, knn=None):
+def fps_two_level(xyz: torch.Tensor, m1: int, m2: int, query=None, knn=None, query_counts: bool = False):
     """The reference's two chained samplings  i1 = FPS(xyz, m1); l1 = xyz[i1]; i2 = FPS(l1, m2)  (backbones.py:98-104)
     -> (i1 (B,m1), l1 (B,m1,3), i2 (B,m2)) int32/float32, bit-identical to running both.  The second pass is
     skipped per cloud when level 1 had no tied arg-max among its first m2 picks (include/pn2_ext.h).
     query=(radius, nsample): level 1's ball query is done by the launch that produces l1 (ball_query_picks) and its
-    index tensor (B,m1,nsample) is returned as a fourth value.
+    index tensor (B,m1,nsample) is returned as a fourth value; with query_counts=True its hit counts (B,m1) int32 (min(hits,
+    nsample), 1 where nothing was hit; written by the same launch) follow as a fifth.
     knn=(points (B,nq,3), k, k2): also knn_indices(k, points, xyz, k2) -- appended to the result as one more value, the pair
     (idx (B,nq,k), idx2 (B,nq,k2) | None) -- in the launch of the first sampling level when the kernels cover the sizes
     (include/pn2_ext.h: pn2x_fps_radii_knn), as its own launch otherwise."""
@@ -567,6 +644,8 @@ def fps_two_level(xyz: torch.Tensor, m1: int, m2: int, query=None, knn=None):
         i1 = ops.furthest_point_sample(xyz, m1)
         l1 = gather_rows(xyz, i1)
         i2 = ops.furthest_point_sample(l1, m2)
+        if query is not None and query_counts:
+            raise ValueError("fps_two_level: query_counts needs m2 <= 1024 and N <= 16384")
         res = (i1, l1, i2) if query is None else (i1, l1, i2, ops.ball_query(query[0], query[1], xyz, l1))
         return res if knn is None else res + (knn_alone(),)
     px = _native._ptr(xyz, "xyz", torch.float32, B * N * 3)
@@ -575,6 +654,9 @@ def fps_two_level(xyz: torch.Tensor, m1: int, m2: int, query=None, knn=None):
     radii = torch.empty((B, m1), dtype=torch.float32, device=xyz.device)
     flags = torch.empty((B, nf), dtype=torch.int32, device=xyz.device)
     i2 = torch.empty((B, m2), dtype=torch.int32, device=xyz.device)
+    if query_counts and query is None:
+        raise ValueError("fps_two_level: query_counts without query")
+    cnt1 = torch.empty((B, m1), dtype=torch.int32, device=xyz.device) if query_counts else None
     with torch.cuda.device(xyz.device):
         st = _native._stream(xyz)
         lists = None
@@ -594,18 +676,27 @@ def fps_two_level(xyz: torch.Tensor, m1: int, m2: int, query=None, knn=None):
             # level 1's ball query and the tie check of the sampling run both start from the picks: one launch
             idx1 = torch.empty((B, m1, query[1]), dtype=torch.int32, device=xyz.device)
             l1 = torch.empty((B, m1, 3), dtype=torch.float32, device=xyz.device)
-            _native._check(_native._call(_lib.pn2x_ball_query_picks_ties, "ball_tie_kernel", None, B, N, m1, float(query[0]), query[1], px,
-                                         i1.data_ptr(), l1.data_ptr(), idx1.data_ptr(), None, 0, m2, radii.data_ptr(), flags.data_ptr(), st),
-                           "fps_two_level/query+ties")
+            if query_counts:
+                _native._check(_native._call(_lib.pn2x_ball_query_picks_ties_counts, "ball_tie_kernel", None, B, N, m1, float(query[0]), query[1],
+                                             px, i1.data_ptr(), l1.data_ptr(), idx1.data_ptr(), None, 0, m2, radii.data_ptr(),
+                                             flags.data_ptr(), cnt1.data_ptr(), st), "fps_two_level/query+ties")
+            else:
+                _native._check(_native._call(_lib.pn2x_ball_query_picks_ties, "ball_tie_kernel", None, B, N, m1, float(query[0]), query[1], px,
+                                             i1.data_ptr(), l1.data_ptr(), idx1.data_ptr(), None, 0, m2, radii.data_ptr(), flags.data_ptr(), st),
+                               "fps_two_level/query+ties")
         else:
             if query is None:
                 l1 = gather_rows(xyz, i1)
+            elif query_counts:
+                idx1, l1, cnt1 = ball_query_picks(query[0], query[1], xyz, i1, counts=True)
             else:
                 idx1, l1 = ball_query_picks(query[0], query[1], xyz, i1)
             _native._check(_lib.pn2x_fps_prefix_ties(B, N, m1, m2, px, i1.data_ptr(), radii.data_ptr(), flags.data_ptr(), st), "fps_two_level/ties")
         _native._check(_native._call(_lib.pn2x_furthest_point_sampling_prefix, "fps_prefix_kernel", None, B, m1, m2, l1.data_ptr(),
                                      flags.data_ptr(), nf, i2.data_ptr(), st), "fps_two_level/2")
     res = (i1, l1, i2) if query is None else (i1, l1, i2, idx1)
+    if query_counts:
+        res = res + (cnt1,)
     if knn is None:
         return res
     return res + (lists if lists is not None else knn_alone(),)

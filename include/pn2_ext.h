@@ -82,6 +82,31 @@ int pn2x_sa_mlp_max(int b, int n, int s, int k, int c1, int c2, int c3, const fl
 int pn2x_sa_mlp_max_supported(int k, int c1, int c2, int c3);
 
 /*
+ * pn2x_sa_mlp_max on ball-query lists without their padding ("class walk", csrc/sa_fused.hip).  idx (b, s, 32) are lists
+ * whose slots past counts[b, s] repeat slot 0 (pn2x_ball_query_picks_counts).  A centroid is served with its first 8, 16 or 32
+ * slots -- the smallest of the three that holds its count -- so layers 2 and 3 run over about a quarter of the positions when
+ * most lists are short.  The result is BIT-IDENTICAL to pn2x_sa_mlp_max on the same idx: each position's output is independent
+ * of the tile it sits in, and the max over a list equals the max over the list without its duplicates.
+ *
+ * pn2x_sa_class_lists: counts (b*s) -> list (b*s, 4) int32 records {b*s' id = cloud * s + centroid, cloud * n, cloud, centroid},
+ *   class "32" (count 17..32) first, then "16" (9..16), then "8" (<= 8), ascending id inside a class; sizes[0..2] = the three
+ *   class sizes.  n: points per cloud of the level the lists index.  One launch, deterministic, nothing reaches the host.
+ *   list 16-byte aligned; b*s and b*n below 2^24 (PN2_ERANGE).
+ * pn2x_sa_mlp_max_classes: the arguments of pn2x_sa_mlp_max plus list and sizes; one persistent launch whose workgroups read
+ *   the class sizes on the device and each walk an equal contiguous share of the tiles, class 32 first (capturable; a replay on
+ *   inputs with another class mix is correct).  Supported (pn2x_sa_mlp_max_classes_supported): k = 32 and widths (32,32,64) or
+ *   (64,64,128); cadd rows and out rows of consecutive clouds must continue each other (cloud stride = s * row stride for cadd;
+ *   any out_b).  Honours pn2x_sa_set_compute_units.
+ */
+int pn2x_sa_class_lists(int b, int s, int n, const int *counts, int *list, int *sizes, void *stream);
+int pn2x_sa_mlp_max_classes_supported(int k, int c1, int c2, int c3);
+int pn2x_sa_mlp_max_classes(int b, int n, int s, int k, int c1, int c2, int c3, const float *a1f, int a1f_ld,
+                            const float *xyz, const float *cxyz, const float *wx, const float *b1, const float *cadd,
+                            int cadd_ld, const int *idx, const int *cls_list, const int *cls_sizes,
+                            const float *w2, const float *b2, const float *w3, const float *b3, float *out,
+                            long out_b, int out_s, int out_c, void *stream);
+
+/*
  * In-place y[b,c,n] = act(y[b,c,n] + bias[c]) (relu != 0 -> ReLU): the epilogue of an eval-mode,
  * BatchNorm-folded 1x1 convolution (reference: Conv1d + BatchNorm1d + ReLU of the feature-propagation
  * stacks, pointnet_utils.py:460-462) whose GEMM half is a library GEMM on the (b, c, n) tensor.
@@ -176,6 +201,16 @@ int pn2x_knn_indices(int b, int n, int m, int k, int k2, const float *unknown, c
  */
 int pn2x_ball_query_picks(int b, int n, int m, float radius, int nsample, const float *xyz, const int *picks, float *new_xyz,
                           int *idx, float *new_xyz_copy, int copy_ld, void *stream);
+/*
+ * The same launches with one more output: counts (b, m) int32 (or NULL: exactly the calls above) = min(hits, nsample) of every
+ * centroid, 1 for a centroid without a hit (its list is all point 0, so its first slot alone gives the same pooled result).
+ * A list's slots past its count repeat slot 0 (ball_query_gpu.cu:35-39), which is what pn2x_sa_mlp_max_classes skips.
+ */
+int pn2x_ball_query_picks_counts(int b, int n, int m, float radius, int nsample, const float *xyz, const int *picks, float *new_xyz,
+                                 int *idx, float *new_xyz_copy, int copy_ld, int *counts, void *stream);
+int pn2x_ball_query_picks_ties_counts(int b, int n, int m, float radius, int nsample, const float *xyz, const int *picks, float *new_xyz,
+                                      int *idx, float *new_xyz_copy, int copy_ld, int m2, const float *radii, int *flags, int *counts,
+                                      void *stream);
 
 /*
  * pn2_ball_query through a cell grid (csrc/ball_query_grid.hip): identical output for every input -- the same hit test on

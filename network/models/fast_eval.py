@@ -50,6 +50,7 @@ class FastEval:
         self._consts = {}
         self._idents = {}
         self.row_chain = True  # large batches: fp1 -> conv1 -> q layer 1 over the kNN-listed rows only (ext.row_chain)
+        self.sa_classes = True  # large batches: sa1 / sa2 skip their ball-query padding (ext.sa_mlp_max_classes); False = fixed K
 
     def _palm_idx(self, device):
         key = ("palm", str(device))
@@ -291,8 +292,17 @@ class FastEval:
         # in the launch of sampling level 1, which keeps one compute unit per cloud busy and nothing else
         qK = [P["q"][("q1", i)]["K"] for i in range(2)]
         knn_req = (xyz1, max(qK), min(qK) if min(qK) < max(qK) else 0)
-        _, l1_xyz, i_l2, idx1, knn_lists = ext.fps_two_level(xyz2, S1, bh.sa2.npoint, query=(bh.sa1.radius_list[0], K1), knn=knn_req)
-        return dict(P=P, pts=pts, B=B, N=N, J=J, c_i=c_i, fp1_in=fp1_in, nonfinite=nonfinite, R=R, t=t, xyz2=xyz2, xyz1=xyz1,
+        # large batches: the ball queries also report their hit counts, and sa1 / sa2 run layers 2-3 over the hits only
+        classes = self.sa_classes and self._large_batch(B, N) and all(
+            ext.sa_mlp_max_classes_supported(int(m.nsample_list[0]), *(int(c.weight.shape[0]) for c in m.conv_blocks[0]))
+            for m in (bh.sa1, bh.sa2))
+        cnt1 = None
+        if classes:
+            _, l1_xyz, i_l2, idx1, cnt1, knn_lists = ext.fps_two_level(xyz2, S1, bh.sa2.npoint, query=(bh.sa1.radius_list[0], K1),
+                                                                       knn=knn_req, query_counts=True)
+        else:
+            _, l1_xyz, i_l2, idx1, knn_lists = ext.fps_two_level(xyz2, S1, bh.sa2.npoint, query=(bh.sa1.radius_list[0], K1), knn=knn_req)
+        return dict(cnt1=cnt1, P=P, pts=pts, B=B, N=N, J=J, c_i=c_i, fp1_in=fp1_in, nonfinite=nonfinite, R=R, t=t, xyz2=xyz2, xyz1=xyz1,
                     canon=canon, S1=S1, K1=K1, l1_xyz=l1_xyz, i_l2=i_l2, idx1=idx1, knn_lists=knn_lists)
 
     def _dense(self, G, flag_dict):
@@ -309,17 +319,29 @@ class FastEval:
         fp2_w = P["fp2"][0][0].shape[1]
         fp2_in = torch.empty((B, S1, fp2_w), **f32)  # [l1_feat | interp(l2 -> l1)]
         l1_feat = fp2_in[:, :, :c_l1]
-        ext.sa_mlp_max(idx1, *p["l2"], *p["l3"], xyz=xyz2, cxyz=l1_xyz, wx=p["wx"], b1=p["b1"], out=l1_feat)
+        cnt1 = G["cnt1"]
+        if cnt1 is not None:
+            ext.sa_mlp_max_classes(idx1, ext.sa_class_lists(cnt1, N), *p["l2"], *p["l3"], xyz=xyz2, cxyz=l1_xyz, wx=p["wx"], b1=p["b1"],
+                                   out=l1_feat)
+        else:
+            ext.sa_mlp_max(idx1, *p["l2"], *p["l3"], xyz=xyz2, cxyz=l1_xyz, wx=p["wx"], b1=p["b1"], out=l1_feat)
 
         # ---- sa2: 256 -> 128, r = 0.2, K = 32, MLP [64+3 -> 64 -> 64 -> 128] ---------------------------
         p = P["sa2"]
         S2, K2 = bh.sa2.npoint, bh.sa2.nsample_list[0]
         c_l2 = p["l3"][0].shape[0]
         sa3_in = torch.empty((B, S2, c_l2 + 4), **f32)  # [l2_feat | l2_xyz | pad]: sa3's group-all input, no torch.cat
-        idx2, l2_xyz = ext.ball_query_picks(bh.sa2.radius_list[0], K2, l1_xyz, i_l2, xyz_copy=sa3_in[:, :, c_l2:c_l2 + 3])
+        if cnt1 is not None:
+            idx2, l2_xyz, cnt2 = ext.ball_query_picks(bh.sa2.radius_list[0], K2, l1_xyz, i_l2, xyz_copy=sa3_in[:, :, c_l2:c_l2 + 3], counts=True)
+        else:
+            idx2, l2_xyz = ext.ball_query_picks(bh.sa2.radius_list[0], K2, l1_xyz, i_l2, xyz_copy=sa3_in[:, :, c_l2:c_l2 + 3])
         a1f = _lin(l1_feat.reshape(B * S1, c_l1), p["w1f"]).view(B, S1, -1)
         l2_feat = sa3_in[:, :, :c_l2]
-        ext.sa_mlp_max(idx2, *p["l2"], *p["l3"], a1f=a1f, xyz=l1_xyz, cxyz=l2_xyz, wx=p["wx"], b1=p["b1"], out=l2_feat)
+        if cnt1 is not None:
+            ext.sa_mlp_max_classes(idx2, ext.sa_class_lists(cnt2, S1), *p["l2"], *p["l3"], a1f=a1f, xyz=l1_xyz, cxyz=l2_xyz, wx=p["wx"],
+                                   b1=p["b1"], out=l2_feat)
+        else:
+            ext.sa_mlp_max(idx2, *p["l2"], *p["l3"], a1f=a1f, xyz=l1_xyz, cxyz=l2_xyz, wx=p["wx"], b1=p["b1"], out=l2_feat)
 
         large = self._large_batch(B, N)
         mc = P["mid_chain"]
