@@ -32,12 +32,19 @@ def _load(*parts):
         return yaml.safe_load(f)
 
 
+def peek_track(args):
+    """The `track` value get_config will arrive at, from the command line or else the main YAML alone: nothing is created,
+    composed or loaded (entry points check flag combinations with it before any work)."""
+    track = getattr(args, "track", None)
+    return track if track is not None else _load("all_config", args.config).get("track")
+
+
 def get_config(args, save=True):
     cfg = _load("all_config", args.config)
     cli = dict(vars(args))
     cli.pop("config")
     for key, item in cli.items():
-        if item is not None and key not in ("mode_name", "debug", "debug_save", "save", "num_workers", "synthetic_frames", "max_iters"):
+        if item is not None and key not in ("mode_name", "debug", "debug_save", "save", "num_workers", "synthetic_frames", "max_iters", "seq_batch"):
             overwrite_config(cfg, key, key.split("/"), item)
     if not isinstance(cfg.get("opt"), dict):
         cfg["opt"] = {}

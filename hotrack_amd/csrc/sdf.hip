@@ -210,12 +210,15 @@ __global__ void opt_init_kernel(float *work, float c1) {
     if (t == 14) reinterpret_cast<unsigned *>(work)[W_TICKET] = 0u;
 }
 
+// One workgroup's share of one iteration of one problem: particle i's evaluation, then -- in the workgroup that draws the
+// problem's last ticket -- the pose / search-size update.  Shared by the single-problem and the batched kernel, so the two
+// accumulate in the same order and agree in every bit.
 template <int FMT>
-__global__ void __launch_bounds__(256) obj_optimize_kernel(const OptArgs A) {
+__device__ __forceinline__ void obj_optimize_block(const OptArgs &A, const int i) {
     __shared__ float sm[4];
     __shared__ float red[9 * 4 + 4];
     __shared__ int is_last;
-    const int i = blockIdx.x, tid = threadIdx.x;
+    const int tid = threadIdx.x;
     float *__restrict__ work = A.work;
     float *__restrict__ energy = work + W_ENERGY;
 
@@ -354,6 +357,56 @@ __global__ void __launch_bounds__(256) obj_optimize_kernel(const OptArgs A) {
     if (success) work[W_PREV_SCALAR] = 0.0f;
     work[W_PREV_OK] = success ? 1.0f : 0.0f;
     reinterpret_cast<unsigned *>(work)[W_TICKET] = 0u;
+}
+
+template <int FMT>
+__global__ void __launch_bounds__(256) obj_optimize_kernel(const OptArgs A) {
+    obj_optimize_block<FMT>(A, blockIdx.x);
+}
+
+// ---- the same loop for S independent problems per launch (pn2s_obj_optimize_batch) ---------------------------------
+// Grid (p, s): workgroup (i, k) is particle i of problem k.  Problem k owns the work record at work + k * work_stride
+// (the layout above, padded to a multiple of 16 floats), its slice [cloud_off[k], cloud_off[k+1]) of the packed cloud,
+// vols[k] and poses[12k .. 12k+12).  Nothing is shared between problems but read-only inputs, and the last workgroup of
+// problem k is decided by problem k's own ticket: no workgroup ever waits for another, of its own problem or of any other.
+struct OptBatchArgs {
+    int p, work_stride;
+    const float *pcld, *pre;
+    const int *cloud_off;
+    const void *const *vols;
+    SdfVol V;  // .p is unused: every problem has its own volume of this format, size and stride
+    float c2, beta, one_minus_beta, carry0;
+    float *poses, *work;
+};
+
+constexpr int opt_work_stride(int p) { return (W_ENERGY + p + 15) / 16 * 16; }
+
+__global__ void opt_init_batch_kernel(float *work, int work_stride, float c1) {
+    float *w = work + (size_t)blockIdx.x * work_stride;
+    const int t = threadIdx.x;
+    if (t < 12) w[t] = c1;  // W_SEARCH, W_PREV
+    if (t == 12) w[W_PREV_OK] = 1.0f;
+    if (t == 13) w[W_PREV_SCALAR] = 1.0f;
+    if (t == 14) reinterpret_cast<unsigned *>(w)[W_TICKET] = 0u;
+}
+
+template <int FMT>
+__global__ void __launch_bounds__(256) obj_optimize_batch_kernel(const OptBatchArgs B) {
+    const int k = blockIdx.y;
+    const int o0 = B.cloud_off[k], o1 = B.cloud_off[k + 1];
+    const void *vol = B.vols[k];  // the table's entry, not the volume: loaded for every problem, dereferenced for active ones only
+    if (o0 < 0 || o1 <= o0) return;  // inactive problem: its pose is left alone and its volume is never read
+    OptArgs A;
+    A.p = B.p;
+    A.n = o1 - o0;
+    A.pcld = B.pcld + 3 * (size_t)o0;
+    A.pre = B.pre;
+    A.V = B.V;
+    A.V.p = vol;
+    A.c2 = B.c2; A.beta = B.beta; A.one_minus_beta = B.one_minus_beta; A.carry0 = B.carry0;
+    A.pose = B.poses + 12 * (size_t)k;
+    A.work = B.work + (size_t)k * B.work_stride;
+    obj_optimize_block<FMT>(A, blockIdx.x);
 }
 
 // ---- gf_optimize_hand_pose.query_sdf (+ get_penetration_loss) (optimization_hand.py:252-268) -----------------------
@@ -508,6 +561,35 @@ extern "C" int pn2s_obj_optimize(int p, int n, int iterations, const float *pcld
     hipLaunchKernelGGL(opt_init_kernel, dim3(1), dim3(64), 0, st, work, c1);
     for (int it = 0; it < iterations; ++it) {
         SDF_FMT_DISPATCH(vol_fmt, hipLaunchKernelGGL(obj_optimize_kernel<FMT>, dim3(p), dim3(256), 0, st, A))
+    }
+    return check_launch();
+}
+
+extern "C" long pn2s_obj_optimize_batch_work_floats(int s, int p) {
+    return (s < 0 || p < 0) ? (long)PN2_EINVAL : (long)s * opt_work_stride(p);
+}
+
+extern "C" int pn2s_obj_optimize_batch(int s, int p, int iterations, const float *pcld, const int *cloud_off,
+                                       const float *pre_sampled, const void *const *vols, int vol_fmt, int res, float bbox_min,
+                                       float stride, float clamp_lo, float clamp_hi, float c1, float c2, float beta,
+                                       float *poses, float *work, long work_floats, void *stream) {
+    if (s < 0 || p < 1 || iterations < 0 || !vol_args_ok(res, stride) || vol_fmt < 0 || vol_fmt > 3) return PN2_EINVAL;
+    if (s == 0) return PN2_OK;
+    if (!pcld || !cloud_off || !pre_sampled || !vols || !poses || !work) return PN2_ENULL;
+    if (s > PN2S_OPT_BATCH_MAX || p > (1 << 20) || (long)s * p > (1L << 22)) return PN2_ERANGE;
+    if (work_floats < pn2s_obj_optimize_batch_work_floats(s, p)) return PN2_ESCRATCH;
+    OptBatchArgs B;
+    B.p = p; B.work_stride = opt_work_stride(p);
+    B.pcld = pcld; B.pre = pre_sampled; B.cloud_off = cloud_off; B.vols = vols;
+    B.V = SdfVol{nullptr, res, bbox_min, stride, clamp_lo, clamp_hi};
+    B.c2 = c2; B.beta = beta;
+    B.one_minus_beta = (float)(1.0 - (double)beta);  // as pn2s_obj_optimize
+    B.carry0 = (float)((1.0 - (double)beta) * (double)c1);
+    B.poses = poses; B.work = work;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(opt_init_batch_kernel, dim3(s), dim3(64), 0, st, work, B.work_stride, c1);
+    for (int it = 0; it < iterations; ++it) {
+        SDF_FMT_DISPATCH(vol_fmt, hipLaunchKernelGGL(obj_optimize_batch_kernel<FMT>, dim3(p, s), dim3(256), 0, st, B))
     }
     return check_launch();
 }

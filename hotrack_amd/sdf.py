@@ -30,6 +30,11 @@ _lib.pn2s_build_corner_volume.argtypes = [_vp, _ci, _ci, _vp, _vp]
 _lib.pn2s_build_corner_volume.restype = _ci
 _lib.pn2s_corner_volume_elems.argtypes = [_ci]
 _lib.pn2s_corner_volume_elems.restype = ctypes.c_long
+_lib.pn2s_obj_optimize_batch.argtypes = [_ci, _ci, _ci, _vp, _vp, _vp, _vp, _ci, _ci, _cf, _cf, _cf, _cf, _cf, _cf, _cf, _vp, _vp,
+                                         ctypes.c_long, _vp]
+_lib.pn2s_obj_optimize_batch.restype = _ci
+_lib.pn2s_obj_optimize_batch_work_floats.argtypes = [_ci, _ci]
+_lib.pn2s_obj_optimize_batch_work_floats.restype = ctypes.c_long
 
 BBOX_MIN = -0.2  # optimization_obj.py:186
 CLAMP = (-0.05, 0.05)  # optimization_obj.py:227
@@ -134,6 +139,131 @@ def obj_optimize(pcld: torch.Tensor, rotation: torch.Tensor, translation: torch.
                                     beta, pose.data_ptr(), work.data_ptr(), _native._stream(pcld))
     _native._check(rc, "sdf.obj_optimize")
     return pose[:9].view(1, 3, 3), pose[9:].view(1, 3, 1)
+
+
+def _volume_table(volumes, active, device, cache):
+    """-> (device int64 tensor of the S volume pointers, vol_fmt, res).  Every volume given must share one layout, dtype and
+    resolution; None (a NULL entry) is allowed where the problem is inactive.  With a `cache` dict the table of a list of
+    the same volume objects is uploaded once."""
+    key = ("vols", str(device), tuple(map(id, volumes)))
+    hit = None if cache is None else cache.get(key)
+    if hit is None:
+        ptrs, first = [], None
+        for k, v in enumerate(volumes):
+            if v is None:
+                ptrs.append(0)
+                continue
+            pv, fmt, res = _volume(v)
+            if first is None:
+                first = (k, fmt, res)
+            elif (fmt, res) != first[1:]:
+                what = lambda f, r: "%s %s res %d" % ("corner" if f >= 2 else "linear", "float16" if f & 1 else "float32", r)
+                raise ValueError(f"volumes[{first[0]}] ({what(*first[1:])}) and volumes[{k}] ({what(fmt, res)}) differ: "
+                                 "a batch shares one layout, dtype and resolution")
+            ptrs.append(pv)
+        if first is None:
+            raise ValueError("volumes holds no volume")
+        # (the volumes are kept with the table: the key's ids stay theirs)
+        hit = (torch.tensor(ptrs, dtype=torch.int64, device=device), first[1], first[2], list(volumes))
+        if cache is not None:
+            cache[key] = hit
+    for k in active:
+        if volumes[k] is None:
+            raise ValueError(f"volumes[{k}] is None but problem {k} has a cloud (or the clouds are packed: every problem needs one)")
+    return hit[:3]
+
+
+def obj_optimize_batch_work_floats(S: int, P: int) -> int:
+    """Floats of scratch obj_optimize_batch needs for S problems of P particles (pn2s_obj_optimize_batch_work_floats)."""
+    need = _lib.pn2s_obj_optimize_batch_work_floats(S, P)
+    if need < 0:
+        raise ValueError(f"S and P must not be negative, got {S} and {P}")
+    return need
+
+
+def obj_optimize_batch(pclds, rotations, translations, pre_sampled_particle: torch.Tensor, volumes,
+                       voxel_scale: float, iterations: int = 10, scaling_coefficient1: float = 0.02,
+                       scaling_coefficient2: float = 2.0, beta: float = 0.9, bbox_min: float = BBOX_MIN, clamp=CLAMP, work=None,
+                       cloud_offsets=None, cache=None):
+    """obj_optimize for S independent problems with ONE set of launches (include/pn2_sdf.h: pn2s_obj_optimize_batch); every
+    problem's result is bit-for-bit what obj_optimize returns for it alone.
+    pclds: a list of S clouds (n_k,3)|(1,n_k,3) -- an empty one, or None, marks an INACTIVE problem, whose pose comes back
+      unchanged -- or one packed (sum n_k,3) tensor with `cloud_offsets`, an int32 GPU tensor of S+1 offsets in points that
+      lie inside it (cloud_offsets[k+1] <= cloud_offsets[k]: inactive).  The offsets stay on the device, so on this route the
+      caller answers for them and EVERY problem needs a volume (None is refused: which slices are empty is not known here);
+    rotations (S,3,3) and translations (S,3)|(S,3,1), or two lists of S tensors (3,3)|(1,3,3) and (3,)|(1,3,1);
+    pre_sampled_particle (P,6), row 0 == 0, shared;
+    volumes: S CornerVolumes or S linear volume tensors of one layout, dtype and resolution (all read with `voxel_scale`);
+      None is allowed for an inactive problem of the list form;
+    work: >= pn2s_obj_optimize_batch_work_floats(S,P) floats, or None;
+    cache: a dict the caller keeps between calls: the offsets of a repeated list of cloud sizes and the pointer table of a
+      repeated list of volumes are then uploaded once (a steady-state call uploads nothing; required for graph capture).
+    Returns (rotations (S,3,3), translations (S,3,1)) as new tensors."""
+    if isinstance(rotations, (list, tuple)):  # S poses held one by one (a tracker's state): assembled by ONE concatenation
+        S = len(rotations)
+        if S == 0 or len(translations) != S:
+            raise ValueError(f"rotations and translations must be two lists of S >= 1 tensors, got {S} and {len(translations)}")
+        pose = torch.cat([x.reshape(1, n).to(_f32) for R, t in zip(rotations, translations) for x, n in ((R, 9), (t, 3))], dim=1).view(S, 12)
+    else:
+        if rotations.dim() != 3 or tuple(rotations.shape[1:]) != (3, 3):
+            raise ValueError(f"rotations must be (S,3,3), got {tuple(rotations.shape)}")
+        S = rotations.shape[0]
+        if translations.numel() != 3 * S:
+            raise ValueError(f"translations must be (S,3) or (S,3,1) with S = {S}, got {tuple(translations.shape)}")
+        pose = torch.cat([rotations.reshape(S, 9).to(_f32), translations.reshape(S, 3).to(_f32)], dim=1).contiguous()
+    _native._ptr(pose, "rotations/translations", _f32, 12 * S)
+    device = pose.device
+    out = pose[:, :9].view(S, 3, 3), pose[:, 9:].reshape(S, 3, 1)
+    if len(volumes) != S:
+        raise ValueError(f"volumes must hold S = {S} entries, got {len(volumes)}")
+    pre = pre_sampled_particle.contiguous()
+    if pre.dim() != 2 or pre.shape[1] != 6:
+        raise ValueError("pre_sampled_particle must be (P,6)")
+    P = pre.shape[0]
+    p_pre = _native._ptr(pre, "pre_sampled_particle", _f32, P * 6)
+    if cloud_offsets is None:
+        if len(pclds) != S:
+            raise ValueError(f"pclds must hold S = {S} clouds, got {len(pclds)}")
+        clouds = [None if c is None or c.numel() == 0 else c.reshape(-1, 3) for c in pclds]
+        sizes = tuple(0 if c is None else c.shape[0] for c in clouds)
+        active = [k for k, n in enumerate(sizes) if n]
+        if not active:
+            return out
+        packed = clouds[active[0]] if len(active) == 1 else torch.cat([clouds[k] for k in active])
+        packed = packed.contiguous()
+        key = ("off", str(device), sizes)
+        off = None if cache is None else cache.get(key)
+        if off is None:
+            acc = [0]
+            for n in sizes:
+                acc.append(acc[-1] + n)
+            off = torch.tensor(acc, dtype=torch.int32, device=device)
+            if cache is not None:
+                cache[key] = off
+        total = sum(sizes)
+    else:
+        if not isinstance(pclds, torch.Tensor) or pclds.dim() != 2 or pclds.shape[1] != 3:
+            raise ValueError("with cloud_offsets, pclds must be one packed (N,3) tensor")
+        packed, off, total = pclds.contiguous(), cloud_offsets, pclds.shape[0]
+        active = range(S)  # (which slices are empty is known on the device only: no problem may go without a volume)
+        if total == 0:
+            return out
+    p_pcld = _native._ptr(packed, "pclds", _f32, total * 3)
+    p_off = _native._ptr(off, "cloud_offsets", torch.int32, S + 1)
+    table, fmt, res = _volume_table(volumes, active, device, cache)
+    if packed.device != device or pre.device != device:
+        raise RuntimeError(f"the clouds, poses and particles are on different devices ({packed.device}, {device}, {pre.device})")
+    need = obj_optimize_batch_work_floats(S, P)
+    if work is None:
+        work = torch.empty((need,), dtype=_f32, device=device)
+    elif work.numel() < need or work.dtype != _f32 or not work.is_cuda or not work.is_contiguous():
+        raise ValueError(f"work must be a contiguous float32 GPU tensor of >= {need} elements")
+    with torch.cuda.device(device):
+        rc = _lib.pn2s_obj_optimize_batch(S, P, iterations, p_pcld, p_off, p_pre, table.data_ptr(), fmt, res, bbox_min, voxel_scale,
+                                          clamp[0], clamp[1], scaling_coefficient1, scaling_coefficient2, beta, pose.data_ptr(),
+                                          work.data_ptr(), work.numel(), _native._stream(pose))
+    _native._check(rc, "sdf.obj_optimize_batch")
+    return out
 
 
 def query_sdf(hand: torch.Tensor, obj_r: torch.Tensor, obj_t: torch.Tensor, sdf_volume: torch.Tensor, voxel_scale: float,

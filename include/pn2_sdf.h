@@ -79,6 +79,35 @@ int pn2s_obj_optimize(int p, int n, int iterations, const float *pcld, const flo
 int pn2s_obj_optimize_work_floats(int p);
 
 /*
+ * pn2s_obj_optimize for s independent problems at once (one frame step of s object sequences tracked in lockstep): one
+ * init launch and `iterations` launches of a (p, s) grid for all of them together, no host synchronisation, capturable in a
+ * HIP graph.  Workgroup (i, k) evaluates particle i of problem k; the last workgroup of problem k to finish -- by problem
+ * k's own ticket -- does problem k's update.  No workgroup waits for another, and no problem reads what another writes.
+ * Every problem's result is bit-for-bit what pn2s_obj_optimize returns for it alone (the same device code, the same
+ * accumulation order).
+ *   pcld        packed clouds, (sum_k n_k, 3);
+ *   cloud_off   DEVICE array of s+1 ints, in points: problem k owns rows [cloud_off[k], cloud_off[k+1]).  The offsets must lie
+ *               inside pcld (the caller's duty: they are read on the device only).  A problem with an empty slice
+ *               (cloud_off[k+1] <= cloud_off[k]) is INACTIVE: its pose is left untouched; the entry vols[k] is loaded but
+ *               the volume is never read, so the entry may be NULL -- how a sequence that has ended sits out the remaining
+ *               frames of its group;
+ *   pre_sampled (p,6), row 0 == 0, shared by all problems;
+ *   vols        DEVICE array of s volume pointers, all of one vol_fmt, res, bbox_min and stride;
+ *   poses       in/out (s,12): rotation (3,3) row-major, then translation (3), per problem;
+ *   work        scratch of at least pn2s_obj_optimize_batch_work_floats(s, p) floats = s records of the single entry's
+ *               layout, each padded to a multiple of 16 floats; contents undefined on return except the tickets, which are
+ *               zero again.
+ * s == 0 is a no-op that reads nothing.  Limits (PN2_ERANGE beyond): s <= PN2S_OPT_BATCH_MAX (the grid's second
+ * dimension), p <= 2^20, s * p <= 2^22 (workgroups per launch).  PN2_ESCRATCH when work_floats is too small.
+ */
+#define PN2S_OPT_BATCH_MAX 65535
+int pn2s_obj_optimize_batch(int s, int p, int iterations, const float *pcld, const int *cloud_off, const float *pre_sampled,
+                            const void *const *vols, int vol_fmt, int res, float bbox_min, float stride, float clamp_lo,
+                            float clamp_hi, float c1, float c2, float beta, float *poses, float *work, long work_floats,
+                            void *stream);
+long pn2s_obj_optimize_batch_work_floats(int s, int p);
+
+/*
  * query_sdf(hand) (+ get_penetration_loss)  (optimization_hand.py:252-268): nearest-voxel read.
  *   hand (b,n,3); obj_r (3,3); obj_t (3):  q = (hand - obj_t) @ obj_r;
  *   index per axis = clamp(q // voxel_scale, -(res/2), res/2) + res/2   (`//` = torch's floor division);

@@ -37,6 +37,7 @@ class gf_optimize_obj:
         self.pre_sampled_particle = torch.tensor(pre, dtype=torch.float32, device=self.device)
         self.sdf_volume = None
         self._work = None
+        self._batch_work, self._batch_cache = None, {}  # optimize_batch: scratch; uploaded offsets / volume pointer tables
 
     def load_volume(self, sdf_volume: torch.Tensor, voxel_scale: float | None = None):
         """Install a (V,V,V) fp16/fp32 SDF volume (what load_obj produces at :139-149)."""
@@ -73,3 +74,28 @@ class gf_optimize_obj:
                                  iterations=self.iteration, scaling_coefficient1=self.scaling_coefficient1,
                                  scaling_coefficient2=float(self.scaling_coefficient2), beta=self.beta, work=self._work)
         return {"rotation": R, "translation": t.reshape(1, 3, 1)}
+
+    def optimize_batch(self, pclds, init_obj_poses, corner_volumes, voxel_scale=None):
+        """`optimize` for S independent problems (one frame step of S sequences) with one set of launches: the same 11
+        kernels over a (particle, problem) grid (hotrack_amd.sdf.obj_optimize_batch).  pclds: S clouds, an empty one or
+        None for a problem that sits this step out (its pose is returned unchanged); init_obj_poses: S pose dicts;
+        corner_volumes: S hotrack_amd.sdf.CornerVolume (None where the problem sits out), all of one resolution and dtype and
+        read with `voxel_scale` (default: this instance's).  Shares the instance's pre_sampled_particle and constants.
+        Returns S dicts {'rotation' (1,3,3), 'translation' (1,3,1)}, each bit-equal to what `optimize` returns for it."""
+        S = len(init_obj_poses)
+        if S == 0:
+            return []
+        poses = [{k: p[k].float().to(self.device) for k in ("rotation", "translation")} for p in init_obj_poses]
+        pclds = [None if c is None else c.float().to(self.device) for c in pclds]
+        if len(self._batch_cache) > 64:  # (a long evaluation with ever new groups of volumes: start over)
+            self._batch_cache.clear()
+        need = _sdf.obj_optimize_batch_work_floats(S, self.pre_sampled_particle.shape[0])
+        if self._batch_work is None or self._batch_work.numel() < need:
+            self._batch_work = torch.empty(need, dtype=torch.float32, device=self.device)
+        R, t = _sdf.obj_optimize_batch(pclds, [p["rotation"] for p in poses], [p["translation"] for p in poses],
+                                       self.pre_sampled_particle, list(corner_volumes),
+                                       self.voxel_scale if voxel_scale is None else float(voxel_scale),
+                                       iterations=self.iteration, scaling_coefficient1=self.scaling_coefficient1,
+                                       scaling_coefficient2=float(self.scaling_coefficient2), beta=self.beta,
+                                       work=self._batch_work, cache=self._batch_cache)
+        return [{"rotation": R[k:k + 1], "translation": t[k:k + 1]} for k in range(S)]

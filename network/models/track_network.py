@@ -305,6 +305,80 @@ class ObjTrackModel_Optimization(nn.Module):
             rets.append(ret)
         return rets
 
+    def _sequence_volume(self, frame0, built):
+        """The volume `forward` would load for a sequence whose first frame is `frame0`, in its lookup layout ->
+        (hotrack_amd.sdf.CornerVolume, voxel_scale).  `built` maps id(volume tensor) to what was built from it, so sequences
+        that hand over the same tensor (or the same mesh: mesh_sdf caches its volume) share one copy.  Leaves the optimiser
+        in the state `forward` leaves it in (volume_size, voxel_scale, sdf_volume), which the next mesh build reads."""
+        opt = self.optimizer
+        if "sdf_volume" in frame0:
+            src, scale = frame0["sdf_volume"], frame0.get("voxel_scale")
+        else:
+            from . import mesh_sdf
+            scale = float(frame0.get("voxel_scale", opt.voxel_scale))
+            src = mesh_sdf.frame_volume(frame0, opt.volume_size, scale, self.device)
+            if src is None:
+                if opt.sdf_volume is None:
+                    raise RuntimeError("no SDF volume: decoding it from a DeepSDF latent needs the checkpoints (out of scope); "
+                                       "put 'sdf_volume' / 'voxel_scale', or the object's mesh as 'obj_mesh' ({'vertices', 'faces'}) or "
+                                       "'obj_mesh_path', into the sequence's first frame")
+                return opt._corners, opt.voxel_scale  # (as forward: the volume loaded last stays)
+        hit = built.get(id(src))
+        if hit is None:
+            opt.load_volume(src, scale)
+            built[id(src)] = (src, opt.sdf_volume, opt._corners)
+        else:
+            opt.volume_size, opt.sdf_volume, opt._corners = hit[0].shape[0], hit[1], hit[2]
+            if scale is not None:
+                opt.voxel_scale = float(scale)
+        return opt._corners, opt.voxel_scale
+
+    def forward_batch(self, inputs, flag_dict):
+        """`forward` for S sequences in lockstep: frame index t of every sequence that still has one is ONE
+        `gf_optimize_obj.optimize_batch` call (the same 11 launches over a (particle, sequence) grid), so the device works on S
+        sequences' particles while each one's serial tail runs, and the per-frame host work is paid once per step instead of
+        once per sequence.  inputs: a list of S sequences, each what `forward` takes; sequences shorter than the longest sit
+        out once they have ended.  All volumes must share one resolution, dtype and voxel_scale (one launch reads them all).
+        Returns a list of S `ret_dict_lst`, bit-equal to S `forward` calls."""
+        flag_dict["track_flag"] = True
+        assert flag_dict["test_flag"]
+        built, vols, scales = {}, [], []
+        for seq in inputs:
+            v, s = self._sequence_volume(seq[0], built) if len(seq) else (None, None)
+            vols.append(v)
+            scales.append(s)
+        known = [(k, s) for k, s in enumerate(scales) if s is not None]
+        for k, s in known:
+            if s != known[0][1]:
+                raise ValueError(f"sequences {known[0][0]} and {k} differ in voxel_scale ({known[0][1]}, {s}): a group tracked in "
+                                 "lockstep shares one; track them in separate groups")
+        S = len(inputs)
+        last = [None] * S
+        rets = [[] for _ in range(S)]
+        for t in range(max((len(seq) for seq in inputs), default=0)):
+            live = [k for k in range(S) if t < len(inputs[k])]
+            for k in live:
+                data = inputs[k][t]
+                if last[k] is not None:
+                    data["jittered_obj_pose"] = last[k]
+                else:
+                    jp = data["jittered_obj_pose"]
+                    jp["translation"] = jp["translation"].float().reshape(1, 3, 1).to(self.device)
+                    jp["rotation"] = jp["rotation"].float().reshape(1, 3, 3).to(self.device)
+                    jp["prev_translation"], jp["prev_rotation"] = jp["translation"], jp["rotation"]
+                    last[k] = {"translation": jp["translation"], "rotation": jp["rotation"]}
+            # (a sequence that has ended keeps its slot, with no cloud and no volume: the launch skips it; an EMPTY sequence
+            # has no pose either and borrows a live one's, which comes back unchanged and is dropped)
+            out = self.optimizer.optimize_batch([inputs[k][t]["obj_points"] if t < len(inputs[k]) else None for k in range(S)],
+                                                [last[k] if last[k] is not None else last[live[0]] for k in range(S)],
+                                                [vols[k] if t < len(inputs[k]) else None for k in range(S)], known[0][1])
+            for k in live:
+                ret = out[k]
+                last[k]["prev_translation"], last[k]["prev_rotation"] = last[k]["translation"], last[k]["rotation"]
+                last[k]["translation"], last[k]["rotation"] = ret["translation"], ret["rotation"]
+                rets[k].append(ret)
+        return rets
+
     def compute_loss(self, input, ret_dict_lst, flag_dict):
         """The reference's evaluation of a tracked sequence (track_network.py:385-434) next to this project's three figures,
         every frame at once on the device (eval_metrics; hotrack_amd/csrc/seq_eval.hip) with one read-back per sequence:

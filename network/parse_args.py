@@ -43,4 +43,20 @@ def add_args(parser):
                              "PLY, object frame, metres; models/mesh_sdf.py) instead of the analytic capsule volume")
     parser.add_argument("--obj_as_mesh", action="store_const", const=True, default=None,
                         help="the synthetic sequences carry the capsule as a triangle mesh and the tracker builds the volume")
+    parser.add_argument("--seq_batch", type=int, default=1,
+                        help="test.py, track=obj_opt: track this many sequences in lockstep on one batched optimiser call per frame "
+                             "step (same poses, bit for bit, as one sequence at a time); 1 = one sequence at a time")
     return parser
+
+
+SEQ_BATCH_TRACKS = ("obj_opt",)
+
+
+def check_seq_batch(seq_batch, track):
+    """--seq_batch > 1 exists for the object tracker only: refuse anything else before any work is done."""
+    if seq_batch < 1:
+        raise SystemExit("--seq_batch must be >= 1, got %d" % seq_batch)
+    if seq_batch > 1 and track not in SEQ_BATCH_TRACKS:
+        raise SystemExit("--seq_batch %d needs track: obj_opt (the object tracker's sequences are tracked in lockstep on the batched "
+                         "particle optimiser); this configuration has track: %s, which tracks one sequence at a time -- drop the flag"
+                         % (seq_batch, track))

@@ -796,6 +796,18 @@ class Trainer(nn.Module):
             loss_dict, ret = self.model.compute_loss(data, ret, flags)
         return loss_dict, ret
 
+    def test_batch(self, datas, save_flag=False):
+        """`test` for a list of sequences tracked in lockstep (track: obj_opt, --seq_batch): one forward_batch for all of them,
+        then compute_loss per sequence.  Returns a list of (loss_dict, ret), one per sequence, equal to `test` on each."""
+        if not hasattr(self.model, "forward_batch"):
+            raise NotImplementedError("test_batch: track=%s has no lockstep route (obj_opt has)" % self.cfg["track"])
+        flags = self.init_flag_dict()
+        flags["test_flag"], flags["save_flag"] = True, save_flag
+        self.model.eval()
+        with torch.no_grad():
+            rets = self.model.forward_batch(datas, flags)
+            return [self.model.compute_loss(data, ret, flags) for data, ret in zip(datas, rets)]
+
 
 def _tree_flatten(obj):
     """(tensor leaves, structure) of nested dicts / lists / tuples / None (dict keys in sorted order)."""
