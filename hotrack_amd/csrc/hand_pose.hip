@@ -18,7 +18,15 @@
 // hand_pose_update_kernel.  One workgroup of 1024 threads: gate, energies, weights and the 20 weighted sums (thread-strided
 // in index order, a butterfly per wave, an in-order sum over the 16 waves -- as hand_shape.hip), then thread 0 applies the
 // reference's update with its host branches as selects and threads 64..108 the 45 joint angles.
+//
+// hand_pose_eval_batch_kernel / hand_pose_update_batch_kernel (pn2x_hand_pose_opt_batch).  S independent problems per launch:
+// the bodies above are the device functions hand_pose_eval_block / hand_pose_update_block, which the single kernels call with
+// their own argument and the batched kernels with a Frame built from the batch's shared fields and the problem's record
+// (pn2x_hand_pose_problem, a device array read at a workgroup-uniform address).  The eval grid's y and the update grid's x is
+// the problem; a problem that is not active returns before it reads any of its record's pointers.  No workgroup waits for another.
 #include <hip/hip_fp16.h>
+
+#include <cstring>
 
 #include "pn2_common.h"
 #include "sdf_device.h"
@@ -91,7 +99,7 @@ __device__ __forceinline__ void rodrigues(float ax, float ay, float az, float *R
 }
 
 template <bool F16>
-__global__ void __launch_bounds__(256) hand_pose_eval_kernel(const Frame A) {
+__device__ __forceinline__ void hand_pose_eval_block(const Frame A) {
     extern __shared__ float4 dyn[];
     __shared__ float4 skel[4][NJ * 3];  // per wave and joint: R (9, row-major), t (3)
     const int V = A.V, K = A.K, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -303,14 +311,40 @@ __global__ void __launch_bounds__(256) hand_pose_eval_kernel(const Frame A) {
     }
 }
 
+template <bool F16>
+__global__ void __launch_bounds__(256) hand_pose_eval_kernel(const Frame A) {
+    hand_pose_eval_block<F16>(A);
+}
+
+// a record is read through the constant address space: nothing writes the table while a kernel that reads it runs, and a
+// read-only, workgroup-uniform address makes every field a scalar load
+typedef __attribute__((address_space(4))) pn2x_hand_pose_problem ConstProblem;
+
+// The batch: `shared` holds what the problems have in common (its per-problem fields are unset), `prob` the S records.
+struct Batch {
+    Frame shared;
+    const pn2x_hand_pose_problem *prob;
+};
+
+template <bool F16>
+__global__ void __launch_bounds__(256) hand_pose_eval_batch_kernel(const Batch B) {
+    const ConstProblem *r = (const ConstProblem *)B.prob + blockIdx.y;
+    if (!r->active) return;
+    Frame A = B.shared;
+    A.rest_j = r->rest_joints; A.rest_v = r->rest_verts; A.state = r->state; A.pred_kp = r->pred_kp; A.last_kp = r->last_kp;
+    A.vis = r->vis_mask; A.obj_r = r->obj_r; A.obj_t = r->obj_t; A.vol = r->vol; A.mask = r->mask; A.h = r->h; A.w = r->w;
+    A.fx = r->fx; A.fy = r->fy; A.cx = r->cx; A.cy = r->cy; A.terms = r->work;
+    hand_pose_eval_block<F16>(A);
+}
+
 __global__ void __launch_bounds__(256) hand_pose_energy_kernel(int P, const float *__restrict__ terms, float *__restrict__ energy) {
     const bool gate = terms[2] != 0.f;
     for (int q = blockIdx.x * 256 + threadIdx.x; q < P; q += gridDim.x * 256) energy[q] = candidate_energy(terms, q, gate);
 }
 
-__global__ void __launch_bounds__(UT) hand_pose_update_kernel(int P, const float *__restrict__ pre, const float *__restrict__ terms,
-                                                              const float *__restrict__ comps, float theta_scale, float c2, float beta,
-                                                              float one_minus_beta, float *__restrict__ state, float *__restrict__ trace) {
+__device__ __forceinline__ void hand_pose_update_block(int P, const float *__restrict__ pre, const float *__restrict__ terms,
+                                                       const float *__restrict__ comps, float theta_scale, float c2, float beta,
+                                                       float one_minus_beta, float *__restrict__ state, float *__restrict__ trace) {
     __shared__ float red[UW * NV], tot[NV];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const bool gate = terms[2] != 0.f;
@@ -409,6 +443,36 @@ __global__ void __launch_bounds__(UT) hand_pose_update_kernel(int P, const float
     state[S_PREV_OK] = success ? 1.f : 0.f;
 }
 
+__global__ void __launch_bounds__(UT) hand_pose_update_kernel(int P, const float *__restrict__ pre, const float *__restrict__ terms,
+                                                              const float *__restrict__ comps, float theta_scale, float c2, float beta,
+                                                              float one_minus_beta, float *__restrict__ state, float *__restrict__ trace) {
+    hand_pose_update_block(P, pre, terms, comps, theta_scale, c2, beta, one_minus_beta, state, trace);
+}
+
+// one workgroup per problem; `it` picks the iteration's row of the problem's trace slice
+__global__ void __launch_bounds__(UT) hand_pose_update_batch_kernel(int P, const float *__restrict__ pre,
+                                                                    const pn2x_hand_pose_problem *__restrict__ prob,
+                                                                    const float *__restrict__ comps, float theta_scale, float c2,
+                                                                    float beta, float one_minus_beta, int it) {
+    const ConstProblem *r = (const ConstProblem *)prob + blockIdx.x;
+    if (!r->active) return;
+    hand_pose_update_block(P, pre, r->work, comps, theta_scale, c2, beta, one_minus_beta, r->state,
+                           r->trace ? r->trace + (size_t)it * (3 + ND) : nullptr);
+}
+
+// records handed over by value (kernel arguments are captured with a graph): thread t copies 8-byte word t of the chunk
+constexpr int FILL = 16, REC_WORDS = sizeof(pn2x_hand_pose_problem) / 8;
+static_assert(sizeof(pn2x_hand_pose_problem) == 128 && sizeof(pn2x_hand_pose_problem) % 8 == 0, "record layout (pn2_ext.h)");
+struct ProblemChunk {
+    unsigned long long w[FILL * REC_WORDS];
+};
+
+__global__ void __launch_bounds__(FILL * REC_WORDS) hand_pose_problems_fill_kernel(unsigned long long *__restrict__ dst, int n,
+                                                                                   const ProblemChunk c) {
+    const int t = threadIdx.x;
+    if (t < n * REC_WORDS) dst[t] = c.w[t];
+}
+
 }  // namespace hpose
 }  // namespace pn2
 
@@ -497,6 +561,77 @@ extern "C" int pn2x_hand_pose_opt(HAND_POSE_MODEL_PARAMS, int iterations, double
         hipLaunchKernelGGL(hand_pose_update_kernel, dim3(1), dim3(UT), 0, st, p, pre, work, comps, theta_scale,
                            (float)scaling_coefficient2, (float)beta, (float)(1.0 - beta), state,
                            trace ? trace + (size_t)it * (3 + ND) : nullptr);
+    }
+    return check_launch();
+}
+
+extern "C" long pn2x_hand_pose_opt_batch_work_floats(int p, int s) {
+    return (p < 0 || s < 0) ? (long)PN2_EINVAL : (long)TERMS * p * s;
+}
+
+extern "C" int pn2x_hand_pose_problems_fill(pn2x_hand_pose_problem *problems, int s, const pn2x_hand_pose_problem *host, void *stream) {
+    if (s < 1) return PN2_EINVAL;
+    if (s > 65535) return PN2_ERANGE;
+    if (!problems || !host) return PN2_ENULL;
+    for (int q = 0; q < s; ++q) {  // the records are host memory here: what the batched entry cannot check
+        const pn2x_hand_pose_problem &r = host[q];
+        if (!r.active) continue;
+        if (r.h < 1 || r.w < 1) return PN2_EINVAL;
+        if ((long)r.h * r.w >= (1L << 31)) return PN2_ERANGE;
+        if (!r.state || !r.work || !r.rest_joints || !r.rest_verts || !r.pred_kp || !r.vis_mask || !r.obj_r || !r.obj_t || !r.vol ||
+            !r.mask)
+            return PN2_ENULL;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    for (int q0 = 0; q0 < s; q0 += FILL) {
+        const int n = s - q0 < FILL ? s - q0 : FILL;
+        ProblemChunk c;
+        memset(&c, 0, sizeof(c));
+        memcpy(c.w, host + q0, (size_t)n * sizeof(pn2x_hand_pose_problem));
+        hipLaunchKernelGGL(hand_pose_problems_fill_kernel, dim3(1), dim3(FILL * REC_WORDS), 0, st,
+                           reinterpret_cast<unsigned long long *>(problems + q0), n, c);
+    }
+    return check_launch();
+}
+
+extern "C" int pn2x_hand_pose_opt_batch(int p, int v, int j, int k, const int *parents, const int *pose_block, const int *skin_pack,
+                                        const float *skin_w, const float *comps, float theta_scale, const float *pre, int vol_f16,
+                                        int res, float voxel_scale, float w_sil, float w_pen, float w_vis, float w_invis,
+                                        float w_temporal, float w_attr, int s, int active, const pn2x_hand_pose_problem *problems,
+                                        int iterations, double scaling_coefficient2, double beta, void *stream) {
+    if (p < 1 || v < 1 || j < 1 || k < 1 || res < 1 || (res & 1) == 0 || !(voxel_scale > 0.f) || (vol_f16 != 0 && vol_f16 != 1) ||
+        s < 1 || active < 0 || active > s || iterations < 0)
+        return PN2_EINVAL;
+    if (!pn2x_hand_pose_opt_supported(p, v, j, k, NC, res) || s > 65535 || iterations > 4096) return PN2_ERANGE;
+    if (!parents || !pose_block || !skin_pack || !skin_w || !comps || !pre) return PN2_ENULL;
+    if (iterations == 0) return PN2_OK;
+    if (!problems) return PN2_ENULL;
+    if (active == 0) return PN2_OK;
+    Batch B;
+    memset(&B, 0, sizeof(B));
+    Frame &A = B.shared;
+    A.P = p; A.V = v; A.K = k;
+    A.parents = parents; A.pose_block = pose_block; A.pack = skin_pack; A.skin_w = skin_w; A.comps = comps;
+    A.theta_scale = theta_scale; A.pre = pre; A.res = res; A.voxel_scale = voxel_scale;
+    A.w_sil = w_sil; A.w_pen = w_pen; A.w_vis = w_vis; A.w_invis = w_invis; A.w_tmp = w_temporal; A.w_attr = w_attr;
+    B.prob = problems;
+    static PerDeviceOnce raised;
+    if (raised.first_use()) {
+        (void)hipFuncSetAttribute((const void *)hand_pose_eval_batch_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)eval_lds_bytes(MAXV, MAXK));
+        (void)hipFuncSetAttribute((const void *)hand_pose_eval_batch_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)eval_lds_bytes(MAXV, MAXK));
+    }
+    // eval_launch's rule with the three covers of the compute units shared among the active problems: a problem's x extent
+    // deals its candidates evenly over at most 3 CUs / active workgroups, and never fewer than one
+    const int wgs = (p + 3) / 4, share = 3 * num_compute_units() / active, cap = share < 1 ? 1 : share;
+    const int rounds = (wgs + cap - 1) / cap, gx = (wgs + rounds - 1) / rounds;
+    hipStream_t st = (hipStream_t)stream;
+    for (int it = 0; it < iterations; ++it) {
+        if (vol_f16) hipLaunchKernelGGL(hand_pose_eval_batch_kernel<true>, dim3(gx, s), dim3(256), eval_lds_bytes(v, k), st, B);
+        else hipLaunchKernelGGL(hand_pose_eval_batch_kernel<false>, dim3(gx, s), dim3(256), eval_lds_bytes(v, k), st, B);
+        hipLaunchKernelGGL(hand_pose_update_batch_kernel, dim3(s), dim3(UT), 0, st, p, pre, problems, comps, theta_scale,
+                           (float)scaling_coefficient2, (float)beta, (float)(1.0 - beta), it);
     }
     return check_launch();
 }

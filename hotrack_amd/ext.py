@@ -1124,6 +1124,98 @@ def hand_pose_opt(model, rest, theta_scale, pre, state, pred_kp, last_kp, vis_ma
     return tr
 
 
+# ---- the same loop for S problems per launch (include/pn2_ext.h: pn2x_hand_pose_opt_batch) ------------------------------------
+class _HandPoseProblem(ctypes.Structure):
+    """pn2x_hand_pose_problem (128 bytes)."""
+    _fields_ = ([(n, _vp) for n in ("state", "work", "rest_joints", "rest_verts", "pred_kp", "last_kp", "vis_mask", "obj_r", "obj_t",
+                                    "vol", "mask", "trace")] +
+                [("h", _ci), ("w", _ci), ("fx", _cf), ("fy", _cf), ("cx", _cf), ("cy", _cf), ("active", _ci), ("reserved", _ci)])
+
+
+_lib.pn2x_hand_pose_opt_batch_work_floats.argtypes = [_ci, _ci]
+_lib.pn2x_hand_pose_opt_batch_work_floats.restype = _cl
+_lib.pn2x_hand_pose_problems_fill.argtypes = [_vp, _ci, ctypes.POINTER(_HandPoseProblem), _vp]
+_lib.pn2x_hand_pose_problems_fill.restype = _ci
+_lib.pn2x_hand_pose_opt_batch.argtypes = ([_ci] * 4 + [_vp] * 5 + [_cf, _vp, _ci, _ci] + [_cf] * 7 + [_ci, _ci, _vp, _ci, _cd, _cd, _vp])
+_lib.pn2x_hand_pose_opt_batch.restype = _ci
+_HAND_POSE_FRAME_KEYS = ("rest", "theta_scale", "pre", "pred_kp", "last_kp", "vis_mask", "obj_r", "obj_t", "volume", "voxel_scale", "mask",
+                         "proj", "weights")
+
+
+def hand_pose_opt_batch(model, frames, states, iterations: int, scaling_coefficient2: float, beta: float, trace: bool = False):
+    """hand_pose_opt for S independent problems with ONE set of launches (pn2x_hand_pose_opt_batch): every problem's state and
+    trace are bit-for-bit what hand_pose_opt gives for it alone.
+    frames: a list of S entries, each a dict of hand_pose_opt's per-frame arguments (rest, theta_scale, pre, pred_kp, last_kp,
+      vis_mask, obj_r, obj_t, volume, voxel_scale, mask, proj, weights; a 'model' key is ignored) or None for a problem that
+      sits out.  rest, pred_kp, last_kp (None or a tensor), vis_mask, the object pose, the volume (problems may share one), the
+      mask with its size and proj differ per problem; pre (one tensor), theta_scale, weights and the volumes' resolution, dtype
+      and voxel_scale are shared, and a batch that mixes them is refused.
+    states (S, 90): updated in place; the rows of problems that sit out are not touched.
+    Every tensor is read in place by the launches, and the record table is written by launches that carry the records as
+    arguments: no upload, no host read -- a captured call replays on whatever its buffers hold then.
+    -> trace (S, iterations, 19) (zero rows for problems that sit out) or None."""
+    f32 = torch.float32
+    S, iterations = len(frames), int(iterations)
+    if S < 1:
+        raise ValueError("hand_pose_opt_batch: frames is empty")
+    if states.dim() != 2 or tuple(states.shape) != (S, HAND_POSE_STATE_FLOATS):
+        raise ValueError(f"hand_pose_opt_batch: states {tuple(states.shape)} is not ({S}, {HAND_POSE_STATE_FLOATS})")
+    _native._ptr(states, "states", f32, S * HAND_POSE_STATE_FLOATS)
+    dev = states.device
+    tr = torch.zeros((S, iterations, HAND_POSE_TRACE_FLOATS), dtype=f32, device=dev) if trace else None
+    first, shared, per = None, None, [None] * S
+    for q, fr in enumerate(frames):
+        if fr is None:
+            continue
+        missing = [k for k in _HAND_POSE_FRAME_KEYS if k not in fr]
+        if missing:
+            raise ValueError(f"hand_pose_opt_batch: frames[{q}] lacks {missing}")
+        P, a = _hand_pose_args(model, *[fr[k] for k in _HAND_POSE_FRAME_KEYS])
+        vol = fr["volume"]
+        mine = {"volume resolution": a[20], "volume dtype": vol.dtype, "voxel_scale": a[21], "theta_scale": a[11], "weights": tuple(a[29:]),
+                "pre": (a[12], P), "device": vol.device}
+        for name, t in (("pre", fr["pre"]), ("pred_kp", fr["pred_kp"]), ("mask", fr["mask"]), ("rest_joints", fr["rest"][0])):
+            if t.device != dev:
+                raise RuntimeError(f"hand_pose_opt_batch: frames[{q}]['{name}'] is on {t.device}, states on {dev}")
+        if first is None:
+            first, shared = q, mine
+        else:
+            for name in mine:
+                if mine[name] != shared[name]:
+                    what = "one tensor of candidates" if name == "pre" else f"{shared[name]} and {mine[name]}"
+                    raise ValueError(f"hand_pose_opt_batch: frames[{first}] and frames[{q}] differ in {name} ({what}): a batch "
+                                     "shares it; run them in separate batches")
+        per[q] = a
+    if first is None or iterations == 0:
+        if iterations < 0:
+            raise ValueError(f"hand_pose_opt_batch: iterations = {iterations}")
+        return tr
+    a0 = per[first]
+    P = shared["pre"][1]
+    need = _lib.pn2x_hand_pose_opt_batch_work_floats(P, S)
+    work = torch.empty((S, need // S), dtype=f32, device=dev)
+    table = torch.empty((S, ctypes.sizeof(_HandPoseProblem) // 8), dtype=torch.int64, device=dev)
+    recs = (_HandPoseProblem * S)()
+    wstride, sstride, tstride = work.stride(0) * 4, HAND_POSE_STATE_FLOATS * 4, iterations * HAND_POSE_TRACE_FLOATS * 4
+    for q, a in enumerate(per):
+        if a is None:
+            continue  # (a zeroed record: active == 0, every pointer NULL)
+        r = recs[q]
+        r.state, r.work = states.data_ptr() + q * sstride, work.data_ptr() + q * wstride
+        r.rest_joints, r.rest_verts, r.pred_kp, r.last_kp, r.vis_mask, r.obj_r, r.obj_t, r.vol, r.mask = a[6], a[7], a[13], a[14], a[15], a[16], a[17], a[18], a[22]
+        r.trace = None if tr is None else tr.data_ptr() + q * tstride
+        r.h, r.w, r.fx, r.fy, r.cx, r.cy, r.active = a[23], a[24], a[25], a[26], a[27], a[28], 1
+    n_active = sum(a is not None for a in per)
+    with torch.cuda.device(dev):
+        st = _native._stream(states)
+        _native._check(_native._call(_lib.pn2x_hand_pose_problems_fill, "hand_pose_problems_fill", None, table.data_ptr(), S, recs, st),
+                       "hand_pose_problems_fill")
+        _native._check(_native._call(_lib.pn2x_hand_pose_opt_batch, "hand_pose_opt_batch", None, *a0[0:6], *a0[8:13], a0[19], a0[20], a0[21],
+                                     *a0[29:], S, n_active, table.data_ptr(), iterations, float(scaling_coefficient2), float(beta), st),
+                       "hand_pose_opt_batch")
+    return tr
+
+
 _lib.pn2x_posed_chamfer_partial_floats.argtypes = [_ci, _ci, _ci]
 _lib.pn2x_posed_chamfer_partial_floats.restype = ctypes.c_long
 _lib.pn2x_posed_chamfer.argtypes = [_ci, _ci, _ci] + [_vp] * 7 + [ctypes.c_long, _vp, _vp]

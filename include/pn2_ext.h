@@ -444,6 +444,52 @@ int pn2x_hand_pose_opt(int p, int v, int j, int k, const int *parents, const int
                        double beta, float *state, float *work, float *trace, void *stream);
 
 /*
+ * pn2x_hand_pose_opt for s independent problems (hand sequences that advance one frame together) with one set of launches:
+ * per iteration one launch of hand_pose_eval_batch_kernel over a (candidates, problem) grid and one launch of
+ * hand_pose_update_batch_kernel with a workgroup per problem.  The kernels run pn2x_hand_pose_opt's device functions, so a
+ * problem's state and trace equal, bit for bit, what pn2x_hand_pose_opt gives for it alone.
+ *
+ * Shared by the batch: p, v, j, k, parents, pose_block, skin_pack, skin_w, comps, theta_scale, pre, the volume's type, res and
+ * voxel_scale, the six weights, iterations, scaling_coefficient2, beta.  Per problem, one pn2x_hand_pose_problem record in a
+ * DEVICE array `problems` (s records): state (90, in/out), work (pn2x_hand_pose_opt_work_floats(p) floats of its own),
+ * rest_joints / rest_verts (they carry the sequence's shape code), pred_kp, last_kp (may be NULL), vis_mask, obj_r, obj_t, vol
+ * (problems may share one), mask with its h and w, fx, fy, cx, cy, trace (its (iterations, 19) slice, or NULL) and `active`: a
+ * problem with active == 0 sits out -- no pointer of its record is read (all may be NULL) and nothing of it is written.
+ * `active` (the argument) is the number of active records; it sizes the grid: a problem's x extent deals its ceil(p / 4)
+ * workgroups evenly over at most max(1, 3 * compute units / active), so the launch covers the device about three times.
+ *
+ * pn2x_hand_pose_problems_fill writes s records from HOST memory `host` into the device array by kernel launches that carry
+ * them as arguments (16 records per launch): no copy engine, no pinned memory, and a captured graph holds the records.  It is
+ * where the records are checked: for an active record PN2_EINVAL for h or w < 1, PN2_ERANGE for h * w >= 2^31, PN2_ENULL for a
+ * NULL pointer other than last_kp and trace.
+ * pn2x_hand_pose_opt_batch_work_floats(p, s) = s * pn2x_hand_pose_opt_work_floats(p): scratch for s problems (slice q for
+ * problem q).
+ * Errors of pn2x_hand_pose_opt_batch, before any device work: PN2_EINVAL for s < 1, active outside [0, s] and whatever
+ * pn2x_hand_pose_opt answers with it; PN2_ERANGE beyond pn2x_hand_pose_opt_supported, s > 65535 or iterations > 4096; PN2_ENULL
+ * for a NULL shared pointer or, when there is work to do, NULL `problems`.  iterations == 0 and active == 0 return PN2_OK and
+ * launch nothing.  No host sync or allocation (capturable).
+ */
+typedef struct pn2x_hand_pose_problem {
+    float *state, *work;
+    const float *rest_joints, *rest_verts, *pred_kp, *last_kp;
+    const unsigned char *vis_mask;
+    const float *obj_r, *obj_t;
+    const void *vol;
+    const unsigned char *mask;
+    float *trace;
+    int h, w;
+    float fx, fy, cx, cy;
+    int active, reserved;
+} pn2x_hand_pose_problem; /* 128 bytes */
+long pn2x_hand_pose_opt_batch_work_floats(int p, int s);
+int pn2x_hand_pose_problems_fill(pn2x_hand_pose_problem *problems, int s, const pn2x_hand_pose_problem *host, void *stream);
+int pn2x_hand_pose_opt_batch(int p, int v, int j, int k, const int *parents, const int *pose_block, const int *skin_pack,
+                             const float *skin_w, const float *comps, float theta_scale, const float *pre, int vol_f16, int res,
+                             float voxel_scale, float w_sil, float w_pen, float w_vis, float w_invis, float w_temporal, float w_attr,
+                             int s, int active, const pn2x_hand_pose_problem *problems, int iterations, double scaling_coefficient2,
+                             double beta, void *stream);
+
+/*
  * IKNet forward in eval mode (reference hand_network.py:264-322; hotrack_amd/csrc/iknet.hip) for m <= 16 rows, fp32:
  *     kp_hf = R^T (kp - t) / 0.2  (frame 0, 'kp')   or   kp * 5  (frame 1, 'camera'; R and t are not read)
  *     x     = [kp_hf | kp_hf - kp_hf[parent]]  coordinate-major (m, 126)

@@ -382,6 +382,91 @@ class gf_optimize_hand_pose:
                                                     th_trans=self.curr_t.squeeze(-1), use_registed_beta=True)
         return final_kp, self.curr_theta, self.curr_r.squeeze(0), self.curr_t.squeeze(-1)
 
+    _OPTIMIZE_ARGS = ("init_mano", "init_hand_pose", "init_kp", "last_frame_kp", "vis_mask", "init_obj_pose", "hand_shape", "projection",
+                      "background_mask")
+
+    def _split_call(self, call):
+        """An optimize_batch entry -> (optimize()'s keyword arguments, (volume, voxel_scale) or None)."""
+        if isinstance(call, dict):
+            kw = {k: v for k, v in call.items() if k not in ("sdf_volume", "voxel_scale")}
+            vol = (call["sdf_volume"], call.get("voxel_scale")) if call.get("sdf_volume") is not None else None
+        else:
+            kw, vol = dict(zip(self._OPTIMIZE_ARGS, call)), None
+        unknown = [k for k in kw if k not in self._OPTIMIZE_ARGS]
+        if unknown:
+            raise TypeError(f"optimize_batch: unknown argument(s) {unknown}")
+        return kw, vol
+
+    def optimize_batch(self, calls):
+        """optimize() for S independent sequences' current frames with ONE set of launches (hotrack_amd.ext.hand_pose_opt_batch:
+        per iteration one evaluation launch over a (candidates, sequence) grid and one update launch with a workgroup per
+        sequence), bit-equal per sequence to optimize() on it alone.
+        calls: a list of S entries -- the arguments of optimize() as a tuple or as a dict by name, or None for a sequence that sits
+        out.  A dict may also carry the sequence's own 'sdf_volume' (and 'voxel_scale'); without one the loaded volume is used.
+        All volumes of a batch share resolution, dtype and voxel_scale.  Shape code, volume, object pose, mask and projection are
+        kept per sequence; the hand model's registered shape is what it was before the call.
+        -> a list of S (final_kp, theta, rot, trans) tuples, None where the entry was None.
+        Without the device-resident route (use_kernel() false) it is optimize() per entry."""
+        split = [None if c is None else self._split_call(c) for c in calls]
+        if not self.use_kernel():
+            out = []
+            for sc in split:
+                if sc is not None and sc[1] is not None:
+                    self.load_volume(*sc[1])
+                out.append(None if sc is None else self.optimize(**sc[0]))
+            return out
+        from hotrack_amd import ext
+        hm, m = self.mano_layer_right, self._kernel_model()
+        before = getattr(hm, "registered_beta", None)
+        own_volume, own_scale = self.sdf_volume, self.voxel_scale
+        frames, states, betas = [], [], []
+        try:
+            for sc in split:
+                if sc is None:
+                    frames.append(None)
+                    states.append(torch.zeros(90, device=self.device))
+                    betas.append(None)
+                    continue
+                kw, vol = sc
+                # set_init_para with the shape code held aside: the model's one registered shape is not the batch's
+                shape = kw.get("hand_shape")
+                self.set_init_para(kw["init_mano"], kw["init_hand_pose"], kw["init_kp"], kw["last_frame_kp"], kw["vis_mask"],
+                                   kw["init_obj_pose"], None, kw.get("projection"), kw.get("background_mask"))
+                beta_k = before if shape is None else torch.as_tensor(shape, dtype=torch.float32, device=self.device).reshape(1, -1)
+                if vol is not None:
+                    self.sdf_volume = vol[0].to(self.device).contiguous()
+                    self.voxel_scale = own_scale if vol[1] is None else float(vol[1])
+                fr = self._kernel_frame()
+                fr["rest"] = ext.hand_pose_rest(m, beta_k)
+                del fr["model"]
+                self.sdf_volume, self.voxel_scale = own_volume, own_scale
+                frames.append(fr)
+                states.append(self._pack_state(self.initial_scale))
+                betas.append(beta_k)
+            state = torch.stack(states)
+            tr = ext.hand_pose_opt_batch(m, frames, state, self.iteration, self.scaling_coefficient2, self.beta, trace=self.keep_trace)
+            self.trace = tr
+            out = []
+            for k, fr in enumerate(frames):
+                if fr is None:
+                    out.append(None)
+                    continue
+                st = state[k]
+                self.curr_r, self.curr_t, self.curr_theta = st[0:9].view(1, 3, 3), st[9:12].view(1, 3, 1), st[12:57].view(1, 45)
+                self.search_size, self.prev_search_size, self.prev_success = st[57:73], st[73:89], st[89] != 0
+                # optimize()'s own last lines, at the sequence's shape
+                if betas[k] is not None:
+                    hm.register_beta(betas[k])
+                curr_axisangle = quaternion_to_axis_angle(matrix_to_unit_quaternion(self.curr_r))
+                _, final_kp = hm.forward(th_pose_coeffs=torch.cat([curr_axisangle, self.curr_theta], dim=-1),
+                                         th_trans=self.curr_t.squeeze(-1), use_registed_beta=True)
+                out.append((final_kp, self.curr_theta, self.curr_r.squeeze(0), self.curr_t.squeeze(-1)))
+        finally:
+            self.sdf_volume, self.voxel_scale = own_volume, own_scale
+            if hasattr(hm, "registered_beta"):
+                hm.registered_beta = before
+        return out
+
     def _optimize_torch(self):
         dev = self.device
         search_size = self.initial_scale

@@ -226,6 +226,102 @@ class HandTrackModel(nn.Module):
             rets.append(ret)
         return rets
 
+    def forward_batch(self, inputs, flag_dict):
+        """`forward` for S sequences in lockstep.  At frame index t every sequence that still has a frame t runs its own
+        HandTrackNet step, shape estimate and IKNet / `_pose_init` -- forward()'s calls in forward()'s order, on that sequence's
+        own carried state (last keypoints, previous pose code, palm template, shape code, the shape optimiser's history, the hand
+        model's registered shape, the object's volume) -- and then ONE `gf_optimize_hand_pose.optimize_batch` call serves all of
+        them: per iteration one evaluation launch over a (candidates, sequence) grid and one update launch with a workgroup per
+        sequence, instead of S times two.  Sequences shorter than the longest sit out once they have ended.  All volumes must
+        share one resolution, dtype and voxel_scale.  Returns a list of S `ret_dict_lst`, each what `forward` returns for that
+        sequence alone on a tracker in this one's state at the call.  Without `use_optimization` it is `forward` per sequence."""
+        if not self.use_optimization:
+            return [self.forward(seq, flag_dict) for seq in inputs]
+        from types import SimpleNamespace
+        flag_dict["track_flag"] = True
+        assert flag_dict["test_flag"]
+        flag_dict["opt_flag"] = True
+        flag_dict["IKNet_flag"] = True
+        graph_ok = (self.use_graph and pointnet_utils.fused_backend() is not None and not self.training
+                    and not torch.is_grad_enabled() and torch.device(self.device).type == "cuda")
+        ik_graph_ok = (self.use_graph and not self.training and not torch.is_grad_enabled() and torch.device(self.device).type == "cuda")
+        opt, hm = self.optimizer, self.optimizer.mano_layer_right
+        has_reg = hasattr(hm, "registered_beta")
+        S = len(inputs)
+        seqs, rets, built = [], [[] for _ in range(S)], {}
+        for seq in inputs:
+            st = SimpleNamespace(last_kp=None, prev_theta=None, shape_code=None, palm=None, volume=None, voxel_scale=None,
+                                 beta=getattr(hm, "registered_beta", None),
+                                 history=None if self.opt_shape is None else self.opt_shape.old_pred_length)
+            seqs.append(st)
+            if not len(seq):
+                continue
+            if self.opt_shape is not None:
+                st.palm = self._shaped_palm_template(torch.zeros((1, self.opt_shape.optimize_dim), device=self.device))
+            else:
+                st.palm = seq[0]["gt_hand_pose"]["palm_template"].to(self.device).float()
+            # the volume forward() would load; sequences that hand over one tensor share its device copy
+            src = seq[0].get("sdf_volume")
+            if src is not None and id(src) in built:
+                st.volume, st.voxel_scale = built[id(src)][1], seq[0].get("voxel_scale")
+                st.voxel_scale = opt.voxel_scale if st.voxel_scale is None else float(st.voxel_scale)
+                continue
+            if src is not None:
+                opt.load_volume(src, seq[0].get("voxel_scale"))
+                built[id(src)] = (src, opt.sdf_volume)
+            elif not _load_mesh_volume(opt, seq[0], self.device) and opt.sdf_volume is None:
+                raise RuntimeError("use_optimization: no SDF volume (decoding it from a DeepSDF latent needs the checkpoints); "
+                                   "put 'sdf_volume' / 'voxel_scale', or the object's mesh as 'obj_mesh' ({'vertices', 'faces'}) "
+                                   "or 'obj_mesh_path', into the sequence's first frame")
+            st.volume, st.voxel_scale = opt.sdf_volume, opt.voxel_scale
+        for t in range(max((len(seq) for seq in inputs), default=0)):
+            live = [k for k in range(S) if t < len(inputs[k])]
+            calls, centres = [None] * S, {}
+            for k in live:
+                st, data = seqs[k], inputs[k][t]
+                if has_reg:
+                    hm.registered_beta = st.beta
+                if self.opt_shape is not None:
+                    self.opt_shape.old_pred_length = st.history
+                data["pred_palm_template"] = st.palm
+                points = data["hand_points"].to(self.device, non_blocking=True).float()
+                centres[k] = centre = points.mean(dim=-2, keepdim=True)
+                if st.last_kp is not None:
+                    data["jittered_hand_kp"] = st.last_kp + centre
+                if graph_ok:
+                    ret = self._graph_step(points, data["jittered_hand_kp"].to(self.device).float(), st.palm, flag_dict)
+                else:
+                    ret = self.handnet(data, flag_dict)
+                ret["baseline_pred_kp"] = ret["pred_kp"].clone()
+                if self.opt_shape is not None:
+                    if self._shape_due(t):
+                        st.shape_code = self.opt_shape.optimize(ret["baseline_pred_kp"], use_old=self.shape_mode == 3).clone()
+                        st.palm = self._shaped_palm_template(st.shape_code)
+                        st.history = self.opt_shape.old_pred_length
+                    data["pred_beta"] = st.shape_code
+                    ret["pred_beta"] = st.shape_code
+                if self.IKnet is not None:
+                    theta0, pose0 = self._iknet(ret, data, st.palm, ik_graph_ok)
+                else:
+                    theta0, pose0 = self._pose_init(ret["baseline_pred_kp"], st.prev_theta)
+                obj_pose = data["pred_obj_pose"] if (self.use_pred_obj_pose and "pred_obj_pose" in data) else data["gt_obj_pose"]
+                calls[k] = dict(init_mano=theta0, init_hand_pose=pose0, init_kp=ret["baseline_pred_kp"], last_frame_kp=st.last_kp,
+                                vis_mask=ret["pred_kp_vis_mask"], init_obj_pose=obj_pose, hand_shape=data.get("pred_beta"),
+                                projection=data["projection"], background_mask=data["background_mask"], sdf_volume=st.volume,
+                                voxel_scale=st.voxel_scale)
+                rets[k].append(ret)
+            outs = opt.optimize_batch(calls)
+            for k in live:
+                st, ret = seqs[k], rets[k][-1]
+                kp, theta, rot, trans = outs[k]
+                ret["pred_kp"], ret["MANO_theta"] = kp, theta
+                ret["global_pose"] = {"rotation": rot.unsqueeze(0), "translation": trans.unsqueeze(-1)}
+                st.prev_theta = theta
+                st.last_kp = (ret["pred_kp"] - centres[k]).clone()
+                if calls[k]["hand_shape"] is not None and getattr(hm, "num_betas", 0) > 0:  # what optimize() registers
+                    st.beta = torch.as_tensor(calls[k]["hand_shape"]).reshape(1, -1).to(self.device).float()
+        return rets
+
     def _iknet(self, ret, data, palm_template, graph_ok):
         data["baseline_pred_kp"] = ret["baseline_pred_kp"]
         raw, theta, canon, _ = self._iknet_step(ret["baseline_pred_kp"], palm_template, graph_ok)

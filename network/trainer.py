@@ -797,10 +797,11 @@ class Trainer(nn.Module):
         return loss_dict, ret
 
     def test_batch(self, datas, save_flag=False):
-        """`test` for a list of sequences tracked in lockstep (track: obj_opt, --seq_batch): one forward_batch for all of them,
-        then compute_loss per sequence.  Returns a list of (loss_dict, ret), one per sequence, equal to `test` on each."""
+        """`test` for a list of sequences tracked in lockstep (the object tracker, `--seq_batch`, and the hand trackers, whose
+        batched pose optimiser is reached through this API only): one forward_batch for all of them, then compute_loss per
+        sequence.  Returns a list of (loss_dict, ret), one per sequence, equal to `test` on each."""
         if not hasattr(self.model, "forward_batch"):
-            raise NotImplementedError("test_batch: track=%s has no lockstep route (obj_opt has)" % self.cfg["track"])
+            raise NotImplementedError("test_batch: track=%s has no lockstep route (obj_opt and the hand trackers have)" % self.cfg["track"])
         flags = self.init_flag_dict()
         flags["test_flag"], flags["save_flag"] = True, save_flag
         self.model.eval()
