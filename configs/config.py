@@ -49,6 +49,7 @@ def get_config(args, save=True):
     if not isinstance(cfg.get("opt"), dict):
         cfg["opt"] = {}
     cfg["opt"].setdefault("fused_pose", False)  # hand-pose particle optimiser on the device-resident route (--fused_hand_pose)
+    cfg.setdefault("fused_hand_eval", False)  # tracked hand sequences evaluated in two launches (--fused_hand_eval)
     data_cfg = _load("data_config", cfg["data_config"])
     cfg["pointnet"] = {k: _load("pointnet_config", v) for k, v in cfg["pointnet_cfg"].items()}
 

@@ -397,6 +397,171 @@ hand_loss_bwd_kernel(int B, int pb, const float *__restrict__ pred_hf, float s, 
         for (int c = 0; c < 3; ++c) d[c * kHlJ + kHlPalmIdx[j]] += dyl[3 * j + c] * s;
 }
 
+// ---- evaluation of tracked hand sequences (include/pn2_ext.h: pn2x_hand_seq_metrics) in two launches -------------------------------
+// The dictionary of HandTrackNet.compute_loss with track_flag set (reference hand_network.py:159-221), one row of twelve values per
+// FRAME (the reference's batch is one frame when it tracks), for the F frames of S sequences packed one after the other; then the
+// reference's sequence rule (track_network.py:300-306) per sequence.  Columns (network/models/eval_metrics.HAND_METRIC_KEYS):
+//   0 hand_pred_kp_loss  1 hand_pred_kp_diff  2 hand_init_kp_diff  3 hand_pred_r_loss  4 hand_pred_t_loss  5 hand_init_r_diff
+//   6 hand_init_t_diff   7 hand_pred_r_diff   8 hand_pred_t_diff   9 hand_canon_r_diff 10 hand_canon_t_diff 11 MANO_theta_diff
+constexpr int kHsCols = 12;
+constexpr int kHsWaves = 4;  // frames per workgroup of hand_seq_rows_kernel (one wave each; the waves share nothing)
+
+__device__ __forceinline__ float lane_f32(float v, int l) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
+}
+
+__device__ __forceinline__ double lane_f64(double v, int l) {
+    const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)u, l);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u >> 32), l);
+    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+
+// angle of a rotation with trace tr, degrees (the reference's acos(clamp((tr - 1) / 2, -1, 1)) * 180 / pi)
+__device__ __forceinline__ float rot_angle_deg(double tr) {
+    return (float)(acos(fmin(fmax((tr - 1.0) * 0.5, -1.0), 1.0)) * 57.295779513082320877);
+}
+
+// mode 0 (Kabsch): (R, t) / (R_gt, t_gt) = the rigid fits of the sequence's palm template (palm (S,6,3), found through seq_off)
+// onto the palm keypoints of pred_s / gt_s; pose_R / pose_t unused; gt_R / gt_t optional (columns 9, 10).
+// mode 1 (pose): (R, t) = (pose_R, pose_t)[f], (R_gt, t_gt) = (gt_R, gt_t)[f]; columns 5, 6 are not produced; palm unused.
+// theta / theta_gt (F,45) optional (column 11).  Absent columns are written as 0.
+// A wave per frame: lanes 0..20 are the keypoints (phase (1) of hand_loss_fwd_kernel, same arithmetic order, the scale per
+// frame), lanes 0..44 the pose-code entries; lane 0 then fits the ground-truth palm and lane 1 the predicted one side by side,
+// and lane 0 forms the pose terms in fp64 from the fp64 fits.  Values travel between lanes through v_readlane: no LDS, no
+// atomics, no barrier (a wave past the last frame simply leaves).
+__global__ void __launch_bounds__(kHsWaves * 64)
+hand_seq_rows_kernel(int F, int S, int mode, const float *__restrict__ pred_hf, const float *__restrict__ init_hf,
+                     const float *__restrict__ gt_kp, const float *__restrict__ pred_kp, const float *__restrict__ Rc,
+                     const float *__restrict__ tc, const float *__restrict__ scale, const float *__restrict__ palm,
+                     const int *__restrict__ seq_off, const float *__restrict__ pose_R, const float *__restrict__ pose_t,
+                     const float *__restrict__ gt_R, const float *__restrict__ gt_t, const float *__restrict__ theta,
+                     const float *__restrict__ theta_gt, float *__restrict__ rows) {
+    const int lane = threadIdx.x & 63;
+    const int f = blockIdx.x * kHsWaves + (threadIdx.x >> 6);
+    if (f >= F) return;
+    const float *Rb = Rc + 9 * (size_t)f, *tb = tc + 3 * (size_t)f;
+    const float s = scale[f];
+    float gs[3] = {0.f, 0.f, 0.f}, ps[3] = {0.f, 0.f, 0.f};
+    float l1 = 0.f, dinit = 0.f, dpred = 0.f, dth = 0.f;
+    if (lane < kHlJ) {
+        const int k = lane;
+        const float *g = gt_kp + ((size_t)f * kHlJ + k) * 3, *pk = pred_kp + ((size_t)f * kHlJ + k) * 3;
+        const float d0 = g[0] - tb[0], d1 = g[1] - tb[1], d2 = g[2] - tb[2];
+        float n2 = 0.f;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            gs[c] = ((d0 * Rb[c] + d1 * Rb[3 + c] + d2 * Rb[6 + c]) / s) * s;  // canonicalize (hand_utils.py:30-31), then * s
+            ps[c] = pred_hf[((size_t)f * 3 + c) * kHlJ + k] * s;
+            const float is = init_hf[((size_t)f * 3 + c) * kHlJ + k] * s;
+            l1 += fabsf(ps[c] - gs[c]);
+            n2 += (is - gs[c]) * (is - gs[c]);
+        }
+        dinit = sqrtf(n2);
+        dpred = sqrtf((pk[0] - g[0]) * (pk[0] - g[0]) + (pk[1] - g[1]) * (pk[1] - g[1]) + (pk[2] - g[2]) * (pk[2] - g[2]));
+    }
+    const bool has_theta = theta != nullptr && theta_gt != nullptr;
+    if (has_theta && lane < 45) dth = fabsf(theta[(size_t)f * 45 + lane] - theta_gt[(size_t)f * 45 + lane]);
+    l1 = wave_sum_f32(l1); dinit = wave_sum_f32(dinit); dpred = wave_sum_f32(dpred); dth = wave_sum_f32(dth);
+
+    double R[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, t[3] = {0, 0, 0};      // lane 0: (R_gt, t_gt); lane 1 (Kabsch mode): (R, t)
+    double Rp[3][3], tp[3];                                                      // (R, t) as lane 0 sees it
+    if (mode == 0) {
+        int q = 0, hi = S - 1;  // the frame's sequence: the last q with seq_off[q] <= f (empty sequences share an offset with the next)
+        while (q < hi) {
+            const int mid = (q + hi + 1) >> 1;
+            if (seq_off[mid] <= f) q = mid; else hi = mid - 1;
+        }
+        float y[kHlPalm * 3];
+#pragma unroll
+        for (int j = 0; j < kHlPalm; ++j)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float yg = lane_f32(gs[c], kHlPalmIdx[j]), yp = lane_f32(ps[c], kHlPalmIdx[j]);
+                y[3 * j + c] = lane == 0 ? yg : yp;
+            }
+        if (lane < 2) kabsch_solve<true>(kHlPalm, palm + (size_t)q * kHlPalm * 3, y, 3, R, t);
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) Rp[a][c] = lane_f64(R[a][c], 1);
+            tp[a] = lane_f64(t[a], 1);
+        }
+    }
+    if (lane != 0) return;
+    float *row = rows + (size_t)f * kHsCols;
+    if (mode != 0) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                Rp[a][c] = (double)pose_R[(size_t)f * 9 + 3 * a + c];
+                R[a][c] = (double)gt_R[(size_t)f * 9 + 3 * a + c];
+            }
+            tp[a] = (double)pose_t[(size_t)f * 3 + a];
+            t[a] = (double)gt_t[(size_t)f * 3 + a];
+        }
+    }
+    double rl = 0, tl = 0, tr_gt = R[0][0] + R[1][1] + R[2][2], tr_rel = 0, tn = 0, dn = 0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            rl += fabs(Rp[a][c] - R[a][c]);
+            tr_rel += Rp[a][c] * R[a][c];  // trace(R^T R_gt)
+        }
+        tl += fabs(tp[a] - t[a]);
+        tn += t[a] * t[a];
+        dn += (tp[a] - t[a]) * (tp[a] - t[a]);
+    }
+    row[0] = l1 / 63.f;
+    row[1] = dpred / 21.f;
+    row[2] = dinit / 21.f;
+    row[3] = (float)(rl / 9.0);
+    row[4] = (float)(tl / 3.0);
+    row[5] = mode == 0 ? rot_angle_deg(tr_gt) : 0.f;
+    row[6] = mode == 0 ? (float)sqrt(tn) : 0.f;
+    row[7] = rot_angle_deg(tr_rel);
+    row[8] = (float)sqrt(dn);
+    float cr = 0.f, ct = 0.f;
+    if (gt_R != nullptr && gt_t != nullptr) {  // the hand frame against the ground-truth hand pose (hand_network.py:206-215)
+        double trc = 0, cn = 0;
+#pragma unroll
+        for (int a = 0; a < 9; ++a) trc += (double)Rb[a] * (double)gt_R[(size_t)f * 9 + a];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const double d = (double)gt_t[(size_t)f * 3 + a] - (double)tb[a];
+            cn += d * d;
+        }
+        cr = rot_angle_deg(trc);
+        ct = (float)sqrt(cn);
+    }
+    row[9] = cr;
+    row[10] = ct;
+    row[11] = has_theta ? dth / 45.f : 0.f;
+}
+
+// rows (F,12) -> seq (S,12): a wave per sequence, lanes 0..11 the columns.  Columns 2, 5, 6 (the reference's 'init' keys) are the
+// row of the sequence's first frame, every other column the sum of its rows in frame order (fp64, serial: the order depends on
+// nothing but the sequence) over its length.  A sequence without frames gets zeros and reads nothing.
+__global__ void __launch_bounds__(64)
+hand_seq_reduce_kernel(int F, int S, const float *__restrict__ rows, const int *__restrict__ seq_off, float *__restrict__ seq) {
+    const int q = blockIdx.x, col = threadIdx.x;
+    if (q >= S || col >= kHsCols) return;
+    const int f0 = max(seq_off[q], 0), f1 = min(seq_off[q + 1], F);  // (offsets outside the rows can never be read through)
+    float v = 0.f;
+    if (f1 > f0) {
+        if (col == 2 || col == 5 || col == 6) {
+            v = rows[(size_t)f0 * kHsCols + col];
+        } else {
+            double acc = 0.0;
+            for (int f = f0; f < f1; ++f) acc += (double)rows[(size_t)f * kHsCols + col];
+            v = (float)(acc / (double)(f1 - f0));
+        }
+    }
+    seq[(size_t)q * kHsCols + col] = v;
+}
+
 // pn2x_hand_frame: Kabsch on the palm keypoints + canonicalisation of the whole cloud, one workgroup per cloud.
 // Replaces ransac_rt + canonicalize (reference hand_network.py:100,118-119; hand_utils.py:30-31,42-66): the CPU
 // SVD hop, the cat/transpose and ~8 small torch kernels become one launch.
@@ -491,6 +656,29 @@ extern "C" int pn2x_hand_losses_backward(int b, int pb, const float *pred_hf, fl
     hipLaunchKernelGGL(pn2::hand_loss_bwd_kernel, dim3((b + 63) / 64), dim3(64), 0, (hipStream_t)stream, b, pb, pred_hf, scale, palm, saved,
                        grad3, d_pred_hf, grad_total, weights);
     return pn2::check_launch();
+}
+
+// Returns the bit mask of the valid columns (bit c = column c of rows / seq), or a negative PN2_E* code.
+extern "C" int pn2x_hand_seq_metrics(int f, int s, int j, int mode, const float *pred_hf, const float *init_hf, const float *gt_kp,
+                                      const float *pred_kp, const float *rc, const float *tc, const float *scale, const float *palm,
+                                      const int *seq_off, const float *pose_r, const float *pose_t, const float *gt_r, const float *gt_t,
+                                      const float *theta, const float *theta_gt, float *rows, float *seq, void *stream) {
+    if (f < 0 || s < 0 || j != pn2::kHlJ || !(mode == 0 || mode == 1)) return PN2_EINVAL;
+    int mask = 0x19f;  // columns 0-4, 7, 8
+    if (mode == 0) mask |= 0x60;
+    if (gt_r && gt_t) mask |= 0x600;
+    if (theta && theta_gt) mask |= 0x800;
+    if (f == 0 || s == 0) return mask;
+    if (!pred_hf || !init_hf || !gt_kp || !pred_kp || !rc || !tc || !scale || !seq_off || !rows || !seq) return PN2_ENULL;
+    if (mode == 0 ? !palm : (!pose_r || !pose_t || !gt_r || !gt_t)) return PN2_ENULL;
+    hipLaunchKernelGGL(pn2::hand_seq_rows_kernel, dim3((f + pn2::kHsWaves - 1) / pn2::kHsWaves), dim3(pn2::kHsWaves * 64), 0,
+                       (hipStream_t)stream, f, s, mode, pred_hf, init_hf, gt_kp, pred_kp, rc, tc, scale, palm, seq_off, pose_r, pose_t,
+                       gt_r, gt_t, theta, theta_gt, rows);
+    int rcode = pn2::check_launch();
+    if (rcode != PN2_OK) return rcode;
+    hipLaunchKernelGGL(pn2::hand_seq_reduce_kernel, dim3(s), dim3(64), 0, (hipStream_t)stream, f, s, rows, seq_off, seq);
+    rcode = pn2::check_launch();
+    return rcode != PN2_OK ? rcode : mask;
 }
 
 extern "C" int pn2x_hand_frame(int b, int xb, int num, int n, int j, const float *palm_template, const float *kp,

@@ -1256,3 +1256,54 @@ def obj_pose_metrics(gt_R: torch.Tensor, gt_t: torch.Tensor, pred_R: torch.Tenso
                                      _native._ptr(pred_t, "pred_t", f32, T * 3), int(axis), 1 if up_and_down_sym else 0,
                                      out.data_ptr(), _native._stream(gt_R)), "obj_pose_metrics")
     return out
+
+
+_lib.pn2x_hand_seq_metrics.argtypes = [_ci] * 4 + [_vp] * 18
+_lib.pn2x_hand_seq_metrics.restype = _ci
+HAND_SEQ_COLS = 12
+
+
+def hand_seq_metrics(pred_hf: torch.Tensor, init_hf: torch.Tensor, gt_kp: torch.Tensor, pred_kp: torch.Tensor, Rc: torch.Tensor,
+                     tc: torch.Tensor, scale: torch.Tensor, offsets, palm=None, pose_R=None, pose_t=None, gt_R=None, gt_t=None,
+                     theta=None, theta_gt=None, seq_off=None):
+    """The tracked-hand evaluation of F frames in S sequences (pn2x_hand_seq_metrics): pred_hf / init_hf (F,3,21), gt_kp / pred_kp
+    (F,21,3), Rc (F,3,3), tc (F,3), scale (F,) -> rows (F,12), seq (S,12), mask (bit c: column c is valid).  offsets: the HOST
+    list of S + 1 frame offsets (non-decreasing, offsets[0] = 0, offsets[-1] = F); seq_off: the same offsets as an int32 device
+    tensor when the caller already holds one (a captured graph must: building it is a host-to-device copy), else it is built
+    here.  palm (S,6,3) selects the Kabsch mode, pose_R (F,3,3) / pose_t (F,3) with gt_R / gt_t the pose mode; gt_R / gt_t
+    (F,3,3) / (F,3) are optional in the Kabsch mode, theta / theta_gt (F,45) in both.  Two launches, no host sync."""
+    f32 = torch.float32
+    offsets = [int(o) for o in offsets]
+    F, S = pred_hf.shape[0], len(offsets) - 1
+    if S < 0 or offsets[0] != 0 or offsets[-1] != F or any(b < a for a, b in zip(offsets, offsets[1:])):
+        raise ValueError(f"hand_seq_metrics: offsets must be non-decreasing from 0 to F = {F}, got {offsets}")
+    if (palm is None) == (pose_R is None):
+        raise ValueError("hand_seq_metrics: give either the palm templates (Kabsch mode) or the global pose (pose mode)")
+    mode = 0 if palm is not None else 1
+    if (gt_R is None) != (gt_t is None) or (theta is None) != (theta_gt is None) or (mode == 1 and (pose_t is None or gt_R is None)):
+        raise ValueError("hand_seq_metrics: gt_R / gt_t and theta / theta_gt come in pairs; the pose mode needs pose_t, gt_R and gt_t")
+    if pred_hf.dim() != 3 or tuple(pred_hf.shape[1:]) != (3, 21):
+        raise ValueError(f"hand_seq_metrics: pred_hf must be (F,3,21), got {tuple(pred_hf.shape)}")
+    dev = pred_hf.device
+    if seq_off is None:
+        seq_off = torch.tensor(offsets, dtype=torch.int32, device=dev)
+    opt = lambda t, name, n: None if t is None else _native._ptr(t, name, f32, n)
+    args = [_native._ptr(pred_hf, "pred_hf", f32, F * 63), _native._ptr(init_hf, "init_hf", f32, F * 63),
+            _native._ptr(gt_kp, "gt_kp", f32, F * 63), _native._ptr(pred_kp, "pred_kp", f32, F * 63),
+            _native._ptr(Rc, "Rc", f32, F * 9), _native._ptr(tc, "tc", f32, F * 3), _native._ptr(scale, "scale", f32, F),
+            opt(palm, "palm", S * 18), _native._ptr(seq_off, "seq_off", torch.int32, S + 1),
+            opt(pose_R, "pose_R", F * 9), opt(pose_t, "pose_t", F * 3), opt(gt_R, "gt_R", F * 9), opt(gt_t, "gt_t", F * 3),
+            opt(theta, "theta", F * 45), opt(theta_gt, "theta_gt", F * 45)]
+    for t in (init_hf, gt_kp, pred_kp, Rc, tc, scale, palm, seq_off, pose_R, pose_t, gt_R, gt_t, theta, theta_gt):
+        if t is not None and t.device != dev:
+            raise ValueError(f"hand_seq_metrics: tensors on {dev} and {t.device}")
+    rows = torch.empty((F, HAND_SEQ_COLS), dtype=f32, device=dev)
+    seq = torch.empty((S, HAND_SEQ_COLS), dtype=f32, device=dev)
+    if F == 0:  # nothing to launch (an empty tensor has no address to tell a given input from an absent one): zero rows per sequence
+        return rows, seq.zero_(), 0x19f | (0x60 if mode == 0 else 0) | (0x600 if gt_R is not None else 0) | (0x800 if theta is not None else 0)
+    with torch.cuda.device(dev):
+        rc = _native._call(_lib.pn2x_hand_seq_metrics, "hand_seq_metrics", None, F, S, 21, mode, *args, rows.data_ptr(), seq.data_ptr(),
+                           _native._stream(pred_hf))
+    if rc < 0:
+        _native._check(rc, "hand_seq_metrics")
+    return rows, seq, int(rc)

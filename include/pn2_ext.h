@@ -902,6 +902,30 @@ int pn2x_posed_chamfer(int n, int m, int t, const float *a, const float *b, cons
 int pn2x_obj_pose_metrics(int t, const float *gt_r, const float *gt_t, const float *pred_r, const float *pred_t, int axis,
                           int up_and_down_sym, float *out, void *stream);
 
+/*
+ * Evaluation of tracked hand sequences (csrc/kabsch.hip): HandTrackNet.compute_loss's dictionary with track_flag set (reference
+ * hand_network.py:159-221) for every frame of s sequences, and the reference's sequence rule (track_network.py:300-306), in two
+ * launches without a host sync.  The f frames are those of all sequences packed one sequence after the other; seq_off (s + 1)
+ * int32 on the device, non-decreasing, seq_off[0] = 0, seq_off[s] = f, gives each sequence's frames.  j: keypoints per hand (21).
+ * pred_hf / init_hf (f,3,21) channel-major hand-frame keypoints, gt_kp / pred_kp (f,21,3) camera frame, rc (f,3,3) / tc (f,3) /
+ * scale (f): each frame's hand frame.  rows (f,12) and seq (s,12), columns
+ *   {hand_pred_kp_loss, hand_pred_kp_diff, hand_init_kp_diff, hand_pred_r_loss, hand_pred_t_loss, hand_init_r_diff,
+ *    hand_init_t_diff, hand_pred_r_diff, hand_pred_t_diff, hand_canon_r_diff, hand_canon_t_diff, MANO_theta_diff}.
+ * mode 0: (R, t) / (R_gt, t_gt) are the rigid fits of the sequence's palm template (palm (s,6,3)) onto the palm keypoints of the
+ * scaled predicted / ground-truth keypoints; pose_r / pose_t are not read.  mode 1: (R, t) = (pose_r (f,3,3), pose_t (f,3)),
+ * (R_gt, t_gt) = (gt_r, gt_t); columns 5 and 6 are not produced and palm is not read.  gt_r (f,3,3) / gt_t (f,3): the
+ * ground-truth hand pose, optional in mode 0 (columns 9, 10); theta / theta_gt (f,45) optional (column 11).  A column that is not
+ * produced is written as 0.  seq: columns 2, 5, 6 are the row of the sequence's first frame, every other column the mean of the
+ * sequence's rows summed in frame order; a sequence without frames gets zeros.  Run-to-run bitwise equal, and a sequence's
+ * values do not depend on the other sequences of the call.
+ * Returns the mask of valid columns (bit c = column c; >= 0) or PN2_EINVAL (f < 0, s < 0, j != 21, mode not 0 / 1) / PN2_ENULL (a
+ * required pointer is NULL with f > 0 and s > 0) / PN2_ELAUNCH.  f = 0 or s = 0: the mask, no launch.
+ */
+int pn2x_hand_seq_metrics(int f, int s, int j, int mode, const float *pred_hf, const float *init_hf, const float *gt_kp,
+                          const float *pred_kp, const float *rc, const float *tc, const float *scale, const float *palm,
+                          const int *seq_off, const float *pose_r, const float *pose_t, const float *gt_r, const float *gt_t,
+                          const float *theta, const float *theta_gt, float *rows, float *seq, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

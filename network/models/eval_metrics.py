@@ -124,3 +124,126 @@ def to_eval_frame(pose, eval_frame):
     Tc = eval_frame["translation"].to(R.device, R.dtype).reshape(3, 1)
     R2 = torch.matmul(R, Rc.t())
     return {"rotation": R2, "translation": t - torch.matmul(R2, Tc).squeeze(-1)}
+
+
+# ---- tracked hand sequences -----------------------------------------------------------------------------------------------
+# HandTrackNet.compute_loss's dictionary with track_flag set (reference hand_network.py:159-221), in the reference's key order
+HAND_METRIC_KEYS = ("hand_pred_kp_loss", "hand_pred_kp_diff", "hand_init_kp_diff", "hand_pred_r_loss", "hand_pred_t_loss",
+                    "hand_init_r_diff", "hand_init_t_diff", "hand_pred_r_diff", "hand_pred_t_diff", "hand_canon_r_diff",
+                    "hand_canon_t_diff", "MANO_theta_diff")
+HAND_INIT_COLUMNS = tuple(i for i, k in enumerate(HAND_METRIC_KEYS) if "init" in k)  # the sequence's first frame, not its mean
+_PALM = (0, 1, 5, 9, 13, 17)  # hand_utils.handkp2palmkp
+
+
+def _kabsch(x, y):
+    """Least-squares (R (F,3,3), t (F,3)) with y ~= R x + t for x, y (F,num,3): the reference's solve_rot_and_trans
+    (hand_utils.py:42-66), in the tensors' own dtype on their own device."""
+    cx, cy = x.mean(dim=1, keepdim=True), y.mean(dim=1, keepdim=True)
+    w = torch.bmm((x - cx).transpose(-1, -2), y - cy)
+    u, _, vh = torch.linalg.svd(w)
+    v = vh.transpose(-1, -2)
+    fix = torch.eye(3, dtype=y.dtype, device=y.device).repeat(y.shape[0], 1, 1)
+    fix[:, 2, 2] = torch.det(torch.bmm(v, u.transpose(-1, -2)))
+    R = torch.bmm(torch.bmm(v, fix), u.transpose(-1, -2))
+    return R, (cy - torch.bmm(cx, R.transpose(-1, -2))).squeeze(1)
+
+
+def _angle_deg(prod):
+    """Rotation angle in degrees from the element-wise product of two (F,3,3) rotations (its sum is trace(A^T B))."""
+    return torch.acos(((prod.sum(dim=(-1, -2)) - 1) / 2).clamp(-1.0, 1.0)) * (180.0 / math.pi)
+
+
+def _check_offsets(offsets, F):
+    offsets = [int(o) for o in offsets]
+    if len(offsets) < 1 or offsets[0] != 0 or offsets[-1] != F or any(b < a for a, b in zip(offsets, offsets[1:])):
+        raise ValueError(f"hand_sequence_metrics: offsets must be non-decreasing from 0 to the frame count {F}, got {offsets}")
+    return offsets
+
+
+def hand_sequence_metrics(frames: dict, offsets, palm=None, route=None, seq_off=None):
+    """The evaluation of tracked hand sequences: F frames of S sequences, packed one sequence after the other.
+
+    frames   the stacked per-frame tensors:
+               'pred_kp' (F,21,3), 'pred_kp_handframe' / 'init_kp_handframe' (F,3,21), 'gt_hand_kp' (F,21,3),
+               'canon_rotation' (F,3,3), 'canon_translation' (F,3), 'canon_scale' (F,);
+             optional 'global_rotation' (F,3,3) + 'global_translation' (F,3): the pose mode (the reference's
+               `'global_pose' in ret_dict` branch), which then needs 'gt_rotation' / 'gt_translation';
+             optional 'gt_rotation' (F,3,3) + 'gt_translation' (F,3): the hand_canon_* columns;
+             optional 'MANO_theta' + 'gt_MANO_theta' (F,45): MANO_theta_diff.
+    offsets  the host list of S + 1 frame offsets; palm (S,6,3): the sequences' palm templates (Kabsch mode: without a global
+             pose (R, t) / (R_gt, t_gt) are the rigid fits of the template onto the palm keypoints of the scaled predicted /
+             ground-truth keypoints).  seq_off: the offsets as an int32 device tensor when the caller holds one (graph capture).
+    Returns (rows (F,12), seq (S,12), keys): HAND_METRIC_KEYS columns per frame and per sequence -- the mean of the sequence's
+    frames, except the 'init' columns, which are its first frame's (reference track_network.py:300-306); a sequence without
+    frames is a row of zeros.  Columns that the inputs do not determine are 0 and missing from `keys`."""
+    pose_mode = "global_rotation" in frames
+    F = frames["pred_kp"].shape[0]
+    offsets = _check_offsets(offsets, F)
+    S = len(offsets) - 1
+    if frames["pred_kp"].shape[1] != 21:
+        raise ValueError(f"hand_sequence_metrics: 21 keypoints per hand, got {frames['pred_kp'].shape[1]}")
+    has_gt = "gt_rotation" in frames and "gt_translation" in frames
+    has_theta = "MANO_theta" in frames and "gt_MANO_theta" in frames
+    if pose_mode and not (has_gt and "global_translation" in frames):
+        raise ValueError("hand_sequence_metrics: a global pose needs 'global_translation' and the ground truth 'gt_rotation' / 'gt_translation'")
+    if not pose_mode and (palm is None or palm.reshape(-1, 6, 3).shape[0] != S):
+        raise ValueError("hand_sequence_metrics: without a global pose every sequence needs its palm template (S,6,3)")
+    valid = [True] * 5 + [not pose_mode] * 2 + [True] * 2 + [has_gt] * 2 + [has_theta]
+    keys = [k for k, ok in zip(HAND_METRIC_KEYS, valid) if ok]
+    g = lambda name, *shape: frames[name].reshape(F, *shape)
+    pred_kp, gt_kp = g("pred_kp", 21, 3), g("gt_hand_kp", 21, 3)
+    pred_hf, init_hf = g("pred_kp_handframe", 3, 21), g("init_kp_handframe", 3, 21)
+    Rc, tc, sc = g("canon_rotation", 3, 3), g("canon_translation", 3), g("canon_scale")
+    opt = lambda name, *shape: g(name, *shape) if name in frames else None
+    pR, pt = (opt("global_rotation", 3, 3), opt("global_translation", 3)) if pose_mode else (None, None)
+    gR, gt_ = (opt("gt_rotation", 3, 3), opt("gt_translation", 3)) if has_gt else (None, None)
+    th, thg = (opt("MANO_theta", 45), opt("gt_MANO_theta", 45)) if has_theta else (None, None)
+    palm = None if pose_mode else palm.reshape(S, 6, 3)
+    used = [t for t in (pred_kp, gt_kp, pred_hf, init_hf, Rc, tc, sc, pR, pt, gR, gt_, th, thg, palm) if t is not None]
+    if _kernel_route(route, *used):
+        from hotrack_amd import ext
+        c = lambda t: None if t is None else t.contiguous()
+        rows, seq, mask = ext.hand_seq_metrics(c(pred_hf), c(init_hf), c(gt_kp), c(pred_kp), c(Rc), c(tc), c(sc), offsets, palm=c(palm),
+                                               pose_R=c(pR), pose_t=c(pt), gt_R=c(gR), gt_t=c(gt_), theta=c(th), theta_gt=c(thg),
+                                               seq_off=seq_off)
+        assert mask == sum(1 << i for i, ok in enumerate(valid) if ok), (mask, valid)
+        return rows, seq, keys
+    dt, dev = pred_kp.dtype, pred_kp.device
+    s = sc[:, None, None]
+    gt_cm = gt_kp.transpose(-1, -2)  # (F,3,21)
+    gt_s = (torch.matmul(Rc.transpose(-1, -2), gt_cm - tc[:, :, None]) / s) * s  # canonicalize (hand_utils.py:30-31), then * scale
+    pred_s, init_s = pred_hf * s, init_hf * s
+    rows = torch.zeros((F, len(HAND_METRIC_KEYS)), dtype=dt, device=dev)
+    rows[:, 0] = (pred_s - gt_s).abs().mean(dim=(1, 2))
+    rows[:, 1] = (pred_kp.transpose(-1, -2) - gt_cm).norm(dim=1).mean(dim=-1)
+    rows[:, 2] = (init_s - gt_s).norm(dim=1).mean(dim=-1)
+    if pose_mode:
+        R, t, R_gt, t_gt = pR, pt, gR, gt_
+    else:
+        lengths = torch.tensor([b - a for a, b in zip(offsets, offsets[1:])], device=dev)
+        x = palm.to(dt)[torch.repeat_interleave(torch.arange(S, device=dev), lengths)] if F else palm.to(dt)[:0]
+        idx = torch.tensor(_PALM, device=dev)
+        if F:
+            R_gt, t_gt = _kabsch(x, gt_s.transpose(-1, -2).index_select(1, idx))
+            R, t = _kabsch(x, pred_s.transpose(-1, -2).index_select(1, idx))
+        else:
+            R = R_gt = torch.zeros((0, 3, 3), dtype=dt, device=dev)
+            t = t_gt = torch.zeros((0, 3), dtype=dt, device=dev)
+        rows[:, 5] = _angle_deg(torch.eye(3, dtype=dt, device=dev) * R_gt)
+        rows[:, 6] = t_gt.norm(dim=-1)
+    rows[:, 3] = (R - R_gt).abs().mean(dim=(1, 2))
+    rows[:, 4] = (t - t_gt).abs().mean(dim=-1)
+    rows[:, 7] = _angle_deg(R * R_gt)
+    rows[:, 8] = (t - t_gt).norm(dim=-1)
+    if has_gt:
+        rows[:, 9] = _angle_deg(Rc * gR)
+        rows[:, 10] = (gt_ - tc).norm(dim=-1)
+    if has_theta:
+        rows[:, 11] = (th - thg).abs().mean(dim=-1)
+    seq = torch.zeros((S, len(HAND_METRIC_KEYS)), dtype=dt, device=dev)
+    for q, (a, b) in enumerate(zip(offsets, offsets[1:])):
+        if b > a:
+            seq[q] = rows[a:b].mean(dim=0)
+            for col in HAND_INIT_COLUMNS:
+                seq[q, col] = rows[a, col]
+    return rows, seq, keys

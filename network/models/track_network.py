@@ -41,6 +41,8 @@ class HandTrackModel(nn.Module):
         self.use_optimization = bool(cfg.get("use_optimization", False)) and hand_model is not None
         self.use_pred_obj_pose = bool(cfg.get("use_pred_obj_pose", False))
         self.sym = cfg.get("obj_sym", -1)  # rot_diff_rad's symmetry mode for the obj_pred_* metrics (compute_loss)
+        # compute_loss through compute_loss_batch: every frame's dictionary from two launches (eval_metrics.hand_sequence_metrics)
+        self.fused_hand_eval = bool(cfg.get("fused_hand_eval", False))
         self.optimizer = None
         if self.use_optimization:
             from .optimization_hand import gf_optimize_hand_pose
@@ -332,7 +334,13 @@ class HandTrackModel(nn.Module):
         """HandTrackNet's loss / metric dictionary averaged over the frames.  With `use_pred_obj_pose` and frames that carry
         `pred_obj_pose`, also the reference's object-pose block (track_network.py:244-251): `obj_pred_tdiff_0`,
         `obj_pred_rdiff_0`, `obj_pred_5deg5cm_0`, `obj_pred_10deg10cm_0` of the supplied object poses against gt_obj_pose
-        (eval_metrics.eval_part_full: one launch for the whole sequence, enqueued ahead of the single read-back)."""
+        (eval_metrics.eval_part_full: one launch for the whole sequence, enqueued ahead of the single read-back).
+        With cfg['fused_hand_eval'] (`--fused_hand_eval`) it is compute_loss_batch of this one sequence instead."""
+        if self.fused_hand_eval:
+            return self.compute_loss_batch([input], [ret_dict_lst], flag_dict)[0]
+        return self._compute_loss_frames(input, ret_dict_lst, flag_dict)
+
+    def _compute_loss_frames(self, input, ret_dict_lst, flag_dict):
         total = {}
         for data, ret in zip(input, ret_dict_lst):
             loss, _ = self.handnet.compute_loss(data, ret, flag_dict)
@@ -349,6 +357,119 @@ class HandTrackModel(nn.Module):
         if obj is not None:
             out.update({"obj_pred_" + k: v for k, v in zip(eval_metrics.METRIC_KEYS, obj.tolist())})
         return out, ret_dict_lst
+
+    _said_eval = set()
+
+    def _fused_eval_unsupported(self, inputs, ret_dict_lsts):
+        """Why compute_loss_batch cannot take the two-launch route for these sequences (None: it can)."""
+        if getattr(self.handnet, "handframe", None) == "OBB":
+            return "the OBB hand frame has no pose terms"
+        for seq, rets in zip(inputs, ret_dict_lsts):
+            if len(seq) != len(rets):
+                return "a sequence and its results differ in length"
+            for r in rets:
+                if tuple(r["pred_kp"].shape) != (1, 21, 3):
+                    return "it needs one hand of 21 keypoints per frame, got pred_kp %s" % (tuple(r["pred_kp"].shape),)
+        return None
+
+    def compute_loss_batch(self, inputs, ret_dict_lsts, flag_dict):
+        """`compute_loss` for S tracked sequences at once, on the reference's rule (track_network.py:228-307): every frame of every
+        sequence is stacked, ONE eval_metrics.hand_sequence_metrics call (two launches on the GPU) gives the per-frame and the
+        per-sequence values, the `obj_pred_*` block is enqueued as in compute_loss, and one read-back brings everything to the
+        host.  Returns [(loss_dict, ret_dict_lst)] per sequence, the dictionary in the reference's key order with
+        `MANO_theta_diff` (needs `MANO_theta` in the results and `mano_pose` in gt_hand_pose) after `hand_canon_t_diff`.
+        Unlike compute_loss, the three `init` keys are the sequence's FIRST frame (the reference's rule), not the mean.  With
+        flag_dict['save_flag'], ret_dict_lst[0]['frame_errors'] is the (T,3) CPU table of the per-frame kp_error, r_error and
+        t_error (hand_pred_kp_diff, hand_pred_r_diff, hand_pred_t_diff), and every frame's 'gt_kp_handframe' is filled.  The palm
+        template of a sequence is its first frame's.  Sequences the route does not cover (OBB hand frame, other keypoint counts)
+        go through compute_loss's loop; the reason is printed once."""
+        from . import eval_metrics
+        from .hand_utils import canonicalize
+        why = self._fused_eval_unsupported(inputs, ret_dict_lsts)
+        if why is not None:
+            if why not in HandTrackModel._said_eval:
+                HandTrackModel._said_eval.add(why)
+                print("[Hand Tracking] fused_hand_eval: the per-frame evaluation runs (%s)" % why)
+            return [self._compute_loss_frames(seq, rets, flag_dict) for seq, rets in zip(inputs, ret_dict_lsts)]
+        dev, save = self.device, bool(flag_dict.get("save_flag"))
+        f = lambda x: x.to(dev).float()
+        S = len(inputs)
+        # sequences that determine the same columns share a call (a tracker's sequences all do: one call)
+        sig = lambda seq, rets: (all("global_pose" in r for r in rets), all("rotation" in d.get("gt_hand_pose", {}) for d in seq),
+                                 all("MANO_theta" in r for r in rets) and all("mano_pose" in d.get("gt_hand_pose", {}) for d in seq))
+        groups = {}
+        for k in range(S):
+            if len(inputs[k]):
+                groups.setdefault(sig(inputs[k], ret_dict_lsts[k]), []).append(k)
+        pieces, layout = [], []  # the device tensors of the one read-back; (what, whose, count)
+        for (pose_mode, has_gt, has_theta), members in groups.items():
+            data = [d for k in members for d in inputs[k]]
+            rets = [r for k in members for r in ret_dict_lsts[k]]
+            offsets = [0]
+            for k in members:
+                offsets.append(offsets[-1] + len(inputs[k]))
+            F = offsets[-1]
+            def cat(ts, *shape):  # (F, *shape) on the device: tensors that share a device travel as one copy
+                ts = [torch.as_tensor(t) for t in ts]
+                if len({t.device for t in ts}) == 1:
+                    return f(torch.cat([t.reshape(1, *shape) for t in ts], dim=0))
+                return torch.cat([f(t).reshape(1, *shape) for t in ts], dim=0)
+            frames = {"pred_kp": cat([r["pred_kp"] for r in rets], 21, 3),
+                      "pred_kp_handframe": cat([r["pred_kp_handframe"] for r in rets], 3, 21),
+                      "init_kp_handframe": cat([r["init_kp_handframe"] for r in rets], 3, 21),
+                      "gt_hand_kp": cat([d["gt_hand_kp"] for d in data], 21, 3),
+                      "canon_rotation": cat([r["canon_pose"]["rotation"] for r in rets], 3, 3),
+                      "canon_translation": cat([r["canon_pose"]["translation"] for r in rets], 3),
+                      "canon_scale": cat([r["canon_pose"]["scale"] for r in rets]).reshape(F)}
+            if pose_mode:
+                frames["global_rotation"] = cat([r["global_pose"]["rotation"] for r in rets], 3, 3)
+                frames["global_translation"] = cat([r["global_pose"]["translation"] for r in rets], 3)
+            if has_gt or pose_mode:
+                frames["gt_rotation"] = cat([d["gt_hand_pose"]["rotation"] for d in data], 3, 3)
+                frames["gt_translation"] = cat([d["gt_hand_pose"]["translation"] for d in data], 3)
+            if has_theta:
+                frames["MANO_theta"] = cat([r["MANO_theta"] for r in rets], 45)
+                frames["gt_MANO_theta"] = cat([d["gt_hand_pose"]["mano_pose"].reshape(1, -1)[:, 3:] for d in data], 45)
+            palm = None if pose_mode else cat([inputs[k][0]["gt_hand_pose"]["palm_template"] for k in members], 6, 3)
+            rows, seq, keys = eval_metrics.hand_sequence_metrics(frames, offsets, palm=palm)
+            gt_hf = None
+            if save:
+                gt_hf = canonicalize(frames["gt_hand_kp"].transpose(-1, -2),
+                                     {"rotation": frames["canon_rotation"], "translation": frames["canon_translation"][:, :, None],
+                                      "scale": frames["canon_scale"]})
+            for i, r in enumerate(rets):
+                r["gt_kp_handframe"] = gt_hf[i:i + 1] if save else None
+            cols = [eval_metrics.HAND_METRIC_KEYS.index(k) for k in keys]
+            pieces.append(seq.reshape(-1))
+            layout.append(("seq", (members, keys, cols), seq.numel()))
+            if save:
+                pieces.append(torch.stack([rows[:, 1], rows[:, 7], rows[:, 8]], dim=-1).reshape(-1))
+                layout.append(("frames", (members, offsets), 3 * F))
+        for k in range(S):
+            seq_in = inputs[k]
+            if self.use_pred_obj_pose and len(seq_in) and all("pred_obj_pose" in d and "gt_obj_pose" in d for d in seq_in):
+                err = eval_metrics.eval_part_full(_stack_poses([d["gt_obj_pose"] for d in seq_in], self.device),
+                                                  _stack_poses([d["pred_obj_pose"] for d in seq_in], self.device), axis=int(self.sym),
+                                                  up_and_down_sym=_up_and_down_sym(seq_in[0]["gt_obj_pose"]))
+                pieces.append(torch.stack([err[key] for key in eval_metrics.METRIC_KEYS]).float())
+                layout.append(("obj", k, len(eval_metrics.METRIC_KEYS)))
+        host = torch.cat(pieces).cpu() if pieces else torch.zeros(0)  # the one read-back
+        outs, at = [dict() for _ in range(S)], 0
+        for what, info, n in layout:
+            part = host[at:at + n]
+            at += n
+            if what == "seq":
+                members, keys, cols = info
+                table = part.reshape(len(members), -1).tolist()
+                for j, k in enumerate(members):
+                    outs[k].update((key, table[j][c]) for key, c in zip(keys, cols))
+            elif what == "frames":
+                members, offsets = info
+                for j, k in enumerate(members):
+                    ret_dict_lsts[k][0]["frame_errors"] = part.reshape(-1, 3)[offsets[j]:offsets[j + 1]].clone()
+            else:
+                outs[info].update({"obj_pred_" + key: v for key, v in zip(eval_metrics.METRIC_KEYS, part.tolist())})
+        return [(outs[k], ret_dict_lsts[k]) for k in range(S)]
 
 
 class ObjTrackModel_Optimization(nn.Module):

@@ -38,6 +38,10 @@ def add_args(parser):
                         help="use_optimization: run the hand-pose particle optimiser on the device-resident route (two kernels per "
                              "iteration, hotrack_amd/csrc/hand_pose.hip) instead of the torch route; needs a hand model with "
                              "plain skinning tables")
+    parser.add_argument("--fused_hand_eval", dest="fused_hand_eval", action="store_const", const=True, default=None,
+                        help="track=hand / hand_IKNet: evaluate the tracked sequences through HandTrackModel.compute_loss_batch (every "
+                             "frame's metrics from two launches, hotrack_amd/csrc/kabsch.hip; adds MANO_theta_diff and the per-frame "
+                             "error table; the hand_init_* keys are then the first frame's value, as in the reference, not the mean)")
     parser.add_argument("--obj_mesh", type=str, default=None,
                         help="track the synthetic sequences' clouds against an SDF volume built from this triangle mesh (OBJ or "
                              "PLY, object frame, metres; models/mesh_sdf.py) instead of the analytic capsule volume")

@@ -807,6 +807,8 @@ class Trainer(nn.Module):
         self.model.eval()
         with torch.no_grad():
             rets = self.model.forward_batch(datas, flags)
+            if self.cfg.get("fused_hand_eval") and hasattr(self.model, "compute_loss_batch"):  # all sequences, two launches
+                return self.model.compute_loss_batch(datas, rets, flags)
             return [self.model.compute_loss(data, ret, flags) for data, ret in zip(datas, rets)]
 
 
