@@ -147,19 +147,32 @@ three_nn_split_kernel(int n, int m, const float *__restrict__ unknown_all, const
 // launch.  Feature propagation needs (weight, index) for nothing else (pointnet_utils.py:440-453), so they stay in LDS: wave 0
 // finishes the 64 queries of the workgroup, then all four waves blend the three source rows of each query, 16 bytes per lane --
 // the same fma order as interp_pm_kernel (interpolate.hip), hence the same floats as the two launches.
+// ROWS: the queries of cloud b are the rows row_list[b, 0 : row_counts[b, 1]] (pn2x_row_lists) instead of all n -- workgroup x
+// takes the list entries [64 x, 64 x + 64) and leaves at once when the cloud's count (read on the device) ends before them; each
+// listed row gets the same search, weights and blend at its own place in `out`, no other row is written.
+template <bool ROWS>
 __global__ void __launch_bounds__(256)
 three_nn_interp_kernel(int n, int m, int c4, const float *__restrict__ unknown_all, const float *__restrict__ known_all,
-                       const float *__restrict__ points_all, int ldp, float *__restrict__ out_all, int ldo) {
+                       const float *__restrict__ points_all, int ldp, float *__restrict__ out_all, int ldo,
+                       const int *__restrict__ row_list, const int *__restrict__ row_counts) {
     extern __shared__ __attribute__((aligned(16))) float4 sk[];
     __shared__ float sd[3][3][64];
     __shared__ int si[3][3][64];
     __shared__ float fw[3][64];
     __shared__ int fi[3][64];
+    __shared__ int fq[ROWS ? 64 : 1];  // ROWS: the query row of every entry, -1 = none
     const int b = blockIdx.y;
     const float *__restrict__ known = known_all + (size_t)b * m * 3;
     const int ql = threadIdx.x & 63, c = threadIdx.x >> 6;  // c is wave-uniform
-    const int q = blockIdx.x * 64 + ql;
-    const bool active = q < n;
+    int q = blockIdx.x * 64 + ql, nq = n;
+    if constexpr (ROWS) {
+        nq = row_counts[2 * b + 1];
+        nq = nq < 0 ? 0 : (nq > n ? n : nq);
+        if ((int)blockIdx.x * 64 >= nq) return;  // the whole workgroup, before its first barrier
+        q = q < nq ? row_list[(size_t)b * n + q] : -1;
+        if ((unsigned)q >= (unsigned)n) q = -1;  // an entry that names no row of the cloud is skipped
+    }
+    const bool active = ROWS ? q >= 0 : q < n;
     const float *__restrict__ u = unknown_all + ((size_t)b * n + (active ? q : 0)) * 3;
     const float ux = u[0], uy = u[1], uz = u[2];
     for (int p = threadIdx.x; p < m; p += 256) {
@@ -199,11 +212,12 @@ three_nn_interp_kernel(int n, int m, int c4, const float *__restrict__ unknown_a
         const float norm = (r1 + r2) + r3;  // torch.sum over 3 elements adds left to right
         fw[0][ql] = r1 / norm; fw[1][ql] = r2 / norm; fw[2][ql] = r3 / norm;
         fi[0][ql] = i1; fi[1][ql] = i2; fi[2][ql] = i3;
+        if constexpr (ROWS) fq[ql] = q;
     }
     __syncthreads();
-    const int rows = min(64, n - (int)blockIdx.x * 64);
+    const int rows = min(64, nq - (int)blockIdx.x * 64);
     const float *__restrict__ src = points_all + (size_t)b * m * ldp;
-    float *__restrict__ dst = out_all + ((size_t)b * n + (size_t)blockIdx.x * 64) * ldo;
+    float *__restrict__ dst = out_all + ((size_t)b * n + (ROWS ? (size_t)0 : (size_t)blockIdx.x * 64)) * ldo;
     for (int e = threadIdx.x; e < rows * c4; e += 256) {
         const int r = e / c4, col = e - r * c4;
         const float w0 = fw[0][r], w1 = fw[1][r], w2 = fw[2][r];
@@ -215,7 +229,11 @@ three_nn_interp_kernel(int n, int m, int c4, const float *__restrict__ unknown_a
         o.y = __builtin_fmaf(w2, a2.y, __builtin_fmaf(w0, a0.y, w1 * a1.y));
         o.z = __builtin_fmaf(w2, a2.z, __builtin_fmaf(w0, a0.z, w1 * a1.z));
         o.w = __builtin_fmaf(w2, a2.w, __builtin_fmaf(w0, a0.w, w1 * a1.w));
-        *reinterpret_cast<float4 *>(dst + (size_t)r * ldo + 4 * col) = o;
+        if constexpr (ROWS) {
+            if (fq[r] >= 0) *reinterpret_cast<float4 *>(dst + (size_t)fq[r] * ldo + 4 * col) = o;
+        } else {
+            *reinterpret_cast<float4 *>(dst + (size_t)r * ldo + 4 * col) = o;
+        }
     }
 }
 
@@ -230,7 +248,24 @@ int three_nn_interp_dispatch(int b, int n, int m, int c, const float *unknown, c
     if (b == 0 || n == 0) return PN2_OK;
     if (!three_nn_interp_supported(b, n, m, c, ldp, ldo) || (((uintptr_t)points | (uintptr_t)out) % 16) != 0) return PN2_ERANGE;
     dim3 grid((n + 63) / 64, b);
-    hipLaunchKernelGGL(three_nn_interp_kernel, grid, dim3(256), (size_t)m * sizeof(float4), st, n, m, c / 4, unknown, known, points, ldp, out, ldo);
+    hipLaunchKernelGGL(three_nn_interp_kernel<false>, grid, dim3(256), (size_t)m * sizeof(float4), st, n, m, c / 4, unknown, known, points,
+                       ldp, out, ldo, nullptr, nullptr);
+    return check_launch();
+}
+
+// The listed-rows form has no two-launch counterpart, so it takes every query count and known sets from 3 points up.
+bool three_nn_interp_rows_supported(long b, long n, long m, long c, long ldp, long ldo) {
+    return b <= 65535 && m >= 3 && m <= kNnTile && c >= 4 && c % 4 == 0 && ldp % 4 == 0 && ldo % 4 == 0;
+}
+
+// The grid covers the worst case, n listed rows per cloud; the counts stay on the device.
+int three_nn_interp_rows_dispatch(int b, int n, int m, int c, const float *unknown, const float *known, const float *points, int ldp,
+                                  float *out, int ldo, const int *row_list, const int *row_counts, hipStream_t st) {
+    if (b == 0 || n == 0) return PN2_OK;
+    if (!three_nn_interp_rows_supported(b, n, m, c, ldp, ldo) || (((uintptr_t)points | (uintptr_t)out) % 16) != 0) return PN2_ERANGE;
+    dim3 grid((n + 63) / 64, b);
+    hipLaunchKernelGGL(three_nn_interp_kernel<true>, grid, dim3(256), (size_t)m * sizeof(float4), st, n, m, c / 4, unknown, known, points,
+                       ldp, out, ldo, row_list, row_counts);
     return check_launch();
 }
 

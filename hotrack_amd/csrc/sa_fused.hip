@@ -21,7 +21,7 @@
 //
 // Class walk (pn2x_sa_mlp_max_classes, sa_body with K = 0): ball-query lists pad their 32 slots with copies of the first hit, and
 // on the clouds this serves nine lists in ten hold at most 8 hits.  The walk gives a centroid only the first K' = 8, 16 or 32
-// slots of its row, the smallest that holds its hits: centroids sorted by K' on the device (sa_class_lists_kernel), a position
+// slots of its row, the smallest that holds its hits: centroids sorted by K' on the device (sa_class_lists2_kernel), a position
 // group = 64 / K' listed centroids, K' = 8 pooled with ONE cross-lane step.  It changes no bit of the result: every position's
 // MLP output is independent of the tile and row it sits in, the dropped slots are exact copies of slot 0, and the max over a
 // list is the max over its distinct entries (tests/test_gpu_sa_classes.py holds it to torch.equal with the fixed-K launch).
@@ -170,7 +170,7 @@ __device__ __forceinline__ void sa_body(const SaArgs &A, const int wg, const int
     static_assert(K == 0 || K == 16 || K == 32 || K == 64, "K");
     // K = 0 ("class walk", pn2x_sa_mlp_max_classes): the index rows are ball-query lists of 32 slots whose tail repeats the first
     // hit, and a centroid is served with only the first K' = 8, 16 or 32 slots, the smallest that holds its hits.  The centroids
-    // come sorted by K' in a device-side list (sa_class_lists_kernel), a tile is still TM positions = TM / K' listed centroids,
+    // come sorted by K' in a device-side list (sa_class_lists2_kernel), a tile is still TM positions = TM / K' listed centroids,
     // and the workgroup walks an equal contiguous share of [class-32 tiles | class-16 tiles | class-8 tiles], whose counts it
     // reads from device memory.  NOT A BIT CHANGES: a position's MLP output does not depend on the tile or row it sits in (each
     // row of an MFMA tile is its own dot products, in the same order), the dropped slots are copies of slot 0, and a max over
@@ -1043,59 +1043,136 @@ static bool sa_ranges_ok(long b, long n, long s, long k, long a1f_ld, long cadd_
 }
 
 // ---- class lists of the class walk ------------------------------------------------------------------------------------------
-// counts (M = B*S): hits of every centroid's ball query, 1 .. 32.  One workgroup: thread t owns the centroids [t * per, (t + 1) * per),
-// counts its three classes (17..32 hits | 9..16 | <= 8), a block scan of the per-thread counts places every centroid -- class 32
-// first, then 16, then 8, ascending id inside a class (no atomics: the order is a function of the counts alone) -- and every
-// centroid's record {b*S + s, b*N, b, s} goes to its place.  sizes[0..2] = the class sizes.
+// counts (M = B*S): hits of every centroid's ball query, 1 .. 32.  One workgroup per problem (a launch partitions one level or
+// both): thread t owns the centroids [t * per, (t + 1) * per), per a multiple of 4, reads them ONCE with 16-byte loads and keeps
+// their classes (17..32 hits | 9..16 | <= 8) as 2-bit codes in two registers; a wave scan of the three per-thread class counts
+// plus the 16 wave totals (one barrier) places every centroid -- class 32 first, then 16, then 8, ascending id inside a class (no
+// atomics: the order is a function of the counts alone) -- and every centroid's record {b*S + s, b*N, b, s} goes to its place.
+// sizes[0..2] = the class sizes.  CACHE = false (a run longer than the 32 codes two registers hold, M > 32768): same walk, the
+// second pass reads the counts again.
 constexpr int kClsThreads = 1024;
-__global__ __launch_bounds__(kClsThreads) void sa_class_lists_kernel(int M, int S, int N, const int *__restrict__ counts,
-                                                                      int *__restrict__ list, int *__restrict__ sizes) {
-    __shared__ int scan[3][kClsThreads];
-    const int tid = (int)threadIdx.x;
-    const int per = (M + kClsThreads - 1) / kClsThreads;
-    const long lo = (long)tid * per;
-    const int i0 = (int)(lo < M ? lo : M), i1 = i0 + per < M ? i0 + per : M;
-    int c0 = 0, c1 = 0, c2 = 0;
-    for (int i = i0; i < i1; ++i) {
-        const int k = counts[i];
-        c0 += k > 16 ? 1 : 0;
-        c1 += (k > 8 && k <= 16) ? 1 : 0;
-        c2 += k <= 8 ? 1 : 0;
-    }
-    int s0 = c0, s1 = c1, s2 = c2;  // inclusive scan
-    for (int d = 1; d < kClsThreads; d <<= 1) {
-        scan[0][tid] = s0; scan[1][tid] = s1; scan[2][tid] = s2;
-        __syncthreads();
-        if (tid >= d) { s0 += scan[0][tid - d]; s1 += scan[1][tid - d]; s2 += scan[2][tid - d]; }
-        __syncthreads();
-    }
-    scan[0][tid] = s0; scan[1][tid] = s1; scan[2][tid] = s2;
-    __syncthreads();
-    const int t0 = scan[0][kClsThreads - 1], t1 = scan[1][kClsThreads - 1], t2 = scan[2][kClsThreads - 1];
-    int p0 = s0 - c0, p1 = t0 + s1 - c1, p2 = t0 + t1 + s2 - c2;
-    int b = i0 / S, s = i0 - b * S;
-    int4 *__restrict__ dst = reinterpret_cast<int4 *>(list);
-    for (int i = i0; i < i1; ++i) {
-        const int k = counts[i];
-        const int4 rec = make_int4(i, b * N, b, s);
-        if (k > 16) dst[p0++] = rec;
-        else if (k > 8) dst[p1++] = rec;
-        else dst[p2++] = rec;
-        if (++s == S) { s = 0; ++b; }
-    }
-    if (tid == 0) { sizes[0] = t0; sizes[1] = t1; sizes[2] = t2; }
-}
-}  // namespace pn2
+constexpr int kClsCached = 32;  // centroids per thread whose codes stay in registers
+struct ClsProblem {
+    int M, S, N;
+    const int *counts;
+    int *list, *sizes;
+};
 
-extern "C" int pn2x_sa_class_lists(int b, int s, int n, const int *counts, int *list, int *sizes, void *stream) {
-    using namespace pn2;
+__device__ __forceinline__ unsigned cls_code(int k) { return k > 16 ? 0u : (k > 8 ? 1u : 2u); }
+
+// 2-bit class codes of counts[i .. i + 3] (i a multiple of 4), code 3 past the end
+__device__ __forceinline__ unsigned cls_load4(const int *__restrict__ counts, int i, int M, bool vec) {
+    if (i >= M) return 0xffu;
+    if (vec && i + 3 < M) {
+        const int4 v = *reinterpret_cast<const int4 *>(counts + i);
+        return cls_code(v.x) | (cls_code(v.y) << 2) | (cls_code(v.z) << 4) | (cls_code(v.w) << 6);
+    }
+    unsigned c = 0xffu;
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+        if (i + u < M) c = (c & ~(3u << (2 * u))) | (cls_code(counts[i + u]) << (2 * u));
+    return c;
+}
+
+template <bool CACHE>
+__global__ __launch_bounds__(kClsThreads) void sa_class_lists2_kernel(ClsProblem q0, ClsProblem q1) {
+    __shared__ int wave_tot[3][kClsThreads / 64];
+    const ClsProblem P = blockIdx.x == 0 ? q0 : q1;
+    const int M = P.M, S = P.S, N = P.N;
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int per = ((M + kClsThreads - 1) / kClsThreads + 3) & ~3;  // <= 2^14 + 4: tid * per stays far inside int
+    const int i0 = tid * per;
+    const bool vec = ((uintptr_t)P.counts & 15) == 0;
+    constexpr unsigned long long kEven = 0x5555555555555555ull;
+    unsigned long long codes = ~0ull;  // CACHE: code j at bits 2j, 2j + 1
+    int c0 = 0, c1 = 0, c2 = 0;
+    auto tally = [&](unsigned long long w) {
+        const unsigned long long lo = w & kEven, hi = (w >> 1) & kEven;
+        c0 += __builtin_popcountll(~lo & ~hi & kEven);
+        c1 += __builtin_popcountll(lo & ~hi);
+        c2 += __builtin_popcountll(~lo & hi);
+    };
+    if constexpr (CACHE) {
+        unsigned w[kClsCached / 4];
+#pragma unroll
+        for (int g = 0; g < kClsCached / 4; ++g) w[g] = 4 * g < per ? cls_load4(P.counts, i0 + 4 * g, M, vec) : 0xffu;
+        codes = 0ull;
+#pragma unroll
+        for (int g = 0; g < kClsCached / 4; ++g) codes |= (unsigned long long)w[g] << (8 * g);
+        tally(codes);
+    } else {
+        for (int g = 0; g < per; g += 4) tally(0xffffffffffffff00ull | cls_load4(P.counts, i0 + g, M, vec));
+    }
+    int s0 = c0, s1 = c1, s2 = c2;  // inclusive scan inside the wave
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int u0 = __shfl_up(s0, d), u1 = __shfl_up(s1, d), u2 = __shfl_up(s2, d);
+        if (lane >= d) { s0 += u0; s1 += u1; s2 += u2; }
+    }
+    if (lane == 63) { wave_tot[0][wave] = s0; wave_tot[1][wave] = s1; wave_tot[2][wave] = s2; }
+    __syncthreads();
+    int o0 = 0, o1 = 0, o2 = 0, t0 = 0, t1 = 0, t2 = 0;  // the lower waves' sums, the class sizes
+#pragma unroll
+    for (int w = 0; w < kClsThreads / 64; ++w) {
+        const int v0 = wave_tot[0][w], v1 = wave_tot[1][w], v2 = wave_tot[2][w];
+        t0 += v0; t1 += v1; t2 += v2;
+        if (w < wave) { o0 += v0; o1 += v1; o2 += v2; }
+    }
+    if (tid == 0) { P.sizes[0] = t0; P.sizes[1] = t1; P.sizes[2] = t2; }
+    if (i0 >= M) return;
+    int p0 = o0 + s0 - c0, p1 = t0 + o1 + s1 - c1, p2 = t0 + t1 + o2 + s2 - c2;
+    int b = i0 / S, s = i0 - b * S;
+    int4 *__restrict__ dst = reinterpret_cast<int4 *>(P.list);
+    auto place = [&](int i, unsigned code) {  // code 3 only past the end of the counts
+        if (code == 3u) return;
+        const int pos = code == 0u ? p0 : (code == 1u ? p1 : p2);
+        p0 += code == 0u; p1 += code == 1u; p2 += code == 2u;
+        if (pos < M) dst[pos] = make_int4(i, b * N, b, s);  // always, unless the counts changed under the launch
+        if (++s == S) { s = 0; ++b; }
+    };
+    if constexpr (CACHE) {
+#pragma unroll
+        for (int j = 0; j < kClsCached; ++j) place(i0 + j, (unsigned)(codes >> (2 * j)) & 3u);
+    } else {
+        for (int g = 0; g < per; g += 4) {
+            const unsigned w = cls_load4(P.counts, i0 + g, M, vec);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) place(i0 + g + u, (w >> (2 * u)) & 3u);
+        }
+    }
+}
+
+static int cls_check(int b, int s, int n, const int *counts, const int *list, const int *sizes) {
     if (b < 0 || s < 1 || n < 1) return PN2_EINVAL;
     if ((long)b * s >= (1L << 24) || (long)b * n >= (1L << 24)) return PN2_ERANGE;  // the class walk's 24-bit row numbers
     if (!sizes) return PN2_ENULL;
     if (b > 0 && (!counts || !list)) return PN2_ENULL;
     if ((uintptr_t)list % 16 != 0) return PN2_EINVAL;
-    hipLaunchKernelGGL(sa_class_lists_kernel, dim3(1), dim3(kClsThreads), 0, (hipStream_t)stream, b * s, s, n, counts, list, sizes);
+    return PN2_OK;
+}
+
+static int launch_class_lists(int problems, const ClsProblem &q0, const ClsProblem &q1, hipStream_t st) {
+    const int m = q0.M > q1.M ? q0.M : q1.M;
+    if (m <= kClsThreads * kClsCached) hipLaunchKernelGGL(sa_class_lists2_kernel<true>, dim3(problems), dim3(kClsThreads), 0, st, q0, q1);
+    else hipLaunchKernelGGL(sa_class_lists2_kernel<false>, dim3(problems), dim3(kClsThreads), 0, st, q0, q1);
     return check_launch();
+}
+}  // namespace pn2
+
+extern "C" int pn2x_sa_class_lists(int b, int s, int n, const int *counts, int *list, int *sizes, void *stream) {
+    using namespace pn2;
+    if (const int rc = cls_check(b, s, n, counts, list, sizes); rc != PN2_OK) return rc;
+    const ClsProblem q = {b * s, s, n, counts, list, sizes};
+    return launch_class_lists(1, q, q, (hipStream_t)stream);
+}
+
+extern "C" int pn2x_sa_class_lists2(int b0, int s0, int n0, const int *counts0, int *list0, int *sizes0, int b1, int s1, int n1,
+                                    const int *counts1, int *list1, int *sizes1, void *stream) {
+    using namespace pn2;
+    if (const int rc = cls_check(b0, s0, n0, counts0, list0, sizes0); rc != PN2_OK) return rc;
+    if (const int rc = cls_check(b1, s1, n1, counts1, list1, sizes1); rc != PN2_OK) return rc;
+    const ClsProblem q0 = {b0 * s0, s0, n0, counts0, list0, sizes0}, q1 = {b1 * s1, s1, n1, counts1, list1, sizes1};
+    return launch_class_lists(2, q0, q1, (hipStream_t)stream);
 }
 
 extern "C" int pn2x_sa_mlp_max_classes_supported(int k, int c1, int c2, int c3) {

@@ -114,6 +114,8 @@ _lib.pn2x_sa_mlp_max_classes_supported.argtypes = [_ci] * 4
 _lib.pn2x_sa_mlp_max_classes_supported.restype = _ci
 _lib.pn2x_sa_class_lists.argtypes = [_ci, _ci, _ci, _vp, _vp, _vp, _vp]
 _lib.pn2x_sa_class_lists.restype = _ci
+_lib.pn2x_sa_class_lists2.argtypes = [_ci, _ci, _ci, _vp, _vp, _vp] * 2 + [_vp]
+_lib.pn2x_sa_class_lists2.restype = _ci
 
 
 def sa_mlp_max_classes_supported(k: int, c1: int, c2: int, c3: int) -> bool:
@@ -131,22 +133,41 @@ def sa_class_partition(counts: torch.Tensor):
     return torch.cat([ids[m] for m in masks]), torch.stack([m.sum() for m in masks]).to(torch.int32)
 
 
-def sa_class_lists(counts: torch.Tensor, n: int):
-    """Class lists of the class walk from the ball query's hit counts (include/pn2_ext.h: pn2x_sa_class_lists): counts (B,S) int32
-    -> (lst (B*S,4) int32 records {b*S + s, b*n, b, s}, sizes (3,) int32), one launch, nothing synchronises with the host.
-    n: points per cloud of the level the index lists name."""
+def _class_lists_args(counts, n, what):
+    """Validated (B, S, n, counts pointer, list, sizes) of one partition problem."""
     if not isinstance(counts, torch.Tensor) or counts.dim() != 2 or counts.dtype != torch.int32 or not counts.is_cuda:
-        raise TypeError("sa_class_lists: counts must be a (B,S) int32 GPU tensor")
+        raise TypeError(f"{what}: counts must be a (B,S) int32 GPU tensor")
     if int(n) < 1:
-        raise ValueError("sa_class_lists: n >= 1")
+        raise ValueError(f"{what}: n >= 1")
     B, S = counts.shape
     pc = _native._ptr(counts, "counts", torch.int32, B * S)
     lst = torch.empty((B * S, 4), dtype=torch.int32, device=counts.device)
     sizes = torch.empty(3, dtype=torch.int32, device=counts.device)
+    return B, S, int(n), pc, lst, sizes
+
+
+def sa_class_lists(counts: torch.Tensor, n: int):
+    """Class lists of the class walk from the ball query's hit counts (include/pn2_ext.h: pn2x_sa_class_lists): counts (B,S) int32
+    -> (lst (B*S,4) int32 records {b*S + s, b*n, b, s}, sizes (3,) int32), one launch, nothing synchronises with the host.
+    n: points per cloud of the level the index lists name."""
+    B, S, n, pc, lst, sizes = _class_lists_args(counts, n, "sa_class_lists")
     with torch.cuda.device(counts.device):
-        _native._check(_native._call(_lib.pn2x_sa_class_lists, "sa_class_lists_kernel", None, B, S, int(n), pc, lst.data_ptr(),
+        _native._check(_native._call(_lib.pn2x_sa_class_lists, "sa_class_lists2_kernel", None, B, S, n, pc, lst.data_ptr(),
                                      sizes.data_ptr(), _native._stream(counts)), "sa_class_lists")
     return lst, sizes
+
+
+def sa_class_lists_pair(counts_a: torch.Tensor, n_a: int, counts_b: torch.Tensor, n_b: int):
+    """sa_class_lists of two problems -- both levels of a forward -- in ONE launch (include/pn2_ext.h: pn2x_sa_class_lists2)
+    -> ((lst_a, sizes_a), (lst_b, sizes_b)), each what sa_class_lists returns for its problem."""
+    a = _class_lists_args(counts_a, n_a, "sa_class_lists_pair")
+    b = _class_lists_args(counts_b, n_b, "sa_class_lists_pair")
+    if counts_a.device != counts_b.device:
+        raise ValueError("sa_class_lists_pair: both problems on one device")
+    with torch.cuda.device(counts_a.device):
+        _native._check(_native._call(_lib.pn2x_sa_class_lists2, "sa_class_lists2_kernel", None, *a[:4], a[4].data_ptr(), a[5].data_ptr(),
+                                     *b[:4], b[4].data_ptr(), b[5].data_ptr(), _native._stream(counts_a)), "sa_class_lists_pair")
+    return (a[4], a[5]), (b[4], b[5])
 
 
 def sa_mlp_max_classes(idx: torch.Tensor, classes, w2, b2, w3, b3, *, a1f=None, xyz=None, cxyz=None, wx=None, b1=None, cadd=None,
@@ -327,16 +348,42 @@ _lib.pn2x_three_nn_interpolate_pm.argtypes = [_ci, _ci, _ci, _ci, _vp, _vp, _vp,
 _lib.pn2x_three_nn_interpolate_pm.restype = _ci
 _lib.pn2x_three_nn_interpolate_pm_supported.argtypes = [_ci] * 6
 _lib.pn2x_three_nn_interpolate_pm_supported.restype = _ci
+_lib.pn2x_three_nn_interpolate_pm_rows.argtypes = [_ci, _ci, _ci, _ci, _vp, _vp, _vp, _ci, _vp, _ci, _vp, _vp, _vp]
+_lib.pn2x_three_nn_interpolate_pm_rows.restype = _ci
+_lib.pn2x_three_nn_interpolate_pm_rows_supported.argtypes = [_ci] * 6
+_lib.pn2x_three_nn_interpolate_pm_rows_supported.restype = _ci
 
 
-def three_nn_interpolate_pm(unknown: torch.Tensor, known: torch.Tensor, points: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+def three_nn_interpolate_pm(unknown: torch.Tensor, known: torch.Tensor, points: torch.Tensor, out: torch.Tensor, rows=None) -> torch.Tensor:
     """out (B,n,C) rows <- three_interpolate_pm(points, *three_nn_weights(unknown, known)[::-1]) -- one launch when the sizes are
-    covered (include/pn2_ext.h: pn2x_three_nn_interpolate_pm), the two launches otherwise; same floats either way."""
+    covered (include/pn2_ext.h: pn2x_three_nn_interpolate_pm), the two launches otherwise; same floats either way.
+    rows=(lst, counts), the pair row_lists returns: only the rows lst[b, :counts[b, 1]] of cloud b are searched, blended and
+    written (pn2x_three_nn_interpolate_pm_rows, always one launch); every other row of `out` is left as it is."""
+    if rows is not None:
+        if not (isinstance(rows, (tuple, list)) and len(rows) == 2 and all(isinstance(t, torch.Tensor) for t in rows)):
+            raise TypeError("three_nn_interpolate_pm: rows must be the (list, counts) pair of row_lists")
+        if rows[0].dtype != torch.int32 or rows[1].dtype != torch.int32:
+            raise TypeError("three_nn_interpolate_pm: rows must be int32 tensors")
+        if tuple(rows[0].shape) != tuple(unknown.shape[:2]) or tuple(rows[1].shape) != (unknown.shape[0], 2):
+            raise ValueError("three_nn_interpolate_pm: rows must be list (B,n) and counts (B,2)")
     B, n, _ = unknown.shape
     m, C = known.shape[1], points.shape[2]
     pp, ldp = _rows(points, "points", C)
     po, ldo = _rows(out, "out", C)
     f32 = torch.float32
+    if rows is not None:
+        if not (_lib.pn2x_three_nn_interpolate_pm_rows_supported(B, n, m, C, ldp, ldo) and pp % 16 == 0 and po % 16 == 0):
+            raise ValueError("three_nn_interpolate_pm: rows needs 3 <= m <= 2048 known points, C and the row strides multiples of 4 "
+                             "and 16-byte aligned points / out")
+        if rows[0].device != points.device or rows[1].device != points.device:
+            raise ValueError("three_nn_interpolate_pm: rows on another device than points")
+        with torch.cuda.device(points.device):
+            _native._check(_native._call(_lib.pn2x_three_nn_interpolate_pm_rows, "three_nn_interp_kernel", None, B, n, m, C,
+                                         _native._ptr(unknown, "unknown", f32, B * n * 3), _native._ptr(known, "known", f32, B * m * 3),
+                                         pp, ldp, po, ldo, _native._ptr(rows[0], "rows list", torch.int32, B * n),
+                                         _native._ptr(rows[1], "rows counts", torch.int32, B * 2), _native._stream(points)),
+                           "three_nn_interpolate_pm")
+        return out
     if _lib.pn2x_three_nn_interpolate_pm_supported(B, n, m, C, ldp, ldo) and pp % 16 == 0 and po % 16 == 0:
         with torch.cuda.device(points.device):
             _native._check(_native._call(_lib.pn2x_three_nn_interpolate_pm, "three_nn_interp_kernel", None, B, n, m, C,

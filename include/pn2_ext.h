@@ -90,8 +90,10 @@ int pn2x_sa_mlp_max_supported(int k, int c1, int c2, int c3);
  *
  * pn2x_sa_class_lists: counts (b*s) -> list (b*s, 4) int32 records {b*s' id = cloud * s + centroid, cloud * n, cloud, centroid},
  *   class "32" (count 17..32) first, then "16" (9..16), then "8" (<= 8), ascending id inside a class; sizes[0..2] = the three
- *   class sizes.  n: points per cloud of the level the lists index.  One launch, deterministic, nothing reaches the host.
- *   list 16-byte aligned; b*s and b*n below 2^24 (PN2_ERANGE).
+ *   class sizes.  n: points per cloud of the level the lists index.  One launch of one workgroup, deterministic, nothing reaches
+ *   the host.  list 16-byte aligned; b*s and b*n below 2^24 (PN2_ERANGE).  b = 0 writes sizes = 0, 0, 0.
+ * pn2x_sa_class_lists2: two such problems (both levels of a forward: level 2's counts depend on geometry only) in ONE launch, a
+ *   workgroup each; the checks of pn2x_sa_class_lists hold for either problem.
  * pn2x_sa_mlp_max_classes: the arguments of pn2x_sa_mlp_max plus list and sizes; one persistent launch whose workgroups read
  *   the class sizes on the device and each walk an equal contiguous share of the tiles, class 32 first (capturable; a replay on
  *   inputs with another class mix is correct).  Supported (pn2x_sa_mlp_max_classes_supported): k = 32 and widths (32,32,64) or
@@ -99,6 +101,8 @@ int pn2x_sa_mlp_max_supported(int k, int c1, int c2, int c3);
  *   any out_b).  Honours pn2x_sa_set_compute_units.
  */
 int pn2x_sa_class_lists(int b, int s, int n, const int *counts, int *list, int *sizes, void *stream);
+int pn2x_sa_class_lists2(int b0, int s0, int n0, const int *counts0, int *list0, int *sizes0, int b1, int s1, int n1,
+                         const int *counts1, int *list1, int *sizes1, void *stream);
 int pn2x_sa_mlp_max_classes_supported(int k, int c1, int c2, int c3);
 int pn2x_sa_mlp_max_classes(int b, int n, int s, int k, int c1, int c2, int c3, const float *a1f, int a1f_ld,
                             const float *xyz, const float *cxyz, const float *wx, const float *b1, const float *cadd,
@@ -139,6 +143,18 @@ int pn2x_three_nn_interpolate_pm(int b, int n, int m, int c, const float *unknow
                                  float *out, int ldo, void *stream);
 int pn2x_three_interpolate_pm(int b, int c, int m, int n, const float *points, int ldp, const int *idx,
                               const float *weight, float *out, int ldo, void *stream);
+/*
+ * pn2x_three_nn_interpolate_pm_rows: pn2x_three_nn_interpolate_pm for the query rows a device-side list names.  For cloud b only
+ * the rows row_list[b, 0 : row_counts[b, 1]] (row_list (b, n), row_counts (b, 2): the pair pn2x_row_lists writes; any order, entries
+ * outside 0 .. n-1 are skipped) get their search, weights and blend, written to the same place in `out`; no other row of `out` is
+ * touched.  Every listed row holds the floats the full launch writes there.  The grid covers n rows per cloud and workgroups past a
+ * cloud's count leave after reading it, so the count never reaches the host (capturable; a replay on other lists is correct).
+ * PN2_ERANGE unless pn2x_three_nn_interpolate_pm_rows_supported (3 <= m <= 2048, c / ldp / ldo multiples of 4, b <= 65535) and
+ * points / out 16-byte aligned -- there is no other route for a listed launch.
+ */
+int pn2x_three_nn_interpolate_pm_rows_supported(int b, int n, int m, int c, int ldp, int ldo);
+int pn2x_three_nn_interpolate_pm_rows(int b, int n, int m, int c, const float *unknown, const float *known, const float *points,
+                                      int ldp, float *out, int ldo, const int *row_list, const int *row_counts, void *stream);
 
 /*
  * Two-level furthest point sampling without the second pass.  PointNet++ samples level 2 from level 1's samples

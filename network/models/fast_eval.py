@@ -320,26 +320,27 @@ class FastEval:
         fp2_in = torch.empty((B, S1, fp2_w), **f32)  # [l1_feat | interp(l2 -> l1)]
         l1_feat = fp2_in[:, :, :c_l1]
         cnt1 = G["cnt1"]
-        if cnt1 is not None:
-            ext.sa_mlp_max_classes(idx1, ext.sa_class_lists(cnt1, N), *p["l2"], *p["l3"], xyz=xyz2, cxyz=l1_xyz, wx=p["wx"], b1=p["b1"],
-                                   out=l1_feat)
-        else:
-            ext.sa_mlp_max(idx1, *p["l2"], *p["l3"], xyz=xyz2, cxyz=l1_xyz, wx=p["wx"], b1=p["b1"], out=l1_feat)
-
-        # ---- sa2: 256 -> 128, r = 0.2, K = 32, MLP [64+3 -> 64 -> 64 -> 128] ---------------------------
-        p = P["sa2"]
+        # ---- sa2's geometry: 256 -> 128 centroids, r = 0.2, K = 32 ------------------------------------------------------
+        p2 = P["sa2"]
         S2, K2 = bh.sa2.npoint, bh.sa2.nsample_list[0]
-        c_l2 = p["l3"][0].shape[0]
+        c_l2 = p2["l3"][0].shape[0]
         sa3_in = torch.empty((B, S2, c_l2 + 4), **f32)  # [l2_feat | l2_xyz | pad]: sa3's group-all input, no torch.cat
         if cnt1 is not None:
+            # level 2's ball query reads l1_xyz and i_l2 only, nothing sa1 computes: it runs first, and ONE launch partitions both
+            # levels' centroids into their classes
             idx2, l2_xyz, cnt2 = ext.ball_query_picks(bh.sa2.radius_list[0], K2, l1_xyz, i_l2, xyz_copy=sa3_in[:, :, c_l2:c_l2 + 3], counts=True)
+            cls1, cls2 = ext.sa_class_lists_pair(cnt1, N, cnt2, S1)
+            ext.sa_mlp_max_classes(idx1, cls1, *p["l2"], *p["l3"], xyz=xyz2, cxyz=l1_xyz, wx=p["wx"], b1=p["b1"], out=l1_feat)
         else:
+            ext.sa_mlp_max(idx1, *p["l2"], *p["l3"], xyz=xyz2, cxyz=l1_xyz, wx=p["wx"], b1=p["b1"], out=l1_feat)
             idx2, l2_xyz = ext.ball_query_picks(bh.sa2.radius_list[0], K2, l1_xyz, i_l2, xyz_copy=sa3_in[:, :, c_l2:c_l2 + 3])
+
+        # ---- sa2: MLP [64+3 -> 64 -> 64 -> 128] ---------------------------------------------------------------------------
+        p = p2
         a1f = _lin(l1_feat.reshape(B * S1, c_l1), p["w1f"]).view(B, S1, -1)
         l2_feat = sa3_in[:, :, :c_l2]
         if cnt1 is not None:
-            ext.sa_mlp_max_classes(idx2, ext.sa_class_lists(cnt2, S1), *p["l2"], *p["l3"], a1f=a1f, xyz=l1_xyz, cxyz=l2_xyz, wx=p["wx"],
-                                   b1=p["b1"], out=l2_feat)
+            ext.sa_mlp_max_classes(idx2, cls2, *p["l2"], *p["l3"], a1f=a1f, xyz=l1_xyz, cxyz=l2_xyz, wx=p["wx"], b1=p["b1"], out=l2_feat)
         else:
             ext.sa_mlp_max(idx2, *p["l2"], *p["l3"], a1f=a1f, xyz=l1_xyz, cxyz=l2_xyz, wx=p["wx"], b1=p["b1"], out=l2_feat)
 
@@ -379,7 +380,6 @@ class FastEval:
 
         # ---- fp1: interpolate l1 -> l0, [interp | xyz] (weights permuted to match) -> MLP; conv1 ----------
         assert c_i == l1_out.shape[2]
-        ext.three_nn_interpolate_pm(xyz2, l1_xyz, l1_out, fp1_in[:, :, :c_i])
         q = P["q"]
         # kNN lists are sorted by (distance, index): the K=16 list is the prefix of the K=64 list -> one search (_geometry)
         Ks = [q[("q1", i)]["K"] for i in range(2)]
@@ -392,10 +392,13 @@ class FastEval:
             # the q branches read the per-point features only through their kNN lists (about 2/3 of a cloud's points for K = 64, 1/4 for K = 16), so fp1, conv1 and
             # the layer-1 feature product of all four scales run over the listed rows only, in one launch (rows named by a
             # K = 16 list get the columns of both scales, the others only the K = 64 scale's)
+            # ... and so does fp1's interpolation: row_chain is the only reader of fp1_in's interpolated columns on this route
             lst, counts = ext.row_lists(gi, gi_small, N)
+            ext.three_nn_interpolate_pm(xyz2, l1_xyz, l1_out, fp1_in[:, :, :c_i], rows=(lst, counts))
             a_all = torch.empty((B, N, 4 * c1q), **f32)
             ext.row_chain(fp1_in, lst, counts, rc["wa"], rc["ba"], rc["wb"], rc["bb"], rc["wc"], rc["bc"], rc["wq"], out=a_all)
         else:
+            ext.three_nn_interpolate_pm(xyz2, l1_xyz, l1_out, fp1_in[:, :, :c_i])
             f = P["fp1_fused"]
             if f is not None:  # both fp1 layers in one launch (pn2x_mlp2_rows): rows [interp | xyz | pad] -> 128 -> 128
                 x = ext.mlp2_rows(fp1_in.view(B * N, c_i + 4), f["w2"], f["b2"], f["w3"], f["b3"], w2e=f["w2e"])
