@@ -73,9 +73,9 @@ def get_config(args, save=True):
         cfg["device"] = torch.device("cuda", local % torch.cuda.device_count())  # (% only matters for the shared-GPU self-test)
     else:
         cfg["device"] = "cpu"
-    if cfg.get("hand_model") in ("synthetic", "synthetic_shaped"):  # the same instance poses the synthetic sequences and
-        from models.hand_model import SyntheticLBSHand                 # drives the optimisers
-        cfg["hand_model"] = SyntheticLBSHand(num_betas=10 if cfg["hand_model"] == "synthetic_shaped" else 0)
+    if isinstance(cfg.get("hand_model"), str):  # the same instance poses the synthetic sequences and drives the optimisers
+        from models.hand_model import named_hand_model
+        cfg["hand_model"] = named_hand_model(cfg["hand_model"])
     if cfg.get("track") == "hand_IKNet":  # IKNet runs when its checkpoint and a hand model exist (recorded as cfg["use_iknet"])
         from models.iknet import resolve_use_iknet
         resolve_use_iknet(cfg)

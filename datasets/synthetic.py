@@ -81,8 +81,8 @@ class SyntheticIKFrames(Dataset):
     def __init__(self, cfg, length: int, base_seed: int = 0, pose_range: float = 0.5):
         self.hand = cfg.get("hand_model")
         if self.hand is None or isinstance(self.hand, str):
-            from models.hand_model import SyntheticLBSHand
-            self.hand = SyntheticLBSHand(num_betas=10 if self.hand == "synthetic_shaped" else 0)
+            from models.hand_model import named_hand_model
+            self.hand = named_hand_model(self.hand or "synthetic")
         self.len, self.seed, self.pose_range = length, base_seed, pose_range
         self.jitter = cfg["hand_jitter_cfg"]["rand_scale"]
 

@@ -24,10 +24,21 @@
 // their own argument and the batched kernels with a Frame built from the batch's shared fields and the problem's record
 // (pn2x_hand_pose_problem, a device array read at a workgroup-uniform address).  The eval grid's y and the update grid's x is
 // the problem; a problem that is not active returns before it reads any of its record's pointers.  No workgroup waits for another.
+//
+// hand_pose_offsets_kernel / hand_pose_mano_eval_kernel (pn2x_hand_pose_mano_*).  A hand with MANO's structure (skinning_tables'
+// optional entries): per iteration a pre-pass builds every candidate's 135 pose features vec(R_b - I) -- the skeleton phase's
+// own angle and Rodrigues functions -- and multiplies them with the packed pose blend shapes on the fp32 matrix cores into
+// offsets (P, ceil16(3 V)); the MANO instantiation of hand_pose_eval_block (template <.., bool MANO>, if constexpr: the plain
+// instantiations are the code they were) adds a vertex's offset to its staged v_rest - j_k, takes the fingertip keypoints from
+// skinned vertices (the owner lane leaves the position in the tip joint's unused LDS slot; the keypoint terms run after the
+// vertex loop), and centres on the root.  The update kernel is shared.
 #include <hip/hip_fp16.h>
 
 #include <cstring>
 
+#include <cstdint>
+
+#include "mfma_rows.h"
 #include "pn2_common.h"
 #include "sdf_device.h"
 #include "../../include/pn2_ext.h"
@@ -59,6 +70,14 @@ struct Frame {
     float fx, fy, cx, cy;
     float w_sil, w_pen, w_vis, w_invis, w_tmp, w_attr;
     float *terms, *out_verts, *out_kp;
+};
+
+// What the MANO instantiation reads beyond Frame (a kernel argument of its own: the plain kernels' arguments stay as they are).
+struct ManoExtra {
+    const float *offsets;    // (P, ldo): candidate-major pose-blend offsets, 3 v + coordinate
+    const float *pose_mean;  // (45)
+    const int *kp_vertex;    // (21): >= 0 = the keypoint is a skinned vertex (skin_pack bits 25..29 of that vertex name the joint)
+    int ldo, centre;
 };
 
 inline size_t eval_lds_bytes(int v, int k) { return (size_t)v * k * sizeof(float4) + (size_t)v * sizeof(int); }
@@ -98,8 +117,40 @@ __device__ __forceinline__ void rodrigues(float ax, float ay, float az, float *R
     R[6] = s * -ky + oc * (kx * kz);           R[7] = s * kx + oc * (ky * kz);             R[8] = 1.0f + oc * (-(ky * ky) - kx * kx);
 }
 
-template <bool F16>
-__device__ __forceinline__ void hand_pose_eval_block(const Frame A) {
+// a joint's angles: curr_theta + (coefficients @ comps[:10]) * theta_scale (get_kp_from_delta), for a MANO hand with the mean
+// pose added as the model's forward() adds it
+template <bool MANO>
+__device__ __forceinline__ void joint_angles(const float *sp, const float (&cm)[NC][3], const float *cth, const float *pmean,
+                                             float theta_scale, float *th) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        float acc = sp[7] * cm[0][a];
+#pragma unroll
+        for (int cc = 1; cc < NC; ++cc) acc = fmaf(sp[7 + cc], cm[cc][a], acc);
+        if constexpr (MANO) th[a] = pmean[a] + (cth[a] + acc * theta_scale);
+        else th[a] = cth[a] + acc * theta_scale;
+    }
+}
+
+// keypoint terms (:236-240, :259-262): lane j's distance to pred_kp / last_frame_kp, three wave sums
+__device__ __forceinline__ void keypoint_terms(const Frame &A, int c, int j, bool is_joint, float kx, float ky, float kz,
+                                               const float *pred, const float *last, float visf, float &vis_sum, float &inv_sum,
+                                               float &tmp_sum) {
+    if (A.out_kp && is_joint) {
+        float *o = A.out_kp + ((size_t)c * NJ + j) * 3;
+        o[0] = kx; o[1] = ky; o[2] = kz;
+    }
+    float dx = kx - pred[0], dy = ky - pred[1], dz = kz - pred[2];
+    const float err = sqrtf(dx * dx + dy * dy + dz * dz);
+    dx = kx - last[0]; dy = ky - last[1]; dz = kz - last[2];
+    const float terr = sqrtf(dx * dx + dy * dy + dz * dz);
+    vis_sum = wave_sum_xor(is_joint ? err * visf : 0.f);
+    inv_sum = wave_sum_xor(is_joint ? err * (1.f - visf) : 0.f);
+    tmp_sum = wave_sum_xor(is_joint ? terr : 0.f);
+}
+
+template <bool F16, bool MANO>
+__device__ __forceinline__ void hand_pose_eval_block(const Frame A, const ManoExtra M) {
     extern __shared__ float4 dyn[];
     __shared__ float4 skel[4][NJ * 3];  // per wave and joint: R (9, row-major), t (3)
     const int V = A.V, K = A.K, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -133,13 +184,16 @@ __device__ __forceinline__ void hand_pose_eval_block(const Frame A) {
     int maxdepth = depth;
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) maxdepth = max(maxdepth, __shfl_xor(maxdepth, m, 64));
-    float off[3], pred[3], last[3] = {0.f, 0.f, 0.f}, cth[3] = {0.f, 0.f, 0.f}, cm[NC][3];
+    float off[3], pred[3], last[3] = {0.f, 0.f, 0.f}, cth[3] = {0.f, 0.f, 0.f}, pmean[3] = {0.f, 0.f, 0.f}, cm[NC][3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         off[a] = A.rest_j[3 * j + a] - A.rest_j[3 * pa + a];
         pred[a] = A.pred_kp[3 * j + a];
         if (A.last_kp) last[a] = A.last_kp[3 * j + a];
         if (blk >= 0) cth[a] = A.state[S_THETA + 3 * blk + a];
+        if constexpr (MANO) {
+            if (blk >= 0) pmean[a] = M.pose_mean[3 * blk + a];
+        }
 #pragma unroll
         for (int c = 0; c < NC; ++c) cm[c][a] = blk >= 0 ? A.comps[c * NPOSE + 3 * blk + a] : 0.f;
     }
@@ -147,6 +201,13 @@ __device__ __forceinline__ void hand_pose_eval_block(const Frame A) {
     const unsigned long long vis_bits = __ballot(is_joint && A.vis[j]);
     const int nvis = __popcll(vis_bits), ninv = NJ - nvis;
     const float root[3] = {A.rest_j[0], A.rest_j[1], A.rest_j[2]};
+    bool kp_from_vertex = false;  // MANO: this lane's keypoint is a skinned vertex (a fingertip)
+    float cen[3] = {0.f, 0.f, 0.f};  // MANO: what is subtracted from vertices and keypoints before the translation
+    if constexpr (MANO) {
+        kp_from_vertex = is_joint && M.kp_vertex[j] >= 0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) cen[k] = M.centre ? root[k] : 0.f;
+    }
 
     float R0[9], t0[3], search[ND], oR[9], ot[3];
 #pragma unroll
@@ -176,13 +237,7 @@ __device__ __forceinline__ void hand_pose_eval_block(const Frame A) {
 
         // ---- skeleton -----------------------------------------------------------------------------------------------------------
         float th[3], Rl[9], R[9], t[3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            float acc = sp[7] * cm[0][a];
-#pragma unroll
-            for (int cc = 1; cc < NC; ++cc) acc = fmaf(sp[7 + cc], cm[cc][a], acc);
-            th[a] = cth[a] + acc * A.theta_scale;
-        }
+        joint_angles<MANO>(sp, cm, cth, pmean, A.theta_scale, th);
         rodrigues(th[0], th[1], th[2], Rl);
 #pragma unroll
         for (int k = 0; k < 9; ++k) R[k] = Rg[k];
@@ -213,19 +268,10 @@ __device__ __forceinline__ void hand_pose_eval_block(const Frame A) {
         }
         __builtin_amdgcn_wave_barrier();
 
-        // ---- keypoint terms (:236-240, :259-262) -------------------------------------------------------------------------------
-        const float kx = t[0] + tr[0], ky = t[1] + tr[1], kz = t[2] + tr[2];
-        if (A.out_kp && is_joint) {
-            float *o = A.out_kp + ((size_t)c * NJ + j) * 3;
-            o[0] = kx; o[1] = ky; o[2] = kz;
-        }
-        float dx = kx - pred[0], dy = ky - pred[1], dz = kz - pred[2];
-        const float err = sqrtf(dx * dx + dy * dy + dz * dz);
-        dx = kx - last[0]; dy = ky - last[1]; dz = kz - last[2];
-        const float terr = sqrtf(dx * dx + dy * dy + dz * dz);
-        const float vis_sum = wave_sum_xor(is_joint ? err * visf : 0.f);
-        const float inv_sum = wave_sum_xor(is_joint ? err * (1.f - visf) : 0.f);
-        const float tmp_sum = wave_sum_xor(is_joint ? terr : 0.f);
+        // ---- keypoint terms (a MANO hand's fingertips are skinned vertices: after the vertex loop) ------------------------------
+        float vis_sum, inv_sum, tmp_sum;
+        if constexpr (!MANO)
+            keypoint_terms(A, c, j, is_joint, t[0] + tr[0], t[1] + tr[1], t[2] + tr[2], pred, last, visf, vis_sum, inv_sum, tmp_sum);
 
         // ---- vertices ------------------------------------------------------------------------------------------------------------
         float pen = 0.f, fmin5[5];
@@ -242,10 +288,18 @@ __device__ __forceinline__ void hand_pose_eval_block(const Frame A) {
                 const int p = pk[vv];
                 bits[u] = p >> 20;
                 float x = 0.f, y = 0.f, z = 0.f;
+                float bx = 0.f, by = 0.f, bz = 0.f;  // MANO: the candidate's pose-blend offset of this vertex
+                if constexpr (MANO) {
+                    const float *b = M.offsets + (size_t)c * M.ldo + 3 * vv;
+                    bx = b[0]; by = b[1]; bz = b[2];
+                }
 #pragma unroll
                 for (int k = 0; k < MAXK; ++k)
                     if (k < K) {
-                        const float4 e = tab[k * V + vv];
+                        float4 e = tab[k * V + vv];
+                        if constexpr (MANO) {
+                            e.x += bx; e.y += by; e.z += bz;
+                        }
                         const int jn = min((p >> (5 * k)) & 31, NJ - 1);
                         const float4 a = sk[3 * jn], b = sk[3 * jn + 1], d = sk[3 * jn + 2];
                         const float qx = fmaf(a.z, e.z, fmaf(a.y, e.y, a.x * e.x)) + d.y;
@@ -255,7 +309,13 @@ __device__ __forceinline__ void hand_pose_eval_block(const Frame A) {
                         y = k == 0 ? qy * e.w : fmaf(qy, e.w, y);
                         z = k == 0 ? qz * e.w : fmaf(qz, e.w, z);
                     }
-                x += tr[0]; y += tr[1]; z += tr[2];
+                if constexpr (MANO) {
+                    x = (x - cen[0]) + tr[0]; y = (y - cen[1]) + tr[1]; z = (z - cen[2]) + tr[2];
+                    const int kj = min((p >> 25) & 31, NJ - 1);  // the keypoint this vertex is (0: none): its unused LDS slot
+                    if (kj != 0 && v0 + 64 * u < V) sk[3 * kj + 2] = make_float4(0.f, x, y, z);
+                } else {
+                    x += tr[0]; y += tr[1]; z += tr[2];
+                }
                 if (A.out_verts && v0 + 64 * u < V) {
                     float *o = A.out_verts + ((size_t)c * V + vv) * 3;
                     o[0] = x; o[1] = y; o[2] = z;
@@ -282,6 +342,13 @@ __device__ __forceinline__ void hand_pose_eval_block(const Frame A) {
                     if ((bits[u] >> f) & 1) fmin5[f] = fminf(fmin5[f], tip);
                 count += bg[u] != 0;
             }
+        }
+        if constexpr (MANO) {
+            __builtin_amdgcn_wave_barrier();  // the fingertip slots are written
+            const float4 d = sk[3 * j + 2];
+            keypoint_terms(A, c, j, is_joint, kp_from_vertex ? d.y : (t[0] - cen[0]) + tr[0],
+                           kp_from_vertex ? d.z : (t[1] - cen[1]) + tr[1], kp_from_vertex ? d.w : (t[2] - cen[2]) + tr[2], pred, last,
+                           visf, vis_sum, inv_sum, tmp_sum);
         }
 #pragma unroll
         for (int m = 32; m >= 1; m >>= 1) {
@@ -313,7 +380,80 @@ __device__ __forceinline__ void hand_pose_eval_block(const Frame A) {
 
 template <bool F16>
 __global__ void __launch_bounds__(256) hand_pose_eval_kernel(const Frame A) {
-    hand_pose_eval_block<F16>(A);
+    hand_pose_eval_block<F16, false>(A, ManoExtra{});
+}
+
+template <bool F16>
+__global__ void __launch_bounds__(256) hand_pose_mano_eval_kernel(const Frame A, const ManoExtra M) {
+    hand_pose_eval_block<F16, true>(A, M);
+}
+
+// offsets (P, ldo) = features (P, 136) . posedirs^T: pd (ldo, 136) row-major, row 3 v + coordinate, column 135 and the rows
+// from 3 V on zero.  A workgroup builds the features of OCT candidates in LDS -- thread per (candidate, pose block): the block's
+// angles by joint_angles / rodrigues as the skeleton phase forms them, minus the identity -- and its four waves take 16-row
+// tiles of pd (blockIdx.y-strided): the tile's 136 columns in registers, one v_mfma_f32_16x16x4_f32 per 4 columns against each
+// of the four 16-candidate groups, a lane's four consecutive outputs as one 16-byte store.  In k-group g a lane supplies
+// columns 16 g + 4 (lane / 16) + s of both operands (one 16-byte load each); the last group is half as wide.
+constexpr int NF = 9 * (NPOSE / 3), KP = NF + 1, OCT = 64;
+static_assert(KP % 8 == 0 && KP % 16 == 8, "eight full k-groups of 16 and one of 8");
+
+__global__ void __launch_bounds__(256) hand_pose_offsets_kernel(int P, int ntiles, const float *__restrict__ pd,
+                                                                const float *__restrict__ pose_mean, const float *__restrict__ comps,
+                                                                float theta_scale, const float *__restrict__ pre,
+                                                                const float *__restrict__ state, float *__restrict__ out) {
+    using mrows::f32x4;
+    __shared__ float4 feat4[OCT * KP / 4];
+    float *feat = reinterpret_cast<float *>(feat4);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c0 = blockIdx.x * OCT;
+    float search[ND];
+#pragma unroll
+    for (int k = 0; k < ND; ++k) search[k] = state[S_SEARCH + k];
+    for (int i = tid; i < OCT * (NPOSE / 3); i += 256) {
+        const int cl = i / (NPOSE / 3), b = i - cl * (NPOSE / 3), c = c0 + cl;
+        float R[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};  // a row past the end: zero features
+        if (c < P) {
+            float sp[1 + ND], cm[NC][3], cth[3], pmean[3], th[3];
+            candidate_sample(pre, c, search, sp);
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                cth[a] = state[S_THETA + 3 * b + a];
+                pmean[a] = pose_mean[3 * b + a];
+#pragma unroll
+                for (int cc = 0; cc < NC; ++cc) cm[cc][a] = comps[cc * NPOSE + 3 * b + a];
+            }
+            joint_angles<true>(sp, cm, cth, pmean, theta_scale, th);
+            rodrigues(th[0], th[1], th[2], R);
+        }
+#pragma unroll
+        for (int k = 0; k < 9; ++k) feat[cl * KP + 9 * b + k] = R[k] - ((k & 3) == 0 ? 1.f : 0.f);
+    }
+    if (tid < OCT) feat[tid * KP + NF] = 0.f;
+    __syncthreads();
+
+    const int r = lane & 15, q = lane >> 4;
+    for (int nt = blockIdx.y * 4 + wave; nt < ntiles; nt += gridDim.y * 4) {
+        const float *arow = pd + (size_t)(16 * nt + r) * KP;
+        f32x4 a[KP / 16];
+#pragma unroll
+        for (int g = 0; g < KP / 16; ++g) a[g] = *reinterpret_cast<const f32x4 *>(arow + 16 * g + 4 * q);
+        const float2 a8 = *reinterpret_cast<const float2 *>(arow + 16 * (KP / 16) + 2 * q);
+#pragma unroll
+        for (int mt = 0; mt < OCT / 16; ++mt) {
+            const float *xr = feat + (16 * mt + r) * KP;
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int g = 0; g < KP / 16; ++g) {
+                const f32x4 x = *reinterpret_cast<const f32x4 *>(xr + 16 * g + 4 * q);
+#pragma unroll
+                for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[g][s], x[s], acc, 0, 0, 0);
+            }
+            const float2 x8 = *reinterpret_cast<const float2 *>(xr + 16 * (KP / 16) + 2 * q);
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a8.x, x8.x, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a8.y, x8.y, acc, 0, 0, 0);
+            const int cand = c0 + 16 * mt + r;
+            if (cand < P) *reinterpret_cast<f32x4 *>(out + (size_t)cand * (16 * ntiles) + 16 * nt + 4 * q) = acc;
+        }
+    }
 }
 
 // a record is read through the constant address space: nothing writes the table while a kernel that reads it runs, and a
@@ -334,7 +474,7 @@ __global__ void __launch_bounds__(256) hand_pose_eval_batch_kernel(const Batch B
     A.rest_j = r->rest_joints; A.rest_v = r->rest_verts; A.state = r->state; A.pred_kp = r->pred_kp; A.last_kp = r->last_kp;
     A.vis = r->vis_mask; A.obj_r = r->obj_r; A.obj_t = r->obj_t; A.vol = r->vol; A.mask = r->mask; A.h = r->h; A.w = r->w;
     A.fx = r->fx; A.fy = r->fy; A.cx = r->cx; A.cy = r->cy; A.terms = r->work;
-    hand_pose_eval_block<F16>(A);
+    hand_pose_eval_block<F16, false>(A, ManoExtra{});
 }
 
 __global__ void __launch_bounds__(256) hand_pose_energy_kernel(int P, const float *__restrict__ terms, float *__restrict__ energy) {
@@ -558,6 +698,84 @@ extern "C" int pn2x_hand_pose_opt(HAND_POSE_MODEL_PARAMS, int iterations, double
     hipStream_t st = (hipStream_t)stream;
     for (int it = 0; it < iterations; ++it) {
         eval_launch(A, vol_f16, st);
+        hipLaunchKernelGGL(hand_pose_update_kernel, dim3(1), dim3(UT), 0, st, p, pre, work, comps, theta_scale,
+                           (float)scaling_coefficient2, (float)beta, (float)(1.0 - beta), state,
+                           trace ? trace + (size_t)it * (3 + ND) : nullptr);
+    }
+    return check_launch();
+}
+
+// ---- the MANO-structured hand ---------------------------------------------------------------------------------------------------
+static inline int offsets_ld(int v) { return (3 * v + 15) / 16 * 16; }
+
+extern "C" int pn2x_hand_pose_mano_supported(int p, int v, int j, int k, int d_pose, int res) {
+    return pn2x_hand_pose_opt_supported(p, v, j, k, d_pose, res);
+}
+
+extern "C" long pn2x_hand_pose_mano_work_floats(int p, int v) {
+    return (p < 0 || v < 0) ? (long)PN2_EINVAL : (long)p * offsets_ld(v);
+}
+
+static int fill_mano(ManoExtra &M, const Frame &A, const float *posedirs, const float *pose_mean, const int *kp_vertex,
+                     int centre_root, float *offsets) {
+    if (centre_root != 0 && centre_root != 1) return PN2_EINVAL;
+    if (!posedirs || !pose_mean || !kp_vertex || !offsets) return PN2_ENULL;
+    if (((uintptr_t)posedirs & 15) || ((uintptr_t)offsets & 15)) return PN2_EINVAL;  // 16-byte loads and stores
+    M.offsets = offsets; M.pose_mean = pose_mean; M.kp_vertex = kp_vertex; M.ldo = offsets_ld(A.V); M.centre = centre_root;
+    return PN2_OK;
+}
+
+// one iteration's pre-pass and evaluation
+static void mano_eval_launch(const Frame &A, const ManoExtra &M, const float *posedirs, float *offsets, int f16, hipStream_t st) {
+    static PerDeviceOnce raised;
+    if (raised.first_use()) {
+        (void)hipFuncSetAttribute((const void *)hand_pose_mano_eval_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)eval_lds_bytes(MAXV, MAXK));
+        (void)hipFuncSetAttribute((const void *)hand_pose_mano_eval_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)eval_lds_bytes(MAXV, MAXK));
+    }
+    // pre-pass: x = groups of OCT candidates, y = as many strides over the 16-row tiles as cover the compute units three times
+    const int ntiles = M.ldo / 16, gx = (A.P + OCT - 1) / OCT, cover = 3 * num_compute_units() / gx, most = (ntiles + 3) / 4;
+    const int gy = cover < 1 ? 1 : (cover > most ? most : cover);
+    hipLaunchKernelGGL(hand_pose_offsets_kernel, dim3(gx, gy), dim3(256), 0, st, A.P, ntiles, posedirs, M.pose_mean, A.comps,
+                       A.theta_scale, A.pre, A.state, offsets);
+    const int wgs = (A.P + 3) / 4, cap = 3 * num_compute_units(), rounds = (wgs + cap - 1) / cap, grid = (wgs + rounds - 1) / rounds;
+    if (f16) hipLaunchKernelGGL(hand_pose_mano_eval_kernel<true>, dim3(grid), dim3(256), eval_lds_bytes(A.V, A.K), st, A, M);
+    else hipLaunchKernelGGL(hand_pose_mano_eval_kernel<false>, dim3(grid), dim3(256), eval_lds_bytes(A.V, A.K), st, A, M);
+}
+
+extern "C" int pn2x_hand_pose_mano_energy(HAND_POSE_MODEL_PARAMS, const float *posedirs, const float *pose_mean, const int *kp_vertex,
+                                          int centre_root, const float *state, float *work, float *offsets, float *energy,
+                                          float *out_verts, float *out_kp, void *stream) {
+    Frame A;
+    ManoExtra M;
+    int rc = fill_frame(A, HAND_POSE_MODEL_ARGS);
+    if (rc != PN2_OK) return rc;
+    if (!state || !work || !energy) return PN2_ENULL;
+    if ((rc = fill_mano(M, A, posedirs, pose_mean, kp_vertex, centre_root, offsets)) != PN2_OK) return rc;
+    A.state = state; A.terms = work; A.out_verts = out_verts; A.out_kp = out_kp;
+    hipStream_t st = (hipStream_t)stream;
+    mano_eval_launch(A, M, posedirs, offsets, vol_f16, st);
+    hipLaunchKernelGGL(hand_pose_energy_kernel, dim3((p + 255) / 256), dim3(256), 0, st, p, work, energy);
+    return check_launch();
+}
+
+extern "C" int pn2x_hand_pose_mano_opt(HAND_POSE_MODEL_PARAMS, const float *posedirs, const float *pose_mean, const int *kp_vertex,
+                                       int centre_root, int iterations, double scaling_coefficient2, double beta, float *state,
+                                       float *work, float *offsets, float *trace, void *stream) {
+    Frame A;
+    ManoExtra M;
+    int rc = fill_frame(A, HAND_POSE_MODEL_ARGS);
+    if (rc != PN2_OK) return rc;
+    if (iterations < 0) return PN2_EINVAL;
+    if (iterations > 4096) return PN2_ERANGE;
+    if (iterations == 0) return PN2_OK;
+    if (!state || !work) return PN2_ENULL;
+    if ((rc = fill_mano(M, A, posedirs, pose_mean, kp_vertex, centre_root, offsets)) != PN2_OK) return rc;
+    A.state = state; A.terms = work;
+    hipStream_t st = (hipStream_t)stream;
+    for (int it = 0; it < iterations; ++it) {
+        mano_eval_launch(A, M, posedirs, offsets, vol_f16, st);
         hipLaunchKernelGGL(hand_pose_update_kernel, dim3(1), dim3(UT), 0, st, p, pre, work, comps, theta_scale,
                            (float)scaling_coefficient2, (float)beta, (float)(1.0 - beta), state,
                            trace ? trace + (size_t)it * (3 + ND) : nullptr);

@@ -1067,9 +1067,20 @@ _lib.pn2x_hand_pose_energy.argtypes = _HAND_POSE_COMMON + [_vp] * 6
 _lib.pn2x_hand_pose_energy.restype = _ci
 _lib.pn2x_hand_pose_opt.argtypes = _HAND_POSE_COMMON + [_ci, _cd, _cd] + [_vp] * 4
 _lib.pn2x_hand_pose_opt.restype = _ci
+_lib.pn2x_hand_pose_mano_supported.argtypes = [_ci] * 6
+_lib.pn2x_hand_pose_mano_supported.restype = _ci
+_lib.pn2x_hand_pose_mano_work_floats.argtypes = [_ci, _ci]
+_lib.pn2x_hand_pose_mano_work_floats.restype = _cl
+_lib.pn2x_hand_pose_mano_energy.argtypes = _HAND_POSE_COMMON + [_vp] * 3 + [_ci] + [_vp] * 7
+_lib.pn2x_hand_pose_mano_energy.restype = _ci
+_lib.pn2x_hand_pose_mano_opt.argtypes = _HAND_POSE_COMMON + [_vp] * 3 + [_ci] + [_ci, _cd, _cd] + [_vp] * 5
+_lib.pn2x_hand_pose_mano_opt.restype = _ci
 HAND_POSE_STATE_FLOATS = 90   # curr_r (9), curr_t (3), curr_theta (45), search (16), previous search (16), previous success
 HAND_POSE_TRACE_FLOATS = 19   # E[0], mean_E, success, search after the update (16)
 HAND_POSE_WEIGHTS = ("sil_loss", "penetrate_sum_loss", "vis_regu_loss", "invis_regu_loss", "temporal_smooth", "attraction_loss")
+
+
+HAND_POSE_MANO_ENTRIES = ("posedirs", "pose_mean", "kp_vertex", "centre_root")  # skinning_tables()' optional entries
 
 
 def hand_pose_opt_supported(p: int, v: int, j: int, k: int, d_pose: int = 10, res: int = 151) -> bool:
@@ -1079,7 +1090,11 @@ def hand_pose_opt_supported(p: int, v: int, j: int, k: int, d_pose: int = 10, re
 def hand_pose_model(tables: dict, device) -> dict:
     """HandModel.skinning_tables() as the device arrays the hand-pose kernels read (built once per model and device):
     int32 parents / pose_block, float32 rest and shape tables, skin_w, comps, and skin_pack = the K joint indices of a vertex
-    (5 bits each) with, from bit 20, the tip regions (fingers 0..4 of tips / finger_offsets) the vertex belongs to."""
+    (5 bits each) with, from bit 20, the tip regions (fingers 0..4 of tips / finger_offsets) the vertex belongs to.
+    Tables with a MANO entry (posedirs, pose_mean, kp_vertex, centre_root) set m["mano"] and add what the pn2x_hand_pose_mano_*
+    kernels read: posedirs_pack (ceil16(3 V), 136) = posedirs as rows 3 v + coordinate, zero-padded; pose_mean (45); kp_vertex
+    (J) int32; centre_root 0 / 1; and in skin_pack bits 25..29 of a keypoint vertex the table joint it is (mano_ok: no vertex
+    serves two keypoints).  Such a model goes to hand_pose_mano_energy / hand_pose_mano_opt only."""
     f32, i32 = torch.float32, torch.int32
     idx = tables["skin_idx"].long()
     V, K = idx.shape
@@ -1094,6 +1109,24 @@ def hand_pose_model(tables: dict, device) -> dict:
          "rest_joints": tables["rest_joints"].to(device, f32).contiguous(), "rest_verts": tables["rest_verts"].to(device, f32).contiguous(),
          "skin_pack": pack.to(device, i32).contiguous(), "skin_w": tables["skin_w"].to(device, f32).contiguous(),
          "comps": tables["comps"].to(device, f32).contiguous(), "fingers_ok": all(offs[f + 1] > offs[f] for f in range(5))}
+    m["mano"] = any(k in tables for k in HAND_POSE_MANO_ENTRIES)
+    if m["mano"]:
+        J = m["J"]
+        kpv = tables["kp_vertex"].long() if "kp_vertex" in tables else torch.full((J,), -1, dtype=torch.long)
+        owners = [(j, int(v)) for j, v in enumerate(kpv) if int(v) >= 0]
+        m["mano_ok"] = len({v for _, v in owners}) == len(owners) and all(0 < j < 32 and v < V for j, v in owners)
+        if m["mano_ok"]:
+            for j, v in owners:
+                pack[v] |= j << 25
+            m["skin_pack"] = pack.to(device, i32).contiguous()
+        rows = (3 * V + 15) // 16 * 16
+        pd = torch.zeros(rows, 136, dtype=f32)
+        if "posedirs" in tables:
+            pd[:3 * V, :135] = tables["posedirs"].to(f32).reshape(3 * V, 135)
+        m["posedirs_pack"] = pd.to(device).contiguous()
+        m["pose_mean"] = (tables["pose_mean"].to(f32) if "pose_mean" in tables else torch.zeros(45)).to(device).contiguous()
+        m["kp_vertex"] = kpv.to(device, i32).contiguous()
+        m["centre_root"] = 1 if tables.get("centre_root", False) else 0
     if "shape_joints" in tables:
         D = tables["shape_joints"].shape[0]
         m["shape_joints"] = tables["shape_joints"].to(device, f32).reshape(D, -1).contiguous()
@@ -1110,8 +1143,12 @@ def hand_pose_rest(model: dict, beta: torch.Tensor = None):
             (model["rest_verts"] + (b @ model["shape_verts"]).view(-1, 3)).contiguous())
 
 
-def _hand_pose_args(model, rest, theta_scale, pre, pred_kp, last_kp, vis_mask, obj_r, obj_t, volume, voxel_scale, mask, proj, weights):
+def _hand_pose_args(model, rest, theta_scale, pre, pred_kp, last_kp, vis_mask, obj_r, obj_t, volume, voxel_scale, mask, proj, weights,
+                    mano: bool = False):
     f32, u8 = torch.float32, torch.uint8
+    if bool(model.get("mano", False)) != mano:  # the plain kernels would drop the model's MANO terms without a word
+        raise ValueError("hand_pose: a model with MANO entries goes to hand_pose_mano_energy / hand_pose_mano_opt, a plain one to "
+                         "hand_pose_energy / hand_pose_opt / hand_pose_opt_batch")
     V, K, J = model["V"], model["K"], model["J"]
     if pre.dim() != 2 or pre.shape[1] != 16:
         raise ValueError(f"hand_pose: pre {tuple(pre.shape)} is not (P, 16)")
@@ -1168,6 +1205,70 @@ def hand_pose_opt(model, rest, theta_scale, pre, state, pred_kp, last_kp, vis_ma
         _native._check(_native._call(_lib.pn2x_hand_pose_opt, "hand_pose_opt", None, *args, int(iterations), float(scaling_coefficient2),
                                      float(beta), _native._ptr(state, "state", f32, HAND_POSE_STATE_FLOATS), work.data_ptr(),
                                      None if tr is None else tr.data_ptr(), _native._stream(pre)), "hand_pose_opt")
+    return tr
+
+
+# ---- a hand with MANO's structure (include/pn2_ext.h: pn2x_hand_pose_mano_energy / pn2x_hand_pose_mano_opt) ----------------------
+def hand_pose_mano_supported(p: int, v: int, j: int, k: int, d_pose: int = 10, res: int = 151) -> bool:
+    return bool(_lib.pn2x_hand_pose_mano_supported(int(p), int(v), int(j), int(k), int(d_pose), int(res)))
+
+
+def hand_pose_mano_workspace(p: int, v: int, device) -> torch.Tensor:
+    """The pose-blend offsets of p candidates of a v-vertex hand (pn2x_hand_pose_mano_work_floats floats), to be reused."""
+    return torch.empty(int(_lib.pn2x_hand_pose_mano_work_floats(int(p), int(v))), dtype=torch.float32, device=device)
+
+
+def _hand_pose_mano_extra(model, P, offsets, posedirs):
+    if not model.get("mano_ok", False):
+        raise ValueError("hand_pose_mano: one vertex serves two keypoints (kp_vertex)")
+    V = model["V"]
+    n = int(_lib.pn2x_hand_pose_mano_work_floats(P, V))
+    if offsets is None:
+        offsets = torch.empty(n, dtype=torch.float32, device=model["rest_joints"].device)
+    pd = model["posedirs_pack"] if posedirs is None else posedirs
+    return offsets, [_native._ptr(pd, "posedirs", torch.float32, (3 * V + 15) // 16 * 16 * 136),
+                     _native._ptr(model["pose_mean"], "pose_mean", torch.float32, 45),
+                     _native._ptr(model["kp_vertex"], "kp_vertex", torch.int32, model["J"]), int(model["centre_root"])], \
+        _native._ptr(offsets, "offsets", torch.float32, n)
+
+
+def hand_pose_mano_energy(model, rest, theta_scale, pre, state, pred_kp, last_kp, vis_mask, obj_r, obj_t, volume, voxel_scale, mask, proj,
+                          weights, with_geometry: bool = False, offsets: torch.Tensor = None, posedirs: torch.Tensor = None):
+    """hand_pose_energy for a model with MANO entries (pn2x_hand_pose_mano_energy: the pose-offset pre-pass, then the MANO
+    evaluation).  offsets: hand_pose_mano_workspace(P, V) to reuse (else allocated); posedirs: a packed table to use in place
+    of the model's posedirs_pack (tests)."""
+    P, args = _hand_pose_args(model, rest, theta_scale, pre, pred_kp, last_kp, vis_mask, obj_r, obj_t, volume, voxel_scale, mask, proj,
+                              weights, mano=True)
+    f32, dev = torch.float32, pre.device
+    offsets, extra, off_ptr = _hand_pose_mano_extra(model, P, offsets, posedirs)
+    work = torch.empty(int(_lib.pn2x_hand_pose_opt_work_floats(P)), dtype=f32, device=dev)
+    energy = torch.empty(P, dtype=f32, device=dev)
+    verts = torch.empty((P, model["V"], 3), dtype=f32, device=dev) if with_geometry else None
+    kp = torch.empty((P, model["J"], 3), dtype=f32, device=dev) if with_geometry else None
+    with torch.cuda.device(dev):
+        _native._check(_native._call(_lib.pn2x_hand_pose_mano_energy, "hand_pose_mano_energy", None, *args, *extra,
+                                     _native._ptr(state, "state", f32, HAND_POSE_STATE_FLOATS), work.data_ptr(), off_ptr,
+                                     energy.data_ptr(), None if verts is None else verts.data_ptr(),
+                                     None if kp is None else kp.data_ptr(), _native._stream(pre)), "hand_pose_mano_energy")
+    return energy, verts, kp
+
+
+def hand_pose_mano_opt(model, rest, theta_scale, pre, state, pred_kp, last_kp, vis_mask, obj_r, obj_t, volume, voxel_scale, mask, proj,
+                       weights, iterations: int, scaling_coefficient2: float, beta: float, trace: bool = False,
+                       offsets: torch.Tensor = None):
+    """hand_pose_opt for a model with MANO entries (pn2x_hand_pose_mano_opt): `iterations` x (pose-offset pre-pass, MANO
+    evaluation, the shared update); `state` (90,) is updated in place.  -> trace (iterations, 19) or None."""
+    P, args = _hand_pose_args(model, rest, theta_scale, pre, pred_kp, last_kp, vis_mask, obj_r, obj_t, volume, voxel_scale, mask, proj,
+                              weights, mano=True)
+    f32, dev = torch.float32, pre.device
+    offsets, extra, off_ptr = _hand_pose_mano_extra(model, P, offsets, None)
+    work = torch.empty(int(_lib.pn2x_hand_pose_opt_work_floats(P)), dtype=f32, device=dev)
+    tr = torch.empty((int(iterations), HAND_POSE_TRACE_FLOATS), dtype=f32, device=dev) if trace else None
+    with torch.cuda.device(dev):
+        _native._check(_native._call(_lib.pn2x_hand_pose_mano_opt, "hand_pose_mano_opt", None, *args, *extra, int(iterations),
+                                     float(scaling_coefficient2), float(beta), _native._ptr(state, "state", f32, HAND_POSE_STATE_FLOATS),
+                                     work.data_ptr(), off_ptr, None if tr is None else tr.data_ptr(), _native._stream(pre)),
+                       "hand_pose_mano_opt")
     return tr
 
 

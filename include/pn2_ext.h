@@ -460,6 +460,47 @@ int pn2x_hand_pose_opt(int p, int v, int j, int k, const int *parents, const int
                        double beta, float *state, float *work, float *trace, void *stream);
 
 /*
+ * The same two entries for a hand with MANO's structure (HandModel.skinning_tables with its optional entries; the reference's
+ * OurManoLayer.forward, third_party/mano/our_mano.py:218-360).  The arguments of pn2x_hand_pose_energy / pn2x_hand_pose_opt, and:
+ *   posedirs (ceil16(3 v), 136): the pose blend shapes packed for the matrix cores -- row 3 vertex + coordinate, column
+ *     9 b + 3 r + c the weight of (R_b - I)[r][c] of pose block b's own rotation, column 135 and the rows from 3 v on zero;
+ *     16-byte aligned.  v_rest += posedirs . features before the skinning.
+ *   pose_mean (45): added to the joint angles, theta = pose_mean + (curr_theta + (s[6:16] @ comps[:10]) * theta_scale).
+ *   kp_vertex (21) int32: kp_vertex[i] >= 0 makes keypoint i that skinned vertex instead of joint i's position; joint i then has
+ *     pose_block -1, is nobody's parent and no weight names it, and bits 25..29 of that vertex's skin_pack hold i (a vertex
+ *     serves one keypoint at most); -1 = a joint.  kp_vertex[0] is -1.
+ *   centre_root 0 / 1: keypoint 0 (= rest_joints[0]) is subtracted from vertices and keypoints before the translation is added.
+ *   offsets: pn2x_hand_pose_mano_work_floats(p, v) = p * ceil16(3 v) floats of scratch (the candidates' pose-blend offsets),
+ *     16-byte aligned; `work` is pn2x_hand_pose_opt_work_floats(p) as before.
+ * Per iteration: hand_pose_offsets_kernel (every candidate's 135 features by the evaluation's own angle and Rodrigues functions,
+ * times posedirs on v_mfma_f32_16x16x4_f32, into `offsets`), hand_pose_mano_eval_kernel (the evaluation above with the offset
+ * added to every staged v_rest - j_k, fingertip keypoints from vertices, the centring; the terms, their order and rounding as
+ * in the plain kernel) and, for _opt, the same hand_pose_update_kernel.  Deterministic and capturable like the plain entries;
+ * the limits are the same (pn2x_hand_pose_mano_supported).  Errors as the plain entries, and PN2_ENULL for NULL posedirs,
+ * pose_mean, kp_vertex or offsets, PN2_EINVAL for centre_root not 0 / 1 or a misaligned posedirs / offsets.
+ */
+int pn2x_hand_pose_mano_supported(int p, int v, int j, int k, int d_pose, int res);
+long pn2x_hand_pose_mano_work_floats(int p, int v);
+int pn2x_hand_pose_mano_energy(int p, int v, int j, int k, const int *parents, const int *pose_block, const float *rest_joints,
+                               const float *rest_verts, const int *skin_pack, const float *skin_w, const float *comps,
+                               float theta_scale, const float *pre, const float *pred_kp, const float *last_kp,
+                               const unsigned char *vis_mask, const float *obj_r, const float *obj_t, const void *vol, int vol_f16,
+                               int res, float voxel_scale, const unsigned char *mask, int h, int w, float fx, float fy, float cx,
+                               float cy, float w_sil, float w_pen, float w_vis, float w_invis, float w_temporal, float w_attr,
+                               const float *posedirs, const float *pose_mean, const int *kp_vertex, int centre_root,
+                               const float *state, float *work, float *offsets, float *energy, float *out_verts, float *out_kp,
+                               void *stream);
+int pn2x_hand_pose_mano_opt(int p, int v, int j, int k, const int *parents, const int *pose_block, const float *rest_joints,
+                            const float *rest_verts, const int *skin_pack, const float *skin_w, const float *comps,
+                            float theta_scale, const float *pre, const float *pred_kp, const float *last_kp,
+                            const unsigned char *vis_mask, const float *obj_r, const float *obj_t, const void *vol, int vol_f16,
+                            int res, float voxel_scale, const unsigned char *mask, int h, int w, float fx, float fy, float cx,
+                            float cy, float w_sil, float w_pen, float w_vis, float w_invis, float w_temporal, float w_attr,
+                            const float *posedirs, const float *pose_mean, const int *kp_vertex, int centre_root, int iterations,
+                            double scaling_coefficient2, double beta, float *state, float *work, float *offsets, float *trace,
+                            void *stream);
+
+/*
  * pn2x_hand_pose_opt for s independent problems (hand sequences that advance one frame together) with one set of launches:
  * per iteration one launch of hand_pose_eval_batch_kernel over a (candidates, problem) grid and one launch of
  * hand_pose_update_batch_kernel with a workgroup per problem.  The kernels run pn2x_hand_pose_opt's device functions, so a

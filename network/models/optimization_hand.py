@@ -234,15 +234,18 @@ class gf_optimize_hand_pose:
             return "a test SDF lookup is injected (sdf_lookup)"
         from hotrack_amd import ext
         m = self._kernel_model()
+        if m["mano"] and not m["mano_ok"]:
+            return "one vertex of the hand model serves two keypoints (kp_vertex)"
+        supported = ext.hand_pose_mano_supported if m["mano"] else ext.hand_pose_opt_supported
         if not (m["fingers_ok"] and self.optimize_dim == 16 and self.mano_layer_right.num_pose == 45 and
-                ext.hand_pose_opt_supported(self.particle_size, m["V"], m["J"], m["K"], self.ncomps, self.volume_size)):
+                supported(self.particle_size, m["V"], m["J"], m["K"], self.ncomps, self.volume_size)):
             return (f"the sizes are outside the kernel's limits (particles {self.particle_size}, vertices {m['V']}, joints {m['J']}, "
                     f"weights per vertex {m['K']}, volume {self.volume_size})")
         return None
 
     def use_kernel(self) -> bool:
         """True when optimize() runs on the device-resident route: `fused` is set (cfg['opt']['fused_pose']), the device is a
-        GPU, the hand model has skinning tables, no test SDF lookup is injected and the sizes are within the kernel's limits.
+        GPU, the hand model has skinning tables (plain ones, or with the MANO entries), no test SDF lookup is injected and the sizes are within the kernel's limits.
         With `fused` set and a condition missing, the reason is logged once and the torch route runs."""
         if not self.fused:
             return False
@@ -268,11 +271,22 @@ class gf_optimize_hand_pose:
                     mask=self.gt_background_mask.to(torch.bool).to(torch.uint8).contiguous(), proj=self.proj, weights=self.energy_weight)
 
     def _optimize_fused(self):
-        """optimize()'s loop as `iteration` x (hand_pose_eval_kernel, hand_pose_update_kernel): no host sync (capturable)."""
+        """optimize()'s loop as `iteration` x (hand_pose_eval_kernel, hand_pose_update_kernel): no host sync (capturable).  A
+        model whose tables carry MANO entries runs the MANO kernels (a pose-offset pre-pass before every evaluation); their
+        offsets workspace is allocated once per (particles, vertices)."""
         from hotrack_amd import ext
         state = self._pack_state(self.initial_scale)
-        self.trace = ext.hand_pose_opt(state=state, iterations=self.iteration, scaling_coefficient2=self.scaling_coefficient2,
-                                       beta=self.beta, trace=self.keep_trace, **self._kernel_frame())
+        frame = self._kernel_frame()
+        kw = dict(state=state, iterations=self.iteration, scaling_coefficient2=self.scaling_coefficient2, beta=self.beta,
+                  trace=self.keep_trace, **frame)
+        m = frame["model"]
+        if m["mano"]:
+            key = (self.particle_size, m["V"])
+            if self.__dict__.get("_mano_work_key") != key:
+                self._mano_work, self._mano_work_key = ext.hand_pose_mano_workspace(*key, self.device), key
+            self.trace = ext.hand_pose_mano_opt(offsets=self._mano_work, **kw)
+        else:
+            self.trace = ext.hand_pose_opt(**kw)
         self.curr_r, self.curr_t, self.curr_theta = state[0:9].view(1, 3, 3), state[9:12].view(1, 3, 1), state[12:57].view(1, 45)
         self.search_size, self.prev_search_size, self.prev_success = state[57:73], state[73:89], state[89] != 0
 
@@ -403,12 +417,20 @@ class gf_optimize_hand_pose:
         sequence), bit-equal per sequence to optimize() on it alone.
         calls: a list of S entries -- the arguments of optimize() as a tuple or as a dict by name, or None for a sequence that sits
         out.  A dict may also carry the sequence's own 'sdf_volume' (and 'voxel_scale'); without one the loaded volume is used.
+        A hand model whose tables carry MANO entries has no batched kernel: it runs optimize() per entry (said once).
         All volumes of a batch share resolution, dtype and voxel_scale.  Shape code, volume, object pose, mask and projection are
         kept per sequence; the hand model's registered shape is what it was before the call.
         -> a list of S (final_kp, theta, rot, trans) tuples, None where the entry was None.
         Without the device-resident route (use_kernel() false) it is optimize() per entry."""
         split = [None if c is None else self._split_call(c) for c in calls]
-        if not self.use_kernel():
+        lockstep = self.use_kernel()
+        if lockstep and self._kernel_model()["mano"]:  # no batched MANO kernel: optimize() per entry (the device-resident one)
+            lockstep = False
+            if not self.__dict__.get("_batch_said"):
+                self._batch_said = True
+                print("[Hand pose optimiser] optimize_batch runs optimize() per sequence: the hand model's tables carry MANO entries "
+                      "(pose blend shapes, vertex fingertips) and the lockstep kernels take plain tables only")
+        if not lockstep:
             out = []
             for sc in split:
                 if sc is not None and sc[1] is not None:

@@ -29,10 +29,12 @@ def add_args(parser):
     # additions of this repo (synthetic runs)
     parser.add_argument("--synthetic_frames", type=int, default=None, help="length of the synthetic train set / sequences")
     parser.add_argument("--max_iters", type=int, default=None, help="stop an epoch after this many iterations (smoke runs)")
-    parser.add_argument("--hand_model", type=str, default=None, choices=["synthetic", "synthetic_shaped"],
+    parser.add_argument("--hand_model", type=str, default=None, choices=["synthetic", "synthetic_shaped", "synthetic_mano"],
                         help="track=hand_IKNet with use_optimization: the hand model of the pose optimiser ('synthetic' = the "
                              "linear-blend-skinning stand-in of models/hand_model.py; 'synthetic_shaped' = the same with 10 shape "
-                             "dimensions, for use_pred_hand_shape; a MANO layer is passed programmatically)")
+                             "dimensions, for use_pred_hand_shape; 'synthetic_mano' = a hand with MANO's structure -- pose blend shapes, mean "
+                             "pose, regressed joints, vertex fingertips, root centring -- and seeded tables; a MANO layer is passed "
+                             "programmatically)")
     parser.add_argument("--hand_particles", type=int, default=None, help="candidate hands per optimiser iteration (reference: 5120)")
     parser.add_argument("--fused_hand_pose", dest="opt/fused_pose", action="store_const", const=True, default=None,
                         help="use_optimization: run the hand-pose particle optimiser on the device-resident route (two kernels per "

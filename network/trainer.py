@@ -74,10 +74,8 @@ class Trainer(nn.Module):
             # (track_network.py:214-217) -- and says so.
             hm = cfg.get("hand_model")
             if isinstance(hm, str):
-                if hm not in ("synthetic", "synthetic_shaped"):
-                    raise ValueError("hand_model: 'synthetic', 'synthetic_shaped' or a models.hand_model.HandModel instance")
-                from models.hand_model import SyntheticLBSHand
-                hm = SyntheticLBSHand(num_betas=10 if hm == "synthetic_shaped" else 0)
+                from models.hand_model import named_hand_model
+                hm = named_hand_model(hm)
                 cfg["hand_model"] = hm  # the synthetic sequences pose the same model
             if resolve_use_iknet(cfg):
                 self.log_string("track=hand_IKNet: HandTrackNet tracking + IKNet (%s; hand model: %s)" % (

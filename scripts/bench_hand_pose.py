@@ -1,7 +1,7 @@
 """Per-frame cost of the hand-pose particle optimiser (gf_optimize_hand_pose.optimize) on the MI355X: the torch route against
 the device-resident route (opt.fused_pose, hotrack_amd/csrc/hand_pose.hip), P = 5120 candidates x 5 iterations.
 
-    python scripts/bench_hand_pose.py [--particles 5120] [--frames 16] [--warmup 3] [--rounds 3]
+    python scripts/bench_hand_pose.py [--particles 5120] [--frames 16] [--warmup 3] [--rounds 3] [--hand_model synthetic_mano]
 
 The synthetic hand-object sequence (datasets/synthetic.SyntheticHandObjectSequences, 151^3 fp16 volume, 640 x 480 silhouette)
 is tracked the way HandTrackModel drives the optimiser: jittered ground-truth keypoints stand in for HandTrackNet, the previous
@@ -9,12 +9,15 @@ optimum and a rigid keypoint fit for IKNet, the result feeds the next frame.  Al
 `rounds` times, alternating: the torch route, the fused route eager, the fused route as a replayed graph -- each `warmup`
 passes over the sequence untimed, then one timed pass with device events around every optimize() call (steady state: no
 first-call costs).  Prints one JSON line: per route the median and the range of the per-optimize time over all rounds, the
-per-round medians, and the largest keypoint difference between the routes.
+per-round medians, and the largest keypoint difference between the routes.  With --hand_model synthetic_mano the hand has
+MANO's structure (SyntheticManoHand: the MANO kernels with their pose-offset pre-pass) and the plain hand is measured beside it
+in the same run, the two models' routes alternating; the line then holds one record per model.
 
 Kernel times, in a run of its own (tracing slows the host):
     rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/hand_pose_trace -o hand_pose -- \\
         python scripts/bench_hand_pose.py --rounds 1 --routes fused
-The stats list hand_pose_eval_kernel<true> and hand_pose_update_kernel, five calls each per optimize()."""
+The stats list hand_pose_eval_kernel<true> and hand_pose_update_kernel, five calls each per optimize() (with --hand_model
+synthetic_mano: hand_pose_offsets_kernel, hand_pose_mano_eval_kernel<true> and hand_pose_update_kernel)."""
 import argparse
 import json
 import os
@@ -103,38 +106,45 @@ def main():
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--rounds", type=int, default=3)
     p.add_argument("--routes", default="torch,fused,fused_graph")
+    p.add_argument("--hand_model", default="synthetic", choices=["synthetic", "synthetic_mano"])
     a = p.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_hand_pose.py needs a GPU")
     from datasets.synthetic import SyntheticHandObjectSequences
-    from models.hand_model import SyntheticLBSHand
-    hm = SyntheticLBSHand()
-    cfg = {"num_points": 512, "hand_jitter_cfg": {"rand_scale": 0.004}, "obj_category": ["bottle"], "hand_model": hm}
-    seq = SyntheticHandObjectSequences(cfg, 1, a.frames)[0]
+    from models.hand_model import named_hand_model
     routes = a.routes.split(",")
-    opts = {"torch": make_optimiser(hm, a.particles, False, seq), "fused": make_optimiser(hm, a.particles, True, seq)}
-    if not opts["fused"].use_kernel():
-        raise SystemExit("bench_hand_pose.py: the fused route is not available")
-    frames = stage(seq, opts["fused"].mano_layer_right)
-    graphs = {}
-    per_round, kps = {r: [] for r in routes}, {}
+    models = {}
+    for name in dict.fromkeys([a.hand_model, "synthetic"]):  # the MANO hand first, the plain hand beside it
+        hm = named_hand_model(name)
+        cfg = {"num_points": 512, "hand_jitter_cfg": {"rand_scale": 0.004}, "obj_category": ["bottle"], "hand_model": hm}
+        seq = SyntheticHandObjectSequences(cfg, 1, a.frames)[0]
+        opts = {"torch": make_optimiser(hm, a.particles, False, seq), "fused": make_optimiser(hm, a.particles, True, seq)}
+        if not opts["fused"].use_kernel():
+            raise SystemExit("bench_hand_pose.py: the fused route is not available")
+        models[name] = dict(opts=opts, frames=stage(seq, opts["fused"].mano_layer_right), graphs={}, per_round={r: [] for r in routes}, kps={})
     with torch.no_grad():
         for _ in range(a.rounds):
             for r in routes:
-                opt, gr = opts["torch" if r == "torch" else "fused"], (graphs if r == "fused_graph" else None)
-                for _ in range(a.warmup):
-                    run_pass(opt, frames, False, gr)
-                t, kps[r] = run_pass(opt, frames, True, gr)
-                per_round[r].append(t)
-    rec = {"particles": a.particles, "iterations": 5, "frames_timed_per_round": a.frames - 1, "rounds": a.rounds}
-    for r in routes:
-        allt = [x for t in per_round[r] for x in t]
-        rec[r] = {"ms_per_optimize_median": round(statistics.median(allt), 4), "min": round(min(allt), 4), "max": round(max(allt), 4),
-                  "round_medians": [round(statistics.median(t), 4) for t in per_round[r]]}
-    if "torch" in kps and "fused" in kps:
-        rec["max_kp_diff_fused_vs_torch_m"] = float(max((x - y).abs().max() for x, y in zip(kps["fused"], kps["torch"])))
-        rec["every_fused_run_beats_every_torch_run"] = max(x for t in per_round["fused"] for x in t) < min(x for t in per_round["torch"] for x in t)
-    print(json.dumps(rec), flush=True)
+                for m in models.values():
+                    opt, gr = m["opts"]["torch" if r == "torch" else "fused"], (m["graphs"] if r == "fused_graph" else None)
+                    for _ in range(a.warmup):
+                        run_pass(opt, m["frames"], False, gr)
+                    t, m["kps"][r] = run_pass(opt, m["frames"], True, gr)
+                    m["per_round"][r].append(t)
+    recs = {}
+    for name, m in models.items():
+        per_round, kps = m["per_round"], m["kps"]
+        rec = {"particles": a.particles, "iterations": 5, "frames_timed_per_round": a.frames - 1, "rounds": a.rounds}
+        for r in routes:
+            allt = [x for t in per_round[r] for x in t]
+            rec[r] = {"ms_per_optimize_median": round(statistics.median(allt), 4), "min": round(min(allt), 4), "max": round(max(allt), 4),
+                      "round_medians": [round(statistics.median(t), 4) for t in per_round[r]]}
+        if "torch" in kps and "fused" in kps:
+            rec["max_kp_diff_fused_vs_torch_m"] = float(max((x - y).abs().max() for x, y in zip(kps["fused"], kps["torch"])))
+            fused_runs = [x for r in routes if r != "torch" for t in per_round[r] for x in t]
+            rec["every_fused_run_beats_every_torch_run"] = max(fused_runs) < min(x for t in per_round["torch"] for x in t)
+        recs[name] = rec
+    print(json.dumps(recs["synthetic"] if a.hand_model == "synthetic" else recs), flush=True)
 
 
 if __name__ == "__main__":
