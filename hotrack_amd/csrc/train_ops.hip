@@ -6,7 +6,7 @@
 // is, a GEMM over all R = B*S*K positions (library GEMM, point-major rows), and everything between two GEMMs is ONE pair
 // of streaming kernels per direction:
 //
-//   forward    bn_stats        per-channel sum / sum of squares over the R rows (fp32 partials, fp64 atomics)
+//   forward    bn_stats        per-channel sum / sum of squares over the R rows (fp32 partials around a pivot, fp64 atomics)
 //              bn_relu_apply   H = relu(gamma * (Y - mean) * invstd + beta); the first workgroup also writes the saved
 //                              mean / invstd, the running-statistics update and num_batches_tracked
 //   backward   bn_relu_bwd_reduce   sum(g), sum(g * xhat)  with  g = dH * [H > 0]
@@ -79,21 +79,68 @@ __device__ __forceinline__ void block_reduce_to_sums(float4 a, float4 b, int Q, 
     }
 }
 
+// The forward statistics (sum y, sum y^2) go through a PIVOT: sum y^2 / R - mean^2 cancels, and with fp32 products and fp32
+// partial sums the cancellation happened at fp32 precision -- a channel with |mean| / std = 100 lost four digits of its variance,
+// one with 1000 six percent of it.  A thread accumulates d = y - p and d^2 around p = the first value it meets in each channel
+// (fp32: d is of the size of the spread, not of the mean), and the reduction converts each thread's partials in fp64,
+//   sum y = n p + sum d,   sum y^2 = sum d^2 + 2 p sum d + n p^2,
+// before they meet the other threads': the record keeps its meaning and layout, and s2 / rows - m^2 cancels in fp64 only.
+// n: the rows this thread accumulated (0: it contributes nothing, whatever its pivot holds).
+__device__ __forceinline__ void block_reduce_pivoted_to_sums(float4 a, float4 b, float4 piv, int n, int Q, int rpp, int C,
+                                                             double *__restrict__ sums) {
+    __shared__ float4 red[3][kTT];
+    __shared__ int cnt[kTT];
+    red[0][threadIdx.x] = a;
+    red[1][threadIdx.x] = b;
+    red[2][threadIdx.x] = piv;
+    cnt[threadIdx.x] = n;
+    __syncthreads();
+    if ((int)threadIdx.x < Q) {
+        double s[4] = {0, 0, 0, 0}, t[4] = {0, 0, 0, 0};
+        for (int r = 0; r < rpp; ++r) {
+            const int l = r * Q + threadIdx.x;
+            const double nn = (double)cnt[l];
+            if (nn == 0.0) continue;
+            const float4 u = red[0][l], v = red[1][l], p = red[2][l];
+            const double sd[4] = {u.x, u.y, u.z, u.w}, sq[4] = {v.x, v.y, v.z, v.w}, pp[4] = {p.x, p.y, p.z, p.w};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                s[i] += nn * pp[i] + sd[i];
+                t[i] += sq[i] + 2.0 * pp[i] * sd[i] + nn * (pp[i] * pp[i]);
+            }
+        }
+        const int c0 = threadIdx.x * 4;
+        double *dst = sums + (size_t)(blockIdx.x % kRep) * 2 * C;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            unsafeAtomicAdd(dst + c0 + i, s[i]);
+            unsafeAtomicAdd(dst + C + c0 + i, t[i]);
+        }
+    }
+}
+
 __global__ void __launch_bounds__(kTT)
 bn_stats_kernel(long rows, int C, const float *__restrict__ Y, int ld, int rows_per_block, double *__restrict__ sums) {
     const int Q = C >> 2, rpp = kTT / Q;
     const int q = threadIdx.x % Q, rr = threadIdx.x / Q;
     const long r0 = (long)blockIdx.x * rows_per_block;
     const long r1 = r0 + rows_per_block < rows ? r0 + rows_per_block : rows;
-    float4 s = make_float4(0, 0, 0, 0), t = s;
-    if (rr < rpp) {
+    float4 s = make_float4(0, 0, 0, 0), t = s, p = s;
+    int n = 0;
+    if (rr < rpp && r0 + rr < r1) {
         long r = r0 + rr;
+        p = *reinterpret_cast<const float4 *>(Y + r * ld + 4 * q);  // this thread's pivot: its first row
+        n = (int)((r1 - r + rpp - 1) / rpp);
         for (; r + 3L * rpp < r1; r += 4L * rpp) {  // four independent 16-byte loads in flight per thread
-            const float *p = Y + r * ld + 4 * q;
-            const float4 v0 = *reinterpret_cast<const float4 *>(p);
-            const float4 v1 = *reinterpret_cast<const float4 *>(p + (long)rpp * ld);
-            const float4 v2 = *reinterpret_cast<const float4 *>(p + 2L * rpp * ld);
-            const float4 v3 = *reinterpret_cast<const float4 *>(p + 3L * rpp * ld);
+            const float *py = Y + r * ld + 4 * q;
+            float4 v0 = *reinterpret_cast<const float4 *>(py);
+            float4 v1 = *reinterpret_cast<const float4 *>(py + (long)rpp * ld);
+            float4 v2 = *reinterpret_cast<const float4 *>(py + 2L * rpp * ld);
+            float4 v3 = *reinterpret_cast<const float4 *>(py + 3L * rpp * ld);
+            v0.x -= p.x; v0.y -= p.y; v0.z -= p.z; v0.w -= p.w;
+            v1.x -= p.x; v1.y -= p.y; v1.z -= p.z; v1.w -= p.w;
+            v2.x -= p.x; v2.y -= p.y; v2.z -= p.z; v2.w -= p.w;
+            v3.x -= p.x; v3.y -= p.y; v3.z -= p.z; v3.w -= p.w;
             s.x += (v0.x + v1.x) + (v2.x + v3.x); s.y += (v0.y + v1.y) + (v2.y + v3.y);
             s.z += (v0.z + v1.z) + (v2.z + v3.z); s.w += (v0.w + v1.w) + (v2.w + v3.w);
             t.x += (v0.x * v0.x + v1.x * v1.x) + (v2.x * v2.x + v3.x * v3.x);
@@ -102,12 +149,13 @@ bn_stats_kernel(long rows, int C, const float *__restrict__ Y, int ld, int rows_
             t.w += (v0.w * v0.w + v1.w * v1.w) + (v2.w * v2.w + v3.w * v3.w);
         }
         for (; r < r1; r += rpp) {
-            const float4 v = *reinterpret_cast<const float4 *>(Y + r * ld + 4 * q);
+            float4 v = *reinterpret_cast<const float4 *>(Y + r * ld + 4 * q);
+            v.x -= p.x; v.y -= p.y; v.z -= p.z; v.w -= p.w;
             s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
             t.x += v.x * v.x; t.y += v.y * v.y; t.z += v.z * v.z; t.w += v.w * v.w;
         }
     }
-    block_reduce_to_sums(s, t, Q, rpp, C, sums);
+    block_reduce_pivoted_to_sums(s, t, p, n, Q, rpp, C, sums);
 }
 
 __global__ void __launch_bounds__(kTT)
@@ -656,8 +704,9 @@ sa_layer1_kernel(int n, int S, int K, int Q, const float *__restrict__ a1f, int 
 }
 
 // The same with the BatchNorm statistics of the result taken on the way (pn2x_sa_layer1_stats): a workgroup owns rows_per_block
-// consecutive slots of one cloud, a thread a channel quad of every rpp-th of them, and the per-thread sums of y and y^2 go through
-// block_reduce_to_sums like pn2x_bn_stats' -- the separate pass over y1 (one launch per scale and step) disappears.
+// consecutive slots of one cloud, a thread a channel quad of every rpp-th of them, and the per-thread sums of y - p and (y - p)^2
+// around the thread's pivot p go through block_reduce_pivoted_to_sums like pn2x_bn_stats' -- the separate pass over y1 (one launch
+// per scale and step) disappears.
 struct SaLayer1Args {
     int n, S, K, Q; const float *a1f; int a1f_ld; const float *xyz, *cxyz, *wx; int wx_ld; const float *cadd; int cadd_ld;
     const int *idx; float *out, *rel_out; int rows_per_block; double *sums;
@@ -690,7 +739,8 @@ __device__ __forceinline__ void sa_layer1_stats_body(const SaLayer1Args &A, unsi
 #pragma unroll
             for (int c = 0; c < 3; ++c) w[i][c] = wx[(size_t)(4 * q + i) * wx_ld + c];
     }
-    float4 sm = make_float4(0.f, 0.f, 0.f, 0.f), sq = sm;
+    float4 sm = make_float4(0.f, 0.f, 0.f, 0.f), sq = sm, piv = sm;
+    int cnt = 0;
     typedef float v4 __attribute__((ext_vector_type(4)));  // (an array of float4 STRUCTS stays in scratch memory)
     auto finish = [&](int r, int lr, v4 a, v4 cv) {
         float4 acc = make_float4(a.x, a.y, a.z, a.w);
@@ -703,6 +753,8 @@ __device__ __forceinline__ void sa_layer1_stats_body(const SaLayer1Args &A, unsi
         }
         if (cadd) { acc.x += cv.x; acc.y += cv.y; acc.z += cv.z; acc.w += cv.w; }
         *reinterpret_cast<float4 *>(out + ((size_t)b * sk + r) * (4 * Q) + 4 * q) = acc;
+        if (cnt++ == 0) piv = acc;  // this thread's pivot: the first row it forms (block_reduce_pivoted_to_sums)
+        acc.x -= piv.x; acc.y -= piv.y; acc.z -= piv.z; acc.w -= piv.w;
         sm.x += acc.x; sm.y += acc.y; sm.z += acc.z; sm.w += acc.w;
         sq.x += acc.x * acc.x; sq.y += acc.y * acc.y; sq.z += acc.z * acc.z; sq.w += acc.w * acc.w;
     };
@@ -745,7 +797,7 @@ __device__ __forceinline__ void sa_layer1_stats_body(const SaLayer1Args &A, unsi
             finish(rb + lr, lr, a, cv);
         }
     }
-    block_reduce_to_sums(sm, sq, Q, rpp, 4 * Q, sums);
+    block_reduce_pivoted_to_sums(sm, sq, piv, cnt, Q, rpp, 4 * Q, sums);
 }
 
 __global__ void __launch_bounds__(kTT)
