@@ -1270,6 +1270,7 @@ extern "C" int pn2x_sa_mlp_max_pair_supported(int k0, int k1, int c1, int c2, in
     return (c1 == 128 && c2 == 128 && c3 == 192 && ((k0 == 16 && k1 == 64) || (k0 == 64 && k1 == 16))) ? 1 : 0;
 }
 
+static_assert(sizeof(pn2x_sa_problem) == 144, "record layout (pn2_ext.h)");
 extern "C" int pn2x_sa_mlp_max_pair(int b, int c1, int c2, int c3, const pn2x_sa_problem *p0, const pn2x_sa_problem *p1, void *stream) {
     using namespace pn2;
     if (b < 0 || !p0 || !p1) return b < 0 ? PN2_EINVAL : PN2_ENULL;

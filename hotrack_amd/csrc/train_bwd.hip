@@ -932,36 +932,27 @@ extern "C" int pn2x_tg_bwd_partials(long rows, int c_out, int c_in) {
     return grid_of(rows, s) * s.ks_w;
 }
 
+static_assert(sizeof(pn2x_tg_bwd_slice_problem) == 224, "record layout (pn2_ext.h)");
+
 // One column slice [c0, c0 + n) of a layer with sums_ld >= n channels: the caller passes g / yi / the per-channel vectors / sums_bwd_i /
 // w / dw already offset to the slice; arg (gmode 2) has its own row stride ldarg (g may be a column block of a wider tensor).  g_add (row stride ldga, may alias gp): the data-gradient partial of earlier slices; raw_out: leave
 // mask and sums to a later slice.
-#define PN2_TGB_PARAMS(S)                                                                                                              \
-    long rows##S, int n##S, int k##S, int gmode##S, const float *g##S, int ldg##S, const int *arg##S, int ldarg##S, int kmax##S,         \
-        const float *yi##S, int ldyi##S, const float *mean_i##S, const float *invstd_i##S, const float *gamma_i##S,                    \
-        const float *beta_i##S, const double *sums_bwd_i##S, int sums_ld##S, const float *w##S, int ldw##S, const float *yp##S,        \
-        int ldyp##S, const float *mean_p##S, const float *invstd_p##S, const float *gamma_p##S, const float *beta_p##S, float *gp##S,  \
-        int ldgp##S, double *sums_bwd_p##S, float *partial##S, long partial_floats##S, float *dw##S, const float *g_add##S, int ldga##S, \
-        int raw_out##S
-#define PN2_TGB_ARGS(S)                                                                                                                \
-    rows##S, n##S, k##S, gmode##S, g##S, ldg##S, arg##S, ldarg##S, kmax##S, yi##S, ldyi##S, mean_i##S, invstd_i##S, gamma_i##S, beta_i##S, \
-        sums_bwd_i##S, sums_ld##S, w##S, ldw##S, yp##S, ldyp##S, mean_p##S, invstd_p##S, gamma_p##S, beta_p##S, gp##S, ldgp##S,        \
-        sums_bwd_p##S, partial##S, partial_floats##S, dw##S, g_add##S, ldga##S, raw_out##S
-
 // validation + kernel arguments of one problem (grid-independent part)
-static int fill_bwd(PN2_TGB_PARAMS(), BwdArgs &a, Shape &s) {
-    if (rows < 1 || rows > 0x7fffffffL || !find_shape(k, n, s) || gmode < 0 || gmode > 2 || sums_ld < n) return PN2_EINVAL;
-    if (gmode == 2 && (kmax < 1 || rows % kmax || ldarg < n || ldarg % 4)) return PN2_EINVAL;
-    if ((gmode == 2 && !arg) || (gmode != 0 && !beta_i)) return PN2_ENULL;
-    if (g_add && (ldga < k || ldga % 4 || (uintptr_t)g_add % 16)) return PN2_EINVAL;
-    if ((uintptr_t)arg % 16) return PN2_EINVAL;
-    if (ldg < n || ldg % 4 || ldyi < n || ldyi % 4 || ldw < k || ldyp < k || ldyp % 4 || ldgp < k || ldgp % 4) return PN2_EINVAL;
-    if (!g || !yi || !mean_i || !invstd_i || !gamma_i || !sums_bwd_i || !w || !yp || !mean_p || !invstd_p || !gamma_p || !beta_p ||
-        !gp || !sums_bwd_p || !partial || !dw)
+static int check_tg_bwd_slice(const pn2x_tg_bwd_slice_problem &p, BwdArgs &a, Shape &s) {
+    const int n = p.n, k = p.k;
+    if (p.rows < 1 || p.rows > 0x7fffffffL || !find_shape(k, n, s) || p.gmode < 0 || p.gmode > 2 || p.sums_ld < n) return PN2_EINVAL;
+    if (p.gmode == 2 && (p.kmax < 1 || p.rows % p.kmax || p.ldarg < n || p.ldarg % 4)) return PN2_EINVAL;
+    if ((p.gmode == 2 && !p.arg) || (p.gmode != 0 && !p.beta_i)) return PN2_ENULL;
+    if (p.g_add && (p.ldga < k || p.ldga % 4 || (uintptr_t)p.g_add % 16)) return PN2_EINVAL;
+    if ((uintptr_t)p.arg % 16) return PN2_EINVAL;
+    if (p.ldg < n || p.ldg % 4 || p.ldyi < n || p.ldyi % 4 || p.ldw < k || p.ldyp < k || p.ldyp % 4 || p.ldgp < k || p.ldgp % 4) return PN2_EINVAL;
+    if (!p.g || !p.yi || !p.mean_i || !p.invstd_i || !p.gamma_i || !p.sums_bwd_i || !p.w || !p.yp || !p.mean_p || !p.invstd_p || !p.gamma_p ||
+        !p.beta_p || !p.gp || !p.sums_bwd_p || !p.partial || !p.dw)
         return PN2_ENULL;
-    if (((uintptr_t)g | (uintptr_t)yi | (uintptr_t)yp | (uintptr_t)gp) % 16) return PN2_EINVAL;
-    (void)partial_floats;
-    a = BwdArgs{rows, g, ldg, arg, ldarg, kmax, kshift_of(kmax), yi, ldyi, mean_i, invstd_i, gamma_i, beta_i, sums_bwd_i, sums_ld, g_add, ldga, raw_out ? 1 : 0, w, ldw, yp, ldyp, mean_p, invstd_p, gamma_p, beta_p,
-                gp, ldgp, sums_bwd_p, partial, dw
+    if (((uintptr_t)p.g | (uintptr_t)p.yi | (uintptr_t)p.yp | (uintptr_t)p.gp) % 16) return PN2_EINVAL;
+    a = BwdArgs{p.rows, p.g, p.ldg, p.arg, p.ldarg, p.kmax, kshift_of(p.kmax), p.yi, p.ldyi, p.mean_i, p.invstd_i, p.gamma_i, p.beta_i, p.sums_bwd_i,
+                p.sums_ld, p.g_add, p.ldga, p.raw_out ? 1 : 0, p.w, p.ldw, p.yp, p.ldyp, p.mean_p, p.invstd_p, p.gamma_p, p.beta_p,
+                p.gp, p.ldgp, p.sums_bwd_p, p.partial, p.dw
 #ifdef PN2_TGB_PROFILE
                 , g_prof
 #endif
@@ -969,15 +960,8 @@ static int fill_bwd(PN2_TGB_PARAMS(), BwdArgs &a, Shape &s) {
     return PN2_OK;
 }
 
-extern "C" int pn2x_tg_bwd_slice(PN2_TGB_PARAMS(), void *stream) {
-    Shape s;
-    BwdArgs a;
-    const int rc = fill_bwd(PN2_TGB_ARGS(), a, s);
-    if (rc != PN2_OK) return rc;
-    const int grid = grid_of(rows, s);
-    if (partial_floats < (long)grid * s.ks_w * n * k) return PN2_ESCRATCH;
-    hipStream_t st = (hipStream_t)stream;
-    const int nb = k / 32, kb = n / 32;
+static void launch_tg_bwd(const BwdArgs &a, const Shape &s, int grid, int gmode, hipStream_t st) {
+    const int nb = s.nb, kb = s.kb;
 #define PN2_TGB_LAUNCH(NB_, KB_, GM_)                                                                                  \
     do {                                                                                                              \
         static PerDeviceOnce once;                                                                                    \
@@ -1003,7 +987,7 @@ extern "C" int pn2x_tg_bwd_slice(PN2_TGB_PARAMS(), void *stream) {
     }
         PN2_TGB2_SHAPES(X)
 #undef X
-        return check_launch();
+        return;
     }
 #undef PN2_TGB2_LAUNCH
 #define X(NB_, KB_)                                                                                                   \
@@ -1015,45 +999,15 @@ extern "C" int pn2x_tg_bwd_slice(PN2_TGB_PARAMS(), void *stream) {
     PN2_TGB_SHAPES(X)
 #undef X
 #undef PN2_TGB_LAUNCH
-    return check_launch();
 }
 
 // the pair kernel is instantiated for the 128-channel layers of the keypoint-query modules only (128 -> 128, 128 -> 192)
 extern "C" int pn2x_tg_bwd_pair_supported(int c_in, int c_out) { return (c_in == 128 && (c_out == 128 || c_out == 192)) ? 1 : 0; }
 
 // Two problems of the same layer shape and gradient source in ONE launch (the two neighbourhood sizes of a keypoint-query
-// module): the persistent workgroups are split in proportion to the tile counts.  n_partials[2] receives the number of partial
-// weight-gradient tiles each problem wrote (its share of the grid x the row slices per workgroup): the caller's reduction must
-// sum exactly those.  Each partial buffer must hold what the problem would need alone (pn2x_tg_bwd_partials).
-extern "C" int pn2x_tg_bwd_slice_pair(PN2_TGB_PARAMS(0), PN2_TGB_PARAMS(1), int *n_partials, void *stream) {
-    Shape s0, s1;
-    BwdArgs a0, a1;
-    if (!n_partials) return PN2_ENULL;
-    int rc = fill_bwd(PN2_TGB_ARGS(0), a0, s0);
-    if (rc != PN2_OK) return rc;
-    rc = fill_bwd(PN2_TGB_ARGS(1), a1, s1);
-    if (rc != PN2_OK) return rc;
-    if (n0 != n1 || k0 != k1 || gmode0 != gmode1) return PN2_EINVAL;
-    if (!pn2x_tg_bwd_pair_supported(k0, n0)) return PN2_ERANGE;
-    if (s0.v2 && k0 == 128 && n0 == 192 && gmode0 != 2) {
-        // (the pair form of the 128 -> 192 register-resident-W kernel with a dense source needs three registers more than a
-        // wave has: that combination -- not one of this network's -- keeps the round-4 kernel; same partial-tile layout)
-        s0 = s1 = shape_of<4, 6>();
-    }
-    const long t0 = (rows0 + BM - 1) / BM, t1 = (rows1 + BM - 1) / BM;
-    long cap = (long)num_compute_units() * (!s0.v2 && s0.lds * 2 <= 160 * 1024 ? 2 : 1);
-    if (cap < 2) cap = 2;
-    long rounds = (t0 + t1 + cap - 1) / cap, wg0, wg1;
-    for (;; ++rounds) {  // the same number of rounds for both shares
-        wg0 = (t0 + rounds - 1) / rounds;
-        wg1 = (t1 + rounds - 1) / rounds;
-        if (wg0 + wg1 <= cap || rounds > t0 + t1) break;
-    }
-    if (partial_floats0 < wg0 * s0.ks_w * n0 * k0 || partial_floats1 < wg1 * s1.ks_w * n1 * k1) return PN2_ESCRATCH;
-    n_partials[0] = (int)wg0 * s0.ks_w;
-    n_partials[1] = (int)wg1 * s1.ks_w;
-    hipStream_t st = (hipStream_t)stream;
-    const int nb = k0 / 32, kb = n0 / 32, gmode = gmode0;
+// module): workgroups [0, wg0) run problem 0, the other wg1 problem 1.
+static void launch_tg_bwd_pair(const BwdArgs &a0, const BwdArgs &a1, const Shape &s0, long wg0, long wg1, int gmode, hipStream_t st) {
+    const int nb = s0.nb, kb = s0.kb;
 #define PN2_TGB_LAUNCH(NB_, KB_, GM_)                                                                                  \
     do {                                                                                                              \
         static PerDeviceOnce once;                                                                                    \
@@ -1085,12 +1039,61 @@ extern "C" int pn2x_tg_bwd_slice_pair(PN2_TGB_PARAMS(0), PN2_TGB_PARAMS(1), int 
     if (s0.v2) {
         if (nb == 4 && kb == 4) { Y(4, 4) }
         else PN2_TGB2_LAUNCH(4, 6, 2);
-        return check_launch();
+        return;
     }
 #undef Y
 #undef PN2_TGB2_LAUNCH
     X(4, 4) X(4, 6)
 #undef X
 #undef PN2_TGB_LAUNCH
+}
+
+// n_partials receives the number of partial weight-gradient tiles each problem wrote (its share of the grid x the row slices per
+// workgroup): the caller's reduction must sum exactly those.  Each partial buffer must hold what the problem would need alone
+// (pn2x_tg_bwd_partials).
+extern "C" int pn2x_tg_bwd_slice(const pn2x_tg_bwd_slice_problem *problems, int count, int *n_partials, void *stream) {
+    if (count < 1 || count > 2) return PN2_EINVAL;
+    if (!problems || (count == 2 && !n_partials)) return PN2_ENULL;
+    Shape s[2];
+    BwdArgs a[2];
+    for (int i = 0; i < count; ++i)
+        if (const int rc = check_tg_bwd_slice(problems[i], a[i], s[i])) return rc;
+    const pn2x_tg_bwd_slice_problem &p0 = problems[0];
+    const long tile_floats = (long)p0.n * p0.k;
+    hipStream_t st = (hipStream_t)stream;
+    if (count == 2) {
+        const pn2x_tg_bwd_slice_problem &p1 = problems[1];
+        if (p0.n != p1.n || p0.k != p1.k || p0.gmode != p1.gmode) return PN2_EINVAL;
+    }
+    if (count == 2 && pn2x_tg_bwd_pair_supported(p0.k, p0.n)) {
+        if (s[0].v2 && p0.k == 128 && p0.n == 192 && p0.gmode != 2) {
+            // (the pair form of the 128 -> 192 register-resident-W kernel with a dense source needs three registers more than a
+            // wave has: that combination -- not one of this network's -- keeps the round-4 kernel; same partial-tile layout)
+            s[0] = s[1] = shape_of<4, 6>();
+        }
+        const long t0 = (a[0].R + BM - 1) / BM, t1 = (a[1].R + BM - 1) / BM;
+        long cap = (long)num_compute_units() * (!s[0].v2 && s[0].lds * 2 <= 160 * 1024 ? 2 : 1);
+        if (cap < 2) cap = 2;
+        long rounds = (t0 + t1 + cap - 1) / cap, wg0, wg1;
+        for (;; ++rounds) {  // the same number of rounds for both shares
+            wg0 = (t0 + rounds - 1) / rounds;
+            wg1 = (t1 + rounds - 1) / rounds;
+            if (wg0 + wg1 <= cap || rounds > t0 + t1) break;
+        }
+        if (p0.partial_floats < wg0 * s[0].ks_w * tile_floats || problems[1].partial_floats < wg1 * s[1].ks_w * tile_floats) return PN2_ESCRATCH;
+        n_partials[0] = (int)wg0 * s[0].ks_w;
+        n_partials[1] = (int)wg1 * s[1].ks_w;
+        launch_tg_bwd_pair(a[0], a[1], s[0], wg0, wg1, p0.gmode, st);
+        return check_launch();
+    }
+    int grid[2];
+    for (int i = 0; i < count; ++i) {
+        grid[i] = grid_of(a[i].R, s[i]);
+        if (problems[i].partial_floats < (long)grid[i] * s[i].ks_w * tile_floats) return PN2_ESCRATCH;
+    }
+    for (int i = 0; i < count; ++i) {
+        if (n_partials) n_partials[i] = grid[i] * s[i].ks_w;
+        launch_tg_bwd(a[i], s[i], grid[i], problems[i].gmode, st);
+    }
     return check_launch();
 }

@@ -273,19 +273,27 @@ extern "C" int pn2x_tg_fwd2_supported(int c_in, int c_out) {
     return ((c_in == 64 || c_in == 128 || c_in == 256) && blocks_for_k(c_in, c_out) != 0) ? 1 : 0;
 }
 
-extern "C" int pn2x_tg_fwd2(long rows, int k, int n, const float *x, int ldx, const float *w, int ldw, float *y, int ldy,
-                            const double *sums_in, const float *gamma, const float *beta, const float *conv_bias, float eps,
-                            float momentum, float *running_mean, float *running_var, long long *num_batches_tracked,
-                            float *save_mean, float *save_invstd, double *sums_out, void *stream) {
-    if (rows < 1 || !pn2x_tg_fwd2_supported(k, n) || ldx < k || ldx % 4 || ldw < k || ldw % 4 || ldy < n) return PN2_EINVAL;
-    if (!x || !w || !y || !sums_in || !gamma || !beta || !save_mean || !save_invstd) return PN2_ENULL;
-    if (((uintptr_t)x | (uintptr_t)w) % 16) return PN2_EINVAL;
-    FwdArgs a{rows, n, x, ldx, w, ldw, y, ldy, sums_in, gamma, beta, conv_bias, eps, momentum, running_mean, running_var,
-              num_batches_tracked, save_mean, save_invstd, sums_out};
-    const int nblk = blocks_for_k(k, n), kb = k / 32;
+// instantiated for the 128-channel layers of the keypoint-query modules (128 -> 128, 128 -> 192)
+extern "C" int pn2x_tg_fwd2_pair_supported(int c_in, int c_out) {
+    return (c_in == 128 && (c_out == 128 || c_out == 192) && blocks_for_k(c_in, c_out) != 0) ? 1 : 0;
+}
+
+static_assert(sizeof(pn2x_tg_fwd2_problem) == 144, "record layout (pn2_ext.h)");
+
+// validation + kernel arguments of one problem
+static int check_tg_fwd2(const pn2x_tg_fwd2_problem &p, FwdArgs &a) {
+    if (p.rows < 1 || !pn2x_tg_fwd2_supported(p.k, p.n) || p.ldx < p.k || p.ldx % 4 || p.ldw < p.k || p.ldw % 4 || p.ldy < p.n) return PN2_EINVAL;
+    if (!p.x || !p.w || !p.y || !p.sums_in || !p.gamma || !p.beta || !p.save_mean || !p.save_invstd) return PN2_ENULL;
+    if (((uintptr_t)p.x | (uintptr_t)p.w) % 16) return PN2_EINVAL;
+    a = FwdArgs{p.rows, p.n, p.x, p.ldx, p.w, p.ldw, p.y, p.ldy, p.sums_in, p.gamma, p.beta, p.conv_bias, p.eps, p.momentum, p.running_mean,
+                p.running_var, p.num_batches_tracked, p.save_mean, p.save_invstd, p.sums_out};
+    return PN2_OK;
+}
+
+static void launch_tg_fwd2(const FwdArgs &a, int k, hipStream_t st) {
+    const int n = a.N, nblk = blocks_for_k(k, n), kb = k / 32;
     const int ny = n / (32 * nblk);
-    const long tiles = (rows + BM - 1) / BM;
-    hipStream_t st = (hipStream_t)stream;
+    const long tiles = (a.R + BM - 1) / BM;
 #define PN2_TGF_LAUNCH(KB_, NBLK_)                                                                                      \
     do {                                                                                                              \
         using P = Plan<KB_, NBLK_>;                                                                                   \
@@ -314,40 +322,16 @@ extern "C" int pn2x_tg_fwd2(long rows, int k, int n, const float *x, int ldx, co
         else PN2_TGF_LAUNCH(2, 2);
     }
 #undef PN2_TGF_LAUNCH
-    return check_launch();
-}
-
-// instantiated for the 128-channel layers of the keypoint-query modules (128 -> 128, 128 -> 192)
-extern "C" int pn2x_tg_fwd2_pair_supported(int c_in, int c_out) {
-    return (c_in == 128 && (c_out == 128 || c_out == 192) && blocks_for_k(c_in, c_out) != 0) ? 1 : 0;
 }
 
 // Two problems of the SAME layer shape (k -> n) in one launch: the persistent workgroups are split in proportion to the
 // problems' tile counts, so both shares run the same number of rounds.  The two neighbourhood sizes of a keypoint-query module
 // (10752 and 43008 rows at 32 clouds) as two launches were 168 one-tile workgroups + 3 ragged rounds, each launch paying its own
 // constants / W_i prologue and tail.
-extern "C" int pn2x_tg_fwd2_pair(long rows0, int k, int n, const float *x0, int ldx0, const float *w0, int ldw0, float *y0, int ldy0,
-                                 const double *sums_in0, const float *gamma0, const float *beta0, const float *conv_bias0, float eps0,
-                                 float momentum0, float *running_mean0, float *running_var0, long long *nbt0, float *save_mean0,
-                                 float *save_invstd0, double *sums_out0,
-                                 long rows1, const float *x1, int ldx1, const float *w1, int ldw1, float *y1, int ldy1,
-                                 const double *sums_in1, const float *gamma1, const float *beta1, const float *conv_bias1, float eps1,
-                                 float momentum1, float *running_mean1, float *running_var1, long long *nbt1, float *save_mean1,
-                                 float *save_invstd1, double *sums_out1, void *stream) {
-    if (rows0 < 1 || rows1 < 1) return PN2_EINVAL;
-    if (!pn2x_tg_fwd2_pair_supported(k, n)) return PN2_ERANGE;
-    if (ldx0 < k || ldx0 % 4 || ldw0 < k || ldw0 % 4 || ldy0 < n || ldx1 < k || ldx1 % 4 || ldw1 < k || ldw1 % 4 || ldy1 < n) return PN2_EINVAL;
-    if (!x0 || !w0 || !y0 || !sums_in0 || !gamma0 || !beta0 || !save_mean0 || !save_invstd0) return PN2_ENULL;
-    if (!x1 || !w1 || !y1 || !sums_in1 || !gamma1 || !beta1 || !save_mean1 || !save_invstd1) return PN2_ENULL;
-    if (((uintptr_t)x0 | (uintptr_t)w0 | (uintptr_t)x1 | (uintptr_t)w1) % 16) return PN2_EINVAL;
-    FwdArgs a0{rows0, n, x0, ldx0, w0, ldw0, y0, ldy0, sums_in0, gamma0, beta0, conv_bias0, eps0, momentum0, running_mean0, running_var0,
-               nbt0, save_mean0, save_invstd0, sums_out0};
-    FwdArgs a1{rows1, n, x1, ldx1, w1, ldw1, y1, ldy1, sums_in1, gamma1, beta1, conv_bias1, eps1, momentum1, running_mean1, running_var1,
-               nbt1, save_mean1, save_invstd1, sums_out1};
-    const int nblk = blocks_for_k(k, n);
+static void launch_tg_fwd2_pair(const FwdArgs &a0, const FwdArgs &a1, int k, hipStream_t st) {
+    const int n = a0.N, nblk = blocks_for_k(k, n);
     const int ny = n / (32 * nblk);
-    const long t0 = (rows0 + BM - 1) / BM, t1 = (rows1 + BM - 1) / BM;
-    hipStream_t st = (hipStream_t)stream;
+    const long t0 = (a0.R + BM - 1) / BM, t1 = (a1.R + BM - 1) / BM;
 #define PN2_TGF_PAIR(KB_, NBLK_)                                                                                        \
     do {                                                                                                              \
         using P = Plan<KB_, NBLK_>;                                                                                   \
@@ -371,5 +355,21 @@ extern "C" int pn2x_tg_fwd2_pair(long rows0, int k, int n, const float *x0, int 
     if (nblk == 6) PN2_TGF_PAIR(4, 6);
     else PN2_TGF_PAIR(4, 4);
 #undef PN2_TGF_PAIR
+}
+
+extern "C" int pn2x_tg_fwd2(const pn2x_tg_fwd2_problem *problems, int count, void *stream) {
+    if (count < 1 || count > 2) return PN2_EINVAL;
+    if (!problems) return PN2_ENULL;
+    FwdArgs a[2];
+    for (int i = 0; i < count; ++i)
+        if (const int rc = check_tg_fwd2(problems[i], a[i])) return rc;
+    const int k = problems[0].k;
+    if (count == 2 && (problems[1].k != k || problems[1].n != problems[0].n)) return PN2_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    if (count == 2 && pn2x_tg_fwd2_pair_supported(k, a[0].N)) {
+        launch_tg_fwd2_pair(a[0], a[1], k, st);
+    } else {
+        for (int i = 0; i < count; ++i) launch_tg_fwd2(a[i], k, st);
+    }
     return check_launch();
 }

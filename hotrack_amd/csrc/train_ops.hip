@@ -1313,52 +1313,41 @@ extern "C" int pn2x_rows_outer3(long rows, int c, const float *dy, int ldy, cons
 }
 
 namespace pn2 {
-static int routed_args(long groups, int k, int c, const float *dout, int ldd, const int *arg, int lda, const float *y, int ldy,
-                       const float *mean, const float *invstd, const float *gamma, const float *beta, double *sums, RoutedArgs &a,
-                       unsigned &blocks_out) {
-    if (groups < 1 || k < 1 || bad_c(c) || ldy < c || ldd < c || lda < c || groups * k > 0x7fffffffL) return PN2_EINVAL;
-    if (!dout || !arg || !y || !mean || !invstd || !gamma || !beta || !sums) return PN2_ENULL;
+static int check_bn_bwd_reduce_routed(const pn2x_bn_bwd_reduce_routed_problem &p, RoutedArgs &a, unsigned &blocks_out) {
+    const int c = p.c;
+    if (p.groups < 1 || p.k < 1 || bad_c(c) || p.ldy < c || p.ldd < c || p.lda < c || p.groups * p.k > 0x7fffffffL) return PN2_EINVAL;
+    if (!p.dout || !p.arg || !p.y || !p.mean || !p.invstd || !p.gamma || !p.beta || !p.sums) return PN2_ENULL;
     const int ny = (c + 63) / 64;
     long blocks = (4L * num_compute_units() + ny - 1) / ny;
-    long gpb = (groups + blocks - 1) / blocks;
+    long gpb = (p.groups + blocks - 1) / blocks;
     gpb = (gpb + 3) / 4 * 4;
     if (gpb < 16) gpb = 16;
-    blocks = (groups + gpb - 1) / gpb;
+    blocks = (p.groups + gpb - 1) / gpb;
     blocks_out = (unsigned)blocks;
-    a = RoutedArgs{groups, k, c, dout, ldd, arg, lda, y, ldy, mean, invstd, gamma, beta, gpb, sums};
+    a = RoutedArgs{p.groups, p.k, c, p.dout, p.ldd, p.arg, p.lda, p.y, p.ldy, p.mean, p.invstd, p.gamma, p.beta, gpb, p.sums};
     return PN2_OK;
 }
 }  // namespace pn2
 
-extern "C" int pn2x_bn_bwd_reduce_routed(long groups, int k, int c, const float *dout, int ldd, const int *arg, int lda, const float *y, int ldy,
-                                         const float *mean, const float *invstd, const float *gamma, const float *beta, double *sums,
-                                         void *stream) {
-    using namespace pn2;
-    RoutedArgs a;
-    unsigned blocks = 0;
-    if (int rc = routed_args(groups, k, c, dout, ldd, arg, lda, y, ldy, mean, invstd, gamma, beta, sums, a, blocks)) return rc;
-    hipLaunchKernelGGL(bn_bwd_reduce_routed_kernel, dim3(blocks, (c + 63) / 64), dim3(kTT), 0, (hipStream_t)stream, a);
-    return check_launch();
-}
+static_assert(sizeof(pn2x_bn_bwd_reduce_routed_problem) == 96, "record layout (pn2_ext.h)");
 
-// two problems of the same channel count in one launch (two calls when the counts differ); same results
-extern "C" int pn2x_bn_bwd_reduce_routed_pair(long groups_a, int k_a, int c_a, const float *dout_a, int ldd_a, const int *arg_a, int lda_a,
-                                              const float *y_a, int ldy_a, const float *mean_a, const float *invstd_a, const float *gamma_a,
-                                              const float *beta_a, double *sums_a, long groups_b, int k_b, int c_b, const float *dout_b,
-                                              int ldd_b, const int *arg_b, int lda_b, const float *y_b, int ldy_b, const float *mean_b,
-                                              const float *invstd_b, const float *gamma_b, const float *beta_b, double *sums_b, void *stream) {
+// two problems whose channels fill the same number of 64-channel tiles in one launch (a launch each otherwise); same results
+extern "C" int pn2x_bn_bwd_reduce_routed(const pn2x_bn_bwd_reduce_routed_problem *problems, int count, void *stream) {
     using namespace pn2;
-    RoutedArgs a, b;
-    unsigned na = 0, nb = 0;
-    if (int rc = routed_args(groups_a, k_a, c_a, dout_a, ldd_a, arg_a, lda_a, y_a, ldy_a, mean_a, invstd_a, gamma_a, beta_a, sums_a, a, na)) return rc;
-    if (int rc = routed_args(groups_b, k_b, c_b, dout_b, ldd_b, arg_b, lda_b, y_b, ldy_b, mean_b, invstd_b, gamma_b, beta_b, sums_b, b, nb)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    if ((c_a + 63) / 64 != (c_b + 63) / 64) {
-        hipLaunchKernelGGL(bn_bwd_reduce_routed_kernel, dim3(na, (c_a + 63) / 64), dim3(kTT), 0, st, a);
-        hipLaunchKernelGGL(bn_bwd_reduce_routed_kernel, dim3(nb, (c_b + 63) / 64), dim3(kTT), 0, st, b);
-        return check_launch();
+    if (count < 1 || count > 2) return PN2_EINVAL;
+    if (!problems) return PN2_ENULL;
+    RoutedArgs a[2];
+    unsigned nb[2] = {0, 0}, ny[2] = {0, 0};
+    for (int i = 0; i < count; ++i) {
+        if (const int rc = check_bn_bwd_reduce_routed(problems[i], a[i], nb[i])) return rc;
+        ny[i] = (unsigned)((problems[i].c + 63) / 64);
     }
-    hipLaunchKernelGGL(bn_bwd_reduce_routed_pair_kernel, dim3(na + nb, (c_a + 63) / 64), dim3(kTT), 0, st, a, b, na);
+    hipStream_t st = (hipStream_t)stream;
+    if (count == 2 && ny[0] == ny[1]) {
+        hipLaunchKernelGGL(bn_bwd_reduce_routed_pair_kernel, dim3(nb[0] + nb[1], ny[0]), dim3(kTT), 0, st, a[0], a[1], nb[0]);
+    } else {
+        for (int i = 0; i < count; ++i) hipLaunchKernelGGL(bn_bwd_reduce_routed_kernel, dim3(nb[i], ny[i]), dim3(kTT), 0, st, a[i]);
+    }
     return check_launch();
 }
 
@@ -1384,130 +1373,94 @@ extern "C" long pn2x_bn_bwd_apply_rel_scratch_floats(long rows, int c) {
 }
 
 namespace pn2 {
-static int apply_rel_args(long rows, int c, const float *g, int ldg, const float *y, int ldy, const float *mean, const float *invstd,
-                          const float *gamma, const float *beta, int relu, const double *sums, float *dy, int ldo, float *dgamma,
-                          float *dbeta, float *dbias, const float *rel, float *scratch, long scratch_floats, float *dwx, ApplyRelArgs &a,
-                          long &blocks) {
-    if (rows < 1 || bad_c(c) || c > 256 || ldy < c || ldy % 4 || ldg < c || ldg % 4 || ldo < c || ldo % 4) return PN2_EINVAL;
-    if (!g || !y || !mean || !invstd || !gamma || !beta || !sums || !dy || !dgamma || !dbeta || !rel || !scratch || !dwx) return PN2_ENULL;
-    if (((uintptr_t)y | (uintptr_t)g | (uintptr_t)dy) % 16) return PN2_EINVAL;
-    const int rpb = rows_per_block_for(rows, c);
-    blocks = (rows + rpb - 1) / rpb;
-    if (scratch_floats < blocks * 3L * c) return PN2_ESCRATCH;
-    a = ApplyRelArgs{rows, c, g, ldg, y, ldy, mean, invstd, gamma, beta, sums, rpb, relu, dy, ldo, dgamma, dbeta, dbias, rel, scratch};
+static int check_bn_bwd_apply_rel(const pn2x_bn_bwd_apply_rel_problem &p, ApplyRelArgs &a, long &blocks) {
+    const int c = p.c;
+    if (p.rows < 1 || bad_c(c) || c > 256 || p.ldy < c || p.ldy % 4 || p.ldg < c || p.ldg % 4 || p.ldo < c || p.ldo % 4) return PN2_EINVAL;
+    if (!p.g || !p.y || !p.mean || !p.invstd || !p.gamma || !p.beta || !p.sums || !p.dy || !p.dgamma || !p.dbeta || !p.rel || !p.scratch || !p.dwx)
+        return PN2_ENULL;
+    if (((uintptr_t)p.y | (uintptr_t)p.g | (uintptr_t)p.dy) % 16) return PN2_EINVAL;
+    const int rpb = rows_per_block_for(p.rows, c);
+    blocks = (p.rows + rpb - 1) / rpb;
+    if (p.scratch_floats < blocks * 3L * c) return PN2_ESCRATCH;
+    a = ApplyRelArgs{p.rows, c, p.g, p.ldg, p.y, p.ldy, p.mean, p.invstd, p.gamma, p.beta, p.sums, rpb, p.relu, p.dy, p.ldo, p.dgamma, p.dbeta,
+                     p.dbias, p.rel, p.scratch};
     return PN2_OK;
 }
 }  // namespace pn2
 
-extern "C" int pn2x_bn_bwd_apply_rel(long rows, int c, const float *g, int ldg, const float *y, int ldy, const float *mean,
-                                     const float *invstd, const float *gamma, const float *beta, int relu, const double *sums, float *dy,
-                                     int ldo, float *dgamma, float *dbeta, float *dbias, const float *rel, float *scratch,
-                                     long scratch_floats, float *dwx, void *stream) {
-    using namespace pn2;
-    ApplyRelArgs a;
-    long blocks = 0;
-    if (int rc = apply_rel_args(rows, c, g, ldg, y, ldy, mean, invstd, gamma, beta, relu, sums, dy, ldo, dgamma, dbeta, dbias, rel, scratch,
-                                scratch_floats, dwx, a, blocks)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(bn_relu_bwd_apply_rel_kernel, dim3((unsigned)blocks), dim3(kTT), 0, st, a);
-    hipLaunchKernelGGL(rows_outer3_sum_kernel, dim3((3 * c + 15) / 16), dim3(kTT), 0, st, (int)blocks, 3 * c, scratch, dwx);
-    return check_launch();
-}
+static_assert(sizeof(pn2x_bn_bwd_apply_rel_problem) == 152, "record layout (pn2_ext.h)");
 
 // Two problems (the two neighbourhood sizes of a keypoint-query module: pointnet_utils.py:566-581) in ONE launch each: the K = 16
 // scale alone is a 16 us launch for a quarter of the K = 64 scale's rows.
-extern "C" int pn2x_bn_bwd_apply_rel_pair(long rows_a, int c_a, const float *g_a, int ldg_a, const float *y_a, int ldy_a, const float *mean_a,
-                                          const float *invstd_a, const float *gamma_a, const float *beta_a, int relu_a, const double *sums_a,
-                                          float *dy_a, int ldo_a, float *dgamma_a, float *dbeta_a, float *dbias_a, const float *rel_a,
-                                          float *scratch_a, long scratch_floats_a, float *dwx_a, long rows_b, int c_b, const float *g_b,
-                                          int ldg_b, const float *y_b, int ldy_b, const float *mean_b, const float *invstd_b,
-                                          const float *gamma_b, const float *beta_b, int relu_b, const double *sums_b, float *dy_b, int ldo_b,
-                                          float *dgamma_b, float *dbeta_b, float *dbias_b, const float *rel_b, float *scratch_b,
-                                          long scratch_floats_b, float *dwx_b, void *stream) {
+extern "C" int pn2x_bn_bwd_apply_rel(const pn2x_bn_bwd_apply_rel_problem *problems, int count, void *stream) {
     using namespace pn2;
-    ApplyRelArgs a, b;
-    long na = 0, nb = 0;
-    if (int rc = apply_rel_args(rows_a, c_a, g_a, ldg_a, y_a, ldy_a, mean_a, invstd_a, gamma_a, beta_a, relu_a, sums_a, dy_a, ldo_a, dgamma_a,
-                                dbeta_a, dbias_a, rel_a, scratch_a, scratch_floats_a, dwx_a, a, na)) return rc;
-    if (int rc = apply_rel_args(rows_b, c_b, g_b, ldg_b, y_b, ldy_b, mean_b, invstd_b, gamma_b, beta_b, relu_b, sums_b, dy_b, ldo_b, dgamma_b,
-                                dbeta_b, dbias_b, rel_b, scratch_b, scratch_floats_b, dwx_b, b, nb)) return rc;
+    if (count < 1 || count > 2) return PN2_EINVAL;
+    if (!problems) return PN2_ENULL;
+    ApplyRelArgs a[2];
+    long nb[2] = {0, 0};
+    for (int i = 0; i < count; ++i)
+        if (const int rc = check_bn_bwd_apply_rel(problems[i], a[i], nb[i])) return rc;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(bn_relu_bwd_apply_rel_pair_kernel, dim3((unsigned)(na + nb)), dim3(kTT), 0, st, a, b, (unsigned)na);
-    const unsigned sa = (3 * c_a + 15) / 16, sb = (3 * c_b + 15) / 16;
-    hipLaunchKernelGGL(rows_outer3_sum_pair_kernel, dim3(sa + sb), dim3(kTT), 0, st, (int)na, 3 * c_a, scratch_a, dwx_a, (int)nb, 3 * c_b, scratch_b,
-                       dwx_b, sa);
-    return check_launch();
-}
-
-extern "C" int pn2x_bn_relu_max(long groups, int k, int c, const float *y, int ldy, const double *sums, const float *gamma,
-                                const float *beta, const float *conv_bias, float eps, float momentum, float *running_mean,
-                                float *running_var, long long *num_batches_tracked, float *save_mean, float *save_invstd, float *out,
-                                int *arg, void *stream) {
-    return pn2x_bn_relu_max_ld(groups, k, c, y, ldy, sums, gamma, beta, conv_bias, eps, momentum, running_mean, running_var,
-                               num_batches_tracked, save_mean, save_invstd, out, c, arg, stream);
-}
-
-// ... with the output rows ldo floats apart: `out` may be a column block of a wider (groups x ldo) buffer -- the two scales of a
-// module write the two halves of ONE tensor instead of being concatenated by a copy launch (round 6)
-extern "C" int pn2x_bn_relu_max_ld(long groups, int k, int c, const float *y, int ldy, const double *sums, const float *gamma,
-                                   const float *beta, const float *conv_bias, float eps, float momentum, float *running_mean,
-                                   float *running_var, long long *num_batches_tracked, float *save_mean, float *save_invstd, float *out,
-                                   int ldo, int *arg, void *stream) {
-    using namespace pn2;
-    if (groups < 1 || k < 1 || bad_c(c) || ldy < c || ldy % 4 || ldo < c || ldo % 4) return PN2_EINVAL;
-    if (!y || !sums || !gamma || !beta || !save_mean || !save_invstd || !out || !arg) return PN2_ENULL;
-    if (((uintptr_t)y | (uintptr_t)out | (uintptr_t)arg) % 16) return PN2_EINVAL;
-    const long items = groups * (c / 4);
-    int split = 1;  // rows of a group over `split` lanes while that keeps fewer than ~128k threads busy
-    while (split < 64 && 2 * split <= k && items * split < 131072) split *= 2;
-    if (split >= 4) {
-        const int ipb = kTT / split;
-        const MaxSplitArgs a{groups, k, c, split, y, ldy, sums, gamma, beta, conv_bias, eps, momentum, running_mean, running_var,
-                             num_batches_tracked, save_mean, save_invstd, out, arg, ldo};
-        hipLaunchKernelGGL(bn_relu_max_split_kernel, dim3((unsigned)((items + ipb - 1) / ipb)), dim3(kTT), 0, (hipStream_t)stream, a);
+    const pn2x_bn_bwd_apply_rel_problem &p = problems[0];
+    if (count == 1) {
+        hipLaunchKernelGGL(bn_relu_bwd_apply_rel_kernel, dim3((unsigned)nb[0]), dim3(kTT), 0, st, a[0]);
+        hipLaunchKernelGGL(rows_outer3_sum_kernel, dim3((3 * p.c + 15) / 16), dim3(kTT), 0, st, (int)nb[0], 3 * p.c, p.scratch, p.dwx);
         return check_launch();
     }
-    hipLaunchKernelGGL(bn_relu_max_kernel, dim3((unsigned)((items + kTT - 1) / kTT)), dim3(kTT), 0, (hipStream_t)stream, groups, k, c, y, ldy,
-                       sums, gamma, beta, conv_bias, eps, momentum, running_mean, running_var, num_batches_tracked, save_mean, save_invstd,
-                       out, ldo, arg);
+    const pn2x_bn_bwd_apply_rel_problem &q = problems[1];
+    hipLaunchKernelGGL(bn_relu_bwd_apply_rel_pair_kernel, dim3((unsigned)(nb[0] + nb[1])), dim3(kTT), 0, st, a[0], a[1], (unsigned)nb[0]);
+    const unsigned sa = (3 * p.c + 15) / 16, sb = (3 * q.c + 15) / 16;
+    hipLaunchKernelGGL(rows_outer3_sum_pair_kernel, dim3(sa + sb), dim3(kTT), 0, st, (int)nb[0], 3 * p.c, p.scratch, p.dwx, (int)nb[1], 3 * q.c,
+                       q.scratch, q.dwx, sa);
     return check_launch();
 }
 
-// pn2x_bn_relu_max_ld for two problems (the two neighbourhood sizes of a module) in ONE launch where both take the split kernel (few
-// groups: rows of a group over several lanes); two calls otherwise.  Same results.
-extern "C" int pn2x_bn_relu_max_pair(long groups_a, int k_a, int c_a, const float *y_a, int ldy_a, const double *sums_a, const float *gamma_a,
-                                        const float *beta_a, const float *conv_bias_a, float eps_a, float momentum_a, float *running_mean_a,
-                                        float *running_var_a, long long *nbt_a, float *save_mean_a, float *save_invstd_a, float *out_a, int ldo_a,
-                                        int *arg_a, long groups_b, int k_b, int c_b, const float *y_b, int ldy_b, const double *sums_b,
-                                        const float *gamma_b, const float *beta_b, const float *conv_bias_b, float eps_b, float momentum_b,
-                                        float *running_mean_b, float *running_var_b, long long *nbt_b, float *save_mean_b, float *save_invstd_b,
-                                        float *out_b, int ldo_b, int *arg_b, void *stream) {
+static_assert(sizeof(pn2x_bn_relu_max_problem) == 128, "record layout (pn2_ext.h)");
+
+namespace pn2 {
+// a.S >= 4: the problem takes the split kernel (few groups: the rows of a group over several lanes)
+static int check_bn_relu_max(const pn2x_bn_relu_max_problem &p, MaxSplitArgs &a) {
+    const int c = p.c;
+    if (p.groups < 1 || p.k < 1 || bad_c(c) || p.ldy < c || p.ldy % 4 || p.ldo < c || p.ldo % 4) return PN2_EINVAL;
+    if (!p.y || !p.sums || !p.gamma || !p.beta || !p.save_mean || !p.save_invstd || !p.out || !p.arg) return PN2_ENULL;
+    if (((uintptr_t)p.y | (uintptr_t)p.out | (uintptr_t)p.arg) % 16) return PN2_EINVAL;
+    const long items = p.groups * (c / 4);
+    int split = 1;  // rows of a group over `split` lanes while that keeps fewer than ~128k threads busy
+    while (split < 64 && 2 * split <= p.k && items * split < 131072) split *= 2;
+    a = MaxSplitArgs{p.groups, p.k, c, split, p.y, p.ldy, p.sums, p.gamma, p.beta, p.conv_bias, p.eps, p.momentum, p.running_mean, p.running_var,
+                     p.num_batches_tracked, p.save_mean, p.save_invstd, p.out, p.arg, p.ldo};
+    return PN2_OK;
+}
+}  // namespace pn2
+
+// The output rows are ldo floats apart: `out` may be a column block of a wider (groups x ldo) buffer -- the two scales of a
+// module write the two halves of ONE tensor instead of being concatenated by a copy launch (round 6).  Two problems (the two
+// neighbourhood sizes of a module) share ONE launch where both take the split kernel; a launch each otherwise.  Same results.
+extern "C" int pn2x_bn_relu_max(const pn2x_bn_relu_max_problem *problems, int count, void *stream) {
     using namespace pn2;
-    auto split_of = [](long groups, int k, int c) {
-        const long items = groups * (c / 4);
-        int split = 1;
-        while (split < 64 && 2 * split <= k && items * split < 131072) split *= 2;
-        return split;
-    };
-    const bool ok_a = groups_a >= 1 && k_a >= 1 && !bad_c(c_a) && ldy_a >= c_a && ldy_a % 4 == 0 && y_a && sums_a && gamma_a && beta_a &&
-                      save_mean_a && save_invstd_a && out_a && arg_a && (((uintptr_t)y_a | (uintptr_t)out_a | (uintptr_t)arg_a) % 16) == 0 && ldo_a >= c_a && ldo_a % 4 == 0;
-    const bool ok_b = groups_b >= 1 && k_b >= 1 && !bad_c(c_b) && ldy_b >= c_b && ldy_b % 4 == 0 && y_b && sums_b && gamma_b && beta_b &&
-                      save_mean_b && save_invstd_b && out_b && arg_b && (((uintptr_t)y_b | (uintptr_t)out_b | (uintptr_t)arg_b) % 16) == 0 && ldo_b >= c_b && ldo_b % 4 == 0;
-    const int sa = ok_a ? split_of(groups_a, k_a, c_a) : 1, sb = ok_b ? split_of(groups_b, k_b, c_b) : 1;
-    if (!ok_a || !ok_b || sa < 4 || sb < 4) {
-        const int rc = pn2x_bn_relu_max_ld(groups_a, k_a, c_a, y_a, ldy_a, sums_a, gamma_a, beta_a, conv_bias_a, eps_a, momentum_a, running_mean_a,
-                                           running_var_a, nbt_a, save_mean_a, save_invstd_a, out_a, ldo_a, arg_a, stream);
-        if (rc != PN2_OK) return rc;
-        return pn2x_bn_relu_max_ld(groups_b, k_b, c_b, y_b, ldy_b, sums_b, gamma_b, beta_b, conv_bias_b, eps_b, momentum_b, running_mean_b,
-                                   running_var_b, nbt_b, save_mean_b, save_invstd_b, out_b, ldo_b, arg_b, stream);
+    if (count < 1 || count > 2) return PN2_EINVAL;
+    if (!problems) return PN2_ENULL;
+    MaxSplitArgs a[2];
+    unsigned nb[2] = {0, 0};
+    for (int i = 0; i < count; ++i) {
+        if (const int rc = check_bn_relu_max(problems[i], a[i])) return rc;
+        const int ipb = a[i].S >= 4 ? kTT / a[i].S : kTT;  // (group, quad) items per workgroup
+        nb[i] = (unsigned)((a[i].groups * (a[i].C / 4) + ipb - 1) / ipb);
     }
-    const MaxSplitArgs a{groups_a, k_a, c_a, sa, y_a, ldy_a, sums_a, gamma_a, beta_a, conv_bias_a, eps_a, momentum_a, running_mean_a,
-                         running_var_a, nbt_a, save_mean_a, save_invstd_a, out_a, arg_a, ldo_a};
-    const MaxSplitArgs b{groups_b, k_b, c_b, sb, y_b, ldy_b, sums_b, gamma_b, beta_b, conv_bias_b, eps_b, momentum_b, running_mean_b,
-                         running_var_b, nbt_b, save_mean_b, save_invstd_b, out_b, arg_b, ldo_b};
-    const long ia = groups_a * (c_a / 4), ib = groups_b * (c_b / 4);
-    const unsigned na = (unsigned)((ia + kTT / sa - 1) / (kTT / sa)), nb = (unsigned)((ib + kTT / sb - 1) / (kTT / sb));
-    hipLaunchKernelGGL(bn_relu_max_split_pair_kernel, dim3(na + nb), dim3(kTT), 0, (hipStream_t)stream, a, b, na);
+    hipStream_t st = (hipStream_t)stream;
+    if (count == 2 && a[0].S >= 4 && a[1].S >= 4) {
+        hipLaunchKernelGGL(bn_relu_max_split_pair_kernel, dim3(nb[0] + nb[1]), dim3(kTT), 0, st, a[0], a[1], nb[0]);
+        return check_launch();
+    }
+    for (int i = 0; i < count; ++i) {
+        const MaxSplitArgs &m = a[i];
+        if (m.S >= 4)
+            hipLaunchKernelGGL(bn_relu_max_split_kernel, dim3(nb[i]), dim3(kTT), 0, st, m);
+        else
+            hipLaunchKernelGGL(bn_relu_max_kernel, dim3(nb[i]), dim3(kTT), 0, st, m.groups, m.K, m.C, m.Y, m.ldy, m.sums, m.gamma, m.beta,
+                               m.conv_bias, m.eps, m.momentum, m.running_mean, m.running_var, m.nbt, m.save_mean, m.save_invstd, m.out, m.ldo,
+                               m.arg);
+    }
     return check_launch();
 }
 
@@ -1583,77 +1536,63 @@ extern "C" int pn2x_sa_layer1(int b, int n, int s, int k, int c1, const float *a
     return check_launch();
 }
 
-// pn2x_sa_layer1 that also accumulates the BatchNorm statistics of its output into `sums` (pn2x_bn_sums_doubles(c1) doubles, zeroed
-// by the caller; the layout pn2x_bn_stats writes): in the same launch when the channel quads divide the workgroup, by a
-// pn2x_bn_stats launch behind it otherwise.
+static_assert(sizeof(pn2x_sa_layer1_stats_problem) == 80, "record layout (pn2_ext.h)");
+
 namespace pn2 {
-// 1: the statistics cannot be taken in the launch (channel quads do not divide the workgroup): the caller runs the two-launch form
-static int sa_layer1_stats_args(int b, int n, int s, int k, int c1, const float *a1f, int a1f_ld, const float *xyz, const float *cxyz,
-                                const float *wx, int wx_ld, const float *cadd, int cadd_ld, const int *idx, float *out, float *rel_out,
-                                double *sums, SaLayer1Args &a, unsigned &nbx) {
-    if (!sums) return PN2_ENULL;
-    const int Q = c1 >= 4 ? c1 / 4 : 1;
-    if (c1 % 4 || c1 < 4 || kTT % Q || (long)b * s * k > 2147483647L) return 1;
-    if (b < 0 || n < 1 || s < 0 || k < 1 || (xyz && wx_ld < 3)) return PN2_EINVAL;
-    if (b == 0 || s == 0) { nbx = 0; return PN2_OK; }
-    if (!idx || !out || (!a1f && !xyz)) return PN2_ENULL;
-    if (xyz && (!cxyz || !wx)) return PN2_ENULL;
-    if ((a1f && (a1f_ld < c1 || a1f_ld % 4)) || (cadd && (cadd_ld < c1 || cadd_ld % 4))) return PN2_EINVAL;
-    if (((uintptr_t)a1f | (uintptr_t)cadd | (uintptr_t)out) % 16) return PN2_EINVAL;
+// nbx > 0: the statistics are taken in the launch (the channel quads divide the workgroup); nbx == 0: the two-launch form
+// (pn2x_sa_layer1, then pn2x_bn_stats), or nothing to do (b == 0 || s == 0)
+static int check_sa_layer1_stats(const pn2x_sa_layer1_stats_problem &p, int b, int n, int s, const float *xyz, const float *cxyz,
+                                 SaLayer1Args &a, unsigned &nbx) {
+    const int k = p.k, c1 = p.c1;
+    nbx = 0;
+    if (!p.sums) return PN2_ENULL;
+    if (b < 0 || n < 1 || s < 0 || k < 1 || c1 < 4 || c1 % 4 || (xyz && p.wx_ld < 3)) return PN2_EINVAL;
+    if (b == 0 || s == 0) return PN2_OK;
+    if (!p.idx || !p.out || (!p.a1f && !xyz)) return PN2_ENULL;
+    if (xyz && (!cxyz || !p.wx)) return PN2_ENULL;
+    if ((p.a1f && (p.a1f_ld < c1 || p.a1f_ld % 4)) || (p.cadd && (p.cadd_ld < c1 || p.cadd_ld % 4))) return PN2_EINVAL;
+    if (((uintptr_t)p.a1f | (uintptr_t)p.cadd | (uintptr_t)p.out) % 16) return PN2_EINVAL;
+    const int Q = c1 / 4;
+    if (kTT % Q || (long)b * s * k > 2147483647L) return bad_c(c1) ? PN2_EINVAL : PN2_OK;  // (pn2x_bn_stats: c1 <= 1024)
     const int rpp = kTT / Q, sk = s * k;
     constexpr int target_wgs = 2048;  // (a sweep from 128 to 2048 workgroups moved the kernel by < 5 % between 512 and 2048)
     int rpb = (int)(((long)sk * b + target_wgs - 1) / target_wgs);  // ~2048 workgroups on a large problem, at least 8 rows per thread
     if (rpb < 8 * rpp) rpb = 8 * rpp;
     rpb = (rpb + rpp - 1) / rpp * rpp;
     nbx = (unsigned)((sk + rpb - 1) / rpb);
-    a = SaLayer1Args{n, s, k, Q, a1f, a1f_ld, xyz, cxyz, wx, wx_ld, cadd, cadd_ld, idx, out, rel_out, rpb, sums};
+    a = SaLayer1Args{n, s, k, Q, p.a1f, p.a1f_ld, xyz, cxyz, p.wx, p.wx_ld, p.cadd, p.cadd_ld, p.idx, p.out, p.rel_out, rpb, p.sums};
     return PN2_OK;
 }
 }  // namespace pn2
 
 // pn2x_sa_layer1 that also accumulates the BatchNorm statistics of its output into `sums` (pn2x_bn_sums_doubles(c1) doubles, zeroed
 // by the caller; the layout pn2x_bn_stats writes): in the same launch when the channel quads divide the workgroup, by a
-// pn2x_bn_stats launch behind it otherwise.
-extern "C" int pn2x_sa_layer1_stats(int b, int n, int s, int k, int c1, const float *a1f, int a1f_ld, const float *xyz, const float *cxyz,
-                                    const float *wx, int wx_ld, const float *cadd, int cadd_ld, const int *idx, float *out, float *rel_out,
-                                    double *sums, void *stream) {
+// pn2x_bn_stats launch behind it otherwise.  Two scales of one module (same clouds, coordinates and centres; own neighbour lists,
+// weights, outputs and statistics) share ONE launch where both can take their statistics in it.
+extern "C" int pn2x_sa_layer1_stats(const pn2x_sa_layer1_stats_problem *problems, int count, int b, int n, int s, const float *xyz,
+                                    const float *cxyz, void *stream) {
     using namespace pn2;
-    SaLayer1Args a;
-    unsigned nbx = 0;
-    const int rc0 = sa_layer1_stats_args(b, n, s, k, c1, a1f, a1f_ld, xyz, cxyz, wx, wx_ld, cadd, cadd_ld, idx, out, rel_out, sums, a, nbx);
-    if (rc0 == 1) {
-        const int rc = pn2x_sa_layer1(b, n, s, k, c1, a1f, a1f_ld, xyz, cxyz, wx, wx_ld, cadd, cadd_ld, idx, out, rel_out, stream);
-        if (rc != PN2_OK || b == 0 || s == 0) return rc;
-        return pn2x_bn_stats((long)b * s * k, c1, out, c1, sums, stream);
+    if (count < 1 || count > 2) return PN2_EINVAL;
+    if (!problems) return PN2_ENULL;
+    SaLayer1Args a[2];
+    unsigned nbx[2] = {0, 0};
+    for (int i = 0; i < count; ++i)
+        if (const int rc = check_sa_layer1_stats(problems[i], b, n, s, xyz, cxyz, a[i], nbx[i])) return rc;
+    if (b == 0 || s == 0) return PN2_OK;
+    if (count == 2 && nbx[0] && nbx[1]) {
+        hipLaunchKernelGGL(sa_layer1_stats_pair_kernel, dim3(nbx[0] + nbx[1], b), dim3(kTT), 0, (hipStream_t)stream, a[0], a[1], nbx[0]);
+        return check_launch();
     }
-    if (rc0 != PN2_OK || nbx == 0) return rc0;
-    hipLaunchKernelGGL(sa_layer1_stats_kernel, dim3(nbx, b), dim3(kTT), 0, (hipStream_t)stream, a);
-    return check_launch();
-}
-
-// ... for the two neighbourhood sizes of one module (same clouds, coordinates and centres; own neighbour lists, weights, outputs and
-// statistics) in ONE launch; falls back to two pn2x_sa_layer1_stats calls where a scale cannot take its statistics in the launch.
-extern "C" int pn2x_sa_layer1_stats_pair(int b, int n, int s, const float *xyz, const float *cxyz, int k_a, int c1_a, const float *a1f_a,
-                                         int a1f_ld_a, const float *wx_a, int wx_ld_a, const float *cadd_a, int cadd_ld_a, const int *idx_a,
-                                         float *out_a, float *rel_out_a, double *sums_a, int k_b, int c1_b, const float *a1f_b, int a1f_ld_b,
-                                         const float *wx_b, int wx_ld_b, const float *cadd_b, int cadd_ld_b, const int *idx_b, float *out_b,
-                                         float *rel_out_b, double *sums_b, void *stream) {
-    using namespace pn2;
-    SaLayer1Args a, c;
-    unsigned na = 0, nb = 0;
-    const int ra = sa_layer1_stats_args(b, n, s, k_a, c1_a, a1f_a, a1f_ld_a, xyz, cxyz, wx_a, wx_ld_a, cadd_a, cadd_ld_a, idx_a, out_a, rel_out_a,
-                                        sums_a, a, na);
-    const int rb = sa_layer1_stats_args(b, n, s, k_b, c1_b, a1f_b, a1f_ld_b, xyz, cxyz, wx_b, wx_ld_b, cadd_b, cadd_ld_b, idx_b, out_b, rel_out_b,
-                                        sums_b, c, nb);
-    if (ra != PN2_OK || rb != PN2_OK || na == 0 || nb == 0) {
-        if ((ra != PN2_OK && ra != 1) || (rb != PN2_OK && rb != 1)) return ra != PN2_OK && ra != 1 ? ra : rb;
-        const int rc = pn2x_sa_layer1_stats(b, n, s, k_a, c1_a, a1f_a, a1f_ld_a, xyz, cxyz, wx_a, wx_ld_a, cadd_a, cadd_ld_a, idx_a, out_a,
-                                            rel_out_a, sums_a, stream);
+    for (int i = 0; i < count; ++i) {
+        const pn2x_sa_layer1_stats_problem &p = problems[i];
+        if (nbx[i]) {
+            hipLaunchKernelGGL(sa_layer1_stats_kernel, dim3(nbx[i], b), dim3(kTT), 0, (hipStream_t)stream, a[i]);
+            continue;
+        }
+        int rc = pn2x_sa_layer1(b, n, s, p.k, p.c1, p.a1f, p.a1f_ld, xyz, cxyz, p.wx, p.wx_ld, p.cadd, p.cadd_ld, p.idx, p.out, p.rel_out, stream);
+        if (rc == PN2_OK) rc = pn2x_bn_stats((long)b * s * p.k, p.c1, p.out, p.c1, p.sums, stream);
         if (rc != PN2_OK) return rc;
-        return pn2x_sa_layer1_stats(b, n, s, k_b, c1_b, a1f_b, a1f_ld_b, xyz, cxyz, wx_b, wx_ld_b, cadd_b, cadd_ld_b, idx_b, out_b, rel_out_b,
-                                    sums_b, stream);
     }
-    hipLaunchKernelGGL(sa_layer1_stats_pair_kernel, dim3(na + nb, b), dim3(kTT), 0, (hipStream_t)stream, a, c, na);
     return check_launch();
 }
 
@@ -1685,58 +1624,67 @@ extern "C" int pn2x_inverse_index(int b, int n_dst, int l, const int *idx, int *
     return inverse_index_launch(b, n_dst, l, idx, offsets, order, (hipStream_t)stream);
 }
 
-extern "C" int pn2x_rows_segment_sum(int b, int n_dst, int m_src, int t, int c, const float *dout, int ldo, const int *offsets,
-                                     const int *order, const float *weight, float *din, int ldi, int accumulate, void *stream) {
-    using namespace pn2;
-    if (b < 0 || n_dst < 1 || m_src < 0 || c < 0 || c % 4 || ldo < c || ldo % 4 || ldi < c || ldi % 4 || (t != 1 && t != 3)) return PN2_EINVAL;
+static_assert(sizeof(pn2x_rows_segment_sum_problem) == 64, "record layout (pn2_ext.h)");
+
+namespace pn2 {
+// el: lanes a destination's segment is split over (1: the one-thread-per-(destination, quad) kernel); 0: nothing to do
+static int check_rows_segment_sum(const pn2x_rows_segment_sum_problem &p, int b, int n_dst, int &el) {
+    const int c = p.c;
+    el = 0;
+    if (b < 0 || n_dst < 1 || p.m_src < 0 || c < 0 || c % 4 || p.ldo < c || p.ldo % 4 || p.ldi < c || p.ldi % 4 || (p.t != 1 && p.t != 3))
+        return PN2_EINVAL;
     if (b == 0 || c == 0) return PN2_OK;
-    if (!dout || !offsets || !order || !din || (t == 3 && !weight)) return PN2_ENULL;
-    if (((uintptr_t)dout | (uintptr_t)din) % 16) return PN2_EINVAL;
+    if (!p.dout || !p.offsets || !p.order || !p.din || (p.t == 3 && !p.weight)) return PN2_ENULL;
+    if (((uintptr_t)p.dout | (uintptr_t)p.din) % 16) return PN2_EINVAL;
     const int Q = c / 4;
+    el = 1;
     // long segments on average (>= 4 entries per destination) and a quad count that divides 256: split every segment over lanes
-    int el = 1;
-    if ((long)m_src * t >= 4L * n_dst && Q <= 64 && kTT % Q == 0) {
+    if ((long)p.m_src * p.t >= 4L * n_dst && Q <= 64 && kTT % Q == 0) {
         el = kTT / Q;
         if (el > 16) el = 16;
     }
-    if (el > 1) {
-        const int dpb = kTT / (Q * el);
-        const dim3 sgrid((unsigned)((n_dst + dpb - 1) / dpb), b);
-        if (t == 1)
-            hipLaunchKernelGGL(rows_segment_sum_split_kernel<1>, sgrid, dim3(kTT), 0, (hipStream_t)stream, n_dst, m_src, Q, el, dout, ldo, offsets, order, weight, din, ldi, accumulate);
-        else
-            hipLaunchKernelGGL(rows_segment_sum_split_kernel<3>, sgrid, dim3(kTT), 0, (hipStream_t)stream, n_dst, m_src, Q, el, dout, ldo, offsets, order, weight, din, ldi, accumulate);
+    return PN2_OK;
+}
+}  // namespace pn2
+
+// Two t = 1 problems (two index lists over the same destination rows) share ONE launch where both take the
+// one-thread-per-(destination, quad) kernel (short segments); a launch per problem otherwise.  Same results.
+extern "C" int pn2x_rows_segment_sum(const pn2x_rows_segment_sum_problem *problems, int count, int b, int n_dst, int accumulate,
+                                     void *stream) {
+    using namespace pn2;
+    if (count < 1 || count > 2) return PN2_EINVAL;
+    if (!problems) return PN2_ENULL;
+    int el[2] = {0, 0};
+    for (int i = 0; i < count; ++i)
+        if (const int rc = check_rows_segment_sum(problems[i], b, n_dst, el[i])) return rc;
+    if (!el[0] && !el[1]) return PN2_OK;
+    hipStream_t st = (hipStream_t)stream;
+    auto args = [&](const pn2x_rows_segment_sum_problem &p) {
+        return SegSumArgs{n_dst, p.m_src, p.c / 4, p.dout, p.ldo, p.offsets, p.order, p.weight, p.din, p.ldi, accumulate};
+    };
+    auto blocks = [&](const pn2x_rows_segment_sum_problem &p) { return (unsigned)(((long)n_dst * (p.c / 4) + kTT - 1) / kTT); };
+    if (count == 2 && el[0] == 1 && el[1] == 1 && problems[0].t == 1 && problems[1].t == 1) {
+        const unsigned na = blocks(problems[0]), nb = blocks(problems[1]);
+        hipLaunchKernelGGL(rows_segment_sum_pair_kernel, dim3(na + nb, b), dim3(kTT), 0, st, args(problems[0]), args(problems[1]), na);
         return check_launch();
     }
-    const long total = (long)n_dst * Q;
-    const dim3 grid((unsigned)((total + kTT - 1) / kTT), b);
-    const SegSumArgs a{n_dst, m_src, Q, dout, ldo, offsets, order, weight, din, ldi, accumulate};
-    if (t == 1)
-        hipLaunchKernelGGL(rows_segment_sum_kernel<1>, grid, dim3(kTT), 0, (hipStream_t)stream, a);
-    else
-        hipLaunchKernelGGL(rows_segment_sum_kernel<3>, grid, dim3(kTT), 0, (hipStream_t)stream, a);
-    return check_launch();
-}
-
-// pn2x_rows_segment_sum (t = 1) for two index lists over the same destination rows in ONE launch where both take the
-// one-thread-per-(destination, quad) kernel (short segments); two calls otherwise.  Same results.
-extern "C" int pn2x_rows_segment_sum_pair(int b, int n_dst, int m_a, int c_a, const float *dout_a, int ldo_a, const int *offsets_a,
-                                          const int *order_a, float *din_a, int ldi_a, int m_b, int c_b, const float *dout_b, int ldo_b,
-                                          const int *offsets_b, const int *order_b, float *din_b, int ldi_b, int accumulate, void *stream) {
-    using namespace pn2;
-    auto split = [&](int m, int c) { const int Q = c / 4; return c >= 4 && (long)m >= 4L * n_dst && Q <= 64 && kTT % Q == 0; };
-    const bool ok = b > 0 && n_dst >= 1 && c_a >= 4 && c_b >= 4 && c_a % 4 == 0 && c_b % 4 == 0 && !split(m_a, c_a) && !split(m_b, c_b) &&
-                    dout_a && dout_b && offsets_a && offsets_b && order_a && order_b && din_a && din_b && ldo_a >= c_a && ldo_b >= c_b &&
-                    ldo_a % 4 == 0 && ldo_b % 4 == 0 && ldi_a >= c_a && ldi_b >= c_b && ldi_a % 4 == 0 && ldi_b % 4 == 0 &&
-                    (((uintptr_t)dout_a | (uintptr_t)dout_b | (uintptr_t)din_a | (uintptr_t)din_b) % 16) == 0 && m_a >= 0 && m_b >= 0;
-    if (!ok) {
-        const int rc = pn2x_rows_segment_sum(b, n_dst, m_a, 1, c_a, dout_a, ldo_a, offsets_a, order_a, nullptr, din_a, ldi_a, accumulate, stream);
-        if (rc != PN2_OK) return rc;
-        return pn2x_rows_segment_sum(b, n_dst, m_b, 1, c_b, dout_b, ldo_b, offsets_b, order_b, nullptr, din_b, ldi_b, accumulate, stream);
+    for (int i = 0; i < count; ++i) {
+        const pn2x_rows_segment_sum_problem &p = problems[i];
+        const int Q = p.c / 4;
+        if (el[i] > 1) {
+            const int dpb = kTT / (Q * el[i]);
+            const dim3 sgrid((unsigned)((n_dst + dpb - 1) / dpb), b);
+            if (p.t == 1)
+                hipLaunchKernelGGL(rows_segment_sum_split_kernel<1>, sgrid, dim3(kTT), 0, st, n_dst, p.m_src, Q, el[i], p.dout, p.ldo, p.offsets, p.order, p.weight, p.din, p.ldi, accumulate);
+            else
+                hipLaunchKernelGGL(rows_segment_sum_split_kernel<3>, sgrid, dim3(kTT), 0, st, n_dst, p.m_src, Q, el[i], p.dout, p.ldo, p.offsets, p.order, p.weight, p.din, p.ldi, accumulate);
+        } else if (el[i] == 1) {
+            const dim3 grid(blocks(p), b);
+            if (p.t == 1)
+                hipLaunchKernelGGL(rows_segment_sum_kernel<1>, grid, dim3(kTT), 0, st, args(p));
+            else
+                hipLaunchKernelGGL(rows_segment_sum_kernel<3>, grid, dim3(kTT), 0, st, args(p));
+        }
     }
-    const SegSumArgs a{n_dst, m_a, c_a / 4, dout_a, ldo_a, offsets_a, order_a, nullptr, din_a, ldi_a, accumulate};
-    const SegSumArgs c{n_dst, m_b, c_b / 4, dout_b, ldo_b, offsets_b, order_b, nullptr, din_b, ldi_b, accumulate};
-    const unsigned na = (unsigned)(((long)n_dst * a.Q + kTT - 1) / kTT), nb = (unsigned)(((long)n_dst * c.Q + kTT - 1) / kTT);
-    hipLaunchKernelGGL(rows_segment_sum_pair_kernel, dim3(na + nb, b), dim3(kTT), 0, (hipStream_t)stream, a, c, na);
     return check_launch();
 }

@@ -27,15 +27,36 @@ _lib.pn2x_bn_relu_bwd.argtypes = [_cl, _ci, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _
 _lib.pn2x_scatter_add_rows.argtypes = [_ci, _ci, _ci, _ci, _vp, _ci, _vp, _vp, _ci, _vp]
 _lib.pn2x_three_interpolate_pm_grad.argtypes = [_ci, _ci, _ci, _ci, _vp, _ci, _vp, _vp, _vp, _ci, _vp]
 _lib.pn2x_sa_layer1.argtypes = [_ci] * 5 + [_vp, _ci, _vp, _vp, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp]
-_lib.pn2x_sa_layer1_stats.argtypes = [_ci] * 5 + [_vp, _ci, _vp, _vp, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _vp]
+
+
+class _SaLayer1StatsProblem(ctypes.Structure):
+    """include/pn2_ext.h: pn2x_sa_layer1_stats_problem (80 bytes)."""
+    _fields_ = ([(n, _vp) for n in ("a1f", "wx", "cadd", "idx", "out", "rel_out", "sums")] +
+                [(n, _ci) for n in ("k", "c1", "a1f_ld", "wx_ld", "cadd_ld", "reserved")])
+
+
+class _RowsSegmentSumProblem(ctypes.Structure):
+    """include/pn2_ext.h: pn2x_rows_segment_sum_problem (64 bytes)."""
+    _fields_ = ([(n, _vp) for n in ("dout", "offsets", "order", "weight", "din")] +
+                [(n, _ci) for n in ("m_src", "t", "c", "ldo", "ldi", "reserved")])
+
+
+class _BnReluMaxProblem(ctypes.Structure):
+    """include/pn2_ext.h: pn2x_bn_relu_max_problem (128 bytes)."""
+    _fields_ = ([(n, _vp) for n in ("y", "sums", "gamma", "beta", "conv_bias", "running_mean", "running_var", "num_batches_tracked",
+                                    "save_mean", "save_invstd", "out", "arg")] +
+                [("groups", _cl), ("k", _ci), ("c", _ci), ("ldy", _ci), ("ldo", _ci), ("eps", _cf), ("momentum", _cf)])
+
+
+def _records(*problems):
+    """The problems (ctypes records of one type) as the contiguous array an entry takes, and their count."""
+    return (type(problems[0]) * len(problems))(*problems), len(problems)
+
+
+_lib.pn2x_sa_layer1_stats.argtypes = [ctypes.POINTER(_SaLayer1StatsProblem), _ci, _ci, _ci, _ci, _vp, _vp, _vp]
 _lib.pn2x_sa_layer1_stats.restype = _ci
 _lib.pn2x_bn_sums_doubles.argtypes = [_ci]
 _lib.pn2x_bn_sums_doubles.restype = _ci
-_SCALE = [_ci, _ci, _vp, _ci, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp]  # k, c1, a1f, a1f_ld, wx, wx_ld, cadd, cadd_ld, idx, out, rel_out, sums
-_lib.pn2x_sa_layer1_stats_pair.argtypes = [_ci, _ci, _ci, _vp, _vp] + _SCALE + _SCALE + [_vp]
-_lib.pn2x_sa_layer1_stats_pair.restype = _ci
-_lib.pn2x_rows_segment_sum_pair.argtypes = [_ci, _ci] + [_ci, _ci, _vp, _ci, _vp, _vp, _vp, _ci] * 2 + [_ci, _vp]
-_lib.pn2x_rows_segment_sum_pair.restype = _ci
 PAIR_SCALES = True  # the two scales of a module: one launch where a pair kernel exists (False: one launch per scale; tests compare)
 _lib.pn2x_rows_outer3.argtypes = [_cl, _ci, _vp, _ci, _vp, _vp, _vp, _cl, _vp]
 _lib.pn2x_rows_outer3.restype = _ci
@@ -47,15 +68,13 @@ for _n in ("pn2x_bn_stats", "pn2x_bn_relu_apply", "pn2x_bn_relu_bwd", "pn2x_scat
 
 _lib.pn2x_inverse_index.argtypes = [_ci, _ci, _ci, _vp, _vp, _vp, _vp]
 _lib.pn2x_inverse_index.restype = _ci
-_lib.pn2x_rows_segment_sum.argtypes = [_ci, _ci, _ci, _ci, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _ci, _ci, _vp]
+_lib.pn2x_rows_segment_sum.argtypes = [ctypes.POINTER(_RowsSegmentSumProblem), _ci, _ci, _ci, _ci, _vp]
 _lib.pn2x_rows_segment_sum.restype = _ci
 INVERSE_MAX_ROWS = 16127  # pn2x_inverse_index keeps n_dst + 1 + 256 counters in 64 KiB of LDS
-_lib.pn2x_bn_relu_max.argtypes = [_cl, _ci, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _cf, _cf, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+_lib.pn2x_bn_relu_max.argtypes = [ctypes.POINTER(_BnReluMaxProblem), _ci, _vp]
 _lib.pn2x_bn_relu_max.restype = _ci
 _lib.pn2x_bn_relu_max_bwd.argtypes = [_cl, _ci, _ci, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _vp]
 _lib.pn2x_bn_relu_max_bwd.restype = _ci
-_lib.pn2x_bn_sums_doubles.argtypes = [_ci]
-_lib.pn2x_bn_sums_doubles.restype = _ci
 _f32 = torch.float32
 
 
@@ -162,9 +181,11 @@ class _BnReluMax(torch.autograd.Function):
         st = _native._stream(y)
         with torch.cuda.device(y.device):
             _native._check(_lib.pn2x_bn_stats(R, C, py, ldy, ws_f.data_ptr(), st), "bn_stats")
-            _native._check(_lib.pn2x_bn_relu_max(G, K, C, py, ldy, ws_f.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _p(conv_bias), float(eps),
-                                                 float(momentum), _p(running_mean), _p(running_var), _p(nbt), saved[0].data_ptr(),
-                                                 saved[1].data_ptr(), out.data_ptr(), arg.data_ptr(), st), "bn_relu_max")
+            prob = _BnReluMaxProblem(y=py, sums=ws_f.data_ptr(), gamma=gamma.data_ptr(), beta=beta.data_ptr(), conv_bias=_p(conv_bias),
+                                     running_mean=_p(running_mean), running_var=_p(running_var), num_batches_tracked=_p(nbt),
+                                     save_mean=saved[0].data_ptr(), save_invstd=saved[1].data_ptr(), out=out.data_ptr(),
+                                     arg=arg.data_ptr(), groups=G, k=K, c=C, ldy=ldy, ldo=C, eps=float(eps), momentum=float(momentum))
+            _native._check(_lib.pn2x_bn_relu_max(*_records(prob), st), "bn_relu_max")
         ctx.save_for_backward(y, gamma, beta, saved, arg)
         ctx.ws_b, ctx.K, ctx.has_bias = ws_b, K, conv_bias is not None
         ctx.ws, ctx.ws_gen = ws, ws.generation
@@ -215,15 +236,19 @@ def rows_segment_sum(dout: torch.Tensor, inv, n_dst: int, din: torch.Tensor, wei
     """din[b, i, :] (+)= sum over the entries e of target i of (weight[b, e] *) dout[b, e (// 3), :]  -- no atomics, every row of
     din written once.  dout (B,M,C) rows (contiguous, or a column block of a wider gradient: see _row_block);
     inv = inverse_index(idx.view(B, -1), n_dst); din (B,n_dst,>=C) rows."""
-    B, M, C = dout.shape
-    offsets, order = inv
-    t = 1 if weight is None else 3
     dout = _row_block(dout)
     with torch.cuda.device(dout.device):
-        _native._check(_lib.pn2x_rows_segment_sum(B, n_dst, M, t, C, dout.data_ptr(), dout.stride(1) if M > 1 else max(dout.stride(1), C), offsets.data_ptr(),
-                                                  order.data_ptr(), _p(weight), din.data_ptr(), din.stride(1), 1 if accumulate else 0,
-                                                  _native._stream(dout)), "rows_segment_sum")
+        _native._check(_lib.pn2x_rows_segment_sum(*_records(_segment_sum_problem(dout, inv, din, weight)), dout.shape[0], n_dst,
+                                                  1 if accumulate else 0, _native._stream(dout)), "rows_segment_sum")
     return din
+
+
+def _segment_sum_problem(dout, inv, din, weight=None) -> _RowsSegmentSumProblem:
+    """One problem of pn2x_rows_segment_sum: dout (B,M,C) as _row_block returns it, inv = (offsets, order), din (B,n_dst,>=C) rows."""
+    _, M, C = dout.shape
+    return _RowsSegmentSumProblem(dout=dout.data_ptr(), offsets=inv[0].data_ptr(), order=inv[1].data_ptr(), weight=_p(weight),
+                                  din=din.data_ptr(), m_src=M, t=1 if weight is None else 3, c=C,
+                                  ldo=dout.stride(1) if M > 1 else max(dout.stride(1), C), ldi=din.stride(1))
 
 
 def _row_block(t: torch.Tensor) -> torch.Tensor:
@@ -281,7 +306,7 @@ class _SaLayer1(torch.autograd.Function):
         col = 0
         st = _native._stream(xyz)
         ws = aux.get("ws") if aux is not None else None  # the consumer stacks' workspace: BatchNorm statistics taken on the way
-        pending = []  # per scale (common args, per-scale args, sums slice): launched alone, or two scales as one pair launch
+        pending = []  # per scale its problem record (sums NULL: no statistics asked for) and the tensors it points into
         for idx, wx in zip(idxs, wxs):
             K, C1 = idx.shape[2], wx.shape[0]
             out = torch.empty((B, S * K, C1), dtype=_f32, device=xyz.device)
@@ -290,26 +315,27 @@ class _SaLayer1(torch.autograd.Function):
                 wx = wx.contiguous().float()
             sm = ws.take(_lib.pn2x_bn_sums_doubles(C1)) if ws is not None else None
             # (the (C1, 3) block is read in place: a column block of the layer's weight)
-            pending.append((K, C1, None if a1f is None else a1f.data_ptr() + 4 * col, 0 if a1f is None else a1f.stride(1),
-                            wx.data_ptr(), wx.stride(0) if C1 > 1 else 3, None if cadd is None else cadd.data_ptr() + 4 * col,
-                            0 if cadd is None else cadd.stride(1), _native._ptr(idx, "idx", torch.int32, B * S * K), out.data_ptr(),
-                            rel.data_ptr(), sm, wx))
+            pending.append((_SaLayer1StatsProblem(
+                a1f=None if a1f is None else a1f.data_ptr() + 4 * col, wx=wx.data_ptr(), cadd=None if cadd is None else cadd.data_ptr() + 4 * col,
+                idx=_native._ptr(idx, "idx", torch.int32, B * S * K), out=out.data_ptr(), rel_out=rel.data_ptr(), sums=_p(sm), k=K, c1=C1,
+                a1f_ld=0 if a1f is None else a1f.stride(1), wx_ld=wx.stride(0) if C1 > 1 else 3,
+                cadd_ld=0 if cadd is None else cadd.stride(1)), wx))
             outs.append(out)
             rels.append(rel)
             sums.append(sm)
             col += C1
         with torch.cuda.device(xyz.device):
-            if PAIR_SCALES and len(pending) == 2 and all(p[11] is not None for p in pending):
-                pa, pb = pending
-                _native._check(_lib.pn2x_sa_layer1_stats_pair(B, N, S, xyz.data_ptr(), cxyz.data_ptr(), *pa[:11], pa[11].data_ptr(),
-                                                              *pb[:11], pb[11].data_ptr(), st), "sa_layer1_stats_pair")
+            probs = [p for p, _wx in pending]
+            shared = (B, N, S, xyz.data_ptr(), cxyz.data_ptr(), st)
+            if PAIR_SCALES and len(probs) == 2 and all(p.sums for p in probs):
+                _native._check(_lib.pn2x_sa_layer1_stats(*_records(*probs), *shared), "sa_layer1_stats")
             else:
-                for (K, C1, pa1f, lda, pwx, ldw, pcadd, ldc, pidx, pout, prel, sm, _wx) in pending:
-                    args = (B, N, S, K, C1, pa1f, lda, xyz.data_ptr(), cxyz.data_ptr(), pwx, ldw, pcadd, ldc, pidx, pout, prel)
-                    if sm is not None:
-                        _native._check(_lib.pn2x_sa_layer1_stats(*args, sm.data_ptr(), st), "sa_layer1_stats")
+                for p in probs:
+                    if p.sums:
+                        _native._check(_lib.pn2x_sa_layer1_stats(*_records(p), *shared), "sa_layer1_stats")
                     else:
-                        _native._check(_lib.pn2x_sa_layer1(*args, st), "sa_layer1")
+                        _native._check(_lib.pn2x_sa_layer1(B, N, S, p.k, p.c1, p.a1f, p.a1f_ld, xyz.data_ptr(), cxyz.data_ptr(), p.wx, p.wx_ld,
+                                                           p.cadd, p.cadd_ld, p.idx, p.out, p.rel_out, st), "sa_layer1")
         ctx.aux = aux
         if aux is not None:
             aux["rel"], aux["dwx"] = list(rels), {}
@@ -339,15 +365,12 @@ class _SaLayer1(torch.autograd.Function):
         douts = [dy.contiguous() for dy in douts]
         paired = False
         if PAIR_SCALES and n == 2 and d_a1f is not None and fits and invs:
-            # the two scales scatter into two column blocks of the same rows: one launch (pn2x_rows_segment_sum_pair)
+            # the two scales scatter into two column blocks of the same rows: one call, one launch where the pair kernel applies
             (da, db_), Bq = douts, douts[0].shape[0]
             ca, cb = da.shape[2], db_.shape[2]
-            blk_a, blk_b = d_a1f[:, :, :ca], d_a1f[:, :, ca:ca + cb]
+            probs = _records(_segment_sum_problem(da, invs[0:2], d_a1f[:, :, :ca]), _segment_sum_problem(db_, invs[2:4], d_a1f[:, :, ca:ca + cb]))
             with torch.cuda.device(dev):
-                _native._check(_lib.pn2x_rows_segment_sum_pair(
-                    Bq, a1f_shape[1], da.shape[1], ca, da.data_ptr(), da.stride(1), invs[0].data_ptr(), invs[1].data_ptr(), blk_a.data_ptr(),
-                    blk_a.stride(1), db_.shape[1], cb, db_.data_ptr(), db_.stride(1), invs[2].data_ptr(), invs[3].data_ptr(), blk_b.data_ptr(),
-                    blk_b.stride(1), 0, _native._stream(da)), "rows_segment_sum_pair")
+                _native._check(_lib.pn2x_rows_segment_sum(*probs, Bq, a1f_shape[1], 0, _native._stream(da)), "rows_segment_sum")
             paired = True
         # the centre term's gradient = per centroid the sum of its K consecutive rows: for two scales ONE segment-sum launch over
         # trivial lists (group g <- rows g K ... g K + K - 1) instead of two torch reductions
@@ -356,12 +379,9 @@ class _SaLayer1(torch.autograd.Function):
             (da, db_), Bq = douts, douts[0].shape[0]
             ca, cb = da.shape[2], db_.shape[2]
             ga, gb = _group_lists(Bq, S, da.shape[1] // S, dev), _group_lists(Bq, S, db_.shape[1] // S, dev)
-            blk_a, blk_b = d_cadd[:, :, :ca], d_cadd[:, :, ca:ca + cb]
+            probs = _records(_segment_sum_problem(da, ga, d_cadd[:, :, :ca]), _segment_sum_problem(db_, gb, d_cadd[:, :, ca:ca + cb]))
             with torch.cuda.device(dev):
-                _native._check(_lib.pn2x_rows_segment_sum_pair(
-                    Bq, S, da.shape[1], ca, da.data_ptr(), da.stride(1), ga[0].data_ptr(), ga[1].data_ptr(), blk_a.data_ptr(), blk_a.stride(1),
-                    db_.shape[1], cb, db_.data_ptr(), db_.stride(1), gb[0].data_ptr(), gb[1].data_ptr(), blk_b.data_ptr(), blk_b.stride(1), 0,
-                    _native._stream(da)), "rows_segment_sum_pair")
+                _native._check(_lib.pn2x_rows_segment_sum(*probs, Bq, S, 0, _native._stream(da)), "rows_segment_sum")
             cadd_done = True
         for i, (dy, idx, rel) in enumerate(zip(douts, idxs, rels)):
             B, SK, C1 = dy.shape

@@ -20,6 +20,7 @@ from __future__ import annotations
 
 import ctypes
 import os as _os
+from typing import NamedTuple
 
 import torch
 
@@ -32,7 +33,16 @@ _lib.pn2x_tg_supported.argtypes = [_ci, _ci]
 _lib.pn2x_tg_supported.restype = _ci
 _lib.pn2x_tg_fwd.argtypes = [_cl, _ci, _ci, _vp, _ci, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _cf, _cf, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
 _lib.pn2x_tg_fwd.restype = _ci
-_lib.pn2x_tg_fwd2.argtypes = _lib.pn2x_tg_fwd.argtypes
+
+
+class _TgFwd2Problem(ctypes.Structure):
+    """include/pn2_ext.h: pn2x_tg_fwd2_problem (144 bytes)."""
+    _fields_ = ([(n, _vp) for n in ("x", "w", "y", "sums_in", "gamma", "beta", "conv_bias", "running_mean", "running_var",
+                                    "num_batches_tracked", "save_mean", "save_invstd", "sums_out")] +
+                [("rows", _cl)] + [(n, _ci) for n in ("k", "n", "ldx", "ldw", "ldy")] + [("eps", _cf), ("momentum", _cf), ("reserved", _ci)])
+
+
+_lib.pn2x_tg_fwd2.argtypes = [ctypes.POINTER(_TgFwd2Problem), _ci, _vp]
 _lib.pn2x_tg_fwd2.restype = _ci
 _lib.pn2x_tg_fwd2_supported.argtypes = [_ci, _ci]
 _lib.pn2x_tg_fwd2_supported.restype = _ci
@@ -49,17 +59,23 @@ _lib.pn2x_tg_bwd_supported.argtypes = [_ci, _ci]
 _lib.pn2x_tg_bwd_supported.restype = _ci
 _lib.pn2x_tg_bwd_partials.argtypes = [_cl, _ci, _ci]
 _lib.pn2x_tg_bwd_partials.restype = _ci
-_lib.pn2x_tg_bwd_slice.argtypes = [_cl, _ci, _ci, _ci, _vp, _ci, _vp, _ci, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _vp, _ci, _vp, _vp,
-                                   _vp, _vp, _vp, _ci, _vp, _vp, _cl, _vp, _vp, _ci, _ci, _vp]
+
+
+class _TgBwdSliceProblem(ctypes.Structure):
+    """include/pn2_ext.h: pn2x_tg_bwd_slice_problem (224 bytes)."""
+    _fields_ = ([(n, _vp) for n in ("g", "arg", "yi", "mean_i", "invstd_i", "gamma_i", "beta_i", "sums_bwd_i", "w", "yp", "mean_p",
+                                    "invstd_p", "gamma_p", "beta_p", "gp", "sums_bwd_p", "partial", "dw", "g_add")] +
+                [("rows", _cl), ("partial_floats", _cl)] +
+                [(n, _ci) for n in ("n", "k", "gmode", "ldg", "ldarg", "kmax", "ldyi", "sums_ld", "ldw", "ldyp", "ldgp", "ldga", "raw_out",
+                                    "reserved")])
+
+
+_lib.pn2x_tg_bwd_slice.argtypes = [ctypes.POINTER(_TgBwdSliceProblem), _ci, ctypes.POINTER(_ci), _vp]
 _lib.pn2x_tg_bwd_slice.restype = _ci
 _lib.pn2x_tg_fwd2_pair_supported.argtypes = [_ci, _ci]
 _lib.pn2x_tg_fwd2_pair_supported.restype = _ci
 _lib.pn2x_tg_bwd_pair_supported.argtypes = [_ci, _ci]
 _lib.pn2x_tg_bwd_pair_supported.restype = _ci
-_lib.pn2x_tg_fwd2_pair.argtypes = _lib.pn2x_tg_fwd.argtypes[:-1] + [_cl] + _lib.pn2x_tg_fwd.argtypes[3:-1] + [_vp]  # (k, n once)
-_lib.pn2x_tg_fwd2_pair.restype = _ci
-_lib.pn2x_tg_bwd_slice_pair.argtypes = _lib.pn2x_tg_bwd_slice.argtypes[:-1] * 2 + [ctypes.POINTER(_ci), _vp]
-_lib.pn2x_tg_bwd_slice_pair.restype = _ci
 PAIR_LAUNCH = _os.environ.get("HOTRACK_STACK_PAIR_LAUNCH", "1") != "0"  # one launch for equal-shaped layers of two sibling stacks
 _lib.pn2x_tg_reduce_multi.argtypes = [_ci, ctypes.POINTER(_vp), ctypes.POINTER(_ci), ctypes.POINTER(_ci), ctypes.POINTER(_vp),
                                       ctypes.POINTER(_vp), ctypes.POINTER(_ci), ctypes.POINTER(_ci), ctypes.POINTER(_vp),
@@ -78,7 +94,13 @@ def _bwd_slices(c_in: int, c_out: int):
     return None
 
 
-_lib.pn2x_bn_bwd_reduce_routed.argtypes = [_cl, _ci, _ci, _vp, _ci, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp]
+class _BnBwdReduceRoutedProblem(ctypes.Structure):
+    """include/pn2_ext.h: pn2x_bn_bwd_reduce_routed_problem (96 bytes)."""
+    _fields_ = ([(n, _vp) for n in ("dout", "arg", "y", "mean", "invstd", "gamma", "beta", "sums")] + [("groups", _cl)] +
+                [(n, _ci) for n in ("k", "c", "ldd", "lda", "ldy", "reserved")])
+
+
+_lib.pn2x_bn_bwd_reduce_routed.argtypes = [ctypes.POINTER(_BnBwdReduceRoutedProblem), _ci, _vp]
 _lib.pn2x_bn_bwd_reduce_routed.restype = _ci
 _lib.pn2x_tg_bwd_set_variant.argtypes = [_ci]
 _lib.pn2x_tg_bwd_set_variant.restype = _ci
@@ -283,17 +305,15 @@ def _reduce_items(items):
         _native._check(_lib.pn2x_tg_reduce_multi(n, part, P, numel, dw, sm, ch, sld, dg, db, dbi, st), "tg_reduce_multi")
 
 
-_lib.pn2x_bn_bwd_apply_rel.argtypes = [_cl, _ci, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _cl, _vp, _vp]
+class _BnBwdApplyRelProblem(ctypes.Structure):
+    """include/pn2_ext.h: pn2x_bn_bwd_apply_rel_problem (152 bytes)."""
+    _fields_ = ([(n, _vp) for n in ("g", "y", "mean", "invstd", "gamma", "beta", "sums", "dy", "dgamma", "dbeta", "dbias", "rel", "scratch",
+                                    "dwx")] +
+                [("rows", _cl), ("scratch_floats", _cl)] + [(n, _ci) for n in ("c", "ldg", "ldy", "relu", "ldo", "reserved")])
+
+
+_lib.pn2x_bn_bwd_apply_rel.argtypes = [ctypes.POINTER(_BnBwdApplyRelProblem), _ci, _vp]
 _lib.pn2x_bn_bwd_apply_rel.restype = _ci
-_lib.pn2x_bn_bwd_reduce_routed_pair.argtypes = _lib.pn2x_bn_bwd_reduce_routed.argtypes[:-1] * 2 + [_vp]
-_lib.pn2x_bn_bwd_reduce_routed_pair.restype = _ci
-_MAX_LD = _t._lib.pn2x_bn_relu_max.argtypes[:-2] + [_ci, _vp]  # (..., out, ldo, arg): the output rows ldo floats apart
-_lib.pn2x_bn_relu_max_ld.argtypes = _MAX_LD + [_vp]
-_lib.pn2x_bn_relu_max_ld.restype = _ci
-_lib.pn2x_bn_relu_max_pair.argtypes = _MAX_LD * 2 + [_vp]
-_lib.pn2x_bn_relu_max_pair.restype = _ci
-_lib.pn2x_bn_bwd_apply_rel_pair.argtypes = _lib.pn2x_bn_bwd_apply_rel.argtypes[:-1] * 2 + [_vp]
-_lib.pn2x_bn_bwd_apply_rel_pair.restype = _ci
 _lib.pn2x_bn_bwd_apply_rel_scratch_floats.argtypes = [_cl, _ci]
 _lib.pn2x_bn_bwd_apply_rel_scratch_floats.restype = _cl
 _lib.pn2x_bn_bwd_apply.argtypes = [_cl, _ci, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _vp, _ci, _vp, _vp, _vp, _vp]
@@ -318,8 +338,16 @@ class Layer:
 # The forward / backward of ONE stack are generators: wherever a launch could be grouped with the same launch of a sibling stack
 # (the W-resident forward and the one-kernel layer backward of csrc/train_fwd.hip / train_bwd.hip), they yield the launch request
 # instead of issuing it; _drive() advances one or two stacks in lockstep and issues each request alone or, for two stacks of
-# the same layer shape, as one pair launch (pn2x_tg_fwd2_pair / pn2x_tg_bwd_slice_pair: the two neighbourhood sizes of a
-# keypoint-query module).  Everything else is launched where it stands.
+# the same layer shape, as one call with two problem records (one launch where a pair kernel exists: the two neighbourhood sizes
+# of a keypoint-query module).  Everything else is launched where it stands.
+class _Request(NamedTuple):
+    kind: str                 # "fwd2" | "max" | "routed" | "bwd" | "apply_rel"
+    record: ctypes.Structure  # the problem record of the kind's entry
+    stream: int
+    device: torch.device
+    partials: int = 0         # "bwd": the partial tiles the problem writes when it is launched alone (pn2x_tg_bwd_partials)
+
+
 class _Fwd:
     @staticmethod
     def gen(y1, K, ws, metas, aux, tensors, out_dst=None):
@@ -353,13 +381,17 @@ class _Fwd:
                 y = torch.empty((R, N), dtype=_f32, device=dev)
                 sv = torch.empty((2, Kc), dtype=_f32, device=dev)
                 x = ys[-1]
-                fargs = (R, Kc, N, x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), y.data_ptr(), N,
-                         ws_f[i - 1].data_ptr(), gamma_p.data_ptr(), beta_p.data_ptr(), _p(bias_p), float(eps),
-                         float(mom), _p(rm), _p(rv), _p(nbt), sv[0].data_ptr(), sv[1].data_ptr(), ws_f[i].data_ptr())
+                f = _TgFwd2Problem(x=x.data_ptr(), w=w.data_ptr(), y=y.data_ptr(), sums_in=ws_f[i - 1].data_ptr(), gamma=gamma_p.data_ptr(),
+                                   beta=beta_p.data_ptr(), conv_bias=_p(bias_p), running_mean=_p(rm), running_var=_p(rv),
+                                   num_batches_tracked=_p(nbt), save_mean=sv[0].data_ptr(), save_invstd=sv[1].data_ptr(),
+                                   sums_out=ws_f[i].data_ptr(), rows=R, k=Kc, n=N, ldx=x.stride(0), ldw=w.stride(0), ldy=N, eps=float(eps),
+                                   momentum=float(mom))
                 if FWD2 and _lib.pn2x_tg_fwd2_supported(Kc, N):
-                    yield ("fwd2", fargs, st, dev)  # (issued by _drive: alone, or grouped with a sibling stack's)
+                    yield _Request("fwd2", f, st, dev)  # (issued by _drive: alone, or grouped with a sibling stack's)
                 else:
-                    _native._check(_lib.pn2x_tg_fwd(*fargs, st), "tg_fwd")
+                    _native._check(_lib.pn2x_tg_fwd(f.rows, f.k, f.n, f.x, f.ldx, f.w, f.ldw, f.y, f.ldy, f.sums_in, f.gamma, f.beta,
+                                                    f.conv_bias, f.eps, f.momentum, f.running_mean, f.running_var, f.num_batches_tracked,
+                                                    f.save_mean, f.save_invstd, f.sums_out, st), "tg_fwd")
                 ys.append(y)
                 saved.append(sv)
             # top of the stack: the streaming kernels (they also finalise the last layer's statistics)
@@ -378,9 +410,12 @@ class _Fwd:
                 else:
                     out = torch.empty((G, C), dtype=_f32, device=dev)
                 arg = torch.empty((G, C), dtype=torch.int32, device=dev)
-                yield ("max", (G, K, C, yl.data_ptr(), yl.stride(0), ws_f[L - 1].data_ptr(), gamma.data_ptr(), beta.data_ptr(), _p(bias),
-                               float(eps), float(mom), _p(rm), _p(rv), _p(nbt), sv[0].data_ptr(), sv[1].data_ptr(), out.data_ptr(),
-                               out.stride(0) if G > 1 else C, arg.data_ptr()), st, dev)  # (issued by _drive: alone, or with the sibling stack's as one pair launch)
+                # (issued by _drive: alone, or with the sibling stack's as one pair launch)
+                yield _Request("max", _t._BnReluMaxProblem(
+                    y=yl.data_ptr(), sums=ws_f[L - 1].data_ptr(), gamma=gamma.data_ptr(), beta=beta.data_ptr(), conv_bias=_p(bias),
+                    running_mean=_p(rm), running_var=_p(rv), num_batches_tracked=_p(nbt), save_mean=sv[0].data_ptr(),
+                    save_invstd=sv[1].data_ptr(), out=out.data_ptr(), arg=arg.data_ptr(), groups=G, k=K, c=C, ldy=yl.stride(0),
+                    ldo=out.stride(0) if G > 1 else C, eps=float(eps), momentum=float(mom)), st, dev)
             else:
                 out = torch.empty((R, C), dtype=_f32, device=dev)
                 _native._check(_lib.pn2x_bn_relu_apply(R, C, yl.data_ptr(), yl.stride(0), ws_f[L - 1].data_ptr(), gamma.data_ptr(),
@@ -451,9 +486,10 @@ class _Bwd:
             if routed:
                 # the routed gradient is non-zero in one row per (group, channel): the sums need the arg-max rows only, and the
                 # one-kernel layer backward below routes dout on load (no rows x C gradient tensor at all)
-                yield ("routed", (R // K, K, Cl, dout.data_ptr(), dout.stride(0), arg.data_ptr(), Cl, yl.data_ptr(), yl.stride(0),
-                                  svl[0].data_ptr(), svl[1].data_ptr(), gam(L - 1).data_ptr(), bet(L - 1).data_ptr(),
-                                  sums[L - 1].data_ptr()), st, dev)
+                yield _Request("routed", _BnBwdReduceRoutedProblem(
+                    dout=dout.data_ptr(), arg=arg.data_ptr(), y=yl.data_ptr(), mean=svl[0].data_ptr(), invstd=svl[1].data_ptr(),
+                    gamma=gam(L - 1).data_ptr(), beta=bet(L - 1).data_ptr(), sums=sums[L - 1].data_ptr(), groups=R // K, k=K, c=Cl,
+                    ldd=dout.stride(0), lda=Cl, ldy=yl.stride(0)), st, dev)
             elif K and ROUTE_DENSE:
                 # the reduction reads dout / arg / y_L anyway: it also writes the routed, masked gradient once (dense), and the two
                 # GEMMs of the top layer read that instead of routing through arg-max on every load (their slowest variant)
@@ -482,17 +518,19 @@ class _Bwd:
                         np_ = int(_lib.pn2x_tg_bwd_partials(R, wd, Kc))
                         partial = torch.empty(np_ * wd * Kc, dtype=_f32, device=dev)
                         o4 = 4 * off
-                        bargs = (
-                            R, wd, Kc, gmode, g.data_ptr() + o4, g.stride(0), (arg.data_ptr() + o4) if gmode == 2 else None,
-                            arg.stride(0) if gmode == 2 else 4, K if gmode == 2 else 1, yi.data_ptr() + o4, yi.stride(0), svi[0].data_ptr() + o4, svi[1].data_ptr() + o4,
-                            gam(i).data_ptr() + o4, bet(i).data_ptr() + o4, sums[i].data_ptr() + 8 * off, N,
-                            wc.data_ptr() + o4 * wc.stride(0), wc.stride(0), yp.data_ptr(), yp.stride(0), svp[0].data_ptr(),
-                            svp[1].data_ptr(), gam(i - 1).data_ptr(), bet(i - 1).data_ptr(), gp.data_ptr(), Kc, sums[i - 1].data_ptr(),
-                            partial.data_ptr(), partial.numel(), dw.data_ptr() + o4 * Kc, gp.data_ptr() if j else None, Kc,
-                            1 if j + 1 < len(slices) else 0)
+                        brec = _TgBwdSliceProblem(
+                            g=g.data_ptr() + o4, arg=(arg.data_ptr() + o4) if gmode == 2 else None, yi=yi.data_ptr() + o4,
+                            mean_i=svi[0].data_ptr() + o4, invstd_i=svi[1].data_ptr() + o4, gamma_i=gam(i).data_ptr() + o4,
+                            beta_i=bet(i).data_ptr() + o4, sums_bwd_i=sums[i].data_ptr() + 8 * off, w=wc.data_ptr() + o4 * wc.stride(0),
+                            yp=yp.data_ptr(), mean_p=svp[0].data_ptr(), invstd_p=svp[1].data_ptr(), gamma_p=gam(i - 1).data_ptr(),
+                            beta_p=bet(i - 1).data_ptr(), gp=gp.data_ptr(), sums_bwd_p=sums[i - 1].data_ptr(), partial=partial.data_ptr(),
+                            dw=dw.data_ptr() + o4 * Kc, g_add=gp.data_ptr() if j else None, rows=R, partial_floats=partial.numel(), n=wd,
+                            k=Kc, gmode=gmode, ldg=g.stride(0), ldarg=arg.stride(0) if gmode == 2 else 4, kmax=K if gmode == 2 else 1,
+                            ldyi=yi.stride(0), sums_ld=N, ldw=wc.stride(0), ldyp=yp.stride(0), ldgp=Kc, ldga=Kc,
+                            raw_out=1 if j + 1 < len(slices) else 0)
                         # issued by _drive; the answer is the number of partial tiles actually written (a pair launch gives this
                         # problem a share of the grid, fewer workgroups than it would get alone)
-                        np_ = yield ("bwd", bargs, st, dev, np_)
+                        np_ = yield _Request("bwd", brec, st, dev, np_)
                         item = (partial, np_, dw[off:off + wd], sums[i][off:], [t_[off:off + wd] for t_ in dpar], st, N)
                         if defer:
                             _defer(item)
@@ -536,9 +574,11 @@ class _Bwd:
                 scratch = torch.empty(nf, dtype=_f32, device=dev)
                 dwx = torch.empty((C1, 3), dtype=_f32, device=dev)
                 # (issued by _drive: alone, or with the sibling stack's as one pair launch)
-                yield ("apply_rel", (R, C1, g.data_ptr(), g.stride(0), y1.data_ptr(), y1.stride(0), sv1[0].data_ptr(), sv1[1].data_ptr(),
-                                     gam(0).data_ptr(), bet(0).data_ptr(), 0, sums[0].data_ptr(), dy1.data_ptr(), C1, dpar[0].data_ptr(),
-                                     dpar[1].data_ptr(), dpar[2].data_ptr(), rel.data_ptr(), scratch.data_ptr(), nf, dwx.data_ptr()), st, dev)
+                yield _Request("apply_rel", _BnBwdApplyRelProblem(
+                    g=g.data_ptr(), y=y1.data_ptr(), mean=sv1[0].data_ptr(), invstd=sv1[1].data_ptr(), gamma=gam(0).data_ptr(),
+                    beta=bet(0).data_ptr(), sums=sums[0].data_ptr(), dy=dy1.data_ptr(), dgamma=dpar[0].data_ptr(), dbeta=dpar[1].data_ptr(),
+                    dbias=dpar[2].data_ptr(), rel=rel.data_ptr(), scratch=scratch.data_ptr(), dwx=dwx.data_ptr(), rows=R, scratch_floats=nf,
+                    c=C1, ldg=g.stride(0), ldy=y1.stride(0), relu=0, ldo=C1), st, dev)
                 adict["dwx"][ai] = dwx
             else:
                 _native._check(_lib.pn2x_bn_bwd_apply(R, C1, g.data_ptr(), g.stride(0), y1.data_ptr(), y1.stride(0), sv1[0].data_ptr(),
@@ -551,54 +591,32 @@ class _Bwd:
         return dy1, grads
 
 
-def _pairable(a, b):
+def _pairable(a: _Request, b: _Request) -> bool:
     """Two launch requests that one pair launch can serve: same kind, same layer shape (and gradient source), same stream."""
-    if a[0] != b[0] or a[2] != b[2] or a[3] != b[3] or not PAIR_LAUNCH:
+    if a.kind != b.kind or a.stream != b.stream or a.device != b.device or not PAIR_LAUNCH:
         return False
-    if a[0] == "fwd2":
-        return a[1][1:3] == b[1][1:3] and bool(_lib.pn2x_tg_fwd2_pair_supported(a[1][1], a[1][2]))
-    if a[0] in ("apply_rel", "max", "routed"):
-        return True
-    return a[1][1:4] == b[1][1:4] and bool(_lib.pn2x_tg_bwd_pair_supported(a[1][2], a[1][1]))
+    ra, rb = a.record, b.record
+    if a.kind == "fwd2":
+        return (ra.k, ra.n) == (rb.k, rb.n) and bool(_lib.pn2x_tg_fwd2_pair_supported(ra.k, ra.n))
+    if a.kind == "bwd":
+        return (ra.n, ra.k, ra.gmode) == (rb.n, rb.k, rb.gmode) and bool(_lib.pn2x_tg_bwd_pair_supported(ra.k, ra.n))
+    return True
 
 
-def _issue(req):
-    kind, args, st, dev = req[:4]
-    with torch.cuda.device(dev):
-        if kind == "fwd2":
-            _native._check(_lib.pn2x_tg_fwd2(*args, st), "tg_fwd2")
-            return None
-        if kind == "apply_rel":
-            _native._check(_lib.pn2x_bn_bwd_apply_rel(*args, st), "bn_bwd_apply_rel")
-            return None
-        if kind == "max":
-            _native._check(_lib.pn2x_bn_relu_max_ld(*args, st), "bn_relu_max")
-            return None
-        if kind == "routed":
-            _native._check(_lib.pn2x_bn_bwd_reduce_routed(*args, st), "bn_bwd_reduce_routed")
-            return None
-        _native._check(_lib.pn2x_tg_bwd_slice(*args, st), "tg_bwd")
-        return req[4]
-
-
-def _issue_pair(a, b):
-    kind, st, dev = a[0], a[2], a[3]
-    with torch.cuda.device(dev):
-        if kind == "fwd2":
-            _native._check(_lib.pn2x_tg_fwd2_pair(*a[1], b[1][0], *b[1][3:], st), "tg_fwd2_pair")
-            return None, None
-        if kind == "apply_rel":
-            _native._check(_lib.pn2x_bn_bwd_apply_rel_pair(*a[1], *b[1], st), "bn_bwd_apply_rel_pair")
-            return None, None
-        if kind == "max":
-            _native._check(_lib.pn2x_bn_relu_max_pair(*a[1], *b[1], st), "bn_relu_max_pair")
-            return None, None
-        if kind == "routed":
-            _native._check(_lib.pn2x_bn_bwd_reduce_routed_pair(*a[1], *b[1], st), "bn_bwd_reduce_routed_pair")
-            return None, None
-        nparts = (_ci * 2)()
-        _native._check(_lib.pn2x_tg_bwd_slice_pair(*a[1], *b[1], nparts, st), "tg_bwd_pair")
-        return int(nparts[0]), int(nparts[1])
+def _issue(requests):
+    """Issue one request, or two pairable ones, through the entry of their kind; returns what each generator is answered: for a
+    layer backward the number of partial tiles its problem wrote, None otherwise."""
+    first, count = requests[0], len(requests)
+    records = (type(first.record) * count)(*(r.record for r in requests))
+    with torch.cuda.device(first.device):
+        if first.kind == "bwd":
+            nparts = (_ci * count)(*(r.partials for r in requests))
+            _native._check(_lib.pn2x_tg_bwd_slice(records, count, nparts if count > 1 else None, first.stream), "tg_bwd")
+            return [int(n) for n in nparts]
+        entry = {"fwd2": _lib.pn2x_tg_fwd2, "max": _lib.pn2x_bn_relu_max, "routed": _lib.pn2x_bn_bwd_reduce_routed,
+                 "apply_rel": _lib.pn2x_bn_bwd_apply_rel, }[first.kind]
+        _native._check(entry(records, count, first.stream), first.kind)
+    return [None] * count
 
 
 class _guarded_by_drive:
@@ -636,11 +654,11 @@ def _drive(gens, dev):
                         alive.remove(i)
                     answer[i] = None
                 if len(reqs) == 2 and _pairable(*reqs.values()):
-                    (i, a), (j, b) = reqs.items()
-                    answer[i], answer[j] = _issue_pair(a, b)
+                    for i, ans in zip(reqs, _issue(list(reqs.values()))):
+                        answer[i] = ans
                 else:
                     for i, r in reqs.items():
-                        answer[i] = _issue(r)
+                        answer[i], = _issue([r])
     finally:
         for g in gens:
             g.close()
@@ -716,14 +734,7 @@ def mlp_stack(y1: torch.Tensor, layers, ws, max_over: int = 0, aux=None) -> torc
     if len(layers) == 1:  # nothing to fuse: the streaming kernels
         l = layers[0]
         return _t.bn_relu_max(y1, max_over, l.bn, ws, l.conv_bias) if max_over else _t.bn_relu(y1, l.bn, ws, l.conv_bias)
-    metas, tensors = [], []
-    for i, l in enumerate(layers):
-        bn = l.bn
-        track = bn.track_running_stats and bn.running_mean is not None
-        metas.append((bn.running_mean if track else None, bn.running_var if track else None,
-                      bn.num_batches_tracked if track else None, bn.eps, bn.momentum if bn.momentum is not None else 0.1))
-        none = y1.new_empty(0)
-        tensors += [l.weight if i else none, bn.weight, bn.bias, l.conv_bias if l.conv_bias is not None else none]
+    metas, tensors = _stack_inputs(y1, layers)
     return _Stack.apply(y1, int(max_over), ws, metas, aux, *tensors)
 
 

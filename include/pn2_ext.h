@@ -610,20 +610,21 @@ int pn2x_bn_relu_bwd(long rows, int c, const float *dh, int ldd, const float *y,
 int pn2x_sa_layer1(int b, int n, int s, int k, int c1, const float *a1f, int a1f_ld, const float *xyz, const float *cxyz,
                    const float *wx, int wx_ld, const float *cadd, int cadd_ld, const int *idx, float *out, float *rel_out,
                    void *stream);
-/* the same, also accumulating the BatchNorm statistics of `out` into sums (pn2x_bn_sums_doubles(c1) doubles, zeroed by the caller,
- * as pn2x_bn_stats would): the layer that follows is a train-mode BatchNorm (pointnet_utils.py:399-401), and its separate
- * statistics pass over the (b s k, c1) tensor -- one launch per scale and step -- is saved */
-int pn2x_sa_layer1_stats(int b, int n, int s, int k, int c1, const float *a1f, int a1f_ld, const float *xyz, const float *cxyz,
-                         const float *wx, int wx_ld, const float *cadd, int cadd_ld, const int *idx, float *out, float *rel_out,
-                         double *sums, void *stream);
-/* ... for the TWO neighbourhood sizes of one module (pointnet_utils.py:566-581: same clouds, coordinates and centres; per scale its
- * neighbour list, weight block, per-point / per-centre terms, output, relative coordinates and statistics) in ONE launch: alone, the
- * K = 16 scale is a 12 us launch for a quarter of the K = 64 scale's rows.  Same results as two pn2x_sa_layer1_stats calls. */
-int pn2x_sa_layer1_stats_pair(int b, int n, int s, const float *xyz, const float *cxyz, int k_a, int c1_a, const float *a1f_a, int a1f_ld_a,
-                              const float *wx_a, int wx_ld_a, const float *cadd_a, int cadd_ld_a, const int *idx_a, float *out_a,
-                              float *rel_out_a, double *sums_a, int k_b, int c1_b, const float *a1f_b, int a1f_ld_b, const float *wx_b,
-                              int wx_ld_b, const float *cadd_b, int cadd_ld_b, const int *idx_b, float *out_b, float *rel_out_b,
-                              double *sums_b, void *stream);
+/* The same for `count` (1 or 2) scales of one module (pointnet_utils.py:566-581: same clouds, coordinates and centres; per scale
+ * its neighbour list, weight block, per-point / per-centre terms, output and relative coordinates), also accumulating the
+ * BatchNorm statistics of every `out` into its `sums` (pn2x_bn_sums_doubles(c1) doubles, zeroed by the caller, as pn2x_bn_stats
+ * would): the layer that follows is a train-mode BatchNorm (pointnet_utils.py:399-401), and its separate statistics pass over
+ * the (b s k, c1) tensor is saved.  Two scales share ONE launch where both can take their statistics in it (alone, the K = 16
+ * scale is a 12 us launch for a quarter of the K = 64 scale's rows); a scale that cannot runs pn2x_sa_layer1 + pn2x_bn_stats. */
+typedef struct pn2x_sa_layer1_stats_problem {
+    const float *a1f, *wx, *cadd;
+    const int *idx;
+    float *out, *rel_out;
+    double *sums;
+    int k, c1, a1f_ld, wx_ld, cadd_ld, reserved;
+} pn2x_sa_layer1_stats_problem; /* 80 bytes */
+int pn2x_sa_layer1_stats(const pn2x_sa_layer1_stats_problem *problems, int count, int b, int n, int s, const float *xyz,
+                         const float *cxyz, void *stream);
 /*
  * Transpose of pn2x_gather_rows (group_points_grad on point-major rows, reference group_points_gpu.cu:8-25):
  *   din[b, idx[b,j], :] += dout[b, j, :]      dout (b, m, ldo), idx (b, m) int32, din (b, n, ldi) accumulated into.
@@ -648,13 +649,17 @@ int pn2x_three_interpolate_pm_grad(int b, int c, int m, int n, const float *dout
  * accumulate == 0 overwrites (nothing to pre-zero), != 0 adds to din.  The order inside a list is unspecified.
  */
 int pn2x_inverse_index(int b, int n_dst, int l, const int *idx, int *offsets, int *order, void *stream);
-int pn2x_rows_segment_sum(int b, int n_dst, int m_src, int t, int c, const float *dout, int ldo, const int *offsets,
-                          const int *order, const float *weight, float *din, int ldi, int accumulate, void *stream);
-/* t = 1 for TWO index lists over the same destination rows (the two neighbourhood sizes of a module scatter into two column blocks of
- * one gradient) in one launch where both take the one-thread-per-(destination, quad) kernel; two calls otherwise.  Same results. */
-int pn2x_rows_segment_sum_pair(int b, int n_dst, int m_a, int c_a, const float *dout_a, int ldo_a, const int *offsets_a, const int *order_a,
-                               float *din_a, int ldi_a, int m_b, int c_b, const float *dout_b, int ldo_b, const int *offsets_b,
-                               const int *order_b, float *din_b, int ldi_b, int accumulate, void *stream);
+/* `count` (1 or 2) index lists over the same destination rows (the two neighbourhood sizes of a module scatter into two column
+ * blocks of one gradient).  Two t == 1 problems share one launch where both take the one-thread-per-(destination, quad) kernel;
+ * one launch per problem otherwise.  Same results either way. */
+typedef struct pn2x_rows_segment_sum_problem {
+    const float *dout;
+    const int *offsets, *order;
+    const float *weight;
+    float *din;
+    int m_src, t, c, ldo, ldi, reserved;
+} pn2x_rows_segment_sum_problem; /* 64 bytes */
+int pn2x_rows_segment_sum(const pn2x_rows_segment_sum_problem *problems, int count, int b, int n_dst, int accumulate, void *stream);
 
 /*
  * Backward of group_points / gather_points (t = 1) and three_interpolate (t = 3) on the reference's channel-major layout with
@@ -677,23 +682,22 @@ int pn2x_scatter_cm(int t, int b, int c, int n_dst, int m_src, const float *grad
  * pn2x_bn_relu_max_bwd: backward through max + ReLU + BatchNorm given dout (groups, c): only the arg-max row of a group
  * receives dout (times the ReLU mask); dy (groups*k, ldo), dgamma, dbeta, dbias as pn2x_bn_relu_bwd.
  */
-int pn2x_bn_relu_max(long groups, int k, int c, const float *y, int ldy, const double *sums, const float *gamma, const float *beta,
-                     const float *conv_bias, float eps, float momentum, float *running_mean, float *running_var,
-                     long long *num_batches_tracked, float *save_mean, float *save_invstd, float *out, int *arg, void *stream);
-/* the same with the output rows ldo floats apart (`out` = a column block of a wider buffer: the scales of a multi-scale module,
- * reference pointnet_utils.py:405-409 / :583-590 `torch.cat(new_points_list, dim=1)`, write the halves of one tensor) */
-int pn2x_bn_relu_max_ld(long groups, int k, int c, const float *y, int ldy, const double *sums, const float *gamma, const float *beta,
-                        const float *conv_bias, float eps, float momentum, float *running_mean, float *running_var,
-                        long long *num_batches_tracked, float *save_mean, float *save_invstd, float *out, int ldo, int *arg, void *stream);
-/* pn2x_bn_relu_max_ld for two problems (the two neighbourhood sizes of a module) in ONE launch where both take the few-groups
- * kernel; two calls otherwise */
-int pn2x_bn_relu_max_pair(long groups_a, int k_a, int c_a, const float *y_a, int ldy_a, const double *sums_a, const float *gamma_a,
-                          const float *beta_a, const float *conv_bias_a, float eps_a, float momentum_a, float *running_mean_a,
-                          float *running_var_a, long long *nbt_a, float *save_mean_a, float *save_invstd_a, float *out_a, int ldo_a,
-                          int *arg_a, long groups_b, int k_b, int c_b, const float *y_b, int ldy_b, const double *sums_b,
-                          const float *gamma_b, const float *beta_b, const float *conv_bias_b, float eps_b, float momentum_b,
-                          float *running_mean_b, float *running_var_b, long long *nbt_b, float *save_mean_b, float *save_invstd_b,
-                          float *out_b, int ldo_b, int *arg_b, void *stream);
+/* `count` (1 or 2) problems.  The output rows are ldo floats apart: `out` may be a column block of a wider buffer (the scales of
+ * a multi-scale module, reference pointnet_utils.py:405-409 / :583-590 `torch.cat(new_points_list, dim=1)`, write the halves of
+ * one tensor).  Two problems (the two neighbourhood sizes of a module) share ONE launch where both take the few-groups kernel. */
+typedef struct pn2x_bn_relu_max_problem {
+    const float *y;
+    const double *sums;
+    const float *gamma, *beta, *conv_bias;
+    float *running_mean, *running_var;
+    long long *num_batches_tracked;
+    float *save_mean, *save_invstd, *out;
+    int *arg;
+    long groups;
+    int k, c, ldy, ldo;
+    float eps, momentum;
+} pn2x_bn_relu_max_problem; /* 128 bytes */
+int pn2x_bn_relu_max(const pn2x_bn_relu_max_problem *problems, int count, void *stream);
 int pn2x_bn_relu_max_bwd(long groups, int k, int c, const float *dout, const int *arg, const float *y, int ldy, const float *mean,
                          const float *invstd, const float *gamma, const float *beta, double *sums, float *dy, int ldo, float *dgamma,
                          float *dbeta, float *dbias, void *stream);
@@ -713,14 +717,16 @@ int pn2x_bn_bwd_reduce(long rows, int c, const float *dh, int ldd, const int *ar
                        void *stream);
 /* The same sums for a max-routed top layer from its arg-max rows only (groups x c gathered reads of y instead of rows x c):
  * dout (groups x c, row stride ldd: may be a column block of a wider gradient), arg (groups x c, row stride lda), y ((groups * k) x c).  The layer below then routes on load (pn2x_tg_bwd_slice, gmode 2). */
-int pn2x_bn_bwd_reduce_routed(long groups, int k, int c, const float *dout, int ldd, const int *arg, int lda, const float *y, int ldy,
-                              const float *mean, const float *invstd, const float *gamma, const float *beta, double *sums, void *stream);
-/* two problems of the same channel count in one launch (two launches when the counts differ); same results */
-int pn2x_bn_bwd_reduce_routed_pair(long groups_a, int k_a, int c_a, const float *dout_a, int ldd_a, const int *arg_a, int lda_a,
-                                   const float *y_a, int ldy_a, const float *mean_a, const float *invstd_a, const float *gamma_a,
-                                   const float *beta_a, double *sums_a, long groups_b, int k_b, int c_b, const float *dout_b, int ldd_b,
-                                   const int *arg_b, int lda_b, const float *y_b, int ldy_b, const float *mean_b, const float *invstd_b,
-                                   const float *gamma_b, const float *beta_b, double *sums_b, void *stream);
+/* `count` (1 or 2) problems; two whose channel counts fill the same number of 64-channel tiles share one launch. */
+typedef struct pn2x_bn_bwd_reduce_routed_problem {
+    const float *dout;
+    const int *arg;
+    const float *y, *mean, *invstd, *gamma, *beta;
+    double *sums;
+    long groups;
+    int k, c, ldd, lda, ldy, reserved;
+} pn2x_bn_bwd_reduce_routed_problem; /* 96 bytes */
+int pn2x_bn_bwd_reduce_routed(const pn2x_bn_bwd_reduce_routed_problem *problems, int count, void *stream);
 /* out (c x 3) = dy^T rel: dy (rows x c, row stride ldy), rel (rows x 3) -- the gradient of the three xyz columns of a grouped
  * layer-1 weight.  c / 4 must divide 256; scratch of pn2x_rows_outer3_scratch_floats(rows, c) floats (per-workgroup partials). */
 long pn2x_rows_outer3_scratch_floats(long rows, int c);
@@ -734,18 +740,17 @@ int pn2x_bn_bwd_apply(long rows, int c, const float *g, int ldg, const float *y,
  * registers (rel (rows x 3): the relative coordinates pn2x_sa_layer1 wrote) -- the separate pn2x_rows_outer3 pass disappears.
  * c <= 256; scratch: pn2x_bn_bwd_apply_rel_scratch_floats(rows, c) floats. */
 long pn2x_bn_bwd_apply_rel_scratch_floats(long rows, int c);
-int pn2x_bn_bwd_apply_rel(long rows, int c, const float *g, int ldg, const float *y, int ldy, const float *mean, const float *invstd,
-                          const float *gamma, const float *beta, int relu, const double *sums, float *dy, int ldo, float *dgamma,
-                          float *dbeta, float *dbias, const float *rel, float *scratch, long scratch_floats, float *dwx, void *stream);
-/* two problems (the two neighbourhood sizes of a module) in one launch each of the two kernels; same results as two calls */
-int pn2x_bn_bwd_apply_rel_pair(long rows_a, int c_a, const float *g_a, int ldg_a, const float *y_a, int ldy_a, const float *mean_a,
-                               const float *invstd_a, const float *gamma_a, const float *beta_a, int relu_a, const double *sums_a,
-                               float *dy_a, int ldo_a, float *dgamma_a, float *dbeta_a, float *dbias_a, const float *rel_a,
-                               float *scratch_a, long scratch_floats_a, float *dwx_a, long rows_b, int c_b, const float *g_b, int ldg_b,
-                               const float *y_b, int ldy_b, const float *mean_b, const float *invstd_b, const float *gamma_b,
-                               const float *beta_b, int relu_b, const double *sums_b, float *dy_b, int ldo_b, float *dgamma_b,
-                               float *dbeta_b, float *dbias_b, const float *rel_b, float *scratch_b, long scratch_floats_b, float *dwx_b,
-                               void *stream);
+/* `count` (1 or 2) problems; two (the two neighbourhood sizes of a module) run in one launch each of the two kernels. */
+typedef struct pn2x_bn_bwd_apply_rel_problem {
+    const float *g, *y, *mean, *invstd, *gamma, *beta;
+    const double *sums;
+    float *dy, *dgamma, *dbeta, *dbias;
+    const float *rel;
+    float *scratch, *dwx;
+    long rows, scratch_floats;
+    int c, ldg, ldy, relu, ldo, reserved;
+} pn2x_bn_bwd_apply_rel_problem; /* 152 bytes */
+int pn2x_bn_bwd_apply_rel(const pn2x_bn_bwd_apply_rel_problem *problems, int count, void *stream);
 
 /*
  * Train-mode [Conv 1x1 + BatchNorm + ReLU] layers with the BatchNorm folded into fp32-MFMA GEMMs (csrc/train_gemm.hip;
@@ -852,12 +857,28 @@ int pn2x_tg_reduce_multi(int count, const float *const *partial, const int *n_pa
                          const double *const *sums_bwd, const int *channels, const int *sums_ld, float *const *dgamma,
                          float *const *dbeta, float *const *dbias, void *stream);
 /* pn2x_tg_fwd with a different schedule for 64- / 128-channel inputs (csrc/train_fwd.hip: W_i resident in LDS, 64-row tiles whose
- * normalised operand is built once, one 32 x 32 output block per wave).  Same arguments and results (up to summation order). */
+ * normalised operand is built once, one 32 x 32 output block per wave).  Same arguments (as a record) and results (up to
+ * summation order), for `count` (1 or 2) problems: two must have the same k and n (else PN2_EINVAL) and share ONE launch where
+ * pn2x_tg_fwd2_pair_supported(k, n) -- the two neighbourhood sizes of a keypoint-query module: same widths, different weights and
+ * row counts (reference pointnet_utils.py:566-581 runs them as separate Conv2d stacks); the persistent workgroups are split in
+ * proportion to the tile counts. */
+typedef struct pn2x_tg_fwd2_problem {
+    const float *x, *w;
+    float *y;
+    const double *sums_in;
+    const float *gamma, *beta, *conv_bias;
+    float *running_mean, *running_var;
+    long long *num_batches_tracked;
+    float *save_mean, *save_invstd;
+    double *sums_out;
+    long rows;
+    int k, n, ldx, ldw, ldy;
+    float eps, momentum;
+    int reserved;
+} pn2x_tg_fwd2_problem; /* 144 bytes */
 int pn2x_tg_fwd2_supported(int c_in, int c_out);
-int pn2x_tg_fwd2(long rows, int k, int n, const float *x, int ldx, const float *w, int ldw, float *y, int ldy, const double *sums_in,
-                 const float *gamma, const float *beta, const float *conv_bias, float eps, float momentum, float *running_mean,
-                 float *running_var, long long *num_batches_tracked, float *save_mean, float *save_invstd, double *sums_out,
-                 void *stream);
+int pn2x_tg_fwd2_pair_supported(int c_in, int c_out);
+int pn2x_tg_fwd2(const pn2x_tg_fwd2_problem *problems, int count, void *stream);
 
 /* The whole backward of fused layer i in one kernel (csrc/train_bwd.hip): g_{i-1} (gp, with the ReLU mask and the
  * BatchNorm-backward sums of layer i-1, as pn2x_tg_dgrad) AND the weight-gradient partial tiles (as pn2x_tg_wgrad with
@@ -867,36 +888,27 @@ int pn2x_tg_fwd2(long rows, int k, int n, const float *x, int ldx, const float *
  * of (n x k) partial tiles written (partial_floats >= that * n * k), to be summed by pn2x_tg_reduce_multi.  dw is zeroed.
  * pn2x_tg_bwd_slice runs one column slice [c0, c0 + n) of a layer with sums_ld channels (all layer-i pointers offset to the slice by the
  * caller; a whole layer is the one slice c0 = 0, sums_ld = n, ldarg = ldg, g_add = NULL, raw_out = 0).  A wider layer runs as consecutive slices: raw_out = 1 leaves the unmasked partial data gradient in gp, the next slice
- * passes it as g_add (may alias gp) and the last one applies the mask and accumulates the sums.  gmode 1: dense g, masked from Y_i. */
-int pn2x_tg_bwd_slice(long rows, int n, int k, int gmode, const float *g, int ldg, const int *arg, int ldarg, int kmax, const float *yi, int ldyi,
-                      const float *mean_i, const float *invstd_i, const float *gamma_i, const float *beta_i, const double *sums_bwd_i,
-                      int sums_ld, const float *w, int ldw, const float *yp, int ldyp, const float *mean_p, const float *invstd_p,
-                      const float *gamma_p, const float *beta_p, float *gp, int ldgp, double *sums_bwd_p, float *partial,
-                      long partial_floats, float *dw, const float *g_add, int ldga, int raw_out, void *stream);
-/* Two problems of the same layer shape (and gradient source) in ONE launch -- the two neighbourhood sizes of a keypoint-query
- * module: same widths, different weights and row counts (reference pointnet_utils.py:566-581 runs them as separate Conv2d stacks).
- * Arguments: those of pn2x_tg_bwd_slice / pn2x_tg_fwd2 twice (n, k and gmode must agree); the persistent workgroups are split in
- * proportion to the tile counts.  n_partials[2] receives the number of weight-gradient partial tiles each problem wrote. */
+ * passes it as g_add (may alias gp) and the last one applies the mask and accumulates the sums.  gmode 1: dense g, masked from Y_i.
+ * `count` (1 or 2) problems.  Two must have the same n, k and gmode (else PN2_EINVAL) and share ONE launch where
+ * pn2x_tg_bwd_pair_supported(k, n) (the two neighbourhood sizes of a keypoint-query module), the persistent workgroups split in
+ * proportion to the tile counts.  n_partials (`count` ints; may be NULL when count == 1) receives the number of weight-gradient
+ * partial tiles each problem wrote: in a shared launch a problem gets a share of the grid, so fewer than pn2x_tg_bwd_partials
+ * reports for it alone (which its partial buffer must hold all the same). */
+typedef struct pn2x_tg_bwd_slice_problem {
+    const float *g;
+    const int *arg;
+    const float *yi, *mean_i, *invstd_i, *gamma_i, *beta_i;
+    const double *sums_bwd_i;
+    const float *w, *yp, *mean_p, *invstd_p, *gamma_p, *beta_p;
+    float *gp;
+    double *sums_bwd_p;
+    float *partial, *dw;
+    const float *g_add;
+    long rows, partial_floats;
+    int n, k, gmode, ldg, ldarg, kmax, ldyi, sums_ld, ldw, ldyp, ldgp, ldga, raw_out, reserved;
+} pn2x_tg_bwd_slice_problem; /* 224 bytes */
 int pn2x_tg_bwd_pair_supported(int c_in, int c_out);
-int pn2x_tg_fwd2_pair_supported(int c_in, int c_out);
-int pn2x_tg_bwd_slice_pair(long rows0, int n0, int k0, int gmode0, const float *g0, int ldg0, const int *arg0, int ldarg0, int kmax0,
-                           const float *yi0, int ldyi0, const float *mean_i0, const float *invstd_i0, const float *gamma_i0,
-                           const float *beta_i0, const double *sums_bwd_i0, int sums_ld0, const float *w0, int ldw0, const float *yp0,
-                           int ldyp0, const float *mean_p0, const float *invstd_p0, const float *gamma_p0, const float *beta_p0, float *gp0,
-                           int ldgp0, double *sums_bwd_p0, float *partial0, long partial_floats0, float *dw0, const float *g_add0, int ldga0,
-                           int raw_out0,
-                           long rows1, int n1, int k1, int gmode1, const float *g1, int ldg1, const int *arg1, int ldarg1, int kmax1,
-                           const float *yi1, int ldyi1, const float *mean_i1, const float *invstd_i1, const float *gamma_i1,
-                           const float *beta_i1, const double *sums_bwd_i1, int sums_ld1, const float *w1, int ldw1, const float *yp1,
-                           int ldyp1, const float *mean_p1, const float *invstd_p1, const float *gamma_p1, const float *beta_p1, float *gp1,
-                           int ldgp1, double *sums_bwd_p1, float *partial1, long partial_floats1, float *dw1, const float *g_add1, int ldga1,
-                           int raw_out1, int *n_partials, void *stream);
-int pn2x_tg_fwd2_pair(long rows0, int k, int n, const float *x0, int ldx0, const float *w0, int ldw0, float *y0, int ldy0,
-                      const double *sums_in0, const float *gamma0, const float *beta0, const float *conv_bias0, float eps0, float momentum0,
-                      float *running_mean0, float *running_var0, long long *nbt0, float *save_mean0, float *save_invstd0, double *sums_out0,
-                      long rows1, const float *x1, int ldx1, const float *w1, int ldw1, float *y1, int ldy1, const double *sums_in1,
-                      const float *gamma1, const float *beta1, const float *conv_bias1, float eps1, float momentum1, float *running_mean1,
-                      float *running_var1, long long *nbt1, float *save_mean1, float *save_invstd1, double *sums_out1, void *stream);
+int pn2x_tg_bwd_slice(const pn2x_tg_bwd_slice_problem *problems, int count, int *n_partials, void *stream);
 int pn2x_tg_bwd_supported(int c_in, int c_out);
 int pn2x_tg_bwd_partials(long rows, int c_out, int c_in);
 /* Round 5: for c_in in {64, 128} the kernel keeps W_i in registers as the B operand of v_mfma_f32_16x16x4_f32 (16-column slices

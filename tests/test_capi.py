@@ -100,7 +100,7 @@ def test_library_exports_every_declared_symbol(hip_lib_path):
         for name in _declared(header):
             assert hasattr(lib, name), f"{name} declared in {header} but not exported"
     lib.pn2_abi_version.restype = ctypes.c_int
-    assert lib.pn2_abi_version() == 2  # 2: the superseded pn2x_* shims removed, their successors renamed
+    assert lib.pn2_abi_version() == 3  # 3: the pairable training operators take problem records, their _pair / _ld entries removed
     lib.pn2_strerror.restype = ctypes.c_char_p
     assert b"NULL" in lib.pn2_strerror(-2)
 
@@ -205,6 +205,144 @@ def test_sa_mlp_max_argument_validation_without_gpu(hip_lib_path):
         for k0 in ks:
             for k1 in ks:
                 assert lib.pn2x_sa_mlp_max_pair_supported(k0, k1, *w) == int(w == (128, 128, 192) and (k0, k1) in ((16, 64), (64, 16))), (k0, k1, w)
+
+
+def _header_records():
+    """{record name: [(field name, kind)]} of every `typedef struct pn2x_* { ... }` the three headers declare, in declaration
+    order; kind = pointer / int / long / float / double (comments stripped as in _prototypes)."""
+    out = {}
+    for header in ("pn2_hip.h", "pn2_ext.h", "pn2_sdf.h"):
+        src = open(os.path.join(ROOT, "include", header)).read()
+        src = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", src, flags=re.S))
+        for m in re.finditer(r"typedef\s+struct\s+(pn2x_\w+)\s*\{(.*?)\}\s*(\w+)\s*;", src, flags=re.S):
+            assert m.group(3) == m.group(1)
+            fields = []
+            for stmt in filter(None, (s.strip() for s in m.group(2).split(";"))):
+                first, *more = [d.strip() for d in stmt.split(",")]
+                words = re.sub(r"\b(const|unsigned)\b", "", first.replace("*", " * ")).split()
+                base = {"int": "int", "long": "long", "float": "float", "double": "double"}.get(words[0], "other")
+                for d in (first, *more):
+                    kind = "pointer" if "*" in d else base
+                    assert kind != "other", (m.group(1), stmt)
+                    fields.append((re.findall(r"\w+", d)[-1], kind))
+            out[m.group(1)] = fields
+    return out
+
+
+def test_bound_records_match_the_header_structs():
+    """Every problem record of the headers has a ctypes.Structure in the bindings whose _fields_ match it field by field (name,
+    order, kind) and whose size is the one the library asserts beside the entry (static_assert(sizeof(...) == N))."""
+    from hotrack_amd import ext, train_ops, train_stack
+    c = ctypes
+    bound = {"pn2x_sa_problem": ext._SaProblem, "pn2x_hand_pose_problem": ext._HandPoseProblem,
+             "pn2x_sa_layer1_stats_problem": train_ops._SaLayer1StatsProblem,
+             "pn2x_rows_segment_sum_problem": train_ops._RowsSegmentSumProblem,
+             "pn2x_bn_relu_max_problem": train_ops._BnReluMaxProblem,
+             "pn2x_bn_bwd_reduce_routed_problem": train_stack._BnBwdReduceRoutedProblem,
+             "pn2x_bn_bwd_apply_rel_problem": train_stack._BnBwdApplyRelProblem,
+             "pn2x_tg_fwd2_problem": train_stack._TgFwd2Problem, "pn2x_tg_bwd_slice_problem": train_stack._TgBwdSliceProblem}
+    kinds = {c.c_void_p: "pointer", c.c_int: "int", c.c_long: "long", c.c_float: "float", c.c_double: "double"}
+    records = _header_records()
+    assert sorted(records) == sorted(bound)
+    csrc = os.path.join(ROOT, "hotrack_amd", "csrc")
+    asserted = {}
+    for f in os.listdir(csrc):
+        if f.endswith(".hip"):
+            for name, size in re.findall(r"static_assert\(sizeof\((pn2x_\w+)\) == (\d+)", open(os.path.join(csrc, f)).read()):
+                asserted[name] = int(size)
+    for name, fields in records.items():
+        assert [(n, kinds[t]) for n, t in bound[name]._fields_] == fields, name
+        assert c.sizeof(bound[name]) == asserted[name], name
+    # pointers, then 8-byte, then 4-byte scalars in the records of the training operators: no implicit padding
+    for name in sorted(set(records) - {"pn2x_sa_problem", "pn2x_hand_pose_problem"}):
+        sizes = [c.sizeof(t) for _, t in bound[name]._fields_]
+        assert sizes == sorted(sizes, reverse=True) and sum(sizes) == c.sizeof(bound[name]), name
+
+
+def test_training_record_entries_validate_without_gpu(hip_lib_path):
+    """The seven record entries of the training operators refuse an invalid record -- the first or the second of a pair -- with the
+    code the rule has, before any launch: fake non-null pointers, one violation per call."""
+    from hotrack_amd import train_ops as TO, train_stack as TS
+    lib = TO._lib
+    P = 16  # a fake, 16-byte aligned, non-null pointer
+    EINVAL, ENULL, ESCRATCH = -1, -2, -4
+
+    def rec(cls, **values):
+        r = cls(**{n: P for n, t in cls._fields_ if t is ctypes.c_void_p})
+        for n, v in values.items():
+            setattr(r, n, v)
+        return r
+
+    def arr(*records):
+        return (type(records[0]) * len(records))(*records)
+
+    def cases(call, good, violations, other=None):
+        """call(array, count) -> code.  violations: (field changes, code); each is tried alone and as the second of a pair whose
+        first record (`other`, or the good one) is valid."""
+        for change, code in violations:
+            bad = good(**change)
+            assert call(arr(bad), 1) == code, change
+            assert call(arr((other or good)(), bad), 2) == code, change
+
+    # pn2x_tg_fwd2
+    fwd = lambda **ch: rec(TS._TgFwd2Problem, **{**dict(rows=640, k=128, n=128, ldx=128, ldw=128, ldy=128, eps=1e-5, momentum=0.1), **ch})
+    call = lambda a, n: lib.pn2x_tg_fwd2(a, n, None)
+    assert call(arr(fwd()), 0) == EINVAL and call(arr(fwd(), fwd(), fwd()), 3) == EINVAL and call(None, 1) == ENULL
+    cases(call, fwd, [(dict(ldx=124), EINVAL), (dict(ldw=130), EINVAL), (dict(ldy=64), EINVAL), (dict(x=20), EINVAL), (dict(w=None), ENULL),
+                      (dict(rows=0), EINVAL), (dict(k=96, ldx=96, ldw=96), EINVAL)])
+    assert call(arr(fwd(), fwd(n=192, ldy=192)), 2) == EINVAL   # unequal layer shapes
+    assert call(arr(fwd(), fwd(k=64)), 2) == EINVAL
+    # pn2x_tg_bwd_slice
+    bwd = lambda **ch: rec(TS._TgBwdSliceProblem, **{**dict(
+        rows=640, partial_floats=1 << 40, n=128, k=128, gmode=0, ldg=128, ldarg=128, kmax=1, ldyi=128, sums_ld=128, ldw=128, ldyp=128,
+        ldgp=128, ldga=128, raw_out=0), **ch})
+    nparts = (ctypes.c_int * 2)()
+    call = lambda a, n: lib.pn2x_tg_bwd_slice(a, n, nparts, None)
+    assert call(arr(bwd()), 0) == EINVAL and call(arr(bwd(), bwd(), bwd()), 3) == EINVAL and call(None, 1) == ENULL
+    assert lib.pn2x_tg_bwd_slice(arr(bwd(), bwd()), 2, None, None) == ENULL   # a pair reports both partial counts
+    cases(call, bwd, [(dict(ldg=124), EINVAL), (dict(ldyp=130), EINVAL), (dict(sums_ld=64), EINVAL), (dict(gmode=3), EINVAL),
+                      (dict(gmode=2, kmax=3), EINVAL), (dict(gmode=2, arg=None), ENULL), (dict(gp=24), EINVAL), (dict(dw=None), ENULL),
+                      (dict(g_add=P, ldga=64), EINVAL), (dict(partial_floats=0), ESCRATCH)])
+    assert call(arr(bwd(), bwd(n=192, ldg=192, ldyi=192, sums_ld=192)), 2) == EINVAL   # unequal layer shapes
+    assert call(arr(bwd(), bwd(k=64)), 2) == EINVAL
+    assert call(arr(bwd(), bwd(gmode=1)), 2) == EINVAL                                 # unequal gradient sources
+    assert call(arr(bwd(partial_floats=0), bwd()), 2) == ESCRATCH
+    # pn2x_bn_relu_max
+    mx = lambda **ch: rec(TO._BnReluMaxProblem, **{**dict(groups=300, k=24, c=64, ldy=64, ldo=72, eps=1e-5, momentum=0.1), **ch})
+    call = lambda a, n: lib.pn2x_bn_relu_max(a, n, None)
+    assert call(arr(mx()), 0) == EINVAL and call(arr(mx(), mx(), mx()), 3) == EINVAL and call(None, 2) == ENULL
+    cases(call, mx, [(dict(ldo=60), EINVAL), (dict(ldo=66), EINVAL), (dict(ldy=62), EINVAL), (dict(c=1028, ldy=1028, ldo=1028), EINVAL),
+                     (dict(out=20), EINVAL), (dict(arg=None), ENULL), (dict(k=0), EINVAL)])
+    # pn2x_bn_bwd_reduce_routed
+    rt = lambda **ch: rec(TS._BnBwdReduceRoutedProblem, **{**dict(groups=300, k=24, c=64, ldd=128, lda=64, ldy=64), **ch})
+    call = lambda a, n: lib.pn2x_bn_bwd_reduce_routed(a, n, None)
+    assert call(arr(rt()), 0) == EINVAL and call(arr(rt(), rt(), rt()), 3) == EINVAL and call(None, 1) == ENULL
+    cases(call, rt, [(dict(ldd=60), EINVAL), (dict(lda=32), EINVAL), (dict(ldy=32), EINVAL), (dict(c=6), EINVAL), (dict(sums=None), ENULL),
+                     (dict(groups=1 << 30, k=64), EINVAL)])
+    # pn2x_bn_bwd_apply_rel
+    ar = lambda **ch: rec(TS._BnBwdApplyRelProblem, **{**dict(rows=7200, scratch_floats=1 << 40, c=64, ldg=64, ldy=64, relu=0, ldo=64), **ch})
+    call = lambda a, n: lib.pn2x_bn_bwd_apply_rel(a, n, None)
+    assert call(arr(ar()), 0) == EINVAL and call(arr(ar(), ar(), ar()), 3) == EINVAL and call(None, 1) == ENULL
+    cases(call, ar, [(dict(ldg=60), EINVAL), (dict(ldo=66), EINVAL), (dict(c=260, ldg=260, ldy=260, ldo=260), EINVAL), (dict(dy=24), EINVAL),
+                     (dict(rel=None), ENULL), (dict(dbias=None, dwx=None), ENULL), (dict(scratch_floats=3 * 64 - 1), ESCRATCH)])
+    # pn2x_sa_layer1_stats (b, n, s, xyz, cxyz shared)
+    sa = lambda **ch: rec(TO._SaLayer1StatsProblem, **{**dict(k=16, c1=32, a1f_ld=64, wx_ld=3, cadd_ld=64), **ch})
+    call = lambda a, n, b=2, xyz=P, cxyz=P: lib.pn2x_sa_layer1_stats(a, n, b, 300, 37, xyz, cxyz, None)
+    assert call(arr(sa()), 0) == EINVAL and call(arr(sa(), sa(), sa()), 3) == EINVAL and call(None, 1) == ENULL
+    cases(call, sa, [(dict(a1f_ld=28), EINVAL), (dict(cadd_ld=34), EINVAL), (dict(wx_ld=2), EINVAL), (dict(a1f=24), EINVAL),
+                     (dict(sums=None), ENULL), (dict(idx=None), ENULL), (dict(k=0), EINVAL), (dict(c1=6), EINVAL),
+                     (dict(c1=12, a1f_ld=8), EINVAL)])        # (c1 = 12: the statistics cannot be taken in the launch)
+    assert call(arr(sa(), sa()), 2, cxyz=None) == ENULL and call(arr(sa(), sa()), 2, b=-1) == EINVAL
+    assert call(arr(sa(), sa(idx=None)), 2, b=0) == 0        # an empty batch: nothing is read
+    # pn2x_rows_segment_sum (b, n_dst, accumulate shared)
+    sg = lambda **ch: rec(TO._RowsSegmentSumProblem, **{**dict(m_src=96, t=1, c=8, ldo=8, ldi=16), **ch})
+    call = lambda a, n, b=2, n_dst=64: lib.pn2x_rows_segment_sum(a, n, b, n_dst, 0, None)
+    assert call(arr(sg()), 0) == EINVAL and call(arr(sg(), sg(), sg()), 3) == EINVAL and call(None, 1) == ENULL
+    cases(call, sg, [(dict(ldo=4), EINVAL), (dict(ldi=18), EINVAL), (dict(t=2), EINVAL), (dict(c=6), EINVAL), (dict(din=20), EINVAL),
+                     (dict(order=None), ENULL), (dict(t=3, weight=None), ENULL)])
+    cases(call, sg, [(dict(ldo=4), EINVAL), (dict(t=3, weight=None), ENULL)], other=lambda: sg(t=3, m_src=40))   # beside a t == 3 problem
+    assert call(arr(sg(), sg()), 2, n_dst=0) == EINVAL
+    assert call(arr(sg(c=0, dout=None), sg(c=0)), 2) == 0    # no channels: nothing to do
 
 
 def test_python_boundary_exports_reference_names():

@@ -190,7 +190,7 @@ def test_bn_relu_dead_channel_and_nan():
 
 
 # ---- bn_relu_max --------------------------------------------------------------------------------------------------------------------
-# pn2x_bn_relu_max_ld splits a group's rows over lanes when K >= 4 and groups x C / 4 < 65536 (split >= 4), else one thread per
+# pn2x_bn_relu_max splits a group's rows over lanes when K >= 4 and groups x C / 4 < 65536 (split >= 4), else one thread per
 # (group, quad): at C = 64 the switch is at 4096 groups.  K = 1, 3: always the serial kernel.
 @pytest.mark.parametrize("G,K,C", [(300, 1, 64), (50, 3, 12),      # serial (K < 4)
                                    (300, 24, 64), (40, 64, 192),   # split kernel (few groups)
@@ -268,18 +268,20 @@ def test_bn_relu_max_ld_sentinel_and_pair_launch():
                 torch.empty(2, C, device=DEV), torch.zeros(C, device=DEV), torch.ones(C, device=DEV),
                 torch.zeros((), dtype=torch.int64, device=DEV))
 
-    def args(p, b):
+    def record(p, b):
         G, K, y, sums = p
         wide, arg, saved, rm, rv, nbt = b
-        return [G, K, C, y.data_ptr(), C, sums.data_ptr(), gamma.data_ptr(), beta.data_ptr(), None, 1e-5, 0.1, rm.data_ptr(), rv.data_ptr(),
-                nbt.data_ptr(), saved[0].data_ptr(), saved[1].data_ptr(), wide[:, 4:].data_ptr(), C + 8, arg.data_ptr()]
+        return TO._BnReluMaxProblem(y=y.data_ptr(), sums=sums.data_ptr(), gamma=gamma.data_ptr(), beta=beta.data_ptr(), conv_bias=None,
+                                    running_mean=rm.data_ptr(), running_var=rv.data_ptr(), num_batches_tracked=nbt.data_ptr(),
+                                    save_mean=saved[0].data_ptr(), save_invstd=saved[1].data_ptr(), out=wide[:, 4:].data_ptr(),
+                                    arg=arg.data_ptr(), groups=G, k=K, c=C, ldy=C, ldo=C + 8, eps=1e-5, momentum=0.1)
 
     st = TO._native._stream(probs[0][2])
     single = [bufs(p[0]) for p in probs]
     for p, b in zip(probs, single):
-        TO._native._check(lib.pn2x_bn_relu_max_ld(*args(p, b), st), "bn_relu_max_ld")
+        TO._native._check(lib.pn2x_bn_relu_max(*TO._records(record(p, b)), st), "bn_relu_max")
     pair = [bufs(p[0]) for p in probs]
-    TO._native._check(lib.pn2x_bn_relu_max_pair(*args(probs[0], pair[0]), *args(probs[1], pair[1]), st), "bn_relu_max_pair")
+    TO._native._check(lib.pn2x_bn_relu_max(*TO._records(record(probs[0], pair[0]), record(probs[1], pair[1])), st), "bn_relu_max")
     for p, s, q in zip(probs, single, pair):
         for a, b in zip(s, q):
             assert torch.equal(a, b)
@@ -296,8 +298,9 @@ def test_bn_relu_max_ld_sentinel_and_pair_launch():
 def _sa_layer1_case(name, Ks, C1s, with_feat, with_centre, variants):
     """sa_layer1 over the scales (Ks[i], C1s[i]) -- scale i reads and writes column block i of a1f / cadd and of their gradients --
     against the float64 reference scale by scale, beside the fp32 torch composition.  variants: (statistics in the launch, inverted
-    neighbour lists handed in) per run; with two scales the first switch selects pn2x_sa_layer1_stats_pair over two plain
-    launches and the second pn2x_rows_segment_sum_pair over two segment sums for d(a1f) (d(cadd) of two scales is always the pair)."""
+    neighbour lists handed in) per run; with two scales the first switch selects one two-record pn2x_sa_layer1_stats call over two
+    plain launches and the second one two-record pn2x_rows_segment_sum call over two segment sums for d(a1f) (d(cadd) of two scales
+    is always the pair)."""
     from hotrack_amd.train_ops import Workspace, inverse_index, sa_layer1
     B, N, S, W = 3, 300, 37, sum(C1s)
     cols = [slice(sum(C1s[:i]), sum(C1s[:i + 1])) for i in range(len(Ks))]
@@ -352,8 +355,8 @@ def test_sa_layer1_matches_fp64(with_feat, with_centre, K):
 @pytest.mark.parametrize("with_feat,with_centre", [(False, False), (True, False), (False, True), (True, True)])
 def test_sa_layer1_two_scales_match_fp64(with_feat, with_centre):
     """Two scales of unequal width (column blocks [0, 32) and [32, 96) of a1f / cadd): as two plain launches with the backward's
-    own list inversion, and as the pair launches (pn2x_sa_layer1_stats_pair forward; pn2x_rows_segment_sum_pair for d(a1f) over
-    the handed-in inverted lists and for d(cadd)).  A wrong column offset or a row of the other scale's problem shows in out,
+    own list inversion, and as the pair launches (pn2x_sa_layer1_stats forward; pn2x_rows_segment_sum for d(a1f) over the
+    handed-in inverted lists and for d(cadd), two records each).  A wrong column offset or a row of the other scale's problem shows in out,
     d_a1f or d_cadd of one scale."""
     _sa_layer1_case("sa_layer1 pair", [7, 32], [32, 64], with_feat, with_centre, [(False, False), (True, True)])
 
@@ -435,6 +438,39 @@ def test_scatter_add_rows_and_accumulating_segment_sum(C):
     got = rows_segment_sum(dout.to(DEV), inverse_index(idx.to(DEV), N), N, init.to(DEV).clone(), accumulate=True)
     _check(f"rows_segment_sum accumulate C={C}", "din", got, want, tor, 1e-5, 1e-3)
     assert torch.equal(got[:, N - 1].cpu(), init[:, N - 1])
+
+
+def test_rows_segment_sum_pair_with_an_interpolation_problem():
+    """A plain row scatter (t = 1) and a weighted three-NN scatter (t = 3) over the same destination rows as ONE two-record call --
+    the pair kernel covers t = 1 only, so this runs as two launches -- bit for bit equal to the two one-record calls, and both
+    against float64 index_add at rows_segment_sum's tolerance (test_scatter_add_rows_and_accumulating_segment_sum)."""
+    from hotrack_amd import train_ops as TO
+    B, N, C = 2, 64, 8
+    g = torch.Generator().manual_seed(5)
+    cases = []
+    for t, m in ((1, 96), (3, 40)):
+        idx = torch.randint(0, N - 1, (B, m * t), generator=g, dtype=torch.int32)      # row N - 1 receives nothing
+        dout = torch.randn(B, m, C, generator=g)
+        w = torch.rand(B, m * t, generator=g) if t == 3 else None
+        rows = lambda x, ww: x.repeat_interleave(t, dim=1) * (ww.unsqueeze(-1) if t == 3 else 1.0)  # one row per index entry
+        want, tor = torch.zeros(B, N, C, dtype=f64), torch.zeros(B, N, C, device=DEV)
+        for b in range(B):
+            want[b].index_add_(0, idx[b].long(), rows(dout.double(), w.double() if t == 3 else None)[b])
+            tor[b].index_add_(0, idx[b].long().to(DEV), rows(dout, w)[b].to(DEV))
+        cases.append((dout.to(DEV), TO.inverse_index(idx.to(DEV), N), None if w is None else w.to(DEV), want, tor))
+    st = TO._native._stream(cases[0][0])
+
+    def run(which):
+        dins = [torch.full((B, N, C), 3.0, device=DEV) for _ in cases]                   # accumulate = 0: overwritten
+        recs = [TO._segment_sum_problem(c[0], c[1], din, c[2]) for c, din in zip(cases, dins)]
+        TO._native._check(TO._lib.pn2x_rows_segment_sum(*TO._records(*(recs[i] for i in which)), B, N, 0, st), "rows_segment_sum")
+        return dins
+
+    both = run((0, 1))
+    for i, (c, got) in enumerate(zip(cases, both)):
+        assert torch.equal(got, run((i,))[i])
+        _check(f"rows_segment_sum pair t={1 if c[2] is None else 3}", "din", got, c[3], c[4], 1e-5, 1e-3)
+        assert float(got[:, N - 1].abs().max()) == 0.0
 
 
 # ---- FusedAdam ----------------------------------------------------------------------------------------------------------------------
