@@ -84,13 +84,17 @@ __global__ __launch_bounds__(NT) void hand_shape_kernel(int P, int D, int T, int
                 }
                 len[b] = sqrtf(v0 * v0 + v1 * v1 + v2 * v2);
             }
-            float e = 0.f;
-            for (int t = 0; t < T; ++t) {  // mean over the bones, then over the targets (:55)
+            // mean over the bones, then over the targets (:55).  The sum over the targets is compensated: a plain running sum
+            // of T = 1024 rows is off by some 8 ulp, which the weights origin - E of pass 2 magnify by E / (origin - E).
+            float e = 0.f, lost = 0.f;
+            for (int t = 0; t < T; ++t) {
                 const float *lt = L + t * NB;
                 float a = 0.f;
 #pragma unroll
                 for (int b = 0; b < NB; ++b) a += fabsf(len[b] - lt[b]);
-                e += a * inv15;
+                const float y = a * inv15 - lost, sum = e + y;
+                lost = (sum - e) - y;
+                e = sum;
             }
             E[p] = e / (float)T;
         }

@@ -996,7 +996,8 @@ def hand_shape_opt(k0: torch.Tensor, k: torch.Tensor, pre: torch.Tensor, targets
                    scaling_coefficient2: float, beta: float, iterations: int, out: torch.Tensor = None, trace: bool = False):
     """The whole shape-code search of gf_optimize_hand_shape.optimize in one launch (pn2x_hand_shape_opt).  k0 (21,3) and
     k (D,21,3): keypoints affine in the shape code (HandModel.shape_keypoint_basis); pre (P,D) pre-sampled particles, row 0
-    zero; targets (T,15) bone lengths; initial_scale (D).  -> (shape code (D,), trace (iterations, 3 + D) or None)."""
+    zero; targets (T,15) bone lengths; initial_scale (D).  -> (shape code (D,), trace (iterations, 3 + D) or None).  With iterations = 0 the code is zero, in a
+    caller's `out` too."""
     P, D = pre.shape
     T = targets.shape[0]
     f32 = torch.float32
@@ -1015,6 +1016,8 @@ def hand_shape_opt(k0: torch.Tensor, k: torch.Tensor, pre: torch.Tensor, targets
                                      _native._ptr(initial_scale, "initial_scale", f32, D), float(scaling_coefficient2), float(beta),
                                      _native._ptr(out, "out", f32, D), None if tr is None else tr.data_ptr(),
                                      _native._stream(pre)), "hand_shape_opt")
+        if iterations == 0:  # no launch: the C entry leaves `out` alone, and the code after no iterations is the zero code
+            out.zero_()
     return out, tr
 
 
