@@ -18,14 +18,22 @@ namespace mrows {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// acc[nt][mt] += W[tile nt] . X[rows of m-tile mt]^T over KG k-groups of 16.  wp: packed weights of the first n-tile
-// ([n-tile][k-group][lane][4], KG k-groups per n-tile); xs: LDS rows, ld floats apart.  Lane l supplies, in k-step s of a
-// k-group, W[n0 + l%16][16 kg + 4 (l/16) + s] and X[m0 + l%16][16 kg + 4 (l/16) + s]: one 16-byte load of each per k-group.
+// acc[nt][mt] += W[tile nt] . X[rows of m-tile mt]^T over KG k-groups of 16, k-groups and the four k-steps of each in
+// ascending order.  wp: packed weights of the first n-tile ([n-tile][k-group][lane][4], KG k-groups per n-tile); xs: LDS
+// rows, ld floats apart.  Lane l supplies, in k-step s of a k-group, W[n0 + l%16][16 kg + 4 (l/16) + s] and
+// X[m0 + l%16][16 kg + 4 (l/16) + s]: one 16-byte load of each per k-group.
+//
+// Three operand slots: the loads of k-group kg + 2 (NT weight loads from L2, MT LDS reads) are issued at the top of the step
+// that consumes k-group kg, one load per MFMA (sched_group_barrier pins that order; left to itself hipcc issued a slot's
+// loads a few MFMAs before the step that needs them and waited vmcnt(0) there, with one wave per SIMD and nothing else to
+// issue).  A step waits only for operands requested two steps earlier, and the loads of kg + 1 and kg + 2 stay in flight
+// behind it: vmcnt reaches 0 only in the last step of a layer.
 template <int NT, int MT, int KG, int LD>
 __device__ __forceinline__ void mm(f32x4 (&acc)[NT][MT], const float *__restrict__ wp, const float *xs, int lane) {
+    static_assert(KG >= 5, "the pipeline is two k-groups deep");
     const f32x4 *w4 = reinterpret_cast<const f32x4 *>(wp) + lane;
     const float *xr = xs + (lane & 15) * LD + 4 * (lane >> 4);
-    f32x4 w[2][NT], x[2][MT];
+    f32x4 w[3][NT], x[3][MT];
     auto load = [&](int kg, int slot) {
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) w[slot][nt] = w4[(nt * KG + kg) * 64];
@@ -42,15 +50,35 @@ __device__ __forceinline__ void mm(f32x4 (&acc)[NT][MT], const float *__restrict
                     acc[nt][mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[slot][nt][s], x[slot][mt][s], acc[nt][mt], 0, 0, 0);
     };
     load(0, 0);
-    int kg = 0;
+    load(1, 1);
+    constexpr int MAIN = (KG - 2) / 3;  // iterations of three steps in which every step has a k-group kg + 2 to load
 #pragma unroll 1
-    for (; kg + 2 <= KG; kg += 2) {
-        load(kg + 1, 1);
-        step(0);
-        if (kg + 2 < KG) load(kg + 2, 0);
-        step(1);
+    for (int it = 0; it < MAIN; ++it) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            load(3 * it + j + 2, (j + 2) % 3);
+            step(j);
+            // one load, one MFMA, ... until the NT + MT loads are out; then the rest of the step's 4 NT MT MFMAs
+#pragma unroll
+            for (int i = 0; i < NT; ++i) {
+                __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);  // VMEM read
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
+            }
+#pragma unroll
+            for (int i = 0; i < MT; ++i) {
+                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // DS read
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            }
+            __builtin_amdgcn_sched_group_barrier(0x008, 4 * NT * MT - NT - MT, 0);
+            __builtin_amdgcn_sched_barrier(0);
+        }
     }
-    if constexpr (KG & 1) step(0);
+#pragma unroll
+    for (int kg = 3 * MAIN; kg < KG; ++kg) {  // the last 2 .. 4 steps: nothing left to load in the last two
+        if (kg + 2 < KG) load(kg + 2, (kg + 2) % 3);
+        step(kg % 3);
+        __builtin_amdgcn_sched_barrier(0);
+    }
 }
 
 // every accumulator of n-tile nt0 + nt starts at the bias of its four channels (bias may point to global memory or LDS)
