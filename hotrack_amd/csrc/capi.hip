@@ -53,7 +53,7 @@ static inline bool fits_int(long v) { return v >= 0 && v <= 2147483647L; }
 
 extern "C" {
 
-int pn2_abi_version(void) { return 3; }
+int pn2_abi_version(void) { return 4; }
 
 int pn2_last_hip_error(void) { return g_last_hip_error; }
 

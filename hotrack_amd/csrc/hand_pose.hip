@@ -25,8 +25,8 @@
 // (pn2x_hand_pose_problem, a device array read at a workgroup-uniform address).  The eval grid's y and the update grid's x is
 // the problem; a problem that is not active returns before it reads any of its record's pointers.  No workgroup waits for another.
 //
-// hand_pose_offsets_kernel / hand_pose_mano_eval_kernel (pn2x_hand_pose_mano_*).  A hand with MANO's structure (skinning_tables'
-// optional entries): per iteration a pre-pass builds every candidate's 135 pose features vec(R_b - I) -- the skeleton phase's
+// hand_pose_offsets_kernel / hand_pose_mano_eval_kernel (a pn2x_hand_pose_setup with posedirs set).  A hand with MANO's structure
+// (skinning_tables' optional entries): per iteration a pre-pass builds every candidate's 135 pose features vec(R_b - I) -- the skeleton phase's
 // own angle and Rodrigues functions -- and multiplies them with the packed pose blend shapes on the fp32 matrix cores into
 // offsets (P, ceil16(3 V)); the MANO instantiation of hand_pose_eval_block (template <.., bool MANO>, if constexpr: the plain
 // instantiations are the code they were) adds a vertex's offset to its staged v_rest - j_k, takes the fingertip keypoints from
@@ -619,187 +619,166 @@ __global__ void __launch_bounds__(FILL * REC_WORDS) hand_pose_problems_fill_kern
 using namespace pn2;
 using namespace pn2::hpose;
 
+static_assert(sizeof(pn2x_hand_pose_setup) == 136, "record layout (pn2_ext.h)");
+
 extern "C" int pn2x_hand_pose_opt_supported(int p, int v, int j, int k, int d_pose, int res) {
     return (p >= 1 && p <= MAXP && v >= 1 && v <= MAXV && j == NJ && k >= 1 && k <= MAXK && d_pose == NC && res >= 1 &&
             res <= 1024 && (res & 1) == 1) ? 1 : 0;
 }
 
-extern "C" long pn2x_hand_pose_opt_work_floats(int p) { return p < 0 ? (long)PN2_EINVAL : (long)TERMS * p; }
-
-static int eval_launch(const Frame &A, int f16, hipStream_t st) {
-    static PerDeviceOnce raised;
-    if (raised.first_use()) {
-        (void)hipFuncSetAttribute((const void *)hand_pose_eval_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)eval_lds_bytes(MAXV, MAXK));
-        (void)hipFuncSetAttribute((const void *)hand_pose_eval_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)eval_lds_bytes(MAXV, MAXK));
-    }
-    // a workgroup's four waves take a candidate each; the grid covers the compute units at most three times and the
-    // candidates are dealt evenly over it
-    const int wgs = (A.P + 3) / 4, cap = 3 * num_compute_units(), rounds = (wgs + cap - 1) / cap, grid = (wgs + rounds - 1) / rounds;
-    if (f16) hipLaunchKernelGGL(hand_pose_eval_kernel<true>, dim3(grid), dim3(256), eval_lds_bytes(A.V, A.K), st, A);
-    else hipLaunchKernelGGL(hand_pose_eval_kernel<false>, dim3(grid), dim3(256), eval_lds_bytes(A.V, A.K), st, A);
-    return PN2_OK;
-}
-
-#define HAND_POSE_MODEL_PARAMS                                                                                                    \
-    int p, int v, int j, int k, const int *parents, const int *pose_block, const float *rest_joints, const float *rest_verts,    \
-        const int *skin_pack, const float *skin_w, const float *comps, float theta_scale, const float *pre,                       \
-        const float *pred_kp, const float *last_kp, const unsigned char *vis_mask, const float *obj_r, const float *obj_t,        \
-        const void *vol, int vol_f16, int res, float voxel_scale, const unsigned char *mask, int h, int w, float fx, float fy,    \
-        float cx, float cy, float w_sil, float w_pen, float w_vis, float w_invis, float w_temporal, float w_attr
-
-static int fill_frame(Frame &A, HAND_POSE_MODEL_PARAMS) {
-    if (p < 1 || v < 1 || j < 1 || k < 1 || res < 1 || (res & 1) == 0 || !(voxel_scale > 0.f) || h < 1 || w < 1 ||
-        (vol_f16 != 0 && vol_f16 != 1))
-        return PN2_EINVAL;
-    if (!pn2x_hand_pose_opt_supported(p, v, j, k, NC, res) || (long)h * w >= (1L << 31)) return PN2_ERANGE;
-    if (!parents || !pose_block || !rest_joints || !rest_verts || !skin_pack || !skin_w || !comps || !pre || !pred_kp || !vis_mask ||
-        !obj_r || !obj_t || !vol || !mask)
-        return PN2_ENULL;
-    A.P = p; A.V = v; A.K = k;
-    A.parents = parents; A.pose_block = pose_block; A.rest_j = rest_joints; A.rest_v = rest_verts; A.pack = skin_pack;
-    A.skin_w = skin_w; A.comps = comps; A.theta_scale = theta_scale; A.pre = pre; A.pred_kp = pred_kp; A.last_kp = last_kp;
-    A.vis = vis_mask; A.obj_r = obj_r; A.obj_t = obj_t; A.vol = vol; A.res = res; A.voxel_scale = voxel_scale; A.mask = mask;
-    A.h = h; A.w = w; A.fx = fx; A.fy = fy; A.cx = cx; A.cy = cy;
-    A.w_sil = w_sil; A.w_pen = w_pen; A.w_vis = w_vis; A.w_invis = w_invis; A.w_tmp = w_temporal; A.w_attr = w_attr;
-    A.state = nullptr; A.terms = nullptr; A.out_verts = nullptr; A.out_kp = nullptr;
-    return PN2_OK;
-}
-
-#define HAND_POSE_MODEL_ARGS                                                                                                     \
-    p, v, j, k, parents, pose_block, rest_joints, rest_verts, skin_pack, skin_w, comps, theta_scale, pre, pred_kp, last_kp,     \
-        vis_mask, obj_r, obj_t, vol, vol_f16, res, voxel_scale, mask, h, w, fx, fy, cx, cy, w_sil, w_pen, w_vis, w_invis,        \
-        w_temporal, w_attr
-
-extern "C" int pn2x_hand_pose_energy(HAND_POSE_MODEL_PARAMS, const float *state, float *work, float *energy, float *out_verts,
-                                     float *out_kp, void *stream) {
-    Frame A;
-    const int rc = fill_frame(A, HAND_POSE_MODEL_ARGS);
-    if (rc != PN2_OK) return rc;
-    if (!state || !work || !energy) return PN2_ENULL;
-    A.state = state; A.terms = work; A.out_verts = out_verts; A.out_kp = out_kp;
-    hipStream_t st = (hipStream_t)stream;
-    eval_launch(A, vol_f16, st);
-    hipLaunchKernelGGL(hand_pose_energy_kernel, dim3((p + 255) / 256), dim3(256), 0, st, p, work, energy);
-    return check_launch();
-}
-
-extern "C" int pn2x_hand_pose_opt(HAND_POSE_MODEL_PARAMS, int iterations, double scaling_coefficient2, double beta, float *state,
-                                  float *work, float *trace, void *stream) {
-    Frame A;
-    const int rc = fill_frame(A, HAND_POSE_MODEL_ARGS);
-    if (rc != PN2_OK) return rc;
-    if (iterations < 0) return PN2_EINVAL;
-    if (iterations > 4096) return PN2_ERANGE;
-    if (iterations == 0) return PN2_OK;
-    if (!state || !work) return PN2_ENULL;
-    A.state = state; A.terms = work;
-    hipStream_t st = (hipStream_t)stream;
-    for (int it = 0; it < iterations; ++it) {
-        eval_launch(A, vol_f16, st);
-        hipLaunchKernelGGL(hand_pose_update_kernel, dim3(1), dim3(UT), 0, st, p, pre, work, comps, theta_scale,
-                           (float)scaling_coefficient2, (float)beta, (float)(1.0 - beta), state,
-                           trace ? trace + (size_t)it * (3 + ND) : nullptr);
-    }
-    return check_launch();
-}
-
-// ---- the MANO-structured hand ---------------------------------------------------------------------------------------------------
 static inline int offsets_ld(int v) { return (3 * v + 15) / 16 * 16; }
 
-extern "C" int pn2x_hand_pose_mano_supported(int p, int v, int j, int k, int d_pose, int res) {
-    return pn2x_hand_pose_opt_supported(p, v, j, k, d_pose, res);
-}
-
+extern "C" long pn2x_hand_pose_opt_work_floats(int p) { return p < 0 ? (long)PN2_EINVAL : (long)TERMS * p; }
 extern "C" long pn2x_hand_pose_mano_work_floats(int p, int v) {
     return (p < 0 || v < 0) ? (long)PN2_EINVAL : (long)p * offsets_ld(v);
 }
-
-static int fill_mano(ManoExtra &M, const Frame &A, const float *posedirs, const float *pose_mean, const int *kp_vertex,
-                     int centre_root, float *offsets) {
-    if (centre_root != 0 && centre_root != 1) return PN2_EINVAL;
-    if (!posedirs || !pose_mean || !kp_vertex || !offsets) return PN2_ENULL;
-    if (((uintptr_t)posedirs & 15) || ((uintptr_t)offsets & 15)) return PN2_EINVAL;  // 16-byte loads and stores
-    M.offsets = offsets; M.pose_mean = pose_mean; M.kp_vertex = kp_vertex; M.ldo = offsets_ld(A.V); M.centre = centre_root;
-    return PN2_OK;
-}
-
-// one iteration's pre-pass and evaluation
-static void mano_eval_launch(const Frame &A, const ManoExtra &M, const float *posedirs, float *offsets, int f16, hipStream_t st) {
-    static PerDeviceOnce raised;
-    if (raised.first_use()) {
-        (void)hipFuncSetAttribute((const void *)hand_pose_mano_eval_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)eval_lds_bytes(MAXV, MAXK));
-        (void)hipFuncSetAttribute((const void *)hand_pose_mano_eval_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)eval_lds_bytes(MAXV, MAXK));
-    }
-    // pre-pass: x = groups of OCT candidates, y = as many strides over the 16-row tiles as cover the compute units three times
-    const int ntiles = M.ldo / 16, gx = (A.P + OCT - 1) / OCT, cover = 3 * num_compute_units() / gx, most = (ntiles + 3) / 4;
-    const int gy = cover < 1 ? 1 : (cover > most ? most : cover);
-    hipLaunchKernelGGL(hand_pose_offsets_kernel, dim3(gx, gy), dim3(256), 0, st, A.P, ntiles, posedirs, M.pose_mean, A.comps,
-                       A.theta_scale, A.pre, A.state, offsets);
-    const int wgs = (A.P + 3) / 4, cap = 3 * num_compute_units(), rounds = (wgs + cap - 1) / cap, grid = (wgs + rounds - 1) / rounds;
-    if (f16) hipLaunchKernelGGL(hand_pose_mano_eval_kernel<true>, dim3(grid), dim3(256), eval_lds_bytes(A.V, A.K), st, A, M);
-    else hipLaunchKernelGGL(hand_pose_mano_eval_kernel<false>, dim3(grid), dim3(256), eval_lds_bytes(A.V, A.K), st, A, M);
-}
-
-extern "C" int pn2x_hand_pose_mano_energy(HAND_POSE_MODEL_PARAMS, const float *posedirs, const float *pose_mean, const int *kp_vertex,
-                                          int centre_root, const float *state, float *work, float *offsets, float *energy,
-                                          float *out_verts, float *out_kp, void *stream) {
-    Frame A;
-    ManoExtra M;
-    int rc = fill_frame(A, HAND_POSE_MODEL_ARGS);
-    if (rc != PN2_OK) return rc;
-    if (!state || !work || !energy) return PN2_ENULL;
-    if ((rc = fill_mano(M, A, posedirs, pose_mean, kp_vertex, centre_root, offsets)) != PN2_OK) return rc;
-    A.state = state; A.terms = work; A.out_verts = out_verts; A.out_kp = out_kp;
-    hipStream_t st = (hipStream_t)stream;
-    mano_eval_launch(A, M, posedirs, offsets, vol_f16, st);
-    hipLaunchKernelGGL(hand_pose_energy_kernel, dim3((p + 255) / 256), dim3(256), 0, st, p, work, energy);
-    return check_launch();
-}
-
-extern "C" int pn2x_hand_pose_mano_opt(HAND_POSE_MODEL_PARAMS, const float *posedirs, const float *pose_mean, const int *kp_vertex,
-                                       int centre_root, int iterations, double scaling_coefficient2, double beta, float *state,
-                                       float *work, float *offsets, float *trace, void *stream) {
-    Frame A;
-    ManoExtra M;
-    int rc = fill_frame(A, HAND_POSE_MODEL_ARGS);
-    if (rc != PN2_OK) return rc;
-    if (iterations < 0) return PN2_EINVAL;
-    if (iterations > 4096) return PN2_ERANGE;
-    if (iterations == 0) return PN2_OK;
-    if (!state || !work) return PN2_ENULL;
-    if ((rc = fill_mano(M, A, posedirs, pose_mean, kp_vertex, centre_root, offsets)) != PN2_OK) return rc;
-    A.state = state; A.terms = work;
-    hipStream_t st = (hipStream_t)stream;
-    for (int it = 0; it < iterations; ++it) {
-        mano_eval_launch(A, M, posedirs, offsets, vol_f16, st);
-        hipLaunchKernelGGL(hand_pose_update_kernel, dim3(1), dim3(UT), 0, st, p, pre, work, comps, theta_scale,
-                           (float)scaling_coefficient2, (float)beta, (float)(1.0 - beta), state,
-                           trace ? trace + (size_t)it * (3 + ND) : nullptr);
-    }
-    return check_launch();
-}
-
 extern "C" long pn2x_hand_pose_opt_batch_work_floats(int p, int s) {
     return (p < 0 || s < 0) ? (long)PN2_EINVAL : (long)TERMS * p * s;
 }
 
-extern "C" int pn2x_hand_pose_problems_fill(pn2x_hand_pose_problem *problems, int s, const pn2x_hand_pose_problem *host, void *stream) {
-    if (s < 1) return PN2_EINVAL;
-    if (s > 65535) return PN2_ERANGE;
-    if (!problems || !host) return PN2_ENULL;
-    for (int q = 0; q < s; ++q) {  // the records are host memory here: what the batched entry cannot check
-        const pn2x_hand_pose_problem &r = host[q];
-        if (!r.active) continue;
-        if (r.h < 1 || r.w < 1) return PN2_EINVAL;
-        if ((long)r.h * r.w >= (1L << 31)) return PN2_ERANGE;
-        if (!r.state || !r.work || !r.rest_joints || !r.rest_verts || !r.pred_kp || !r.vis_mask || !r.obj_r || !r.obj_t || !r.vol ||
-            !r.mask)
-            return PN2_ENULL;
+// What an entry's argument checks found, whichever check found it: a bad value before a limit before a NULL pointer.
+struct Faults {
+    bool inval = false, range = false, null = false;
+    int code() const { return inval ? PN2_EINVAL : range ? PN2_ERANGE : null ? PN2_ENULL : PN2_OK; }
+};
+
+// A record pointer is read only if a process can own the address: nothing is mapped below 64 KiB.  A caller built against
+// ABI version 3 passes its candidate count where the setup record is now, and is refused (PN2_EINVAL) instead of read.
+static bool is_record(const void *rec) { return (uintptr_t)rec >= 65536; }
+static bool is_record(const void *rec, Faults &f) {
+    if (is_record(rec)) return true;
+    (rec ? f.inval : f.null) = true;
+    return false;
+}
+
+static void check_setup(const pn2x_hand_pose_setup *s, Faults &f) {
+    if (!is_record(s, f)) return;
+    f.inval |= s->p < 1 || s->v < 1 || s->j < 1 || s->k < 1 || s->res < 1 || (s->res & 1) == 0 || !(s->voxel_scale > 0.f) ||
+               (s->vol_f16 != 0 && s->vol_f16 != 1);
+    f.range |= !pn2x_hand_pose_opt_supported(s->p, s->v, s->j, s->k, NC, s->res);
+    f.null |= !s->parents || !s->pose_block || !s->skin_pack || !s->skin_w || !s->comps || !s->pre;
+    if (s->posedirs) {  // the MANO part; posedirs is read by 16-byte loads
+        f.inval |= (s->centre_root != 0 && s->centre_root != 1) || ((uintptr_t)s->posedirs & 15);
+        f.null |= !s->pose_mean || !s->kp_vertex;
     }
+}
+
+// a record in host memory: a single problem's frame, or an active record on its way into a batch's table
+static void check_frame(const pn2x_hand_pose_problem *r, Faults &f) {
+    if (!is_record(r, f)) return;
+    f.inval |= r->h < 1 || r->w < 1;
+    f.range |= (long)r->h * r->w >= (1L << 31);
+    f.null |= !r->state || !r->work || !r->rest_joints || !r->rest_verts || !r->pred_kp || !r->vis_mask || !r->obj_r || !r->obj_t ||
+              !r->vol || !r->mask;
+}
+
+// the candidates' pose-blend offsets, a MANO setup's scratch: 16-byte stores
+static void check_offsets(const pn2x_hand_pose_setup *s, const float *offsets, Faults &f) {
+    if (!is_record(s) || !s->posedirs) return;
+    f.inval |= ((uintptr_t)offsets & 15) != 0;
+    f.null |= !offsets;
+}
+
+// the kernel argument with the setup's fields set and the per-problem ones unset (the batched kernel sets them from its record)
+static Frame shared_frame(const pn2x_hand_pose_setup &s) {
+    Frame A;
+    memset(&A, 0, sizeof(A));
+    A.P = s.p; A.V = s.v; A.K = s.k;
+    A.parents = s.parents; A.pose_block = s.pose_block; A.pack = s.skin_pack; A.skin_w = s.skin_w; A.comps = s.comps;
+    A.theta_scale = s.theta_scale; A.pre = s.pre; A.res = s.res; A.voxel_scale = s.voxel_scale;
+    A.w_sil = s.w_sil; A.w_pen = s.w_pen; A.w_vis = s.w_vis; A.w_invis = s.w_invis; A.w_tmp = s.w_temporal; A.w_attr = s.w_attr;
+    return A;
+}
+
+// a single problem's kernel argument: what hand_pose_eval_batch_kernel takes from a record, from a record in host memory
+static Frame single_frame(const pn2x_hand_pose_setup &s, const pn2x_hand_pose_problem &r) {
+    Frame A = shared_frame(s);
+    A.rest_j = r.rest_joints; A.rest_v = r.rest_verts; A.state = r.state; A.pred_kp = r.pred_kp; A.last_kp = r.last_kp;
+    A.vis = r.vis_mask; A.obj_r = r.obj_r; A.obj_t = r.obj_t; A.vol = r.vol; A.mask = r.mask; A.h = r.h; A.w = r.w;
+    A.fx = r.fx; A.fy = r.fy; A.cx = r.cx; A.cy = r.cy; A.terms = r.work;
+    return A;
+}
+
+// One evaluation launch of `Kernel` (an instantiation of the three evaluation kernels), whose dynamic-LDS limit is raised once
+// per device.  A workgroup's four waves take a candidate each; the grid's x deals a problem's ceil(p / 4) workgroups evenly
+// over at most max(1, 3 * compute units / active), so the launch covers the device at most three times (a single problem
+// is active == 1); its y is the problem.
+template <auto Kernel, typename... Args>
+static void launch_eval(const pn2x_hand_pose_setup &s, int active, int problems, hipStream_t st, const Args &...args) {
+    static PerDeviceOnce raised;
+    if (raised.first_use())
+        (void)hipFuncSetAttribute((const void *)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)eval_lds_bytes(MAXV, MAXK));
+    const int wgs = (s.p + 3) / 4, share = 3 * num_compute_units() / active, cap = share < 1 ? 1 : share;
+    const int rounds = (wgs + cap - 1) / cap, gx = (wgs + rounds - 1) / rounds;
+    hipLaunchKernelGGL(Kernel, dim3(gx, problems), dim3(256), eval_lds_bytes(s.v, s.k), st, args...);
+}
+
+// a single problem's evaluation: the plain kernel, or for a MANO setup the pose-offset pre-pass and the MANO kernel
+static void eval_single(const pn2x_hand_pose_setup &s, const Frame &A, float *offsets, hipStream_t st) {
+    if (!s.posedirs) {
+        if (s.vol_f16) launch_eval<hand_pose_eval_kernel<true>>(s, 1, 1, st, A);
+        else launch_eval<hand_pose_eval_kernel<false>>(s, 1, 1, st, A);
+        return;
+    }
+    ManoExtra M;
+    M.offsets = offsets; M.pose_mean = s.pose_mean; M.kp_vertex = s.kp_vertex; M.ldo = offsets_ld(s.v); M.centre = s.centre_root;
+    // pre-pass: x = groups of OCT candidates, y = as many strides over the 16-row tiles as cover the compute units three times
+    const int ntiles = M.ldo / 16, gx = (s.p + OCT - 1) / OCT, cover = 3 * num_compute_units() / gx, most = (ntiles + 3) / 4;
+    const int gy = cover < 1 ? 1 : (cover > most ? most : cover);
+    hipLaunchKernelGGL(hand_pose_offsets_kernel, dim3(gx, gy), dim3(256), 0, st, s.p, ntiles, s.posedirs, s.pose_mean, s.comps,
+                       s.theta_scale, s.pre, A.state, offsets);
+    if (s.vol_f16) launch_eval<hand_pose_mano_eval_kernel<true>>(s, 1, 1, st, A, M);
+    else launch_eval<hand_pose_mano_eval_kernel<false>>(s, 1, 1, st, A, M);
+}
+
+extern "C" int pn2x_hand_pose_energy(const pn2x_hand_pose_setup *setup, const pn2x_hand_pose_problem *frame, float *offsets,
+                                     float *energy, float *out_verts, float *out_kp, void *stream) {
+    Faults f;
+    check_setup(setup, f);
+    check_frame(frame, f);
+    check_offsets(setup, offsets, f);
+    f.null |= !energy;
+    if (f.code() != PN2_OK) return f.code();
+    Frame A = single_frame(*setup, *frame);
+    A.out_verts = out_verts; A.out_kp = out_kp;
+    hipStream_t st = (hipStream_t)stream;
+    eval_single(*setup, A, offsets, st);
+    hipLaunchKernelGGL(hand_pose_energy_kernel, dim3((setup->p + 255) / 256), dim3(256), 0, st, setup->p, frame->work, energy);
+    return check_launch();
+}
+
+extern "C" int pn2x_hand_pose_opt(const pn2x_hand_pose_setup *setup, const pn2x_hand_pose_problem *frame, float *offsets,
+                                  int iterations, double scaling_coefficient2, double beta, void *stream) {
+    Faults f;
+    check_setup(setup, f);
+    f.inval |= iterations < 0;
+    f.range |= iterations > 4096;
+    if (iterations != 0) {  // nothing to do: the frame is not looked at
+        check_frame(frame, f);
+        check_offsets(setup, offsets, f);
+    }
+    if (f.code() != PN2_OK || iterations == 0) return f.code();
+    const pn2x_hand_pose_setup &s = *setup;
+    const Frame A = single_frame(s, *frame);
+    hipStream_t st = (hipStream_t)stream;
+    for (int it = 0; it < iterations; ++it) {
+        eval_single(s, A, offsets, st);
+        hipLaunchKernelGGL(hand_pose_update_kernel, dim3(1), dim3(UT), 0, st, s.p, s.pre, frame->work, s.comps, s.theta_scale,
+                           (float)scaling_coefficient2, (float)beta, (float)(1.0 - beta), frame->state,
+                           frame->trace ? frame->trace + (size_t)it * (3 + ND) : nullptr);
+    }
+    return check_launch();
+}
+
+extern "C" int pn2x_hand_pose_problems_fill(pn2x_hand_pose_problem *problems, int s, const pn2x_hand_pose_problem *host, void *stream) {
+    Faults f;
+    f.inval = s < 1;
+    f.range = s > 65535;
+    f.null = !problems || !host;
+    if (f.code() != PN2_OK) return f.code();
+    for (int q = 0; q < s; ++q)  // the records are host memory here: what the batched entry cannot check
+        if (host[q].active) check_frame(host + q, f);
+    if (f.code() != PN2_OK) return f.code();
     hipStream_t st = (hipStream_t)stream;
     for (int q0 = 0; q0 < s; q0 += FILL) {
         const int n = s - q0 < FILL ? s - q0 : FILL;
@@ -812,44 +791,24 @@ extern "C" int pn2x_hand_pose_problems_fill(pn2x_hand_pose_problem *problems, in
     return check_launch();
 }
 
-extern "C" int pn2x_hand_pose_opt_batch(int p, int v, int j, int k, const int *parents, const int *pose_block, const int *skin_pack,
-                                        const float *skin_w, const float *comps, float theta_scale, const float *pre, int vol_f16,
-                                        int res, float voxel_scale, float w_sil, float w_pen, float w_vis, float w_invis,
-                                        float w_temporal, float w_attr, int s, int active, const pn2x_hand_pose_problem *problems,
+extern "C" int pn2x_hand_pose_opt_batch(const pn2x_hand_pose_setup *setup, int s, int active, const pn2x_hand_pose_problem *problems,
                                         int iterations, double scaling_coefficient2, double beta, void *stream) {
-    if (p < 1 || v < 1 || j < 1 || k < 1 || res < 1 || (res & 1) == 0 || !(voxel_scale > 0.f) || (vol_f16 != 0 && vol_f16 != 1) ||
-        s < 1 || active < 0 || active > s || iterations < 0)
-        return PN2_EINVAL;
-    if (!pn2x_hand_pose_opt_supported(p, v, j, k, NC, res) || s > 65535 || iterations > 4096) return PN2_ERANGE;
-    if (!parents || !pose_block || !skin_pack || !skin_w || !comps || !pre) return PN2_ENULL;
-    if (iterations == 0) return PN2_OK;
+    Faults f;
+    check_setup(setup, f);
+    f.inval |= (is_record(setup) && setup->posedirs) || s < 1 || active < 0 || active > s || iterations < 0;  // (no batched MANO kernel)
+    f.range |= s > 65535 || iterations > 4096;
+    if (f.code() != PN2_OK || iterations == 0) return f.code();
     if (!problems) return PN2_ENULL;
     if (active == 0) return PN2_OK;
     Batch B;
-    memset(&B, 0, sizeof(B));
-    Frame &A = B.shared;
-    A.P = p; A.V = v; A.K = k;
-    A.parents = parents; A.pose_block = pose_block; A.pack = skin_pack; A.skin_w = skin_w; A.comps = comps;
-    A.theta_scale = theta_scale; A.pre = pre; A.res = res; A.voxel_scale = voxel_scale;
-    A.w_sil = w_sil; A.w_pen = w_pen; A.w_vis = w_vis; A.w_invis = w_invis; A.w_tmp = w_temporal; A.w_attr = w_attr;
+    B.shared = shared_frame(*setup);
     B.prob = problems;
-    static PerDeviceOnce raised;
-    if (raised.first_use()) {
-        (void)hipFuncSetAttribute((const void *)hand_pose_eval_batch_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)eval_lds_bytes(MAXV, MAXK));
-        (void)hipFuncSetAttribute((const void *)hand_pose_eval_batch_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)eval_lds_bytes(MAXV, MAXK));
-    }
-    // eval_launch's rule with the three covers of the compute units shared among the active problems: a problem's x extent
-    // deals its candidates evenly over at most 3 CUs / active workgroups, and never fewer than one
-    const int wgs = (p + 3) / 4, share = 3 * num_compute_units() / active, cap = share < 1 ? 1 : share;
-    const int rounds = (wgs + cap - 1) / cap, gx = (wgs + rounds - 1) / rounds;
     hipStream_t st = (hipStream_t)stream;
     for (int it = 0; it < iterations; ++it) {
-        if (vol_f16) hipLaunchKernelGGL(hand_pose_eval_batch_kernel<true>, dim3(gx, s), dim3(256), eval_lds_bytes(v, k), st, B);
-        else hipLaunchKernelGGL(hand_pose_eval_batch_kernel<false>, dim3(gx, s), dim3(256), eval_lds_bytes(v, k), st, B);
-        hipLaunchKernelGGL(hand_pose_update_batch_kernel, dim3(s), dim3(UT), 0, st, p, pre, problems, comps, theta_scale,
-                           (float)scaling_coefficient2, (float)beta, (float)(1.0 - beta), it);
+        if (setup->vol_f16) launch_eval<hand_pose_eval_batch_kernel<true>>(*setup, active, s, st, B);
+        else launch_eval<hand_pose_eval_batch_kernel<false>>(*setup, active, s, st, B);
+        hipLaunchKernelGGL(hand_pose_update_batch_kernel, dim3(s), dim3(UT), 0, st, setup->p, setup->pre, problems, setup->comps,
+                           setup->theta_scale, (float)scaling_coefficient2, (float)beta, (float)(1.0 - beta), it);
     }
     return check_launch();
 }

@@ -1059,31 +1059,46 @@ def iknet_forward(kp: torch.Tensor, R: torch.Tensor, t: torch.Tensor, w1, b1, wh
     return raw, theta, kp_hf
 
 
-# ---- hand-pose particle optimiser on the device (include/pn2_ext.h: pn2x_hand_pose_energy / pn2x_hand_pose_opt) ---------------
+# ---- hand-pose particle optimiser on the device (include/pn2_ext.h: pn2x_hand_pose_energy / _opt / _opt_batch) -----------------
 _cf, _cd = ctypes.c_float, ctypes.c_double
-_HAND_POSE_COMMON = ([_ci] * 4 + [_vp] * 7 + [_cf] + [_vp] * 7 + [_ci, _ci, _cf, _vp, _ci, _ci] + [_cf] * 10)
+HAND_POSE_STATE_FLOATS = 90   # curr_r (9), curr_t (3), curr_theta (45), search (16), previous search (16), previous success
+HAND_POSE_TRACE_FLOATS = 19   # E[0], mean_E, success, search after the update (16)
+HAND_POSE_WEIGHTS = ("sil_loss", "penetrate_sum_loss", "vis_regu_loss", "invis_regu_loss", "temporal_smooth", "attraction_loss")
+HAND_POSE_MANO_ENTRIES = ("posedirs", "pose_mean", "kp_vertex", "centre_root")  # skinning_tables()' optional entries
+
+
+class _HandPoseSetup(ctypes.Structure):
+    """pn2x_hand_pose_setup (136 bytes): what the problems of a batch share."""
+    _WEIGHTS = ("w_sil", "w_pen", "w_vis", "w_invis", "w_temporal", "w_attr")   # in HAND_POSE_WEIGHTS' order
+    _fields_ = ([(n, _vp) for n in ("parents", "pose_block", "skin_pack", "skin_w", "comps", "pre", "posedirs", "pose_mean", "kp_vertex")] +
+                [(n, _ci) for n in ("p", "v", "j", "k", "vol_f16", "res", "centre_root", "reserved")] +
+                [(n, _cf) for n in ("theta_scale", "voxel_scale") + _WEIGHTS])
+
+
+class _HandPoseProblem(ctypes.Structure):
+    """pn2x_hand_pose_problem (128 bytes): one problem's frame."""
+    _fields_ = ([(n, _vp) for n in ("state", "work", "rest_joints", "rest_verts", "pred_kp", "last_kp", "vis_mask", "obj_r", "obj_t",
+                                    "vol", "mask", "trace")] +
+                [("h", _ci), ("w", _ci), ("fx", _cf), ("fy", _cf), ("cx", _cf), ("cy", _cf), ("active", _ci), ("reserved", _ci)])
+
+
+_HP_SETUP, _HP_PROBLEM = ctypes.POINTER(_HandPoseSetup), ctypes.POINTER(_HandPoseProblem)
 _lib.pn2x_hand_pose_opt_supported.argtypes = [_ci] * 6
 _lib.pn2x_hand_pose_opt_supported.restype = _ci
 _lib.pn2x_hand_pose_opt_work_floats.argtypes = [_ci]
 _lib.pn2x_hand_pose_opt_work_floats.restype = _cl
-_lib.pn2x_hand_pose_energy.argtypes = _HAND_POSE_COMMON + [_vp] * 6
-_lib.pn2x_hand_pose_energy.restype = _ci
-_lib.pn2x_hand_pose_opt.argtypes = _HAND_POSE_COMMON + [_ci, _cd, _cd] + [_vp] * 4
-_lib.pn2x_hand_pose_opt.restype = _ci
-_lib.pn2x_hand_pose_mano_supported.argtypes = [_ci] * 6
-_lib.pn2x_hand_pose_mano_supported.restype = _ci
 _lib.pn2x_hand_pose_mano_work_floats.argtypes = [_ci, _ci]
 _lib.pn2x_hand_pose_mano_work_floats.restype = _cl
-_lib.pn2x_hand_pose_mano_energy.argtypes = _HAND_POSE_COMMON + [_vp] * 3 + [_ci] + [_vp] * 7
-_lib.pn2x_hand_pose_mano_energy.restype = _ci
-_lib.pn2x_hand_pose_mano_opt.argtypes = _HAND_POSE_COMMON + [_vp] * 3 + [_ci] + [_ci, _cd, _cd] + [_vp] * 5
-_lib.pn2x_hand_pose_mano_opt.restype = _ci
-HAND_POSE_STATE_FLOATS = 90   # curr_r (9), curr_t (3), curr_theta (45), search (16), previous search (16), previous success
-HAND_POSE_TRACE_FLOATS = 19   # E[0], mean_E, success, search after the update (16)
-HAND_POSE_WEIGHTS = ("sil_loss", "penetrate_sum_loss", "vis_regu_loss", "invis_regu_loss", "temporal_smooth", "attraction_loss")
-
-
-HAND_POSE_MANO_ENTRIES = ("posedirs", "pose_mean", "kp_vertex", "centre_root")  # skinning_tables()' optional entries
+_lib.pn2x_hand_pose_opt_batch_work_floats.argtypes = [_ci, _ci]
+_lib.pn2x_hand_pose_opt_batch_work_floats.restype = _cl
+_lib.pn2x_hand_pose_energy.argtypes = [_HP_SETUP, _HP_PROBLEM, _vp, _vp, _vp, _vp, _vp]
+_lib.pn2x_hand_pose_energy.restype = _ci
+_lib.pn2x_hand_pose_opt.argtypes = [_HP_SETUP, _HP_PROBLEM, _vp, _ci, _cd, _cd, _vp]
+_lib.pn2x_hand_pose_opt.restype = _ci
+_lib.pn2x_hand_pose_problems_fill.argtypes = [_vp, _ci, _HP_PROBLEM, _vp]
+_lib.pn2x_hand_pose_problems_fill.restype = _ci
+_lib.pn2x_hand_pose_opt_batch.argtypes = [_HP_SETUP, _ci, _ci, _vp, _ci, _cd, _cd, _vp]
+_lib.pn2x_hand_pose_opt_batch.restype = _ci
 
 
 def hand_pose_opt_supported(p: int, v: int, j: int, k: int, d_pose: int = 10, res: int = 151) -> bool:
@@ -1094,10 +1109,10 @@ def hand_pose_model(tables: dict, device) -> dict:
     """HandModel.skinning_tables() as the device arrays the hand-pose kernels read (built once per model and device):
     int32 parents / pose_block, float32 rest and shape tables, skin_w, comps, and skin_pack = the K joint indices of a vertex
     (5 bits each) with, from bit 20, the tip regions (fingers 0..4 of tips / finger_offsets) the vertex belongs to.
-    Tables with a MANO entry (posedirs, pose_mean, kp_vertex, centre_root) set m["mano"] and add what the pn2x_hand_pose_mano_*
+    Tables with a MANO entry (posedirs, pose_mean, kp_vertex, centre_root) set m["mano"] and add what the MANO
     kernels read: posedirs_pack (ceil16(3 V), 136) = posedirs as rows 3 v + coordinate, zero-padded; pose_mean (45); kp_vertex
     (J) int32; centre_root 0 / 1; and in skin_pack bits 25..29 of a keypoint vertex the table joint it is (mano_ok: no vertex
-    serves two keypoints).  Such a model goes to hand_pose_mano_energy / hand_pose_mano_opt only."""
+    serves two keypoints).  hand_pose_energy / hand_pose_opt run such a model on the MANO kernels; hand_pose_opt_batch refuses it."""
     f32, i32 = torch.float32, torch.int32
     idx = tables["skin_idx"].long()
     V, K = idx.shape
@@ -1146,12 +1161,13 @@ def hand_pose_rest(model: dict, beta: torch.Tensor = None):
             (model["rest_verts"] + (b @ model["shape_verts"]).view(-1, 3)).contiguous())
 
 
-def _hand_pose_args(model, rest, theta_scale, pre, pred_kp, last_kp, vis_mask, obj_r, obj_t, volume, voxel_scale, mask, proj, weights,
-                    mano: bool = False):
-    f32, u8 = torch.float32, torch.uint8
-    if bool(model.get("mano", False)) != mano:  # the plain kernels would drop the model's MANO terms without a word
-        raise ValueError("hand_pose: a model with MANO entries goes to hand_pose_mano_energy / hand_pose_mano_opt, a plain one to "
-                         "hand_pose_energy / hand_pose_opt / hand_pose_opt_batch")
+def _hand_pose_setup(model, pre, theta_scale, volume, voxel_scale, weights, posedirs=None) -> _HandPoseSetup:
+    """The pn2x_hand_pose_setup record of a call: the model's tables, the candidates, the volumes' type and the weights; for a
+    model with MANO entries also its MANO part (posedirs: a packed table in place of the model's posedirs_pack)."""
+    f32, i32 = torch.float32, torch.int32
+    mano = bool(model.get("mano", False))
+    if mano and not model.get("mano_ok", False):
+        raise ValueError("hand_pose_mano: one vertex serves two keypoints (kp_vertex)")
     V, K, J = model["V"], model["K"], model["J"]
     if pre.dim() != 2 or pre.shape[1] != 16:
         raise ValueError(f"hand_pose: pre {tuple(pre.shape)} is not (P, 16)")
@@ -1159,61 +1175,38 @@ def _hand_pose_args(model, rest, theta_scale, pre, pred_kp, last_kp, vis_mask, o
     if volume.dim() != 3 or len(set(volume.shape)) != 1 or volume.dtype not in (torch.float16, f32):
         raise ValueError(f"hand_pose: volume {tuple(volume.shape)} {volume.dtype} is not a cubic fp16 / fp32 volume")
     res = volume.shape[0]
+    if not hand_pose_opt_supported(P, V, J, K, 10, res):
+        raise ValueError(f"hand_pose: P = {P}, V = {V}, J = {J}, K = {K}, res = {res} outside 1..8192, 1..1024, 21, 1..4, odd <= 1024")
+    s = _HandPoseSetup(p=P, v=V, j=J, k=K, vol_f16=1 if volume.dtype == torch.float16 else 0, res=res,
+                       theta_scale=float(theta_scale), voxel_scale=float(voxel_scale))
+    s.parents, s.pose_block = _native._ptr(model["parents"], "parents", i32, J), _native._ptr(model["pose_block"], "pose_block", i32, J)
+    s.skin_pack, s.skin_w = _native._ptr(model["skin_pack"], "skin_pack", i32, V), _native._ptr(model["skin_w"], "skin_w", f32, V * K)
+    s.comps, s.pre = _native._ptr(model["comps"], "comps", f32, 45 * 45), _native._ptr(pre, "pre", f32, P * 16)
+    for field, key in zip(_HandPoseSetup._WEIGHTS, HAND_POSE_WEIGHTS):
+        setattr(s, field, float(weights[key]))
+    if mano:
+        s.posedirs = _native._ptr(model["posedirs_pack"] if posedirs is None else posedirs, "posedirs", f32, (3 * V + 15) // 16 * 16 * 136)
+        s.pose_mean, s.kp_vertex = _native._ptr(model["pose_mean"], "pose_mean", f32, 45), _native._ptr(model["kp_vertex"], "kp_vertex", i32, J)
+        s.centre_root = int(model["centre_root"])
+    return s
+
+
+def _hand_pose_frame(model, state, work, trace, rest, pred_kp, last_kp, vis_mask, obj_r, obj_t, volume, mask, proj) -> _HandPoseProblem:
+    """A pn2x_hand_pose_problem record from the per-frame tensors; state, work and trace (or None) are device addresses."""
+    f32, u8 = torch.float32, torch.uint8
+    V, J = model["V"], model["J"]
     if mask.dim() != 2:
         raise ValueError(f"hand_pose: mask {tuple(mask.shape)} is not (h, w)")
     h, w = mask.shape
-    if not hand_pose_opt_supported(P, V, J, K, 10, res):
-        raise ValueError(f"hand_pose: P = {P}, V = {V}, J = {J}, K = {K}, res = {res} outside 1..8192, 1..1024, 21, 1..4, odd <= 1024")
     rest_j, rest_v = rest
-    args = [P, V, J, K, _native._ptr(model["parents"], "parents", torch.int32, J), _native._ptr(model["pose_block"], "pose_block", torch.int32, J),
-            _native._ptr(rest_j, "rest_joints", f32, J * 3), _native._ptr(rest_v, "rest_verts", f32, V * 3),
-            _native._ptr(model["skin_pack"], "skin_pack", torch.int32, V), _native._ptr(model["skin_w"], "skin_w", f32, V * K),
-            _native._ptr(model["comps"], "comps", f32, 45 * 45), float(theta_scale), _native._ptr(pre, "pre", f32, P * 16),
-            _native._ptr(pred_kp, "pred_kp", f32, J * 3), None if last_kp is None else _native._ptr(last_kp, "last_kp", f32, J * 3),
-            _native._ptr(vis_mask, "vis_mask", u8, J), _native._ptr(obj_r, "obj_r", f32, 9), _native._ptr(obj_t, "obj_t", f32, 3),
-            _native._ptr(volume, "volume", volume.dtype, res ** 3), 1 if volume.dtype == torch.float16 else 0, res, float(voxel_scale),
-            _native._ptr(mask, "mask", u8, h * w), h, w, float(proj["fx"]), float(proj["fy"]), float(proj["cx"]), float(proj["cy"])]
-    return P, args + [float(weights[k]) for k in HAND_POSE_WEIGHTS]
-
-
-def hand_pose_energy(model, rest, theta_scale, pre, state, pred_kp, last_kp, vis_mask, obj_r, obj_t, volume, voxel_scale, mask, proj,
-                     weights, with_geometry: bool = False):
-    """One evaluation of all candidates at `state` (pn2x_hand_pose_energy): model = hand_pose_model(...), rest = hand_pose_rest(...),
-    pre (P,16), state (90,), pred_kp / last_kp (21,3) (last_kp may be None), vis_mask (21,) uint8, obj_r (3,3), obj_t (3,), volume
-    (res,res,res) fp16 / fp32, mask (h,w) uint8 (non-zero = background), proj {fx, fy, cx, cy}, weights {energy_weight names}.
-    -> (energy (P,), vertices (P,V,3) or None, keypoints (P,21,3) or None)."""
-    P, args = _hand_pose_args(model, rest, theta_scale, pre, pred_kp, last_kp, vis_mask, obj_r, obj_t, volume, voxel_scale, mask, proj, weights)
-    f32, dev = torch.float32, pre.device
-    work = torch.empty(int(_lib.pn2x_hand_pose_opt_work_floats(P)), dtype=f32, device=dev)
-    energy = torch.empty(P, dtype=f32, device=dev)
-    verts = torch.empty((P, model["V"], 3), dtype=f32, device=dev) if with_geometry else None
-    kp = torch.empty((P, model["J"], 3), dtype=f32, device=dev) if with_geometry else None
-    with torch.cuda.device(dev):
-        _native._check(_native._call(_lib.pn2x_hand_pose_energy, "hand_pose_energy", None, *args,
-                                     _native._ptr(state, "state", f32, HAND_POSE_STATE_FLOATS), work.data_ptr(), energy.data_ptr(),
-                                     None if verts is None else verts.data_ptr(), None if kp is None else kp.data_ptr(),
-                                     _native._stream(pre)), "hand_pose_energy")
-    return energy, verts, kp
-
-
-def hand_pose_opt(model, rest, theta_scale, pre, state, pred_kp, last_kp, vis_mask, obj_r, obj_t, volume, voxel_scale, mask, proj,
-                  weights, iterations: int, scaling_coefficient2: float, beta: float, trace: bool = False):
-    """`iterations` x (evaluate, update) of gf_optimize_hand_pose.optimize on the device (pn2x_hand_pose_opt), arguments as
-    hand_pose_energy; `state` (90,) is updated in place.  -> trace (iterations, 19) or None."""
-    P, args = _hand_pose_args(model, rest, theta_scale, pre, pred_kp, last_kp, vis_mask, obj_r, obj_t, volume, voxel_scale, mask, proj, weights)
-    f32, dev = torch.float32, pre.device
-    work = torch.empty(int(_lib.pn2x_hand_pose_opt_work_floats(P)), dtype=f32, device=dev)
-    tr = torch.empty((int(iterations), HAND_POSE_TRACE_FLOATS), dtype=f32, device=dev) if trace else None
-    with torch.cuda.device(dev):
-        _native._check(_native._call(_lib.pn2x_hand_pose_opt, "hand_pose_opt", None, *args, int(iterations), float(scaling_coefficient2),
-                                     float(beta), _native._ptr(state, "state", f32, HAND_POSE_STATE_FLOATS), work.data_ptr(),
-                                     None if tr is None else tr.data_ptr(), _native._stream(pre)), "hand_pose_opt")
-    return tr
-
-
-# ---- a hand with MANO's structure (include/pn2_ext.h: pn2x_hand_pose_mano_energy / pn2x_hand_pose_mano_opt) ----------------------
-def hand_pose_mano_supported(p: int, v: int, j: int, k: int, d_pose: int = 10, res: int = 151) -> bool:
-    return bool(_lib.pn2x_hand_pose_mano_supported(int(p), int(v), int(j), int(k), int(d_pose), int(res)))
+    r = _HandPoseProblem(state=state, work=work, trace=trace, h=h, w=w, fx=float(proj["fx"]), fy=float(proj["fy"]), cx=float(proj["cx"]),
+                         cy=float(proj["cy"]), active=1)
+    r.rest_joints, r.rest_verts = _native._ptr(rest_j, "rest_joints", f32, J * 3), _native._ptr(rest_v, "rest_verts", f32, V * 3)
+    r.pred_kp = _native._ptr(pred_kp, "pred_kp", f32, J * 3)
+    r.last_kp = None if last_kp is None else _native._ptr(last_kp, "last_kp", f32, J * 3)
+    r.vis_mask, r.obj_r, r.obj_t = _native._ptr(vis_mask, "vis_mask", u8, J), _native._ptr(obj_r, "obj_r", f32, 9), _native._ptr(obj_t, "obj_t", f32, 3)
+    r.vol, r.mask = _native._ptr(volume, "volume", volume.dtype, volume.shape[0] ** 3), _native._ptr(mask, "mask", u8, h * w)
+    return r
 
 
 def hand_pose_mano_workspace(p: int, v: int, device) -> torch.Tensor:
@@ -1221,76 +1214,62 @@ def hand_pose_mano_workspace(p: int, v: int, device) -> torch.Tensor:
     return torch.empty(int(_lib.pn2x_hand_pose_mano_work_floats(int(p), int(v))), dtype=torch.float32, device=device)
 
 
-def _hand_pose_mano_extra(model, P, offsets, posedirs):
-    if not model.get("mano_ok", False):
-        raise ValueError("hand_pose_mano: one vertex serves two keypoints (kp_vertex)")
-    V = model["V"]
-    n = int(_lib.pn2x_hand_pose_mano_work_floats(P, V))
-    if offsets is None:
-        offsets = torch.empty(n, dtype=torch.float32, device=model["rest_joints"].device)
-    pd = model["posedirs_pack"] if posedirs is None else posedirs
-    return offsets, [_native._ptr(pd, "posedirs", torch.float32, (3 * V + 15) // 16 * 16 * 136),
-                     _native._ptr(model["pose_mean"], "pose_mean", torch.float32, 45),
-                     _native._ptr(model["kp_vertex"], "kp_vertex", torch.int32, model["J"]), int(model["centre_root"])], \
-        _native._ptr(offsets, "offsets", torch.float32, n)
+def _hand_pose_single(setup, model, offsets, state, trace, rest, pred_kp, last_kp, vis_mask, obj_r, obj_t, volume, mask, proj):
+    """What a single-problem call hands over beside the setup: (frame record, offsets address or None, the tensors they point into).
+    A model with MANO entries needs `offsets` (hand_pose_mano_workspace, allocated here when None)."""
+    f32, dev = torch.float32, model["rest_joints"].device
+    work = torch.empty(int(_lib.pn2x_hand_pose_opt_work_floats(setup.p)), dtype=f32, device=dev)
+    off_ptr = None
+    if model.get("mano", False):
+        if offsets is None:
+            offsets = hand_pose_mano_workspace(setup.p, setup.v, dev)
+        off_ptr = _native._ptr(offsets, "offsets", f32, int(_lib.pn2x_hand_pose_mano_work_floats(setup.p, setup.v)))
+    frame = _hand_pose_frame(model, _native._ptr(state, "state", f32, HAND_POSE_STATE_FLOATS), work.data_ptr(),
+                             None if trace is None else trace.data_ptr(), rest, pred_kp, last_kp, vis_mask, obj_r, obj_t, volume, mask, proj)
+    return frame, off_ptr, (work, offsets)
 
 
-def hand_pose_mano_energy(model, rest, theta_scale, pre, state, pred_kp, last_kp, vis_mask, obj_r, obj_t, volume, voxel_scale, mask, proj,
-                          weights, with_geometry: bool = False, offsets: torch.Tensor = None, posedirs: torch.Tensor = None):
-    """hand_pose_energy for a model with MANO entries (pn2x_hand_pose_mano_energy: the pose-offset pre-pass, then the MANO
-    evaluation).  offsets: hand_pose_mano_workspace(P, V) to reuse (else allocated); posedirs: a packed table to use in place
-    of the model's posedirs_pack (tests)."""
-    P, args = _hand_pose_args(model, rest, theta_scale, pre, pred_kp, last_kp, vis_mask, obj_r, obj_t, volume, voxel_scale, mask, proj,
-                              weights, mano=True)
-    f32, dev = torch.float32, pre.device
-    offsets, extra, off_ptr = _hand_pose_mano_extra(model, P, offsets, posedirs)
-    work = torch.empty(int(_lib.pn2x_hand_pose_opt_work_floats(P)), dtype=f32, device=dev)
+def hand_pose_energy(model, rest, theta_scale, pre, state, pred_kp, last_kp, vis_mask, obj_r, obj_t, volume, voxel_scale, mask, proj,
+                     weights, with_geometry: bool = False, *, offsets: torch.Tensor = None, posedirs: torch.Tensor = None):
+    """One evaluation of all candidates at `state` (pn2x_hand_pose_energy): model = hand_pose_model(...), rest = hand_pose_rest(...),
+    pre (P,16), state (90,), pred_kp / last_kp (21,3) (last_kp may be None), vis_mask (21,) uint8, obj_r (3,3), obj_t (3,), volume
+    (res,res,res) fp16 / fp32, mask (h,w) uint8 (non-zero = background), proj {fx, fy, cx, cy}, weights {energy_weight names}.
+    A model with MANO entries runs the pose-offset pre-pass and the MANO evaluation.  offsets: hand_pose_mano_workspace(P, V) to
+    reuse (else allocated); posedirs: a packed table to use in place of the model's posedirs_pack (tests).
+    -> (energy (P,), vertices (P,V,3) or None, keypoints (P,21,3) or None)."""
+    setup = _hand_pose_setup(model, pre, theta_scale, volume, voxel_scale, weights, posedirs)
+    frame, off_ptr, keep = _hand_pose_single(setup, model, offsets, state, None, rest, pred_kp, last_kp, vis_mask, obj_r, obj_t, volume, mask, proj)
+    f32, dev, P = torch.float32, pre.device, setup.p
     energy = torch.empty(P, dtype=f32, device=dev)
     verts = torch.empty((P, model["V"], 3), dtype=f32, device=dev) if with_geometry else None
     kp = torch.empty((P, model["J"], 3), dtype=f32, device=dev) if with_geometry else None
     with torch.cuda.device(dev):
-        _native._check(_native._call(_lib.pn2x_hand_pose_mano_energy, "hand_pose_mano_energy", None, *args, *extra,
-                                     _native._ptr(state, "state", f32, HAND_POSE_STATE_FLOATS), work.data_ptr(), off_ptr,
+        _native._check(_native._call(_lib.pn2x_hand_pose_energy, "hand_pose_energy", None, ctypes.byref(setup), ctypes.byref(frame), off_ptr,
                                      energy.data_ptr(), None if verts is None else verts.data_ptr(),
-                                     None if kp is None else kp.data_ptr(), _native._stream(pre)), "hand_pose_mano_energy")
+                                     None if kp is None else kp.data_ptr(), _native._stream(pre)), "hand_pose_energy")
     return energy, verts, kp
 
 
-def hand_pose_mano_opt(model, rest, theta_scale, pre, state, pred_kp, last_kp, vis_mask, obj_r, obj_t, volume, voxel_scale, mask, proj,
-                       weights, iterations: int, scaling_coefficient2: float, beta: float, trace: bool = False,
-                       offsets: torch.Tensor = None):
-    """hand_pose_opt for a model with MANO entries (pn2x_hand_pose_mano_opt): `iterations` x (pose-offset pre-pass, MANO
-    evaluation, the shared update); `state` (90,) is updated in place.  -> trace (iterations, 19) or None."""
-    P, args = _hand_pose_args(model, rest, theta_scale, pre, pred_kp, last_kp, vis_mask, obj_r, obj_t, volume, voxel_scale, mask, proj,
-                              weights, mano=True)
-    f32, dev = torch.float32, pre.device
-    offsets, extra, off_ptr = _hand_pose_mano_extra(model, P, offsets, None)
-    work = torch.empty(int(_lib.pn2x_hand_pose_opt_work_floats(P)), dtype=f32, device=dev)
-    tr = torch.empty((int(iterations), HAND_POSE_TRACE_FLOATS), dtype=f32, device=dev) if trace else None
-    with torch.cuda.device(dev):
-        _native._check(_native._call(_lib.pn2x_hand_pose_mano_opt, "hand_pose_mano_opt", None, *args, *extra, int(iterations),
-                                     float(scaling_coefficient2), float(beta), _native._ptr(state, "state", f32, HAND_POSE_STATE_FLOATS),
-                                     work.data_ptr(), off_ptr, None if tr is None else tr.data_ptr(), _native._stream(pre)),
-                       "hand_pose_mano_opt")
+def hand_pose_opt(model, rest, theta_scale, pre, state, pred_kp, last_kp, vis_mask, obj_r, obj_t, volume, voxel_scale, mask, proj,
+                  weights, iterations: int, scaling_coefficient2: float, beta: float, trace: bool = False, *,
+                  offsets: torch.Tensor = None):
+    """`iterations` x (evaluate, update) of gf_optimize_hand_pose.optimize on the device (pn2x_hand_pose_opt), arguments as
+    hand_pose_energy; `state` (90,) is updated in place.  -> trace (iterations, 19) or None."""
+    setup = _hand_pose_setup(model, pre, theta_scale, volume, voxel_scale, weights)
+    tr = torch.empty((int(iterations), HAND_POSE_TRACE_FLOATS), dtype=torch.float32, device=pre.device) if trace else None
+    frame, off_ptr, keep = _hand_pose_single(setup, model, offsets, state, tr, rest, pred_kp, last_kp, vis_mask, obj_r, obj_t, volume, mask, proj)
+    with torch.cuda.device(pre.device):
+        _native._check(_native._call(_lib.pn2x_hand_pose_opt, "hand_pose_opt", None, ctypes.byref(setup), ctypes.byref(frame), off_ptr,
+                                     int(iterations), float(scaling_coefficient2), float(beta), _native._stream(pre)), "hand_pose_opt")
     return tr
 
 
-# ---- the same loop for S problems per launch (include/pn2_ext.h: pn2x_hand_pose_opt_batch) ------------------------------------
-class _HandPoseProblem(ctypes.Structure):
-    """pn2x_hand_pose_problem (128 bytes)."""
-    _fields_ = ([(n, _vp) for n in ("state", "work", "rest_joints", "rest_verts", "pred_kp", "last_kp", "vis_mask", "obj_r", "obj_t",
-                                    "vol", "mask", "trace")] +
-                [("h", _ci), ("w", _ci), ("fx", _cf), ("fy", _cf), ("cx", _cf), ("cy", _cf), ("active", _ci), ("reserved", _ci)])
-
-
-_lib.pn2x_hand_pose_opt_batch_work_floats.argtypes = [_ci, _ci]
-_lib.pn2x_hand_pose_opt_batch_work_floats.restype = _cl
-_lib.pn2x_hand_pose_problems_fill.argtypes = [_vp, _ci, ctypes.POINTER(_HandPoseProblem), _vp]
-_lib.pn2x_hand_pose_problems_fill.restype = _ci
-_lib.pn2x_hand_pose_opt_batch.argtypes = ([_ci] * 4 + [_vp] * 5 + [_cf, _vp, _ci, _ci] + [_cf] * 7 + [_ci, _ci, _vp, _ci, _cd, _cd, _vp])
-_lib.pn2x_hand_pose_opt_batch.restype = _ci
+# ---- the same loop for S problems per launch (pn2x_hand_pose_opt_batch) --------------------------------------------------------
 _HAND_POSE_FRAME_KEYS = ("rest", "theta_scale", "pre", "pred_kp", "last_kp", "vis_mask", "obj_r", "obj_t", "volume", "voxel_scale", "mask",
                          "proj", "weights")
+# how hand_pose_opt_batch names the setup fields in which two frames of a batch may differ (the model's tables are one object)
+_HAND_POSE_SHARED = {"pre": "pre", "p": "pre", "res": "volume resolution", "vol_f16": "volume dtype", "voxel_scale": "voxel_scale",
+                     "theta_scale": "theta_scale", **{w: "weights" for w in _HandPoseSetup._WEIGHTS}}
 
 
 def hand_pose_opt_batch(model, frames, states, iterations: int, scaling_coefficient2: float, beta: float, trace: bool = False):
@@ -1300,7 +1279,7 @@ def hand_pose_opt_batch(model, frames, states, iterations: int, scaling_coeffici
       vis_mask, obj_r, obj_t, volume, voxel_scale, mask, proj, weights; a 'model' key is ignored) or None for a problem that
       sits out.  rest, pred_kp, last_kp (None or a tensor), vis_mask, the object pose, the volume (problems may share one), the
       mask with its size and proj differ per problem; pre (one tensor), theta_scale, weights and the volumes' resolution, dtype
-      and voxel_scale are shared, and a batch that mixes them is refused.
+      and voxel_scale are shared, and a batch that mixes them is refused.  So is a model with MANO entries.
     states (S, 90): updated in place; the rows of problems that sit out are not touched.
     Every tensor is read in place by the launches, and the record table is written by launches that carry the records as
     arguments: no upload, no host read -- a captured call replays on whatever its buffers hold then.
@@ -1309,11 +1288,14 @@ def hand_pose_opt_batch(model, frames, states, iterations: int, scaling_coeffici
     S, iterations = len(frames), int(iterations)
     if S < 1:
         raise ValueError("hand_pose_opt_batch: frames is empty")
+    if model.get("mano", False):  # the lockstep kernels would drop the model's MANO terms without a word
+        raise ValueError("hand_pose_opt_batch: a model with MANO entries goes to hand_pose_energy / hand_pose_opt")
     if states.dim() != 2 or tuple(states.shape) != (S, HAND_POSE_STATE_FLOATS):
         raise ValueError(f"hand_pose_opt_batch: states {tuple(states.shape)} is not ({S}, {HAND_POSE_STATE_FLOATS})")
     _native._ptr(states, "states", f32, S * HAND_POSE_STATE_FLOATS)
     dev = states.device
     tr = torch.zeros((S, iterations, HAND_POSE_TRACE_FLOATS), dtype=f32, device=dev) if trace else None
+    sstride, tstride = HAND_POSE_STATE_FLOATS * 4, iterations * HAND_POSE_TRACE_FLOATS * 4
     first, shared, per = None, None, [None] * S
     for q, fr in enumerate(frames):
         if fr is None:
@@ -1321,49 +1303,41 @@ def hand_pose_opt_batch(model, frames, states, iterations: int, scaling_coeffici
         missing = [k for k in _HAND_POSE_FRAME_KEYS if k not in fr]
         if missing:
             raise ValueError(f"hand_pose_opt_batch: frames[{q}] lacks {missing}")
-        P, a = _hand_pose_args(model, *[fr[k] for k in _HAND_POSE_FRAME_KEYS])
-        vol = fr["volume"]
-        mine = {"volume resolution": a[20], "volume dtype": vol.dtype, "voxel_scale": a[21], "theta_scale": a[11], "weights": tuple(a[29:]),
-                "pre": (a[12], P), "device": vol.device}
-        for name, t in (("pre", fr["pre"]), ("pred_kp", fr["pred_kp"]), ("mask", fr["mask"]), ("rest_joints", fr["rest"][0])):
+        mine = _hand_pose_setup(model, fr["pre"], fr["theta_scale"], fr["volume"], fr["voxel_scale"], fr["weights"])
+        for name, t in (("pre", fr["pre"]), ("pred_kp", fr["pred_kp"]), ("mask", fr["mask"]), ("rest_joints", fr["rest"][0]),
+                        ("volume", fr["volume"])):
             if t.device != dev:
                 raise RuntimeError(f"hand_pose_opt_batch: frames[{q}]['{name}'] is on {t.device}, states on {dev}")
         if first is None:
             first, shared = q, mine
-        else:
-            for name in mine:
-                if mine[name] != shared[name]:
-                    what = "one tensor of candidates" if name == "pre" else f"{shared[name]} and {mine[name]}"
-                    raise ValueError(f"hand_pose_opt_batch: frames[{first}] and frames[{q}] differ in {name} ({what}): a batch "
-                                     "shares it; run them in separate batches")
-        per[q] = a
+        for field, name in _HAND_POSE_SHARED.items() if bytes(mine) != bytes(shared) else ():
+            a, b = getattr(shared, field), getattr(mine, field)
+            if a != b:
+                what = "one tensor of candidates" if name == "pre" else f"{a} and {b}"
+                raise ValueError(f"hand_pose_opt_batch: frames[{first}] and frames[{q}] differ in {name} ({what}): a batch "
+                                 "shares it; run them in separate batches")
+        per[q] = _hand_pose_frame(model, states.data_ptr() + q * sstride, None, None if tr is None else tr.data_ptr() + q * tstride,
+                                  fr["rest"], fr["pred_kp"], fr["last_kp"], fr["vis_mask"], fr["obj_r"], fr["obj_t"], fr["volume"],
+                                  fr["mask"], fr["proj"])
     if first is None or iterations == 0:
         if iterations < 0:
             raise ValueError(f"hand_pose_opt_batch: iterations = {iterations}")
         return tr
-    a0 = per[first]
-    P = shared["pre"][1]
-    need = _lib.pn2x_hand_pose_opt_batch_work_floats(P, S)
+    need = _lib.pn2x_hand_pose_opt_batch_work_floats(shared.p, S)
     work = torch.empty((S, need // S), dtype=f32, device=dev)
     table = torch.empty((S, ctypes.sizeof(_HandPoseProblem) // 8), dtype=torch.int64, device=dev)
-    recs = (_HandPoseProblem * S)()
-    wstride, sstride, tstride = work.stride(0) * 4, HAND_POSE_STATE_FLOATS * 4, iterations * HAND_POSE_TRACE_FLOATS * 4
-    for q, a in enumerate(per):
-        if a is None:
-            continue  # (a zeroed record: active == 0, every pointer NULL)
-        r = recs[q]
-        r.state, r.work = states.data_ptr() + q * sstride, work.data_ptr() + q * wstride
-        r.rest_joints, r.rest_verts, r.pred_kp, r.last_kp, r.vis_mask, r.obj_r, r.obj_t, r.vol, r.mask = a[6], a[7], a[13], a[14], a[15], a[16], a[17], a[18], a[22]
-        r.trace = None if tr is None else tr.data_ptr() + q * tstride
-        r.h, r.w, r.fx, r.fy, r.cx, r.cy, r.active = a[23], a[24], a[25], a[26], a[27], a[28], 1
-    n_active = sum(a is not None for a in per)
+    recs = (_HandPoseProblem * S)()   # (a zeroed record: active == 0, every pointer NULL)
+    for q, r in enumerate(per):
+        if r is not None:
+            r.work = work.data_ptr() + q * work.stride(0) * 4
+            recs[q] = r
+    n_active = sum(r is not None for r in per)
     with torch.cuda.device(dev):
         st = _native._stream(states)
         _native._check(_native._call(_lib.pn2x_hand_pose_problems_fill, "hand_pose_problems_fill", None, table.data_ptr(), S, recs, st),
                        "hand_pose_problems_fill")
-        _native._check(_native._call(_lib.pn2x_hand_pose_opt_batch, "hand_pose_opt_batch", None, *a0[0:6], *a0[8:13], a0[19], a0[20], a0[21],
-                                     *a0[29:], S, n_active, table.data_ptr(), iterations, float(scaling_coefficient2), float(beta), st),
-                       "hand_pose_opt_batch")
+        _native._check(_native._call(_lib.pn2x_hand_pose_opt_batch, "hand_pose_opt_batch", None, ctypes.byref(shared), S, n_active,
+                                     table.data_ptr(), iterations, float(scaling_coefficient2), float(beta), st), "hand_pose_opt_batch")
     return tr
 
 

@@ -404,64 +404,17 @@ int pn2x_hand_shape_opt(int p, int d, int t, int iterations, const float *k0, co
 /*
  * Hand-pose particle optimiser (reference gf_optimize_hand_pose.evaluate / optimize, network/models/optimization_hand.py:215-293,
  * :335-394) on the device (hotrack_amd/csrc/hand_pose.hip): hand_pose_eval_kernel evaluates all p candidate hands in one
- * launch, hand_pose_update_kernel (one workgroup) applies an iteration's update.
+ * launch, hand_pose_update_kernel (one workgroup) applies an iteration's update.  Two records carry the arguments.
  *
- * The hand model is a linear-blend-skinning table (HandModel.skinning_tables) at the frame's shape:
+ * pn2x_hand_pose_setup: what the problems of a batch share.  HOST memory, read during the call only.  The hand model is a
+ * linear-blend-skinning table (HandModel.skinning_tables):
  *   parents (j) int32, parents[i] < i, joint 0 the root;  pose_block (j) int32: the 3-vector of the 45 joint angles that rotates
- *   joint i, -1 for none;  rest_joints (j,3), rest_verts (v,3): rest + beta @ shape_*;  skin_w (v,k);  skin_pack (v) int32: bits
- *   5i..5i+4 the joint of weight i < k, bits 20..24 the tip regions (fingers 0..4 of get_attraction_loss) the vertex belongs to;
- *   comps (45,45), rows [0,10) used;  theta_scale (30).  Keypoints are the joint positions.
- * state, 90 floats: [0,9) curr_r row-major, [9,12) curr_t, [12,57) curr_theta, [57,73) search size, [73,89) previous search
- * size, [89] previous success (0 / 1).  Candidate q (pre (p,16), row 0 zero):
- *     s = pre[q] * search;  quat = [sqrt(1 - s0^2 - s1^2 - s2^2), s0, s1, s2]  (NaN for a negative argument, as the reference)
- *     root rotation = curr_r @ quat2mat(quat) (used as a matrix, not through axis-angle);  translation = curr_t + s[3:6];
- *     joint angles = curr_theta + (s[6:16] @ comps[:10]) * theta_scale;  Rodrigues, kinematic chain, skinning (fp32)
- *     per vertex: object frame and nearest voxel exactly as pn2s_nearest (obj_r (3,3), obj_t (3), vol res^3 fp16 / fp32, res odd);
- *       penetration = max |sdf| [sdf < 0];  per finger min of sdf [sdf > 0] over its tip region;  silhouette pixel
- *       (row, col) = trunc(y/z*fy+cy, x/z*fx+cx) clamped to the h x w byte image `mask` (non-zero = background), count / v
- *     keypoints: visible / invisible mean distance to pred_kp (21,3) under vis_mask (21 bytes) with clamp(count, 1) denominators,
- *       mean distance to last_kp (21,3), or no temporal term when last_kp is NULL
- *     energy = sil w_sil + pen w_pen + vis w_vis + invis w_invis + temporal w_temporal + attraction w_attr, added in that order;
- *       penetration, attraction and their products with the weights are rounded to the volume's type; the attraction term
- *       counts for every candidate only if candidate 0 penetrates.
- * work: pn2x_hand_pose_opt_work_floats(p) floats (per candidate: energy without attraction, attraction term, penetration, 0).
- *
- * pn2x_hand_pose_energy: one evaluation at `state` -> energy (p); out_verts (p,v,3) / out_kp (p,21,3) or NULL: the candidates'
- * vertices and keypoints as the optimiser's device function computes them (tests, diagnostics).
- * pn2x_hand_pose_opt: `iterations` x (evaluate, update); state in/out.  Update (:349-386, host branches as selects):
- *     w = (E[0] - E) [E < E[0]];  success = any(E < E[0]);  mean_E = success ? sum w E / sum w : E[0];  mt = sum w [quat | s] / sum w;
- *     mt[:4] /= |mt[:4]|;  on success curr_r = gram_schmidt_rows(curr_r @ quat2mat(mt[:4])), curr_t += mt[4:7],
- *     curr_theta += (mt[7:] @ comps[:10]) * theta_scale;  sz = |success ? mt[1:] : 0| + 1e-3;
- *     search = mean_E * scaling_coefficient2 * sz / ||sz|| + 1e-3;  if (previous success && success) search = beta search +
- *     (1 - beta) previous search;  if (success) previous search = search;  previous success = success.
- *   trace (iterations, 19) or NULL: per iteration [E[0], mean_E, success, search after the update].
- * Sums run in a fixed order (xor butterflies inside a wave, waves in index order), no atomics, no waits between workgroups:
- * two runs give bitwise-equal results.  No host sync or allocation (capturable).  Limits (pn2x_hand_pose_opt_supported): 1 <= p <=
- * 8192, 1 <= v <= 1024, j == 21, 1 <= k <= 4, d_pose == 10 pose components, res odd and <= 1024.  Errors, checked before any
- * device work: PN2_EINVAL for a size < 1, an even res, voxel_scale <= 0, vol_f16 not 0 / 1 or iterations < 0; PN2_ERANGE beyond
- * the limits (or h * w >= 2^31, iterations > 4096); PN2_ENULL for a NULL pointer other than last_kp, out_verts, out_kp, trace;
- * iterations == 0 returns PN2_OK and touches nothing.
- */
-int pn2x_hand_pose_opt_supported(int p, int v, int j, int k, int d_pose, int res);
-long pn2x_hand_pose_opt_work_floats(int p);
-int pn2x_hand_pose_energy(int p, int v, int j, int k, const int *parents, const int *pose_block, const float *rest_joints,
-                          const float *rest_verts, const int *skin_pack, const float *skin_w, const float *comps, float theta_scale,
-                          const float *pre, const float *pred_kp, const float *last_kp, const unsigned char *vis_mask,
-                          const float *obj_r, const float *obj_t, const void *vol, int vol_f16, int res, float voxel_scale,
-                          const unsigned char *mask, int h, int w, float fx, float fy, float cx, float cy, float w_sil, float w_pen,
-                          float w_vis, float w_invis, float w_temporal, float w_attr, const float *state, float *work, float *energy,
-                          float *out_verts, float *out_kp, void *stream);
-int pn2x_hand_pose_opt(int p, int v, int j, int k, const int *parents, const int *pose_block, const float *rest_joints,
-                       const float *rest_verts, const int *skin_pack, const float *skin_w, const float *comps, float theta_scale,
-                       const float *pre, const float *pred_kp, const float *last_kp, const unsigned char *vis_mask,
-                       const float *obj_r, const float *obj_t, const void *vol, int vol_f16, int res, float voxel_scale,
-                       const unsigned char *mask, int h, int w, float fx, float fy, float cx, float cy, float w_sil, float w_pen,
-                       float w_vis, float w_invis, float w_temporal, float w_attr, int iterations, double scaling_coefficient2,
-                       double beta, float *state, float *work, float *trace, void *stream);
-
-/*
- * The same two entries for a hand with MANO's structure (HandModel.skinning_tables with its optional entries; the reference's
- * OurManoLayer.forward, third_party/mano/our_mano.py:218-360).  The arguments of pn2x_hand_pose_energy / pn2x_hand_pose_opt, and:
+ *   joint i, -1 for none;  skin_w (v,k);  skin_pack (v) int32: bits 5i..5i+4 the joint of weight i < k, bits 20..24 the tip regions
+ *   (fingers 0..4 of get_attraction_loss) the vertex belongs to;  comps (45,45), rows [0,10) used;  theta_scale (30);  pre (p,16),
+ *   row 0 zero: the candidates;  vol_f16 0 / 1, res (odd), voxel_scale: the SDF volumes' type, size and spacing;  w_*: the six
+ *   energy weights;  reserved: not read.  Keypoints are the joint positions.
+ * posedirs != NULL makes it a hand with MANO's structure (skinning_tables' optional entries; the reference's
+ * OurManoLayer.forward, third_party/mano/our_mano.py:218-360); with posedirs NULL the other three fields are not read:
  *   posedirs (ceil16(3 v), 136): the pose blend shapes packed for the matrix cores -- row 3 vertex + coordinate, column
  *     9 b + 3 r + c the weight of (R_b - I)[r][c] of pose block b's own rotation, column 135 and the rows from 3 v on zero;
  *     16-byte aligned.  v_rest += posedirs . features before the skinning.
@@ -470,62 +423,72 @@ int pn2x_hand_pose_opt(int p, int v, int j, int k, const int *parents, const int
  *     pose_block -1, is nobody's parent and no weight names it, and bits 25..29 of that vertex's skin_pack hold i (a vertex
  *     serves one keypoint at most); -1 = a joint.  kp_vertex[0] is -1.
  *   centre_root 0 / 1: keypoint 0 (= rest_joints[0]) is subtracted from vertices and keypoints before the translation is added.
- *   offsets: pn2x_hand_pose_mano_work_floats(p, v) = p * ceil16(3 v) floats of scratch (the candidates' pose-blend offsets),
- *     16-byte aligned; `work` is pn2x_hand_pose_opt_work_floats(p) as before.
- * Per iteration: hand_pose_offsets_kernel (every candidate's 135 features by the evaluation's own angle and Rodrigues functions,
- * times posedirs on v_mfma_f32_16x16x4_f32, into `offsets`), hand_pose_mano_eval_kernel (the evaluation above with the offset
- * added to every staged v_rest - j_k, fingertip keypoints from vertices, the centring; the terms, their order and rounding as
- * in the plain kernel) and, for _opt, the same hand_pose_update_kernel.  Deterministic and capturable like the plain entries;
- * the limits are the same (pn2x_hand_pose_mano_supported).  Errors as the plain entries, and PN2_ENULL for NULL posedirs,
- * pose_mean, kp_vertex or offsets, PN2_EINVAL for centre_root not 0 / 1 or a misaligned posedirs / offsets.
- */
-int pn2x_hand_pose_mano_supported(int p, int v, int j, int k, int d_pose, int res);
-long pn2x_hand_pose_mano_work_floats(int p, int v);
-int pn2x_hand_pose_mano_energy(int p, int v, int j, int k, const int *parents, const int *pose_block, const float *rest_joints,
-                               const float *rest_verts, const int *skin_pack, const float *skin_w, const float *comps,
-                               float theta_scale, const float *pre, const float *pred_kp, const float *last_kp,
-                               const unsigned char *vis_mask, const float *obj_r, const float *obj_t, const void *vol, int vol_f16,
-                               int res, float voxel_scale, const unsigned char *mask, int h, int w, float fx, float fy, float cx,
-                               float cy, float w_sil, float w_pen, float w_vis, float w_invis, float w_temporal, float w_attr,
-                               const float *posedirs, const float *pose_mean, const int *kp_vertex, int centre_root,
-                               const float *state, float *work, float *offsets, float *energy, float *out_verts, float *out_kp,
-                               void *stream);
-int pn2x_hand_pose_mano_opt(int p, int v, int j, int k, const int *parents, const int *pose_block, const float *rest_joints,
-                            const float *rest_verts, const int *skin_pack, const float *skin_w, const float *comps,
-                            float theta_scale, const float *pre, const float *pred_kp, const float *last_kp,
-                            const unsigned char *vis_mask, const float *obj_r, const float *obj_t, const void *vol, int vol_f16,
-                            int res, float voxel_scale, const unsigned char *mask, int h, int w, float fx, float fy, float cx,
-                            float cy, float w_sil, float w_pen, float w_vis, float w_invis, float w_temporal, float w_attr,
-                            const float *posedirs, const float *pose_mean, const int *kp_vertex, int centre_root, int iterations,
-                            double scaling_coefficient2, double beta, float *state, float *work, float *offsets, float *trace,
-                            void *stream);
-
-/*
- * pn2x_hand_pose_opt for s independent problems (hand sequences that advance one frame together) with one set of launches:
- * per iteration one launch of hand_pose_eval_batch_kernel over a (candidates, problem) grid and one launch of
- * hand_pose_update_batch_kernel with a workgroup per problem.  The kernels run pn2x_hand_pose_opt's device functions, so a
- * problem's state and trace equal, bit for bit, what pn2x_hand_pose_opt gives for it alone.
  *
- * Shared by the batch: p, v, j, k, parents, pose_block, skin_pack, skin_w, comps, theta_scale, pre, the volume's type, res and
- * voxel_scale, the six weights, iterations, scaling_coefficient2, beta.  Per problem, one pn2x_hand_pose_problem record in a
- * DEVICE array `problems` (s records): state (90, in/out), work (pn2x_hand_pose_opt_work_floats(p) floats of its own),
- * rest_joints / rest_verts (they carry the sequence's shape code), pred_kp, last_kp (may be NULL), vis_mask, obj_r, obj_t, vol
- * (problems may share one), mask with its h and w, fx, fy, cx, cy, trace (its (iterations, 19) slice, or NULL) and `active`: a
- * problem with active == 0 sits out -- no pointer of its record is read (all may be NULL) and nothing of it is written.
- * `active` (the argument) is the number of active records; it sizes the grid: a problem's x extent deals its ceil(p / 4)
- * workgroups evenly over at most max(1, 3 * compute units / active), so the launch covers the device about three times.
+ * pn2x_hand_pose_problem: one problem's frame.  state (90, in/out; below);  work: pn2x_hand_pose_opt_work_floats(p) floats of
+ * its own (per candidate: energy without attraction, attraction term, penetration, 0);  rest_joints (j,3), rest_verts (v,3):
+ * rest + beta @ shape_* (they carry the sequence's shape code);  pred_kp (21,3);  last_kp (21,3) or NULL;  vis_mask (21 bytes);
+ * obj_r (3,3), obj_t (3);  vol res^3 fp16 / fp32 (problems may share one);  mask: the h x w byte image (non-zero = background);
+ * fx, fy, cx, cy;  trace (iterations, 19) or NULL;  active, reserved: read by the batched entry only.
  *
+ * state, 90 floats: [0,9) curr_r row-major, [9,12) curr_t, [12,57) curr_theta, [57,73) search size, [73,89) previous search size, [89]
+ * previous success (0 / 1).  Candidate q:
+ *     s = pre[q] * search;  quat = [sqrt(1 - s0^2 - s1^2 - s2^2), s0, s1, s2]  (NaN for a negative argument, as the reference)
+ *     root rotation = curr_r @ quat2mat(quat) (used as a matrix, not through axis-angle);  translation = curr_t + s[3:6];
+ *     joint angles = curr_theta + (s[6:16] @ comps[:10]) * theta_scale;  Rodrigues, kinematic chain, skinning (fp32)
+ *     per vertex: object frame and nearest voxel exactly as pn2s_nearest;  penetration = max |sdf| [sdf < 0];  per finger min of
+ *       sdf [sdf > 0] over its tip region;  silhouette pixel (row, col) = trunc(y/z*fy+cy, x/z*fx+cx) clamped to the mask, count / v
+ *     keypoints: visible / invisible mean distance to pred_kp under vis_mask with clamp(count, 1) denominators, mean distance
+ *       to last_kp, or no temporal term when last_kp is NULL
+ *     energy = sil w_sil + pen w_pen + vis w_vis + invis w_invis + temporal w_temporal + attraction w_attr, added in that order;
+ *       penetration, attraction and their products with the weights are rounded to the volume's type; the attraction term
+ *       counts for every candidate only if candidate 0 penetrates.
+ * A MANO setup runs, before every evaluation, hand_pose_offsets_kernel (every candidate's 135 features by the evaluation's own
+ * angle and Rodrigues functions, times posedirs on v_mfma_f32_16x16x4_f32, into `offsets`) and then hand_pose_mano_eval_kernel
+ * (the evaluation above with the offset added to every staged v_rest - j_k, fingertip keypoints from vertices, the centring;
+ * the terms, their order and rounding as in the plain kernel).  offsets: pn2x_hand_pose_mano_work_floats(p, v) = p *
+ * ceil16(3 v) floats of scratch, 16-byte aligned, required exactly when posedirs is set.
+ *
+ * pn2x_hand_pose_energy: one evaluation at frame->state -> energy (p); out_verts (p,v,3) / out_kp (p,21,3) or NULL: the
+ * candidates' vertices and keypoints as the optimiser's device function computes them (tests, diagnostics).
+ * pn2x_hand_pose_opt: `iterations` x (evaluate, update).  Update (:349-386, host branches as selects):
+ *     w = (E[0] - E) [E < E[0]];  success = any(E < E[0]);  mean_E = success ? sum w E / sum w : E[0];  mt = sum w [quat | s] / sum w;
+ *     mt[:4] /= |mt[:4]|;  on success curr_r = gram_schmidt_rows(curr_r @ quat2mat(mt[:4])), curr_t += mt[4:7],
+ *     curr_theta += (mt[7:] @ comps[:10]) * theta_scale;  sz = |success ? mt[1:] : 0| + 1e-3;
+ *     search = mean_E * scaling_coefficient2 * sz / ||sz|| + 1e-3;  if (previous success && success) search = beta search +
+ *     (1 - beta) previous search;  if (success) previous search = search;  previous success = success.
+ *   trace row per iteration: [E[0], mean_E, success, search after the update].
+ * For both, `frame` is one record in HOST memory, read during the call.
+ * pn2x_hand_pose_opt_batch: pn2x_hand_pose_opt for s independent problems (hand sequences that advance one frame together) with
+ * one set of launches: per iteration hand_pose_eval_batch_kernel over a (candidates, problem) grid and
+ * hand_pose_update_batch_kernel with a workgroup per problem.  They run pn2x_hand_pose_opt's device functions, so a problem's
+ * state and trace equal, bit for bit, what pn2x_hand_pose_opt gives for it alone.  `problems` is a DEVICE array of s records;
+ * a record with active == 0 sits out -- no pointer of it is read (all may be NULL) and nothing of it is written.  `active`
+ * (the argument) is the number of active records.  There is no batched MANO kernel: a setup with posedirs set is PN2_EINVAL.
+ * Every evaluation grid deals a problem's ceil(p / 4) workgroups evenly over at most max(1, 3 * compute units / active)
+ * (active = 1 for the single entries), so the launch covers the device about three times.
  * pn2x_hand_pose_problems_fill writes s records from HOST memory `host` into the device array by kernel launches that carry
- * them as arguments (16 records per launch): no copy engine, no pinned memory, and a captured graph holds the records.  It is
- * where the records are checked: for an active record PN2_EINVAL for h or w < 1, PN2_ERANGE for h * w >= 2^31, PN2_ENULL for a
- * NULL pointer other than last_kp and trace.
+ * them as arguments (16 records per launch): no copy engine, no pinned memory, and a captured graph holds the records.  It
+ * checks the active records as the single entries check their frame.
  * pn2x_hand_pose_opt_batch_work_floats(p, s) = s * pn2x_hand_pose_opt_work_floats(p): scratch for s problems (slice q for
  * problem q).
- * Errors of pn2x_hand_pose_opt_batch, before any device work: PN2_EINVAL for s < 1, active outside [0, s] and whatever
- * pn2x_hand_pose_opt answers with it; PN2_ERANGE beyond pn2x_hand_pose_opt_supported, s > 65535 or iterations > 4096; PN2_ENULL
- * for a NULL shared pointer or, when there is work to do, NULL `problems`.  iterations == 0 and active == 0 return PN2_OK and
- * launch nothing.  No host sync or allocation (capturable).
+ *
+ * Sums run in a fixed order (xor butterflies inside a wave, waves in index order), no atomics, no waits between workgroups:
+ * two runs give bitwise-equal results.  No host sync or allocation (capturable).  Limits (pn2x_hand_pose_opt_supported): 1 <= p <=
+ * 8192, 1 <= v <= 1024, j == 21, 1 <= k <= 4, d_pose == 10 pose components, res odd and <= 1024.  Errors, checked before any
+ * device work, PN2_EINVAL before PN2_ERANGE before PN2_ENULL: PN2_EINVAL for a size < 1 (p, v, j, k, res, h, w, s), an even res,
+ * voxel_scale <= 0, vol_f16 or centre_root not 0 / 1, a misaligned posedirs / offsets, iterations < 0 or active outside [0, s];
+ * PN2_ERANGE beyond the limits, for h * w >= 2^31, iterations > 4096 or s > 65535; PN2_ENULL for a NULL record or a NULL
+ * pointer other than last_kp, trace, out_verts, out_kp (and posedirs).  A host record pointer below 64 KiB is PN2_EINVAL and is not
+ * read: it is what a caller built against ABI version 3 passes (its first argument was p), and no process owns such an address.  iterations == 0 returns PN2_OK and touches nothing --
+ * the frame record or the table may then be NULL, a bad setup is still refused -- and so does active == 0 with a table.
  */
+typedef struct pn2x_hand_pose_setup {
+    const int *parents, *pose_block, *skin_pack;
+    const float *skin_w, *comps, *pre, *posedirs, *pose_mean;
+    const int *kp_vertex;
+    int p, v, j, k, vol_f16, res, centre_root, reserved;
+    float theta_scale, voxel_scale, w_sil, w_pen, w_vis, w_invis, w_temporal, w_attr;
+} pn2x_hand_pose_setup; /* 136 bytes */
 typedef struct pn2x_hand_pose_problem {
     float *state, *work;
     const float *rest_joints, *rest_verts, *pred_kp, *last_kp;
@@ -538,13 +501,17 @@ typedef struct pn2x_hand_pose_problem {
     float fx, fy, cx, cy;
     int active, reserved;
 } pn2x_hand_pose_problem; /* 128 bytes */
+int pn2x_hand_pose_opt_supported(int p, int v, int j, int k, int d_pose, int res);
+long pn2x_hand_pose_opt_work_floats(int p);
+long pn2x_hand_pose_mano_work_floats(int p, int v);
 long pn2x_hand_pose_opt_batch_work_floats(int p, int s);
+int pn2x_hand_pose_energy(const pn2x_hand_pose_setup *setup, const pn2x_hand_pose_problem *frame, float *offsets, float *energy,
+                          float *out_verts, float *out_kp, void *stream);
+int pn2x_hand_pose_opt(const pn2x_hand_pose_setup *setup, const pn2x_hand_pose_problem *frame, float *offsets, int iterations,
+                       double scaling_coefficient2, double beta, void *stream);
 int pn2x_hand_pose_problems_fill(pn2x_hand_pose_problem *problems, int s, const pn2x_hand_pose_problem *host, void *stream);
-int pn2x_hand_pose_opt_batch(int p, int v, int j, int k, const int *parents, const int *pose_block, const int *skin_pack,
-                             const float *skin_w, const float *comps, float theta_scale, const float *pre, int vol_f16, int res,
-                             float voxel_scale, float w_sil, float w_pen, float w_vis, float w_invis, float w_temporal, float w_attr,
-                             int s, int active, const pn2x_hand_pose_problem *problems, int iterations, double scaling_coefficient2,
-                             double beta, void *stream);
+int pn2x_hand_pose_opt_batch(const pn2x_hand_pose_setup *setup, int s, int active, const pn2x_hand_pose_problem *problems,
+                             int iterations, double scaling_coefficient2, double beta, void *stream);
 
 /*
  * IKNet forward in eval mode (reference hand_network.py:264-322; hotrack_amd/csrc/iknet.hip) for m <= 16 rows, fp32:

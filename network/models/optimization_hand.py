@@ -236,9 +236,8 @@ class gf_optimize_hand_pose:
         m = self._kernel_model()
         if m["mano"] and not m["mano_ok"]:
             return "one vertex of the hand model serves two keypoints (kp_vertex)"
-        supported = ext.hand_pose_mano_supported if m["mano"] else ext.hand_pose_opt_supported
         if not (m["fingers_ok"] and self.optimize_dim == 16 and self.mano_layer_right.num_pose == 45 and
-                supported(self.particle_size, m["V"], m["J"], m["K"], self.ncomps, self.volume_size)):
+                ext.hand_pose_opt_supported(self.particle_size, m["V"], m["J"], m["K"], self.ncomps, self.volume_size)):
             return (f"the sizes are outside the kernel's limits (particles {self.particle_size}, vertices {m['V']}, joints {m['J']}, "
                     f"weights per vertex {m['K']}, volume {self.volume_size})")
         return None
@@ -277,16 +276,13 @@ class gf_optimize_hand_pose:
         from hotrack_amd import ext
         state = self._pack_state(self.initial_scale)
         frame = self._kernel_frame()
-        kw = dict(state=state, iterations=self.iteration, scaling_coefficient2=self.scaling_coefficient2, beta=self.beta,
-                  trace=self.keep_trace, **frame)
         m = frame["model"]
         if m["mano"]:
             key = (self.particle_size, m["V"])
             if self.__dict__.get("_mano_work_key") != key:
                 self._mano_work, self._mano_work_key = ext.hand_pose_mano_workspace(*key, self.device), key
-            self.trace = ext.hand_pose_mano_opt(offsets=self._mano_work, **kw)
-        else:
-            self.trace = ext.hand_pose_opt(**kw)
+        self.trace = ext.hand_pose_opt(state=state, iterations=self.iteration, scaling_coefficient2=self.scaling_coefficient2,
+                                       beta=self.beta, trace=self.keep_trace, offsets=self._mano_work if m["mano"] else None, **frame)
         self.curr_r, self.curr_t, self.curr_theta = state[0:9].view(1, 3, 3), state[9:12].view(1, 3, 1), state[12:57].view(1, 45)
         self.search_size, self.prev_search_size, self.prev_success = state[57:73], state[73:89], state[89] != 0
 

@@ -100,7 +100,7 @@ def test_library_exports_every_declared_symbol(hip_lib_path):
         for name in _declared(header):
             assert hasattr(lib, name), f"{name} declared in {header} but not exported"
     lib.pn2_abi_version.restype = ctypes.c_int
-    assert lib.pn2_abi_version() == 3  # 3: the pairable training operators take problem records, their _pair / _ld entries removed
+    assert lib.pn2_abi_version() == 4  # 4: the hand-pose entries take a setup and a problem record, the _mano_ entries removed
     lib.pn2_strerror.restype = ctypes.c_char_p
     assert b"NULL" in lib.pn2_strerror(-2)
 
@@ -235,6 +235,7 @@ def test_bound_records_match_the_header_structs():
     from hotrack_amd import ext, train_ops, train_stack
     c = ctypes
     bound = {"pn2x_sa_problem": ext._SaProblem, "pn2x_hand_pose_problem": ext._HandPoseProblem,
+             "pn2x_hand_pose_setup": ext._HandPoseSetup,
              "pn2x_sa_layer1_stats_problem": train_ops._SaLayer1StatsProblem,
              "pn2x_rows_segment_sum_problem": train_ops._RowsSegmentSumProblem,
              "pn2x_bn_relu_max_problem": train_ops._BnReluMaxProblem,
@@ -253,7 +254,7 @@ def test_bound_records_match_the_header_structs():
     for name, fields in records.items():
         assert [(n, kinds[t]) for n, t in bound[name]._fields_] == fields, name
         assert c.sizeof(bound[name]) == asserted[name], name
-    # pointers, then 8-byte, then 4-byte scalars in the records of the training operators: no implicit padding
+    # pointers, then 8-byte, then 4-byte scalars in the records of the training operators and the hand-pose setup: no implicit padding
     for name in sorted(set(records) - {"pn2x_sa_problem", "pn2x_hand_pose_problem"}):
         sizes = [c.sizeof(t) for _, t in bound[name]._fields_]
         assert sizes == sorted(sizes, reverse=True) and sum(sizes) == c.sizeof(bound[name]), name

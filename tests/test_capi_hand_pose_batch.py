@@ -3,27 +3,10 @@ pn2x_hand_pose_problems_fill, pn2x_hand_pose_opt_batch_work_floats) -- bad sizes
 iterations and a batch whose problems all sit out are no-ops -- before anything touches the device."""
 import ctypes
 
-vp, ci, cl, cf, cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_double
+from hotrack_amd.ext import _HandPoseProblem as Problem, _HandPoseSetup as Setup, _lib
+
+vp = ctypes.c_void_p
 EINVAL, ENULL, ERANGE = -1, -2, -3
-
-
-class Problem(ctypes.Structure):
-    _fields_ = ([(n, vp) for n in ("state", "work", "rest_joints", "rest_verts", "pred_kp", "last_kp", "vis_mask", "obj_r", "obj_t", "vol",
-                                   "mask", "trace")] +
-                [("h", ci), ("w", ci), ("fx", cf), ("fy", cf), ("cx", cf), ("cy", cf), ("active", ci), ("reserved", ci)])
-
-
-def _lib(path):
-    lib = ctypes.CDLL(path)
-    lib.pn2x_hand_pose_opt_batch_work_floats.argtypes = [ci, ci]
-    lib.pn2x_hand_pose_opt_batch_work_floats.restype = cl
-    lib.pn2x_hand_pose_opt_work_floats.argtypes = [ci]
-    lib.pn2x_hand_pose_opt_work_floats.restype = cl
-    lib.pn2x_hand_pose_problems_fill.argtypes = [vp, ci, ctypes.POINTER(Problem), vp]
-    lib.pn2x_hand_pose_problems_fill.restype = ci
-    lib.pn2x_hand_pose_opt_batch.argtypes = [ci] * 4 + [vp] * 5 + [cf, vp, ci, ci] + [cf] * 7 + [ci, ci, vp, ci, cd, cd, vp]
-    lib.pn2x_hand_pose_opt_batch.restype = ci
-    return lib
 
 
 def test_the_library_exports_the_batched_entry(hip_lib_path):
@@ -33,22 +16,22 @@ def test_the_library_exports_the_batched_entry(hip_lib_path):
     assert ctypes.sizeof(Problem) == 128
 
 
-def test_work_floats(hip_lib_path):
-    lib = _lib(hip_lib_path)
+def test_work_floats():
+    lib = _lib
     for p, s in ((1, 1), (5120, 1), (5120, 16), (260, 5), (0, 3), (3, 0), (8192, 65535)):
         assert lib.pn2x_hand_pose_opt_batch_work_floats(p, s) == s * lib.pn2x_hand_pose_opt_work_floats(p) == 4 * p * s, (p, s)
     assert lib.pn2x_hand_pose_opt_batch_work_floats(-1, 2) == EINVAL and lib.pn2x_hand_pose_opt_batch_work_floats(2, -1) == EINVAL
 
 
-def test_hand_pose_opt_batch_argument_validation(hip_lib_path):
-    lib = _lib(hip_lib_path)
+def test_hand_pose_opt_batch_argument_validation():
+    lib = _lib
     one = vp(16)
-    model = dict(parents=one, pose_block=one, pack=one, skin_w=one, comps=one, pre=one)
+    model = dict(parents=16, pose_block=16, skin_pack=16, skin_w=16, comps=16, pre=16)
 
     def call(p=256, v=70, j=21, k=2, f16=1, res=17, scale=0.01, s=3, active=3, problems=one, iterations=5, **ptr):
-        m = dict(model, **ptr)
-        return lib.pn2x_hand_pose_opt_batch(p, v, j, k, m["parents"], m["pose_block"], m["pack"], m["skin_w"], m["comps"], 30.0, m["pre"],
-                                            f16, res, scale, 0.1, 1.0, 10.0, 0.0, 1.0, 0.05, s, active, problems, iterations, 0.1, 0.9, None)
+        setup = Setup(p=p, v=v, j=j, k=k, vol_f16=f16, res=res, theta_scale=30.0, voxel_scale=scale, w_sil=0.1, w_pen=1.0, w_vis=10.0,
+                      w_invis=0.0, w_temporal=1.0, w_attr=0.05, **dict(model, **ptr))
+        return lib.pn2x_hand_pose_opt_batch(setup, s, active, problems, iterations, 0.1, 0.9, None)
 
     # bad sizes: what pn2x_hand_pose_opt rejects, and s < 1, active outside [0, s]
     assert call(s=0) == EINVAL and call(s=-2) == EINVAL and call(active=-1) == EINVAL and call(active=4) == EINVAL
@@ -67,10 +50,11 @@ def test_hand_pose_opt_batch_argument_validation(hip_lib_path):
     assert call(active=0) == 0 and call(active=0, problems=None, iterations=0) == 0
     assert call(s=65535, active=0) == 0
     assert call(iterations=0, s=0) == EINVAL and call(iterations=0, pre=None) == ENULL   # (a no-op does not excuse a bad argument)
+    assert lib.pn2x_hand_pose_opt_batch(None, 3, 3, one, 5, 0.1, 0.9, None) == ENULL      # the setup record itself
 
 
-def test_problems_fill_argument_validation(hip_lib_path):
-    lib = _lib(hip_lib_path)
+def test_problems_fill_argument_validation():
+    lib = _lib
     one = vp(16)
 
     def recs(n=3, **change):

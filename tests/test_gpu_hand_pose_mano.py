@@ -124,14 +124,14 @@ def _started(name):
 
 def _kernel_eval(opt, **kw):
     from hotrack_amd import ext
-    out = ext.hand_pose_mano_energy(state=opt._pack_state(opt.initial_scale), with_geometry=True, **opt._kernel_frame(), **kw)
+    out = ext.hand_pose_energy(state=opt._pack_state(opt.initial_scale), with_geometry=True, **opt._kernel_frame(), **kw)
     torch.cuda.synchronize()
     return [x.cpu() for x in out]
 
 
 def test_the_mano_route_exists_and_is_taken():
     from hotrack_amd import ext
-    assert callable(ext.hand_pose_mano_opt) and callable(ext.hand_pose_mano_energy)
+    assert callable(ext.hand_pose_opt) and callable(ext.hand_pose_energy)
     from models.hand_model import named_hand_model
     cfg = {"device": "cuda", "opt": {"fused_pose": True}}
     opt = gf_optimize_hand_pose(cfg, hand_model=named_hand_model("synthetic_mano"), particle_size=64)
