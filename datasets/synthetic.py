@@ -128,12 +128,12 @@ def get_dataloader(cfg, mode="train", shuffle=False, num_workers=0, distributed=
             and cfg.get("hand_model") is not None):
         ds = SyntheticHandObjectSequences(cfg, syn.get("test_sequences", 2), syn.get("sequence_frames", 20) if length is None else length,
                                           hand_beta=syn.get("hand_beta"), obj_as_mesh=bool(cfg.get("obj_as_mesh", False)),
-                                          obj_mesh_path=cfg.get("obj_mesh"))
+                                          obj_mesh_path=cfg.get("obj_mesh"), from_depth=bool(cfg.get("from_depth", False)))
         return torch.utils.data.DataLoader(ds, batch_size=1, shuffle=False, collate_fn=lambda b: b[0])
     if cfg.get("track") == "obj_opt":
         ds = SyntheticObjectSequences(cfg, syn.get("test_sequences", 2), syn.get("sequence_frames", 30) if length is None else length,
                                       obj_as_mesh=bool(cfg.get("obj_as_mesh", False)),
-                                          obj_mesh_path=cfg.get("obj_mesh"))
+                                      obj_mesh_path=cfg.get("obj_mesh"), from_depth=bool(cfg.get("from_depth", False)))
         return torch.utils.data.DataLoader(ds, batch_size=1, shuffle=False, collate_fn=lambda b: b[0])
     if cfg.get("track"):
         ds = SyntheticSequences(cfg, syn.get("test_sequences", 4),
@@ -144,6 +144,54 @@ def get_dataloader(cfg, mode="train", shuffle=False, num_workers=0, distributed=
     sampler = torch.utils.data.distributed.DistributedSampler(ds, shuffle=shuffle) if distributed else None
     return torch.utils.data.DataLoader(ds, batch_size=cfg["batch_size"], shuffle=shuffle and sampler is None, sampler=sampler,
                                        num_workers=num_workers, drop_last=(mode == "train"))
+
+
+# ---- depth frames (models/frame_frontend.py reads them) ---------------------------------------------------------------
+def render_depth_frame(hand_pts, obj_pts, K, h: int, w: int, splat: int = 0, depth_scale: float = 0.001):
+    """Z-buffer point splat on the CPU: what a depth camera with intrinsics K = {fx, fy, cx, cy} (or a 3x3 matrix) and an h x w
+    sensor sees of two clouds (n,3) in the camera frame (z > 0 forward; either may be None).  A point lands on the pixel nearest
+    to its projection (and on the (2 splat + 1)^2 pixels round it) with its own z; the nearest z wins a pixel.
+    -> depth (h,w) float32 metres, 0 where nothing landed;  seg (h,w,3) uint8, channel 0 == 255 on the hand's pixels and channel
+    1 == 255 on the object's (HO3D's colours);  depth_u16 (h,w) uint16 = round(depth / depth_scale);  depth_scale."""
+    if not isinstance(K, dict):
+        K = np.asarray(K, dtype=np.float64)
+        K = {"fx": K[0, 0], "fy": K[1, 1], "cx": K[0, 2], "cy": K[1, 2]}
+    fx, fy, cx, cy = (float(np.asarray(K[k]).reshape(-1)[0]) for k in ("fx", "fy", "cx", "cy"))
+    depth = np.full((h, w), np.inf, dtype=np.float32)
+    label = np.full((h, w), -1, dtype=np.int64)
+    for cls, pts in enumerate((hand_pts, obj_pts)):
+        if pts is None or len(pts) == 0:
+            continue
+        pts = np.asarray(pts, dtype=np.float64).reshape(-1, 3)
+        pts = pts[pts[:, 2] > 1e-6]
+        u0 = np.rint(pts[:, 0] / pts[:, 2] * fx + cx).astype(np.int64)
+        v0 = np.rint(pts[:, 1] / pts[:, 2] * fy + cy).astype(np.int64)
+        z = pts[:, 2].astype(np.float32)
+        for dv in range(-splat, splat + 1):
+            for du in range(-splat, splat + 1):
+                u, v = u0 + du, v0 + dv
+                ok = (u >= 0) & (u < w) & (v >= 0) & (v < h)
+                flat = v[ok] * w + u[ok]
+                order = np.argsort(-z[ok], kind="stable")   # far to near: the nearest point is written last
+                flat, zz = flat[order], z[ok][order]
+                near = zz < depth.reshape(-1)[flat]
+                depth.reshape(-1)[flat[near]] = zz[near]
+                label.reshape(-1)[flat[near]] = cls
+    depth[~np.isfinite(depth)] = 0.0
+    seg = np.zeros((h, w, 3), dtype=np.uint8)
+    seg[..., 0][label == 0] = 255
+    seg[..., 1][label == 1] = 255
+    raw = np.clip(np.rint(depth.astype(np.float64) / depth_scale), 0, 65535).astype(np.uint16)
+    return depth, seg, raw, float(depth_scale)
+
+
+def _depth_entries(hand_pts, obj_pts, proj, hand_centre, obj_centre):
+    """The entries a `from_depth` frame carries in place of its clouds (leading batch dimension of 1)."""
+    depth, seg, _, _ = render_depth_frame(hand_pts, obj_pts, proj, int(proj["h"]), int(proj["w"]), splat=1)
+    f = lambda a: torch.from_numpy(np.asarray(a, dtype=np.float32))
+    return {"depth": torch.from_numpy(depth)[None], "seg": torch.from_numpy(seg)[None],
+            "intrinsics": {k: float(proj[k]) for k in ("fx", "fy", "cx", "cy")},
+            "hand_centre": f(hand_centre).reshape(1, 3), "obj_centre": f(obj_centre).reshape(1, 3)}
 
 
 # ---- object sequences (track: obj_opt) ---------------------------------------------------------------------------------
@@ -215,10 +263,14 @@ class SyntheticObjectSequences(Dataset):
     reference decodes -- the object's SDF volume, and obj_model_points (2048,3): surface samples for the chamfer metrics.
     obj_as_mesh: frame 0 carries `obj_mesh` ({'vertices', 'faces'}: capsule_mesh()) instead of `sdf_volume` and the tracker
     builds the volume (models/mesh_sdf.py); every other entry and every random draw is unchanged.  obj_mesh_path: frame 0
-    carries that `obj_mesh_path` (an OBJ / PLY file, object frame, metres) instead: the clouds are tracked against its volume."""
+    carries that `obj_mesh_path` (an OBJ / PLY file, object frame, metres) instead: the clouds are tracked against its volume.
+    from_depth: a frame carries, instead of obj_points, a 480 x 640 depth image and segmentation rendered from 16 n surface
+    samples of a generator of its own (render_depth_frame), the intrinsics and the crop centre; the tracker builds the cloud
+    (models/frame_frontend.py).  Every other entry and every other random draw is unchanged."""
 
     def __init__(self, cfg, num_sequences: int, frames: int, res: int = 201, stride: float = 0.002, obj_as_mesh: bool = False,
-                 obj_mesh_path=None):
+                 obj_mesh_path=None, from_depth: bool = False):
+        self.from_depth = bool(from_depth)
         self.cfg, self.ns, self.nf = cfg, num_sequences, frames
         self.res, self.stride = res, stride
         self._vol = None
@@ -250,6 +302,11 @@ class SyntheticObjectSequences(Dataset):
             fr = {"obj_points": f(pts).unsqueeze(0), "category": [self.cfg["obj_category"][0]], "file_name": [f"synthetic_obj_{s:03d}/{k:04d}"],
                   "gt_obj_pose": {"rotation": f(R).reshape(1, 1, 3, 3), "translation": f(t).reshape(1, 1, 3, 1)},
                   "projection": {"w": [640], "h": [480]}}
+            if self.from_depth:
+                del fr["obj_points"]
+                dense = capsule_surface(np.random.default_rng(90_000 + 1000 * s + k), 16 * n) @ R.T + t
+                proj = dict(fx=600.0, fy=600.0, cx=320.0, cy=240.0, w=640, h=480)
+                fr.update(_depth_entries(None, dense, proj, t, t))
             if k == 0:
                 ang = np.deg2rad(float(jit.get("r", 5))) * rng.standard_normal()
                 Rj = R @ _rot(rng.standard_normal(3), ang)
@@ -278,10 +335,15 @@ class SyntheticHandObjectSequences(Dataset):
     carries `mano_beta` (1, num_betas).
 
     obj_as_mesh / obj_mesh_path: as in SyntheticObjectSequences -- frame 0 carries `obj_mesh` / `obj_mesh_path` instead of
-    `sdf_volume`."""
+    `sdf_volume`.
+    from_depth: a frame carries, instead of hand_points and background_mask, a depth image and segmentation of the projection's
+    size rendered from 16 n samples of the hand and of the capsule (a generator of its own; render_depth_frame), the intrinsics
+    and the two crop centres (keypoint 9, the object's translation); the tracker builds the cloud and the mask
+    (models/frame_frontend.py).  Every other entry and every other random draw is unchanged."""
 
     def __init__(self, cfg, num_sequences: int, frames: int, res: int = 151, stride: float = 0.003, hand_beta=None,
-                 obj_as_mesh: bool = False, obj_mesh_path=None):
+                 obj_as_mesh: bool = False, obj_mesh_path=None, from_depth: bool = False):
+        self.from_depth = bool(from_depth)
         self.cfg, self.ns, self.nf, self.res, self.stride = cfg, num_sequences, frames, res, stride
         self.hand = cfg["hand_model"]
         self.hand_beta = hand_beta
@@ -341,6 +403,12 @@ class SyntheticHandObjectSequences(Dataset):
                   "gt_obj_pose": {"rotation": f(R_obj).reshape(1, 3, 3), "translation": f(t_obj).reshape(1, 3, 1)},
                   "projection": {kk: [vv] for kk, vv in proj.items()}, "background_mask": background,
                   "category": [self.cfg["obj_category"][0]], "file_name": [f"synthetic_handobj_{s:03d}/{k:04d}"]}
+            if self.from_depth:
+                del fr["hand_points"], fr["background_mask"]
+                drng = np.random.default_rng(90_000 + 1000 * s + k)
+                dense_hand = verts[0, drng.integers(0, verts.shape[1], 16 * n)].numpy() + drng.normal(0, 0.0015, (16 * n, 3))
+                dense_obj = capsule_surface(drng, 16 * n) @ R_obj.T + t_obj
+                fr.update(_depth_entries(dense_hand, dense_obj, proj, kp[0, 9].numpy(), t_obj))
             if k == 0:
                 fr["voxel_scale"] = self.stride
                 fr.update({"obj_mesh_path": self.obj_mesh_path} if self.obj_mesh_path is not None else

@@ -1432,3 +1432,85 @@ def hand_seq_metrics(pred_hf: torch.Tensor, init_hf: torch.Tensor, gt_kp: torch.
     if rc < 0:
         _native._check(rc, "hand_seq_metrics")
     return rows, seq, int(rc)
+
+
+# ---- hand and object clouds from depth frames (include/pn2_ext.h: pn2x_depth_frame_clouds) --------------------------------------
+class _DepthFrame(ctypes.Structure):
+    """pn2x_depth_frame (144 bytes)."""
+    _fields_ = ([(n, _vp) for n in ("depth", "seg", "intrinsics")] + [("centre", _vp * 2)] +
+                [(n, _vp) for n in ("clouds", "counts", "background", "work")] + [("depth_scale", _cd)] +
+                [(n, _ci) for n in ("b", "h", "w", "hs", "ws", "c", "cap", "depth_u16", "flip_yz", "reserved")] +
+                [("channel", _ci * 2), ("value", _ci * 2), ("radius", _cf * 2)])
+
+
+_lib.pn2x_depth_frame_supported.argtypes = [_ci] * 6
+_lib.pn2x_depth_frame_supported.restype = _ci
+_lib.pn2x_depth_frame_work_ints.argtypes = [_ci] * 3
+_lib.pn2x_depth_frame_work_ints.restype = _cl
+_lib.pn2x_depth_frame_clouds.argtypes = [ctypes.POINTER(_DepthFrame), _vp]
+_lib.pn2x_depth_frame_clouds.restype = _ci
+DEPTH_FRAME_MAX_CAP = 16384   # the register-resident FPS range
+DEPTH_FRAME_CALLS = 0         # calls of depth_frame_clouds so far (tests: a frame that has its clouds never gets here)
+
+
+def depth_frame_supported(h: int, w: int, hs: int, ws: int, c: int, cap: int) -> bool:
+    return bool(_lib.pn2x_depth_frame_supported(int(h), int(w), int(hs), int(ws), int(c), int(cap)))
+
+
+def depth_frame_workspace(b: int, h: int, w: int, cap: int, device):
+    """What a depth_frame_clouds call writes, to be reused: (tile counts, clouds (b,2,cap,3), counts (b,2), background (b,h,w)).
+    Nothing in it needs a value: every element is written on every call."""
+    ints = int(_lib.pn2x_depth_frame_work_ints(int(b), int(h), int(w)))
+    if ints < 0:
+        raise ValueError(f"depth_frame_workspace: b = {b}, h = {h}, w = {w}")
+    return (torch.empty(max(ints, 1), dtype=torch.int32, device=device), torch.empty((b, 2, cap, 3), dtype=torch.float32, device=device),
+            torch.empty((b, 2), dtype=torch.int32, device=device), torch.empty((b, h, w), dtype=torch.uint8, device=device))
+
+
+def depth_frame_clouds(depth: torch.Tensor, seg: torch.Tensor, intrinsics: torch.Tensor, hand, obj, cap: int, flip_yz: bool = False,
+                       depth_scale: float = None, work=None):
+    """Back-projection, split by segment and crop to a ball of B depth frames in two launches (pn2x_depth_frame_clouds).
+    depth (B,H,W) fp32 metres, or uint16 / int16 raw counts with depth_scale;  seg (B,Hs,Ws,C) uint8, C 1 or 3, H = f Hs and
+    W = f Ws;  intrinsics (B,4) fp32 on the device: fx, fy, cx, cy;  hand / obj = (channel, value, centre (B,3) fp32 on the device,
+    radius);  cap: slots per cloud, 1..16384;  work: depth_frame_workspace(B, H, W, cap) to write into, else allocated.
+    -> (clouds (B,2,cap,3), counts (B,2) int32, background (B,H,W) uint8), as pn2_ext.h describes them.  No host sync."""
+    global DEPTH_FRAME_CALLS
+    f32, u8 = torch.float32, torch.uint8
+    for name, t in (("depth", depth), ("seg", seg), ("intrinsics", intrinsics), ("hand centre", hand[2]), ("obj centre", obj[2])):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"depth_frame_clouds: {name} must be a torch.Tensor, got {type(t).__name__}")
+        if not t.is_cuda:
+            raise RuntimeError(f"depth_frame_clouds: {name} must be a GPU (HIP) tensor -- hotrack_amd has no CPU path (got device {t.device})")
+    if depth.dim() != 3 or seg.dim() != 4 or seg.shape[0] != depth.shape[0]:
+        raise ValueError(f"depth_frame_clouds: depth {tuple(depth.shape)} is not (B,H,W) or seg {tuple(seg.shape)} not (B,Hs,Ws,C)")
+    B, H, W = depth.shape
+    _, Hs, Ws, C = seg.shape
+    cap = int(cap)
+    raw = depth.dtype in (torch.uint16, torch.int16)   # (int16: the same 16 bits, for a torch without uint16 arithmetic)
+    if raw == (depth_scale is None) or (not raw and depth.dtype != f32):
+        raise TypeError(f"depth_frame_clouds: depth is fp32 metres, or uint16 counts with a depth_scale (got {depth.dtype}, "
+                        f"depth_scale = {depth_scale})")
+    if not depth_frame_supported(H, W, Hs, Ws, C, cap):
+        raise ValueError(f"depth_frame_clouds: depth {H} x {W}, seg {Hs} x {Ws} x {C}, cap {cap}: one integer factor between the "
+                         f"two images, C 1 or 3, H W < 2^29 and 1 <= cap <= {DEPTH_FRAME_MAX_CAP}")
+    if work is None:
+        work = depth_frame_workspace(B, H, W, cap, depth.device)
+    tiles, clouds, counts, background = work
+    r = _DepthFrame(b=B, h=H, w=W, hs=Hs, ws=Ws, c=C, cap=cap, depth_u16=int(raw), flip_yz=int(bool(flip_yz)),
+                    depth_scale=0.0 if depth_scale is None else float(depth_scale))
+    r.depth, r.seg = _native._ptr(depth, "depth", depth.dtype, B * H * W), _native._ptr(seg, "seg", u8, B * Hs * Ws * C)
+    r.intrinsics = _native._ptr(intrinsics, "intrinsics", f32, B * 4)
+    for k, (channel, value, centre, radius) in enumerate((hand, obj)):
+        r.channel[k], r.value[k], r.radius[k] = int(channel), int(value), float(radius)
+        r.centre[k] = _native._ptr(centre, "centre", f32, B * 3)
+    r.clouds, r.counts = _native._ptr(clouds, "clouds", f32, B * 2 * cap * 3), _native._ptr(counts, "counts", torch.int32, B * 2)
+    r.background = _native._ptr(background, "background", u8, B * H * W)
+    r.work = _native._ptr(tiles, "work", torch.int32, max(int(_lib.pn2x_depth_frame_work_ints(B, H, W)), 1))
+    for t in (seg, intrinsics, hand[2], obj[2], tiles, clouds, counts, background):
+        if t.device != depth.device:
+            raise ValueError(f"depth_frame_clouds: tensors on {depth.device} and {t.device}")
+    DEPTH_FRAME_CALLS += 1
+    with torch.cuda.device(depth.device):
+        _native._check(_native._call(_lib.pn2x_depth_frame_clouds, "depth_frame_kernels", None, ctypes.byref(r), _native._stream(depth)),
+                       "depth_frame_clouds")
+    return clouds, counts, background

@@ -962,6 +962,51 @@ int pn2x_hand_seq_metrics(int f, int s, int j, int mode, const float *pred_hf, c
                           const int *seq_off, const float *pose_r, const float *pose_t, const float *gt_r, const float *gt_t,
                           const float *theta, const float *theta_gt, float *rows, float *seq, void *stream);
 
+/*
+ * Hand and object clouds from depth frames (hotrack_amd/csrc/depth_frame.hip): what the reference's dataset readers do in numpy
+ * on the host in front of FPS (datasets/HO3D_dataset.py:66-112, :163-177, DexYCB_dataset.py:76-111) -- back-projection of the valid
+ * pixels, the split by segment, the crop to a ball -- for b frames of one size, in two launches over a (tiles, b) grid, a tile
+ * being 1024 consecutive pixels.  pn2x_depth_frame is HOST memory, read during the call; its pointers are DEVICE memory:
+ *   depth (b,h,w): fp32 metres, or with depth_u16 = 1 uint16 raw counts, z = (float)((double)raw * depth_scale);
+ *   seg (b,hs,ws,c) bytes, c 1 or 3, h = f hs and w = f ws with one integer f >= 1: pixel (v,u) reads seg[v / f, u / f];
+ *   intrinsics (b,4): fx, fy, cx, cy of each frame;
+ *   class k (0 the hand, 1 the object): seg byte channel[k] == value[k], centre[k] (b,3), radius[k].
+ * Per pixel, fp32, every operation rounded once (no fused multiply-add): valid if z > 1e-6f; x = ((float)u - cx) * z / fx,
+ * y = ((float)v - cy) * z / fy; flip_yz = 1 negates y and z; the pixel is of class k if it is valid, its segment byte matches and
+ * sqrtf((dx dx + dy dy) + dz dz) < radius[k] for d = point - centre[k].
+ * clouds (b,2,cap,3), counts (b,2) int32 = n, the pixels of the class.  With r the rank of a pixel among its class in row-major
+ * pixel order:  n <= cap: the point of rank r in slot r, slots n..cap-1 copies of the point of rank 0 (at distance 0 of FPS's first
+ * pick: a sample of a cloud with enough distinct points comes from the real ones);  n > cap: rank r is kept iff
+ * floor((r + 1) cap / n) > floor(r cap / n), in slot floor(r cap / n) (64-bit integers) -- exactly cap points, evenly spaced in
+ * rank;  n == 0: zeros.  background (b,h,w) bytes: 1 where all c segment bytes of the pixel are zero.
+ * work: pn2x_depth_frame_work_ints(b, h, w) = 2 b tiles int32, the per-tile counts the first launch leaves for the second.
+ * Every element of every output is written on every call by exactly one workgroup: nothing is pre-set, no atomics, no workgroup
+ * waits for another, two calls give the same bits.  No host sync or allocation (capturable).
+ * Errors, checked before any device work, PN2_EINVAL before PN2_ERANGE before PN2_ENULL: PN2_EINVAL for b < 0, a size < 1, h / hs
+ * and w / ws not one integer factor, c not 1 or 3, a class channel outside [0, c) or value outside [0, 255], a radius that is not
+ * > 0, cap < 1, depth_u16 or flip_yz not 0 / 1;  PN2_ERANGE for h w >= 2^29, cap > 16384 (the register-resident FPS range) or
+ * b > 65535;  PN2_ENULL for a NULL record or pointer.  b == 0 launches nothing (pointers are then not looked at).
+ * pn2x_depth_frame_supported: 1 when a frame geometry passes the checks above.
+ */
+struct pn2x_depth_frame {
+    const void *depth;
+    const unsigned char *seg;
+    const float *intrinsics;
+    const float *centre[2];
+    float *clouds;
+    int *counts;
+    unsigned char *background;
+    int *work;
+    double depth_scale;
+    int b, h, w, hs, ws, c, cap, depth_u16, flip_yz, reserved;
+    int channel[2], value[2];
+    float radius[2];
+}; /* 144 bytes */
+typedef struct pn2x_depth_frame pn2x_depth_frame;
+int pn2x_depth_frame_supported(int h, int w, int hs, int ws, int c, int cap);
+long pn2x_depth_frame_work_ints(int b, int h, int w);
+int pn2x_depth_frame_clouds(const pn2x_depth_frame *frames, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,23 @@ import torch.nn as nn
 from . import pointnet_utils
 
 
+class _FrontEndSlot:
+    """A tracker's depth front end, built on first use: a frame that carries `depth` and lacks the tracker's cloud is completed by
+    DepthFrontEnd.fill (models/frame_frontend.py); a frame that has the cloud is not touched."""
+
+    def __init__(self, cfg):
+        self.cfg = {"num_points": cfg.get("num_points", 1024), "device": cfg["device"], "depth_frontend": cfg.get("depth_frontend")}
+        self.front = None
+
+    def complete(self, data, cloud_key):
+        if cloud_key in data or "depth" not in data:
+            return
+        if self.front is None:
+            from .frame_frontend import DepthFrontEnd
+            self.front = DepthFrontEnd.from_cfg(self.cfg)
+        self.front.fill(data)
+
+
 class HandTrackModel(nn.Module):
     """hand_model (models/hand_model.HandModel, e.g. a MANO layer with the reference's call signature): enables the
     hand-pose particle optimisation of the reference's `use_optimization` branch (track_network.py:142-156, :203-211) on
@@ -38,6 +55,7 @@ class HandTrackModel(nn.Module):
             print("[Hand Tracking] Use IKNet: True")
         self.use_graph = True  # GPU + fused backend: one captured HIP graph per (N, keypoints) shape, replayed per frame
         self._graphs = {}
+        self._front_end = _FrontEndSlot(cfg)  # frames that carry a depth image instead of hand_points (models/frame_frontend.py)
         self.use_optimization = bool(cfg.get("use_optimization", False)) and hand_model is not None
         self.use_pred_obj_pose = bool(cfg.get("use_pred_obj_pose", False))
         self.sym = cfg.get("obj_sym", -1)  # rot_diff_rad's symmetry mode for the obj_pred_* metrics (compute_loss)
@@ -194,6 +212,7 @@ class HandTrackModel(nn.Module):
         prev_theta = None
         for i, data in enumerate(input):
             data["pred_palm_template"] = palm_template
+            self._front_end.complete(data, "hand_points")
             points = data["hand_points"].to(self.device, non_blocking=True).float()
             centre = points.mean(dim=-2, keepdim=True)
             if last_kp is not None:
@@ -286,6 +305,7 @@ class HandTrackModel(nn.Module):
                 if self.opt_shape is not None:
                     self.opt_shape.old_pred_length = st.history
                 data["pred_palm_template"] = st.palm
+                self._front_end.complete(data, "hand_points")
                 points = data["hand_points"].to(self.device, non_blocking=True).float()
                 centres[k] = centre = points.mean(dim=-2, keepdim=True)
                 if st.last_kp is not None:
@@ -494,6 +514,7 @@ class ObjTrackModel_Optimization(nn.Module):
         self.num_parts = cfg.get("num_parts", 1)
         self.sym = cfg.get("obj_sym", -1)
         self.optimizer = gf_optimize_obj(cfg)
+        self._front_end = _FrontEndSlot(cfg)  # frames that carry a depth image instead of obj_points (models/frame_frontend.py)
 
     def forward(self, input, flag_dict):
         flag_dict["track_flag"] = True
@@ -515,6 +536,7 @@ class ObjTrackModel_Optimization(nn.Module):
                 jp["rotation"] = jp["rotation"].float().reshape(1, 3, 3).to(self.device)
                 jp["prev_translation"], jp["prev_rotation"] = jp["translation"], jp["rotation"]
                 last = {"translation": jp["translation"], "rotation": jp["rotation"]}
+            self._front_end.complete(data, "obj_points")
             ret = self.optimizer.optimize(data["obj_points"], data["jittered_obj_pose"], data["category"][0],
                                           data["file_name"][0], data.get("projection"))
             last["prev_translation"], last["prev_rotation"] = last["translation"], last["rotation"]  # last frame's pose
@@ -576,6 +598,7 @@ class ObjTrackModel_Optimization(nn.Module):
             live = [k for k in range(S) if t < len(inputs[k])]
             for k in live:
                 data = inputs[k][t]
+                self._front_end.complete(data, "obj_points")
                 if last[k] is not None:
                     data["jittered_obj_pose"] = last[k]
                 else:

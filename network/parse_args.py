@@ -49,6 +49,10 @@ def add_args(parser):
                              "PLY, object frame, metres; models/mesh_sdf.py) instead of the analytic capsule volume")
     parser.add_argument("--obj_as_mesh", action="store_const", const=True, default=None,
                         help="the synthetic sequences carry the capsule as a triangle mesh and the tracker builds the volume")
+    parser.add_argument("--from_depth", action="store_const", const=True, default=None,
+                        help="the synthetic hand-object and object sequences hand over rendered depth frames (depth, seg, intrinsics, "
+                             "crop centres) instead of clouds, and the trackers build hand_points / obj_points / background_mask on "
+                             "the GPU (models/frame_frontend.py, hotrack_amd/csrc/depth_frame.hip)")
     parser.add_argument("--seq_batch", type=int, default=1,
                         help="test.py, track=obj_opt: track this many sequences in lockstep on one batched optimiser call per frame "
                              "step (same poses, bit for bit, as one sequence at a time); 1 = one sequence at a time")
