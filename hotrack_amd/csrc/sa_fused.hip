@@ -921,106 +921,119 @@ static int sa_compute_units() {
     return (g_sa_cus > 0 && g_sa_cus < all) ? g_sa_cus : all;
 }
 
-template <int C1, int C2, int C3, int WC, int RTC, int MINW, int NB1, int K, int MODE>
-static int launch_sa_km(int b, SaArgs a, hipStream_t st) {
-    constexpr int WP = 4 / WC, TM = WP * 64;
-    const int sk = a.S * a.K;
-    a.tiles_per_cloud = (sk + TM - 1) / TM;
-    const long num_tiles_l = (long)b * a.tiles_per_cloud;
-    if (num_tiles_l > 2147483647L) return PN2_ERANGE;
-    a.num_tiles = (int)num_tiles_l;
-    a.B = b;
+// ---- launch shape and the three grid rules (plain integers: nothing here needs a device) ------------------------------------
+constexpr int sa_tile_rows(int WC) { return (4 / WC) * 64; }  // TM of sa_body: positions per tile
+
+// Fixed K: tiles per cloud, tiles of the launch and lgK of a problem whose B, S and K are set, on tiles of `tm` positions.
+static int sa_set_tiles(SaArgs &a, int tm) {
+    a.tiles_per_cloud = (a.S * a.K + tm - 1) / tm;
+    const long num_tiles = (long)a.B * a.tiles_per_cloud;
+    if (num_tiles > 2147483647L) return PN2_ERANGE;
+    a.num_tiles = (int)num_tiles;
     a.lgK = 0;
     while ((1 << a.lgK) < a.K) ++a.lgK;
-    const size_t lds = (size_t)TM * (NB1 * (C1 + SA_PAD) + C2 + SA_PAD) * sizeof(float);
-    auto kfn = sa_mlp_max_kernel<C1, C2, C3, WC, RTC, MINW, NB1, K, MODE>;
+    return PN2_OK;
+}
+
+// Balanced persistent grid: every workgroup runs the same number of tiles (ceil(tiles / rounds)), so the launch
+// takes `rounds` tile-times either way but leaves the CUs a ragged last round would idle to concurrent streams
+// (1344 tiles: 224 workgroups x 6 instead of 256 of which 64 run 6 and 192 run 5).
+static int sa_grid_rounds(int tiles, int max_wg) {
+    const int rounds = (tiles + max_wg - 1) / max_wg;
+    return (tiles + rounds - 1) / rounds;
+}
+
+// Two shares of one grid: same number of rounds for both (a tile costs the same in either: 64 positions through the same layers)
+static void sa_grid_pair(int tiles0, int tiles1, int max_wg, int &n0, int &n1) {
+    const int total = tiles0 + tiles1;
+    for (int rounds = (total + max_wg - 1) / max_wg;; ++rounds) {
+        n0 = (tiles0 + rounds - 1) / rounds;
+        n1 = (tiles1 + rounds - 1) / rounds;
+        if (n0 + n1 <= max_wg || rounds > total) break;
+    }
+}
+
+// The class walk: the tile count lives in device memory (the class sizes; nothing of it reaches the host, so the launch can be
+// captured and replayed on other inputs), hence no "equal rounds" sizing here: the grid is every workgroup the compute units in
+// use can hold -- capped by the tile count of all-full lists -- and the kernel cuts the tile sequence into that many equal
+// contiguous shares.
+static int sa_grid_classes(long centroids, int tm, long max_wg) {
+    const long most = (centroids * 32 + tm - 1) / tm + 2;  // all lists full; + 2: the two class boundaries' short tiles
+    return (int)(most < max_wg ? most : max_wg);
+}
+
+// LDS bytes of a workgroup of kernel `kfn` -> lds, and the most workgroups its persistent grid may have (the weights are loaded
+// into registers once per workgroup).  Raises the kernel's dynamic-LDS limit on first use.
+template <auto kfn, int C1, int C2, int WC, int MINW, int NB1>
+static int sa_launch_shape(size_t &lds) {
+    lds = (size_t)sa_tile_rows(WC) * (NB1 * (C1 + SA_PAD) + C2 + SA_PAD) * sizeof(float);
     static PerDeviceOnce raised;  // once per instantiation and device; never during a later stream capture
     if (lds > 64 * 1024 && raised.first_use())
         (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    // persistent workgroups: weights are loaded into registers once per workgroup
     const int wg_per_cu = (int)((160 * 1024) / lds) < MINW / 2 ? (int)((160 * 1024) / lds) : MINW / 2;
-    const int max_wg = sa_compute_units() * (wg_per_cu < 1 ? 1 : wg_per_cu);
-    // Balanced persistent grid: every workgroup runs the same number of tiles (ceil(tiles / rounds)), so the launch
-    // takes `rounds` tile-times either way but leaves the CUs a ragged last round would idle to concurrent streams
-    // (1344 tiles: 224 workgroups x 6 instead of 256 of which 64 run 6 and 192 run 5).
-    const int rounds = (a.num_tiles + max_wg - 1) / max_wg;
-    const int grid = (a.num_tiles + rounds - 1) / rounds;
+    return sa_compute_units() * (wg_per_cu < 1 ? 1 : wg_per_cu);
+}
+
+template <int C1, int C2, int C3, int WC, int RTC, int MINW, int NB1, int K, int MODE>
+static int launch_sa_km(SaArgs a, hipStream_t st) {
+    if (sa_set_tiles(a, sa_tile_rows(WC)) != PN2_OK) return PN2_ERANGE;
+    constexpr auto kfn = sa_mlp_max_kernel<C1, C2, C3, WC, RTC, MINW, NB1, K, MODE>;
+    size_t lds;
+    const int max_wg = sa_launch_shape<kfn, C1, C2, WC, MINW, NB1>(lds);
+    const int grid = sa_grid_rounds(a.num_tiles, max_wg);
     hipLaunchKernelGGL(kfn, dim3(grid), dim3(512), lds, st, a, grid);
     return check_launch();
 }
 
-// The class walk's launch: the tile count lives in device memory (the class sizes; nothing of it reaches the host, so the
-// launch can be captured and replayed on other inputs), hence no "equal rounds" sizing here: the grid is every workgroup the
-// compute units in use can hold -- capped by the tile count of all-full lists -- and the kernel cuts the tile sequence into
-// that many equal contiguous shares.
 template <int C1, int C2, int C3, int WC, int RTC, int MINW, int NB1, int MODE>
-static int launch_sa_classes(int b, SaArgs a, hipStream_t st) {
-    constexpr int WP = 4 / WC, TM = WP * 64;
-    a.B = b; a.K = 32; a.lgK = 5; a.tiles_per_cloud = 1; a.num_tiles = 0;
-    const size_t lds = (size_t)TM * (NB1 * (C1 + SA_PAD) + C2 + SA_PAD) * sizeof(float);
-    auto kfn = sa_mlp_max_classes_kernel<C1, C2, C3, WC, RTC, MINW, NB1, MODE>;
-    static PerDeviceOnce raised;
-    if (lds > 64 * 1024 && raised.first_use())
-        (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    const int wg_per_cu = (int)((160 * 1024) / lds) < MINW / 2 ? (int)((160 * 1024) / lds) : MINW / 2;
-    const long max_wg = (long)sa_compute_units() * (wg_per_cu < 1 ? 1 : wg_per_cu);
-    const long most = ((long)b * a.S * 32 + TM - 1) / TM + 2;  // all lists full; + 2: the two class boundaries' short tiles
-    const int grid = (int)(most < max_wg ? most : max_wg);
+static int launch_sa_classes(SaArgs a, hipStream_t st) {
+    a.lgK = 5; a.tiles_per_cloud = 1;  // (K = 32; num_tiles stays 0: the tiles are counted on the device)
+    constexpr auto kfn = sa_mlp_max_classes_kernel<C1, C2, C3, WC, RTC, MINW, NB1, MODE>;
+    size_t lds;
+    const int max_wg = sa_launch_shape<kfn, C1, C2, WC, MINW, NB1>(lds);
+    const int grid = sa_grid_classes((long)a.B * a.S, sa_tile_rows(WC), max_wg);
     hipLaunchKernelGGL(kfn, dim3(grid), dim3(512), lds, st, a, grid);
     return check_launch();
-}
-
-template <int C1, int C2, int C3, int WC, int RTC, int MINW, int NB1>
-static void sa_tiles(int b, SaArgs &a) {
-    constexpr int WP = 4 / WC, TM = WP * 64;
-    a.tiles_per_cloud = (a.S * a.K + TM - 1) / TM;
-    a.num_tiles = b * a.tiles_per_cloud;
-    a.B = b;
-    a.lgK = 0;
-    while ((1 << a.lgK) < a.K) ++a.lgK;
 }
 
 template <int C1, int C2, int C3, int WC, int RTC, int MINW, int NB1, int K0, int K1, int MODE>
-static int launch_sa_pair(int b, SaArgs a0, SaArgs a1, hipStream_t st) {
-    constexpr int WP = 4 / WC, TM = WP * 64;
-    if ((long)b * ((a0.S * a0.K + TM - 1) / TM) + (long)b * ((a1.S * a1.K + TM - 1) / TM) > 2147483647L) return PN2_ERANGE;
-    sa_tiles<C1, C2, C3, WC, RTC, MINW, NB1>(b, a0);
-    sa_tiles<C1, C2, C3, WC, RTC, MINW, NB1>(b, a1);
-    const size_t lds = (size_t)TM * (NB1 * (C1 + SA_PAD) + C2 + SA_PAD) * sizeof(float);
-    auto kfn = sa_mlp_max_pair_kernel<C1, C2, C3, WC, RTC, MINW, NB1, K0, K1, MODE>;
-    static PerDeviceOnce raised;
-    if (lds > 64 * 1024 && raised.first_use())
-        (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    const int wg_per_cu = (int)((160 * 1024) / lds) < MINW / 2 ? (int)((160 * 1024) / lds) : MINW / 2;
-    const int max_wg = sa_compute_units() * (wg_per_cu < 1 ? 1 : wg_per_cu);
-    // same number of rounds for both shares (a tile costs the same in either: 64 positions through the same layers)
-    const int total = a0.num_tiles + a1.num_tiles;
-    int rounds = (total + max_wg - 1) / max_wg;
+static int launch_sa_pair(SaArgs a0, SaArgs a1, hipStream_t st) {
+    if (sa_set_tiles(a0, sa_tile_rows(WC)) != PN2_OK || sa_set_tiles(a1, sa_tile_rows(WC)) != PN2_OK ||
+        (long)a0.num_tiles + a1.num_tiles > 2147483647L)
+        return PN2_ERANGE;
+    constexpr auto kfn = sa_mlp_max_pair_kernel<C1, C2, C3, WC, RTC, MINW, NB1, K0, K1, MODE>;
+    size_t lds;
+    const int max_wg = sa_launch_shape<kfn, C1, C2, WC, MINW, NB1>(lds);
     int n0, n1;
-    for (;; ++rounds) {
-        n0 = (a0.num_tiles + rounds - 1) / rounds;
-        n1 = (a1.num_tiles + rounds - 1) / rounds;
-        if (n0 + n1 <= max_wg || rounds > total) break;
-    }
+    sa_grid_pair(a0.num_tiles, a1.num_tiles, max_wg, n0, n1);
     hipLaunchKernelGGL(kfn, dim3(n0 + n1), dim3(512), lds, st, a0, a1, n0, n1);
     return check_launch();
 }
 
-template <int C1, int C2, int C3, int WC, int RTC, int MINW, int NB1, int K>
-static int launch_sa_k(int b, const SaArgs &a, hipStream_t st) {
+// MODE of sa_body for a problem's layer-1 operands: 0 = xyz only, 1 = a1f + xyz, 2 = a1f + xyz + cadd, 3 = any other set (the
+// instance that tests its operands at run time).  Every entry picks its instantiation from this one answer.
+static int sa_mode(const SaArgs &a) {
     const bool fa = a.a1f != nullptr, fx = a.xyz != nullptr, fc = a.cadd != nullptr;
-    if (!fa && fx && !fc) return launch_sa_km<C1, C2, C3, WC, RTC, MINW, NB1, K, 0>(b, a, st);
-    if (fa && fx && !fc) return launch_sa_km<C1, C2, C3, WC, RTC, MINW, NB1, K, 1>(b, a, st);
-    if (fa && fx && fc) return launch_sa_km<C1, C2, C3, WC, RTC, MINW, NB1, K, 2>(b, a, st);
-    return launch_sa_km<C1, C2, C3, WC, RTC, MINW, NB1, K, 3>(b, a, st);
+    if (!fx || (fc && !fa)) return 3;
+    return fa ? (fc ? 2 : 1) : 0;
+}
+
+template <int C1, int C2, int C3, int WC, int RTC, int MINW, int NB1, int K>
+static int launch_sa_k(const SaArgs &a, hipStream_t st) {
+    switch (sa_mode(a)) {
+        case 0: return launch_sa_km<C1, C2, C3, WC, RTC, MINW, NB1, K, 0>(a, st);
+        case 1: return launch_sa_km<C1, C2, C3, WC, RTC, MINW, NB1, K, 1>(a, st);
+        case 2: return launch_sa_km<C1, C2, C3, WC, RTC, MINW, NB1, K, 2>(a, st);
+    }
+    return launch_sa_km<C1, C2, C3, WC, RTC, MINW, NB1, K, 3>(a, st);
 }
 
 template <int C1, int C2, int C3, int WC, int RTC, int MINW, int NB1>
-static int launch_sa(int b, const SaArgs &a, hipStream_t st) {
+static int launch_sa(const SaArgs &a, hipStream_t st) {
     switch (a.K) {
-        case 16: return launch_sa_k<C1, C2, C3, WC, RTC, MINW, NB1, 16>(b, a, st);
-        case 32: return launch_sa_k<C1, C2, C3, WC, RTC, MINW, NB1, 32>(b, a, st);
-        case 64: return launch_sa_k<C1, C2, C3, WC, RTC, MINW, NB1, 64>(b, a, st);
+        case 16: return launch_sa_k<C1, C2, C3, WC, RTC, MINW, NB1, 16>(a, st);
+        case 32: return launch_sa_k<C1, C2, C3, WC, RTC, MINW, NB1, 32>(a, st);
+        case 64: return launch_sa_k<C1, C2, C3, WC, RTC, MINW, NB1, 64>(a, st);
     }
     return PN2_ERANGE;
 }
@@ -1040,6 +1053,32 @@ static bool sa_ranges_ok(long b, long n, long s, long k, long a1f_ld, long cadd_
     if (out_s < 0 || out_c < 0 || 4 * ((s - 1) * out_s + (c3 - 1) * out_c + 1) >= lim) return false;  // one store descriptor per cloud
     return n < (1L << 24) && s < (1L << 24) && 4 * a1f_ld < (1L << 24) && 4 * cadd_ld < (1L << 24) &&
            4 * b * n * (a1f_ld > 3 ? a1f_ld : 3) <= lim && 4 * s * (cadd_ld > 3 ? cadd_ld : 3) <= lim && 4 * s * k <= lim;
+}
+
+// Every operand check of one set-abstraction problem of b > 0 clouds, in the order pn2_ext.h states above pn2x_sa_mlp_max, then
+// the kernel's arguments (what a launch derives -- tiles, lgK -- stays zero).  walk: the class walk, with its list and sizes.
+static int sa_check_fill(int b, const pn2x_sa_problem &p, int c1, int c3, SaArgs &a, bool walk = false, const int *cls_list = nullptr,
+                         const int *cls_sizes = nullptr) {
+    if (p.n < 1 || p.s < 1 || p.k < 1) return PN2_EINVAL;
+    if (!p.idx || !p.w2 || !p.b2 || !p.w3 || !p.b3 || !p.out || (walk && (!cls_list || !cls_sizes))) return PN2_ENULL;
+    if (!p.a1f && !p.xyz) return PN2_ENULL;  // layer 1 needs at least one per-point term
+    if (p.xyz && (!p.cxyz || !p.wx)) return PN2_ENULL;
+    if ((p.a1f && (p.a1f_ld < c1 || p.a1f_ld % 4)) || (p.cadd && (p.cadd_ld < c1 || p.cadd_ld % 4))) return PN2_EINVAL;
+    if (((uintptr_t)p.a1f | (uintptr_t)p.cadd | (uintptr_t)p.b1 | (uintptr_t)p.w2 | (uintptr_t)p.w3 | (uintptr_t)cls_list) % 16 != 0) return PN2_EINVAL;
+    if (!sa_ranges_ok(b, p.n, p.s, p.k, p.a1f ? p.a1f_ld : 0, p.cadd ? p.cadd_ld : 0, c3, p.out_s, p.out_c)) return PN2_ERANGE;
+    if (walk) {  // whole-tensor descriptors and 24-bit row numbers b*n + j, b*s + s' (sa_body, class walk)
+        const long lim = 0xffffffffL, s = p.s;
+        if (p.out_b < 0 || (long)b * p.n >= (1L << 24) || b * s >= (1L << 24) || 128L * b * s > lim ||
+            4L * b * s * (p.cadd && p.cadd_ld > 3 ? p.cadd_ld : 3) > lim || 4 * ((b - 1) * p.out_b + (s - 1) * p.out_s + (c3 - 1L) * p.out_c + 1) >= lim)
+            return PN2_ERANGE;
+    }
+    a = SaArgs{};
+    a.B = b; a.N = p.n; a.S = p.s; a.K = p.k;
+    a.a1f = p.a1f; a.xyz = p.xyz; a.cxyz = p.cxyz; a.wx = p.wx; a.b1 = p.b1; a.cadd = p.cadd; a.a1f_ld = p.a1f_ld; a.cadd_ld = p.cadd_ld;
+    a.idx = p.idx; a.w2 = p.w2; a.b2 = p.b2; a.w3 = p.w3; a.b3 = p.b3;
+    a.out = p.out; a.out_b = p.out_b; a.out_s = p.out_s; a.out_c = p.out_c;
+    a.cls_list = cls_list; a.cls_sizes = cls_sizes;
+    return PN2_OK;
 }
 
 // ---- class lists of the class walk ------------------------------------------------------------------------------------------
@@ -1187,31 +1226,18 @@ extern "C" int pn2x_sa_mlp_max_classes(int b, int n, int s, int k, int c1, int c
     using namespace pn2;
     if (b < 0 || n < 1 || s < 0 || k < 1) return PN2_EINVAL;
     if (b == 0 || s == 0) return PN2_OK;
-    if (!idx || !cls_list || !cls_sizes || !w2 || !b2 || !w3 || !b3 || !out) return PN2_ENULL;
-    if (!a1f && !xyz) return PN2_ENULL;
-    if (xyz && (!cxyz || !wx)) return PN2_ENULL;
-    if ((a1f && (a1f_ld < c1 || a1f_ld % 4)) || (cadd && (cadd_ld < c1 || cadd_ld % 4))) return PN2_EINVAL;
-    if (!pn2x_sa_mlp_max_classes_supported(k, c1, c2, c3)) return PN2_ERANGE;
-    if (!sa_ranges_ok(b, n, s, k, a1f ? a1f_ld : 0, cadd ? cadd_ld : 0, c3, out_s, out_c)) return PN2_ERANGE;
-    // whole-tensor descriptors and 24-bit row numbers b*n + j, b*s + s' (sa_body, class walk)
-    const long lim = 0xffffffffL;
-    if (out_b < 0 || (long)b * n >= (1L << 24) || (long)b * s >= (1L << 24) || 128L * b * s > lim ||
-        4L * b * s * (cadd && cadd_ld > 3 ? cadd_ld : 3) > lim || 4 * ((b - 1) * out_b + (s - 1L) * out_s + (c3 - 1L) * out_c + 1) >= lim)
-        return PN2_ERANGE;
-    if (((uintptr_t)a1f | (uintptr_t)cadd | (uintptr_t)b1 | (uintptr_t)w2 | (uintptr_t)w3 | (uintptr_t)cls_list) % 16 != 0) return PN2_EINVAL;
+    const pn2x_sa_problem p = {n, s, k, a1f, a1f_ld, xyz, cxyz, wx, b1, cadd, cadd_ld, idx, w2, b2, w3, b3, out, out_b, out_s, out_c};
     SaArgs a;
-    a.B = b; a.N = n; a.S = s; a.K = k; a.lgK = 5;
-    a.a1f = a1f; a.a1f_ld = a1f_ld; a.cadd_ld = cadd_ld; a.xyz = xyz; a.cxyz = cxyz; a.wx = wx; a.b1 = b1; a.cadd = cadd; a.idx = idx;
-    a.w2 = w2; a.b2 = b2; a.w3 = w3; a.b3 = b3; a.w2e = nullptr; a.out = out; a.out_b = out_b; a.out_s = out_s; a.out_c = out_c;
-    a.num_tiles = 0; a.tiles_per_cloud = 1; a.trace = nullptr; a.cls_list = cls_list; a.cls_sizes = cls_sizes;
+    if (const int rc = sa_check_fill(b, p, c1, c3, a, true, cls_list, cls_sizes); rc != PN2_OK) return rc;
+    if (!pn2x_sa_mlp_max_classes_supported(k, c1, c2, c3)) return PN2_ERANGE;
     hipStream_t st = (hipStream_t)stream;
-    const bool fa = a1f != nullptr, fx = xyz != nullptr, fc = cadd != nullptr;
+    const int mode = sa_mode(a);
     if (c1 == 32) {  // sa1: coordinates only; any other operand set through the instance that tests its operands at run time
-        if (!fa && fx && !fc) return launch_sa_classes<32, 32, 64, 2, 4, 4, SA_NB1, 0>(b, a, st);
-        return launch_sa_classes<32, 32, 64, 2, 4, 4, SA_NB1, 3>(b, a, st);
+        if (mode == 0) return launch_sa_classes<32, 32, 64, 2, 4, 4, SA_NB1, 0>(a, st);
+        return launch_sa_classes<32, 32, 64, 2, 4, 4, SA_NB1, 3>(a, st);
     }
-    if (fa && fx && !fc) return launch_sa_classes<64, 64, 128, 4, 2, 4, SA_NB1, 1>(b, a, st);  // sa2: features + coordinates
-    return launch_sa_classes<64, 64, 128, 4, 2, 4, SA_NB1, 3>(b, a, st);
+    if (mode == 1) return launch_sa_classes<64, 64, 128, 4, 2, 4, SA_NB1, 1>(a, st);  // sa2: features + coordinates
+    return launch_sa_classes<64, 64, 128, 4, 2, 4, SA_NB1, 3>(a, st);
 }
 
 extern "C" int pn2x_sa_set_compute_units(int n) {
@@ -1230,41 +1256,16 @@ extern "C" int pn2x_sa_mlp_max(int b, int n, int s, int k, int c1, int c2, int c
     using namespace pn2;
     if (b < 0 || n < 1 || s < 0 || k < 1) return PN2_EINVAL;
     if (b == 0 || s == 0) return PN2_OK;
-    if (!idx || !w2 || !b2 || !w3 || !b3 || !out) return PN2_ENULL;
-    if (!a1f && !xyz) return PN2_ENULL;          // layer 1 needs at least one per-point term
-    if (xyz && (!cxyz || !wx)) return PN2_ENULL;
-    if ((a1f && (a1f_ld < c1 || a1f_ld % 4)) || (cadd && (cadd_ld < c1 || cadd_ld % 4))) return PN2_EINVAL;
-    if (!(k == 16 || k == 32 || k == 64)) return PN2_ERANGE;
-    if (!sa_ranges_ok(b, n, s, k, a1f ? a1f_ld : 0, cadd ? cadd_ld : 0, c3, out_s, out_c)) return PN2_ERANGE;
-    if (((uintptr_t)a1f | (uintptr_t)cadd | (uintptr_t)b1 | (uintptr_t)w2 | (uintptr_t)w3) % 16 != 0) return PN2_EINVAL;
+    const pn2x_sa_problem p = {n, s, k, a1f, a1f_ld, xyz, cxyz, wx, b1, cadd, cadd_ld, idx, w2, b2, w3, b3, out, out_b, out_s, out_c};
     SaArgs a;
-    a.B = b; a.N = n; a.S = s; a.K = k; a.lgK = 0;
-    a.a1f = a1f; a.a1f_ld = a1f_ld; a.cadd_ld = cadd_ld; a.xyz = xyz; a.cxyz = cxyz; a.wx = wx; a.b1 = b1; a.cadd = cadd; a.idx = idx;
-    a.w2 = w2; a.b2 = b2; a.w3 = w3; a.b3 = b3; a.w2e = nullptr; a.out = out; a.out_b = out_b; a.out_s = out_s; a.out_c = out_c;
-    a.num_tiles = 0; a.tiles_per_cloud = 0; a.trace = g_sa_trace; a.cls_list = nullptr; a.cls_sizes = nullptr;
-    hipStream_t st = (hipStream_t)stream;
-    if (c1 == 32 && c2 == 32 && c3 == 64) return launch_sa<32, 32, 64, 2, 4, 4, SA_NB1>(b, a, st);
-    if (c1 == 64 && c2 == 64 && c3 == 128) return launch_sa<64, 64, 128, 4, 2, 4, SA_NB1>(b, a, st);
-    if (c1 == 128 && c2 == 128 && c3 == 192) return launch_sa<128, 128, 192, 4, SA_RTC128, 2, SA_NB1>(b, a, st);
+    if (const int rc = sa_check_fill(b, p, c1, c3, a); rc != PN2_OK) return rc;
+    a.trace = g_sa_trace;
+    hipStream_t st = (hipStream_t)stream;  // (a k or widths without an instantiation: PN2_ERANGE, as pn2x_sa_mlp_max_supported says)
+    if (c1 == 32 && c2 == 32 && c3 == 64) return launch_sa<32, 32, 64, 2, 4, 4, SA_NB1>(a, st);
+    if (c1 == 64 && c2 == 64 && c3 == 128) return launch_sa<64, 64, 128, 4, 2, 4, SA_NB1>(a, st);
+    if (c1 == 128 && c2 == 128 && c3 == 192) return launch_sa<128, 128, 192, 4, SA_RTC128, 2, SA_NB1>(a, st);
     return PN2_ERANGE;
 }
-
-namespace pn2 {
-static int fill_sa_args(int b, const pn2x_sa_problem &p, int c1, int c3, SaArgs &a) {
-    if (p.n < 1 || p.s < 1 || p.k < 1) return PN2_EINVAL;
-    if (!p.idx || !p.w2 || !p.b2 || !p.w3 || !p.b3 || !p.out) return PN2_ENULL;
-    if (!p.a1f && !p.xyz) return PN2_ENULL;
-    if (p.xyz && (!p.cxyz || !p.wx)) return PN2_ENULL;
-    if ((p.a1f && (p.a1f_ld < c1 || p.a1f_ld % 4)) || (p.cadd && (p.cadd_ld < c1 || p.cadd_ld % 4))) return PN2_EINVAL;
-    if (((uintptr_t)p.a1f | (uintptr_t)p.cadd | (uintptr_t)p.b1 | (uintptr_t)p.w2 | (uintptr_t)p.w3) % 16 != 0) return PN2_EINVAL;
-    if (!sa_ranges_ok(b, p.n, p.s, p.k, p.a1f ? p.a1f_ld : 0, p.cadd ? p.cadd_ld : 0, c3, p.out_s, p.out_c)) return PN2_ERANGE;
-    a.B = 0; a.N = p.n; a.S = p.s; a.K = p.k; a.lgK = 0;
-    a.a1f = p.a1f; a.a1f_ld = p.a1f_ld; a.cadd_ld = p.cadd_ld; a.xyz = p.xyz; a.cxyz = p.cxyz; a.wx = p.wx; a.b1 = p.b1;
-    a.cadd = p.cadd; a.idx = p.idx; a.w2 = p.w2; a.b2 = p.b2; a.w3 = p.w3; a.b3 = p.b3; a.w2e = nullptr; a.out = p.out; a.out_b = p.out_b;
-    a.out_s = p.out_s; a.out_c = p.out_c; a.num_tiles = 0; a.tiles_per_cloud = 0; a.trace = nullptr; a.cls_list = nullptr; a.cls_sizes = nullptr;
-    return PN2_OK;
-}
-}  // namespace pn2
 
 extern "C" int pn2x_sa_mlp_max_pair_supported(int k0, int k1, int c1, int c2, int c3) {
     return (c1 == 128 && c2 == 128 && c3 == 192 && ((k0 == 16 && k1 == 64) || (k0 == 64 && k1 == 16))) ? 1 : 0;
@@ -1278,15 +1279,13 @@ extern "C" int pn2x_sa_mlp_max_pair(int b, int c1, int c2, int c3, const pn2x_sa
     if (!pn2x_sa_mlp_max_pair_supported(p0->k, p1->k, c1, c2, c3)) return PN2_ERANGE;
     if (p0->k > p1->k) { const pn2x_sa_problem *t = p0; p0 = p1; p1 = t; }
     SaArgs a0, a1;
-    int rc = fill_sa_args(b, *p0, c1, c3, a0);
-    if (rc != PN2_OK) return rc;
-    rc = fill_sa_args(b, *p1, c1, c3, a1);
-    if (rc != PN2_OK) return rc;
-    const bool fa = a0.a1f && a1.a1f, fx = a0.xyz && a1.xyz, fc0 = a0.cadd != nullptr, fc1 = a1.cadd != nullptr;
-    if (!fa || !fx || fc0 != fc1 || (a0.a1f == nullptr) != (a1.a1f == nullptr)) return PN2_ERANGE;  // both scales: a1f + xyz (+ cadd)
+    if (const int rc = sa_check_fill(b, *p0, c1, c3, a0); rc != PN2_OK) return rc;
+    if (const int rc = sa_check_fill(b, *p1, c1, c3, a1); rc != PN2_OK) return rc;
+    const int mode = sa_mode(a0);
+    if (mode != sa_mode(a1) || (mode != 1 && mode != 2)) return PN2_ERANGE;  // both scales: a1f + xyz (+ cadd)
     hipStream_t st = (hipStream_t)stream;
-    if (fc0) return launch_sa_pair<128, 128, 192, 4, SA_RTC128, 2, SA_NB1, 16, 64, 2>(b, a0, a1, st);
-    return launch_sa_pair<128, 128, 192, 4, SA_RTC128, 2, SA_NB1, 16, 64, 1>(b, a0, a1, st);
+    if (mode == 2) return launch_sa_pair<128, 128, 192, 4, SA_RTC128, 2, SA_NB1, 16, 64, 2>(a0, a1, st);
+    return launch_sa_pair<128, 128, 192, 4, SA_RTC128, 2, SA_NB1, 16, 64, 1>(a0, a1, st);
 }
 
 // ---- two-layer MLP over plain rows: out[r, :] = relu(W3 relu(W2 x[r, :] + b2) + b3) -----------------------------------------
@@ -1303,13 +1302,11 @@ extern "C" int pn2x_mlp2_rows(long rows, int c1, int c2, int c3, const float *x,
     if (!pn2x_mlp2_rows_supported(c1, c2, c3)) return PN2_ERANGE;
     if (((uintptr_t)x | (uintptr_t)w2 | (uintptr_t)w3 | (uintptr_t)out) % 16 != 0) return PN2_EINVAL;
     if (rows >= (1L << 24) - 64 || 4L * ldx >= (1L << 24) || 4L * rows * ldx > 0xffffffffL || 4L * rows * ldo > 0xffffffffL) return PN2_ERANGE;
-    SaArgs a;
-    a.B = 1; a.N = (int)rows; a.K = 16; a.S = (int)((rows + 15) / 16); a.lgK = 4;
-    a.a1f = x; a.a1f_ld = ldx; a.cadd_ld = 0; a.xyz = nullptr; a.cxyz = nullptr; a.wx = nullptr; a.b1 = nullptr; a.cadd = nullptr; a.idx = nullptr;
-    a.w2 = w2; a.b2 = b2; a.w3 = w3; a.b3 = b3; a.w2e = w2e; a.out = out; a.out_b = 0; a.out_s = ldo; a.out_c = 1;
-    a.num_tiles = 0; a.tiles_per_cloud = 0; a.trace = nullptr; a.cls_list = nullptr; a.cls_sizes = nullptr;
-    if (w2e) return launch_sa_km<128, 128, 128, 4, 2, 2, SA_NB1, 16, 5>(1, a, (hipStream_t)stream);
-    return launch_sa_km<128, 128, 128, 4, 2, 2, SA_NB1, 16, 4>(1, a, (hipStream_t)stream);
+    SaArgs a = {};  // one "cloud" of rows / 16 "centroids" of 16 plain rows
+    a.B = 1; a.N = (int)rows; a.K = 16; a.S = (int)((rows + 15) / 16);
+    a.a1f = x; a.a1f_ld = ldx; a.w2 = w2; a.b2 = b2; a.w3 = w3; a.b3 = b3; a.w2e = w2e; a.out = out; a.out_s = ldo; a.out_c = 1;
+    if (w2e) return launch_sa_km<128, 128, 128, 4, 2, 2, SA_NB1, 16, 5>(a, (hipStream_t)stream);
+    return launch_sa_km<128, 128, 128, 4, 2, 2, SA_NB1, 16, 4>(a, (hipStream_t)stream);
 }
 
 extern "C" int pn2x_sa_mlp_max_supported(int k, int c1, int c2, int c3) {

@@ -73,6 +73,17 @@ int pn2x_hand_frame(int b, int xb, int num, int n, int j, const float *palm_temp
  * v_mfma_f32_16x16x4_f32, exact fp32).  Supported: k in {16,32,64} and (c1,c2,c3) in
  * {(32,32,64), (64,64,128), (128,128,192)} -- PN2_ERANGE otherwise (query with
  * pn2x_sa_mlp_max_supported; callers keep the unfused operator path for other shapes).
+ *
+ * Return codes of pn2x_sa_mlp_max, pn2x_sa_mlp_max_classes and, per record, pn2x_sa_mlp_max_pair -- one shared check; a call
+ * with several faults gets the first of:
+ *   1. a size below its minimum (b < 0; n, k < 1; s < 0, in a pair record s < 1)            PN2_EINVAL
+ *   2. an empty problem (b = 0, or s = 0 in the positional entries): nothing is done        PN2_OK
+ *   3. a required pointer NULL (an operand without its companions counts: xyz needs cxyz and wx)   PN2_ENULL
+ *   4. a1f_ld / cadd_ld below c1 or no multiple of 4; a1f, cadd, b1, w2, w3 (cls_list) not 16-byte aligned   PN2_EINVAL
+ *   5. beyond a limit of the addressing (24-bit rows and strides, 32-bit offsets), or a k / width set / operand set without an
+ *      instantiation                                                                        PN2_ERANGE
+ * The pair refuses a NULL record (PN2_ENULL) before step 2 and tests pn2x_sa_mlp_max_pair_supported right after it, before it
+ * reads anything else of its records.
  */
 int pn2x_sa_mlp_max(int b, int n, int s, int k, int c1, int c2, int c3, const float *a1f, int a1f_ld,
                     const float *xyz, const float *cxyz, const float *wx, const float *b1, const float *cadd,
@@ -127,11 +138,6 @@ int pn2x_three_nn_weights(int b, int n, int m, const float *unknown, const float
                           void *stream);
 
 /*
- * three_interpolate on POINT-MAJOR features: points (b, m, ldp), out (b, n, ldo), c <= ldp, ldo channels
- * per row; out[b,j,ch] = sum_t weight[b,j,t] * points[b, idx[b,j,t], ch]  (same arithmetic as
- * pn2_three_interpolate).  `out` may point at a column block of a wider row (ldo > c).
- */
-/*
  * pn2x_three_nn_interpolate_pm: pn2x_three_nn_weights followed by pn2x_three_interpolate_pm in ONE launch, for callers that need
  * the (weight, index) pair for nothing else (the forward of feature propagation, pointnet_utils.py:440-453): out (b, n, ldo) rows
  * <- the inverse-distance blend of the three nearest `known` (b,m,3) points' rows of `points` (b, m, ldp), c columns.  Same floats
@@ -141,6 +147,11 @@ int pn2x_three_nn_weights(int b, int n, int m, const float *unknown, const float
 int pn2x_three_nn_interpolate_pm_supported(int b, int n, int m, int c, int ldp, int ldo);
 int pn2x_three_nn_interpolate_pm(int b, int n, int m, int c, const float *unknown, const float *known, const float *points, int ldp,
                                  float *out, int ldo, void *stream);
+/*
+ * three_interpolate on POINT-MAJOR features: points (b, m, ldp), out (b, n, ldo), c <= ldp, ldo channels
+ * per row; out[b,j,ch] = sum_t weight[b,j,t] * points[b, idx[b,j,t], ch]  (same arithmetic as
+ * pn2_three_interpolate).  `out` may point at a column block of a wider row (ldo > c).
+ */
 int pn2x_three_interpolate_pm(int b, int c, int m, int n, const float *points, int ldp, const int *idx,
                               const float *weight, float *out, int ldo, void *stream);
 /*
@@ -284,13 +295,7 @@ int pn2x_pose_head(int b, int j, int c, const float *h, const float *w, const fl
                    const float *R, const float *t, float scale, float *kp_hand, float *kp_cam, const int *nonfinite,
                    void *stream);
 
-/*
- * Both scales of a keypoint-query module (reference PointNetSetAbstractionMsg_GivenCenterPoints, pointnet_utils.py:536-590:
- * two kNN neighbourhood sizes, same layer widths) in ONE persistent launch: every compute unit stays busy and each
- * workgroup loads only its own scale's weights (see sa_fused.hip).  A problem = the per-scale arguments of
- * pn2x_sa_mlp_max.  Supported (pn2x_sa_mlp_max_pair_supported): widths 128-128-192, k = {16, 64}, both problems with the
- * same set of layer-1 operands (a1f + xyz, optionally + cadd); anything else returns PN2_ERANGE (launch them separately).
- */
+/* One problem of pn2x_sa_mlp_max_pair (below) = the per-scale arguments of pn2x_sa_mlp_max, under their names there. */
 typedef struct pn2x_sa_problem {
     int n, s, k;
     const float *a1f;
@@ -304,6 +309,12 @@ typedef struct pn2x_sa_problem {
     int out_s, out_c;
 } pn2x_sa_problem;
 /*
+ * Number of compute units the persistent grids of pn2x_sa_mlp_max / _pair / pn2x_mlp2_rows may occupy (0 = all, the default;
+ * also PN2_SA_CUS in the environment).  A workgroup of these kernels fills its CU, so a caller that keeps several batches in
+ * flight on different streams gains by leaving a few CUs to the other stream (bench.py: 240 of 256 with two in flight).
+ */
+int pn2x_sa_set_compute_units(int n);
+/*
  * pn2x_mlp2_rows: out[r, :] = relu(W3 relu(W2 x[r, :c1] + W2e x[r, c1:c1+3] + b2) + b3) for `rows` point-major rows (x: ldx
  * floats apart; out: ldo floats apart, c3 written; BatchNorm folded into W / b by the caller) -- two consecutive
  * [Conv1d 1x1 + BN + ReLU] layers of a feature-propagation MLP (pointnet_utils.py:504-506) in ONE launch: the tile loop of
@@ -313,15 +324,16 @@ typedef struct pn2x_sa_problem {
  * x and out 16-byte aligned, ldx and ldo multiples of 4 floats (rows are read and written in 16-byte segments), else PN2_EINVAL.
  * PN2_ERANGE unless pn2x_mlp2_rows_supported(c1, c2, c3).
  */
-/*
- * Number of compute units the persistent grids of pn2x_sa_mlp_max / _pair / pn2x_mlp2_rows may occupy (0 = all, the default;
- * also PN2_SA_CUS in the environment).  A workgroup of these kernels fills its CU, so a caller that keeps several batches in
- * flight on different streams gains by leaving a few CUs to the other stream (bench.py: 240 of 256 with two in flight).
- */
-int pn2x_sa_set_compute_units(int n);
 int pn2x_mlp2_rows_supported(int c1, int c2, int c3);
 int pn2x_mlp2_rows(long rows, int c1, int c2, int c3, const float *x, int ldx, const float *w2, const float *w2e, const float *b2,
                    const float *w3, const float *b3, float *out, int ldo, void *stream);
+/*
+ * Both scales of a keypoint-query module (reference PointNetSetAbstractionMsg_GivenCenterPoints, pointnet_utils.py:536-590:
+ * two kNN neighbourhood sizes, same layer widths) in ONE persistent launch: every compute unit stays busy and each
+ * workgroup loads only its own scale's weights (see sa_fused.hip).  Supported (pn2x_sa_mlp_max_pair_supported): widths
+ * 128-128-192, k = {16, 64}, both problems with the same set of layer-1 operands (a1f + xyz, optionally + cadd); anything else
+ * returns PN2_ERANGE (launch them separately).  Each record is checked as pn2x_sa_mlp_max checks its arguments.
+ */
 int pn2x_sa_mlp_max_pair_supported(int k0, int k1, int c1, int c2, int c3);
 int pn2x_sa_mlp_max_pair(int b, int c1, int c2, int c3, const pn2x_sa_problem *p0, const pn2x_sa_problem *p1, void *stream);
 

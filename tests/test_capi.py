@@ -177,6 +177,13 @@ def test_sa_mlp_max_argument_validation_without_gpu(hip_lib_path):
     assert call(k=8) == -3
     assert call(c1=64, c2=64, c3=64, out_b=256, out_s=64) == -3
     assert call(a1f=vp(20)) == -1                          # not 16-byte aligned
+    for name in ("w2", "b2", "w3", "b3", "out", "wx"):
+        assert call(**{name: None}) == -2, name
+    for name in ("cadd", "b1", "w2", "w3"):
+        assert call(**{name: vp(20)}) == -1, name
+    assert call(n=0) == -1 and call(s=-1) == -1
+    assert call(cadd_ld=124) == -1
+    assert call(n=1 << 24) == -3 and call(cadd_ld=1 << 23) == -3 and call(out_c=-1) == -3
 
     class Problem(ctypes.Structure):                       # include/pn2_ext.h: pn2x_sa_problem
         _fields_ = [("n", ci), ("s", ci), ("k", ci), ("a1f", vp), ("a1f_ld", ci), ("xyz", vp), ("cxyz", vp), ("wx", vp), ("b1", vp),
@@ -194,6 +201,32 @@ def test_sa_mlp_max_argument_validation_without_gpu(hip_lib_path):
     assert lib.pn2x_sa_mlp_max_pair(-1, 128, 128, 192, ctypes.byref(p16), ctypes.byref(p64), None) == -1
     assert lib.pn2x_sa_mlp_max_pair(2, 128, 128, 192, ctypes.byref(p32), ctypes.byref(p64), None) == -3
     assert lib.pn2x_sa_mlp_max_pair(0, 128, 128, 192, ctypes.byref(p16), ctypes.byref(p64), None) == 0
+
+    # every field of a record, one fault per call, in the first record and in the second: none reaches a launch
+    def pair(first, **change):
+        bad = problem(16 if first else 64)
+        for name, value in change.items():
+            assert name in dict(Problem._fields_)
+            setattr(bad, name, value)
+        recs = (bad, p64) if first else (p16, bad)
+        return lib.pn2x_sa_mlp_max_pair(2, 128, 128, 192, ctypes.byref(recs[0]), ctypes.byref(recs[1]), None)
+
+    for first in (True, False):
+        for name in ("idx", "w2", "b2", "w3", "b3", "out", "cxyz", "wx"):
+            assert pair(first, **{name: None}) == -2, name
+        assert pair(first, a1f=None, xyz=None) == -2                 # layer 1 needs a per-point term
+        for name in ("a1f_ld", "cadd_ld"):
+            assert pair(first, **{name: 124}) == -1, name            # below c1
+            assert pair(first, **{name: 130}) == -1, name            # rows are read as 16-byte quads
+            assert pair(first, **{name: 1 << 23}) == -3, name        # a row stride past the 24-bit multiplier
+        for name in ("a1f", "cadd", "b1", "w2", "w3"):
+            assert pair(first, **{name: 20}) == -1, name             # not 16-byte aligned
+        assert pair(first, n=0) == -1 and pair(first, s=0) == -1
+        assert pair(first, k=0) == -3                                # (k0, k1) is tested first: not a supported pair
+        assert pair(first, n=1 << 24) == -3 and pair(first, s=1 << 24) == -3   # row numbers past 24 bits
+        assert pair(first, out_s=-384) == -3
+        # the two records must name the same layer-1 operands, a1f + xyz (+ cadd)
+        assert pair(first, cadd=None) == -3 and pair(first, a1f=None) == -3 and pair(first, xyz=None) == -3
 
     widths = {(32, 32, 64), (64, 64, 128), (128, 128, 192)}
     near = sorted(widths | {(32, 32, 32), (32, 64, 64), (64, 64, 64), (64, 64, 192), (64, 128, 128), (128, 128, 128), (128, 128, 256),

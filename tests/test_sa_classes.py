@@ -67,6 +67,18 @@ def test_sa_classes_argument_validation_without_gpu(hip_lib_path):
     assert call(cls_list=vp(24)) == -1                     # records are read as 16-byte quads
     assert call(b=1 << 20, n=64) == -3                     # b * n beyond the 24-bit row numbers
     assert call(out_b=1 << 31) == -3                       # the whole output must sit behind one 32-bit offset
+    # the first b * n and b * s past the 24-bit row numbers, each the call's only fault (a1f / cadd left out: their whole-tensor
+    # byte limits would be passed too)
+    assert call(b=1 << 12, n=1 << 12, a1f=None) == -3
+    assert call(b=1 << 12, s=1 << 12, cadd=None) == -3
+    assert call(out_b=-512) == -3
+    for name in ("w2", "b2", "w3", "b3", "out", "wx"):
+        assert call(**{name: None}) == -2, name
+    for name in ("a1f", "cadd", "b1", "w2", "w3"):
+        assert call(**{name: vp(20)}) == -1, name
+    assert call(n=0) == -1 and call(s=-1) == -1
+    assert call(cadd_ld=60) == -1
+    assert call(n=1 << 24) == -3 and call(a1f_ld=1 << 23) == -3
     for k in (8, 16, 31, 32, 33, 64):
         for w in ((32, 32, 64), (64, 64, 128), (128, 128, 192), (64, 64, 64), (32, 32, 128)):
             assert lib.pn2x_sa_mlp_max_classes_supported(k, *w) == int(k == 32 and w in ((32, 32, 64), (64, 64, 128))), (k, w)
