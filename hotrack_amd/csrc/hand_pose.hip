@@ -32,6 +32,12 @@
 // instantiations are the code they were) adds a vertex's offset to its staged v_rest - j_k, takes the fingertip keypoints from
 // skinned vertices (the owner lane leaves the position in the tip joint's unused LDS slot; the keypoint terms run after the
 // vertex loop), and centres on the root.  The update kernel is shared.
+//
+// hand_pose_offsets_batch_kernel / hand_pose_mano_eval_batch_kernel (pn2x_hand_pose_mano_opt_batch).  The MANO kernels for S
+// problems per launch: the pre-pass is the device function hand_pose_offsets_block, which the single kernel calls with its own
+// arguments and the batched one (grid z = the problem) with the record's state and slice z of ONE offsets workspace (S slices
+// of P * ceil16(3 V) floats); an output element is the same 34 accumulations whatever the grid.  The batched evaluation builds
+// its Frame as hand_pose_eval_batch_kernel does and points ManoExtra::offsets at the problem's slice.
 #include <hip/hip_fp16.h>
 
 #include <cstring>
@@ -397,10 +403,11 @@ __global__ void __launch_bounds__(256) hand_pose_mano_eval_kernel(const Frame A,
 constexpr int NF = 9 * (NPOSE / 3), KP = NF + 1, OCT = 64;
 static_assert(KP % 8 == 0 && KP % 16 == 8, "eight full k-groups of 16 and one of 8");
 
-__global__ void __launch_bounds__(256) hand_pose_offsets_kernel(int P, int ntiles, const float *__restrict__ pd,
-                                                                const float *__restrict__ pose_mean, const float *__restrict__ comps,
-                                                                float theta_scale, const float *__restrict__ pre,
-                                                                const float *__restrict__ state, float *__restrict__ out) {
+// The body is a device function: the single kernel calls it with its own arguments, the batched one with a problem's.
+__device__ __forceinline__ void hand_pose_offsets_block(int P, int ntiles, const float *__restrict__ pd,
+                                                        const float *__restrict__ pose_mean, const float *__restrict__ comps,
+                                                        float theta_scale, const float *__restrict__ pre,
+                                                        const float *__restrict__ state, float *__restrict__ out) {
     using mrows::f32x4;
     __shared__ float4 feat4[OCT * KP / 4];
     float *feat = reinterpret_cast<float *>(feat4);
@@ -456,6 +463,13 @@ __global__ void __launch_bounds__(256) hand_pose_offsets_kernel(int P, int ntile
     }
 }
 
+__global__ void __launch_bounds__(256) hand_pose_offsets_kernel(int P, int ntiles, const float *__restrict__ pd,
+                                                                const float *__restrict__ pose_mean, const float *__restrict__ comps,
+                                                                float theta_scale, const float *__restrict__ pre,
+                                                                const float *__restrict__ state, float *__restrict__ out) {
+    hand_pose_offsets_block(P, ntiles, pd, pose_mean, comps, theta_scale, pre, state, out);
+}
+
 // a record is read through the constant address space: nothing writes the table while a kernel that reads it runs, and a
 // read-only, workgroup-uniform address makes every field a scalar load
 typedef __attribute__((address_space(4))) pn2x_hand_pose_problem ConstProblem;
@@ -475,6 +489,33 @@ __global__ void __launch_bounds__(256) hand_pose_eval_batch_kernel(const Batch B
     A.vis = r->vis_mask; A.obj_r = r->obj_r; A.obj_t = r->obj_t; A.vol = r->vol; A.mask = r->mask; A.h = r->h; A.w = r->w;
     A.fx = r->fx; A.fy = r->fy; A.cx = r->cx; A.cy = r->cy; A.terms = r->work;
     hand_pose_eval_block<F16, false>(A, ManoExtra{});
+}
+
+// The MANO batch (pn2x_hand_pose_mano_opt_batch): M.offsets is the base of the batch's offsets workspace, s slices of P * ldo
+// floats; problem z's pre-pass writes slice z (grid z = the problem) and its evaluation (grid y = the problem) reads it.
+__global__ void __launch_bounds__(256) hand_pose_offsets_batch_kernel(int P, int ntiles, const float *__restrict__ pd,
+                                                                      const float *__restrict__ pose_mean,
+                                                                      const float *__restrict__ comps, float theta_scale,
+                                                                      const float *__restrict__ pre,
+                                                                      const pn2x_hand_pose_problem *__restrict__ prob,
+                                                                      float *__restrict__ offsets) {
+    const ConstProblem *r = (const ConstProblem *)prob + blockIdx.z;
+    if (!r->active) return;
+    hand_pose_offsets_block(P, ntiles, pd, pose_mean, comps, theta_scale, pre, r->state,
+                            offsets + (size_t)blockIdx.z * (size_t)P * (size_t)(16 * ntiles));
+}
+
+template <bool F16>
+__global__ void __launch_bounds__(256) hand_pose_mano_eval_batch_kernel(const Batch B, const ManoExtra M0) {
+    const ConstProblem *r = (const ConstProblem *)B.prob + blockIdx.y;
+    if (!r->active) return;
+    Frame A = B.shared;  // (the record's fields as hand_pose_eval_batch_kernel takes them)
+    A.rest_j = r->rest_joints; A.rest_v = r->rest_verts; A.state = r->state; A.pred_kp = r->pred_kp; A.last_kp = r->last_kp;
+    A.vis = r->vis_mask; A.obj_r = r->obj_r; A.obj_t = r->obj_t; A.vol = r->vol; A.mask = r->mask; A.h = r->h; A.w = r->w;
+    A.fx = r->fx; A.fy = r->fy; A.cx = r->cx; A.cy = r->cy; A.terms = r->work;
+    ManoExtra M = M0;
+    M.offsets = M0.offsets + (size_t)blockIdx.y * (size_t)A.P * (size_t)M0.ldo;
+    hand_pose_eval_block<F16, true>(A, M);
 }
 
 __global__ void __launch_bounds__(256) hand_pose_energy_kernel(int P, const float *__restrict__ terms, float *__restrict__ energy) {
@@ -635,6 +676,9 @@ extern "C" long pn2x_hand_pose_mano_work_floats(int p, int v) {
 extern "C" long pn2x_hand_pose_opt_batch_work_floats(int p, int s) {
     return (p < 0 || s < 0) ? (long)PN2_EINVAL : (long)TERMS * p * s;
 }
+extern "C" long pn2x_hand_pose_mano_batch_work_floats(int p, int v, int s) {
+    return (p < 0 || v < 0 || s < 0) ? (long)PN2_EINVAL : (long)s * p * offsets_ld(v);
+}
 
 // What an entry's argument checks found, whichever check found it: a bad value before a limit before a NULL pointer.
 struct Faults {
@@ -713,6 +757,21 @@ static void launch_eval(const pn2x_hand_pose_setup &s, int active, int problems,
     hipLaunchKernelGGL(Kernel, dim3(gx, problems), dim3(256), eval_lds_bytes(s.v, s.k), st, args...);
 }
 
+// what the MANO evaluation reads beyond its Frame; `offsets` is a single problem's scratch or the base of a batch's workspace
+static ManoExtra mano_extra(const pn2x_hand_pose_setup &s, const float *offsets) {
+    ManoExtra M;
+    M.offsets = offsets; M.pose_mean = s.pose_mean; M.kp_vertex = s.kp_vertex; M.ldo = offsets_ld(s.v); M.centre = s.centre_root;
+    return M;
+}
+
+// The pre-pass grid: x = groups of OCT candidates, y = as many strides over the 16-row tiles as cover the compute units three
+// times, the device shared among the `active` problems (a single problem is active == 1); the batched launch's z is the problem.
+static dim3 offsets_grid(const pn2x_hand_pose_setup &s, int active, int problems) {
+    const int ntiles = offsets_ld(s.v) / 16, gx = (s.p + OCT - 1) / OCT, most = (ntiles + 3) / 4;
+    const int cover = (int)(3L * num_compute_units() / ((long)gx * active));
+    return dim3(gx, cover < 1 ? 1 : (cover > most ? most : cover), problems);
+}
+
 // a single problem's evaluation: the plain kernel, or for a MANO setup the pose-offset pre-pass and the MANO kernel
 static void eval_single(const pn2x_hand_pose_setup &s, const Frame &A, float *offsets, hipStream_t st) {
     if (!s.posedirs) {
@@ -720,13 +779,9 @@ static void eval_single(const pn2x_hand_pose_setup &s, const Frame &A, float *of
         else launch_eval<hand_pose_eval_kernel<false>>(s, 1, 1, st, A);
         return;
     }
-    ManoExtra M;
-    M.offsets = offsets; M.pose_mean = s.pose_mean; M.kp_vertex = s.kp_vertex; M.ldo = offsets_ld(s.v); M.centre = s.centre_root;
-    // pre-pass: x = groups of OCT candidates, y = as many strides over the 16-row tiles as cover the compute units three times
-    const int ntiles = M.ldo / 16, gx = (s.p + OCT - 1) / OCT, cover = 3 * num_compute_units() / gx, most = (ntiles + 3) / 4;
-    const int gy = cover < 1 ? 1 : (cover > most ? most : cover);
-    hipLaunchKernelGGL(hand_pose_offsets_kernel, dim3(gx, gy), dim3(256), 0, st, s.p, ntiles, s.posedirs, s.pose_mean, s.comps,
-                       s.theta_scale, s.pre, A.state, offsets);
+    const ManoExtra M = mano_extra(s, offsets);
+    hipLaunchKernelGGL(hand_pose_offsets_kernel, offsets_grid(s, 1, 1), dim3(256), 0, st, s.p, M.ldo / 16, s.posedirs, s.pose_mean,
+                       s.comps, s.theta_scale, s.pre, A.state, offsets);
     if (s.vol_f16) launch_eval<hand_pose_mano_eval_kernel<true>>(s, 1, 1, st, A, M);
     else launch_eval<hand_pose_mano_eval_kernel<false>>(s, 1, 1, st, A, M);
 }
@@ -791,24 +846,63 @@ extern "C" int pn2x_hand_pose_problems_fill(pn2x_hand_pose_problem *problems, in
     return check_launch();
 }
 
+// what the two batched entries check beside the setup
+static void check_batch(int s, int active, int iterations, Faults &f) {
+    f.inval |= s < 1 || active < 0 || active > s || iterations < 0;
+    f.range |= s > 65535 || iterations > 4096;
+}
+
+// The batched entries' loop over checked arguments: per iteration, for a MANO setup (`offsets` is then the batch's workspace)
+// the pre-pass over (candidate groups, tile strides, problem), then the evaluation over (candidates, problem) and the update
+// with a workgroup per problem.
+static int opt_batch_loop(const pn2x_hand_pose_setup &s, int n, int active, const pn2x_hand_pose_problem *problems, float *offsets,
+                          int iterations, double scaling_coefficient2, double beta, hipStream_t st) {
+    Batch B;
+    B.shared = shared_frame(s);
+    B.prob = problems;
+    const bool mano = s.posedirs != nullptr;
+    const ManoExtra M = mano_extra(s, offsets);
+    for (int it = 0; it < iterations; ++it) {
+        if (mano) {
+            hipLaunchKernelGGL(hand_pose_offsets_batch_kernel, offsets_grid(s, active, n), dim3(256), 0, st, s.p, M.ldo / 16,
+                               s.posedirs, s.pose_mean, s.comps, s.theta_scale, s.pre, problems, offsets);
+            if (s.vol_f16) launch_eval<hand_pose_mano_eval_batch_kernel<true>>(s, active, n, st, B, M);
+            else launch_eval<hand_pose_mano_eval_batch_kernel<false>>(s, active, n, st, B, M);
+        } else if (s.vol_f16) {
+            launch_eval<hand_pose_eval_batch_kernel<true>>(s, active, n, st, B);
+        } else {
+            launch_eval<hand_pose_eval_batch_kernel<false>>(s, active, n, st, B);
+        }
+        hipLaunchKernelGGL(hand_pose_update_batch_kernel, dim3(n), dim3(UT), 0, st, s.p, s.pre, problems, s.comps, s.theta_scale,
+                           (float)scaling_coefficient2, (float)beta, (float)(1.0 - beta), it);
+    }
+    return check_launch();
+}
+
 extern "C" int pn2x_hand_pose_opt_batch(const pn2x_hand_pose_setup *setup, int s, int active, const pn2x_hand_pose_problem *problems,
                                         int iterations, double scaling_coefficient2, double beta, void *stream) {
     Faults f;
     check_setup(setup, f);
-    f.inval |= (is_record(setup) && setup->posedirs) || s < 1 || active < 0 || active > s || iterations < 0;  // (no batched MANO kernel)
-    f.range |= s > 65535 || iterations > 4096;
+    check_batch(s, active, iterations, f);
+    f.inval |= is_record(setup) && setup->posedirs;  // a MANO setup goes to pn2x_hand_pose_mano_opt_batch
     if (f.code() != PN2_OK || iterations == 0) return f.code();
     if (!problems) return PN2_ENULL;
     if (active == 0) return PN2_OK;
-    Batch B;
-    B.shared = shared_frame(*setup);
-    B.prob = problems;
-    hipStream_t st = (hipStream_t)stream;
-    for (int it = 0; it < iterations; ++it) {
-        if (setup->vol_f16) launch_eval<hand_pose_eval_batch_kernel<true>>(*setup, active, s, st, B);
-        else launch_eval<hand_pose_eval_batch_kernel<false>>(*setup, active, s, st, B);
-        hipLaunchKernelGGL(hand_pose_update_batch_kernel, dim3(s), dim3(UT), 0, st, setup->p, setup->pre, problems, setup->comps,
-                           setup->theta_scale, (float)scaling_coefficient2, (float)beta, (float)(1.0 - beta), it);
+    return opt_batch_loop(*setup, s, active, problems, nullptr, iterations, scaling_coefficient2, beta, (hipStream_t)stream);
+}
+
+extern "C" int pn2x_hand_pose_mano_opt_batch(const pn2x_hand_pose_setup *setup, int s, int active,
+                                             const pn2x_hand_pose_problem *problems, float *offsets, int iterations,
+                                             double scaling_coefficient2, double beta, void *stream) {
+    Faults f;
+    check_setup(setup, f);
+    check_batch(s, active, iterations, f);
+    f.inval |= is_record(setup) && !setup->posedirs;  // a plain setup goes to pn2x_hand_pose_opt_batch
+    const bool work = iterations != 0 && active != 0;  // nothing to do: neither the table nor the workspace is looked at
+    if (work) {
+        f.inval |= ((uintptr_t)offsets & 15) != 0;  // 16-byte stores; a slice is a multiple of 16 floats
+        f.null |= !offsets || !problems;
     }
-    return check_launch();
+    if (f.code() != PN2_OK || !work) return f.code();
+    return opt_batch_loop(*setup, s, active, problems, offsets, iterations, scaling_coefficient2, beta, (hipStream_t)stream);
 }

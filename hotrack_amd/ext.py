@@ -1091,6 +1091,10 @@ _lib.pn2x_hand_pose_problems_fill.argtypes = [_vp, _ci, _HP_PROBLEM, _vp]
 _lib.pn2x_hand_pose_problems_fill.restype = _ci
 _lib.pn2x_hand_pose_opt_batch.argtypes = [_HP_SETUP, _ci, _ci, _vp, _ci, _cd, _cd, _vp]
 _lib.pn2x_hand_pose_opt_batch.restype = _ci
+_lib.pn2x_hand_pose_mano_batch_work_floats.argtypes = [_ci, _ci, _ci]
+_lib.pn2x_hand_pose_mano_batch_work_floats.restype = _cl
+_lib.pn2x_hand_pose_mano_opt_batch.argtypes = [_HP_SETUP, _ci, _ci, _vp, _vp, _ci, _cd, _cd, _vp]
+_lib.pn2x_hand_pose_mano_opt_batch.restype = _ci
 
 
 def hand_pose_opt_supported(p: int, v: int, j: int, k: int, d_pose: int = 10, res: int = 151) -> bool:
@@ -1104,7 +1108,8 @@ def hand_pose_model(tables: dict, device) -> dict:
     Tables with a MANO entry (posedirs, pose_mean, kp_vertex, centre_root) set m["mano"] and add what the MANO
     kernels read: posedirs_pack (ceil16(3 V), 136) = posedirs as rows 3 v + coordinate, zero-padded; pose_mean (45); kp_vertex
     (J) int32; centre_root 0 / 1; and in skin_pack bits 25..29 of a keypoint vertex the table joint it is (mano_ok: no vertex
-    serves two keypoints).  hand_pose_energy / hand_pose_opt run such a model on the MANO kernels; hand_pose_opt_batch refuses it."""
+    serves two keypoints).  hand_pose_energy / hand_pose_opt run such a model on the MANO kernels, hand_pose_mano_opt_batch in lockstep;
+    hand_pose_opt_batch refuses it."""
     f32, i32 = torch.float32, torch.int32
     idx = tables["skin_idx"].long()
     V, K = idx.shape
@@ -1256,7 +1261,7 @@ def hand_pose_opt(model, rest, theta_scale, pre, state, pred_kp, last_kp, vis_ma
     return tr
 
 
-# ---- the same loop for S problems per launch (pn2x_hand_pose_opt_batch) --------------------------------------------------------
+# ---- the same loop for S problems per launch (pn2x_hand_pose_opt_batch / pn2x_hand_pose_mano_opt_batch) ------------------------
 _HAND_POSE_FRAME_KEYS = ("rest", "theta_scale", "pre", "pred_kp", "last_kp", "vis_mask", "obj_r", "obj_t", "volume", "voxel_scale", "mask",
                          "proj", "weights")
 # how hand_pose_opt_batch names the setup fields in which two frames of a batch may differ (the model's tables are one object)
@@ -1271,19 +1276,48 @@ def hand_pose_opt_batch(model, frames, states, iterations: int, scaling_coeffici
       vis_mask, obj_r, obj_t, volume, voxel_scale, mask, proj, weights; a 'model' key is ignored) or None for a problem that
       sits out.  rest, pred_kp, last_kp (None or a tensor), vis_mask, the object pose, the volume (problems may share one), the
       mask with its size and proj differ per problem; pre (one tensor), theta_scale, weights and the volumes' resolution, dtype
-      and voxel_scale are shared, and a batch that mixes them is refused.  So is a model with MANO entries.
+      and voxel_scale are shared, and a batch that mixes them is refused.  So is a model with MANO entries: it goes to
+      hand_pose_mano_opt_batch.
     states (S, 90): updated in place; the rows of problems that sit out are not touched.
     Every tensor is read in place by the launches, and the record table is written by launches that carry the records as
     arguments: no upload, no host read -- a captured call replays on whatever its buffers hold then.
     -> trace (S, iterations, 19) (zero rows for problems that sit out) or None."""
+    return _hand_pose_batch(False, model, frames, states, iterations, scaling_coefficient2, beta, trace, None)
+
+
+def hand_pose_mano_batch_workspace(p: int, v: int, s: int, device) -> torch.Tensor:
+    """The pose-blend offsets of s problems of p candidates of a v-vertex hand, one allocation of
+    pn2x_hand_pose_mano_batch_work_floats floats (problem q uses slice q), to be reused."""
+    return torch.empty(int(_lib.pn2x_hand_pose_mano_batch_work_floats(int(p), int(v), int(s))), dtype=torch.float32, device=device)
+
+
+def hand_pose_mano_opt_batch(model, frames, states, iterations: int, scaling_coefficient2: float, beta: float, trace: bool = False,
+                             offsets: torch.Tensor = None):
+    """hand_pose_opt_batch for a model with MANO entries (pn2x_hand_pose_mano_opt_batch): per iteration the pose-offset pre-pass
+    over all problems, the MANO evaluation over (candidates, problem) and the shared update -- every problem's state and trace
+    are bit-for-bit what hand_pose_opt gives for it alone on the MANO kernels.  frames, states, the shared fields, the record
+    table and the result are hand_pose_opt_batch's.  A plain model is refused (it goes to hand_pose_opt_batch), and so is a
+    model whose mano_ok is false.
+    offsets: hand_pose_mano_batch_workspace(P, V, S) to reuse (else allocated): S times the single route's workspace."""
+    return _hand_pose_batch(True, model, frames, states, iterations, scaling_coefficient2, beta, trace, offsets)
+
+
+def _hand_pose_batch(mano, model, frames, states, iterations, scaling_coefficient2, beta, trace, offsets):
+    """The two batched bindings: `mano` names the kind of model the entry takes."""
     f32 = torch.float32
+    what = "hand_pose_mano_opt_batch" if mano else "hand_pose_opt_batch"
     S, iterations = len(frames), int(iterations)
     if S < 1:
-        raise ValueError("hand_pose_opt_batch: frames is empty")
-    if model.get("mano", False):  # the lockstep kernels would drop the model's MANO terms without a word
-        raise ValueError("hand_pose_opt_batch: a model with MANO entries goes to hand_pose_energy / hand_pose_opt")
+        raise ValueError(f"{what}: frames is empty")
+    if not mano and model.get("mano", False):  # the lockstep kernels would drop the model's MANO terms without a word
+        raise ValueError("hand_pose_opt_batch: a model with MANO entries goes to hand_pose_mano_opt_batch (or, one problem at a "
+                         "time, to hand_pose_energy / hand_pose_opt)")
+    if mano and not model.get("mano", False):
+        raise ValueError("hand_pose_mano_opt_batch: a model without MANO entries goes to hand_pose_opt_batch")
+    if mano and not model.get("mano_ok", False):
+        raise ValueError("hand_pose_mano: one vertex serves two keypoints (kp_vertex)")
     if states.dim() != 2 or tuple(states.shape) != (S, HAND_POSE_STATE_FLOATS):
-        raise ValueError(f"hand_pose_opt_batch: states {tuple(states.shape)} is not ({S}, {HAND_POSE_STATE_FLOATS})")
+        raise ValueError(f"{what}: states {tuple(states.shape)} is not ({S}, {HAND_POSE_STATE_FLOATS})")
     _native._ptr(states, "states", f32, S * HAND_POSE_STATE_FLOATS)
     dev = states.device
     tr = torch.zeros((S, iterations, HAND_POSE_TRACE_FLOATS), dtype=f32, device=dev) if trace else None
@@ -1294,26 +1328,26 @@ def hand_pose_opt_batch(model, frames, states, iterations: int, scaling_coeffici
             continue
         missing = [k for k in _HAND_POSE_FRAME_KEYS if k not in fr]
         if missing:
-            raise ValueError(f"hand_pose_opt_batch: frames[{q}] lacks {missing}")
+            raise ValueError(f"{what}: frames[{q}] lacks {missing}")
         mine = _hand_pose_setup(model, fr["pre"], fr["theta_scale"], fr["volume"], fr["voxel_scale"], fr["weights"])
         for name, t in (("pre", fr["pre"]), ("pred_kp", fr["pred_kp"]), ("mask", fr["mask"]), ("rest_joints", fr["rest"][0]),
                         ("volume", fr["volume"])):
             if t.device != dev:
-                raise RuntimeError(f"hand_pose_opt_batch: frames[{q}]['{name}'] is on {t.device}, states on {dev}")
+                raise RuntimeError(f"{what}: frames[{q}]['{name}'] is on {t.device}, states on {dev}")
         if first is None:
             first, shared = q, mine
         for field, name in _HAND_POSE_SHARED.items() if bytes(mine) != bytes(shared) else ():
             a, b = getattr(shared, field), getattr(mine, field)
             if a != b:
-                what = "one tensor of candidates" if name == "pre" else f"{a} and {b}"
-                raise ValueError(f"hand_pose_opt_batch: frames[{first}] and frames[{q}] differ in {name} ({what}): a batch "
+                kind = "one tensor of candidates" if name == "pre" else f"{a} and {b}"
+                raise ValueError(f"{what}: frames[{first}] and frames[{q}] differ in {name} ({kind}): a batch "
                                  "shares it; run them in separate batches")
         per[q] = _hand_pose_frame(model, states.data_ptr() + q * sstride, None, None if tr is None else tr.data_ptr() + q * tstride,
                                   fr["rest"], fr["pred_kp"], fr["last_kp"], fr["vis_mask"], fr["obj_r"], fr["obj_t"], fr["volume"],
                                   fr["mask"], fr["proj"])
     if first is None or iterations == 0:
         if iterations < 0:
-            raise ValueError(f"hand_pose_opt_batch: iterations = {iterations}")
+            raise ValueError(f"{what}: iterations = {iterations}")
         return tr
     need = _lib.pn2x_hand_pose_opt_batch_work_floats(shared.p, S)
     work = torch.empty((S, need // S), dtype=f32, device=dev)
@@ -1324,12 +1358,21 @@ def hand_pose_opt_batch(model, frames, states, iterations: int, scaling_coeffici
             r.work = work.data_ptr() + q * work.stride(0) * 4
             recs[q] = r
     n_active = sum(r is not None for r in per)
+    tail = (iterations, float(scaling_coefficient2), float(beta))
+    if mano:
+        if offsets is None:
+            offsets = hand_pose_mano_batch_workspace(shared.p, shared.v, S, dev)
+        if offsets.device != dev:
+            raise RuntimeError(f"{what}: offsets is on {offsets.device}, states on {dev}")
+        off_ptr = _native._ptr(offsets, "offsets", f32, int(_lib.pn2x_hand_pose_mano_batch_work_floats(shared.p, shared.v, S)))
+        entry, args = _lib.pn2x_hand_pose_mano_opt_batch, (table.data_ptr(), off_ptr) + tail
+    else:
+        entry, args = _lib.pn2x_hand_pose_opt_batch, (table.data_ptr(),) + tail
     with torch.cuda.device(dev):
         st = _native._stream(states)
         _native._check(_native._call(_lib.pn2x_hand_pose_problems_fill, "hand_pose_problems_fill", None, table.data_ptr(), S, recs, st),
                        "hand_pose_problems_fill")
-        _native._check(_native._call(_lib.pn2x_hand_pose_opt_batch, "hand_pose_opt_batch", None, ctypes.byref(shared), S, n_active,
-                                     table.data_ptr(), iterations, float(scaling_coefficient2), float(beta), st), "hand_pose_opt_batch")
+        _native._check(_native._call(entry, what, None, ctypes.byref(shared), S, n_active, *args, st), what)
     return tr
 
 

@@ -475,7 +475,18 @@ int pn2x_hand_shape_opt(int p, int d, int t, int iterations, const float *k0, co
  * hand_pose_update_batch_kernel with a workgroup per problem.  They run pn2x_hand_pose_opt's device functions, so a problem's
  * state and trace equal, bit for bit, what pn2x_hand_pose_opt gives for it alone.  `problems` is a DEVICE array of s records;
  * a record with active == 0 sits out -- no pointer of it is read (all may be NULL) and nothing of it is written.  `active`
- * (the argument) is the number of active records.  There is no batched MANO kernel: a setup with posedirs set is PN2_EINVAL.
+ * (the argument) is the number of active records.  A setup with posedirs set is PN2_EINVAL here: it goes to
+ * pn2x_hand_pose_mano_opt_batch.
+ * pn2x_hand_pose_mano_opt_batch: the same for a MANO setup (posedirs set; a setup without is PN2_EINVAL, the mirror of the plain
+ * entry's refusal).  Per iteration hand_pose_offsets_batch_kernel over a (groups of 64 candidates, tile strides, problem) grid,
+ * hand_pose_mano_eval_batch_kernel over (candidates, problem) and the shared hand_pose_update_batch_kernel: the device functions
+ * of the single MANO kernels, so a problem's state and trace equal, bit for bit, what pn2x_hand_pose_opt gives for it alone.
+ * `problems` and pn2x_hand_pose_problems_fill are used as they are (a record's work stays pn2x_hand_pose_opt_work_floats(p)
+ * floats).  offsets: ONE device allocation of pn2x_hand_pose_mano_batch_work_floats(p, v, s) = s * p * ceil16(3 v) floats,
+ * 16-byte aligned; problem q uses slice q (a slice is a multiple of 16 floats, so the alignment carries over), and the slice of
+ * a record that sits out is neither read nor written.  The pre-pass grid's y is 3 * compute units / (groups * active) clamped
+ * to [1, ceil(tiles / 4)] (active = 1 for the single entries).  NULL offsets is PN2_ENULL, misaligned PN2_EINVAL; with
+ * iterations == 0 or active == 0 neither the table nor offsets is looked at.
  * Every evaluation grid deals a problem's ceil(p / 4) workgroups evenly over at most max(1, 3 * compute units / active)
  * (active = 1 for the single entries), so the launch covers the device about three times.
  * pn2x_hand_pose_problems_fill writes s records from HOST memory `host` into the device array by kernel launches that carry
@@ -524,6 +535,9 @@ int pn2x_hand_pose_opt(const pn2x_hand_pose_setup *setup, const pn2x_hand_pose_p
 int pn2x_hand_pose_problems_fill(pn2x_hand_pose_problem *problems, int s, const pn2x_hand_pose_problem *host, void *stream);
 int pn2x_hand_pose_opt_batch(const pn2x_hand_pose_setup *setup, int s, int active, const pn2x_hand_pose_problem *problems,
                              int iterations, double scaling_coefficient2, double beta, void *stream);
+long pn2x_hand_pose_mano_batch_work_floats(int p, int v, int s);
+int pn2x_hand_pose_mano_opt_batch(const pn2x_hand_pose_setup *setup, int s, int active, const pn2x_hand_pose_problem *problems,
+                                  float *offsets, int iterations, double scaling_coefficient2, double beta, void *stream);
 
 /*
  * IKNet forward in eval mode (reference hand_network.py:264-322; hotrack_amd/csrc/iknet.hip) for m <= 16 rows, fp32:

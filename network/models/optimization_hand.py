@@ -170,6 +170,9 @@ class gf_optimize_hand_pose:
         self.device = torch.device(cfg.get("device", device))
         # the device-resident route (hotrack_amd/csrc/hand_pose.hip): opt-in, see use_kernel()
         self.fused = bool((cfg.get("opt") or {}).get("fused_pose", False))
+        # optimize_batch on a MANO-structured model in lockstep (ext.hand_pose_mano_opt_batch): opt-in, its offsets workspace
+        # is S times optimize()'s
+        self.lockstep_mano = bool((cfg.get("opt") or {}).get("lockstep_mano", False))
         self._fused_said = False
         self.keep_trace = False
         self.trace = None
@@ -413,19 +416,24 @@ class gf_optimize_hand_pose:
         sequence), bit-equal per sequence to optimize() on it alone.
         calls: a list of S entries -- the arguments of optimize() as a tuple or as a dict by name, or None for a sequence that sits
         out.  A dict may also carry the sequence's own 'sdf_volume' (and 'voxel_scale'); without one the loaded volume is used.
-        A hand model whose tables carry MANO entries has no batched kernel: it runs optimize() per entry (said once).
+        A hand model whose tables carry MANO entries runs optimize() per entry (said once) unless cfg['opt']['lockstep_mano']
+        is set: then it is ONE ext.hand_pose_mano_opt_batch call (per iteration the pose-offset pre-pass over all sequences,
+        the MANO evaluation and the update), bit-equal per sequence as well.  Its offsets workspace is S times optimize()'s
+        (47.8 MB per sequence at 5120 candidates x 778 vertices), kept per (S, particles, vertices): hence the switch.
         All volumes of a batch share resolution, dtype and voxel_scale.  Shape code, volume, object pose, mask and projection are
         kept per sequence; the hand model's registered shape is what it was before the call.
         -> a list of S (final_kp, theta, rot, trans) tuples, None where the entry was None.
         Without the device-resident route (use_kernel() false) it is optimize() per entry."""
         split = [None if c is None else self._split_call(c) for c in calls]
         lockstep = self.use_kernel()
-        if lockstep and self._kernel_model()["mano"]:  # no batched MANO kernel: optimize() per entry (the device-resident one)
+        mano = lockstep and self._kernel_model()["mano"]
+        if mano and not self.lockstep_mano:  # optimize() per entry (the device-resident one)
             lockstep = False
             if not self.__dict__.get("_batch_said"):
                 self._batch_said = True
                 print("[Hand pose optimiser] optimize_batch runs optimize() per sequence: the hand model's tables carry MANO entries "
-                      "(pose blend shapes, vertex fingertips) and the lockstep kernels take plain tables only")
+                      "(pose blend shapes, vertex fingertips) and their lockstep kernels are opt-in (cfg['opt']['lockstep_mano']: "
+                      "the offsets workspace grows with the number of sequences)")
         if not lockstep:
             out = []
             for sc in split:
@@ -462,7 +470,14 @@ class gf_optimize_hand_pose:
                 states.append(self._pack_state(self.initial_scale))
                 betas.append(beta_k)
             state = torch.stack(states)
-            tr = ext.hand_pose_opt_batch(m, frames, state, self.iteration, self.scaling_coefficient2, self.beta, trace=self.keep_trace)
+            if mano:
+                key = (len(frames), self.particle_size, m["V"])
+                if self.__dict__.get("_mano_batch_work_key") != key:
+                    self._mano_batch_work, self._mano_batch_work_key = ext.hand_pose_mano_batch_workspace(key[1], key[2], key[0], self.device), key
+                tr = ext.hand_pose_mano_opt_batch(m, frames, state, self.iteration, self.scaling_coefficient2, self.beta,
+                                                  trace=self.keep_trace, offsets=self._mano_batch_work)
+            else:
+                tr = ext.hand_pose_opt_batch(m, frames, state, self.iteration, self.scaling_coefficient2, self.beta, trace=self.keep_trace)
             self.trace = tr
             out = []
             for k, fr in enumerate(frames):

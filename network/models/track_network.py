@@ -253,7 +253,9 @@ class HandTrackModel(nn.Module):
         own carried state (last keypoints, previous pose code, palm template, shape code, the shape optimiser's history, the hand
         model's registered shape, the object's volume) -- and then ONE `gf_optimize_hand_pose.optimize_batch` call serves all of
         them: per iteration one evaluation launch over a (candidates, sequence) grid and one update launch with a workgroup per
-        sequence, instead of S times two.  Sequences shorter than the longest sit out once they have ended.  All volumes must
+        sequence, instead of S times two.  (A hand model with MANO entries runs that call in lockstep only with
+        cfg['opt']['lockstep_mano']; without it optimize_batch runs optimize() per sequence.)  Sequences shorter than the longest
+        sit out once they have ended.  All volumes must
         share one resolution, dtype and voxel_scale.  Returns a list of S `ret_dict_lst`, each what `forward` returns for that
         sequence alone on a tracker in this one's state at the call.  Without `use_optimization` it is `forward` per sequence."""
         if not self.use_optimization:

@@ -2,7 +2,11 @@
 route a -- the parent route) against ONE `optimize_batch` of S (route b), on the synthetic hand-object sequences at the
 reference's sizes (5120 candidates x 5 iterations, 778 vertices, 151^3 volume, 640 x 480 mask).
 
-    python scripts/bench_hand_track_batch.py [--sizes 1,2,4,8,16] [--reps 15] [--rounds 3] [--out FILE.md]
+    python scripts/bench_hand_track_batch.py [--sizes 1,2,4,8,16] [--reps 15] [--rounds 3] [--hand_model synthetic_mano] [--out FILE.md]
+
+`--hand_model synthetic_mano` is the hand with MANO's structure: route a is then what `optimize_batch` falls back to without
+`opt.lockstep_mano` (optimize() per sequence on the single MANO kernels), route b the lockstep MANO route with the switch on
+(`ext.hand_pose_mano_opt_batch`; its offsets workspace is S times route a's).
 
 Every S runs in a child process of its own under a time limit (`--limit` seconds); the first child that fails, or runs out of
 time, ends the run -- nothing more is started on the device after it.  Per S and route a repetition is `--steps-total` / S frame
@@ -34,18 +38,20 @@ def child(args, S):
     if not torch.cuda.is_available():
         raise SystemExit("bench_hand_track_batch.py measures on a GPU; none is visible")
     from datasets.synthetic import SyntheticHandObjectSequences
-    from models.hand_model import SyntheticLBSHand
+    from models.hand_model import named_hand_model
     from models.optimization_hand import gf_optimize_hand_pose
 
     dev = torch.device("cuda", 0)
-    hm = SyntheticLBSHand()
+    hm = named_hand_model(args.hand_model)
     cfg = {"device": dev, "num_points": 512, "hand_jitter_cfg": {"rand_scale": 0.004}, "obj_category": ["bottle"], "hand_model": hm,
-           "opt": {"fused_pose": True}}
+           "opt": {"fused_pose": True, "lockstep_mano": True}}
     ds = SyntheticHandObjectSequences(cfg, S, 2)
     opt = gf_optimize_hand_pose(cfg, hand_model=hm, particle_size=args.particles)
     opt.load_volume(ds[0][0]["sdf_volume"], ds[0][0]["voxel_scale"])
     if not opt.use_kernel():
         raise SystemExit("the device-resident route is not available: nothing to compare")
+    if opt._kernel_model()["mano"] != (args.hand_model == "synthetic_mano"):
+        raise SystemExit(f"--hand_model {args.hand_model}: not the kind of skinning tables the name stands for")
     calls = []
     for s in range(S):   # resident inputs: the loader is not what is timed
         f0, f1 = ds[s]
@@ -92,6 +98,7 @@ def child(args, S):
                     res[name][1].append(w)
             round_medians.append((statistics.median(res["a"][0][-args.reps:]), statistics.median(res["a"][1][-args.reps:])))
     row = {"S": S, "steps": steps, "bit_equal": True, "device": torch.cuda.get_device_name(0), "particles": args.particles,
+           "hand_model": args.hand_model, "vertices": opt._kernel_model()["V"],
            "iterations": opt.iteration,
            "a_round_spread_us": {"device": max(m[0] for m in round_medians) - min(m[0] for m in round_medians),
                                  "wall": max(m[1] for m in round_medians) - min(m[1] for m in round_medians)}}
@@ -110,6 +117,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--particles", type=int, default=5120)
+    ap.add_argument("--hand_model", choices=("synthetic", "synthetic_mano"), default="synthetic",
+                    help="synthetic_mano: the per-sequence fallback (a) against the lockstep MANO route (b)")
     ap.add_argument("--limit", type=int, default=240, help="seconds a size may take")
     ap.add_argument("--out", default=None, help="write the table (markdown) here, and the raw figures next to it as .json")
     ap.add_argument("--child", type=int, default=None, help=argparse.SUPPRESS)
@@ -134,8 +143,9 @@ def main():
         return "%.1f (%.1f-%.1f)" % (c["median"], c["q1"], c["q3"])
 
     lines = ["# Lockstep hand tracking: S sequential fused optimize calls against one optimize_batch of S", "",
-             "`python scripts/bench_hand_track_batch.py --sizes %s --steps-total %d --reps %d --rounds %d --warmup %d --particles %d`"
-             % (args.sizes, args.steps_total, args.reps, args.rounds, args.warmup, args.particles), "",
+             "`python scripts/bench_hand_track_batch.py --sizes %s --steps-total %d --reps %d --rounds %d --warmup %d --particles %d%s`"
+             % (args.sizes, args.steps_total, args.reps, args.rounds, args.warmup, args.particles,
+                "" if args.hand_model == "synthetic" else " --hand_model " + args.hand_model), "",
              "Per frame step, microseconds: median (q1-q3) over %d x %d repetitions of max(4, %d / S) steps, routes alternating; %s; "
              "%d candidates x %d iterations." % (args.rounds, args.reps, args.steps_total, rows[0]["device"], rows[0]["particles"],
                                                  rows[0]["iterations"]),
