@@ -6,6 +6,13 @@
 // Definition.  |d|(p) = the exact minimum over all triangles of the distance from p to the triangle's closest point (face, edge
 // or vertex); sign from the generalised winding number w(p) = (1/4pi) sum_f Omega_f(p), Omega_f = 2 atan2(a.(b x c),
 // |a||b||c| + (a.b)|c| + (b.c)|a| + (c.a)|b|) with a, b, c = v - p (Van Oosterom-Strackee); inside (negative) iff w > 0.5.
+// The face region is decided by three edge functions against the unit normal, n . ((end - start) x (p - start)) = |edge| times
+// the distance of p's projection inside that edge's line, each held to a margin of 2^-20 |edge| |p - start|: the rounding of
+// the expression stays below it, so a projection accepted as inside is inside, and one rejected within the margin lies within
+// 2^-20 |p - start| of an edge, where the edge's distance exceeds the plane's by at most that (second order off the plane).
+// The unit normal is built in fp64 by the prepare launch: the fp32 cross product of a sliver's edges keeps eps / sin(angle) of
+// its direction, which tilts the plane by millimetres at sin = 1e-5.  Triangles down to the degeneracy threshold are exact to
+// the same bound as well-shaped ones.
 // A torch composition builds (points x faces) temporaries for every term; here a triangle is a 80-byte record prepared once,
 // a workgroup stages the records through LDS and each thread keeps its query, its running minimum and its running sum of
 // angles in registers.  No triangle is skipped; no atomics: a thread sums its angles in face order, so two runs are bitwise
@@ -22,9 +29,10 @@ constexpr int kMsChunk = 512;      // triangles staged in LDS at a time: 40 KB o
 constexpr int kMsRec = 5;          // float4 per triangle record
 constexpr int kMsHeader = 4;       // floats in front of the records: [0] = bad-face-index flag (int), 16-byte alignment
 constexpr int kMsMaxFaces = 1 << 24, kMsMaxVerts = 1 << 24, kMsMaxRes = 1023;
-// sin^2 of the angle at vertex a below which a triangle counts as degenerate (collinear or repeated vertices): fp32 rounding
-// leaves a cross product of collinear edges at ~1e-14 |e0|^2 |e1|^2, and a sliver this thin is its longest edge to fp32
-constexpr float kMsDegenerate = 1e-12f;
+// sin^2 of the angle at vertex a (in fp64, from the fp32 vertices) at or below which a triangle counts as degenerate (collinear
+// or repeated vertices): a sliver this thin is its longest edge to fp32
+constexpr double kMsDegenerate = 1e-12;
+constexpr double kMsFaceMargin = 0x1p-20;  // 16 half-ulps: above the rounding of an edge function, see the header
 
 __device__ __forceinline__ float ms_dot(float ax, float ay, float az, float bx, float by, float bz) {
     return __builtin_fmaf(az, bz, __builtin_fmaf(ay, by, ax * bx));
@@ -32,8 +40,8 @@ __device__ __forceinline__ float ms_dot(float ax, float ay, float az, float bx, 
 
 // Record of triangle f, 5 float4:
 //   (a, 1/|b-a|^2) (b, 1/|c-b|^2) (c, 1/|a-c|^2)      the reciprocal is 0 for an edge of zero length
-//   (n = (b-a) x (c-a), 1/|n|^2)                       1/|n|^2 = 0 marks a degenerate triangle: no face region, no solid angle
-//   (e0.e0, e0.e1, e1.e1, e0.e0 e1.e1 - (e0.e1)^2)     e0 = b-a, e1 = c-a; the last is -1 for a degenerate triangle
+//   (n / |n|, 1)    n = (b-a) x (c-a) in fp64           (0, 0, 0, 0) marks a degenerate triangle: no face region, no solid angle
+//   (|b-a|, |c-b|, |a-c|, 0) * kMsFaceMargin            the margins of the three edge functions
 // A face index outside [0, nv) sets the flag and the triangle is built from vertex 0 (nothing is read out of bounds).
 __global__ void __launch_bounds__(kMsThreads)
 mesh_sdf_prepare_kernel(int nv, const float *__restrict__ verts, int nf, const int *__restrict__ faces, float *__restrict__ work) {
@@ -50,17 +58,31 @@ mesh_sdf_prepare_kernel(int nv, const float *__restrict__ verts, int nf, const i
     const float e0x = bx - ax, e0y = by - ay, e0z = bz - az;
     const float e1x = cx - ax, e1y = cy - ay, e1z = cz - az;
     const float e2x = cx - bx, e2y = cy - by, e2z = cz - bz;
-    const float d00 = ms_dot(e0x, e0y, e0z, e0x, e0y, e0z), d01 = ms_dot(e0x, e0y, e0z, e1x, e1y, e1z),
-                d11 = ms_dot(e1x, e1y, e1z, e1x, e1y, e1z), d22 = ms_dot(e2x, e2y, e2z, e2x, e2y, e2z);
-    const float nx = e0y * e1z - e0z * e1y, ny = e0z * e1x - e0x * e1z, nz = e0x * e1y - e0y * e1x;
-    const float nn = ms_dot(nx, ny, nz, nx, ny, nz);
-    const bool degenerate = !(nn > kMsDegenerate * d00 * d11);
+    const float d00 = ms_dot(e0x, e0y, e0z, e0x, e0y, e0z), d11 = ms_dot(e1x, e1y, e1z, e1x, e1y, e1z),
+                d22 = ms_dot(e2x, e2y, e2z, e2x, e2y, e2z);
+    // the face's side in fp64: differences of fp32 values are exact there, the cross product is good to 1e-16 / sin(angle)
+    const double f0x = (double)bx - ax, f0y = (double)by - ay, f0z = (double)bz - az;
+    const double f1x = (double)cx - ax, f1y = (double)cy - ay, f1z = (double)cz - az;
+    const double f2x = (double)cx - bx, f2y = (double)cy - by, f2z = (double)cz - bz;
+    const double nx = f0y * f1z - f0z * f1y, ny = f0z * f1x - f0x * f1z, nz = f0x * f1y - f0y * f1x;
+    const double nn = nx * nx + ny * ny + nz * nz, l0 = f0x * f0x + f0y * f0y + f0z * f0z, l1 = f1x * f1x + f1y * f1y + f1z * f1z,
+                 l2 = f2x * f2x + f2y * f2y + f2z * f2z;
+    const bool degenerate = !(nn > kMsDegenerate * l0 * l1);
+    const double inv_n = degenerate ? 0.0 : 1.0 / sqrt(nn);
     float4 *rec = reinterpret_cast<float4 *>(work + kMsHeader) + (size_t)f * kMsRec;
     rec[0] = make_float4(ax, ay, az, d00 > 0.f ? 1.f / d00 : 0.f);
     rec[1] = make_float4(bx, by, bz, d22 > 0.f ? 1.f / d22 : 0.f);
     rec[2] = make_float4(cx, cy, cz, d11 > 0.f ? 1.f / d11 : 0.f);
-    rec[3] = make_float4(nx, ny, nz, degenerate ? 0.f : 1.f / nn);
-    rec[4] = make_float4(d00, d01, d11, degenerate ? -1.f : d00 * d11 - d01 * d01);
+    rec[3] = make_float4((float)(nx * inv_n), (float)(ny * inv_n), (float)(nz * inv_n), degenerate ? 0.f : 1.f);
+    rec[4] = make_float4((float)(sqrt(l0) * kMsFaceMargin), (float)(sqrt(l2) * kMsFaceMargin), (float)(sqrt(l1) * kMsFaceMargin), 0.f);
+}
+
+// n . ((e - s) x q), q = query - s: |e - s| times the distance of the query's projection inside the line s -> e of a triangle
+// with unit normal n (counter-clockwise seen from n)
+__device__ __forceinline__ float ms_edge_fn(float qx, float qy, float qz, float sx, float sy, float sz, float ex, float ey, float ez,
+                                            float nx, float ny, float nz) {
+    const float dx = ex - sx, dy = ey - sy, dz = ez - sz;
+    return ms_dot(nx, ny, nz, dy * qz - dz * qy, dz * qx - dx * qz, dx * qy - dy * qx);
 }
 
 // Squared distance from the query to the segment s -> e, given q = query - s: every edge of every triangle goes through this
@@ -113,18 +135,17 @@ mesh_sdf_kernel(int m, const float *__restrict__ pts, int res, float stride, int
             float d2 = ms_segment(ax, ay, az, A.x, A.y, A.z, B.x, B.y, B.z, A.w);
             d2 = __builtin_fminf(d2, ms_segment(bx, by, bz, B.x, B.y, B.z, C.x, C.y, C.z, B.w));
             d2 = __builtin_fminf(d2, ms_segment(cx, cy, cz, C.x, C.y, C.z, A.x, A.y, A.z, C.w));
-            // the face, where the projection falls inside the triangle (barycentric v, w scaled by the Gram determinant)
-            const float e0x = B.x - A.x, e0y = B.y - A.y, e0z = B.z - A.z, e1x = C.x - A.x, e1y = C.y - A.y, e1z = C.z - A.z;
-            const float d20 = ms_dot(ax, ay, az, e0x, e0y, e0z), d21 = ms_dot(ax, ay, az, e1x, e1y, e1z);
-            const float v = D.z * d20 - D.y * d21, w = D.x * d21 - D.y * d20;
+            const float la = __builtin_sqrtf(ms_dot(ax, ay, az, ax, ay, az)), lb = __builtin_sqrtf(ms_dot(bx, by, bz, bx, by, bz)),
+                        lc = __builtin_sqrtf(ms_dot(cx, cy, cz, cx, cy, cz));
+            // the face, where the projection falls inside all three edges' lines by more than the margin
+            const bool inside = N.w != 0.f && ms_edge_fn(ax, ay, az, A.x, A.y, A.z, B.x, B.y, B.z, N.x, N.y, N.z) >= D.x * la &&
+                                ms_edge_fn(bx, by, bz, B.x, B.y, B.z, C.x, C.y, C.z, N.x, N.y, N.z) >= D.y * lb &&
+                                ms_edge_fn(cx, cy, cz, C.x, C.y, C.z, A.x, A.y, A.z, N.x, N.y, N.z) >= D.z * lc;
             const float nd = ms_dot(ax, ay, az, N.x, N.y, N.z);
-            const float plane2 = nd * nd * N.w;
-            d2 = (v >= 0.f && w >= 0.f && v + w <= D.w) ? __builtin_fminf(d2, plane2) : d2;
+            d2 = inside ? __builtin_fminf(d2, nd * nd) : d2;
             best = __builtin_fminf(best, d2);
             // Van Oosterom-Strackee with (query - vertex) vectors: the dot products are those of (vertex - query), the triple
             // product changes sign
-            const float la = __builtin_sqrtf(ms_dot(ax, ay, az, ax, ay, az)), lb = __builtin_sqrtf(ms_dot(bx, by, bz, bx, by, bz)),
-                        lc = __builtin_sqrtf(ms_dot(cx, cy, cz, cx, cy, cz));
             const float kx = by * cz - bz * cy, ky = bz * cx - bx * cz, kz = bx * cy - by * cx;
             const float num = -ms_dot(ax, ay, az, kx, ky, kz);
             const float den = __builtin_fmaf(ms_dot(cx, cy, cz, ax, ay, az), lb,

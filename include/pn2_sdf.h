@@ -124,8 +124,11 @@ int pn2s_nearest(int b, int n, const float *hand, const float *obj_r, const floa
  * compute the SDF volume from a mesh if we assume the mesh is known"; the reference leaves it commented out because it needs
  * kaolin).  verts (nv,3) fp32; faces (nf,3) int32 vertex indices, closed and outward oriented.
  *   magnitude: the exact minimum over ALL triangles of the distance to the triangle's closest point (face, edge or vertex);
- *              no triangle is culled;
- *   sign:      generalised winding number w = (1/4pi) sum_f Omega_f, Omega_f = 2 atan2(a.(b x c), |a||b||c| + (a.b)|c| +
+ *              no triangle is culled.  The face counts where the query's projection lies inside all three edges' lines,
+ *              n . ((end - start) x (p - start)) >= 2^-20 |end - start| |p - start| with n the unit normal (built in fp64):
+ *              well conditioned for slivers down to the degeneracy threshold below; within the margin the nearest edge stands
+ *              in for the face, at most 2^-20 |p - start| farther;
+ *   sign:     generalised winding number w = (1/4pi) sum_f Omega_f, Omega_f = 2 atan2(a.(b x c), |a||b||c| + (a.b)|c| +
  *              (b.c)|a| + (c.a)|b|), a, b, c = v - p (Van Oosterom-Strackee); negative (inside) iff w > 0.5.  Every query sums its
  *              angles in face order: no atomics, two runs are bitwise equal;
  *   degenerate triangles (a repeated vertex, three collinear vertices: |n|^2 <= 1e-12 |b-a|^2 |c-a|^2) contribute the distance

@@ -23,6 +23,7 @@ import torch
 _said = set()
 CHUNK_FLOATS = 1 << 22  # torch route: elements of one (points x faces) temporary (a dozen are alive at a time)
 DEGENERATE = 1e-12      # |n|^2 <= DEGENERATE |b-a|^2 |c-a|^2: the triangle is a segment or a point (include/pn2_sdf.h)
+FACE_MARGIN_EPS = 8.0   # the face region ends this many eps x |point - vertex| inside each edge's line (fp32: 2^-20, the kernel's)
 
 
 # ---- files ----------------------------------------------------------------------------------------------------------------
@@ -125,6 +126,10 @@ def _sub(a, b):
     return (a[0] - b[0], a[1] - b[1], a[2] - b[2])
 
 
+def _cross(a, b):
+    return (a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0])
+
+
 def _segment(q, s, e, inv_len2):
     """Squared distance to the segment s -> e given q = point - s ((P,1) against (F,) broadcasts)."""
     d = _sub(e, s)
@@ -143,15 +148,22 @@ def signed_distance_torch(points, verts, faces, return_winding: bool = False):
     if int(faces.min()) < 0 or int(faces.max()) >= nv:
         raise ValueError("mesh_sdf: a face index lies outside [0, number of vertices)")
     A, B, C = (tuple(verts[faces[:, k], j] for j in range(3)) for k in range(3))  # per vertex: (x, y, z), each (F,)
-    e0, e1, e2 = _sub(B, A), _sub(C, A), _sub(C, B)
-    d00, d01, d11, d22 = _dot(e0, e0), _dot(e0, e1), _dot(e1, e1), _dot(e2, e2)
-    n = (e0[1] * e1[2] - e0[2] * e1[1], e0[2] * e1[0] - e0[0] * e1[2], e0[0] * e1[1] - e0[1] * e1[0])
-    nn = _dot(n, n)
-    proper = nn > DEGENERATE * d00 * d11
-    zero, one = torch.zeros_like(nn), torch.ones_like(nn)
+    e0, e2, ec = _sub(B, A), _sub(C, B), _sub(A, C)  # the edges a->b, b->c, c->a
+    d00, d11, d22 = _dot(e0, e0), _dot(ec, ec), _dot(e2, e2)
+    zero, one = torch.zeros_like(d00), torch.ones_like(d00)
     inv = lambda x, ok: torch.where(ok, one / torch.where(ok, x, one), zero)
-    il0, il1, il2, inv_nn = inv(d00, d00 > 0), inv(d22, d22 > 0), inv(d11, d11 > 0), inv(nn, proper)
-    gram = torch.where(proper, d00 * d11 - d01 * d01, -one)
+    il0, il1, il2 = inv(d00, d00 > 0), inv(d22, d22 > 0), inv(d11, d11 > 0)
+    # The face's side of the record in float64, as the prepare kernel builds it: the cross product of a sliver's edges cancels
+    # to eps / sin(angle) of its digits, which in the queries' precision would tilt the plane.  unit normal, |edge| * margin.
+    A64, B64, C64 = (tuple(x.double() for x in V) for V in (A, B, C))
+    f0, f1, f2 = _sub(B64, A64), _sub(C64, A64), _sub(C64, B64)
+    n64 = _cross(f0, f1)
+    nn64 = _dot(n64, n64)
+    proper = nn64 > DEGENERATE * _dot(f0, f0) * _dot(f1, f1)
+    scale = torch.where(proper, nn64, torch.ones_like(nn64)).rsqrt()
+    n = tuple((x * scale).to(verts.dtype) for x in n64)
+    margin = FACE_MARGIN_EPS * torch.finfo(verts.dtype).eps
+    k0, k1, k2 = ((_dot(f, f).sqrt() * margin).to(verts.dtype) for f in (f0, f2, f1))
     out = torch.empty(points.shape[0], dtype=points.dtype, device=points.device)
     wn = torch.empty_like(out)
     step = max(1, CHUNK_FLOATS // nf)
@@ -159,14 +171,14 @@ def signed_distance_torch(points, verts, faces, return_winding: bool = False):
         P = tuple(points[p0:p0 + step, j, None] for j in range(3))  # (P,1) each
         a, b, c = _sub(P, A), _sub(P, B), _sub(P, C)                 # point - vertex, (P,F) each
         d2 = torch.minimum(torch.minimum(_segment(a, A, B, il0), _segment(b, B, C, il1)), _segment(c, C, A, il2))
-        d20, d21 = _dot(a, e0), _dot(a, e1)
-        v, w = d11 * d20 - d01 * d21, d00 * d21 - d01 * d20
-        nd = _dot(a, n)
-        inside = (v >= 0) & (w >= 0) & (v + w <= gram)
-        d2 = torch.where(inside, torch.minimum(d2, nd * nd * inv_nn), d2)
         la, lb, lc = _dot(a, a).sqrt(), _dot(b, b).sqrt(), _dot(c, c).sqrt()
-        k = (b[1] * c[2] - b[2] * c[1], b[2] * c[0] - b[0] * c[2], b[0] * c[1] - b[1] * c[0])
-        num = -_dot(a, k)
+        # the face, where the projection falls inside the triangle by more than rounding: n . (edge x (point - start)) is
+        # |edge| times the projection's distance inside that edge's line (include/pn2_sdf.h)
+        inside = (proper & (_dot(n, _cross(e0, a)) >= k0 * la) & (_dot(n, _cross(e2, b)) >= k1 * lb)
+                  & (_dot(n, _cross(ec, c)) >= k2 * lc))
+        nd = _dot(a, n)
+        d2 = torch.where(inside, torch.minimum(d2, nd * nd), d2)
+        num = -_dot(a, _cross(b, c))
         den = la * lb * lc + _dot(a, b) * lc + _dot(b, c) * la + _dot(c, a) * lb
         # a degenerate triangle adds exactly zero, whatever rounding leaves in den (atan2(0, den < 0) would be pi)
         w_p = torch.where(proper, torch.atan2(num, den), zero).sum(dim=1) * (1.0 / (2.0 * math.pi))

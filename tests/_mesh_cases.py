@@ -4,7 +4,8 @@
     SDF; torus and capsule meshes are inscribed tessellations (every vertex on the surface), so their SDF lies within the
     tessellation's sagitta of the analytic one -- `sagitta` measures it on the mesh.
 (b) `oracle`: a float64 numpy brute force of the definition -- the closest point of every triangle by Ericson's region walk
-    (Real-Time Collision Detection 5.1.5; not the edge/face decomposition the kernel and the torch route use), the sign from the
+    (Real-Time Collision Detection 5.1.5; not the edge/face decomposition the kernel and the torch route use; in the face
+    region the distance to the plane, so that a sliver's ill-conditioned weights do not enter), the sign from the
     generalised winding number with the Van Oosterom-Strackee solid angle.  Results are cached per (mesh, query set).
 
 Tolerances (fp32 against float64, measured on the CPU over the three meshes x the 25^3 grid: magnitude within 3.2e-8 m, winding
@@ -150,6 +151,10 @@ def oracle_uncached(points, verts, faces, chunk_elems=1 << 18):
             sv, sw = np.where(cond, cv, sv), np.where(cond, cw, sw)
         r = tuple(ap[k] - ab[k] * sv - ac[k] * sw for k in range(3))
         dd = _d3(r, r)
+        # in the face region the closest point is the projection: the distance to the plane.  The weights' determinants lose
+        # 1e-16 / sin^2 of their digits on a sliver, which slides r along the plane; the regions' sign tests and the normal do not.
+        face = ~functools.reduce(np.logical_or, conds)
+        dd = np.where(face, _d3(ap, nrm) ** 2 / _d3(nrm, nrm), dd)
         if len(g):  # a segment or a point: the nearest of its three (possibly empty) edges
             ag, bg, cg = (tuple(x[:, g] for x in t) for t in (a, b, c))
             dd[:, g] = np.minimum(np.minimum(_segment_dist2(p, ag, bg), _segment_dist2(p, bg, cg)), _segment_dist2(p, cg, ag))
