@@ -55,6 +55,11 @@ struct Smem {
     float *r2;       // h1 (LDH), later conv1's output (LDC)
 };
 
+// dynamic LDS of a launch over `clouds` clouds: r1, r2, rows, both prefix arrays, the scan's [2][256]
+constexpr size_t lds_bytes(int clouds) {
+    return (size_t)64 * (LDX + LDC) * sizeof(float) + (size_t)(64 + 2 * (clouds + 1) + 512) * sizeof(int);
+}
+
 // row e of list `seq` (0 = small-K rows, 1 = large-K-only rows) -> global row index
 __device__ __forceinline__ int lookup(const ChainArgs &A, const Smem &S, int seq, int e) {
     const int *P = seq ? S.p_large : S.p_small;
@@ -285,10 +290,12 @@ extern "C" int pn2x_row_chain(int b, int n, const float *x, int ldx, const int *
     ChainArgs a;
     a.B = b; a.N = n; a.ldx = ldx; a.ldo = ldo; a.x = x; a.list = list; a.counts = counts;
     a.wa = wa; a.ba = ba; a.wb = wb; a.bb = bb; a.wc = wc; a.bc = bc; a.wq = wq; a.out = out;
-    const size_t lds = (size_t)64 * (LDX + LDC) * sizeof(float) + (size_t)(64 + 2 * (b + 1) + 512) * sizeof(int);
+    const size_t lds = lds_bytes(b);
+    // the opt-in is made once per device, so it covers the largest batch the entry accepts, not the first call's
+    static_assert(lds_bytes(MAXB) <= 160 * 1024, "row_chain's LDS at MAXB clouds exceeds a compute unit's 160 KB");
     static PerDeviceOnce raised;
     if (raised.first_use())
-        (void)hipFuncSetAttribute((const void *)row_chain_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute((const void *)row_chain_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(MAXB));
     const int cus = num_compute_units();
     if (grid == 0 || grid > cus) grid = cus;
     hipLaunchKernelGGL(row_chain_kernel, dim3(grid), dim3(256), lds, (hipStream_t)stream, a);
