@@ -50,6 +50,8 @@ def get_config(args, save=True):
         cfg["opt"] = {}
     cfg["opt"].setdefault("fused_pose", False)  # hand-pose particle optimiser on the device-resident route (--fused_hand_pose)
     cfg.setdefault("fused_hand_eval", False)  # tracked hand sequences evaluated in two launches (--fused_hand_eval)
+    cfg.setdefault("hand_interaction_eval", False)  # hand-object penetration / contact columns (--hand_interaction_eval)
+    cfg["opt"].setdefault("contact_threshold", 0.005)  # metres: a fingertip region this near the surface is in contact
     data_cfg = _load("data_config", cfg["data_config"])
     cfg["pointnet"] = {k: _load("pointnet_config", v) for k, v in cfg["pointnet_cfg"].items()}
 

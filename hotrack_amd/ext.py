@@ -1160,26 +1160,27 @@ def hand_pose_rest(model: dict, beta: torch.Tensor = None):
 
 def _hand_pose_setup(model, pre, theta_scale, volume, voxel_scale, weights, posedirs=None) -> _HandPoseSetup:
     """The pn2x_hand_pose_setup record of a call: the model's tables, the candidates, the volumes' type and the weights; for a
-    model with MANO entries also its MANO part (posedirs: a packed table in place of the model's posedirs_pack)."""
+    model with MANO entries also its MANO part (posedirs: a packed table in place of the model's posedirs_pack).  pre / weights
+    None: the record of an entry that reads the model alone (hand_interaction_metrics) -- p = 0, no candidates, zero weights."""
     f32, i32 = torch.float32, torch.int32
     mano = bool(model.get("mano", False))
     if mano and not model.get("mano_ok", False):
         raise ValueError("hand_pose_mano: one vertex serves two keypoints (kp_vertex)")
     V, K, J = model["V"], model["K"], model["J"]
-    if pre.dim() != 2 or pre.shape[1] != 16:
+    if pre is not None and (pre.dim() != 2 or pre.shape[1] != 16):
         raise ValueError(f"hand_pose: pre {tuple(pre.shape)} is not (P, 16)")
-    P = pre.shape[0]
+    P = 0 if pre is None else pre.shape[0]
     if volume.dim() != 3 or len(set(volume.shape)) != 1 or volume.dtype not in (torch.float16, f32):
         raise ValueError(f"hand_pose: volume {tuple(volume.shape)} {volume.dtype} is not a cubic fp16 / fp32 volume")
     res = volume.shape[0]
-    if not hand_pose_opt_supported(P, V, J, K, 10, res):
+    if not hand_pose_opt_supported(1 if pre is None else P, V, J, K, 10, res):
         raise ValueError(f"hand_pose: P = {P}, V = {V}, J = {J}, K = {K}, res = {res} outside 1..8192, 1..1024, 21, 1..4, odd <= 1024")
     s = _HandPoseSetup(p=P, v=V, j=J, k=K, vol_f16=1 if volume.dtype == torch.float16 else 0, res=res,
                        theta_scale=float(theta_scale), voxel_scale=float(voxel_scale))
     s.parents, s.pose_block = _native._ptr(model["parents"], "parents", i32, J), _native._ptr(model["pose_block"], "pose_block", i32, J)
     s.skin_pack, s.skin_w = _native._ptr(model["skin_pack"], "skin_pack", i32, V), _native._ptr(model["skin_w"], "skin_w", f32, V * K)
-    s.comps, s.pre = _native._ptr(model["comps"], "comps", f32, 45 * 45), _native._ptr(pre, "pre", f32, P * 16)
-    for field, key in zip(_HandPoseSetup._WEIGHTS, HAND_POSE_WEIGHTS):
+    s.comps, s.pre = _native._ptr(model["comps"], "comps", f32, 45 * 45), None if pre is None else _native._ptr(pre, "pre", f32, P * 16)
+    for field, key in zip(_HandPoseSetup._WEIGHTS, HAND_POSE_WEIGHTS) if weights is not None else ():
         setattr(s, field, float(weights[key]))
     if mano:
         s.posedirs = _native._ptr(model["posedirs_pack"] if posedirs is None else posedirs, "posedirs", f32, (3 * V + 15) // 16 * 16 * 136)
@@ -1467,6 +1468,77 @@ def hand_seq_metrics(pred_hf: torch.Tensor, init_hf: torch.Tensor, gt_kp: torch.
     if rc < 0:
         _native._check(rc, "hand_seq_metrics")
     return rows, seq, int(rc)
+
+
+# ---- hand-object penetration and contact of tracked hand sequences (include/pn2_ext.h: pn2x_hand_interaction_metrics) -----------
+_lib.pn2x_hand_interaction_metrics.argtypes = [_HP_SETUP, _ci, _ci, _ci] + [_vp] * 11 + [_cf] + [_vp] * 5
+_lib.pn2x_hand_interaction_metrics.restype = _ci
+HAND_INTERACTION_COLS = 8
+
+
+def hand_interaction_metrics(model, global_r: torch.Tensor, global_t: torch.Tensor, theta: torch.Tensor, obj_r: torch.Tensor,
+                             obj_t: torch.Tensor, rest, rest_of: torch.Tensor, volumes, voxel_scale: float, offsets,
+                             contact_threshold: float = 0.005, pred_kp: torch.Tensor = None, seq_off: torch.Tensor = None,
+                             vol_table: torch.Tensor = None, with_geometry: bool = False):
+    """Penetration and contact of F posed hands in S sequences against the sequences' SDF volumes (pn2x_hand_interaction_metrics):
+    model = hand_pose_model(...); global_r (F,3,3), global_t (F,3), theta (F,45), obj_r (F,3,3), obj_t (F,3), pred_kp (F,21,3) or
+    None; rest = (rest_joints (G,21,3), rest_verts (G,V,3)), the G shape tables (hand_pose_rest, stacked), rest_of (F,) int32 the
+    table of each frame; volumes: the S sequences' (res,res,res) fp16 / fp32 volumes (one resolution and dtype; None for a
+    sequence without frames); offsets: the HOST list of S + 1 frame offsets.  seq_off / vol_table: the offsets as an int32 and
+    the volumes' addresses as an int64 device tensor when the caller holds them (a captured graph must: building them is a
+    host-to-device copy).  -> (rows (F,8) and seq (S,8) in metres, mask (bit c: column c is valid), vertices (F,V,3) or None,
+    keypoints (F,21,3) or None).  Two launches, no host sync."""
+    f32, i32 = torch.float32, torch.int32
+    offsets = [int(o) for o in offsets]
+    F, S = global_r.shape[0], len(offsets) - 1
+    if S < 0 or offsets[0] != 0 or offsets[-1] != F or any(b < a for a, b in zip(offsets, offsets[1:])):
+        raise ValueError(f"hand_interaction_metrics: offsets must be non-decreasing from 0 to F = {F}, got {offsets}")
+    if len(volumes) != S:
+        raise ValueError(f"hand_interaction_metrics: {len(volumes)} volumes for {S} sequences")
+    if not float(contact_threshold) >= 0:
+        raise ValueError(f"hand_interaction_metrics: contact_threshold = {contact_threshold}")
+    given = [v for v in volumes if v is not None]
+    for q, (a, b) in enumerate(zip(offsets, offsets[1:])):
+        if b > a and volumes[q] is None:
+            raise ValueError(f"hand_interaction_metrics: sequence {q} has frames and no volume")
+    if not given:
+        raise ValueError("hand_interaction_metrics: volumes holds no volume")
+    for v in given:
+        if v.shape != given[0].shape or v.dtype != given[0].dtype:
+            raise ValueError(f"hand_interaction_metrics: volumes {tuple(given[0].shape)} {given[0].dtype} and {tuple(v.shape)} {v.dtype} "
+                             "differ: a call shares one resolution and dtype")
+    setup = _hand_pose_setup(model, None, 0.0, given[0], voxel_scale, None)
+    dev, V, J = global_r.device, model["V"], model["J"]
+    rest_j, rest_v = rest
+    G = rest_j.shape[0] if rest_j.dim() == 3 else 1
+    # (rest_of is device memory and is not read here: the kernel clamps an index outside [0, G) into it)
+    if seq_off is None:
+        seq_off = torch.tensor(offsets, dtype=i32, device=dev)
+    if vol_table is None:
+        vol_table = torch.tensor([0 if v is None else _native._ptr(v, "volume", v.dtype, setup.res ** 3) for v in volumes],
+                                 dtype=torch.int64, device=dev)
+    args = [_native._ptr(global_r, "global_r", f32, F * 9), _native._ptr(global_t, "global_t", f32, F * 3),
+            _native._ptr(theta, "theta", f32, F * 45), _native._ptr(obj_r, "obj_r", f32, F * 9), _native._ptr(obj_t, "obj_t", f32, F * 3),
+            None if pred_kp is None else _native._ptr(pred_kp, "pred_kp", f32, F * J * 3),
+            _native._ptr(rest_j, "rest_joints", f32, G * J * 3), _native._ptr(rest_v, "rest_verts", f32, G * V * 3),
+            _native._ptr(rest_of, "rest_of", i32, F), _native._ptr(vol_table, "vol_table", torch.int64, S),
+            _native._ptr(seq_off, "seq_off", i32, S + 1)]
+    for t in (global_t, theta, obj_r, obj_t, pred_kp, rest_j, rest_v, rest_of, vol_table, seq_off, *given):
+        if t is not None and t.device != dev:
+            raise ValueError(f"hand_interaction_metrics: tensors on {dev} and {t.device}")
+    rows = torch.empty((F, HAND_INTERACTION_COLS), dtype=f32, device=dev)
+    seq = torch.empty((S, HAND_INTERACTION_COLS), dtype=f32, device=dev)
+    verts = torch.empty((F, V, 3), dtype=f32, device=dev) if with_geometry else None
+    kp = torch.empty((F, J, 3), dtype=f32, device=dev) if with_geometry else None
+    if F == 0 or S == 0:  # nothing to launch (an empty tensor has no address): zero rows per sequence
+        return rows, seq.zero_(), 0xbf | (0x40 if pred_kp is not None else 0), verts, kp
+    with torch.cuda.device(dev):
+        rc = _native._call(_lib.pn2x_hand_interaction_metrics, "hand_interaction_metrics", None, ctypes.byref(setup), F, S, G, *args,
+                           float(contact_threshold), rows.data_ptr(), seq.data_ptr(), None if verts is None else verts.data_ptr(),
+                           None if kp is None else kp.data_ptr(), _native._stream(global_r))
+    if rc < 0:
+        _native._check(rc, "hand_interaction_metrics")
+    return rows, seq, int(rc), verts, kp
 
 
 # ---- hand and object clouds from depth frames (include/pn2_ext.h: pn2x_depth_frame_clouds) --------------------------------------

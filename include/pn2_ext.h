@@ -989,6 +989,53 @@ int pn2x_hand_seq_metrics(int f, int s, int j, int mode, const float *pred_hf, c
                           const float *theta, const float *theta_gt, float *rows, float *seq, void *stream);
 
 /*
+ * Hand-object penetration and contact of tracked hand sequences (hotrack_amd/csrc/hand_interact.hip): the quantities the hand-pose
+ * optimiser minimises (reference optimization_hand.py:264-293) for the hands the tracker ended up with, per frame and per sequence,
+ * in two launches without a host sync.  The definitions are this project's (the reference has no such evaluation).  The f frames
+ * are those of s sequences packed one sequence after the other; seq_off (s + 1) int32 on the device as for pn2x_hand_seq_metrics.
+ * model: the pn2x_hand_pose_setup record (HOST memory, read during the call).  Read: parents, pose_block, skin_pack, skin_w,
+ * posedirs, pose_mean, kp_vertex, v, j, k, vol_f16, res, centre_root, voxel_scale.  Not read: p, pre, comps, theta_scale, the
+ * weights.  Per frame (DEVICE memory): global_r (f,3,3) the root rotation, used as a matrix as the optimiser uses it; global_t
+ * (f,3); theta (f,45) the joint angles (a MANO setup adds pose_mean); obj_r (f,3,3), obj_t (f,3) the object pose; pred_kp (f,21,3)
+ * or NULL; rest_of (f) int32: the shape table the frame is posed with, rest_joints (g,21,3) / rest_verts (g,v,3) being g tables of
+ * rest + beta @ shape_* (a tracker that re-estimates the shape has several per sequence).  vols (s): a device array of the
+ * sequences' volume pointers (res^3 fp16 / fp32, sequences may share one; the entry of a sequence without frames is not read).
+ * hand_interact_rows_kernel, a workgroup per frame, poses the hand with HandModel.lbs_forward_from_tables' semantics (kinematic
+ * chain over parents / pose_block, k <= 4 skinning weights; with posedirs set: pose_mean, the pose blend shapes -- 3 v x 135
+ * multiply-adds on the vector ALUs, column order, no workspace --, kp_vertex fingertips and centre_root), takes every vertex
+ * into the object frame and reads its voxel exactly as pn2s_nearest, the value as fp32, and reduces to rows (f,8):
+ *   0  penetration depth [m]: max of -sdf over the vertices with sdf < 0, else 0
+ *   1  share of vertices with sdf < 0: (float)count / (float)v
+ *   2  1 if column 0 > 0, else 0
+ *   3  number of fingers (0..5) in contact: min of sdf over the finger's tip region <= contact_threshold; the tip regions are
+ *      bits 20..24 of skin_pack (fingers 0..4 of get_attraction_loss); an empty region is not in contact
+ *   4  tip gap [m]: mean over the fingers with a non-empty tip region of max(min sdf over the region, 0), summed in finger
+ *      order; 0 if no finger has one
+ *   5  signed minimum of sdf over all vertices [m]
+ *   6  mean over the 21 keypoints of |posed model keypoint - pred_kp[f]| [m]; 0 and not valid when pred_kp is NULL
+ *   7  1 if column 3 > 0, else 0
+ * hand_interact_reduce_kernel, a workgroup per sequence: seq (s,8) = the mean of the sequence's rows, added in frame order
+ * (fp64); a sequence without frames gets zeros.  out_verts (f,v,3) / out_kp (f,21,3) or NULL: the posed vertices and keypoints
+ * (tests, diagnostics).  No atomics, fixed summation order: run-to-run bitwise equal, and a sequence's values do not depend on
+ * the other sequences of the call.  No host sync or allocation (capturable).
+ * Returns the mask of valid columns (bit c = column c: 0xbf, or 0xff with pred_kp) or a negative code.  Limits as
+ * pn2x_hand_pose_opt_supported for v, j, k, res.  Errors, checked before any device work, PN2_EINVAL before PN2_ERANGE before
+ * PN2_ENULL: PN2_EINVAL for f < 0, s < 0, g < 0 (g < 1 with frames to evaluate), contact_threshold < 0 or NaN, a size of the
+ * record < 1, an even res, voxel_scale <= 0, vol_f16 or centre_root not 0 / 1, a misaligned posedirs (16-byte loads), a record
+ * pointer below 64 KiB (not read); PN2_ERANGE beyond the limits; PN2_ENULL for a NULL record, a NULL table of the record (with
+ * posedirs set: pose_mean, kp_vertex) and, with f > 0 and s > 0, any NULL array but pred_kp, out_verts, out_kp.  f = 0 or s = 0:
+ * the mask, no launch, the arrays are not looked at (a bad record is still refused).  rest_of and seq_off are device memory and
+ * NOT checked: a rest_of outside [0, g) is clamped into it, offsets outside [0, f] are clamped and a non-monotone seq_off gives
+ * that sequence zeros or the wrong frames' mean -- nothing outside the arrays is read; a NULL vols entry of a sequence that has
+ * frames gives those frames zero rows.
+ */
+int pn2x_hand_interaction_metrics(const pn2x_hand_pose_setup *model, int f, int s, int g, const float *global_r, const float *global_t,
+                                  const float *theta, const float *obj_r, const float *obj_t, const float *pred_kp,
+                                  const float *rest_joints, const float *rest_verts, const int *rest_of, const void *const *vols,
+                                  const int *seq_off, float contact_threshold, float *rows, float *seq, float *out_verts,
+                                  float *out_kp, void *stream);
+
+/*
  * Hand and object clouds from depth frames (hotrack_amd/csrc/depth_frame.hip): what the reference's dataset readers do in numpy
  * on the host in front of FPS (datasets/HO3D_dataset.py:66-112, :163-177, DexYCB_dataset.py:76-111) -- back-projection of the valid
  * pixels, the split by segment, the crop to a ball -- for b frames of one size, in two launches over a (tiles, b) grid, a tile

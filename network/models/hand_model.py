@@ -159,7 +159,7 @@ class HandModel(nn.Module):
         return t if ok else None
 
 
-def lbs_forward_from_tables(tables, pose, trans, beta=None):
+def lbs_forward_from_tables(tables, pose, trans, beta=None, root_R=None):
     """vertices (P,V,3), keypoints (P,J,3) of HandModel.skinning_tables() at pose (P, 3 + num_pose) = [global axis-angle | joint
     angles], trans (P,3) and, for a model with a shape space, beta (P|1, D) -- in pose's dtype, on pose's device:
         rest = rest_* + beta @ shape_*;  R_0 = rodrigues(pose[:, :3]), t_0 = rest_joints[0];
@@ -167,7 +167,9 @@ def lbs_forward_from_tables(tables, pose, trans, beta=None):
         v = sum_k w_k (R_k (rest_v - rest_k) + t_k) + trans;  keypoints = t_j + trans.
     With the optional entries: the joint angles have pose_mean added, rest_v has posedirs . vec(R_b - I) added (after the shape
     term, before the skinning), keypoint j with kp_vertex[j] >= 0 is that skinned vertex, and with centre_root keypoint 0 is
-    subtracted from vertices and keypoints before trans is added."""
+    subtracted from vertices and keypoints before trans is added.
+    root_R (P,3,3): the root's rotation as a matrix, used in place of rodrigues(pose[:, :3]) (which is then not read) -- the way
+    the pose optimiser carries it."""
     dt, dev, P = pose.dtype, pose.device, pose.shape[0]
     T = lambda k: tables[k].to(dev)
     parents, block = [int(v) for v in tables["parents"]], [int(v) for v in tables["pose_block"]]
@@ -181,7 +183,7 @@ def lbs_forward_from_tables(tables, pose, trans, beta=None):
     if "posedirs" in tables:
         feat = (Rl - torch.eye(3, dtype=dt, device=dev)).reshape(P, -1)
         verts = verts + torch.einsum("vcf,pf->pvc", T("posedirs").to(dt), feat)
-    R_w, t_w = [rodrigues(pose[:, :3])], [rest[:, 0].expand(P, 3)]
+    R_w, t_w = [rodrigues(pose[:, :3]) if root_R is None else root_R.to(dev, dt)], [rest[:, 0].expand(P, 3)]
     for j in range(1, len(parents)):
         pa = parents[j]
         t_w.append(t_w[pa] + (R_w[pa] @ (rest[:, j] - rest[:, pa])[..., None]).squeeze(-1))

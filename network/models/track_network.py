@@ -61,6 +61,11 @@ class HandTrackModel(nn.Module):
         self.sym = cfg.get("obj_sym", -1)  # rot_diff_rad's symmetry mode for the obj_pred_* metrics (compute_loss)
         # compute_loss through compute_loss_batch: every frame's dictionary from two launches (eval_metrics.hand_sequence_metrics)
         self.fused_hand_eval = bool(cfg.get("fused_hand_eval", False))
+        # compute_loss / compute_loss_batch also report how the tracked hands sit against the object (eval_metrics.hand_interaction_metrics:
+        # penetration depth and share, fingers in contact, tip gap); contact_threshold [m] is a choice, not a measurement
+        self.hand_interaction_eval = bool(cfg.get("hand_interaction_eval", False))
+        self.contact_threshold = float((cfg.get("opt") or {}).get("contact_threshold", 0.005))
+        self.__dict__["_interaction_hand"] = hand_model  # (not a submodule of this one: the optimiser / IKNet own it)
         self.optimizer = None
         if self.use_optimization:
             from .optimization_hand import gf_optimize_hand_pose
@@ -352,17 +357,126 @@ class HandTrackModel(nn.Module):
         ret["raw_quat"], ret["MANO_theta"], ret["global_pose"] = raw, theta, canon
         return theta, canon
 
-    def compute_loss(self, input, ret_dict_lst, flag_dict):
+    _said_interaction = set()
+
+    def _interaction_volume(self, frame0, built):
+        """The SDF volume forward() / forward_batch() load for a sequence whose first frame is `frame0` -> (volume on the device,
+        voxel_scale), or (None, None).  `built` maps id(volume tensor) to its device copy: sequences that hand over one tensor
+        share it."""
+        opt = self.optimizer
+        size, scale0 = (opt.volume_size, opt.voxel_scale) if opt is not None else (151, 0.003)
+        if "sdf_volume" in frame0:
+            src = frame0["sdf_volume"]
+            if id(src) not in built:
+                built[id(src)] = (src, src.to(self.device).contiguous())
+            scale = frame0.get("voxel_scale")
+            return built[id(src)][1], scale0 if scale is None else float(scale)
+        from . import mesh_sdf
+        scale = float(frame0.get("voxel_scale", scale0))
+        vol = mesh_sdf.frame_volume(frame0, size, scale, self.device)
+        if vol is not None:
+            return vol, scale
+        if opt is not None and opt.sdf_volume is not None:  # (as forward: the volume loaded last stays)
+            return opt.sdf_volume, opt.voxel_scale
+        return None, None
+
+    def _interaction_enqueue(self, inputs, ret_dict_lsts):
+        """The hand-object interaction columns of S tracked sequences, enqueued on the device: [(members, keys, seq (len(members), 8))]
+        per group of sequences whose volumes share resolution, dtype and voxel_scale (a tracker's sequences usually all do: one
+        eval_metrics.hand_interaction_metrics call, two launches).  Nothing is read back here.  [] with the reason printed once
+        when the hand model has no skinning tables, a result lacks MANO_theta / global_pose, or a volume cannot be resolved.  The
+        object pose of a frame is the one the optimiser used (pred_obj_pose with use_pred_obj_pose, else gt_obj_pose), the shape
+        the frame's pred_beta (else the hand model's registered shape)."""
+        from . import eval_metrics
+
+        def skip(why):
+            if why not in HandTrackModel._said_interaction:
+                HandTrackModel._said_interaction.add(why)
+                print("[Hand Tracking] hand_interaction_eval: the hand_pen_* / hand_contact_* columns are left out (%s)" % why)
+            return []
+        hm = self.__dict__.get("_interaction_hand")
+        tables = hm.skinning_tables() if hm is not None and hasattr(hm, "skinning_tables") else None
+        if tables is None:
+            return skip("no hand model" if hm is None else "the hand model has no skinning tables (HandModel.skinning_tables() is None)")
+        obj_pose = lambda d: d["pred_obj_pose"] if (self.use_pred_obj_pose and "pred_obj_pose" in d) else d.get("gt_obj_pose")
+        for seq, rets in zip(inputs, ret_dict_lsts):
+            if len(seq) != len(rets):
+                return skip("a sequence and its results differ in length")
+            if any("MANO_theta" not in r or "global_pose" not in r for r in rets):
+                return skip("the results carry no MANO_theta / global_pose (neither IKNet nor the pose optimiser ran)")
+            if any(obj_pose(d) is None for d in seq):
+                return skip("a frame carries no object pose")
+        built, groups = {}, {}
+        for k, seq in enumerate(inputs):
+            if not len(seq):
+                continue
+            vol, scale = self._interaction_volume(seq[0], built)
+            if vol is None:
+                return skip("a sequence's SDF volume cannot be resolved: no 'sdf_volume' and no mesh in its first frame")
+            groups.setdefault((tuple(vol.shape), vol.dtype, scale), []).append((k, vol))
+        dev, D = self.device, int(getattr(hm, "num_betas", 0)) if "shape_joints" in tables else 0
+        f = lambda x, *shape: torch.as_tensor(x).to(dev).float().reshape(1, *shape)
+        out = []
+        for (_, _, scale), members in groups.items():
+            data = [d for k, _ in members for d in inputs[k]]
+            rets = [r for k, _ in members for r in ret_dict_lsts[k]]
+            offsets = [0]
+            for k, _ in members:
+                offsets.append(offsets[-1] + len(inputs[k]))
+            poses = [obj_pose(d) for d in data]
+            frames = {"MANO_theta": torch.cat([f(r["MANO_theta"], 45) for r in rets]),
+                      "global_rotation": torch.cat([f(r["global_pose"]["rotation"], 3, 3) for r in rets]),
+                      "global_translation": torch.cat([f(r["global_pose"]["translation"], 3) for r in rets]),
+                      "obj_rotation": torch.cat([f(p["rotation"], 3, 3) for p in poses]),
+                      "obj_translation": torch.cat([f(p["translation"], 3) for p in poses])}
+            if all("pred_kp" in r and tuple(r["pred_kp"].shape[-2:]) == (21, 3) and r["pred_kp"].numel() == 63 for r in rets):
+                frames["pred_kp"] = torch.cat([f(r["pred_kp"], 21, 3) for r in rets])
+            if D > 0:  # the shape tables: one per distinct shape code (a re-estimated shape: several per sequence)
+                codes, index, rest_of = [], {}, []
+                for r in rets:
+                    b = r.get("pred_beta")
+                    b = getattr(hm, "registered_beta", None) if b is None else b
+                    key = id(b)
+                    if key not in index:
+                        index[key] = len(codes)
+                        codes.append(torch.zeros((1, D), device=dev) if b is None else f(b, D))
+                    rest_of.append(index[key])
+                frames["beta"], frames["rest_of"] = torch.cat(codes), torch.tensor(rest_of, dtype=torch.long, device=dev)
+            _, seq, keys = eval_metrics.hand_interaction_metrics(frames, offsets, tables, [v for _, v in members], scale,
+                                                                 contact_threshold=self.contact_threshold)
+            out.append(([k for k, _ in members], keys, seq.float()))
+        return out
+
+    def hand_interaction_losses(self, inputs, ret_dict_lsts):
+        """[{the eight hand-object interaction keys}] per sequence (empty where they are left out): one call for all sequences,
+        one read-back."""
+        from . import eval_metrics
+        outs = [dict() for _ in inputs]
+        parts = self._interaction_enqueue(inputs, ret_dict_lsts) if self.hand_interaction_eval else []
+        host = torch.cat([seq.reshape(-1) for _, _, seq in parts]).cpu() if parts else torch.zeros(0)
+        at = 0
+        for members, keys, seq in parts:
+            table = host[at:at + seq.numel()].reshape(len(members), -1).tolist()
+            at += seq.numel()
+            cols = [eval_metrics.HAND_INTERACTION_KEYS.index(k) for k in keys]
+            for j, k in enumerate(members):
+                outs[k].update((key, table[j][c]) for key, c in zip(keys, cols))
+        return outs
+
+    def compute_loss(self, input, ret_dict_lst, flag_dict, interaction=True):
         """HandTrackNet's loss / metric dictionary averaged over the frames.  With `use_pred_obj_pose` and frames that carry
         `pred_obj_pose`, also the reference's object-pose block (track_network.py:244-251): `obj_pred_tdiff_0`,
         `obj_pred_rdiff_0`, `obj_pred_5deg5cm_0`, `obj_pred_10deg10cm_0` of the supplied object poses against gt_obj_pose
         (eval_metrics.eval_part_full: one launch for the whole sequence, enqueued ahead of the single read-back).
-        With cfg['fused_hand_eval'] (`--fused_hand_eval`) it is compute_loss_batch of this one sequence instead."""
+        With cfg['fused_hand_eval'] (`--fused_hand_eval`) it is compute_loss_batch of this one sequence instead.
+        With cfg['hand_interaction_eval'] (`--hand_interaction_eval`) the eight eval_metrics.HAND_INTERACTION_KEYS are added (see
+        _interaction_enqueue for when they are left out); interaction=False leaves them to the caller (Trainer.test_batch asks
+        for all its sequences at once)."""
         if self.fused_hand_eval:
-            return self.compute_loss_batch([input], [ret_dict_lst], flag_dict)[0]
-        return self._compute_loss_frames(input, ret_dict_lst, flag_dict)
+            return self.compute_loss_batch([input], [ret_dict_lst], flag_dict, interaction=interaction)[0]
+        return self._compute_loss_frames(input, ret_dict_lst, flag_dict, interaction=interaction)
 
-    def _compute_loss_frames(self, input, ret_dict_lst, flag_dict):
+    def _compute_loss_frames(self, input, ret_dict_lst, flag_dict, interaction=True):
         total = {}
         for data, ret in zip(input, ret_dict_lst):
             loss, _ = self.handnet.compute_loss(data, ret, flag_dict)
@@ -375,9 +489,12 @@ class HandTrackModel(nn.Module):
                                               _stack_poses([d["pred_obj_pose"] for d in input], self.device), axis=int(self.sym),
                                               up_and_down_sym=_up_and_down_sym(input[0]["gt_obj_pose"]))
             obj = torch.stack([err[k] for k in eval_metrics.METRIC_KEYS])
+        inter = self.hand_interaction_eval and interaction and len(input)
+        extra = self.hand_interaction_losses([input], [ret_dict_lst])[0] if inter else {}
         out = {k: float(v) / len(input) for k, v in total.items()}
         if obj is not None:
             out.update({"obj_pred_" + k: v for k, v in zip(eval_metrics.METRIC_KEYS, obj.tolist())})
+        out.update(extra)
         return out, ret_dict_lst
 
     _said_eval = set()
@@ -394,7 +511,7 @@ class HandTrackModel(nn.Module):
                     return "it needs one hand of 21 keypoints per frame, got pred_kp %s" % (tuple(r["pred_kp"].shape),)
         return None
 
-    def compute_loss_batch(self, inputs, ret_dict_lsts, flag_dict):
+    def compute_loss_batch(self, inputs, ret_dict_lsts, flag_dict, interaction=True):
         """`compute_loss` for S tracked sequences at once, on the reference's rule (track_network.py:228-307): every frame of every
         sequence is stacked, ONE eval_metrics.hand_sequence_metrics call (two launches on the GPU) gives the per-frame and the
         per-sequence values, the `obj_pred_*` block is enqueued as in compute_loss, and one read-back brings everything to the
@@ -412,7 +529,7 @@ class HandTrackModel(nn.Module):
             if why not in HandTrackModel._said_eval:
                 HandTrackModel._said_eval.add(why)
                 print("[Hand Tracking] fused_hand_eval: the per-frame evaluation runs (%s)" % why)
-            return [self._compute_loss_frames(seq, rets, flag_dict) for seq, rets in zip(inputs, ret_dict_lsts)]
+            return [self._compute_loss_frames(seq, rets, flag_dict, interaction=interaction) for seq, rets in zip(inputs, ret_dict_lsts)]
         dev, save = self.device, bool(flag_dict.get("save_flag"))
         f = lambda x: x.to(dev).float()
         S = len(inputs)
@@ -475,12 +592,16 @@ class HandTrackModel(nn.Module):
                                                   up_and_down_sym=_up_and_down_sym(seq_in[0]["gt_obj_pose"]))
                 pieces.append(torch.stack([err[key] for key in eval_metrics.METRIC_KEYS]).float())
                 layout.append(("obj", k, len(eval_metrics.METRIC_KEYS)))
+        # the hand-object interaction columns (cfg['hand_interaction_eval']): enqueued here, read back with everything else
+        for members, keys, seq in (self._interaction_enqueue(inputs, ret_dict_lsts) if self.hand_interaction_eval and interaction else ()):
+            pieces.append(seq.reshape(-1))
+            layout.append(("interaction", (members, keys, [eval_metrics.HAND_INTERACTION_KEYS.index(k) for k in keys]), seq.numel()))
         host = torch.cat(pieces).cpu() if pieces else torch.zeros(0)  # the one read-back
         outs, at = [dict() for _ in range(S)], 0
         for what, info, n in layout:
             part = host[at:at + n]
             at += n
-            if what == "seq":
+            if what in ("seq", "interaction"):
                 members, keys, cols = info
                 table = part.reshape(len(members), -1).tolist()
                 for j, k in enumerate(members):

@@ -44,6 +44,12 @@ def add_args(parser):
                         help="track=hand / hand_IKNet: evaluate the tracked sequences through HandTrackModel.compute_loss_batch (every "
                              "frame's metrics from two launches, hotrack_amd/csrc/kabsch.hip; adds MANO_theta_diff and the per-frame "
                              "error table; the hand_init_* keys are then the first frame's value, as in the reference, not the mean)")
+    parser.add_argument("--hand_interaction_eval", dest="hand_interaction_eval", action="store_const", const=True, default=None,
+                        help="track=hand_IKNet with a hand model: also report how the tracked hands sit against the object -- "
+                             "hand_pen_depth(mm), hand_pen_ratio, hand_pen_frames, hand_contact_fingers, hand_tip_gap(mm), "
+                             "hand_obj_min_sdf(mm), hand_model_kp_diff, hand_contact_frames -- from the tracked MANO_theta / global_pose, "
+                             "the object pose the optimiser used and the sequence's SDF volume (two launches per evaluation, "
+                             "hotrack_amd/csrc/hand_interact.hip; the contact distance is opt.contact_threshold, default 0.005 m)")
     parser.add_argument("--obj_mesh", type=str, default=None,
                         help="track the synthetic sequences' clouds against an SDF volume built from this triangle mesh (OBJ or "
                              "PLY, object frame, metres; models/mesh_sdf.py) instead of the analytic capsule volume")

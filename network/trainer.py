@@ -797,7 +797,8 @@ class Trainer(nn.Module):
     def test_batch(self, datas, save_flag=False):
         """`test` for a list of sequences tracked in lockstep (the object tracker, `--seq_batch`, and the hand trackers, whose
         batched pose optimiser is reached through this API only): one forward_batch for all of them, then compute_loss per
-        sequence.  Returns a list of (loss_dict, ret), one per sequence, equal to `test` on each."""
+        sequence.  Returns a list of (loss_dict, ret), one per sequence, equal to `test` on each.  With `hand_interaction_eval`
+        the hand trackers' hand-object interaction columns of all sequences come from one call (two launches, one read-back)."""
         if not hasattr(self.model, "forward_batch"):
             raise NotImplementedError("test_batch: track=%s has no lockstep route (obj_opt and the hand trackers have)" % self.cfg["track"])
         flags = self.init_flag_dict()
@@ -807,6 +808,11 @@ class Trainer(nn.Module):
             rets = self.model.forward_batch(datas, flags)
             if self.cfg.get("fused_hand_eval") and hasattr(self.model, "compute_loss_batch"):  # all sequences, two launches
                 return self.model.compute_loss_batch(datas, rets, flags)
+            if getattr(self.model, "hand_interaction_eval", False) and hasattr(self.model, "hand_interaction_losses"):
+                out = [self.model.compute_loss(data, ret, flags, interaction=False) for data, ret in zip(datas, rets)]
+                for (loss, _), extra in zip(out, self.model.hand_interaction_losses(datas, rets)):
+                    loss.update(extra)
+                return out
             return [self.model.compute_loss(data, ret, flags) for data, ret in zip(datas, rets)]
 
 
