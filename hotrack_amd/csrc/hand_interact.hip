@@ -17,12 +17,13 @@
 //   wave 0      the 21 keypoints (joints, or a MANO hand's fingertip vertices, left in LDS by their owner threads) against pred_kp.
 // hand_interact_reduce_kernel.  One workgroup per sequence: lane c sums column c of the sequence's rows in frame order (fp64).
 //
-// The posing arithmetic is this file's own statement of HandModel.lbs_forward_from_tables in the order hand_pose.hip uses
-// (v_rest - j_k [+ offset], fma(R2, e2, fma(R1, e1, R0 e0)) + t, weights in index order); fp32 throughout.
-#include <hip/hip_fp16.h>
-
-#include <cstdint>
-
+// The posing arithmetic is hand_lbs.h, shared with hand_pose.hip (HandModel.lbs_forward_from_tables: v_rest - j_k [+ offset],
+// fma(R2, e2, fma(R1, e1, R0 e0)) + t, weights in index order; fp32 throughout), and the lookup is sdf_device.h's: a frame whose
+// pose is an optimiser's candidate gets that candidate's vertices and keypoints bit for bit
+// (tests/test_gpu_hand_pose_interact_bits.py).  What differs is how the pose-blend offset is formed (above): with a non-zero
+// posedirs table a MANO-structured hand agrees with the optimiser's to rounding, not to the bit.
+#include "hand_check.h"
+#include "hand_lbs.h"
 #include "pn2_common.h"
 #include "sdf_device.h"
 #include "../../include/pn2_ext.h"
@@ -30,7 +31,9 @@
 namespace pn2 {
 namespace hinter {
 
-constexpr int NJ = 21, MAXK = 4, NPOSE = 45, NB = NPOSE / 3, NF = 9 * NB, KP = NF + 1, COLS = 8, T = 256, W = T / 64;
+using namespace lbs;
+
+constexpr int COLS = 8, T = 256, W = T / 64;
 
 struct Args {
     int F, S, G, V, K, res, centre, mano;
@@ -42,22 +45,6 @@ struct Args {
     float voxel_scale, contact;
     float *rows, *out_verts, *out_kp;
 };
-
-// hand_model.rodrigues: I + sin K + (1 - cos) K K with K the cross-product matrix of aa / max(|aa|, 1e-12)
-__device__ __forceinline__ void rodrigues(float ax, float ay, float az, float *R) {
-    const float n = fmaxf(sqrtf(ax * ax + ay * ay + az * az), 1e-12f);
-    const float kx = ax / n, ky = ay / n, kz = az / n;
-    const float s = sinf(n), oc = 1.0f - cosf(n);
-    R[0] = 1.0f + oc * (-(kz * kz) - ky * ky);  R[1] = s * -kz + oc * (kx * ky);            R[2] = s * ky + oc * (kx * kz);
-    R[3] = s * kz + oc * (kx * ky);            R[4] = 1.0f + oc * (-(kz * kz) - kx * kx);  R[5] = s * -kx + oc * (ky * kz);
-    R[6] = s * -ky + oc * (kx * kz);           R[7] = s * kx + oc * (ky * kz);             R[8] = 1.0f + oc * (-(ky * ky) - kx * kx);
-}
-
-__device__ __forceinline__ float wave_sum_xor(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
 
 // a pose block's angles: theta (+ pose_mean for a MANO hand, as the model's forward() adds it)
 __device__ __forceinline__ void block_angles(const Args &A, const float *theta, int b, float *th) {
@@ -104,51 +91,14 @@ __global__ void __launch_bounds__(T) hand_interact_rows_kernel(const Args A) {
     float t[3] = {0.f, 0.f, 0.f};  // wave 0, lane j: joint j's posed position
     if (wave == 0) {
         // ---- skeleton (lanes >= 21 carry joint 0 and write nothing) -----------------------------------------------------------------
-        const bool is_joint = lane < NJ;
-        const int j = is_joint ? lane : 0;
-        const int pa = j == 0 ? 0 : min(max(A.parents[j], 0), j - 1);
-        int blk = A.pose_block[j];
-        if (blk < 0 || blk >= NB || j == 0) blk = -1;
-        int depth = 0;
-        for (int s = 0, c = j; s < NJ; ++s)
-            if (c != 0) {
-                c = min(max(A.parents[c], 0), c - 1);
-                ++depth;
-            }
-        int maxdepth = depth;
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) maxdepth = max(maxdepth, __shfl_xor(maxdepth, m, 64));
+        const Joint J = lane_joint(A.parents, A.pose_block, lane);
         float off[3], th[3] = {0.f, 0.f, 0.f}, Rl[9], R[9];
 #pragma unroll
-        for (int a = 0; a < 3; ++a) off[a] = rest_j[3 * j + a] - rest_j[3 * pa + a];
-        if (blk >= 0) block_angles(A, theta, blk, th);
+        for (int a = 0; a < 3; ++a) off[a] = rest_j[3 * J.j + a] - rest_j[3 * J.pa + a];
+        if (J.blk >= 0) block_angles(A, theta, J.blk, th);
         rodrigues(th[0], th[1], th[2], Rl);
-#pragma unroll
-        for (int k = 0; k < 9; ++k) R[k] = A.global_r[(size_t)f * 9 + k];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) t[k] = rest_j[k];
-        for (int lvl = 1; lvl <= maxdepth; ++lvl) {
-            float pR[9], pt[3];
-#pragma unroll
-            for (int k = 0; k < 9; ++k) pR[k] = __shfl(R[k], pa, 64);
-#pragma unroll
-            for (int k = 0; k < 3; ++k) pt[k] = __shfl(t[k], pa, 64);
-            if (depth == lvl) {
-#pragma unroll
-                for (int k = 0; k < 3; ++k)
-                    t[k] = pt[k] + fmaf(pR[3 * k + 2], off[2], fmaf(pR[3 * k + 1], off[1], pR[3 * k] * off[0]));
-                if (blk >= 0) mat3_mul(pR, Rl, R);
-                else {
-#pragma unroll
-                    for (int k = 0; k < 9; ++k) R[k] = pR[k];
-                }
-            }
-        }
-        if (is_joint) {
-            skel[3 * j] = make_float4(R[0], R[1], R[2], R[3]);
-            skel[3 * j + 1] = make_float4(R[4], R[5], R[6], R[7]);
-            skel[3 * j + 2] = make_float4(R[8], t[0], t[1], t[2]);
-        }
+        chain(J, Rl, off, A.global_r + (size_t)f * 9, rest_j, R, t);
+        store_joint(skel, J, R, t);
     } else if (wave == 1) {
         // ---- a MANO hand's pose features: the skeleton's own angle and Rodrigues functions, minus the identity ------------------------
         float *feat = reinterpret_cast<float *>(feat4);
@@ -156,8 +106,7 @@ __global__ void __launch_bounds__(T) hand_interact_rows_kernel(const Args A) {
             float th[3], R[9];
             block_angles(A, theta, lane, th);
             rodrigues(th[0], th[1], th[2], R);
-#pragma unroll
-            for (int k = 0; k < 9; ++k) feat[9 * lane + k] = R[k] - ((k & 3) == 0 ? 1.f : 0.f);
+            pose_features(R, feat + 9 * lane);
         }
         if (lane == NB) feat[NF] = 0.f;
     } else if (wave == 2) {
@@ -185,42 +134,21 @@ __global__ void __launch_bounds__(T) hand_interact_rows_kernel(const Args A) {
                 bz = fmaf(d.w, x.w, fmaf(d.z, x.z, fmaf(d.y, x.y, fmaf(d.x, x.x, bz))));
             }
         }
-        float x = 0.f, y = 0.f, z = 0.f;
-#pragma unroll
-        for (int k = 0; k < MAXK; ++k)
-            if (k < K) {
-                const int jn = min((p >> (5 * k)) & 31, NJ - 1);
-                const float4 rj = restj[jn];
-                float ex = vx - rj.x, ey = vy - rj.y, ez = vz - rj.z;
-                if (A.mano) {
-                    ex += bx; ey += by; ez += bz;
-                }
-                const float w = A.skin_w[(size_t)v * K + k];
-                const float4 a = skel[3 * jn], b = skel[3 * jn + 1], d = skel[3 * jn + 2];
-                const float qx = fmaf(a.z, ez, fmaf(a.y, ey, a.x * ex)) + d.y;
-                const float qy = fmaf(b.y, ez, fmaf(b.x, ey, a.w * ex)) + d.z;
-                const float qz = fmaf(d.x, ez, fmaf(b.w, ey, b.z * ex)) + d.w;
-                x = k == 0 ? qx * w : fmaf(qx, w, x);
-                y = k == 0 ? qy * w : fmaf(qy, w, y);
-                z = k == 0 ? qz * w : fmaf(qz, w, z);
-            }
+        float x, y, z;
+        skin_vertex(p, K, skel, A.mano, bx, by, bz, [&](int k, int jn) {
+            const float4 rj = restj[jn];
+            return make_float4(vx - rj.x, vy - rj.y, vz - rj.z, A.skin_w[(size_t)v * K + k]);
+        }, x, y, z);
+        place(A.mano, cen, tr, x, y, z);
         if (A.mano) {
-            x = (x - cen[0]) + tr[0]; y = (y - cen[1]) + tr[1]; z = (z - cen[2]) + tr[2];
-            const int kj = min((p >> 25) & 31, NJ - 1);  // the keypoint this vertex is (0: none)
+            const int kj = keypoint_of(p);  // the keypoint this vertex is (0: none)
             if (kj != 0) kpv[kj] = make_float4(x, y, z, 0.f);
-        } else {
-            x += tr[0]; y += tr[1]; z += tr[2];
         }
         if (A.out_verts) {
             float *o = A.out_verts + ((size_t)f * V + v) * 3;
             o[0] = x; o[1] = y; o[2] = z;
         }
-        float ox, oy, oz;
-        to_object_frame(x, y, z, ot, oR, ox, oy, oz);
-        const int flat = nearest_voxel(ox, oy, oz, A.voxel_scale, A.res);
-        float s;
-        if constexpr (F16) s = __half2float(reinterpret_cast<const __half *>(vol)[flat]);
-        else s = reinterpret_cast<const float *>(vol)[flat];
+        const float s = sdf_nearest<F16>(vol, x, y, z, ot, oR, A.voxel_scale, A.res);
         if (s < 0.f) {
             pen = fmaxf(pen, -s);
             ++count;
@@ -255,10 +183,9 @@ __global__ void __launch_bounds__(T) hand_interact_rows_kernel(const Args A) {
     // ---- keypoints: joint positions, or a MANO hand's fingertip vertices; centred as the vertices are ----------------------------------
     const bool is_joint = lane < NJ;
     const int j = is_joint ? lane : 0;
-    float kx = (t[0] - cen[0]) + tr[0], ky = (t[1] - cen[1]) + tr[1], kz = (t[2] - cen[2]) + tr[2];
-    if (!A.mano) {
-        kx = t[0] + tr[0]; ky = t[1] + tr[1]; kz = t[2] + tr[2];
-    } else if (A.kp_vertex[j] >= 0) {
+    float kx = t[0], ky = t[1], kz = t[2];
+    place(A.mano, cen, tr, kx, ky, kz);
+    if (A.mano && A.kp_vertex[j] >= 0) {
         const float4 d = kpv[j];
         kx = d.x; ky = d.y; kz = d.z;
     }
@@ -330,29 +257,17 @@ extern "C" int pn2x_hand_interaction_metrics(const pn2x_hand_pose_setup *model, 
                                              const float *pred_kp, const float *rest_joints, const float *rest_verts, const int *rest_of,
                                              const void *const *vols, const int *seq_off, float contact_threshold, float *rows,
                                              float *seq, float *out_verts, float *out_kp, void *stream) {
-    // a bad value before a limit before a NULL pointer, whichever check finds it
-    bool inval = f < 0 || s < 0 || g < 0 || !(contact_threshold >= 0.f), range = false, null = false;
+    Faults bad;
     const bool work = f > 0 && s > 0;
-    inval |= work && g < 1;
-    const bool readable = (uintptr_t)model >= 65536;  // nothing is mapped below 64 KiB: such a "record" is not read
-    if (!readable) (model ? inval : null) = true;
-    else {
-        const pn2x_hand_pose_setup &m = *model;
-        inval |= m.v < 1 || m.j < 1 || m.k < 1 || m.res < 1 || (m.res & 1) == 0 || !(m.voxel_scale > 0.f) ||
-                 (m.vol_f16 != 0 && m.vol_f16 != 1);
-        range |= !pn2x_hand_pose_opt_supported(1, m.v, m.j, m.k, 10, m.res);
-        null |= !m.parents || !m.pose_block || !m.skin_pack || !m.skin_w;
-        if (m.posedirs) {  // the MANO part; posedirs is read by 16-byte loads
-            inval |= (m.centre_root != 0 && m.centre_root != 1) || ((uintptr_t)m.posedirs & 15);
-            null |= !m.pose_mean || !m.kp_vertex;
-        }
+    bad.inval = f < 0 || s < 0 || g < 0 || !(contact_threshold >= 0.f) || (work && g < 1);
+    if (is_record(model, bad)) {
+        check_hand_model(*model, bad);
+        bad.range |= !pn2x_hand_pose_opt_supported(1, model->v, model->j, model->k, 10, model->res);
     }
     if (work)
-        null |= !global_r || !global_t || !theta || !obj_r || !obj_t || !rest_joints || !rest_verts || !rest_of || !vols || !seq_off ||
-                !rows || !seq;
-    if (inval) return PN2_EINVAL;
-    if (range) return PN2_ERANGE;
-    if (null) return PN2_ENULL;
+        bad.null |= !global_r || !global_t || !theta || !obj_r || !obj_t || !rest_joints || !rest_verts || !rest_of || !vols ||
+                    !seq_off || !rows || !seq;
+    if (bad.code() != PN2_OK) return bad.code();
     const int mask = 0xbf | (pred_kp ? 0x40 : 0);  // columns 0-5 and 7, and 6 with pred_kp
     if (!work) return mask;
     const pn2x_hand_pose_setup &m = *model;

@@ -38,12 +38,16 @@
 // arguments and the batched one (grid z = the problem) with the record's state and slice z of ONE offsets workspace (S slices
 // of P * ceil16(3 V) floats); an output element is the same 34 accumulations whatever the grid.  The batched evaluation builds
 // its Frame as hand_pose_eval_batch_kernel does and points ManoExtra::offsets at the problem's slice.
+//
+// Posing the hand -- Rodrigues, the joint set-up, the chain, the joint record, skinning and placing a vertex, the pose features --
+// is hand_lbs.h, shared with hand_interact.hip; the volume lookup is sdf_device.h's; the model's argument checks are hand_check.h's.
 #include <hip/hip_fp16.h>
 
+#include <cstdint>
 #include <cstring>
 
-#include <cstdint>
-
+#include "hand_check.h"
+#include "hand_lbs.h"
 #include "mfma_rows.h"
 #include "pn2_common.h"
 #include "sdf_device.h"
@@ -52,7 +56,9 @@
 namespace pn2 {
 namespace hpose {
 
-constexpr int MAXP = 8192, MAXV = 1024, NJ = 21, MAXK = 4, NC = 10, NPOSE = 45, ND = 6 + NC;
+using namespace lbs;
+
+constexpr int MAXP = 8192, MAXV = 1024, NC = 10, ND = 6 + NC;
 // state (pn2_ext.h): rotation, translation, joint angles, search size, previous search size, previous success
 constexpr int S_R = 0, S_T = 9, S_THETA = 12, S_SEARCH = 57, S_PREV = 73, S_PREV_OK = 89;
 constexpr int TERMS = 4;  // per candidate: gate-independent energy, attraction term, penetration, 0
@@ -94,12 +100,6 @@ __device__ __forceinline__ float vol_round(float x) {  // a value of the volume'
     else return x;
 }
 
-__device__ __forceinline__ float wave_sum_xor(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
 // [qw | pre[q] * search] of optimize() (:343-345): qw = sqrt(1 - x^2 - y^2 - z^2), NaN for a negative argument
 __device__ __forceinline__ void candidate_sample(const float *__restrict__ pre, int q, const float *search, float *s) {
 #pragma unroll
@@ -111,16 +111,6 @@ __device__ __forceinline__ void candidate_sample(const float *__restrict__ pre, 
 __device__ __forceinline__ float candidate_energy(const float *__restrict__ terms, int q, bool gate) {
     const float base = terms[(size_t)q * TERMS], attr = terms[(size_t)q * TERMS + 1];
     return gate ? base + attr : base;
-}
-
-// hand_model.rodrigues: I + sin K + (1 - cos) K K with K the cross-product matrix of aa / max(|aa|, 1e-12)
-__device__ __forceinline__ void rodrigues(float ax, float ay, float az, float *R) {
-    const float n = fmaxf(sqrtf(ax * ax + ay * ay + az * az), 1e-12f);
-    const float kx = ax / n, ky = ay / n, kz = az / n;
-    const float s = sinf(n), oc = 1.0f - cosf(n);
-    R[0] = 1.0f + oc * (-(kz * kz) - ky * ky);  R[1] = s * -kz + oc * (kx * ky);            R[2] = s * ky + oc * (kx * kz);
-    R[3] = s * kz + oc * (kx * ky);            R[4] = 1.0f + oc * (-(kz * kz) - kx * kx);  R[5] = s * -kx + oc * (ky * kz);
-    R[6] = s * -ky + oc * (kx * kz);           R[7] = s * kx + oc * (ky * kz);             R[8] = 1.0f + oc * (-(ky * ky) - kx * kx);
 }
 
 // a joint's angles: curr_theta + (coefficients @ comps[:10]) * theta_scale (get_kp_from_delta), for a MANO hand with the mean
@@ -176,20 +166,9 @@ __device__ __forceinline__ void hand_pose_eval_block(const Frame A, const ManoEx
     }
 
     // ---- this lane's joint (lanes >= 21 carry joint 0's tables and are masked where it matters) ------------------------------
-    const bool is_joint = lane < NJ;
-    const int j = is_joint ? lane : 0;
-    const int pa = j == 0 ? 0 : min(max(A.parents[j], 0), j - 1);
-    int blk = A.pose_block[j];
-    if (blk < 0 || blk >= NPOSE / 3 || j == 0) blk = -1;
-    int depth = 0;
-    for (int s = 0, q = j; s < NJ; ++s)
-        if (q != 0) {
-            q = min(max(A.parents[q], 0), q - 1);
-            ++depth;
-        }
-    int maxdepth = depth;
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) maxdepth = max(maxdepth, __shfl_xor(maxdepth, m, 64));
+    const Joint J = lane_joint(A.parents, A.pose_block, lane);
+    const bool is_joint = J.is_joint;
+    const int j = J.j, pa = J.pa, blk = J.blk;
     float off[3], pred[3], last[3] = {0.f, 0.f, 0.f}, cth[3] = {0.f, 0.f, 0.f}, pmean[3] = {0.f, 0.f, 0.f}, cm[NC][3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
@@ -245,39 +224,15 @@ __device__ __forceinline__ void hand_pose_eval_block(const Frame A, const ManoEx
         float th[3], Rl[9], R[9], t[3];
         joint_angles<MANO>(sp, cm, cth, pmean, A.theta_scale, th);
         rodrigues(th[0], th[1], th[2], Rl);
-#pragma unroll
-        for (int k = 0; k < 9; ++k) R[k] = Rg[k];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) t[k] = root[k];
-        for (int lvl = 1; lvl <= maxdepth; ++lvl) {
-            float pR[9], pt[3];
-#pragma unroll
-            for (int k = 0; k < 9; ++k) pR[k] = __shfl(R[k], pa, 64);
-#pragma unroll
-            for (int k = 0; k < 3; ++k) pt[k] = __shfl(t[k], pa, 64);
-            if (depth == lvl) {
-#pragma unroll
-                for (int k = 0; k < 3; ++k)
-                    t[k] = pt[k] + fmaf(pR[3 * k + 2], off[2], fmaf(pR[3 * k + 1], off[1], pR[3 * k] * off[0]));
-                if (blk >= 0) mat3_mul(pR, Rl, R);
-                else {
-#pragma unroll
-                    for (int k = 0; k < 9; ++k) R[k] = pR[k];
-                }
-            }
-        }
+        chain(J, Rl, off, Rg, root, R, t);
         __builtin_amdgcn_wave_barrier();  // the previous candidate's reads of this slot are issued before these writes
-        if (is_joint) {
-            sk[3 * j] = make_float4(R[0], R[1], R[2], R[3]);
-            sk[3 * j + 1] = make_float4(R[4], R[5], R[6], R[7]);
-            sk[3 * j + 2] = make_float4(R[8], t[0], t[1], t[2]);
-        }
+        store_joint(sk, J, R, t);
         __builtin_amdgcn_wave_barrier();
 
         // ---- keypoint terms (a MANO hand's fingertips are skinned vertices: after the vertex loop) ------------------------------
         float vis_sum, inv_sum, tmp_sum;
-        if constexpr (!MANO)
-            keypoint_terms(A, c, j, is_joint, t[0] + tr[0], t[1] + tr[1], t[2] + tr[2], pred, last, visf, vis_sum, inv_sum, tmp_sum);
+        place(MANO, cen, tr, t[0], t[1], t[2]);  // from here on t is the lane's joint as a keypoint
+        if constexpr (!MANO) keypoint_terms(A, c, j, is_joint, t[0], t[1], t[2], pred, last, visf, vis_sum, inv_sum, tmp_sum);
 
         // ---- vertices ------------------------------------------------------------------------------------------------------------
         float pen = 0.f, fmin5[5];
@@ -293,44 +248,23 @@ __device__ __forceinline__ void hand_pose_eval_block(const Frame A, const ManoEx
                 const int vv = min(v0 + 64 * u, V - 1);  // slots past the end repeat the last vertex and are masked below
                 const int p = pk[vv];
                 bits[u] = p >> 20;
-                float x = 0.f, y = 0.f, z = 0.f;
+                float x, y, z;
                 float bx = 0.f, by = 0.f, bz = 0.f;  // MANO: the candidate's pose-blend offset of this vertex
                 if constexpr (MANO) {
                     const float *b = M.offsets + (size_t)c * M.ldo + 3 * vv;
                     bx = b[0]; by = b[1]; bz = b[2];
                 }
-#pragma unroll
-                for (int k = 0; k < MAXK; ++k)
-                    if (k < K) {
-                        float4 e = tab[k * V + vv];
-                        if constexpr (MANO) {
-                            e.x += bx; e.y += by; e.z += bz;
-                        }
-                        const int jn = min((p >> (5 * k)) & 31, NJ - 1);
-                        const float4 a = sk[3 * jn], b = sk[3 * jn + 1], d = sk[3 * jn + 2];
-                        const float qx = fmaf(a.z, e.z, fmaf(a.y, e.y, a.x * e.x)) + d.y;
-                        const float qy = fmaf(b.y, e.z, fmaf(b.x, e.y, a.w * e.x)) + d.z;
-                        const float qz = fmaf(d.x, e.z, fmaf(b.w, e.y, b.z * e.x)) + d.w;
-                        x = k == 0 ? qx * e.w : fmaf(qx, e.w, x);
-                        y = k == 0 ? qy * e.w : fmaf(qy, e.w, y);
-                        z = k == 0 ? qz * e.w : fmaf(qz, e.w, z);
-                    }
+                skin_vertex(p, K, sk, MANO, bx, by, bz, [&](int k, int) { return tab[k * V + vv]; }, x, y, z);
+                place(MANO, cen, tr, x, y, z);
                 if constexpr (MANO) {
-                    x = (x - cen[0]) + tr[0]; y = (y - cen[1]) + tr[1]; z = (z - cen[2]) + tr[2];
-                    const int kj = min((p >> 25) & 31, NJ - 1);  // the keypoint this vertex is (0: none): its unused LDS slot
+                    const int kj = keypoint_of(p);  // the keypoint this vertex is (0: none): its unused LDS slot
                     if (kj != 0 && v0 + 64 * u < V) sk[3 * kj + 2] = make_float4(0.f, x, y, z);
-                } else {
-                    x += tr[0]; y += tr[1]; z += tr[2];
                 }
                 if (A.out_verts && v0 + 64 * u < V) {
                     float *o = A.out_verts + ((size_t)c * V + vv) * 3;
                     o[0] = x; o[1] = y; o[2] = z;
                 }
-                float ox, oy, oz;
-                to_object_frame(x, y, z, ot, oR, ox, oy, oz);
-                const int flat = nearest_voxel(ox, oy, oz, A.voxel_scale, A.res);
-                if constexpr (F16) sdf[u] = __half2float(reinterpret_cast<const __half *>(A.vol)[flat]);
-                else sdf[u] = reinterpret_cast<const float *>(A.vol)[flat];
+                sdf[u] = sdf_nearest<F16>(A.vol, x, y, z, ot, oR, A.voxel_scale, A.res);
                 // world2point2D (:13-21), .long() = truncation toward zero, clamp to the image (:242-246)
                 const float px = x / z * A.fx + A.cx, py = y / z * A.fy + A.cy;
                 const int row = min(max((int)fminf(fmaxf(py, -1.f), fh), 0), A.h - 1);
@@ -352,9 +286,8 @@ __device__ __forceinline__ void hand_pose_eval_block(const Frame A, const ManoEx
         if constexpr (MANO) {
             __builtin_amdgcn_wave_barrier();  // the fingertip slots are written
             const float4 d = sk[3 * j + 2];
-            keypoint_terms(A, c, j, is_joint, kp_from_vertex ? d.y : (t[0] - cen[0]) + tr[0],
-                           kp_from_vertex ? d.z : (t[1] - cen[1]) + tr[1], kp_from_vertex ? d.w : (t[2] - cen[2]) + tr[2], pred, last,
-                           visf, vis_sum, inv_sum, tmp_sum);
+            keypoint_terms(A, c, j, is_joint, kp_from_vertex ? d.y : t[0], kp_from_vertex ? d.z : t[1], kp_from_vertex ? d.w : t[2],
+                           pred, last, visf, vis_sum, inv_sum, tmp_sum);
         }
 #pragma unroll
         for (int m = 32; m >= 1; m >>= 1) {
@@ -400,8 +333,7 @@ __global__ void __launch_bounds__(256) hand_pose_mano_eval_kernel(const Frame A,
 // tiles of pd (blockIdx.y-strided): the tile's 136 columns in registers, one v_mfma_f32_16x16x4_f32 per 4 columns against each
 // of the four 16-candidate groups, a lane's four consecutive outputs as one 16-byte store.  In k-group g a lane supplies
 // columns 16 g + 4 (lane / 16) + s of both operands (one 16-byte load each); the last group is half as wide.
-constexpr int NF = 9 * (NPOSE / 3), KP = NF + 1, OCT = 64;
-static_assert(KP % 8 == 0 && KP % 16 == 8, "eight full k-groups of 16 and one of 8");
+constexpr int OCT = 64;
 
 // The body is a device function: the single kernel calls it with its own arguments, the batched one with a problem's.
 __device__ __forceinline__ void hand_pose_offsets_block(int P, int ntiles, const float *__restrict__ pd,
@@ -415,8 +347,8 @@ __device__ __forceinline__ void hand_pose_offsets_block(int P, int ntiles, const
     float search[ND];
 #pragma unroll
     for (int k = 0; k < ND; ++k) search[k] = state[S_SEARCH + k];
-    for (int i = tid; i < OCT * (NPOSE / 3); i += 256) {
-        const int cl = i / (NPOSE / 3), b = i - cl * (NPOSE / 3), c = c0 + cl;
+    for (int i = tid; i < OCT * NB; i += 256) {
+        const int cl = i / NB, b = i - cl * NB, c = c0 + cl;
         float R[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};  // a row past the end: zero features
         if (c < P) {
             float sp[1 + ND], cm[NC][3], cth[3], pmean[3], th[3];
@@ -431,8 +363,7 @@ __device__ __forceinline__ void hand_pose_offsets_block(int P, int ntiles, const
             joint_angles<true>(sp, cm, cth, pmean, theta_scale, th);
             rodrigues(th[0], th[1], th[2], R);
         }
-#pragma unroll
-        for (int k = 0; k < 9; ++k) feat[cl * KP + 9 * b + k] = R[k] - ((k & 3) == 0 ? 1.f : 0.f);
+        pose_features(R, feat + cl * KP + 9 * b);
     }
     if (tid < OCT) feat[tid * KP + NF] = 0.f;
     __syncthreads();
@@ -480,15 +411,21 @@ struct Batch {
     const pn2x_hand_pose_problem *prob;
 };
 
+// the shared frame with a problem's fields set from its record: one in host memory, or a ConstProblem on the device
+template <typename Record>
+__host__ __device__ __forceinline__ Frame problem_frame(const Frame &shared, const Record *r) {
+    Frame A = shared;
+    A.rest_j = r->rest_joints; A.rest_v = r->rest_verts; A.state = r->state; A.pred_kp = r->pred_kp; A.last_kp = r->last_kp;
+    A.vis = r->vis_mask; A.obj_r = r->obj_r; A.obj_t = r->obj_t; A.vol = r->vol; A.mask = r->mask; A.h = r->h; A.w = r->w;
+    A.fx = r->fx; A.fy = r->fy; A.cx = r->cx; A.cy = r->cy; A.terms = r->work;
+    return A;
+}
+
 template <bool F16>
 __global__ void __launch_bounds__(256) hand_pose_eval_batch_kernel(const Batch B) {
     const ConstProblem *r = (const ConstProblem *)B.prob + blockIdx.y;
     if (!r->active) return;
-    Frame A = B.shared;
-    A.rest_j = r->rest_joints; A.rest_v = r->rest_verts; A.state = r->state; A.pred_kp = r->pred_kp; A.last_kp = r->last_kp;
-    A.vis = r->vis_mask; A.obj_r = r->obj_r; A.obj_t = r->obj_t; A.vol = r->vol; A.mask = r->mask; A.h = r->h; A.w = r->w;
-    A.fx = r->fx; A.fy = r->fy; A.cx = r->cx; A.cy = r->cy; A.terms = r->work;
-    hand_pose_eval_block<F16, false>(A, ManoExtra{});
+    hand_pose_eval_block<F16, false>(problem_frame(B.shared, r), ManoExtra{});
 }
 
 // The MANO batch (pn2x_hand_pose_mano_opt_batch): M.offsets is the base of the batch's offsets workspace, s slices of P * ldo
@@ -509,13 +446,9 @@ template <bool F16>
 __global__ void __launch_bounds__(256) hand_pose_mano_eval_batch_kernel(const Batch B, const ManoExtra M0) {
     const ConstProblem *r = (const ConstProblem *)B.prob + blockIdx.y;
     if (!r->active) return;
-    Frame A = B.shared;  // (the record's fields as hand_pose_eval_batch_kernel takes them)
-    A.rest_j = r->rest_joints; A.rest_v = r->rest_verts; A.state = r->state; A.pred_kp = r->pred_kp; A.last_kp = r->last_kp;
-    A.vis = r->vis_mask; A.obj_r = r->obj_r; A.obj_t = r->obj_t; A.vol = r->vol; A.mask = r->mask; A.h = r->h; A.w = r->w;
-    A.fx = r->fx; A.fy = r->fy; A.cx = r->cx; A.cy = r->cy; A.terms = r->work;
     ManoExtra M = M0;
-    M.offsets = M0.offsets + (size_t)blockIdx.y * (size_t)A.P * (size_t)M0.ldo;
-    hand_pose_eval_block<F16, true>(A, M);
+    M.offsets = M0.offsets + (size_t)blockIdx.y * (size_t)B.shared.P * (size_t)M0.ldo;
+    hand_pose_eval_block<F16, true>(problem_frame(B.shared, r), M);
 }
 
 __global__ void __launch_bounds__(256) hand_pose_energy_kernel(int P, const float *__restrict__ terms, float *__restrict__ energy) {
@@ -680,31 +613,13 @@ extern "C" long pn2x_hand_pose_mano_batch_work_floats(int p, int v, int s) {
     return (p < 0 || v < 0 || s < 0) ? (long)PN2_EINVAL : (long)s * p * offsets_ld(v);
 }
 
-// What an entry's argument checks found, whichever check found it: a bad value before a limit before a NULL pointer.
-struct Faults {
-    bool inval = false, range = false, null = false;
-    int code() const { return inval ? PN2_EINVAL : range ? PN2_ERANGE : null ? PN2_ENULL : PN2_OK; }
-};
-
-// A record pointer is read only if a process can own the address: nothing is mapped below 64 KiB.  A caller built against
-// ABI version 3 passes its candidate count where the setup record is now, and is refused (PN2_EINVAL) instead of read.
-static bool is_record(const void *rec) { return (uintptr_t)rec >= 65536; }
-static bool is_record(const void *rec, Faults &f) {
-    if (is_record(rec)) return true;
-    (rec ? f.inval : f.null) = true;
-    return false;
-}
-
+// the optimiser's setup: the model (hand_check.h) and its own candidates
 static void check_setup(const pn2x_hand_pose_setup *s, Faults &f) {
     if (!is_record(s, f)) return;
-    f.inval |= s->p < 1 || s->v < 1 || s->j < 1 || s->k < 1 || s->res < 1 || (s->res & 1) == 0 || !(s->voxel_scale > 0.f) ||
-               (s->vol_f16 != 0 && s->vol_f16 != 1);
+    check_hand_model(*s, f);
+    f.inval |= s->p < 1;
     f.range |= !pn2x_hand_pose_opt_supported(s->p, s->v, s->j, s->k, NC, s->res);
-    f.null |= !s->parents || !s->pose_block || !s->skin_pack || !s->skin_w || !s->comps || !s->pre;
-    if (s->posedirs) {  // the MANO part; posedirs is read by 16-byte loads
-        f.inval |= (s->centre_root != 0 && s->centre_root != 1) || ((uintptr_t)s->posedirs & 15);
-        f.null |= !s->pose_mean || !s->kp_vertex;
-    }
+    f.null |= !s->comps || !s->pre;
 }
 
 // a record in host memory: a single problem's frame, or an active record on its way into a batch's table
@@ -736,11 +651,7 @@ static Frame shared_frame(const pn2x_hand_pose_setup &s) {
 
 // a single problem's kernel argument: what hand_pose_eval_batch_kernel takes from a record, from a record in host memory
 static Frame single_frame(const pn2x_hand_pose_setup &s, const pn2x_hand_pose_problem &r) {
-    Frame A = shared_frame(s);
-    A.rest_j = r.rest_joints; A.rest_v = r.rest_verts; A.state = r.state; A.pred_kp = r.pred_kp; A.last_kp = r.last_kp;
-    A.vis = r.vis_mask; A.obj_r = r.obj_r; A.obj_t = r.obj_t; A.vol = r.vol; A.mask = r.mask; A.h = r.h; A.w = r.w;
-    A.fx = r.fx; A.fy = r.fy; A.cx = r.cx; A.cy = r.cy; A.terms = r.work;
-    return A;
+    return problem_frame(shared_frame(s), &r);
 }
 
 // One evaluation launch of `Kernel` (an instantiation of the three evaluation kernels), whose dynamic-LDS limit is raised once

@@ -83,6 +83,14 @@ __device__ __forceinline__ float wave_sum_f32(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
 
+// Full wave64 fp32 sum by xor butterfly: unlike the DPP ladder EVERY lane gets the sum, and the additions pair up in another
+// order (lane l with l ^ 32 first), so the two give different bits and neither may replace the other.
+__device__ __forceinline__ float wave_sum_xor(float v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+
 // fminf without the v_max canonicalisation hipcc inserts in IEEE mode (operands are never sNaN here).
 // index into an LDS-staged array of n entries: a corrupt index (negative or >= n) must not read or update another array's
 // LDS (the global-memory kernels of the reference do not check either, but there a bad index cannot corrupt a neighbour's sums)

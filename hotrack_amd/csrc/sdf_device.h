@@ -1,8 +1,9 @@
-// sdf_device.h -- device arithmetic shared by the particle optimisers' kernels (sdf.hip, hand_pose.hip): the object-frame
-// transform, torch's floor division and the nearest-voxel index of gf_optimize_hand_pose.query_sdf, and the small rotation
-// helpers of the pose updates.  One definition, so that a lookup fused into another kernel reads the same voxel as
-// pn2s_nearest for every input.
+// sdf_device.h -- device arithmetic shared by the particle optimisers' kernels (sdf.hip, hand_pose.hip, hand_interact.hip): the
+// object-frame transform, torch's floor division and the nearest-voxel index of gf_optimize_hand_pose.query_sdf, the lookup
+// fused into the hand kernels, and the small rotation helpers of the pose updates.  One definition, so that a lookup fused
+// into another kernel reads the same voxel as pn2s_nearest for every input.
 #pragma once
+#include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 
 namespace pn2 {
@@ -47,6 +48,17 @@ __device__ __forceinline__ int nearest_voxel(float ox, float oy, float oz, float
     const int iy = (int)clampf(div_floor(oy, voxel_scale), -fh, fh) + half;
     const int iz = (int)clampf(div_floor(oz, voxel_scale), -fh, fh) + half;
     return (ix * res + iy) * res + iz;
+}
+
+// query_sdf for one camera-frame point: the object frame, the nearest voxel, the volume's value (fp16 or fp32) as fp32
+template <bool F16>
+__device__ __forceinline__ float sdf_nearest(const void *vol, float x, float y, float z, const float *ot, const float *oR,
+                                             float voxel_scale, int res) {
+    float ox, oy, oz;
+    to_object_frame(x, y, z, ot, oR, ox, oy, oz);
+    const int flat = nearest_voxel(ox, oy, oz, voxel_scale, res);
+    if constexpr (F16) return __half2float(reinterpret_cast<const __half *>(vol)[flat]);
+    else return reinterpret_cast<const float *>(vol)[flat];
 }
 
 __device__ __forceinline__ void quat_to_matrix(float w, float x, float y, float z, float *m) {  // rotations.py:105-113
