@@ -52,6 +52,7 @@ def get_config(args, save=True):
     cfg.setdefault("fused_hand_eval", False)  # tracked hand sequences evaluated in two launches (--fused_hand_eval)
     cfg.setdefault("hand_interaction_eval", False)  # hand-object penetration / contact columns (--hand_interaction_eval)
     cfg["opt"].setdefault("contact_threshold", 0.005)  # metres: a fingertip region this near the surface is in contact
+    cfg["opt"].setdefault("accumulate_surface", False)  # obj_opt: keep the observed surface of each sequence (--accumulate_obj_surface)
     data_cfg = _load("data_config", cfg["data_config"])
     cfg["pointnet"] = {k: _load("pointnet_config", v) for k, v in cfg["pointnet_cfg"].items()}
 

@@ -1621,3 +1621,83 @@ def depth_frame_clouds(depth: torch.Tensor, seg: torch.Tensor, intrinsics: torch
         _native._check(_native._call(_lib.pn2x_depth_frame_clouds, "depth_frame_kernels", None, ctypes.byref(r), _native._stream(depth)),
                        "depth_frame_clouds")
     return clouds, counts, background
+
+
+_lib.pn2x_cloud_normals.argtypes = [_ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp]
+_lib.pn2x_cloud_normals.restype = _ci
+_lib.pn2x_cloud_normals_limits.argtypes = [ctypes.POINTER(_ci)] * 3
+_lib.pn2x_cloud_normals_limits.restype = None
+
+
+def _cloud_normals_limits():
+    b, n, k = _ci(), _ci(), _ci()
+    _lib.pn2x_cloud_normals_limits(ctypes.byref(b), ctypes.byref(n), ctypes.byref(k))
+    return b.value, n.value, k.value
+
+
+# PN2X_CLOUD_NORMALS_MAX_B / _MAX_N / _MAX_K, as the library was built with them
+CLOUD_NORMALS_MAX_B, CLOUD_NORMALS_MAX_N, CLOUD_NORMALS_MAX_K = _cloud_normals_limits()
+CLOUD_NORMALS_ORIENT = {"none": 0, "view": 1, "reference": 2}
+
+
+def cloud_normals(points: torch.Tensor, k: int = 30, viewpoint=None, valid=None, orient: str = "view"):
+    """Oriented normals of B point clouds in one launch, one wave per query (pn2x_cloud_normals): points (B,N,3) fp32 ->
+    (normals (B,N,3), variation (B,N)).  For every usable query -- `valid` (B,N) bool / uint8 not 0 (None: all) and finite
+    coordinates -- the k nearest usable points of its own cloud, itself included (open3d's estimate_normals convention, whose
+    default k is 30; all of them when fewer than k are usable), their covariance in two fp32 passes, the unit eigenvector of the
+    smallest eigenvalue by cyclic Jacobi sweeps, and variation = lambda0 / (lambda0 + lambda1 + lambda2).  Zeros for a query that
+    is not usable, for fewer than 3 usable points and for neighbours that all coincide.
+    viewpoint (B,3) or (3,), None = the origin (the camera in the camera frame).  orient:
+      "none"       the component of largest magnitude is positive (a deterministic sign, no geometry);
+      "view"       n . (viewpoint - p) >= 0;
+      "reference"  the reference's (2 (n (viewpoint - p) > 0) - 1) n, optimization_obj.py:342: a sign per COMPONENT.  It is NOT a
+                   geometric orientation (the result need not even be +-n); it is what the reference feeds its shape refit.
+    Range: 3 <= N <= CLOUD_NORMALS_MAX_N = 2048 (the register-resident selection), 3 <= k <= CLOUD_NORMALS_MAX_K = 64 (one lane per
+    neighbour), B <= CLOUD_NORMALS_MAX_B = 65535.  No host sync."""
+    if not isinstance(points, torch.Tensor):
+        raise TypeError(f"cloud_normals: points must be a torch.Tensor, got {type(points).__name__}")
+    if points.dim() != 3 or points.shape[-1] != 3:
+        raise ValueError(f"cloud_normals: points must be (B,N,3), got {tuple(points.shape)}")
+    B, N, _ = points.shape
+    k = int(k)
+    if orient not in CLOUD_NORMALS_ORIENT:
+        raise ValueError(f"cloud_normals: orient must be one of {sorted(CLOUD_NORMALS_ORIENT)}, got {orient!r}")
+    if B < 1 or not 3 <= N <= CLOUD_NORMALS_MAX_N:
+        raise ValueError(f"cloud_normals: {B} clouds of {N} points: at least one cloud of 3 to {CLOUD_NORMALS_MAX_N} points (the "
+                         "selection keeps a cloud's distances in one wave's registers)")
+    if B > CLOUD_NORMALS_MAX_B:
+        raise ValueError(f"cloud_normals: {B} clouds: at most {CLOUD_NORMALS_MAX_B} clouds per call (one row of the launch grid each)")
+    if not 3 <= k <= CLOUD_NORMALS_MAX_K:
+        raise ValueError(f"cloud_normals: k = {k}: 3 to {CLOUD_NORMALS_MAX_K} neighbours (one lane of the wave per neighbour)")
+    f32 = torch.float32
+    if points.dtype != f32:
+        raise TypeError(f"cloud_normals: points must be {f32}, got {points.dtype}")
+    if valid is not None:
+        if not isinstance(valid, torch.Tensor) or valid.dtype not in (torch.bool, torch.uint8):
+            raise TypeError("cloud_normals: valid must be a bool or uint8 tensor")
+        if tuple(valid.shape) != (B, N):
+            raise ValueError(f"cloud_normals: valid must be ({B},{N}), got {tuple(valid.shape)}")
+        if valid.device != points.device:
+            raise ValueError(f"cloud_normals: tensors on {points.device} and {valid.device}")
+        if valid.dtype == torch.bool:
+            valid = valid.contiguous().view(torch.uint8) if valid.is_contiguous() else valid.to(torch.uint8)
+    if viewpoint is None:
+        viewpoint = torch.zeros((B, 3), dtype=f32, device=points.device)
+    else:
+        if not isinstance(viewpoint, torch.Tensor) or viewpoint.dtype != f32:
+            raise TypeError(f"cloud_normals: viewpoint must be a {f32} tensor")
+        if viewpoint.device != points.device:
+            raise ValueError(f"cloud_normals: tensors on {points.device} and {viewpoint.device}")
+        if tuple(viewpoint.shape) == (3,):
+            viewpoint = viewpoint.expand(B, 3).contiguous()
+        elif tuple(viewpoint.shape) != (B, 3):
+            raise ValueError(f"cloud_normals: viewpoint must be ({B},3) or (3,), got {tuple(viewpoint.shape)}")
+    pp = _native._ptr(points, "points", f32, B * N * 3)
+    pv = None if valid is None else _native._ptr(valid, "valid", torch.uint8, B * N)
+    pc = _native._ptr(viewpoint, "viewpoint", f32, B * 3)
+    normals = torch.empty((B, N, 3), dtype=f32, device=points.device)
+    variation = torch.empty((B, N), dtype=f32, device=points.device)
+    with torch.cuda.device(points.device):
+        _native._check(_native._call(_lib.pn2x_cloud_normals, "cloud_normals", None, B, N, k, CLOUD_NORMALS_ORIENT[orient], pp, pv, pc,
+                                     normals.data_ptr(), variation.data_ptr(), _native._stream(points)), "cloud_normals")
+    return normals, variation

@@ -1080,6 +1080,32 @@ int pn2x_depth_frame_supported(int h, int w, int hs, int ws, int c, int cap);
 long pn2x_depth_frame_work_ints(int b, int h, int w);
 int pn2x_depth_frame_clouds(const pn2x_depth_frame *frames, void *stream);
 
+/*
+ * Oriented normals of b point clouds (hotrack_amd/csrc/cloud_normals.hip): what the reference's estimate_normal does with open3d on
+ * the host (optimization_obj.py:335-343), in one launch, one wave per query, no host sync or allocation (capturable).
+ * points (b,n,3) fp32; valid (b,n) bytes or NULL (every point valid); viewpoint (b,3); normals (b,n,3), variation (b,n).
+ * A point is usable when its valid byte is not 0 and its coordinates are finite.  For a usable query: its min(k, usable points)
+ * nearest usable points of its own cloud, itself included, by the key (fp32 squared distance bits, index), the lower index on
+ * a tie (the order of pn2_knn); their covariance about their mean in two fp32 passes; the unit eigenvector of its smallest
+ * eigenvalue from five cyclic Jacobi sweeps on the covariance divided by its trace; variation = lambda0 / (lambda0 + lambda1 +
+ * lambda2), lambda0 not below 0.  Zeros for both outputs: a query that is not usable, fewer than 3 usable points, a
+ * covariance whose trace is 0 (all neighbours coincide: the farthest neighbour at
+ * squared distance 0).
+ * orient 0: the component of largest magnitude is positive (the lower index on a tie);  1: n . (viewpoint - p) >= 0;  2: the
+ * reference's rule (2 (n (viewpoint - p) > 0) - 1) n, a sign per COMPONENT -- not a geometric orientation, kept because it is
+ * what the reference hands to its shape refit.  orient 0 does not read viewpoint (it must still be given).
+ * PN2_EINVAL unless b >= 1, 3 <= n <= PN2X_CLOUD_NORMALS_MAX_N (the register-resident selection of knn_wave.h, 32 keys per
+ * lane), 3 <= k <= PN2X_CLOUD_NORMALS_MAX_K (one lane per neighbour) and orient in 0..2; PN2_ERANGE for b > PN2X_CLOUD_NORMALS_MAX_B (the launch grid); PN2_ENULL
+ * for a NULL points, viewpoint, normals or variation.  Run-to-run bitwise equal.
+ */
+#define PN2X_CLOUD_NORMALS_MAX_B 65535
+#define PN2X_CLOUD_NORMALS_MAX_N 2048
+#define PN2X_CLOUD_NORMALS_MAX_K 64
+/* the three limits above, for a binding that cannot read this header (NULL: that one is not wanted) */
+void pn2x_cloud_normals_limits(int *max_b, int *max_n, int *max_k);
+int pn2x_cloud_normals(int b, int n, int k, int orient, const float *points, const unsigned char *valid, const float *viewpoint,
+                       float *normals, float *variation, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

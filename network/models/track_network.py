@@ -638,6 +638,24 @@ class ObjTrackModel_Optimization(nn.Module):
         self.sym = cfg.get("obj_sym", -1)
         self.optimizer = gf_optimize_obj(cfg)
         self._front_end = _FrontEndSlot(cfg)  # frames that carry a depth image instead of obj_points (models/frame_frontend.py)
+        # opt.accumulate_surface: keep each sequence's observed surface (models/obs_surface.py); the poses do not depend on it
+        self.accumulate_surface = bool((cfg.get("opt") or {}).get("accumulate_surface", False))
+        self.surface_seed = 0  # every sequence draws from a generator of its own with this seed: alone or in a group, the same surface
+        self.save_folder = cfg.get("save_dir")
+
+    def _new_surface(self, cloud):
+        """An ObservedSurface for a sequence whose first cloud is `cloud`: as many slots as that cloud has points (the
+        reference's merged cloud is its first cloud), at most the normal kernel's 2048."""
+        from hotrack_amd import ext
+        from .obs_surface import ObservedSurface
+        gen = torch.Generator(device=self.device)
+        gen.manual_seed(int(self.surface_seed))
+        return ObservedSurface(min(cloud.reshape(-1, 3).shape[0], ext.CLOUD_NORMALS_MAX_N), generator=gen)
+
+    @staticmethod
+    def _surface_entry(surf, corner_volume, voxel_scale):
+        from .obs_surface import surface_fit
+        return dict(surf.state(), fit=surface_fit(surf.points, surf.normals, corner_volume, voxel_scale))
 
     def forward(self, input, flag_dict):
         flag_dict["track_flag"] = True
@@ -650,6 +668,7 @@ class ObjTrackModel_Optimization(nn.Module):
                                "'obj_mesh_path', into the sequence's first frame")
         last = None
         rets = []
+        surf = None
         for data in input:
             if last is not None:
                 data["jittered_obj_pose"] = last
@@ -660,11 +679,18 @@ class ObjTrackModel_Optimization(nn.Module):
                 jp["prev_translation"], jp["prev_rotation"] = jp["translation"], jp["rotation"]
                 last = {"translation": jp["translation"], "rotation": jp["rotation"]}
             self._front_end.complete(data, "obj_points")
+            if self.accumulate_surface and surf is None:  # frame 0, the pose tracking starts from (load_obj, :153-158)
+                cloud0 = data["obj_points"].float().to(self.device)
+                surf = self._new_surface(cloud0).start(cloud0, data["jittered_obj_pose"])
             ret = self.optimizer.optimize(data["obj_points"], data["jittered_obj_pose"], data["category"][0],
                                           data["file_name"][0], data.get("projection"))
+            if surf is not None:
+                surf.add(data["obj_points"].float().to(self.device), ret, self.optimizer._corners, self.optimizer.voxel_scale)
             last["prev_translation"], last["prev_rotation"] = last["translation"], last["rotation"]  # last frame's pose
             last["translation"], last["rotation"] = ret["translation"], ret["rotation"]            # current frame's pose
             rets.append(ret)
+        if surf is not None:
+            rets[0]["obj_surface"] = self._surface_entry(surf, self.optimizer._corners, self.optimizer.voxel_scale)
         return rets
 
     def _sequence_volume(self, frame0, built):
@@ -717,6 +743,7 @@ class ObjTrackModel_Optimization(nn.Module):
         S = len(inputs)
         last = [None] * S
         rets = [[] for _ in range(S)]
+        surfs = [None] * S
         for t in range(max((len(seq) for seq in inputs), default=0)):
             live = [k for k in range(S) if t < len(inputs[k])]
             for k in live:
@@ -730,6 +757,9 @@ class ObjTrackModel_Optimization(nn.Module):
                     jp["rotation"] = jp["rotation"].float().reshape(1, 3, 3).to(self.device)
                     jp["prev_translation"], jp["prev_rotation"] = jp["translation"], jp["rotation"]
                     last[k] = {"translation": jp["translation"], "rotation": jp["rotation"]}
+                    if self.accumulate_surface:
+                        cloud0 = data["obj_points"].float().to(self.device)
+                        surfs[k] = self._new_surface(cloud0).start(cloud0, jp)
             # (a sequence that has ended keeps its slot, with no cloud and no volume: the launch skips it; an EMPTY sequence
             # has no pose either and borrows a live one's, which comes back unchanged and is dropped)
             out = self.optimizer.optimize_batch([inputs[k][t]["obj_points"] if t < len(inputs[k]) else None for k in range(S)],
@@ -737,9 +767,14 @@ class ObjTrackModel_Optimization(nn.Module):
                                                 [vols[k] if t < len(inputs[k]) else None for k in range(S)], known[0][1])
             for k in live:
                 ret = out[k]
+                if surfs[k] is not None:
+                    surfs[k].add(inputs[k][t]["obj_points"].float().to(self.device), ret, vols[k], known[0][1])
                 last[k]["prev_translation"], last[k]["prev_rotation"] = last[k]["translation"], last[k]["rotation"]
                 last[k]["translation"], last[k]["rotation"] = ret["translation"], ret["rotation"]
                 rets[k].append(ret)
+        for k in range(S):
+            if surfs[k] is not None:
+                rets[k][0]["obj_surface"] = self._surface_entry(surfs[k], vols[k], known[0][1])
         return rets
 
     def compute_loss(self, input, ret_dict_lst, flag_dict):
@@ -807,11 +842,30 @@ class ObjTrackModel_Optimization(nn.Module):
         elif not ObjTrackModel_Optimization._said_no_points:
             ObjTrackModel_Optimization._said_no_points = True
             print("[Object Tracking] no 'obj_model_points' and no mesh in the sequence's first frame: raw_obj_chamfer(mm) / pred_obj_chamfer(mm) are not reported")
+        surface = ret_dict_lst[0].get("obj_surface")
+        if surface is not None:  # opt.accumulate_surface: how well the model fits what was seen (obs_surface.surface_fit)
+            keys += ["obs_surface_residual(mm)", "obs_surface_normal_agree"]
+            vals += [surface["fit"][0], surface["fit"][1]]
         host = torch.stack([torch.as_tensor(v, dtype=torch.float32, device=self.device).reshape(()) for v in vals]).tolist()  # the one read-back
         out = dict(zip(keys, host))
         for k in keys[:3]:
             out[k] = out[k] / n
+        if surface is not None and flag_dict.get("save_flag") and self.save_folder:
+            self._save_surface(input, ret_dict_lst, surface)
         return out, ret_dict_lst
+
+    def _save_surface(self, input, ret_dict_lst, surface):
+        """--save with opt.accumulate_surface: the sequence's pickle (named as the reference names it, track_network.py:446-451)
+        with the tracked poses and the observed surface."""
+        import os
+        import pickle
+        name = os.path.dirname(input[0]["file_name"][0]) or input[0]["file_name"][0]
+        os.makedirs(self.save_folder, exist_ok=True)
+        cpu = lambda v: v.detach().cpu().numpy() if torch.is_tensor(v) else v
+        with open(os.path.join(self.save_folder, name.replace("/", "_") + ".pkl"), "wb") as f:
+            pickle.dump({"CAD_ID": input[0]["category"][0],
+                         "pred_obj_poses": [{k: cpu(r[k]) for k in ("rotation", "translation")} for r in ret_dict_lst],
+                         "obj_surface": {k: cpu(v) for k, v in surface.items()}}, f)
 
     _said_no_points = False
 

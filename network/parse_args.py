@@ -50,6 +50,13 @@ def add_args(parser):
                              "hand_obj_min_sdf(mm), hand_model_kp_diff, hand_contact_frames -- from the tracked MANO_theta / global_pose, "
                              "the object pose the optimiser used and the sequence's SDF volume (two launches per evaluation, "
                              "hotrack_amd/csrc/hand_interact.hip; the contact distance is opt.contact_threshold, default 0.005 m)")
+    parser.add_argument("--accumulate_obj_surface", dest="opt/accumulate_surface", action="store_const", const=True, default=None,
+                        help="track=obj_opt: keep each sequence's observed surface -- the clouds the tracker saw, in the object "
+                             "frame, filtered to 2 cm of the model and folded into a fixed-size merged cloud with oriented normals "
+                             "(models/obs_surface.py, hotrack_amd/csrc/cloud_normals.hip; the bookkeeping of the reference's "
+                             "opt.updateobjshape route without its DeepSDF refit) -- and report obs_surface_residual(mm) and "
+                             "obs_surface_normal_agree; --save writes the surface into the sequence's pickle.  The tracked poses do "
+                             "not depend on it")
     parser.add_argument("--obj_mesh", type=str, default=None,
                         help="track the synthetic sequences' clouds against an SDF volume built from this triangle mesh (OBJ or "
                              "PLY, object frame, metres; models/mesh_sdf.py) instead of the analytic capsule volume")
