@@ -2,6 +2,8 @@
 // branches only LayerNorms, two small FFNs and the 3-channel head remain.  On the GPU each torch op there is a
 // launch-bound ~5 us kernel over a few KB; these kernels fuse the element-wise runs between the GEMMs:
 //   add_layernorm : out = LN2( LN1( x + y + bias ) )      (residual add + bias + one or two LayerNorms, 1 launch)
+//   perm_sum_rows / add_layernorm_perm : rearrange_module's five-slot neighbour sum taken after its product (no gathered
+//                   (tokens x 5C) operand), alone or as the x operand of add_layernorm
 //   pose_head     : delta = h W^T + b ; kp_hand = delta + xyz1 ; kp_cam = (kp_hand R^T) * scale + t   (1 launch for
 //                   the reference's Conv1d(…,3,1) + add + matmul + mul + add, hand_network.py:141-147)
 #include "pn2_common.h"
@@ -11,29 +13,13 @@ namespace pn2 {
 
 __device__ __forceinline__ float wave_sum(float v) { return wave_sum_f32(v); }  // DPP ladder, no ds_bpermute round trips
 
-// One wave per row; C <= 64 * EPL.  torch.nn.functional.layer_norm semantics: biased variance, eps inside the sqrt.
+// The normalisation of one row held as v[e] = element lane + 64 e (0 beyond c), s = this lane's sum of them: LN1, the optional
+// LN2 straight after it (TransT.s11 -> c11.norm1), and the store.  torch.nn.functional.layer_norm semantics: biased variance,
+// eps inside the sqrt.  Shared by add_layernorm_kernel and add_layernorm_perm_kernel, which differ only in how they form v.
 template <int EPL>
-__global__ void __launch_bounds__(256)
-add_layernorm_kernel(long rows, int c, const float *__restrict__ x, const float *__restrict__ y, const float *__restrict__ bias,
-                     const float *__restrict__ g1, const float *__restrict__ b1, float eps1, const float *__restrict__ g2,
-                     const float *__restrict__ b2, float eps2, float *__restrict__ out) {
-    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int lane = threadIdx.x & 63;
-    float v[EPL];
-    float s = 0.f;
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) {
-        const int ch = lane + 64 * e;
-        float t = 0.f;
-        if (ch < c) {
-            t = x[row * c + ch];
-            if (y) t += y[row * c + ch];
-            if (bias) t += bias[ch];
-        }
-        v[e] = t;
-        s += t;
-    }
+__device__ __forceinline__ void layernorm_row(float (&v)[EPL], float s, int lane, int c, const float *__restrict__ g1,
+                                              const float *__restrict__ b1, float eps1, const float *__restrict__ g2,
+                                              const float *__restrict__ b2, float eps2, float *__restrict__ out_row) {
     const float inv_c = 1.0f / (float)c;
     float mean = wave_sum(s) * inv_c, q = 0.f;
 #pragma unroll
@@ -67,8 +53,103 @@ add_layernorm_kernel(long rows, int c, const float *__restrict__ x, const float 
 #pragma unroll
     for (int e = 0; e < EPL; ++e) {
         const int ch = lane + 64 * e;
-        if (ch < c) out[row * c + ch] = v[e];
+        if (ch < c) out_row[ch] = v[e];
     }
+}
+
+// One wave per row; C <= 64 * EPL.
+template <int EPL>
+__global__ void __launch_bounds__(256)
+add_layernorm_kernel(long rows, int c, const float *__restrict__ x, const float *__restrict__ y, const float *__restrict__ bias,
+                     const float *__restrict__ g1, const float *__restrict__ b1, float eps1, const float *__restrict__ g2,
+                     const float *__restrict__ b2, float eps2, float *__restrict__ out) {
+    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int lane = threadIdx.x & 63;
+    float v[EPL];
+    float s = 0.f;
+#pragma unroll
+    for (int e = 0; e < EPL; ++e) {
+        const int ch = lane + 64 * e;
+        float t = 0.f;
+        if (ch < c) {
+            t = x[row * c + ch];
+            if (y) t += y[row * c + ch];
+            if (bias) t += bias[ch];
+        }
+        v[e] = t;
+        s += t;
+    }
+    layernorm_row<EPL>(v, s, lane, c, g1, b1, eps1, g2, b2, eps2, out + row * c);
+}
+
+// rearrange_module's neighbour table (j tokens x re slots, entries < j), carried in the kernel arguments: the entries are
+// range-checked on the host while they are packed, and a captured graph keeps its own copy.
+constexpr int kPermMaxTokens = 256, kPermMaxEntries = 512;
+struct PermTable {
+    unsigned char p[kPermMaxEntries];
+};
+
+// out[b,t,:] = sum_r z[b, perm[t,r], r*c : (r+1)*c], r = 0 .. re-1 in that order: the five-slot sum of rearrange_module taken
+// AFTER the product with the stacked slot weights (z = tokens x [W_0 | .. | W_re-1]^T, row stride ldz), so the (rows x re*c)
+// gathered operand never exists.  One wave per token, one 16-byte load per slot and quad of channels.
+__global__ void __launch_bounds__(256)
+perm_sum_rows_kernel(long rows, int j, int re, int c4, const float *__restrict__ z, int ldz, PermTable tab, float *__restrict__ out) {
+    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int lane = threadIdx.x & 63;
+    const long base = (row / j) * j;
+    const unsigned char *__restrict__ p = tab.p + (int)(row - base) * re;
+    for (int q = lane; q < c4; q += 64) {
+        float4 a = reinterpret_cast<const float4 *>(z + (base + p[0]) * ldz)[q];
+        for (int r = 1; r < re; ++r) {
+            const float4 t = reinterpret_cast<const float4 *>(z + (base + p[r]) * ldz + (long)r * 4 * c4)[q];
+            a.x += t.x; a.y += t.y; a.z += t.z; a.w += t.w;
+        }
+        reinterpret_cast<float4 *>(out + row * 4 * c4)[q] = a;
+    }
+}
+
+// add_layernorm_kernel with its x operand replaced by that sum (+ bias): out = LN2( LN1( sum_r z[..] + bias ) ).
+template <int EPL>
+__global__ void __launch_bounds__(256)
+add_layernorm_perm_kernel(long rows, int j, int re, int c, const float *__restrict__ z, int ldz, PermTable tab,
+                          const float *__restrict__ bias, const float *__restrict__ g1, const float *__restrict__ b1, float eps1,
+                          const float *__restrict__ g2, const float *__restrict__ b2, float eps2, float *__restrict__ out) {
+    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int lane = threadIdx.x & 63;
+    const long base = (row / j) * j;
+    const unsigned char *__restrict__ p = tab.p + (int)(row - base) * re;
+    float v[EPL];
+#pragma unroll
+    for (int e = 0; e < EPL; ++e) v[e] = 0.f;
+    for (int r = 0; r < re; ++r) {
+        const float *__restrict__ zr = z + (base + p[r]) * ldz + (long)r * c;
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) {
+            const int ch = lane + 64 * e;
+            if (ch < c) v[e] += zr[ch];
+        }
+    }
+    float s = 0.f;
+#pragma unroll
+    for (int e = 0; e < EPL; ++e) {
+        const int ch = lane + 64 * e;
+        if (bias && ch < c) v[e] += bias[ch];
+        s += v[e];
+    }
+    layernorm_row<EPL>(v, s, lane, c, g1, b1, eps1, g2, b2, eps2, out + row * c);
+}
+
+// Packs a host (j, re) int32 table into the kernel-argument form; PN2_EINVAL when it does not fit or an entry is outside [0, j).
+static int pack_perm(int j, int re, const int *perm, PermTable &tab) {
+    if (j < 1 || re < 1 || j > kPermMaxTokens || j * re > kPermMaxEntries) return PN2_EINVAL;
+    for (int i = 0; i < j * re; ++i) {
+        if (perm[i] < 0 || perm[i] >= j) return PN2_EINVAL;
+        tab.p[i] = (unsigned char)perm[i];
+    }
+    return PN2_OK;
 }
 
 // One wave per token (b, j): three dot products of length c, then the rigid transform back to the camera frame.
@@ -118,6 +199,41 @@ extern "C" int pn2x_add_layernorm(long rows, int c, const float *x, const float 
     else if (c <= 512) PN2_LN(8);
     else PN2_LN(16);
 #undef PN2_LN
+    return check_launch();
+}
+
+extern "C" int pn2x_perm_sum_rows(int b, int j, int re, int c, const float *z, int ldz, const int *perm, float *out, void *stream) {
+    if (b < 0 || c < 1 || (c & 3) || ldz < 0 || (ldz & 3) || (long)ldz < (long)re * c) return PN2_EINVAL;
+    if (!perm) return PN2_ENULL;
+    PermTable tab;
+    if (const int rc = pack_perm(j, re, perm, tab)) return rc;
+    if (b == 0) return PN2_OK;
+    if (!z || !out) return PN2_ENULL;
+    if ((((uintptr_t)z | (uintptr_t)out) & 15) != 0) return PN2_EINVAL;  // 16-byte loads and stores
+    const long rows = (long)b * j;
+    hipLaunchKernelGGL(perm_sum_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, rows, j, re, c / 4, z,
+                       ldz, tab, out);
+    return check_launch();
+}
+
+extern "C" int pn2x_add_layernorm_perm(int b, int j, int re, int c, const float *z, int ldz, const int *perm, const float *bias,
+                                       const float *g1, const float *b1, float eps1, const float *g2, const float *b2, float eps2,
+                                       float *out, void *stream) {
+    if (b < 0 || c < 1 || c > 1024 || (c & 3) || ldz < 0 || (long)ldz < (long)re * c) return PN2_EINVAL;
+    if (!perm) return PN2_ENULL;
+    PermTable tab;
+    if (const int rc = pack_perm(j, re, perm, tab)) return rc;
+    if (b == 0) return PN2_OK;
+    if (!z || !g1 || !b1 || !out || ((g2 == nullptr) != (b2 == nullptr))) return PN2_ENULL;
+    const long rows = (long)b * j;
+    const unsigned blocks = (unsigned)((rows + 3) / 4);
+    hipStream_t st = (hipStream_t)stream;
+#define PN2_LNP(E) hipLaunchKernelGGL(add_layernorm_perm_kernel<E>, dim3(blocks), dim3(256), 0, st, rows, j, re, c, z, ldz, tab, bias, g1, b1, eps1, g2, b2, eps2, out)
+    if (c <= 128) PN2_LNP(2);
+    else if (c <= 256) PN2_LNP(4);
+    else if (c <= 512) PN2_LNP(8);
+    else PN2_LNP(16);
+#undef PN2_LNP
     return check_launch();
 }
 

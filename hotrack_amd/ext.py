@@ -505,6 +505,57 @@ def add_layernorm(x: torch.Tensor, ln1, y: torch.Tensor = None, bias: torch.Tens
     return out
 
 
+_lib.pn2x_perm_sum_rows.argtypes = [_ci, _ci, _ci, _ci, _vp, _ci, _vp, _vp, _vp]
+_lib.pn2x_perm_sum_rows.restype = _ci
+_lib.pn2x_add_layernorm_perm.argtypes = [_ci, _ci, _ci, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _cf, _vp, _vp, _cf, _vp, _vp]
+_lib.pn2x_add_layernorm_perm.restype = _ci
+
+
+def _perm_args(z: torch.Tensor, perm: torch.Tensor, c: int, name: str):
+    """z (B*J, >= re*c) product rows (last dim contiguous) and the HOST (J, re) int32 table -> (B, J, re, ldz)."""
+    if not z.is_cuda or z.dtype != torch.float32 or z.dim() != 2 or z.stride(1) != 1:
+        raise TypeError(f"{name}: z must be 2-D float32 GPU rows with a contiguous last dimension")
+    if perm.is_cuda or perm.dtype != torch.int32 or perm.dim() != 2 or not perm.is_contiguous():
+        raise TypeError(f"{name}: perm must be a contiguous (J, re) int32 CPU tensor (the library reads it on the host)")
+    J, re = perm.shape
+    if z.shape[0] % J or z.shape[1] < re * c:
+        raise ValueError(f"{name}: z {tuple(z.shape)} does not hold whole groups of {J} tokens with {re} slots of {c} channels")
+    return z.shape[0] // J, J, re, z.stride(0)
+
+
+def perm_sum_rows(z: torch.Tensor, perm: torch.Tensor, c: int) -> torch.Tensor:
+    """out[b,t,:] = sum_r z[b*J + perm[t,r], r*c:(r+1)*c] -> (B, J, c): rearrange_module's slot sum taken after the product
+    with the stacked slot weights (include/pn2_ext.h: pn2x_perm_sum_rows).  perm: (J, re) int32 on the CPU."""
+    B, J, re, ldz = _perm_args(z, perm, c, "perm_sum_rows")
+    out = torch.empty((B, J, c), dtype=torch.float32, device=z.device)
+    with torch.cuda.device(z.device):
+        _native._check(_lib.pn2x_perm_sum_rows(B, J, re, c, z.data_ptr(), ldz, perm.data_ptr(), out.data_ptr(), _native._stream(z)),
+                       "perm_sum_rows")
+    return out
+
+
+def add_layernorm_perm(z: torch.Tensor, perm: torch.Tensor, ln1, bias: torch.Tensor = None, ln2=None) -> torch.Tensor:
+    """LN2(LN1(perm_sum_rows(z, perm, C) + bias)) -> (B*J, C) in one launch (include/pn2_ext.h: pn2x_add_layernorm_perm);
+    C is the LayerNorms' width, ln2 and bias optional."""
+    C = int(ln1.normalized_shape[-1])
+    f32 = torch.float32
+    for ln in (ln1, ln2):
+        if ln is not None and (tuple(ln.normalized_shape) != (C,) or ln.weight is None or ln.bias is None):
+            raise ValueError("add_layernorm_perm: LayerNorm over the last dimension with affine parameters expected")
+    B, J, re, ldz = _perm_args(z, perm, C, "add_layernorm_perm")
+    pb = None if bias is None else _native._ptr(bias, "bias", f32, C)
+    g1, b1 = _native._ptr(ln1.weight, "ln1.weight", f32, C), _native._ptr(ln1.bias, "ln1.bias", f32, C)
+    g2 = b2 = None
+    eps2 = 0.0
+    if ln2 is not None:
+        g2, b2, eps2 = _native._ptr(ln2.weight, "ln2.weight", f32, C), _native._ptr(ln2.bias, "ln2.bias", f32, C), ln2.eps
+    out = torch.empty((B * J, C), dtype=f32, device=z.device)
+    with torch.cuda.device(z.device):
+        _native._check(_lib.pn2x_add_layernorm_perm(B, J, re, C, z.data_ptr(), ldz, perm.data_ptr(), pb, g1, b1, ln1.eps, g2, b2, eps2,
+                                                    out.data_ptr(), _native._stream(z)), "add_layernorm_perm")
+    return out
+
+
 def pose_head(h: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, xyz1: torch.Tensor, R: torch.Tensor, t: torch.Tensor, scale: float,
               nonfinite: torch.Tensor = None):
     """h (B*J, C), w (3, C), bias (3,), xyz1 (B,J,3), R (B,3,3), t (B,3,1) -> (kp_hand (B,J,3), kp_cam (B,J,3)):

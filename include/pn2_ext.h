@@ -287,6 +287,22 @@ int pn2x_add_layernorm(long rows, int c, const float *x, const float *y, const f
                        const float *b1, float eps1, const float *g2, const float *b2, float eps2, float *out, void *stream);
 
 /*
+ * rearrange_module (blocks.py) mixes each of j tokens with re - 1 neighbours: out = [f[perm[t,0]] | .. | f[perm[t,re-1]]] W^T.
+ * The sum over slots commutes with the gather, so the product runs on the un-gathered tokens against the stacked slot blocks
+ * (z = f [W_0 | .. | W_re-1]^T, (b*j) x (re*c), row stride ldz >= re*c floats) and these entries add the permuted slices:
+ *   pn2x_perm_sum_rows      out[b,t,:] = sum_r z[b, perm[t,r], r*c : (r+1)*c]        (out (b, j, c) contiguous)
+ *   pn2x_add_layernorm_perm out[b,t,:] = LN2( LN1( that sum + bias ) )               (pn2x_add_layernorm's arithmetic; c <= 1024)
+ * summed in the order r = 0 .. re-1.  perm is a HOST table, (j, re) int32 row-major, j <= 256, j*re <= 512: the entry checks
+ * every entry against [0, j) while it packs the table into the kernel arguments (PN2_EINVAL, nothing launched), so no launch
+ * reads a table from device memory and a captured graph holds its own copy.  c % 4 == 0; pn2x_perm_sum_rows moves 16 bytes per
+ * lane: z and out 16-byte aligned, ldz % 4 == 0.  bias and the second LayerNorm (g2, b2 both NULL) are optional.
+ */
+int pn2x_perm_sum_rows(int b, int j, int re, int c, const float *z, int ldz, const int *perm, float *out, void *stream);
+int pn2x_add_layernorm_perm(int b, int j, int re, int c, const float *z, int ldz, const int *perm, const float *bias,
+                            const float *g1, const float *b1, float eps1, const float *g2, const float *b2, float eps2,
+                            float *out, void *stream);
+
+/*
  * Head of HandTrackNet (hand_network.py:141-147): delta = h W^T + bias (W (3, c): the last Conv1d), kp_hand = delta +
  * xyz1, kp_cam = (kp_hand R^T) * scale + t.  h (b*j, c) token-major; xyz1, kp_hand, kp_cam (b, j, 3); R (b,3,3); t (b,3,1).
  * nonfinite: the per-cloud flags of pn2x_hand_frame (or NULL): flagged frames get NaN keypoints in both frames.

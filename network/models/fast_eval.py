@@ -41,6 +41,11 @@ def _lin(x2d: torch.Tensor, W: torch.Tensor, b: torch.Tensor = None) -> torch.Te
 
 class FastEval:
     MAX_POINTS = 16384  # the register-resident FPS with the prefix shortcut covers clouds up to 1024 x 16 points
+    # rearrange_module's slot sum taken after its product: r1 folded into q2's centre product (one GEMM on the un-gathered tokens +
+    # ext.perm_sum_rows), r2's slot sum inside the first LayerNorm launch (ext.add_layernorm_perm).  False: gather_rows + the
+    # (tokens x 5C) GEMMs, as before
+    fold_rearrange = True
+    fold_r2 = True  # with fold_rearrange, on the large-batch route: False keeps r2 as gather_rows + one GEMM
 
     def __init__(self, net):
         self.net = net
@@ -199,6 +204,21 @@ class FastEval:
         P["head_w"] = net.final_mlp[2].weight.detach().squeeze(-1).contiguous()  # (3, 256)
         P["r1"] = (net.r1.linear.weight.detach().squeeze(-1), net.r1.linear.bias.detach(), net.r1._perm.t().contiguous())
         P["r2"] = (net.r2.linear.weight.detach().squeeze(-1), net.r2.linear.bias.detach(), net.r2._perm.t().contiguous())
+        # The slot sum of rearrange_module commutes with its gather: sum_r W_r f[perm[t,r]] = sum_r (f W_r^T)[perm[t,r]], so the
+        # product runs on the un-gathered tokens against the stacked slot blocks and the permuted slices are added where the result is
+        # read.  r1 feeds only q2's centre term (no nonlinearity between): wc2 . Wr1_r is one matrix per slot (formed in fp64) and
+        # wc2 . br1 joins q2's layer-1 bias (a copy; the module's parameters stay as they are).  The tables are read on the host.
+        Wr1, br1, perm1 = P["r1"]
+        Wr2, _, perm2 = P["r2"]
+        re1, re2 = perm1.shape[1], perm2.shape[1]
+        wc2 = P["wc2"].double()
+        P["r1c"] = torch.cat([wc2 @ w for w in Wr1.double().chunk(re1, dim=1)], dim=0).float().contiguous()  # (re*2*c1q, C)
+        cb = (wc2 @ br1.double()).float()
+        c1 = q[("q2", 0)]["b1"].shape[0]
+        for i in range(2):
+            q[("q2", i)]["b1r"] = (q[("q2", i)]["b1"] + cb[i * c1:(i + 1) * c1]).contiguous()
+        P["r2s"] = torch.cat(Wr2.chunk(re2, dim=1), dim=0).contiguous()  # (re*C, C)
+        P["perm_host"] = (perm1.to("cpu", torch.int32).contiguous(), perm2.to("cpu", torch.int32).contiguous())
         self.P, self._key = P, key
         return P
 
@@ -216,14 +236,14 @@ class FastEval:
         return self._idents[key]
 
     @staticmethod
-    def _q_scales(ext, name, plan, q, xyz1, c1q, a_col, cadd, out, c_q):
+    def _q_scales(ext, name, plan, q, xyz1, c1q, a_col, cadd, out, c_q, b1="b1"):
         """The scales of one keypoint-query module: both in ONE persistent launch when there are two (ext.sa_mlp_max_pair,
         which itself falls back to one launch per scale for combinations its kernel does not cover)."""
         probs = []
         for i, (idx, a, nb_xyz) in enumerate(plan):
             p = q[(name, i)]
             probs.append(dict(idx=idx, w2=p["l2"][0], b2=p["l2"][1], w3=p["l3"][0], b3=p["l3"][1], a1f=a[:, :, a_col:a_col + c1q],
-                              xyz=nb_xyz, cxyz=xyz1, wx=p["wx"], b1=p["b1"],
+                              xyz=nb_xyz, cxyz=xyz1, wx=p["wx"], b1=p[b1],
                               cadd=None if cadd is None else cadd[:, :, i * c1q:(i + 1) * c1q], out=out[:, :, i * c_q:(i + 1) * c_q]))
         if len(probs) == 2:
             ext.sa_mlp_max_pair(*probs)
@@ -417,19 +437,30 @@ class FastEval:
             plan.append((idx, a_all[:, :, 2 * c1q * j:2 * c1q * (j + 1)], xyz2))
         f11 = torch.empty((B, J, 2 * c_q), **f32)
         self._q_scales(ext, "q1", plan, q, xyz1, c1q, 0, None, f11, c_q)
-        Wr, br, perm = P["r1"]
-        f12 = _lin(ext.gather_rows(f11, self._perm_idx(perm, B)).view(B * J, -1), Wr, br)  # (B*J, C)
-        cadd = _lin(f12, P["wc2"]).view(B, J, -1)
+        fold = self.fold_rearrange
         f13 = torch.empty((B, J, 2 * c_q), **f32)
-        self._q_scales(ext, "q2", plan, q, xyz1, c1q, c1q, cadd, f13, c_q)
+        if fold:
+            # r1 and q2's centre product as one GEMM on the un-gathered tokens; the five permuted slices are added afterwards
+            cadd = ext.perm_sum_rows(_lin(f11.view(B * J, -1), P["r1c"]), P["perm_host"][0], 2 * c1q)
+            self._q_scales(ext, "q2", plan, q, xyz1, c1q, c1q, cadd, f13, c_q, b1="b1r")
+        else:
+            Wr, br, perm = P["r1"]
+            f12 = _lin(ext.gather_rows(f11, self._perm_idx(perm, B)).view(B * J, -1), Wr, br)  # (B*J, C)
+            cadd = _lin(f12, P["wc2"]).view(B, J, -1)
+            self._q_scales(ext, "q2", plan, q, xyz1, c1q, c1q, cadd, f13, c_q)
         Wr, br, perm = P["r2"]
-        f14 = _lin(ext.gather_rows(f13, self._perm_idx(perm, B)).view(B * J, -1), Wr, br)
+        small = ext.ln_linear_supported(B * J, Wr.shape[0])
+        fold2 = fold and self.fold_r2 and not small
+        if fold2:
+            z14 = _lin(f13.view(B * J, -1), P["r2s"])  # r2's slot sum rides in the first LayerNorm launch below
+        else:  # (few tokens: r2 stays the gather + one GEMM in front of ln_linear)
+            f14 = _lin(ext.gather_rows(f13, self._perm_idx(perm, B)).view(B * J, -1), Wr, br)
 
         # ---- "TransT" with attn=False: only LayerNorms and FFNs are live; the element-wise runs between the GEMMs
         # (residual add, bias, one or two LayerNorms) are one launch each --------------------------------------
         s11, c11, c3 = net.transt.s11, net.transt.c11, net.c3
         wf, bf = net.final_mlp[0].weight.squeeze(-1), net.final_mlp[0].bias
-        if ext.ln_linear_supported(f14.shape[0], f14.shape[1]):
+        if small:
             # few tokens (the tracking loop, B <= 12): every launch here sits at the floor of a graph node, so each LayerNorm launch rides in
             # the Linear that consumes it (pn2x_ln_linear_small: same bits as the two launches) -- 9 launches -> 6
             x, hdn = ext.ln_linear(f14, s11.norm1, c11.linear1.weight, c11.linear1.bias, relu=True, ln2=c11.norm1)
@@ -438,7 +469,10 @@ class FastEval:
             y = _lin(hdn, c3.linear2.weight)
             x, hdn = ext.ln_linear(x, c3.norm2, wf, bf, relu=True, y=y, ybias=c3.linear2.bias)
         else:
-            x = ext.add_layernorm(f14, s11.norm1, ln2=c11.norm1)
+            if fold2:
+                x = ext.add_layernorm_perm(z14, P["perm_host"][1], s11.norm1, bias=br, ln2=c11.norm1)
+            else:
+                x = ext.add_layernorm(f14, s11.norm1, ln2=c11.norm1)
             for blk, nxt in ((c11, c3.norm1), (c3, None)):
                 hdn = _lin_relu(x, blk.linear1.weight, blk.linear1.bias)
                 x = ext.add_layernorm(x, blk.norm2, y=_lin(hdn, blk.linear2.weight), bias=blk.linear2.bias, ln2=nxt)
