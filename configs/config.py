@@ -53,6 +53,7 @@ def get_config(args, save=True):
     cfg.setdefault("hand_interaction_eval", False)  # hand-object penetration / contact columns (--hand_interaction_eval)
     cfg["opt"].setdefault("contact_threshold", 0.005)  # metres: a fingertip region this near the surface is in contact
     cfg["opt"].setdefault("accumulate_surface", False)  # obj_opt: keep the observed surface of each sequence (--accumulate_obj_surface)
+    cfg["opt"].setdefault("extract_mesh", False)  # obj_opt: extract the mesh of each sequence's SDF volume (--extract_obj_mesh)
     data_cfg = _load("data_config", cfg["data_config"])
     cfg["pointnet"] = {k: _load("pointnet_config", v) for k, v in cfg["pointnet_cfg"].items()}
 

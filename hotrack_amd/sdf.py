@@ -7,6 +7,7 @@ Mirrors, function for function, the reference methods it replaces:
   query_sdf         gf_optimize_hand_pose.query_sdf              network/models/optimization_hand.py:252-262
   penetration_loss  ... .get_penetration_loss(query_sdf(hand))   :264-268 (fused with the lookup)
   mesh_signed_distance / mesh_sdf_volume   load_obj_oracle (mesh -> volume; kaolin there)   optimization_obj.py:163-182
+  volume_mesh       gf_optimize_obj.sdf2mesh (volume -> mesh; marching cubes over the decoder there)   :399-405
 """
 from __future__ import annotations
 
@@ -367,3 +368,48 @@ def mesh_sdf_volume(verts: torch.Tensor, faces: torch.Tensor, res: int = 201, vo
     _native._check(rc, "sdf.mesh_sdf_volume")
     _mesh_faces_ok(work, "sdf.mesh_sdf_volume")
     return out
+
+
+# ---- signed distance volume -> mesh (hotrack_amd/csrc/sdf_mesh.hip) -------------------------------------------------------------
+_lib.pn2s_volume_mesh_work_bytes.argtypes = [_ci]
+_lib.pn2s_volume_mesh_work_bytes.restype = _cl
+_lib.pn2s_volume_mesh_count.argtypes = [_vp, _ci, _ci, _cf, _cf, _vp, _cl, _vp]
+_lib.pn2s_volume_mesh_count.restype = _ci
+_lib.pn2s_volume_mesh_emit.argtypes = [_vp, _ci, _ci, _cf, _cf, _vp, _cl, _ci, _ci, _vp, _vp, _vp]
+_lib.pn2s_volume_mesh_emit.restype = _ci
+VOLUME_MESH_MAX_RES = 512
+
+
+def volume_mesh_work_bytes(res: int) -> int:
+    """Bytes of scratch volume_mesh needs at resolution res (pn2s_volume_mesh_work_bytes): an int32 and a byte per voxel."""
+    need = _lib.pn2s_volume_mesh_work_bytes(int(res))
+    if need < 0:
+        raise ValueError(f"res must lie in [2, {VOLUME_MESH_MAX_RES}], got {res}")
+    return need
+
+
+def volume_mesh(sdf_volume: torch.Tensor, voxel_scale: float, level: float = 0.0):
+    """The level set of a (res,res,res) fp16 / fp32 SDF volume as a welded, outward-oriented triangle mesh (marching tetrahedra;
+    include/pn2_sdf.h: pn2s_volume_mesh_count / pn2s_volume_mesh_emit) -> (verts float32 (nv,3), faces int32 (nf,3)) on the
+    volume's device, in the grid of mesh_sdf_volume (voxel centre ((ix,iy,iz) - res//2) * voxel_scale).  The order of vertices
+    and triangles is fixed by the algorithm; a volume with no crossing returns (0,3) / (0,3).  Synchronises once (the two counts)."""
+    if isinstance(sdf_volume, torch.Tensor) and sdf_volume.dim() != 3:
+        raise ValueError(f"sdf volume must be (res,res,res), got shape {tuple(sdf_volume.shape)}")
+    pv, f16, res = _linear_volume(sdf_volume)
+    voxel_scale, level = float(voxel_scale), float(level)
+    if not (voxel_scale > 0 and voxel_scale != float("inf")) or level != level or abs(level) == float("inf"):
+        raise ValueError(f"voxel_scale must be finite and > 0 and level finite, got {voxel_scale} and {level}")
+    need = volume_mesh_work_bytes(res)
+    device = sdf_volume.device
+    work = torch.empty((need // 4 + 1,), dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        st = _native._stream(sdf_volume)
+        rc = _lib.pn2s_volume_mesh_count(pv, f16, res, voxel_scale, level, work.data_ptr(), work.numel() * 4, st)
+        _native._check(rc, "sdf.volume_mesh")
+        nv, nf = work[:2].tolist()  # the one read-back
+        verts = torch.empty((nv, 3), dtype=_f32, device=device)
+        faces = torch.empty((nf, 3), dtype=torch.int32, device=device)
+        rc = _lib.pn2s_volume_mesh_emit(pv, f16, res, voxel_scale, level, work.data_ptr(), work.numel() * 4, nv, nf,
+                                        verts.data_ptr() if nv else None, faces.data_ptr() if nf else None, st)
+        _native._check(rc, "sdf.volume_mesh")
+    return verts, faces

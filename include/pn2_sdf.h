@@ -153,6 +153,36 @@ int pn2s_mesh_sdf_points(int m, const float *pts, int nv, const float *verts, in
 int pn2s_mesh_sdf_volume(int nv, const float *verts, int nf, const int *faces, int res, float stride, float clamp, void *out,
                          int out_f16, float *work, long work_floats, void *stream);
 
+/*
+ * SDF volume -> triangle mesh -- the way back from the volumes above to a surface (the reference: gf_optimize_obj.sdf2mesh,
+ * optimization_obj.py:399-405, marching cubes over its decoder; here marching tetrahedra over the volume itself, so that the
+ * output is fixed index for index; hotrack_amd/csrc/sdf_mesh.hip states the algorithm).
+ *   Grid vertex (ix,iy,iz) is inside iff its value < level (fp32; binary16 converts exactly).  Every cell is split into six
+ *   tetrahedra round its body diagonal; an edge of that grid whose endpoints differ in the inside flag carries one mesh vertex,
+ *   shared by every tetrahedron round it, at  p_a + t (p_b - p_a),  t = (level - s_a) / (s_b - s_a)  with a the lower endpoint and
+ *   p = ((ix,iy,iz) - res/2) * stride, the grid of pn2s_mesh_sdf_volume.  Triangles face outwards (towards increasing value).
+ *   Vertices come in ascending key 7 * linear(lower endpoint) + edge class, triangles in ascending (cell, tetrahedron, triangle):
+ *   nothing depends on launch order, and two runs are bitwise equal.  A value exactly at `level` puts coincident vertices on
+ *   the grid vertex and gives zero-area triangles; the mesh stays closed wherever the surface does not leave the volume.
+ * Two calls, because the caller allocates the outputs:
+ *   pn2s_volume_mesh_count  three launches (count, scan of the workgroup sums by ONE workgroup, apply); on return -- in stream
+ *                           order -- the ints at work[0] and work[1] are the numbers of vertices and of triangles.  The caller
+ *                           reads those two words back (its one synchronisation) and allocates verts (nv,3) and faces (nf,3);
+ *   pn2s_volume_mesh_emit   one launch, with the SAME vol, vol_f16, res, level and the work buffer as pn2s_volume_mesh_count
+ *                           left it.  Nothing is written past nv vertices or nf triangles whatever the buffer holds.
+ *                           nv == nf == 0 is a no-op.
+ * work: at least pn2s_volume_mesh_work_bytes(res) bytes, 16-byte aligned: an int32 prefix and a mask byte per voxel and two
+ *   ints per 256 voxels (201^3: 40.7 MB).
+ * Refused with nothing launched: res < 2, stride not finite or <= 0, level not finite, vol_f16 not 0 / 1 (PN2_EINVAL);
+ *   res > 512 (PN2_ERANGE: beyond it 12 res^3 triangle slots leave an int32; keys 7 res^3 are never formed on the device);
+ *   work_bytes too small (PN2_ESCRATCH).
+ */
+long pn2s_volume_mesh_work_bytes(int res);
+int pn2s_volume_mesh_count(const void *vol, int vol_f16, int res, float stride, float level, void *work, long work_bytes,
+                           void *stream);
+int pn2s_volume_mesh_emit(const void *vol, int vol_f16, int res, float stride, float level, const void *work, long work_bytes,
+                          int nv, int nf, float *verts, int *faces, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -267,6 +267,163 @@ def sample_surface(verts, faces, n: int, seed: int = 0) -> torch.Tensor:
     return (a[pick] + (b[pick] - a[pick]) * (s * (1 - r[:, 1:])) + (c[pick] - a[pick]) * (s * r[:, 1:])).float()
 
 
+# ---- volume -> mesh -----------------------------------------------------------------------------------------------------------
+# Marching tetrahedra on the Kuhn split of every cell (hotrack_amd/csrc/sdf_mesh.hip states the algorithm).
+# A cell's corner is named by offset bits x = 1, y = 2, z = 4.
+_VM_CLASS_BITS = (1, 2, 4, 3, 5, 6, 7)                                # edge class -> offset: +x +y +z +xy +xz +yz +xyz
+_VM_TETS = ((0, 1, 3, 7), (0, 1, 5, 7), (0, 2, 3, 7), (0, 2, 6, 7), (0, 4, 5, 7), (0, 4, 6, 7))  # xyz xzy yxz yzx zxy zyx
+_VM_EDGES = ((0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3))          # of a tetrahedron's corners
+_vm_tables = {}
+
+
+def _vm_tet_table(corners):
+    """(16,6) edge ids: for every inside set of the tetrahedron with these corner bits, the corners of triangle 0 and of
+    triangle 1 as edges of the tetrahedron, outward oriented.  One inside (or outside) corner i, the others j < k < l: the
+    edges (i,j) (i,k) (i,l).  Two inside i < j, two outside k < l: the quad (i,k) (i,l) (j,l) (j,k) cut along (i,k)-(j,l).  A
+    triangle that faces inwards has its last two corners swapped; that is decided here in integers, on twice the edges'
+    midpoints against (outside corners' centroid - inside corners' centroid) scaled by the two counts."""
+    xyz = [[(c >> d) & 1 for d in range(3)] for c in corners]
+    mid2 = lambda e: [xyz[_VM_EDGES[e][0]][d] + xyz[_VM_EDGES[e][1]][d] for d in range(3)]
+    eid = lambda p, q: _VM_EDGES.index((min(p, q), max(p, q)))
+    table = [[0] * 6 for _ in range(16)]
+    for m in range(1, 15):
+        ins = [i for i in range(4) if (m >> i) & 1]
+        outs = [i for i in range(4) if not (m >> i) & 1]
+        if len(ins) == 2:
+            (i, j), (k, l) = ins, outs
+            tris = [[eid(i, k), eid(i, l), eid(j, l)], [eid(i, k), eid(j, l), eid(j, k)]]
+        else:
+            lone, rest = (ins[0], outs) if len(ins) == 1 else (outs[0], ins)
+            tris = [[eid(lone, r) for r in rest]]
+        outward = [len(ins) * sum(xyz[i][d] for i in outs) - len(outs) * sum(xyz[i][d] for i in ins) for d in range(3)]
+        row = []
+        for tri in tris:
+            p0, p1, p2 = (mid2(e) for e in tri)
+            a, b = [p1[d] - p0[d] for d in range(3)], [p2[d] - p0[d] for d in range(3)]
+            n = (a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0])
+            s = sum(n[d] * outward[d] for d in range(3))
+            assert s != 0
+            row += tri if s > 0 else [tri[0], tri[2], tri[1]]
+        table[m][:len(row)] = row
+    return table
+
+
+def volume_mesh_torch(volume, voxel_scale: float, level: float = 0.0):
+    """The algorithm of hotrack_amd/csrc/sdf_mesh.hip as torch operations (any device): per-voxel masks of owned crossing
+    edges, their exclusive prefix, and the same popcount look-up of a triangle's corners -> (verts fp32 (nv,3), faces int32
+    (nf,3)), the kernel's output index for index."""
+    V = volume.detach().float()
+    dev = V.device
+    res = V.shape[0]
+    i64 = dict(dtype=torch.int64, device=dev)
+    vs = torch.tensor(float(voxel_scale), dtype=torch.float32, device=dev)
+    lv = torch.tensor(float(level), dtype=torch.float32, device=dev)
+    inside = V < lv
+    bits = lambda o: ((o & 1), (o >> 1) & 1, o >> 2)
+    lin_off = lambda o: (o & 1) * res * res + ((o >> 1) & 1) * res + (o >> 2)
+    mask = torch.zeros((res, res, res), **i64)
+    for c, o in enumerate(_VM_CLASS_BITS):
+        lo = tuple(slice(0, res - b) for b in bits(o))
+        hi = tuple(slice(b, res) for b in bits(o))
+        mask[lo] |= (inside[lo] != inside[hi]).to(torch.int64) << c
+    mask = mask.reshape(-1)
+    popc = torch.tensor([bin(i).count("1") for i in range(128)], **i64)
+    count = popc[mask]
+    prefix = torch.cumsum(count, 0) - count
+    verts = torch.empty((int(count.sum()), 3), dtype=torch.float32, device=dev)
+    flat = V.reshape(-1)
+    for c, o in enumerate(_VM_CLASS_BITS):
+        v = torch.nonzero((mask >> c) & 1).reshape(-1)
+        if v.numel() == 0:
+            continue
+        sa, sb = flat[v], flat[v + lin_off(o)]
+        t = (lv - sa) / (sb - sa)
+        ijk = torch.stack([v // (res * res), (v // res) % res, v % res], dim=1)
+        pa = (ijk - res // 2).to(torch.float32) * vs
+        step = torch.tensor(bits(o), dtype=torch.float32, device=dev) * vs
+        verts[prefix[v] + popc[mask[v] & ((1 << c) - 1)]] = pa + t[:, None] * step
+    # the cells that hold a crossing, in ascending linear index, and the corner flags of each as a byte
+    code = torch.zeros((res - 1,) * 3, **i64)
+    for o in range(8):
+        code |= inside[tuple(slice(b, res - 1 + b) for b in bits(o))].to(torch.int64) << o
+    cells = torch.nonzero((code > 0) & (code < 255))
+    code = code[cells[:, 0], cells[:, 1], cells[:, 2]]
+    lin = (cells[:, 0] * res + cells[:, 1]) * res + cells[:, 2]
+    if "tets" not in _vm_tables:
+        _vm_tables["tets"] = [_vm_tet_table(t) for t in _VM_TETS]
+    ntri_of = torch.tensor([{0: 0, 1: 1, 2: 2, 3: 1, 4: 0}[bin(m).count("1")] for m in range(16)], **i64)
+    m4 = torch.stack([sum(((code >> t[i]) & 1) << i for i in range(4)) for t in _VM_TETS], dim=1)  # (cells, 6)
+    ntri = ntri_of[m4]
+    start = (torch.cumsum(ntri.reshape(-1), 0) - ntri.reshape(-1)).reshape(-1, 6)
+    faces = torch.empty((int(ntri.sum()), 3), dtype=torch.int32, device=dev)
+    class_of = torch.tensor([0, 0, 1, 3, 2, 4, 5, 6], **i64)  # offset bits -> edge class
+    ep = torch.tensor([e[0] for e in _VM_EDGES], **i64)
+    eq = torch.tensor([e[1] for e in _VM_EDGES], **i64)
+    for k, tet in enumerate(_VM_TETS):
+        table = torch.tensor(_vm_tables["tets"][k], **i64)
+        corner = torch.tensor(tet, **i64)
+        for j in range(2):
+            sel = torch.nonzero(ntri[:, k] > j).reshape(-1)
+            if sel.numel() == 0:
+                continue
+            for q in range(3):
+                e = table[m4[sel, k], 3 * j + q]
+                lo, hi = corner[ep[e]], corner[eq[e]]
+                at = lin[sel] + (lo & 1) * res * res + ((lo >> 1) & 1) * res + (lo >> 2)
+                below = (torch.ones_like(lo) << class_of[hi ^ lo]) - 1
+                faces[start[sel, k] + j, q] = (prefix[at] + popc[mask[at] & below]).to(torch.int32)
+    return verts, faces
+
+
+def volume_to_mesh(volume, voxel_scale: float, level: float = 0.0, route=None):
+    """The level set of a (res,res,res) SDF volume as a welded, outward-oriented triangle mesh in the volume's grid (voxel centre
+    ((ix,iy,iz) - res//2) * voxel_scale) -> (verts fp32 (nv,3), faces int32 (nf,3)) on the volume's device: the reference's
+    sdf2mesh (optimization_obj.py:399-405) on the volume itself.  The kernel route (hotrack_amd.sdf.volume_mesh) takes fp16 /
+    fp32 GPU volumes; the torch route anything else, or route='torch'.  Both give the same vertices (to fp32 rounding) in the
+    same order and the same faces; a volume with no crossing gives (0,3) / (0,3)."""
+    volume = torch.as_tensor(volume)
+    if volume.dim() != 3 or tuple(volume.shape) != (volume.shape[0],) * 3 or volume.shape[0] < 2:
+        raise ValueError(f"volume must be (res,res,res) with res >= 2, got shape {tuple(volume.shape)}")
+    if not (float(voxel_scale) > 0 and math.isfinite(float(voxel_scale)) and math.isfinite(float(level))):
+        raise ValueError(f"voxel_scale must be finite and > 0 and level finite, got {voxel_scale} and {level}")
+    kernel = route != "torch"
+    if kernel:
+        why = (f"the volume is on {volume.device.type}" if not volume.is_cuda else
+               f"the volume is {volume.dtype}" if volume.dtype not in (torch.float16, torch.float32) else None)
+        if why is not None:
+            if route == "kernel":
+                raise RuntimeError(f"volume_to_mesh: the kernel route needs an fp16 / fp32 GPU volume ({why})")
+            if why not in _said:
+                _said.add(why)
+                print(f"[Mesh SDF] the torch route runs: {why}")
+            kernel = False
+    if kernel:
+        from hotrack_amd import sdf
+        return sdf.volume_mesh(volume.contiguous(), float(voxel_scale), float(level))
+    return volume_mesh_torch(volume, voxel_scale, level)
+
+
+def save_mesh(path, verts, faces) -> None:
+    """Write a triangle mesh as binary little-endian PLY (float x y z; uchar-counted int index lists) or, for a path ending in
+    .obj, as Wavefront OBJ; `load_mesh` reads either back (the PLY bit for bit)."""
+    v = np.ascontiguousarray(torch.as_tensor(verts).detach().cpu().numpy(), dtype="<f4").reshape(-1, 3)
+    f = np.ascontiguousarray(torch.as_tensor(faces).detach().cpu().numpy(), dtype="<i4").reshape(-1, 3)
+    path = str(path)
+    if path.lower().endswith(".obj"):
+        with open(path, "w") as fh:
+            fh.writelines("v %.9g %.9g %.9g\n" % tuple(p) for p in v.tolist())
+            fh.writelines("f %d %d %d\n" % (a + 1, b + 1, c + 1) for a, b, c in f.tolist())
+        return
+    rows = np.empty(len(f), dtype=[("n", "u1"), ("i", "<i4", (3,))])
+    rows["n"], rows["i"] = 3, f
+    header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+              "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % (len(v), len(f)))
+    with open(path, "wb") as fh:
+        fh.write(header.encode("ascii"))
+        fh.write(v.tobytes())
+        fh.write(rows.tobytes())
+
+
 # ---- the trackers' side -------------------------------------------------------------------------------------------------------
 _volumes = {}  # (mesh key, res, voxel_scale, device) -> volume; a dataset that repeats an object does not rebuild
 

@@ -49,6 +49,18 @@ class gf_optimize_obj:
         self.sdf_volume = sdf_volume.to(self.device).contiguous()
         self._corners = _sdf.CornerVolume(self.sdf_volume)  # lookup layout (8x memory, same results), built once per object
 
+    def sdf2mesh(self, mesh_filename=None, level: float = 0.0, route=None):
+        """The triangle mesh of the loaded volume's `level` set (the reference's sdf2mesh, :399-405, which decodes its latent on
+        a 128^3 grid and runs marching cubes; here the volume the tracker looks up is extracted, models/mesh_sdf.volume_to_mesh).
+        Writes it to `mesh_filename` (PLY, or OBJ by extension) when one is given.  Returns (verts fp32 (nv,3), faces int32 (nf,3))."""
+        if self.sdf_volume is None:
+            raise RuntimeError("sdf2mesh: no SDF volume is loaded (load_volume)")
+        from . import mesh_sdf
+        verts, faces = mesh_sdf.volume_to_mesh(self.sdf_volume, self.voxel_scale, level, route=route)
+        if mesh_filename is not None:
+            mesh_sdf.save_mesh(mesh_filename, verts, faces)
+        return verts, faces
+
     def Distance(self, V):  # noqa: N802 (reference name)
         return _sdf.distance(V.float(), self._corners, self.voxel_scale)
 

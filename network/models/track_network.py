@@ -640,6 +640,10 @@ class ObjTrackModel_Optimization(nn.Module):
         self._front_end = _FrontEndSlot(cfg)  # frames that carry a depth image instead of obj_points (models/frame_frontend.py)
         # opt.accumulate_surface: keep each sequence's observed surface (models/obs_surface.py); the poses do not depend on it
         self.accumulate_surface = bool((cfg.get("opt") or {}).get("accumulate_surface", False))
+        # opt.extract_mesh: at the end of a sequence extract the mesh of its SDF volume (models/mesh_sdf.volume_to_mesh); the poses
+        # do not depend on it.  extract_mesh_route: None (the kernel for a GPU volume), 'kernel' or 'torch'
+        self.extract_mesh = bool((cfg.get("opt") or {}).get("extract_mesh", False))
+        self.extract_mesh_route = None
         self.surface_seed = 0  # every sequence draws from a generator of its own with this seed: alone or in a group, the same surface
         self.save_folder = cfg.get("save_dir")
 
@@ -656,6 +660,27 @@ class ObjTrackModel_Optimization(nn.Module):
     def _surface_entry(surf, corner_volume, voxel_scale):
         from .obs_surface import surface_fit
         return dict(surf.state(), fit=surface_fit(surf.points, surf.normals, corner_volume, voxel_scale))
+
+    def _attach_mesh(self, input, rets, volume, voxel_scale, flag_dict, shared=None):
+        """opt.extract_mesh, at the end of a sequence (the reference: optimizer.sdf2mesh, track_network.py:380-381): the mesh of
+        the sequence's SDF volume goes into rets[0]['obj_info'] = {'recon_path', 'recon_mesh': {'vertices', 'faces'}}.  With
+        --save and a save directory the mesh is written as <sequence>_recon.ply and 'recon_path' names the file (else None).
+        `shared` maps id(volume) to a mesh already extracted: sequences of a group that share a volume share one extraction."""
+        import os
+        from . import mesh_sdf
+        hit = None if shared is None else shared.get(id(volume))
+        if hit is None:
+            verts, faces = mesh_sdf.volume_to_mesh(volume, voxel_scale, 0.0, route=getattr(self, "extract_mesh_route", None))
+            hit = (volume, {"vertices": verts, "faces": faces})  # (the volume is kept with the mesh: the key's id stays its)
+            if shared is not None:
+                shared[id(volume)] = hit
+        path = None
+        if flag_dict.get("save_flag") and getattr(self, "save_folder", None):
+            name = os.path.dirname(input[0]["file_name"][0]) or input[0]["file_name"][0]
+            os.makedirs(self.save_folder, exist_ok=True)
+            path = os.path.join(self.save_folder, name.replace("/", "_") + "_recon.ply")
+            mesh_sdf.save_mesh(path, hit[1]["vertices"], hit[1]["faces"])
+        rets[0]["obj_info"] = {"recon_path": path, "recon_mesh": hit[1]}
 
     def forward(self, input, flag_dict):
         flag_dict["track_flag"] = True
@@ -691,6 +716,8 @@ class ObjTrackModel_Optimization(nn.Module):
             rets.append(ret)
         if surf is not None:
             rets[0]["obj_surface"] = self._surface_entry(surf, self.optimizer._corners, self.optimizer.voxel_scale)
+        if getattr(self, "extract_mesh", False) and rets:
+            self._attach_mesh(input, rets, self.optimizer.sdf_volume, self.optimizer.voxel_scale, flag_dict)
         return rets
 
     def _sequence_volume(self, frame0, built):
@@ -775,6 +802,11 @@ class ObjTrackModel_Optimization(nn.Module):
         for k in range(S):
             if surfs[k] is not None:
                 rets[k][0]["obj_surface"] = self._surface_entry(surfs[k], vols[k], known[0][1])
+        if getattr(self, "extract_mesh", False):
+            meshes = {}
+            for k in range(S):
+                if rets[k]:
+                    self._attach_mesh(inputs[k], rets[k], vols[k].source, known[0][1], flag_dict, meshes)
         return rets
 
     def compute_loss(self, input, ret_dict_lst, flag_dict):
@@ -796,8 +828,10 @@ class ObjTrackModel_Optimization(nn.Module):
                                                   cloud of more than 2048 points is cut to 2048 by this project's FPS operator
                                                   (the reference: its Python FPS).  Without model points but with a mesh
                                                   ('obj_mesh' / 'obj_mesh_path') 2048 points are sampled from it
-                                                  (mesh_sdf.sample_surface, seed 0); with neither the two keys are absent and
-                                                  the log says so once."""
+                                                  (mesh_sdf.sample_surface, seed 0); with neither, and opt.extract_mesh on, from
+                                                  the mesh extracted from the sequence's volume
+                                                  (ret_dict_lst[0]['obj_info']['recon_mesh']); else the two keys are absent
+                                                  and the log says so once."""
         from . import eval_metrics
         r_err = t_err = a_err = 0.0
         gRs, gts, Rs, ts = [], [], [], []
@@ -830,6 +864,10 @@ class ObjTrackModel_Optimization(nn.Module):
             mesh = mesh_sdf.frame_mesh(input[0], self.device)
             if mesh is not None:
                 model_points = mesh_sdf.sample_surface(mesh[1], mesh[2], 2048, seed=0)
+            else:  # opt.extract_mesh: the mesh extracted from the sequence's own volume stands in
+                recon = (ret_dict_lst[0].get("obj_info") or {}).get("recon_mesh")
+                if recon is not None and recon["faces"].shape[0] > 0:
+                    model_points = mesh_sdf.sample_surface(recon["vertices"], recon["faces"], 2048, seed=0)
         if model_points is not None:
             gt_cloud = self._eval_cloud(model_points)
             pred_cloud = self._eval_cloud(input[0]["obj_recon_points"]) if "obj_recon_points" in input[0] else gt_cloud

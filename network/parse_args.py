@@ -57,6 +57,12 @@ def add_args(parser):
                              "opt.updateobjshape route without its DeepSDF refit) -- and report obs_surface_residual(mm) and "
                              "obs_surface_normal_agree; --save writes the surface into the sequence's pickle.  The tracked poses do "
                              "not depend on it")
+    parser.add_argument("--extract_obj_mesh", dest="opt/extract_mesh", action="store_const", const=True, default=None,
+                        help="track=obj_opt: at the end of a sequence extract the triangle mesh of the sequence's SDF volume "
+                             "(models/mesh_sdf.volume_to_mesh, hotrack_amd/csrc/sdf_mesh.hip; the reference's sdf2mesh) into "
+                             "ret_dict_lst[0]['obj_info']; --save writes it as a PLY ('recon_path').  A sequence that carries "
+                             "neither obj_model_points nor a mesh samples it for the chamfer columns.  The tracked poses do not "
+                             "depend on it")
     parser.add_argument("--obj_mesh", type=str, default=None,
                         help="track the synthetic sequences' clouds against an SDF volume built from this triangle mesh (OBJ or "
                              "PLY, object frame, metres; models/mesh_sdf.py) instead of the analytic capsule volume")
