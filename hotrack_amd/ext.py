@@ -509,6 +509,8 @@ _lib.pn2x_perm_sum_rows.argtypes = [_ci, _ci, _ci, _ci, _vp, _ci, _vp, _vp, _vp]
 _lib.pn2x_perm_sum_rows.restype = _ci
 _lib.pn2x_add_layernorm_perm.argtypes = [_ci, _ci, _ci, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _cf, _vp, _vp, _cf, _vp, _vp]
 _lib.pn2x_add_layernorm_perm.restype = _ci
+_lib.pn2x_add_layernorm_perm_any_slots.argtypes = _lib.pn2x_add_layernorm_perm.argtypes  # the run-time-slot kernel at every re
+_lib.pn2x_add_layernorm_perm_any_slots.restype = _ci
 
 
 def _perm_args(z: torch.Tensor, perm: torch.Tensor, c: int, name: str):
@@ -534,9 +536,10 @@ def perm_sum_rows(z: torch.Tensor, perm: torch.Tensor, c: int) -> torch.Tensor:
     return out
 
 
-def add_layernorm_perm(z: torch.Tensor, perm: torch.Tensor, ln1, bias: torch.Tensor = None, ln2=None) -> torch.Tensor:
+def add_layernorm_perm(z: torch.Tensor, perm: torch.Tensor, ln1, bias: torch.Tensor = None, ln2=None, fixed_slots: bool = True) -> torch.Tensor:
     """LN2(LN1(perm_sum_rows(z, perm, C) + bias)) -> (B*J, C) in one launch (include/pn2_ext.h: pn2x_add_layernorm_perm);
-    C is the LayerNorms' width, ln2 and bias optional."""
+    C is the LayerNorms' width, ln2 and bias optional.  fixed_slots = False: the run-time-slot kernel even at re = 5
+    (pn2x_add_layernorm_perm_any_slots: same bits, for comparison)."""
     C = int(ln1.normalized_shape[-1])
     f32 = torch.float32
     for ln in (ln1, ln2):
@@ -551,8 +554,9 @@ def add_layernorm_perm(z: torch.Tensor, perm: torch.Tensor, ln1, bias: torch.Ten
         g2, b2, eps2 = _native._ptr(ln2.weight, "ln2.weight", f32, C), _native._ptr(ln2.bias, "ln2.bias", f32, C), ln2.eps
     out = torch.empty((B * J, C), dtype=f32, device=z.device)
     with torch.cuda.device(z.device):
-        _native._check(_lib.pn2x_add_layernorm_perm(B, J, re, C, z.data_ptr(), ldz, perm.data_ptr(), pb, g1, b1, ln1.eps, g2, b2, eps2,
-                                                    out.data_ptr(), _native._stream(z)), "add_layernorm_perm")
+        args = (B, J, re, C, z.data_ptr(), ldz, perm.data_ptr(), pb, g1, b1, ln1.eps, g2, b2, eps2, out.data_ptr(), _native._stream(z))
+        _native._check(_lib.pn2x_add_layernorm_perm(*args) if fixed_slots else _lib.pn2x_add_layernorm_perm_any_slots(*args),
+                       "add_layernorm_perm")
     return out
 
 

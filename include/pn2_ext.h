@@ -296,11 +296,17 @@ int pn2x_add_layernorm(long rows, int c, const float *x, const float *y, const f
  * every entry against [0, j) while it packs the table into the kernel arguments (PN2_EINVAL, nothing launched), so no launch
  * reads a table from device memory and a captured graph holds its own copy.  c % 4 == 0; pn2x_perm_sum_rows moves 16 bytes per
  * lane: z and out 16-byte aligned, ldz % 4 == 0.  bias and the second LayerNorm (g2, b2 both NULL) are optional.
+ * pn2x_add_layernorm_perm launches an instance with the slot count fixed at compile time where there is one (re == 5, the
+ * network's: every load of a row in flight at once); pn2x_add_layernorm_perm_any_slots always launches the run-time-slot kernel
+ * that serves every other re.  Same sums in the same order: the two return the same bits.
  */
 int pn2x_perm_sum_rows(int b, int j, int re, int c, const float *z, int ldz, const int *perm, float *out, void *stream);
 int pn2x_add_layernorm_perm(int b, int j, int re, int c, const float *z, int ldz, const int *perm, const float *bias,
                             const float *g1, const float *b1, float eps1, const float *g2, const float *b2, float eps2,
                             float *out, void *stream);
+int pn2x_add_layernorm_perm_any_slots(int b, int j, int re, int c, const float *z, int ldz, const int *perm, const float *bias,
+                                      const float *g1, const float *b1, float eps1, const float *g2, const float *b2, float eps2,
+                                      float *out, void *stream);
 
 /*
  * Head of HandTrackNet (hand_network.py:141-147): delta = h W^T + bias (W (3, c): the last Conv1d), kp_hand = delta +
