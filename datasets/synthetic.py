@@ -133,7 +133,8 @@ def get_dataloader(cfg, mode="train", shuffle=False, num_workers=0, distributed=
     if cfg.get("track") == "obj_opt":
         ds = SyntheticObjectSequences(cfg, syn.get("test_sequences", 2), syn.get("sequence_frames", 30) if length is None else length,
                                       obj_as_mesh=bool(cfg.get("obj_as_mesh", False)),
-                                      obj_mesh_path=cfg.get("obj_mesh"), from_depth=bool(cfg.get("from_depth", False)))
+                                      obj_mesh_path=cfg.get("obj_mesh"), from_depth=bool(cfg.get("from_depth", False)),
+                                      model_radius=float(cfg.get("obj_model_radius") or 0.04))
         return torch.utils.data.DataLoader(ds, batch_size=1, shuffle=False, collate_fn=lambda b: b[0])
     if cfg.get("track"):
         ds = SyntheticSequences(cfg, syn.get("test_sequences", 4),
@@ -195,18 +196,20 @@ def _depth_entries(hand_pts, obj_pts, proj, hand_centre, obj_centre):
 
 
 # ---- object sequences (track: obj_opt) ---------------------------------------------------------------------------------
-def _capsule_sdf(p):
+def _capsule_sdf(p, radius: float = 0.04):
     """Signed distance to a bottle-sized capsule (radius 4 cm, 14 cm core) in the object frame, metres."""
     z = np.clip(p[..., 2], -0.07, 0.07)
-    return np.sqrt(p[..., 0] ** 2 + p[..., 1] ** 2 + (p[..., 2] - z) ** 2) - 0.04
+    return np.sqrt(p[..., 0] ** 2 + p[..., 1] ** 2 + (p[..., 2] - z) ** 2) - radius
 
 
-def capsule_volume(res: int = 201, stride: float = 0.002) -> np.ndarray:
+def capsule_volume(res: int = 201, stride: float = 0.002, model_radius: float = 0.04) -> np.ndarray:
     """(res,res,res) fp16 SDF volume on the +-0.2 m box the reference voxelises its DeepSDF decoder on
-    (optimization_obj.py:133-143: 201^3, stride 0.002, clamped), indexed [ix,iy,iz]."""
+    (optimization_obj.py:133-143: 201^3, stride 0.002, clamped), indexed [ix,iy,iz].  model_radius: the radius of the capsule the
+    VOLUME describes -- the clouds and depth frames always show the true one (0.04): another value hands over a wrong model
+    (what opt.fuse_depth corrects)."""
     ax = (np.arange(res) - res // 2) * float(stride)
     g = np.stack(np.meshgrid(ax, ax, ax, indexing="ij"), axis=-1)
-    return np.clip(_capsule_sdf(g), -0.1, 0.1).astype(np.float16)
+    return np.clip(_capsule_sdf(g, float(model_radius)), -0.1, 0.1).astype(np.float16)
 
 
 def capsule_mesh(n_around: int = 64, n_cap: int = 16):
@@ -266,13 +269,15 @@ class SyntheticObjectSequences(Dataset):
     carries that `obj_mesh_path` (an OBJ / PLY file, object frame, metres) instead: the clouds are tracked against its volume.
     from_depth: a frame carries, instead of obj_points, a 480 x 640 depth image and segmentation rendered from 16 n surface
     samples of a generator of its own (render_depth_frame), the intrinsics and the crop centre; the tracker builds the cloud
-    (models/frame_frontend.py).  Every other entry and every other random draw is unchanged."""
+    (models/frame_frontend.py).  Every other entry and every other random draw is unchanged.
+    model_radius: the radius of the capsule the handed-over `sdf_volume` describes (capsule_volume); the clouds, the depth frames
+    and obj_model_points stay the true capsule's, and every random draw is unchanged."""
 
     def __init__(self, cfg, num_sequences: int, frames: int, res: int = 201, stride: float = 0.002, obj_as_mesh: bool = False,
-                 obj_mesh_path=None, from_depth: bool = False):
+                 obj_mesh_path=None, from_depth: bool = False, model_radius: float = 0.04):
         self.from_depth = bool(from_depth)
         self.cfg, self.ns, self.nf = cfg, num_sequences, frames
-        self.res, self.stride = res, stride
+        self.res, self.stride, self.model_radius = res, stride, float(model_radius)
         self._vol = None
         self.obj_as_mesh, self.obj_mesh_path = bool(obj_as_mesh), obj_mesh_path
         self._mesh = None
@@ -287,7 +292,7 @@ class SyntheticObjectSequences(Dataset):
             if self._mesh is None:
                 self._mesh = _mesh_entry()
         elif self._vol is None:
-            self._vol = torch.from_numpy(capsule_volume(self.res, self.stride))
+            self._vol = torch.from_numpy(capsule_volume(self.res, self.stride, self.model_radius))
         rng = np.random.default_rng(40_000 + s)
         n = self.cfg["num_points"]
         jit = self.cfg.get("obj_jitter_cfg", {})

@@ -8,6 +8,7 @@ Mirrors, function for function, the reference methods it replaces:
   penetration_loss  ... .get_penetration_loss(query_sdf(hand))   :264-268 (fused with the lookup)
   mesh_signed_distance / mesh_sdf_volume   load_obj_oracle (mesh -> volume; kaolin there)   optimization_obj.py:163-182
   volume_mesh       gf_optimize_obj.sdf2mesh (volume -> mesh; marching cubes over the decoder there)   :399-405
+  tsdf_integrate    no counterpart: depth frames fused into a volume, where update_shape refits a DeepSDF latent   :345-403
 """
 from __future__ import annotations
 
@@ -413,3 +414,101 @@ def volume_mesh(sdf_volume: torch.Tensor, voxel_scale: float, level: float = 0.0
                                         verts.data_ptr() if nv else None, faces.data_ptr() if nf else None, st)
         _native._check(rc, "sdf.volume_mesh")
     return verts, faces
+
+
+# ---- depth frames fused into a signed distance volume (hotrack_amd/csrc/tsdf_fuse.hip) ------------------------------------------
+class _TsdfFrames(ctypes.Structure):
+    """pn2s_tsdf_frames (128 bytes)."""
+    _fields_ = ([(n, _vp) for n in ("volume", "weight", "depth", "seg", "intrinsics", "rotation", "translation")] +
+                [("depth_scale", ctypes.c_double)] + [(n, _cf) for n in ("voxel_scale", "trunc", "carve_weight", "max_weight")] +
+                [(n, _ci) for n in ("res", "vol_f16", "frames", "h", "w", "hs", "ws", "c", "depth_u16", "flip_yz", "channel", "value")])
+
+
+assert ctypes.sizeof(_TsdfFrames) == 128
+_lib.pn2s_tsdf_integrate.argtypes = [ctypes.POINTER(_TsdfFrames), _vp]
+_lib.pn2s_tsdf_integrate.restype = _ci
+TSDF_MAX_RES = 512
+
+
+def tsdf_check(volume, weight, voxel_scale, depth, seg, intrinsics, rotation, translation, trunc, obj_class, depth_scale,
+               carve_weight, max_weight):
+    """The argument checks of tsdf_integrate, which mirror pn2s_tsdf_integrate's (include/pn2_sdf.h) and raise; shared with the
+    torch route (network/models/shape_fusion.py), so both refuse the same calls.  Devices are not looked at here.
+    -> (res, F, H, W, Hs, Ws, C, f, depth is raw counts)."""
+    for name, t in (("volume", volume), ("weight", weight), ("depth", depth), ("seg", seg), ("intrinsics", intrinsics),
+                    ("rotation", rotation), ("translation", translation)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"tsdf_integrate: {name} must be a torch.Tensor, got {type(t).__name__}")
+        if not t.is_contiguous():
+            raise ValueError(f"tsdf_integrate: {name} must be contiguous")
+    if volume.dtype not in (torch.float16, torch.float32):
+        raise TypeError(f"tsdf_integrate: the volume must be float16 or float32, got {volume.dtype}")
+    if volume.dim() != 3 or len(set(volume.shape)) != 1:
+        raise ValueError(f"tsdf_integrate: the volume must be (res,res,res), got {tuple(volume.shape)}")
+    res = volume.shape[0]
+    if not 2 <= res <= TSDF_MAX_RES:
+        raise ValueError(f"tsdf_integrate: res must lie in [2, {TSDF_MAX_RES}], got {res}")
+    if weight.dtype != _f32 or weight.shape != volume.shape:
+        raise ValueError(f"tsdf_integrate: weight must be float32 {tuple(volume.shape)}, got {weight.dtype} {tuple(weight.shape)}")
+    if depth.dim() != 3 or depth.shape[0] < 1:
+        raise ValueError(f"tsdf_integrate: depth must be (F,H,W) with F >= 1, got {tuple(depth.shape)}")
+    F, H, W = depth.shape
+    raw = depth.dtype in (torch.uint16, torch.int16)   # (int16: the same 16 bits, for a torch without uint16 arithmetic)
+    if raw == (depth_scale is None) or (not raw and depth.dtype != _f32):
+        raise TypeError(f"tsdf_integrate: depth is fp32 metres, or uint16 counts with a depth_scale (got {depth.dtype}, "
+                        f"depth_scale = {depth_scale})")
+    if raw and not 0 < float(depth_scale) < float("inf"):
+        raise ValueError(f"tsdf_integrate: depth_scale must be finite and > 0, got {depth_scale}")
+    if seg.dtype != torch.uint8 or seg.dim() != 4 or seg.shape[0] != F:
+        raise ValueError(f"tsdf_integrate: seg must be uint8 (F,Hs,Ws,C) with F = {F}, got {seg.dtype} {tuple(seg.shape)}")
+    _, Hs, Ws, C = seg.shape
+    if min(H, W, Hs, Ws) < 1 or H % Hs or W % Ws or H // Hs != W // Ws or C not in (1, 3) or H * W >= 1 << 29 or F > 65535:
+        raise ValueError(f"tsdf_integrate: depth {H} x {W}, seg {Hs} x {Ws} x {C}: one integer factor between the two images, "
+                         "C 1 or 3, H W < 2^29, at most 65535 frames")
+    channel, value = int(obj_class[0]), int(obj_class[1])
+    if not (0 <= channel < C and 0 <= value <= 255):
+        raise ValueError(f"tsdf_integrate: obj_class = (channel, value) with channel in [0, {C}) and value in [0, 255], got {tuple(obj_class)}")
+    for name, t, shape in (("intrinsics", intrinsics, (F, 4)), ("rotation", rotation, (F, 3, 3)), ("translation", translation, (F, 3))):
+        if t.dtype != _f32 or tuple(t.shape) != shape:
+            raise ValueError(f"tsdf_integrate: {name} must be float32 {shape}, got {t.dtype} {tuple(t.shape)}")
+    inf = float("inf")
+    for name, x in (("trunc", trunc), ("voxel_scale", voxel_scale), ("max_weight", max_weight)):
+        if not 0 < float(x) < inf:
+            raise ValueError(f"tsdf_integrate: {name} must be finite and > 0, got {x}")
+    if not 0 <= float(carve_weight) < inf:
+        raise ValueError(f"tsdf_integrate: carve_weight must be finite and >= 0, got {carve_weight}")
+    return res, F, H, W, Hs, Ws, C, H // Hs, raw
+
+
+def tsdf_integrate(volume: torch.Tensor, weight: torch.Tensor, voxel_scale: float, depth: torch.Tensor, seg: torch.Tensor,
+                   intrinsics: torch.Tensor, rotation: torch.Tensor, translation: torch.Tensor, *, trunc: float, obj_class=(1, 255),
+                   depth_scale: float = None, flip_yz: bool = False, carve_weight: float = 1.0, max_weight: float = 64.0):
+    """Integrates F tracked depth frames, in order, into an SDF volume IN PLACE with one launch (include/pn2_sdf.h:
+    pn2s_tsdf_integrate; the rule is stated at the head of hotrack_amd/csrc/tsdf_fuse.hip): per voxel the weighted running
+    average of the truncated signed distances the frames observed.
+    volume (res,res,res) float16 / float32, voxel centre ((ix,iy,iz) - res//2) * voxel_scale;  weight (res,res,res) float32;
+    depth (F,H,W) fp32 metres, or uint16 / int16 raw counts with depth_scale;  seg (F,Hs,Ws,C) uint8, H = f Hs, W = f Ws;
+    intrinsics (F,4) fx, fy, cx, cy;  rotation (F,3,3), translation (F,3): the tracked poses (cloud_obj = (pcld - t) @ R);
+    obj_class: (channel, value) of the object's segment byte; every other valid pixel only carves free space, with carve_weight.
+    All tensors contiguous on one GPU.  Runs on the current stream, no host sync.  -> (volume, weight), the same tensors."""
+    res, F, H, W, Hs, Ws, C, _, raw = tsdf_check(volume, weight, voxel_scale, depth, seg, intrinsics, rotation, translation, trunc,
+                                                 obj_class, depth_scale, carve_weight, max_weight)
+    for name, t in (("volume", volume), ("weight", weight), ("depth", depth), ("seg", seg), ("intrinsics", intrinsics),
+                    ("rotation", rotation), ("translation", translation)):
+        if not t.is_cuda:
+            raise RuntimeError(f"tsdf_integrate: {name} must be a GPU (HIP) tensor -- hotrack_amd has no CPU path (got device {t.device}); "
+                               "network/models/shape_fusion.tsdf_integrate_torch runs anywhere")
+        if t.device != volume.device:
+            raise ValueError(f"tsdf_integrate: tensors on {volume.device} and {t.device}")
+    r = _TsdfFrames(res=res, vol_f16=int(volume.dtype == torch.float16), frames=F, h=H, w=W, hs=Hs, ws=Ws, c=C, depth_u16=int(raw),
+                    flip_yz=int(bool(flip_yz)), channel=int(obj_class[0]), value=int(obj_class[1]),
+                    depth_scale=0.0 if depth_scale is None else float(depth_scale), voxel_scale=float(voxel_scale), trunc=float(trunc),
+                    carve_weight=float(carve_weight), max_weight=float(max_weight))
+    r.volume, r.weight = _native._ptr(volume, "volume", volume.dtype, res ** 3), _native._ptr(weight, "weight", _f32, res ** 3)
+    r.depth, r.seg = _native._ptr(depth, "depth", depth.dtype, F * H * W), _native._ptr(seg, "seg", torch.uint8, F * Hs * Ws * C)
+    r.intrinsics = _native._ptr(intrinsics, "intrinsics", _f32, F * 4)
+    r.rotation, r.translation = _native._ptr(rotation, "rotation", _f32, F * 9), _native._ptr(translation, "translation", _f32, F * 3)
+    with torch.cuda.device(volume.device):
+        rc = _lib.pn2s_tsdf_integrate(ctypes.byref(r), _native._stream(volume))
+    _native._check(rc, "sdf.tsdf_integrate")
+    return volume, weight

@@ -183,6 +183,47 @@ int pn2s_volume_mesh_count(const void *vol, int vol_f16, int res, float stride, 
 int pn2s_volume_mesh_emit(const void *vol, int vol_f16, int res, float stride, float level, const void *work, long work_bytes,
                           int nv, int nf, float *verts, int *faces, void *stream);
 
+/*
+ * Tracked depth frames fused into an SDF volume (hotrack_amd/csrc/tsdf_fuse.hip): the weighted running average of
+ * truncated signed distances per voxel (KinectFusion's update) -- the online shape update of a volume that was built from a mesh or
+ * handed over.  ONE launch integrates `frames` >= 1 frames, in order, into one volume in place; one lane per voxel walks the frames
+ * with V and W in fp32 registers.  pn2s_tsdf_frames is HOST memory, read during the call; its pointers are DEVICE memory:
+ *   volume (res^3) fp32 or, with vol_f16 = 1, binary16, element (ix,iy,iz) at (ix*res + iy)*res + iz, voxel centre
+ *          p = ((ix,iy,iz) - res/2) * voxel_scale (the grid of pn2s_mesh_sdf_volume);  weight (res^3) fp32;  both in/out;
+ *   depth (frames,h,w) fp32 metres, or with depth_u16 = 1 uint16 counts, D = (float)((double)raw * depth_scale);
+ *   seg (frames,hs,ws,c) bytes, c 1 or 3, h = f hs and w = f ws with one integer f >= 1: pixel (v,u) reads seg[v / f, u / f]
+ *          (as pn2x_depth_frame_clouds); the pixel is the object's iff its byte `channel` equals `value`;
+ *   intrinsics (frames,4) fx, fy, cx, cy;  rotation (frames,3,3) row-major and translation (frames,3): the tracked pose, the
+ *          object-frame cloud being (pcld - t) @ R, so that a voxel centre p is seen at q = R p + t.
+ * Per voxel and frame, fp32 (the exact expressions, with their fmaf, are at the head of tsdf_fuse.hip): q = R p + t; flip_yz = 1
+ * negates q_y and q_z (the front end negated them on the way in); skip unless q_z > 1e-6; u = rint(q_x / q_z fx + cx),
+ * v = rint(q_y / q_z fy + cy), skip outside the image; D = depth[v,u], skip unless finite and > 0; d = D - q_z;
+ *   object pixel:  skip if d < -trunc, else s = min(d, trunc), g = 1;
+ *   other pixel:   free space only: d > trunc gives s = trunc, g = carve_weight, else skip;  g == 0 skips;
+ *   V = (V W + s g) / (W + g),  W = min(W + g, max_weight).
+ * A voxel no frame updated is not written (its bytes stay).  No atomics, two runs are bitwise equal; an fp32 volume after one
+ * launch of F frames has the bits of F launches of one frame; an fp16 volume is rounded once, at the end of the launch.
+ * No host sync or allocation (capturable).
+ * Refused with nothing launched: PN2_EINVAL for res < 2, frames < 1, a size < 1, h / hs and w / ws not one integer factor, c not 1
+ *   or 3, channel outside [0, c) or value outside [0, 255], vol_f16 / depth_u16 / flip_yz not 0 / 1, voxel_scale, trunc or
+ *   max_weight not finite and > 0, carve_weight not finite or < 0, depth_u16 = 1 with a depth_scale that is not finite and > 0;
+ *   PN2_ERANGE for res > 512, h w >= 2^29 or frames > 65535;  PN2_ENULL for a NULL record or pointer (checked in this order).
+ */
+struct pn2s_tsdf_frames {
+    void *volume;
+    float *weight;
+    const void *depth;
+    const unsigned char *seg;
+    const float *intrinsics;
+    const float *rotation;
+    const float *translation;
+    double depth_scale;
+    float voxel_scale, trunc, carve_weight, max_weight;
+    int res, vol_f16, frames, h, w, hs, ws, c, depth_u16, flip_yz, channel, value;
+}; /* 128 bytes */
+typedef struct pn2s_tsdf_frames pn2s_tsdf_frames;
+int pn2s_tsdf_integrate(const pn2s_tsdf_frames *frames, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -644,6 +644,19 @@ class ObjTrackModel_Optimization(nn.Module):
         # do not depend on it.  extract_mesh_route: None (the kernel for a GPU volume), 'kernel' or 'torch'
         self.extract_mesh = bool((cfg.get("opt") or {}).get("extract_mesh", False))
         self.extract_mesh_route = None
+        # opt.fuse_depth: fuse every tracked depth frame into the sequence's own copy of the volume (models/shape_fusion.py,
+        # hotrack_amd/csrc/tsdf_fuse.hip) and track the later frames against it.  fuse_every: frames between flushes (the reference
+        # refits its shape every tenth frame);  fuse_trunc: the truncation distance in VOXELS (5: wide enough for the trilinear
+        # lookup's cell and the tracker's centimetre pose errors, narrow enough not to reach through the 8 cm capsule);
+        # fuse_prior_weight: the weight of the handed-over model, in frames (8: a model is trusted like eight observations, so
+        # one flush of ten frames already outweighs it where the object was seen)
+        opt_cfg = cfg.get("opt") or {}
+        self.fuse_depth = bool(opt_cfg.get("fuse_depth", False))
+        self.fuse_every = int(opt_cfg.get("fuse_every", 10))
+        self.fuse_trunc = float(opt_cfg.get("fuse_trunc", 5.0))
+        self.fuse_prior_weight = float(opt_cfg.get("fuse_prior_weight", 8.0))
+        self.fuse_route = None  # None (the kernel for a GPU volume), 'kernel' or 'torch'
+        self._fuse_frontend = dict(cfg.get("depth_frontend") or {})
         self.surface_seed = 0  # every sequence draws from a generator of its own with this seed: alone or in a group, the same surface
         self.save_folder = cfg.get("save_dir")
 
@@ -694,7 +707,12 @@ class ObjTrackModel_Optimization(nn.Module):
         last = None
         rets = []
         surf = None
+        fusion = self._new_fusion(input) if getattr(self, "fuse_depth", False) and len(input) else None
         for data in input:
+            if fusion is not None:  # one upload serves the front end and the fusion
+                for key in ("depth", "seg"):
+                    if key in data and isinstance(data[key], torch.Tensor):
+                        data[key] = data[key].to(self.device, non_blocking=True)
             if last is not None:
                 data["jittered_obj_pose"] = last
             else:
@@ -714,11 +732,36 @@ class ObjTrackModel_Optimization(nn.Module):
             last["prev_translation"], last["prev_rotation"] = last["translation"], last["rotation"]  # last frame's pose
             last["translation"], last["rotation"] = ret["translation"], ret["rotation"]            # current frame's pose
             rets.append(ret)
+            if fusion is not None:
+                missing = [k for k in ("depth", "seg", "intrinsics") if k not in data]
+                if missing:
+                    raise KeyError(f"opt.fuse_depth: frame {len(rets) - 1} ({data['file_name'][0]}) carries no {missing}")
+                fusion.push(data, ret)
+                if fusion.due():  # the later frames are tracked against the fused volume (load_volume rebuilds the corner layout)
+                    self.optimizer.load_volume(fusion.flush(), fusion.voxel_scale)
+        if fusion is not None:
+            if fusion.pending:
+                self.optimizer.load_volume(fusion.flush(), fusion.voxel_scale)
+            rets[0]["obj_fused"] = fusion.state()
         if surf is not None:
             rets[0]["obj_surface"] = self._surface_entry(surf, self.optimizer._corners, self.optimizer.voxel_scale)
         if getattr(self, "extract_mesh", False) and rets:
             self._attach_mesh(input, rets, self.optimizer.sdf_volume, self.optimizer.voxel_scale, flag_dict)
         return rets
+
+    def _new_fusion(self, input):
+        """opt.fuse_depth: the VolumeFusion of a sequence whose volume has just been loaded (a clone: the handed-over tensor,
+        which a dataset may share between sequences, and a cached mesh volume are never written)."""
+        from .shape_fusion import VolumeFusion
+        missing = [k for k in ("depth", "seg", "intrinsics") if k not in input[0]]
+        if missing:
+            raise KeyError(f"opt.fuse_depth fuses depth frames into the object's volume: the sequence's frames must carry 'depth', 'seg' "
+                           f"and 'intrinsics' (as the --from_depth frames do); frame 0 ({input[0]['file_name'][0]}) lacks {missing}")
+        fe = self._fuse_frontend
+        scale = float(self.optimizer.voxel_scale)
+        return VolumeFusion(self.optimizer.sdf_volume, scale, self.fuse_prior_weight, self.fuse_trunc * scale, self.fuse_every,
+                            obj_class=tuple(fe.get("obj_class", (1, 255))), flip_yz=bool(fe.get("flip_yz", False)),
+                            route=getattr(self, "fuse_route", None), device=self.device)
 
     def _sequence_volume(self, frame0, built):
         """The volume `forward` would load for a sequence whose first frame is `frame0`, in its lookup layout ->
@@ -755,6 +798,9 @@ class ObjTrackModel_Optimization(nn.Module):
         once per sequence.  inputs: a list of S sequences, each what `forward` takes; sequences shorter than the longest sit
         out once they have ended.  All volumes must share one resolution, dtype and voxel_scale (one launch reads them all).
         Returns a list of S `ret_dict_lst`, bit-equal to S `forward` calls."""
+        if getattr(self, "fuse_depth", False):
+            raise ValueError("opt.fuse_depth is not available for sequences tracked in lockstep: a group's sequences share volumes, and "
+                             "a fused volume belongs to one sequence (per-sequence copies are a later step); track with --seq_batch 1")
         flag_dict["track_flag"] = True
         assert flag_dict["test_flag"]
         built, vols, scales = {}, [], []

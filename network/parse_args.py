@@ -63,6 +63,16 @@ def add_args(parser):
                              "ret_dict_lst[0]['obj_info']; --save writes it as a PLY ('recon_path').  A sequence that carries "
                              "neither obj_model_points nor a mesh samples it for the chamfer columns.  The tracked poses do not "
                              "depend on it")
+    parser.add_argument("--fuse_obj_depth", dest="opt/fuse_depth", action="store_const", const=True, default=None,
+                        help="track=obj_opt on frames that carry depth images (--from_depth): fuse every tracked depth frame into the "
+                             "sequence's own copy of the SDF volume as a truncated signed distance, a weighted running average per "
+                             "voxel (models/shape_fusion.py, hotrack_amd/csrc/tsdf_fuse.hip), reload the optimiser's volume every "
+                             "opt.fuse_every frames (10) and put the fused volume into ret_dict_lst[0]['obj_fused']; with "
+                             "--extract_obj_mesh the PLY is the reconstruction.  opt.fuse_trunc (5 voxels) and opt.fuse_prior_weight "
+                             "(8) are read from the configuration.  Not with --seq_batch > 1")
+    parser.add_argument("--obj_model_radius", type=float, default=None,
+                        help="track=obj_opt, synthetic sequences: the radius of the capsule the handed-over SDF volume describes "
+                             "(default 0.04, the true one the clouds and depth frames show): another value hands over a wrong model")
     parser.add_argument("--obj_mesh", type=str, default=None,
                         help="track the synthetic sequences' clouds against an SDF volume built from this triangle mesh (OBJ or "
                              "PLY, object frame, metres; models/mesh_sdf.py) instead of the analytic capsule volume")
