@@ -55,6 +55,7 @@ def get_config(args, save=True):
     cfg["opt"].setdefault("accumulate_surface", False)  # obj_opt: keep the observed surface of each sequence (--accumulate_obj_surface)
     cfg["opt"].setdefault("extract_mesh", False)  # obj_opt: extract the mesh of each sequence's SDF volume (--extract_obj_mesh)
     cfg["opt"].setdefault("fuse_depth", False)  # obj_opt: fuse the tracked depth frames into the sequence's volume (--fuse_obj_depth)
+    cfg["opt"].setdefault("lockstep_fuse", False)  # fuse_depth inside lockstep groups: a volume copy per sequence (--lockstep_fuse)
     cfg["opt"].setdefault("fuse_every", 10)  # frames between flushes (the reference refits its shape every tenth frame)
     cfg["opt"].setdefault("fuse_trunc", 5.0)  # truncation distance, in voxels
     cfg["opt"].setdefault("fuse_prior_weight", 8.0)  # weight of the handed-over model, in frames

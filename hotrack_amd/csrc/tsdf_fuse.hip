@@ -27,6 +27,10 @@
 // (ceil(res / 256), ceil(res / 4), res): (ix,iy,iz) come from the block and thread indices, no division of a linear index.  A wave
 // skips a frame's projections when none of its voxels lies in front of the camera, and its loads and updates when none projects
 // into the image (ballots over values every lane computes anyway, so a skip never changes a result).
+//
+// pn2s_tsdf_integrate_batch is the same rule (the one __device__ function below, called by both kernels) for the S volumes of a
+// group of sequences tracked in lockstep, in ONE launch: sequence k integrates its slice of the group's packed frame arrays into
+// its own volume, with the bits pn2s_tsdf_integrate gives for those frames alone.
 #include <hip/hip_fp16.h>
 #include <cmath>
 
@@ -63,11 +67,11 @@ __device__ __forceinline__ void st_vol(void *vol, int i, float x) {
     else reinterpret_cast<float *>(vol)[i] = x;
 }
 
+// The rule, once, for both launches: this lane's kZ voxels (ix, iy, z0 .. z0 + kZ - 1) of `volume` / `weight` over the frames
+// [f0, f1) of A's frame arrays.  iy < res (the caller's duty; z is masked here).
 template <bool F16, typename D>
-__global__ __launch_bounds__(kWave * kRows) void tsdf_integrate_kernel(const Args A) {
+__device__ __forceinline__ void integrate_voxels(const Args &A, void *volume, float *weight, int f0, int f1, int ix, int iy, int z0) {
     const int res = A.res, half = res / 2;
-    const int ix = blockIdx.z, iy = blockIdx.y * kRows + threadIdx.y, z0 = (blockIdx.x * kWave + threadIdx.x) * kZ;
-    if (iy >= res) return;  // (uniform over the wave: a wave is one y row)
     const int base = (ix * res + iy) * res;  // res <= 512: res^3 fits an int
     float V[kZ], W[kZ], pz[kZ];
     unsigned live = 0, touched = 0;
@@ -77,14 +81,14 @@ __global__ __launch_bounds__(kWave * kRows) void tsdf_integrate_kernel(const Arg
         pz[j] = (float)(z0 + j - half) * A.voxel_scale;
         if (z0 + j < res) {
             live |= 1u << j;
-            V[j] = ld_vol<F16>(A.volume, base + z0 + j);
-            W[j] = A.weight[base + z0 + j];
+            V[j] = ld_vol<F16>(volume, base + z0 + j);
+            W[j] = weight[base + z0 + j];
         }
     }
     const float px = (float)(ix - half) * A.voxel_scale, py = (float)(iy - half) * A.voxel_scale;
     const size_t hw = (size_t)A.h * A.w, seg_frame = (size_t)A.hs * A.ws * A.c;
     const float umax = (float)(A.w - 1), vmax = (float)(A.h - 1);
-    for (int fr = 0; fr < A.frames; ++fr) {
+    for (int fr = f0; fr < f1; ++fr) {
         const float *R = A.rotation + 9 * fr, *t = A.translation + 3 * fr, *K = A.intrinsics + 4 * fr;
         const float r02 = R[2], r12 = R[5], r22 = R[8];
         const float ax = __builtin_fmaf(R[0], px, __builtin_fmaf(R[1], py, t[0]));
@@ -147,10 +151,41 @@ __global__ __launch_bounds__(kWave * kRows) void tsdf_integrate_kernel(const Arg
 #pragma unroll
     for (int j = 0; j < kZ; ++j) {
         if ((touched >> j) & 1u) {  // (touched is a subset of live: z0 + j < res)
-            st_vol<F16>(A.volume, base + z0 + j, V[j]);
-            A.weight[base + z0 + j] = W[j];
+            st_vol<F16>(volume, base + z0 + j, V[j]);
+            weight[base + z0 + j] = W[j];
         }
     }
+}
+
+template <bool F16, typename D>
+__global__ __launch_bounds__(kWave * kRows) void tsdf_integrate_kernel(const Args A) {
+    const int ix = blockIdx.z, iy = blockIdx.y * kRows + threadIdx.y, z0 = (blockIdx.x * kWave + threadIdx.x) * kZ;
+    if (iy >= A.res) return;  // (uniform over the wave: a wave is one y row)
+    integrate_voxels<F16, D>(A, A.volume, A.weight, 0, A.frames, ix, iy, z0);
+}
+
+// S volumes in one launch (pn2s_tsdf_integrate_batch).  Grid (ztiles * yblocks, res, S): blockIdx.x carries the z tile in its low
+// `ztshift` bits (ztiles is 1 or 2: kMaxRes <= 2 * kWave * kZ) and the y block above them, so a sequence's workgroups come in
+// the single launch's order (z tile, y block, ix) and no index is divided.  Sequence k owns the frames [off[k], off[k+1]) clamped
+// to [0, total]; with an empty slice its waves leave before the tables or any volume are read.
+struct BatchArgs {
+    Args A;  // (volume, weight and frames unused)
+    void *const *volumes;
+    float *const *weights;
+    const int *frame_off;
+    int total, ztshift;
+};
+static_assert(kMaxRes <= 2 * kWave * kZ, "the z tile is one bit of blockIdx.x");
+
+template <bool F16, typename D>
+__global__ __launch_bounds__(kWave * kRows) void tsdf_integrate_batch_kernel(const BatchArgs B) {
+    const int k = blockIdx.z;
+    const int f0 = max(B.frame_off[k], 0), f1 = min(B.frame_off[k + 1], B.total);
+    if (f1 <= f0) return;  // the sequence sits out (uniform over the workgroup)
+    const int zt = blockIdx.x & ((1 << B.ztshift) - 1), yb = blockIdx.x >> B.ztshift;
+    const int ix = blockIdx.y, iy = yb * kRows + threadIdx.y, z0 = (zt * kWave + threadIdx.x) * kZ;
+    if (iy >= B.A.res) return;
+    integrate_voxels<F16, D>(B.A, B.volumes[k], B.weights[k], f0, f1, ix, iy, z0);
 }
 
 }  // namespace tsdf
@@ -160,15 +195,17 @@ using namespace pn2;
 using namespace pn2::tsdf;
 
 static_assert(sizeof(pn2s_tsdf_frames) == 128, "record layout (pn2_sdf.h)");
+static_assert(sizeof(pn2s_tsdf_group) == 144, "record layout (pn2_sdf.h)");
 
 static inline bool finite_positive(float x) { return std::isfinite(x) && x > 0.f; }
 
-extern "C" int pn2s_tsdf_integrate(const pn2s_tsdf_frames *frames, void *stream) {
-    if (!frames) return PN2_ENULL;
-    const pn2s_tsdf_frames &r = *frames;
+// The checks both records share (their fields carry the same names), in the single entry's order: PN2_EINVAL, then PN2_ERANGE.
+// `frames` is the record's frame count, at least `frames_min`.
+template <typename R>
+static int check_record(const R &r, int frames_min) {
     const bool sizes = r.h >= 1 && r.w >= 1 && r.hs >= 1 && r.ws >= 1;
-    bool inval = r.res < 2 || r.frames < 1 || !sizes || (r.vol_f16 != 0 && r.vol_f16 != 1) || (r.depth_u16 != 0 && r.depth_u16 != 1) ||
-                 (r.flip_yz != 0 && r.flip_yz != 1) || (r.c != 1 && r.c != 3);
+    bool inval = r.res < 2 || r.frames < frames_min || !sizes || (r.vol_f16 != 0 && r.vol_f16 != 1) ||
+                 (r.depth_u16 != 0 && r.depth_u16 != 1) || (r.flip_yz != 0 && r.flip_yz != 1) || (r.c != 1 && r.c != 3);
     inval |= !finite_positive(r.voxel_scale) || !finite_positive(r.trunc) || !finite_positive(r.max_weight) ||
              !(std::isfinite(r.carve_weight) && r.carve_weight >= 0.f);
     inval |= sizes && (r.h % r.hs != 0 || r.w % r.ws != 0 || r.h / r.hs != r.w / r.ws);
@@ -176,16 +213,32 @@ extern "C" int pn2s_tsdf_integrate(const pn2s_tsdf_frames *frames, void *stream)
     inval |= r.depth_u16 == 1 && !(std::isfinite(r.depth_scale) && r.depth_scale > 0.0);
     if (inval) return PN2_EINVAL;
     if (r.res > kMaxRes || (long)r.h * r.w >= (1L << 29) || r.frames > 65535) return PN2_ERANGE;
-    if (!r.volume || !r.weight || !r.depth || !r.seg || !r.intrinsics || !r.rotation || !r.translation) return PN2_ENULL;
+    return PN2_OK;
+}
+
+// The kernels' view of a checked record (volume, weight and frames are the single entry's own).
+template <typename R>
+static Args frame_args(const R &r) {
     Args A;
-    A.volume = r.volume; A.weight = r.weight; A.depth = r.depth; A.seg = r.seg; A.intrinsics = r.intrinsics;
+    A.volume = nullptr; A.weight = nullptr; A.frames = 0;
+    A.depth = r.depth; A.seg = r.seg; A.intrinsics = r.intrinsics;
     A.rotation = r.rotation; A.translation = r.translation; A.depth_scale = r.depth_scale;
     A.voxel_scale = r.voxel_scale; A.trunc = r.trunc; A.carve_weight = r.carve_weight; A.max_weight = r.max_weight;
-    A.res = r.res; A.frames = r.frames; A.h = r.h; A.w = r.w; A.ws = r.ws; A.hs = r.hs; A.c = r.c; A.f = r.h / r.hs;
+    A.res = r.res; A.h = r.h; A.w = r.w; A.ws = r.ws; A.hs = r.hs; A.c = r.c; A.f = r.h / r.hs;
     A.fshift = -1;
     for (int s = 0; s < 30; ++s)
         if (A.f == (1 << s)) A.fshift = s;
     A.flip = r.flip_yz; A.channel = r.channel; A.value = r.value;
+    return A;
+}
+
+extern "C" int pn2s_tsdf_integrate(const pn2s_tsdf_frames *frames, void *stream) {
+    if (!frames) return PN2_ENULL;
+    const pn2s_tsdf_frames &r = *frames;
+    if (const int rc = check_record(r, 1)) return rc;
+    if (!r.volume || !r.weight || !r.depth || !r.seg || !r.intrinsics || !r.rotation || !r.translation) return PN2_ENULL;
+    Args A = frame_args(r);
+    A.volume = r.volume; A.weight = r.weight; A.frames = r.frames;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((r.res + kWave * kZ - 1) / (kWave * kZ), (r.res + kRows - 1) / kRows, r.res), block(kWave, kRows);
     if (r.vol_f16) {
@@ -197,3 +250,30 @@ extern "C" int pn2s_tsdf_integrate(const pn2s_tsdf_frames *frames, void *stream)
     }
     return check_launch();
 }
+
+extern "C" int pn2s_tsdf_integrate_batch(const pn2s_tsdf_group *group, void *stream) {
+    if (!group) return PN2_ENULL;
+    const pn2s_tsdf_group &r = *group;
+    if (r.sequences < 0) return PN2_EINVAL;
+    if (const int rc = check_record(r, 0)) return rc;
+    if (r.sequences > PN2S_TSDF_BATCH_MAX) return PN2_ERANGE;
+    if (r.sequences == 0 || r.frames == 0) return PN2_OK;  // nothing to integrate: nothing is read or launched
+    if (!r.volumes || !r.weights || !r.frame_off || !r.depth || !r.seg || !r.intrinsics || !r.rotation || !r.translation)
+        return PN2_ENULL;
+    BatchArgs B;
+    B.A = frame_args(r);
+    B.volumes = r.volumes; B.weights = r.weights; B.frame_off = r.frame_off; B.total = r.frames;
+    const int ztiles = (r.res + kWave * kZ - 1) / (kWave * kZ);  // 1 or 2
+    B.ztshift = ztiles - 1;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid(ztiles * ((r.res + kRows - 1) / kRows), r.res, r.sequences), block(kWave, kRows);
+    if (r.vol_f16) {
+        if (r.depth_u16) hipLaunchKernelGGL((tsdf_integrate_batch_kernel<true, unsigned short>), grid, block, 0, st, B);
+        else hipLaunchKernelGGL((tsdf_integrate_batch_kernel<true, float>), grid, block, 0, st, B);
+    } else {
+        if (r.depth_u16) hipLaunchKernelGGL((tsdf_integrate_batch_kernel<false, unsigned short>), grid, block, 0, st, B);
+        else hipLaunchKernelGGL((tsdf_integrate_batch_kernel<false, float>), grid, block, 0, st, B);
+    }
+    return check_launch();
+}
+

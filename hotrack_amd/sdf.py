@@ -9,6 +9,7 @@ Mirrors, function for function, the reference methods it replaces:
   mesh_signed_distance / mesh_sdf_volume   load_obj_oracle (mesh -> volume; kaolin there)   optimization_obj.py:163-182
   volume_mesh       gf_optimize_obj.sdf2mesh (volume -> mesh; marching cubes over the decoder there)   :399-405
   tsdf_integrate    no counterpart: depth frames fused into a volume, where update_shape refits a DeepSDF latent   :345-403
+  tsdf_integrate_batch   the same for the volumes of S sequences tracked in lockstep, one launch
 """
 from __future__ import annotations
 
@@ -512,3 +513,135 @@ def tsdf_integrate(volume: torch.Tensor, weight: torch.Tensor, voxel_scale: floa
         rc = _lib.pn2s_tsdf_integrate(ctypes.byref(r), _native._stream(volume))
     _native._check(rc, "sdf.tsdf_integrate")
     return volume, weight
+
+
+class _TsdfGroup(ctypes.Structure):
+    """pn2s_tsdf_group (144 bytes)."""
+    _fields_ = ([(n, _vp) for n in ("volumes", "weights", "frame_off", "depth", "seg", "intrinsics", "rotation", "translation")] +
+                [("depth_scale", ctypes.c_double)] + [(n, _cf) for n in ("voxel_scale", "trunc", "carve_weight", "max_weight")] +
+                [(n, _ci) for n in ("res", "vol_f16", "sequences", "frames", "h", "w", "hs", "ws", "c", "depth_u16", "flip_yz", "channel",
+                                    "value", "pad_")])
+
+
+assert ctypes.sizeof(_TsdfGroup) == 144
+_lib.pn2s_tsdf_integrate_batch.argtypes = [ctypes.POINTER(_TsdfGroup), _vp]
+_lib.pn2s_tsdf_integrate_batch.restype = _ci
+TSDF_BATCH_MAX = 65535  # PN2S_TSDF_BATCH_MAX
+
+
+def tsdf_batch_check(volumes, weights, voxel_scale, depth, seg, intrinsics, rotation, translation, frame_counts, trunc, obj_class,
+                     depth_scale, carve_weight, max_weight):
+    """The argument checks of tsdf_integrate_batch, shared with the torch route (network/models/shape_fusion.py), so both refuse
+    the same calls: the lists' lengths, the counts, tsdf_check for every active sequence on its slice of the frames, one res and
+    dtype, no storage shared between two active sequences.  Devices are not looked at here.
+    -> (offsets: S + 1 ints, active: the sequences with frames)."""
+    S = len(frame_counts)
+    if len(volumes) != S or len(weights) != S:
+        raise ValueError(f"tsdf_integrate_batch: volumes, weights and frame_counts must be lists of one length S, got {len(volumes)}, "
+                         f"{len(weights)} and {S}")
+    if S > TSDF_BATCH_MAX:
+        raise ValueError(f"tsdf_integrate_batch: at most {TSDF_BATCH_MAX} sequences in one launch, got {S}")
+    off = [0]
+    for k, n in enumerate(frame_counts):
+        if isinstance(n, bool) or not isinstance(n, int) or n < 0:
+            raise ValueError(f"tsdf_integrate_batch: frame_counts[{k}] must be a non-negative int, got {n!r}")
+        if (volumes[k] is None) != (weights[k] is None):
+            raise ValueError(f"tsdf_integrate_batch: volumes[{k}] and weights[{k}] must both be given or both be None")
+        if volumes[k] is None and n:
+            raise ValueError(f"tsdf_integrate_batch: sequence {k} has {n} frames but no volume (None marks a sequence that sits out: "
+                             "its count must be 0)")
+        off.append(off[-1] + n)
+    if not isinstance(depth, torch.Tensor) or depth.dim() != 3:
+        raise ValueError("tsdf_integrate_batch: depth must be a (F,H,W) tensor holding the frames of all sequences")
+    if off[-1] != depth.shape[0]:
+        raise ValueError(f"tsdf_integrate_batch: frame_counts sum to {off[-1]}, the packed arrays hold F = {depth.shape[0]} frames")
+    first, spans = None, []
+    for k in range(S):
+        v, w = volumes[k], weights[k]
+        if v is None:
+            continue
+        if frame_counts[k]:
+            a, b = off[k], off[k + 1]
+            tsdf_check(v, w, voxel_scale, *(x[a:b] if isinstance(x, torch.Tensor) else x for x in (depth, seg, intrinsics, rotation, translation)),
+                       trunc, obj_class, depth_scale, carve_weight, max_weight)
+            for t in (v, w):
+                spans.append((t.data_ptr(), t.data_ptr() + t.numel() * t.element_size(), k))
+        elif not (isinstance(v, torch.Tensor) and isinstance(w, torch.Tensor)):
+            raise TypeError(f"tsdf_integrate_batch: volumes[{k}] and weights[{k}] must be tensors or None")
+        if first is None:
+            first = k
+        elif (tuple(v.shape), v.dtype) != (tuple(volumes[first].shape), volumes[first].dtype):
+            raise ValueError(f"tsdf_integrate_batch: volumes[{first}] ({tuple(volumes[first].shape)} {volumes[first].dtype}) and volumes[{k}] "
+                             f"({tuple(v.shape)} {v.dtype}) differ: a group shares one res and dtype")
+    spans.sort()
+    for (_, end, i), (start, _, j) in zip(spans, spans[1:]):
+        if start < end:
+            if i == j:
+                raise ValueError(f"tsdf_integrate_batch: sequence {i}'s volume and weights share storage")
+            raise ValueError(f"tsdf_integrate_batch: sequences {min(i, j)} and {max(i, j)} share volume or weight storage: two "
+                             "workgroups would write one voxel")
+    return off, [k for k in range(S) if frame_counts[k]]
+
+
+def tsdf_integrate_batch(volumes, weights, voxel_scale: float, depth: torch.Tensor, seg: torch.Tensor, intrinsics: torch.Tensor,
+                         rotation: torch.Tensor, translation: torch.Tensor, frame_counts, *, trunc: float, obj_class=(1, 255),
+                         depth_scale: float = None, flip_yz: bool = False, carve_weight: float = 1.0, max_weight: float = 64.0,
+                         cache=None):
+    """tsdf_integrate for the S volumes of a group of sequences with ONE launch (include/pn2_sdf.h: pn2s_tsdf_integrate_batch):
+    sequence k integrates its frame_counts[k] frames, in order, into volumes[k] / weights[k] IN PLACE, with the bits tsdf_integrate
+    gives for them alone.
+    volumes, weights: lists of S tensors of one res and dtype (as tsdf_integrate's), None for a sequence that sits out;
+    frame_counts: S non-negative ints, 0 for a sequence that sits out (its tensors, if given, keep every byte);
+    depth (F,H,W), seg (F,Hs,Ws,C), intrinsics (F,4), rotation (F,3,3), translation (F,3): the sequences' frames packed in sequence
+      order, F = sum(frame_counts); everything else is shared by the group and as in tsdf_integrate.
+    No two active sequences may share volume or weight storage.  All tensors contiguous on one GPU.
+    cache: a dict the caller keeps between calls: the pointer and offset table of a repeated (tensors, counts) is uploaded once.
+    Runs on the current stream, no host sync.  -> (volumes, weights), the same lists."""
+    off, active = tsdf_batch_check(volumes, weights, voxel_scale, depth, seg, intrinsics, rotation, translation, frame_counts, trunc,
+                                   obj_class, depth_scale, carve_weight, max_weight)
+    if not active:
+        return volumes, weights
+    S, F = len(frame_counts), off[-1]
+    device = volumes[active[0]].device
+    named = [(f"volumes[{k}]", volumes[k]) for k in range(S) if volumes[k] is not None]
+    named += [(f"weights[{k}]", weights[k]) for k in range(S) if weights[k] is not None]
+    named += [("depth", depth), ("seg", seg), ("intrinsics", intrinsics), ("rotation", rotation), ("translation", translation)]
+    for name, t in named:
+        if not t.is_cuda:
+            raise RuntimeError(f"tsdf_integrate_batch: {name} must be a GPU (HIP) tensor -- hotrack_amd has no CPU path (got device "
+                               f"{t.device}); network/models/shape_fusion.tsdf_integrate_batch_torch runs anywhere")
+        if t.device != device:
+            raise ValueError(f"tsdf_integrate_batch: tensors on {device} and {t.device}")
+    v0 = volumes[active[0]]
+    res = v0.shape[0]
+    _, H, W = depth.shape
+    _, Hs, Ws, C = seg.shape
+    raw = depth.dtype in (torch.uint16, torch.int16)
+    # one table: S volume pointers, S weight pointers, then the S + 1 offsets as int32 (a sitting-out sequence's tensors are not
+    # checked beyond res and dtype, and never read: its entries stay NULL)
+    key = ("tsdf", str(device), tuple(None if volumes[k] is None else (id(volumes[k]), id(weights[k])) for k in range(S)),
+           tuple(frame_counts))
+    hit = None if cache is None else cache.get(key)
+    if hit is None:
+        on = set(active)
+        words = [volumes[k].data_ptr() if k in on else 0 for k in range(S)] + [weights[k].data_ptr() if k in on else 0 for k in range(S)]
+        host = torch.cat([torch.tensor(words, dtype=torch.int64), torch.tensor(off + [0] * (S % 2 == 0), dtype=torch.int32).view(torch.int64)])
+        # (pinned and asynchronous: no host synchronisation; the tensors are kept with the table: the key's ids stay theirs)
+        hit = (host.pin_memory().to(device, non_blocking=True), list(volumes), list(weights))
+        if cache is not None:
+            if len(cache) > 64:
+                cache.clear()
+            cache[key] = hit
+    table = hit[0]
+    r = _TsdfGroup(res=res, vol_f16=int(v0.dtype == torch.float16), sequences=S, frames=F, h=H, w=W, hs=Hs, ws=Ws, c=C,
+                   depth_u16=int(raw), flip_yz=int(bool(flip_yz)), channel=int(obj_class[0]), value=int(obj_class[1]),
+                   depth_scale=0.0 if depth_scale is None else float(depth_scale), voxel_scale=float(voxel_scale), trunc=float(trunc),
+                   carve_weight=float(carve_weight), max_weight=float(max_weight))
+    r.volumes, r.weights, r.frame_off = table.data_ptr(), table.data_ptr() + 8 * S, table.data_ptr() + 16 * S
+    r.depth, r.seg = _native._ptr(depth, "depth", depth.dtype, F * H * W), _native._ptr(seg, "seg", torch.uint8, F * Hs * Ws * C)
+    r.intrinsics = _native._ptr(intrinsics, "intrinsics", _f32, F * 4)
+    r.rotation, r.translation = _native._ptr(rotation, "rotation", _f32, F * 9), _native._ptr(translation, "translation", _f32, F * 3)
+    with torch.cuda.device(device):
+        rc = _lib.pn2s_tsdf_integrate_batch(ctypes.byref(r), _native._stream(v0))
+    _native._check(rc, "sdf.tsdf_integrate_batch")
+    return volumes, weights

@@ -224,6 +224,47 @@ struct pn2s_tsdf_frames {
 typedef struct pn2s_tsdf_frames pn2s_tsdf_frames;
 int pn2s_tsdf_integrate(const pn2s_tsdf_frames *frames, void *stream);
 
+/*
+ * pn2s_tsdf_integrate for the `sequences` volumes of a group tracked in lockstep, in ONE launch.  Sequence k
+ * integrates the frames [frame_off[k], frame_off[k+1]) of the group's packed frame arrays, in order, into volumes[k] / weights[k];
+ * afterwards both have, bit for bit, what pn2s_tsdf_integrate gives for that volume and those frames alone (one __device__
+ * function holds the rule for both entries; no workgroup reads what another writes).  pn2s_tsdf_group is HOST memory:
+ *   volumes, weights  DEVICE arrays of `sequences` pointers to res^3 volumes (all of one res, vol_f16 and voxel_scale) and fp32 weights;
+ *   frame_off         DEVICE array of sequences + 1 ints, in frames.  Every slice is clamped to [0, frames] on the device, so a
+ *                     wrong table never indexes outside the packed arrays.  A sequence with an empty slice
+ *                     (frame_off[k+1] <= frame_off[k] after clamping) is INACTIVE: its workgroups leave before its table entries,
+ *                     which may be NULL, or any volume are read, and its volume and weights keep every byte -- how a
+ *                     sequence that has ended, or has nothing pending, sits a flush out;
+ *   depth (frames,h,w), seg (frames,hs,ws,c), intrinsics (frames,4), rotation (frames,3,3), translation (frames,3): the packed
+ *                     frames of all sequences, `frames` the group's total; everything else as in pn2s_tsdf_frames, shared.
+ * The three device tables cannot be checked here: that an active sequence's entries point to res^3 elements each, and that no two
+ * active sequences share a volume or weights (two workgroups would then write one voxel), is the caller's duty -- the Python
+ * binding (hotrack_amd.sdf.tsdf_integrate_batch) is the checked boundary.
+ * Grid (z tiles x y blocks, res, sequences): the voxel and the sequence come from block and thread indices; the third grid
+ * dimension gives the limit sequences <= PN2S_TSDF_BATCH_MAX.  sequences == 0 or frames == 0 is a no-op that reads and launches
+ * nothing (with every slice empty and frames > 0 the launch's workgroups all leave at once).
+ * Refused with nothing launched, checked in this order: a NULL record (PN2_ENULL); sequences < 0, frames < 0 and every
+ *   PN2_EINVAL of pn2s_tsdf_integrate; PN2_ERANGE for res > 512, h w >= 2^29, frames > 65535 or sequences > PN2S_TSDF_BATCH_MAX;
+ *   PN2_ENULL for a NULL table or frame array when there is something to integrate.
+ */
+#define PN2S_TSDF_BATCH_MAX 65535
+struct pn2s_tsdf_group {
+    void *const *volumes;
+    float *const *weights;
+    const int *frame_off;
+    const void *depth;
+    const unsigned char *seg;
+    const float *intrinsics;
+    const float *rotation;
+    const float *translation;
+    double depth_scale;
+    float voxel_scale, trunc, carve_weight, max_weight;
+    int res, vol_f16, sequences, frames, h, w, hs, ws, c, depth_u16, flip_yz, channel, value;
+    int pad_; /* to 144 bytes; not read */
+}; /* 144 bytes */
+typedef struct pn2s_tsdf_group pn2s_tsdf_group;
+int pn2s_tsdf_integrate_batch(const pn2s_tsdf_group *group, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -87,6 +87,12 @@ class gf_optimize_obj:
                                  scaling_coefficient2=float(self.scaling_coefficient2), beta=self.beta, work=self._work)
         return {"rotation": R, "translation": t.reshape(1, 3, 1)}
 
+    def forget_volume_tables(self):
+        """Drops optimize_batch's cached volume pointer tables, which keep their volumes alive: for a caller that has just
+        replaced volumes of its group (the next call uploads one table again)."""
+        for key in [k for k in self._batch_cache if k[0] == "vols"]:
+            del self._batch_cache[key]
+
     def optimize_batch(self, pclds, init_obj_poses, corner_volumes, voxel_scale=None):
         """`optimize` for S independent problems (one frame step of S sequences) with one set of launches: the same 11
         kernels over a (particle, problem) grid (hotrack_amd.sdf.obj_optimize_batch).  pclds: S clouds, an empty one or

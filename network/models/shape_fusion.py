@@ -6,7 +6,9 @@ a truncated signed distance, a weighted running average per voxel (KinectFusion'
   tsdf_integrate_torch   the rule of hotrack_amd/csrc/tsdf_fuse.hip in plain torch on any device: the CPU route, and the baseline
                          the kernel is timed against (scripts/bench_tsdf_fuse.py);
   VolumeFusion           a sequence's fused volume and weights: `push` a tracked frame, `flush` integrates what is pending in
-                         one launch (hotrack_amd.sdf.tsdf_integrate)."""
+                         one launch (hotrack_amd.sdf.tsdf_integrate);
+  tsdf_integrate_batch_torch, VolumeFusionGroup   the same for the S sequences of a group tracked in lockstep: one launch per
+                         flush for all of them (hotrack_amd.sdf.tsdf_integrate_batch)."""
 from __future__ import annotations
 
 import numpy as np
@@ -148,3 +150,86 @@ class VolumeFusion:
 
     def state(self) -> dict:
         return {"volume": self.volume, "weight": self.weight, "frames": self.frames, "voxel_scale": self.voxel_scale, "trunc": self.trunc}
+
+
+def tsdf_integrate_batch_torch(volumes, weights, voxel_scale, depth, seg, intrinsics, rotation, translation, frame_counts, *, trunc,
+                               obj_class=(1, 255), depth_scale=None, flip_yz=False, carve_weight=1.0, max_weight=64.0):
+    """hotrack_amd.sdf.tsdf_integrate_batch's arguments on any device: tsdf_integrate_torch per sequence on its slice of the packed
+    frames -- the CPU route, and the baseline the batched launch is timed against.  The same calls are refused, before any volume
+    is written.  -> (volumes, weights), the same lists."""
+    from hotrack_amd.sdf import tsdf_batch_check
+    off, active = tsdf_batch_check(volumes, weights, voxel_scale, depth, seg, intrinsics, rotation, translation, frame_counts, trunc,
+                                   obj_class, depth_scale, carve_weight, max_weight)
+    for k in active:
+        for t in (volumes[k], weights[k], seg, intrinsics, rotation, translation):
+            if t.device != depth.device:
+                raise ValueError(f"tsdf_integrate_batch_torch: tensors on {depth.device} and {t.device}")
+    for k in active:
+        a, b = off[k], off[k + 1]
+        tsdf_integrate_torch(volumes[k], weights[k], voxel_scale, depth[a:b], seg[a:b], intrinsics[a:b], rotation[a:b], translation[a:b],
+                             trunc=trunc, obj_class=obj_class, depth_scale=depth_scale, flip_yz=flip_yz, carve_weight=carve_weight,
+                             max_weight=max_weight)
+    return volumes, weights
+
+
+class VolumeFusionGroup:
+    """The fused volumes of S sequences tracked in lockstep: S VolumeFusion states, each owning clones as a single one does, whose
+    pending frames are integrated together -- `flush(ks)` is ONE launch for the listed sequences
+    (hotrack_amd.sdf.tsdf_integrate_batch), and leaves every sequence's volume and weights with the bits its own VolumeFusion
+    would have after the same pushes and flushes.
+
+    volumes: S handed-over volumes of one res and dtype (None for a sequence without frames); the other arguments are
+    VolumeFusion's and shared by the group."""
+
+    def __init__(self, volumes, voxel_scale: float, prior_weight: float, trunc: float, every: int = 10, obj_class=(1, 255),
+                 flip_yz: bool = False, carve_weight: float = 1.0, max_weight: float = 64.0, route=None, device=None):
+        self.states = [None if v is None else VolumeFusion(v, voxel_scale, prior_weight, trunc, every, obj_class, flip_yz, carve_weight,
+                                                           max_weight, route, device) for v in volumes]
+        self.route = route
+        self._tables = {}  # tsdf_integrate_batch's cache: the table of a repeated (volumes, counts) is uploaded once
+
+    def push(self, k: int, frame: dict, pose: dict) -> None:
+        """VolumeFusion.push for sequence k."""
+        self.states[k].push(frame, pose)
+
+    def pending(self, k: int) -> int:
+        return 0 if self.states[k] is None else self.states[k].pending
+
+    def due(self, k: int) -> bool:
+        return self.states[k] is not None and self.states[k].due()
+
+    def state(self, k: int) -> dict:
+        return self.states[k].state()
+
+    def flush(self, ks):
+        """Integrates what is pending for the sequences `ks`, each sequence's frames in the order they were pushed, with ONE
+        launch (the torch route: one pass per frame and sequence), and returns their volumes, in the order of `ks`.  The pending
+        frames must agree in image sizes and in having (and the value of) 'depth_scale'.  No host synchronisation."""
+        ks = list(ks)
+        todo = sorted(set(k for k in ks if self.pending(k)))
+        if todo:
+            first = self.states[todo[0]]
+            sizes = lambda s: tuple((tuple(fr[0].shape), fr[0].dtype, tuple(fr[1].shape)) for fr in s._pending[:1])
+            for k in todo[1:]:
+                s = self.states[k]
+                if sizes(s) != sizes(first) or s._depth_scale != first._depth_scale:
+                    raise ValueError(f"VolumeFusionGroup.flush: sequences {todo[0]} and {k} differ in their frames (depth "
+                                     f"{sizes(first)[0][0]} {sizes(first)[0][1]}, seg {sizes(first)[0][2]}, depth_scale {first._depth_scale} against "
+                                     f"{sizes(s)[0][0]} {sizes(s)[0][1]}, {sizes(s)[0][2]}, {s._depth_scale}): one launch shares them")
+            S = len(self.states)
+            frames = [fr for k in todo for fr in self.states[k]._pending]
+            depth, seg, intr, rot, trans = (torch.stack(x).contiguous() for x in zip(*frames))
+            counts = [self.states[k].pending if k in todo else 0 for k in range(S)]
+            vols = [self.states[k].volume if counts[k] else None for k in range(S)]
+            wts = [self.states[k].weight if counts[k] else None for k in range(S)]
+            kw = dict(trunc=first.trunc, obj_class=first.obj_class, depth_scale=first._depth_scale, flip_yz=first.flip_yz,
+                      carve_weight=first.carve_weight, max_weight=first.max_weight)
+            if self.route == "kernel" or (self.route is None and first.volume.is_cuda):
+                from hotrack_amd.sdf import tsdf_integrate_batch
+                tsdf_integrate_batch(vols, wts, first.voxel_scale, depth, seg, intr, rot, trans, counts, cache=self._tables, **kw)
+            else:
+                tsdf_integrate_batch_torch(vols, wts, first.voxel_scale, depth, seg, intr, rot, trans, counts, **kw)
+            for k in todo:
+                self.states[k].frames += counts[k]
+                self.states[k]._pending = []
+        return [self.states[k].volume for k in ks]

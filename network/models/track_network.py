@@ -656,6 +656,9 @@ class ObjTrackModel_Optimization(nn.Module):
         self.fuse_trunc = float(opt_cfg.get("fuse_trunc", 5.0))
         self.fuse_prior_weight = float(opt_cfg.get("fuse_prior_weight", 8.0))
         self.fuse_route = None  # None (the kernel for a GPU volume), 'kernel' or 'torch'
+        # opt.lockstep_fuse: allow opt.fuse_depth in forward_batch.  Opt-in, for memory: every sequence of a group then owns a copy
+        # of the volume and its weights, and from its first flush on a corner layout (201^3 fp16: 49 MB + 130 MB per sequence)
+        self.lockstep_fuse = bool(opt_cfg.get("lockstep_fuse", False))
         self._fuse_frontend = dict(cfg.get("depth_frontend") or {})
         self.surface_seed = 0  # every sequence draws from a generator of its own with this seed: alone or in a group, the same surface
         self.save_folder = cfg.get("save_dir")
@@ -763,6 +766,16 @@ class ObjTrackModel_Optimization(nn.Module):
                             obj_class=tuple(fe.get("obj_class", (1, 255))), flip_yz=bool(fe.get("flip_yz", False)),
                             route=getattr(self, "fuse_route", None), device=self.device)
 
+    def _new_fusion_group(self, corner_volumes, voxel_scale):
+        """opt.fuse_depth with opt.lockstep_fuse: the VolumeFusionGroup of a lockstep group whose volumes have just been loaded --
+        every sequence gets a clone of its volume, as `_new_fusion` gives a single one (sequences that share a volume stop sharing)."""
+        from .shape_fusion import VolumeFusionGroup
+        fe = self._fuse_frontend
+        scale = float(voxel_scale)
+        return VolumeFusionGroup([None if c is None else c.source for c in corner_volumes], scale, self.fuse_prior_weight,
+                                 self.fuse_trunc * scale, self.fuse_every, obj_class=tuple(fe.get("obj_class", (1, 255))),
+                                 flip_yz=bool(fe.get("flip_yz", False)), route=getattr(self, "fuse_route", None), device=self.device)
+
     def _sequence_volume(self, frame0, built):
         """The volume `forward` would load for a sequence whose first frame is `frame0`, in its lookup layout ->
         (hotrack_amd.sdf.CornerVolume, voxel_scale).  `built` maps id(volume tensor) to what was built from it, so sequences
@@ -798,11 +811,22 @@ class ObjTrackModel_Optimization(nn.Module):
         once per sequence.  inputs: a list of S sequences, each what `forward` takes; sequences shorter than the longest sit
         out once they have ended.  All volumes must share one resolution, dtype and voxel_scale (one launch reads them all).
         Returns a list of S `ret_dict_lst`, bit-equal to S `forward` calls."""
-        if getattr(self, "fuse_depth", False):
-            raise ValueError("opt.fuse_depth is not available for sequences tracked in lockstep: a group's sequences share volumes, and "
-                             "a fused volume belongs to one sequence (per-sequence copies are a later step); track with --seq_batch 1")
+        fuse = getattr(self, "fuse_depth", False)
+        if fuse and not getattr(self, "lockstep_fuse", False):
+            raise ValueError("opt.fuse_depth for sequences tracked in lockstep needs opt.lockstep_fuse (--lockstep_fuse) as well: a group's "
+                             "sequences share volumes, a fused volume belongs to one sequence, so every sequence of the group then owns "
+                             "a copy of the volume, its weights and, from its first flush on, the corner layout; or track with "
+                             "--seq_batch 1")
         flag_dict["track_flag"] = True
         assert flag_dict["test_flag"]
+        if fuse:  # before any work: every frame must carry what the fusion reads
+            for k, seq in enumerate(inputs):
+                for t, data in enumerate(seq):
+                    missing = [key for key in ("depth", "seg", "intrinsics") if key not in data]
+                    if missing:
+                        raise KeyError(f"opt.fuse_depth fuses depth frames into the object's volume: the frames must carry 'depth', 'seg' "
+                                       f"and 'intrinsics' (as the --from_depth frames do); sequence {k}, frame {t} "
+                                       f"({data['file_name'][0]}) lacks {missing}")
         built, vols, scales = {}, [], []
         for seq in inputs:
             v, s = self._sequence_volume(seq[0], built) if len(seq) else (None, None)
@@ -817,10 +841,15 @@ class ObjTrackModel_Optimization(nn.Module):
         last = [None] * S
         rets = [[] for _ in range(S)]
         surfs = [None] * S
+        group = self._new_fusion_group(vols, known[0][1]) if fuse and known else None
         for t in range(max((len(seq) for seq in inputs), default=0)):
             live = [k for k in range(S) if t < len(inputs[k])]
             for k in live:
                 data = inputs[k][t]
+                if group is not None:  # one upload serves the front end and the fusion
+                    for key in ("depth", "seg"):
+                        if isinstance(data[key], torch.Tensor):
+                            data[key] = data[key].to(self.device, non_blocking=True)
                 self._front_end.complete(data, "obj_points")
                 if last[k] is not None:
                     data["jittered_obj_pose"] = last[k]
@@ -845,7 +874,21 @@ class ObjTrackModel_Optimization(nn.Module):
                 last[k]["prev_translation"], last[k]["prev_rotation"] = last[k]["translation"], last[k]["rotation"]
                 last[k]["translation"], last[k]["rotation"] = ret["translation"], ret["rotation"]
                 rets[k].append(ret)
+            if group is not None:
+                # as `forward`: the frame is pushed with the pose just found; a sequence whose pending frames reach fuse_every, or
+                # whose last frame this was, is flushed -- all of them in ONE launch -- and tracked against its own fused volume
+                # from the next frame on (until its first flush it reads the group's shared corner layout: the same bits)
+                for k in live:
+                    group.push(k, inputs[k][t], out[k])
+                flush = [k for k in live if group.due(k) or t == len(inputs[k]) - 1]
+                if flush:
+                    from hotrack_amd import sdf as _sdf
+                    for k, fused in zip(flush, group.flush(flush)):
+                        vols[k] = _sdf.CornerVolume(fused)
+                    self.optimizer.forget_volume_tables()  # (they hold the corner layouts just replaced)
         for k in range(S):
+            if group is not None and rets[k]:
+                rets[k][0]["obj_fused"] = group.state(k)
             if surfs[k] is not None:
                 rets[k][0]["obj_surface"] = self._surface_entry(surfs[k], vols[k], known[0][1])
         if getattr(self, "extract_mesh", False):

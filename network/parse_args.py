@@ -69,7 +69,14 @@ def add_args(parser):
                              "voxel (models/shape_fusion.py, hotrack_amd/csrc/tsdf_fuse.hip), reload the optimiser's volume every "
                              "opt.fuse_every frames (10) and put the fused volume into ret_dict_lst[0]['obj_fused']; with "
                              "--extract_obj_mesh the PLY is the reconstruction.  opt.fuse_trunc (5 voxels) and opt.fuse_prior_weight "
-                             "(8) are read from the configuration.  Not with --seq_batch > 1")
+                             "(8) are read from the configuration.  With --seq_batch > 1 only together with --lockstep_fuse")
+    parser.add_argument("--lockstep_fuse", dest="opt/lockstep_fuse", action="store_const", const=True, default=None,
+                        help="track=obj_opt: allow --fuse_obj_depth with --seq_batch > 1.  The sequences of a group flush their pending "
+                             "frames in one launch (hotrack_amd.sdf.tsdf_integrate_batch) and every sequence gets, bit for bit, the "
+                             "poses and the fused volume of --seq_batch 1.  Opt-in for its memory: a fused volume cannot be shared, so "
+                             "every sequence of a group owns a copy of the volume and its weights and, from its first flush on, of "
+                             "the corner layout -- at 201^3 fp16 about 49 MB plus 130 MB per sequence.  Without --fuse_obj_depth "
+                             "it changes nothing")
     parser.add_argument("--obj_model_radius", type=float, default=None,
                         help="track=obj_opt, synthetic sequences: the radius of the capsule the handed-over SDF volume describes "
                              "(default 0.04, the true one the clouds and depth frames show): another value hands over a wrong model")

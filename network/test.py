@@ -3,7 +3,8 @@
 Same entry point as the reference's network/test.py: per-sequence tracking (batch 1, frame t seeded by
 frame t-1), prints data / network frames-per-second like the reference (test.py:65-98) -- here with an
 explicit device synchronisation so the network time is real.  Enables the fused inference backend.
---seq_batch S (track: obj_opt only): S sequences at a time in lockstep, one batched optimiser call per frame step."""
+--seq_batch S (track: obj_opt only): S sequences at a time in lockstep, one batched optimiser call per frame step; with
+--fuse_obj_depth it needs --lockstep_fuse (a volume copy per sequence; one fusion launch per flush for the whole group)."""
 import argparse
 import logging
 import os
@@ -29,6 +30,9 @@ def main(args):
     seq_batch = getattr(args, "seq_batch", 1)
     check_seq_batch(seq_batch, peek_track(args))  # (before any work: no directory, no model)
     cfg = get_config(args, save=False)
+    if seq_batch > 1 and cfg["opt"].get("fuse_depth") and not cfg["opt"].get("lockstep_fuse"):
+        raise SystemExit("--fuse_obj_depth with --seq_batch %d needs --lockstep_fuse: every sequence of a group then owns a copy of the "
+                         "volume, its weights and its corner layout (201^3 fp16: about 49 MB plus 130 MB per sequence)" % seq_batch)
     logger = logging.getLogger("TestModel")
     logger.setLevel(logging.INFO)
     if torch.cuda.is_available():
