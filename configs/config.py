@@ -59,6 +59,8 @@ def get_config(args, save=True):
     cfg["opt"].setdefault("fuse_every", 10)  # frames between flushes (the reference refits its shape every tenth frame)
     cfg["opt"].setdefault("fuse_trunc", 5.0)  # truncation distance, in voxels
     cfg["opt"].setdefault("fuse_prior_weight", 8.0)  # weight of the handed-over model, in frames
+    cfg["opt"].setdefault("render_model", False)  # obj_opt: render each sequence's volume at the tracked poses (--render_obj_model)
+    cfg["opt"].setdefault("render_occl_margin", 0.01)  # metres: a non-object pixel this far in front of the model occludes it (a choice)
     data_cfg = _load("data_config", cfg["data_config"])
     cfg["pointnet"] = {k: _load("pointnet_config", v) for k, v in cfg["pointnet_cfg"].items()}
 

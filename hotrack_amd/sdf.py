@@ -10,6 +10,8 @@ Mirrors, function for function, the reference methods it replaces:
   volume_mesh       gf_optimize_obj.sdf2mesh (volume -> mesh; marching cubes over the decoder there)   :399-405
   tsdf_integrate    no counterpart: depth frames fused into a volume, where update_shape refits a DeepSDF latent   :345-403
   tsdf_integrate_batch   the same for the volumes of S sequences tracked in lockstep, one launch
+  volume_raycast    no counterpart: a volume rendered to depth and normal maps at tracked poses (the raycast), one launch
+  raycast_compare   the rendered frames against the observed ones: overlap counts and depth residual sums, one launch
 """
 from __future__ import annotations
 
@@ -645,3 +647,156 @@ def tsdf_integrate_batch(volumes, weights, voxel_scale: float, depth: torch.Tens
         rc = _lib.pn2s_tsdf_integrate_batch(ctypes.byref(r), _native._stream(v0))
     _native._check(rc, "sdf.tsdf_integrate_batch")
     return volumes, weights
+
+
+# ---- an SDF volume rendered to depth and normal maps (hotrack_amd/csrc/sdf_raycast.hip) -----------------------------------------
+class _Raycast(ctypes.Structure):
+    """pn2s_raycast (96 bytes)."""
+    _fields_ = ([(n, _vp) for n in ("volume", "intrinsics", "rotation", "translation", "depth", "normal")] +
+                [(n, _cf) for n in ("voxel_scale", "step_scale", "min_step")] +
+                [(n, _ci) for n in ("res", "vol_f16", "frames", "h", "w", "flip_yz", "refine", "max_steps", "pad_")])
+
+
+class _RaycastFrames(ctypes.Structure):
+    """pn2s_raycast_frames (80 bytes)."""
+    _fields_ = ([(n, _vp) for n in ("rendered", "depth", "seg", "out")] + [("depth_scale", ctypes.c_double), ("occl_margin", _cf)] +
+                [(n, _ci) for n in ("frames", "h", "w", "hs", "ws", "c", "depth_u16", "channel", "value")])
+
+
+assert ctypes.sizeof(_Raycast) == 96 and ctypes.sizeof(_RaycastFrames) == 80
+_lib.pn2s_volume_raycast.argtypes = [ctypes.POINTER(_Raycast), _vp]
+_lib.pn2s_volume_raycast.restype = _ci
+_lib.pn2s_raycast_compare.argtypes = [ctypes.POINTER(_RaycastFrames), _vp]
+_lib.pn2s_raycast_compare.restype = _ci
+RAYCAST_MAX_RES = 512
+# A choice, not a measurement: a non-object pixel counts as an occluder of the model when its depth is more than this in front of
+# the rendered one.  1 cm is above what the tracker's pose error and a depth sensor's noise move a surface by (millimetres) and
+# below the thickness of a finger, so a hand on the object is counted and a background pixel grazing the silhouette is not.
+OCCL_MARGIN = 0.01
+
+
+def raycast_check(volume, voxel_scale, intrinsics, rotation, translation, hw, step_scale, min_step, refine, max_steps):
+    """The argument checks of volume_raycast, which mirror pn2s_volume_raycast's (include/pn2_sdf.h) and raise; shared with the torch
+    route (network/models/volume_render.py), so both refuse the same calls.  Devices are not looked at here.
+    -> (res, F, H, W, max_steps) with max_steps = 8 * res when None was given."""
+    for name, t in (("volume", volume), ("intrinsics", intrinsics), ("rotation", rotation), ("translation", translation)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"volume_raycast: {name} must be a torch.Tensor, got {type(t).__name__}")
+        if not t.is_contiguous():
+            raise ValueError(f"volume_raycast: {name} must be contiguous")
+    if volume.dtype not in (torch.float16, torch.float32):
+        raise TypeError(f"volume_raycast: the volume must be float16 or float32, got {volume.dtype}")
+    if volume.dim() != 3 or len(set(volume.shape)) != 1:
+        raise ValueError(f"volume_raycast: the volume must be (res,res,res) in the linear layout, got {tuple(volume.shape)}")
+    res = volume.shape[0]
+    if not 2 <= res <= RAYCAST_MAX_RES:
+        raise ValueError(f"volume_raycast: res must lie in [2, {RAYCAST_MAX_RES}], got {res}")
+    if intrinsics.dim() != 2 or intrinsics.shape[0] < 1:
+        raise ValueError(f"volume_raycast: intrinsics must be (F,4) with F >= 1, got {tuple(intrinsics.shape)}")
+    F = intrinsics.shape[0]
+    for name, t, shape in (("intrinsics", intrinsics, (F, 4)), ("rotation", rotation, (F, 3, 3)), ("translation", translation, (F, 3))):
+        if t.dtype != _f32 or tuple(t.shape) != shape:
+            raise ValueError(f"volume_raycast: {name} must be float32 {shape}, got {t.dtype} {tuple(t.shape)}")
+    H, W = int(hw[0]), int(hw[1])
+    if H < 1 or W < 1 or H * W >= 1 << 29 or H > 8 * 65535 or F > 65535:
+        raise ValueError(f"volume_raycast: an image of {H} x {W}, {F} frames: sizes >= 1, H W < 2^29, H <= 8 * 65535, at most 65535 frames")
+    inf = float("inf")
+    for name, x in (("voxel_scale", voxel_scale), ("step_scale", step_scale), ("min_step", min_step)):
+        if not 0 < float(x) < inf:
+            raise ValueError(f"volume_raycast: {name} must be finite and > 0, got {x}")
+    if int(refine) != refine or not 0 <= int(refine) <= 16:
+        raise ValueError(f"volume_raycast: refine must be an integer in [0, 16], got {refine}")
+    max_steps = 8 * res if max_steps is None else max_steps
+    if int(max_steps) != max_steps or not 1 <= int(max_steps) < 1 << 31:
+        raise ValueError(f"volume_raycast: max_steps must be an integer >= 1, got {max_steps}")
+    return res, F, H, W, int(max_steps)
+
+
+def volume_raycast(volume: torch.Tensor, voxel_scale: float, intrinsics: torch.Tensor, rotation: torch.Tensor, translation: torch.Tensor,
+                   hw, flip_yz: bool = False, normals: bool = True, step_scale: float = 1.0, min_step: float = 0.5, refine: int = 8,
+                   max_steps: int = None):
+    """Renders an SDF volume at F poses with one launch (include/pn2_sdf.h: pn2s_volume_raycast; the rule is stated at the head of
+    hotrack_amd/csrc/sdf_raycast.hip): the inverse of tsdf_integrate's geometry, the ray parameter being the depth.
+    volume (res,res,res) float16 / float32, linear layout;  intrinsics (F,4) fx, fy, cx, cy;  rotation (F,3,3), translation (F,3): the
+    tracked poses (cloud_obj = (pcld - t) @ R);  hw = (H, W);  step_scale / min_step (voxels): the march's step is
+    max(s * step_scale, min_step * voxel_scale) along the ray;  refine: bisections of the bracket;  max_steps: None = 8 * res.
+    All tensors contiguous on one GPU.  Runs on the current stream, no host sync.
+    -> (depth (F,H,W) float32, 0 = no hit;  normal (F,H,W,3) float32 unit vectors in the camera frame, or None with normals=False)."""
+    res, F, H, W, max_steps = raycast_check(volume, voxel_scale, intrinsics, rotation, translation, hw, step_scale, min_step, refine,
+                                            max_steps)
+    for name, t in (("volume", volume), ("intrinsics", intrinsics), ("rotation", rotation), ("translation", translation)):
+        if not t.is_cuda:
+            raise RuntimeError(f"volume_raycast: {name} must be a GPU (HIP) tensor -- hotrack_amd has no CPU path (got device {t.device}); "
+                               "network/models/volume_render.volume_raycast_torch runs anywhere")
+        if t.device != volume.device:
+            raise ValueError(f"volume_raycast: tensors on {volume.device} and {t.device}")
+    depth = torch.empty((F, H, W), dtype=_f32, device=volume.device)
+    normal = torch.empty((F, H, W, 3), dtype=_f32, device=volume.device) if normals else None
+    r = _Raycast(res=res, vol_f16=int(volume.dtype == torch.float16), frames=F, h=H, w=W, flip_yz=int(bool(flip_yz)), refine=int(refine),
+                 max_steps=max_steps, voxel_scale=float(voxel_scale), step_scale=float(step_scale), min_step=float(min_step))
+    r.volume = _native._ptr(volume, "volume", volume.dtype, res ** 3)
+    r.intrinsics = _native._ptr(intrinsics, "intrinsics", _f32, F * 4)
+    r.rotation, r.translation = _native._ptr(rotation, "rotation", _f32, F * 9), _native._ptr(translation, "translation", _f32, F * 3)
+    r.depth, r.normal = depth.data_ptr(), None if normal is None else normal.data_ptr()
+    with torch.cuda.device(volume.device):
+        rc = _lib.pn2s_volume_raycast(ctypes.byref(r), _native._stream(volume))
+    _native._check(rc, "sdf.volume_raycast")
+    return depth, normal
+
+
+def raycast_compare_check(rendered, depth, seg, obj_class, depth_scale, occl_margin):
+    """The argument checks of raycast_compare (pn2s_raycast_compare's, raised), shared with the torch route.
+    -> (F, H, W, Hs, Ws, C, f, depth is raw counts)."""
+    for name, t in (("rendered", rendered), ("depth", depth), ("seg", seg)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"raycast_compare: {name} must be a torch.Tensor, got {type(t).__name__}")
+        if not t.is_contiguous():
+            raise ValueError(f"raycast_compare: {name} must be contiguous")
+    if depth.dim() != 3 or depth.shape[0] < 1:
+        raise ValueError(f"raycast_compare: depth must be (F,H,W) with F >= 1, got {tuple(depth.shape)}")
+    F, H, W = depth.shape
+    if rendered.dtype != _f32 or rendered.shape != depth.shape:
+        raise ValueError(f"raycast_compare: rendered must be float32 {tuple(depth.shape)}, got {rendered.dtype} {tuple(rendered.shape)}")
+    raw = depth.dtype in (torch.uint16, torch.int16)   # (int16: the same 16 bits, as tsdf_integrate)
+    if raw == (depth_scale is None) or (not raw and depth.dtype != _f32):
+        raise TypeError(f"raycast_compare: depth is fp32 metres, or uint16 counts with a depth_scale (got {depth.dtype}, "
+                        f"depth_scale = {depth_scale})")
+    if raw and not 0 < float(depth_scale) < float("inf"):
+        raise ValueError(f"raycast_compare: depth_scale must be finite and > 0, got {depth_scale}")
+    if seg.dtype != torch.uint8 or seg.dim() != 4 or seg.shape[0] != F:
+        raise ValueError(f"raycast_compare: seg must be uint8 (F,Hs,Ws,C) with F = {F}, got {seg.dtype} {tuple(seg.shape)}")
+    _, Hs, Ws, C = seg.shape
+    if min(H, W, Hs, Ws) < 1 or H % Hs or W % Ws or H // Hs != W // Ws or C not in (1, 3) or H * W >= 1 << 29 or F > 65535:
+        raise ValueError(f"raycast_compare: depth {H} x {W}, seg {Hs} x {Ws} x {C}: one integer factor between the two images, "
+                         "C 1 or 3, H W < 2^29, at most 65535 frames")
+    channel, value = int(obj_class[0]), int(obj_class[1])
+    if not (0 <= channel < C and 0 <= value <= 255):
+        raise ValueError(f"raycast_compare: obj_class = (channel, value) with channel in [0, {C}) and value in [0, 255], got {tuple(obj_class)}")
+    if not 0 <= float(occl_margin) < float("inf"):
+        raise ValueError(f"raycast_compare: occl_margin must be finite and >= 0, got {occl_margin}")
+    return F, H, W, Hs, Ws, C, H // Hs, raw
+
+
+def raycast_compare(rendered: torch.Tensor, depth: torch.Tensor, seg: torch.Tensor, obj_class=(1, 255), depth_scale: float = None,
+                    occl_margin: float = OCCL_MARGIN) -> torch.Tensor:
+    """Compares F rendered frames with the observed ones in one launch (include/pn2_sdf.h: pn2s_raycast_compare).
+    rendered (F,H,W) float32 (volume_raycast's depth);  depth (F,H,W) and seg (F,Hs,Ws,C), obj_class, depth_scale: as tsdf_integrate's.
+    -> (F,4) float32: |A n B|, |A u B|, the sum over A n B of |D - Z| and |Occ|, with A the object's pixels with valid depth, Occ the
+    other valid pixels more than occl_margin in front of a model hit, B the model's hits outside Occ.  No host sync."""
+    F, H, W, Hs, Ws, C, _, raw = raycast_compare_check(rendered, depth, seg, obj_class, depth_scale, occl_margin)
+    for name, t in (("rendered", rendered), ("depth", depth), ("seg", seg)):
+        if not t.is_cuda:
+            raise RuntimeError(f"raycast_compare: {name} must be a GPU (HIP) tensor -- hotrack_amd has no CPU path (got device {t.device}); "
+                               "network/models/volume_render.raycast_compare_torch runs anywhere")
+        if t.device != rendered.device:
+            raise ValueError(f"raycast_compare: tensors on {rendered.device} and {t.device}")
+    out = torch.empty((F, 4), dtype=_f32, device=rendered.device)
+    r = _RaycastFrames(frames=F, h=H, w=W, hs=Hs, ws=Ws, c=C, depth_u16=int(raw), channel=int(obj_class[0]), value=int(obj_class[1]),
+                       depth_scale=0.0 if depth_scale is None else float(depth_scale), occl_margin=float(occl_margin))
+    r.rendered = _native._ptr(rendered, "rendered", _f32, F * H * W)
+    r.depth, r.seg = _native._ptr(depth, "depth", depth.dtype, F * H * W), _native._ptr(seg, "seg", torch.uint8, F * Hs * Ws * C)
+    r.out = out.data_ptr()
+    with torch.cuda.device(rendered.device):
+        rc = _lib.pn2s_raycast_compare(ctypes.byref(r), _native._stream(rendered))
+    _native._check(rc, "sdf.raycast_compare")
+    return out

@@ -265,6 +265,77 @@ struct pn2s_tsdf_group {
 typedef struct pn2s_tsdf_group pn2s_tsdf_group;
 int pn2s_tsdf_integrate_batch(const pn2s_tsdf_group *group, void *stream);
 
+/*
+ * An SDF volume rendered to depth and normal maps at tracked poses (hotrack_amd/csrc/sdf_raycast.hip): the raycast, the
+ * image the model predicts.  The geometry is the inverse of pn2s_tsdf_integrate's, so a raycast of a volume at a pose lands on the
+ * pixels pn2s_tsdf_integrate writes that pose's voxels from.  ONE launch renders `frames` >= 1 frames of one volume, one lane per
+ * pixel, a wave per 8 x 8 tile.  pn2s_raycast is HOST memory, read during the call; its pointers are DEVICE memory:
+ *   volume (res^3) fp32 or, with vol_f16 = 1, binary16, the linear layout (ix*res + iy)*res + iz (not the corner layout);
+ *   intrinsics (frames,4) fx, fy, cx, cy;  rotation (frames,3,3) row-major and translation (frames,3): q = R p + t, as pn2s_tsdf_integrate;
+ *   depth (frames,h,w) fp32 out: the hit's depth z, 0 where there is none (the hit mask is depth > 0);
+ *   normal (frames,h,w,3) fp32 out, unit, camera frame, (0,0,0) where there is no hit or no gradient; NULL skips its six samples.
+ * Per pixel (u,v), fp32 (the exact expressions, with their fmaf, are at the head of sdf_raycast.hip):
+ *   ray     c = ((u - cx) / fx, (v - cy) / fy, 1), flip_yz = 1 negates c_y and c_z;  o = -R^T t,  d = R^T c,  speed = |d|.  The ray
+ *           parameter is the DEPTH z (the projective distance of pn2s_tsdf_integrate), the point o + z d;
+ *   box     the trilinear domain [lo, hi]^3, lo = -(res / 2) voxel_scale, hi = lo + (res - 1) voxel_scale: a slab test gives
+ *           [z_in, z_out], z_in = max(z_in, 1e-3); no ray unless z_out > z_in (a NaN gives no ray);
+ *   sample  s(z): the trilinear value at o + z d, grid coordinate (p - lo) / voxel_scale clamped to [0, res - 1], cell
+ *           min((int)g, res - 2), blended in the order of the reference's Distance (optimization_obj.py:223-226), NOT clamped to +-0.05;
+ *   march   z = z_in; no hit unless s(z_in) > 0.  At most max_steps times: dz = max(s step_scale, min_step voxel_scale) / speed,
+ *           z' = min(z + dz, z_out), s' = s(z'); s' <= 0 brackets the surface in [z, z']; otherwise z' >= z_out is no hit.  Out of
+ *           steps is no hit: the loop is bounded by the count, not by convergence, and a NaN sample never hits and never stalls it;
+ *   refine  `refine` bisections keeping s > 0 at the near end and s <= 0 at the far end, then one linear interpolation
+ *           z_hit = z_a + (z_b - z_a) s_a / (s_a - s_b);
+ *   normal  central differences of s at p_hit +- 0.5 voxel_scale per axis, normalised (a zero gradient stays (0,0,0)), n = R g,
+ *           flip_yz applied.
+ * No atomics, no scratch; every pixel is written once; two runs are bitwise equal, `frames` frames in one launch equal `frames`
+ * launches of one, and the depth does not depend on whether normals are asked for.  No host sync or allocation (capturable).
+ * Refused with nothing launched, checked in this order: a NULL record (PN2_ENULL);  PN2_EINVAL for res < 2, frames < 1, h or w < 1,
+ *   vol_f16 / flip_yz not 0 / 1, voxel_scale, step_scale or min_step not finite and > 0, refine outside [0, 16], max_steps < 1;
+ *   PN2_ERANGE for res > 512, h w >= 2^29, frames > 65535 or h > 8 * 65535 (the grid's second dimension);  PN2_ENULL for a NULL
+ *   pointer other than `normal`.
+ */
+struct pn2s_raycast {
+    const void *volume;
+    const float *intrinsics;
+    const float *rotation;
+    const float *translation;
+    float *depth;
+    float *normal; /* may be NULL */
+    float voxel_scale, step_scale, min_step;
+    int res, vol_f16, frames, h, w, flip_yz, refine, max_steps;
+    int pad_; /* to 96 bytes; not read */
+}; /* 96 bytes */
+typedef struct pn2s_raycast pn2s_raycast;
+int pn2s_volume_raycast(const pn2s_raycast *raycast, void *stream);
+
+/*
+ * Rendered frames compared with the observed ones (sdf_raycast.hip: sdf_raycast_compare_kernel), one workgroup per frame.
+ *   rendered (frames,h,w) fp32: Z, what pn2s_volume_raycast wrote (a hit: Z > 0);
+ *   depth (frames,h,w) and seg (frames,hs,ws,c), depth_u16 / depth_scale, channel / value: the observed frames, decoded and
+ *          addressed exactly as pn2s_tsdf_integrate does (D valid: finite and > 0; pixel (v,u) reads seg[v / f, u / f]);
+ *   out (frames,4) fp32.
+ * With  A = the object's pixels with valid depth,  Occ = the other pixels with valid depth where the model hits and
+ * D < Z - occl_margin (something -- the hand -- is in front of the model),  B = the hit pixels outside Occ:
+ *   out[k] = ( |A n B|,  |A u B|,  sum over A n B of |D - Z|,  |Occ| )
+ * counted in integers and converted once; the sum in fp32 in a fixed order.  No atomics: two runs are bitwise equal.
+ * Refused with nothing launched, checked in this order: a NULL record (PN2_ENULL);  PN2_EINVAL for frames < 1, a size < 1, h / hs and
+ *   w / ws not one integer factor, c not 1 or 3, channel outside [0, c), value outside [0, 255], depth_u16 not 0 / 1, depth_u16 = 1
+ *   with a depth_scale that is not finite and > 0, occl_margin not finite or < 0;  PN2_ERANGE for h w >= 2^29 or frames > 65535;
+ *   PN2_ENULL for a NULL pointer.
+ */
+struct pn2s_raycast_frames {
+    const float *rendered;
+    const void *depth;
+    const unsigned char *seg;
+    float *out;
+    double depth_scale;
+    float occl_margin;
+    int frames, h, w, hs, ws, c, depth_u16, channel, value;
+}; /* 80 bytes */
+typedef struct pn2s_raycast_frames pn2s_raycast_frames;
+int pn2s_raycast_compare(const pn2s_raycast_frames *frames, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

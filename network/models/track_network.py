@@ -660,6 +660,14 @@ class ObjTrackModel_Optimization(nn.Module):
         # of the volume and its weights, and from its first flush on a corner layout (201^3 fp16: 49 MB + 130 MB per sequence)
         self.lockstep_fuse = bool(opt_cfg.get("lockstep_fuse", False))
         self._fuse_frontend = dict(cfg.get("depth_frontend") or {})
+        # opt.render_model: at the end of a sequence render its volume (with opt.fuse_depth the fused one) at every tracked pose in
+        # one launch and compare the maps with the observed frames in a second (models/volume_render.py,
+        # hotrack_amd/csrc/sdf_raycast.hip); the poses do not depend on it.  render_occl_margin (metres) is a choice, like
+        # contact_threshold: how far in front of the model a non-object pixel must lie to count as an occluder
+        # (hotrack_amd.sdf.OCCL_MARGIN says why 1 cm).  render_route: None (the kernels for a GPU volume), 'kernel' or 'torch'
+        self.render_model = bool(opt_cfg.get("render_model", False))
+        self.render_occl_margin = float(opt_cfg.get("render_occl_margin", 0.01))
+        self.render_route = None
         self.surface_seed = 0  # every sequence draws from a generator of its own with this seed: alone or in a group, the same surface
         self.save_folder = cfg.get("save_dir")
 
@@ -698,9 +706,42 @@ class ObjTrackModel_Optimization(nn.Module):
             mesh_sdf.save_mesh(path, hit[1]["vertices"], hit[1]["faces"])
         rets[0]["obj_info"] = {"recon_path": path, "recon_mesh": hit[1]}
 
+    def _check_render_frames(self, frame0, where="frame 0"):
+        """opt.render_model, before any work: the frames must carry what the comparison reads."""
+        missing = [k for k in ("depth", "seg", "intrinsics") if k not in frame0]
+        if missing:
+            raise KeyError(f"opt.render_model compares the rendered model with the observed depth frames: the sequence's frames must "
+                           f"carry 'depth', 'seg' and 'intrinsics' (as the --from_depth frames do); {where} "
+                           f"({frame0['file_name'][0]}) lacks {missing}")
+
+    def _attach_render(self, input, rets, kept, volume, voxel_scale, fused, flag_dict):
+        """opt.render_model, at the end of a sequence: `kept` holds every frame and its tracked pose (device references).  All frames
+        are rendered in one launch and compared in a second (volume_render.model_frame_fit); a fused volume is marched with
+        step_scale 0.8, because a projective TSDF overestimates the distance at grazing angles.
+        rets[0]['obj_render'] = {'depth' (F,H,W), 'normal' (F,H,W,3), 'stats' (F,4), 'columns' (3,), 'skipped' ()}; with --save and
+        a save directory the last frame's maps are written as <sequence>_model_depth.png / _model_normal.png."""
+        import os
+        from . import volume_render
+        fe = self._fuse_frontend
+        out = volume_render.model_frame_fit(volume, voxel_scale, [d for d, _ in kept], [r for _, r in kept],
+                                            obj_class=tuple(fe.get("obj_class", (1, 255))), flip_yz=bool(fe.get("flip_yz", False)),
+                                            step_scale=0.8 if fused else 1.0, occl_margin=getattr(self, "render_occl_margin", 0.01),
+                                            route=getattr(self, "render_route", None))
+        rets[0]["obj_render"] = out
+        if flag_dict.get("save_flag") and getattr(self, "save_folder", None):
+            name = os.path.dirname(input[0]["file_name"][0]) or input[0]["file_name"][0]
+            os.makedirs(self.save_folder, exist_ok=True)
+            stem = os.path.join(self.save_folder, name.replace("/", "_"))
+            out["paths"] = (volume_render.save_depth_png(stem + "_model_depth.png", out["depth"][-1]),
+                            volume_render.save_normal_png(stem + "_model_normal.png", out["normal"][-1]))
+
     def forward(self, input, flag_dict):
         flag_dict["track_flag"] = True
         assert flag_dict["test_flag"]
+        render = getattr(self, "render_model", False) and len(input) > 0
+        if render:
+            self._check_render_frames(input[0])
+        kept = []
         if "sdf_volume" in input[0]:
             self.optimizer.load_volume(input[0]["sdf_volume"], input[0].get("voxel_scale"))
         elif not _load_mesh_volume(self.optimizer, input[0], self.device) and self.optimizer.sdf_volume is None:
@@ -712,7 +753,7 @@ class ObjTrackModel_Optimization(nn.Module):
         surf = None
         fusion = self._new_fusion(input) if getattr(self, "fuse_depth", False) and len(input) else None
         for data in input:
-            if fusion is not None:  # one upload serves the front end and the fusion
+            if fusion is not None or render:  # one upload serves the front end, the fusion and the rendering's comparison
                 for key in ("depth", "seg"):
                     if key in data and isinstance(data[key], torch.Tensor):
                         data[key] = data[key].to(self.device, non_blocking=True)
@@ -735,6 +776,9 @@ class ObjTrackModel_Optimization(nn.Module):
             last["prev_translation"], last["prev_rotation"] = last["translation"], last["rotation"]  # last frame's pose
             last["translation"], last["rotation"] = ret["translation"], ret["rotation"]            # current frame's pose
             rets.append(ret)
+            if render:
+                self._check_render_frames(data, f"frame {len(rets) - 1}")
+                kept.append((data, ret))
             if fusion is not None:
                 missing = [k for k in ("depth", "seg", "intrinsics") if k not in data]
                 if missing:
@@ -746,6 +790,8 @@ class ObjTrackModel_Optimization(nn.Module):
             if fusion.pending:
                 self.optimizer.load_volume(fusion.flush(), fusion.voxel_scale)
             rets[0]["obj_fused"] = fusion.state()
+        if render:  # (after the last flush: the fused volume, else the loaded one)
+            self._attach_render(input, rets, kept, self.optimizer.sdf_volume, self.optimizer.voxel_scale, fusion is not None, flag_dict)
         if surf is not None:
             rets[0]["obj_surface"] = self._surface_entry(surf, self.optimizer._corners, self.optimizer.voxel_scale)
         if getattr(self, "extract_mesh", False) and rets:
@@ -819,6 +865,11 @@ class ObjTrackModel_Optimization(nn.Module):
                              "--seq_batch 1")
         flag_dict["track_flag"] = True
         assert flag_dict["test_flag"]
+        render = getattr(self, "render_model", False)
+        if render:  # before any work, as `forward`
+            for k, seq in enumerate(inputs):
+                for t, data in enumerate(seq):
+                    self._check_render_frames(data, f"sequence {k}, frame {t}")
         if fuse:  # before any work: every frame must carry what the fusion reads
             for k, seq in enumerate(inputs):
                 for t, data in enumerate(seq):
@@ -846,7 +897,7 @@ class ObjTrackModel_Optimization(nn.Module):
             live = [k for k in range(S) if t < len(inputs[k])]
             for k in live:
                 data = inputs[k][t]
-                if group is not None:  # one upload serves the front end and the fusion
+                if group is not None or render:  # one upload serves the front end, the fusion and the rendering's comparison
                     for key in ("depth", "seg"):
                         if isinstance(data[key], torch.Tensor):
                             data[key] = data[key].to(self.device, non_blocking=True)
@@ -889,6 +940,11 @@ class ObjTrackModel_Optimization(nn.Module):
         for k in range(S):
             if group is not None and rets[k]:
                 rets[k][0]["obj_fused"] = group.state(k)
+            if render and rets[k]:
+                # every sequence after the group has finished, one launch per sequence as `forward` (a batched, multi-volume
+                # raycast is not built: DESIGN.md 8m); vols[k].source is the sequence's volume, fused if it was
+                self._attach_render(inputs[k], rets[k], list(zip(inputs[k], rets[k])), vols[k].source, known[0][1], group is not None,
+                                    flag_dict)
             if surfs[k] is not None:
                 rets[k][0]["obj_surface"] = self._surface_entry(surfs[k], vols[k], known[0][1])
         if getattr(self, "extract_mesh", False):
@@ -920,7 +976,10 @@ class ObjTrackModel_Optimization(nn.Module):
                                                   (mesh_sdf.sample_surface, seed 0); with neither, and opt.extract_mesh on, from
                                                   the mesh extracted from the sequence's volume
                                                   (ret_dict_lst[0]['obj_info']['recon_mesh']); else the two keys are absent
-                                                  and the log says so once."""
+                                                  and the log says so once;
+          model_depth_residual(mm), model_silhouette_iou, model_occluded_ratio   with opt.render_model: the sequence's volume
+                                                  rendered at the tracked poses against the observed depth frames, means over
+                                                  frames (volume_render.fit_columns); they need no ground truth."""
         from . import eval_metrics
         r_err = t_err = a_err = 0.0
         gRs, gts, Rs, ts = [], [], [], []
@@ -973,6 +1032,11 @@ class ObjTrackModel_Optimization(nn.Module):
         if surface is not None:  # opt.accumulate_surface: how well the model fits what was seen (obs_surface.surface_fit)
             keys += ["obs_surface_residual(mm)", "obs_surface_normal_agree"]
             vals += [surface["fit"][0], surface["fit"][1]]
+        rendered = ret_dict_lst[0].get("obj_render")
+        if rendered is not None:  # opt.render_model: the rendered model against the observed frames (volume_render.fit_columns)
+            from .volume_render import COLUMNS
+            keys += list(COLUMNS)
+            vals += list(rendered["columns"].unbind())
         host = torch.stack([torch.as_tensor(v, dtype=torch.float32, device=self.device).reshape(()) for v in vals]).tolist()  # the one read-back
         out = dict(zip(keys, host))
         for k in keys[:3]:

@@ -77,6 +77,14 @@ def add_args(parser):
                              "every sequence of a group owns a copy of the volume and its weights and, from its first flush on, of "
                              "the corner layout -- at 201^3 fp16 about 49 MB plus 130 MB per sequence.  Without --fuse_obj_depth "
                              "it changes nothing")
+    parser.add_argument("--render_obj_model", dest="opt/render_model", action="store_const", const=True, default=None,
+                        help="track=obj_opt on frames that carry depth images (--from_depth): at the end of a sequence render its SDF "
+                             "volume (with --fuse_obj_depth the fused one) at every tracked pose in one launch and compare the depth "
+                             "maps with the observed frames in a second (models/volume_render.py, hotrack_amd/csrc/sdf_raycast.hip); "
+                             "report model_depth_residual(mm), model_silhouette_iou and model_occluded_ratio, which need no ground "
+                             "truth, and put the maps into ret_dict_lst[0]['obj_render']; --save writes the last frame's depth and "
+                             "normal maps as <sequence>_model_depth.png / _model_normal.png.  opt.render_occl_margin (0.01 m) is read "
+                             "from the configuration.  The tracked poses do not depend on it")
     parser.add_argument("--obj_model_radius", type=float, default=None,
                         help="track=obj_opt, synthetic sequences: the radius of the capsule the handed-over SDF volume describes "
                              "(default 0.04, the true one the clouds and depth frames show): another value hands over a wrong model")

@@ -4,7 +4,10 @@ Same entry point as the reference's network/test.py: per-sequence tracking (batc
 frame t-1), prints data / network frames-per-second like the reference (test.py:65-98) -- here with an
 explicit device synchronisation so the network time is real.  Enables the fused inference backend.
 --seq_batch S (track: obj_opt only): S sequences at a time in lockstep, one batched optimiser call per frame step; with
---fuse_obj_depth it needs --lockstep_fuse (a volume copy per sequence; one fusion launch per flush for the whole group)."""
+--fuse_obj_depth it needs --lockstep_fuse (a volume copy per sequence; one fusion launch per flush for the whole group).
+--render_obj_model (track: obj_opt, --from_depth): every sequence's volume rendered at its tracked poses and compared with the
+observed frames -- "Test model_depth_residual(mm) / model_silhouette_iou / model_occluded_ratio" lines that need no ground truth;
+with --save the last frame's maps as PNGs."""
 import argparse
 import logging
 import os
