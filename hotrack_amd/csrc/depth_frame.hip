@@ -9,8 +9,9 @@
 //                           wave, a prefix over the four waves) and stores every kept point at the slot its rank decides.
 // The order across tiles comes from the launch boundary alone: no atomics, no workgroup waits for another, and every slot of
 // every output is written by exactly one workgroup on every call.  Arithmetic is fp32 with every operation rounded once (the
-// build sets -ffp-contract=off and correctly rounded '/' and sqrtf), so a numpy restatement reproduces it bit for bit.
-#include "pn2_common.h"
+// build sets -ffp-contract=off and correctly rounded '/' and sqrtf), so a numpy restatement reproduces it bit for bit.  What a
+// depth pixel is in metres and which segment cell is its own: frame_device.h.
+#include "frame_device.h"
 #include "../../include/pn2_ext.h"
 
 namespace pn2 {
@@ -20,20 +21,16 @@ constexpr int kThreads = 256, kPerThread = 4, kTile = kThreads * kPerThread, kWa
 
 struct Args {
     const void *depth;
-    const unsigned char *seg;
+    SegMap class0, class1;  // the two classes, over one seg
     const float *intrinsics, *centre0, *centre1;
     float *clouds;
     int *counts;
     unsigned char *background;
     int *work;
     double depth_scale;
-    int h, w, ws, c, f, cap, tiles, flip;
-    int channel0, channel1, value0, value1;
+    int h, w, cap, tiles, flip;
     float radius0, radius1;
 };
-
-__device__ __forceinline__ float decode(float raw, double) { return raw; }
-__device__ __forceinline__ float decode(unsigned short raw, double scale) { return (float)((double)raw * scale); }
 
 __device__ __forceinline__ void load4(const float *p, float (&raw)[4]) {
     const float4 q = *reinterpret_cast<const float4 *>(p);
@@ -62,16 +59,16 @@ __device__ __forceinline__ void classify(const Args &A, int b, int p0, float (&x
     const float fx = A.intrinsics[4 * b], fy = A.intrinsics[4 * b + 1], cx = A.intrinsics[4 * b + 2], cy = A.intrinsics[4 * b + 3];
     const float ax = A.centre0[3 * b], ay = A.centre0[3 * b + 1], az = A.centre0[3 * b + 2];
     const float bx = A.centre1[3 * b], by = A.centre1[3 * b + 1], bz = A.centre1[3 * b + 2];
-    const unsigned char *seg = A.seg + (size_t)b * (A.h / A.f) * A.ws * A.c;
+    const unsigned char *seg = A.class0.frame(b);
     int v = p0 / A.w, u = p0 - v * A.w;
     m0 = m1 = bg = 0;
 #pragma unroll
     for (int j = 0; j < kPerThread; ++j) {
         x[j] = y[j] = z[j] = 0.f;
         if (p0 + j < hw) {
-            const unsigned char *sp = seg + ((size_t)(v / A.f) * A.ws + (u / A.f)) * A.c;
+            const unsigned char *sp = A.class0.cell(seg, A.class0.down(v), A.class0.down(u));
             unsigned any = sp[0];
-            if (A.c == 3) any |= (unsigned)sp[1] | (unsigned)sp[2];
+            if (A.class0.c == 3) any |= (unsigned)sp[1] | (unsigned)sp[2];
             bg |= (any == 0 ? 1u : 0u) << j;
             float pz = decode(raw[j], A.depth_scale);
             if (pz > 1e-6f) {
@@ -82,11 +79,11 @@ __device__ __forceinline__ void classify(const Args &A, int b, int p0, float (&x
                     pz = -pz;
                 }
                 x[j] = px; y[j] = py; z[j] = pz;
-                if (sp[A.channel0] == A.value0) {
+                if (A.class0.holds(sp)) {
                     const float dx = px - ax, dy = py - ay, dz = pz - az;
                     m0 |= (sqrtf((dx * dx + dy * dy) + dz * dz) < A.radius0 ? 1u : 0u) << j;
                 }
-                if (sp[A.channel1] == A.value1) {
+                if (A.class1.holds(sp)) {
                     const float dx = px - bx, dy = py - by, dz = pz - bz;
                     m1 |= (sqrtf((dx * dx + dy * dy) + dz * dz) < A.radius1 ? 1u : 0u) << j;
                 }
@@ -243,21 +240,15 @@ using namespace pn2::dframe;
 
 static_assert(sizeof(pn2x_depth_frame) == 144, "record layout (pn2_ext.h)");
 
-// a bad value before a limit before a NULL pointer, whichever check found it (as the hand-pose boundary)
-struct Faults {
-    bool inval = false, range = false, null = false;
-    int code() const { return inval ? PN2_EINVAL : range ? PN2_ERANGE : null ? PN2_ENULL : PN2_OK; }
-};
-
-static void check_geometry(int h, int w, int hs, int ws, int c, int cap, Faults &f) {
-    const bool sizes = h >= 1 && w >= 1 && hs >= 1 && ws >= 1;
-    f.inval |= !sizes || h % hs != 0 || w % ws != 0 || h / hs != w / ws || (c != 1 && c != 3) || cap < 1;
-    f.range |= (sizes && (long)h * w >= (1L << 29)) || cap > 16384;
+static void check_geometry(int b, int h, int w, int hs, int ws, int c, int cap, Faults &f) {
+    check_image_pair(b, h, w, hs, ws, c, f);
+    f.inval |= cap < 1;
+    f.range |= cap > 16384;
 }
 
 extern "C" int pn2x_depth_frame_supported(int h, int w, int hs, int ws, int c, int cap) {
     Faults f;
-    check_geometry(h, w, hs, ws, c, cap, f);
+    check_geometry(0, h, w, hs, ws, c, cap, f);
     return f.code() == PN2_OK ? 1 : 0;
 }
 
@@ -271,19 +262,22 @@ extern "C" int pn2x_depth_frame_clouds(const pn2x_depth_frame *frames, void *str
     if (!frames) return PN2_ENULL;
     const pn2x_depth_frame &r = *frames;
     Faults f;
-    check_geometry(r.h, r.w, r.hs, r.ws, r.c, r.cap, f);
+    check_geometry(r.b, r.h, r.w, r.hs, r.ws, r.c, r.cap, f);
+    // (b may be 0, and depth_scale is not looked at: a scale the decoding cannot use is the caller's own)
     f.inval |= r.b < 0 || (r.depth_u16 != 0 && r.depth_u16 != 1) || (r.flip_yz != 0 && r.flip_yz != 1);
-    for (int k = 0; k < 2; ++k)
-        f.inval |= r.channel[k] < 0 || r.channel[k] >= r.c || r.value[k] < 0 || r.value[k] > 255 || !(r.radius[k] > 0.f);
-    f.range |= r.b > 65535;
+    for (int k = 0; k < 2; ++k) {
+        check_class(r.channel[k], r.value[k], r.c, f);
+        f.inval |= !(r.radius[k] > 0.f);
+    }
     if (r.b != 0)
         f.null |= !r.depth || !r.seg || !r.intrinsics || !r.centre[0] || !r.centre[1] || !r.clouds || !r.counts || !r.background || !r.work;
     if (f.code() != PN2_OK || r.b == 0) return f.code();
     Args A;
-    A.depth = r.depth; A.seg = r.seg; A.intrinsics = r.intrinsics; A.centre0 = r.centre[0]; A.centre1 = r.centre[1];
+    A.depth = r.depth; A.intrinsics = r.intrinsics; A.centre0 = r.centre[0]; A.centre1 = r.centre[1];
     A.clouds = r.clouds; A.counts = r.counts; A.background = r.background; A.work = r.work; A.depth_scale = r.depth_scale;
-    A.h = r.h; A.w = r.w; A.ws = r.ws; A.c = r.c; A.f = r.h / r.hs; A.cap = r.cap; A.tiles = (int)tiles_of(r.h, r.w); A.flip = r.flip_yz;
-    A.channel0 = r.channel[0]; A.channel1 = r.channel[1]; A.value0 = r.value[0]; A.value1 = r.value[1];
+    A.class0 = seg_map(r.seg, r.h, r.hs, r.ws, r.c, r.channel[0], r.value[0]);
+    A.class1 = seg_map(r.seg, r.h, r.hs, r.ws, r.c, r.channel[1], r.value[1]);
+    A.h = r.h; A.w = r.w; A.cap = r.cap; A.tiles = (int)tiles_of(r.h, r.w); A.flip = r.flip_yz;
     A.radius0 = r.radius[0]; A.radius1 = r.radius[1];
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(A.tiles, r.b), block(kThreads);

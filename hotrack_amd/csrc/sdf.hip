@@ -7,8 +7,6 @@
 //
 // Arithmetic follows the reference's torch expressions operation for operation (fp32, true division, same
 // association; compiled with -ffp-contract=off), so Distance() is bit-identical to the reference.
-#include <hip/hip_fp16.h>
-
 #include "pn2_common.h"
 #include "sdf_device.h"
 #include "../../include/pn2_sdf.h"
@@ -20,12 +18,6 @@ struct SdfVol {
     int res;
     float bbox_min, stride, lo, hi;
 };
-
-template <int FMT>
-__device__ __forceinline__ float vol_at(const void *v, int i) {
-    if constexpr (FMT & 1) return __half2float(reinterpret_cast<const __half *>(v)[i]);
-    else return reinterpret_cast<const float *>(v)[i];
-}
 
 // One point of gf_optimize_obj.Distance (optimization_obj.py:184-228), in three steps so that callers can issue
 // the gathers of several points before blending any of them (the kernel is gather-latency bound).
@@ -102,10 +94,11 @@ __device__ __forceinline__ void tri_gather(const SdfVol &A, const TriPoint &t, f
         return;
     }
     // the reference clamps each corner index to [0, res^3 - 1] (:215-222); only the upper clamp can bind
-    d[0] = vol_at<FMT>(A.p, i);                          d[1] = vol_at<FMT>(A.p, min(i + 1, last));
-    d[2] = vol_at<FMT>(A.p, min(i + R, last));           d[3] = vol_at<FMT>(A.p, min(i + 1 + R, last));
-    d[4] = vol_at<FMT>(A.p, min(i + RR, last));          d[5] = vol_at<FMT>(A.p, min(i + 1 + RR, last));
-    d[6] = vol_at<FMT>(A.p, min(i + R + RR, last));      d[7] = vol_at<FMT>(A.p, min(i + 1 + R + RR, last));
+    constexpr bool kF16 = (FMT & 1) != 0;
+    d[0] = ld_vol<kF16>(A.p, i);                         d[1] = ld_vol<kF16>(A.p, min(i + 1, last));
+    d[2] = ld_vol<kF16>(A.p, min(i + R, last));          d[3] = ld_vol<kF16>(A.p, min(i + 1 + R, last));
+    d[4] = ld_vol<kF16>(A.p, min(i + RR, last));         d[5] = ld_vol<kF16>(A.p, min(i + 1 + RR, last));
+    d[6] = ld_vol<kF16>(A.p, min(i + R + RR, last));     d[7] = ld_vol<kF16>(A.p, min(i + 1 + R + RR, last));
 }
 
 __device__ __forceinline__ float tri_blend(const SdfVol &A, const TriPoint &t, const float *d) {

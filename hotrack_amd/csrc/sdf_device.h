@@ -1,7 +1,7 @@
-// sdf_device.h -- device arithmetic shared by the particle optimisers' kernels (sdf.hip, hand_pose.hip, hand_interact.hip): the
-// object-frame transform, torch's floor division and the nearest-voxel index of gf_optimize_hand_pose.query_sdf, the lookup
-// fused into the hand kernels, and the small rotation helpers of the pose updates.  One definition, so that a lookup fused
-// into another kernel reads the same voxel as pn2s_nearest for every input.
+// sdf_device.h -- device arithmetic shared by the kernels that read an SDF volume (sdf.hip, hand_pose.hip, hand_interact.hip,
+// tsdf_fuse.hip, sdf_raycast.hip, sdf_mesh.hip): the volume-element loader, the object-frame transform, torch's floor division
+// and the nearest-voxel index of gf_optimize_hand_pose.query_sdf, the lookup fused into the hand kernels, and the small rotation
+// helpers of the pose updates.  One definition, so that a lookup fused into another kernel reads the same voxel as pn2s_nearest.
 #pragma once
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
@@ -50,15 +50,25 @@ __device__ __forceinline__ int nearest_voxel(float ox, float oy, float oz, float
     return (ix * res + iy) * res + iz;
 }
 
+// Element i of a volume, linear or corner layout, fp16 or fp32, as fp32; and its store, an fp16 volume rounded to nearest even.
+template <bool F16>
+__device__ __forceinline__ float ld_vol(const void *vol, int i) {
+    if (F16) return __half2float(reinterpret_cast<const __half *>(vol)[i]);
+    return reinterpret_cast<const float *>(vol)[i];
+}
+template <bool F16>
+__device__ __forceinline__ void st_vol(void *vol, int i, float x) {
+    if (F16) reinterpret_cast<__half *>(vol)[i] = __float2half_rn(x);
+    else reinterpret_cast<float *>(vol)[i] = x;
+}
+
 // query_sdf for one camera-frame point: the object frame, the nearest voxel, the volume's value (fp16 or fp32) as fp32
 template <bool F16>
 __device__ __forceinline__ float sdf_nearest(const void *vol, float x, float y, float z, const float *ot, const float *oR,
                                              float voxel_scale, int res) {
     float ox, oy, oz;
     to_object_frame(x, y, z, ot, oR, ox, oy, oz);
-    const int flat = nearest_voxel(ox, oy, oz, voxel_scale, res);
-    if constexpr (F16) return __half2float(reinterpret_cast<const __half *>(vol)[flat]);
-    else return reinterpret_cast<const float *>(vol)[flat];
+    return ld_vol<F16>(vol, nearest_voxel(ox, oy, oz, voxel_scale, res));
 }
 
 __device__ __forceinline__ void quat_to_matrix(float w, float x, float y, float z, float *m) {  // rotations.py:105-113

@@ -33,10 +33,10 @@
 //           scan of the cells' counts inside the workgroup, their corners looked up the same way.
 // A lane reads the four rows (its own, +y, +x, +x+y) once each; the +z neighbours come from the next lane of the wave (the
 // last lane of a wave reads them itself).
-#include <hip/hip_fp16.h>
 #include <cmath>
 
 #include "pn2_common.h"
+#include "sdf_device.h"
 #include "../../include/pn2_sdf.h"
 
 namespace pn2 {
@@ -114,12 +114,6 @@ constexpr unsigned kVmBitsOfClass = 1u | 2u << 3 | 4u << 6 | 3u << 9 | 5u << 12 
 constexpr unsigned kVmEdgeP = 0u | 0u << 2 | 0u << 4 | 1u << 6 | 1u << 8 | 2u << 10;
 constexpr unsigned kVmEdgeQ = 1u | 2u << 2 | 3u << 4 | 2u << 6 | 3u << 8 | 3u << 10;
 
-template <bool F16>
-__device__ __forceinline__ float vm_ld(const void *vol, int i) {
-    if (F16) return __half2float(reinterpret_cast<const __half *>(vol)[i]);
-    return reinterpret_cast<const float *>(vol)[i];
-}
-
 // What a lane knows of the cell whose lower corner is its grid vertex.
 struct VmCell {
     float s[8];      // corner values by offset bits; a corner outside the grid reads as s[0]
@@ -139,16 +133,16 @@ __device__ __forceinline__ void vm_cell(const void *vol, int res, int n, int lin
     c.iz = l % res;
     const bool vx = live && c.ix < res - 1, vy = live && c.iy < res - 1, vz = live && c.iz < res - 1;
     float r[4];  // the rows: this vertex, +x, +y, +x+y
-    r[0] = live ? vm_ld<F16>(vol, l) : 0.f;
-    r[1] = vx ? vm_ld<F16>(vol, l + res * res) : 0.f;
-    r[2] = vy ? vm_ld<F16>(vol, l + res) : 0.f;
-    r[3] = vx && vy ? vm_ld<F16>(vol, l + res * res + res) : 0.f;
+    r[0] = live ? ld_vol<F16>(vol, l) : 0.f;
+    r[1] = vx ? ld_vol<F16>(vol, l + res * res) : 0.f;
+    r[2] = vy ? ld_vol<F16>(vol, l + res) : 0.f;
+    r[3] = vx && vy ? ld_vol<F16>(vol, l + res * res + res) : 0.f;
     const bool own = (threadIdx.x & (kWave - 1)) == kWave - 1;  // no next lane
 #pragma unroll
     for (int o = 0; o < 4; ++o) {
         const bool have = (!(o & 1) || vx) && (!(o & 2) || vy);
         float z = __shfl_down(r[o], 1);  // lane + 1 holds vertex lin + 1 = this vertex + e_z where vz
-        if (own) z = have && vz ? vm_ld<F16>(vol, l + (o & 1) * res * res + (o >> 1) * res + 1) : 0.f;
+        if (own) z = have && vz ? ld_vol<F16>(vol, l + (o & 1) * res * res + (o >> 1) * res + 1) : 0.f;
         c.s[o] = have ? r[o] : r[0];
         c.s[o | 4] = have && vz ? z : r[0];
     }

@@ -40,10 +40,8 @@
 //
 // pn2s_raycast_compare: one workgroup of 1024 lanes per frame walks the frame's pixels in a fixed order, counts in integers and sums
 // |D - Z| in fp32 per lane, then per wave (xor butterfly), then over the 16 waves in order: no atomics, two runs are bitwise equal.
-#include <hip/hip_fp16.h>
-#include <cmath>
-
-#include "pn2_common.h"
+#include "frame_device.h"
+#include "sdf_device.h"
 #include "../../include/pn2_sdf.h"
 
 namespace pn2 {
@@ -58,12 +56,6 @@ struct Args {
     float voxel_scale, step_scale, min_step;
     int res, h, w, flip, refine, max_steps;
 };
-
-template <bool F16>
-__device__ __forceinline__ float ld_vol(const void *vol, int i) {
-    if (F16) return __half2float(reinterpret_cast<const __half *>(vol)[i]);
-    return reinterpret_cast<const float *>(vol)[i];
-}
 
 // The volume as the sampler sees it: every index it forms lies in [0, res^3) whatever the point (a NaN coordinate clamps to 0).
 struct Field {
@@ -195,18 +187,15 @@ __global__ __launch_bounds__(kTile * kTile * kTilesPerBlock) void sdf_raycast_ke
 struct CompareArgs {
     const float *rendered;
     const void *depth;
-    const unsigned char *seg;
     float *out;
     double depth_scale;
     float occl_margin;
-    int h, w, hs, ws, c, f, fshift, channel, value;
+    int h, w;
+    SegMap object;
 };
 
-__device__ __forceinline__ float decode(float raw, double) { return raw; }
-__device__ __forceinline__ float decode(unsigned short raw, double scale) { return (float)((double)raw * scale); }  // as tsdf_fuse.hip
-
 // Frame blockIdx.x.  With D the observed depth (valid: D > 0 and finite), Z the rendered one (a hit: Z > 0) and `object` the pixel's
-// segment byte seg[v / f, u / f, channel] == value:
+// segment byte seg[v / f, u / f, channel] == value (frame_device.h):
 //   A = object and valid;   Occ = not object, valid, a hit, D < Z - occl_margin (something in front of the model);   B = a hit outside Occ
 //   out[frame] = (|A n B|, |A u B|, sum over A n B of |D - Z|, |Occ|), the counts converted from integers at the end.
 template <typename D>
@@ -216,17 +205,16 @@ __global__ __launch_bounds__(kCompareLanes) void sdf_raycast_compare_kernel(cons
     const int fr = blockIdx.x, tid = threadIdx.x;
     const float *Zf = A.rendered + (size_t)fr * A.h * A.w;
     const D *Df = static_cast<const D *>(A.depth) + (size_t)fr * A.h * A.w;
-    const unsigned char *seg = A.seg + (size_t)fr * A.hs * A.ws * A.c;
+    const unsigned char *seg = A.object.frame(fr);
     unsigned n_and = 0, n_or = 0, n_occ = 0;
     float sum = 0.f;
     // rows by the lane's row of the workgroup, columns by its column: no division of a pixel index.  kCompareLanes = 16 rows of 64
     for (int v = tid >> 6; v < A.h; v += kCompareLanes / kWave) {
-        const int vs = A.fshift >= 0 ? v >> A.fshift : v / A.f;
+        const int vs = A.object.down(v);
         for (int u = tid & 63; u < A.w; u += kWave) {
             const float Z = Zf[(size_t)v * A.w + u];
             const float Dz = decode(Df[(size_t)v * A.w + u], A.depth_scale);
-            const int us = A.fshift >= 0 ? u >> A.fshift : u / A.f;
-            const bool obj = seg[((size_t)vs * A.ws + us) * A.c + A.channel] == A.value;
+            const bool obj = A.object.holds(A.object.cell(seg, vs, A.object.down(u)));
             const bool valid = Dz > 0.f && Dz != __builtin_inff();
             const bool hit = Z > 0.f;
             const bool occ = !obj && valid && hit && Dz < Z - A.occl_margin;
@@ -270,8 +258,6 @@ using namespace pn2::raycast;
 static_assert(sizeof(pn2s_raycast) == 96, "record layout (pn2_sdf.h)");
 static_assert(sizeof(pn2s_raycast_frames) == 80, "record layout (pn2_sdf.h)");
 
-static inline bool finite_positive(float x) { return std::isfinite(x) && x > 0.f; }
-
 extern "C" int pn2s_volume_raycast(const pn2s_raycast *raycast, void *stream) {
     if (!raycast) return PN2_ENULL;
     const pn2s_raycast &r = *raycast;
@@ -302,22 +288,16 @@ extern "C" int pn2s_volume_raycast(const pn2s_raycast *raycast, void *stream) {
 extern "C" int pn2s_raycast_compare(const pn2s_raycast_frames *frames, void *stream) {
     if (!frames) return PN2_ENULL;
     const pn2s_raycast_frames &r = *frames;
-    const bool sizes = r.h >= 1 && r.w >= 1 && r.hs >= 1 && r.ws >= 1;
-    bool inval = r.frames < 1 || !sizes || (r.depth_u16 != 0 && r.depth_u16 != 1) || (r.c != 1 && r.c != 3);
-    inval |= sizes && (r.h % r.hs != 0 || r.w % r.ws != 0 || r.h / r.hs != r.w / r.ws);
-    inval |= r.channel < 0 || r.channel >= r.c || r.value < 0 || r.value > 255;
-    inval |= r.depth_u16 == 1 && !(std::isfinite(r.depth_scale) && r.depth_scale > 0.0);
-    inval |= !(std::isfinite(r.occl_margin) && r.occl_margin >= 0.f);
-    if (inval) return PN2_EINVAL;
-    if ((long)r.h * r.w >= (1L << 29) || r.frames > 65535) return PN2_ERANGE;
-    if (!r.rendered || !r.depth || !r.seg || !r.out) return PN2_ENULL;
+    Faults f;
+    f.inval = r.frames < 1 || !(std::isfinite(r.occl_margin) && r.occl_margin >= 0.f);
+    check_image_pair(r.frames, r.h, r.w, r.hs, r.ws, r.c, f);
+    check_class(r.channel, r.value, r.c, f);
+    check_depth_encoding(r.depth_u16, r.depth_scale, f);
+    f.null = !r.rendered || !r.depth || !r.seg || !r.out;
+    if (f.code() != PN2_OK) return f.code();
     CompareArgs A;
-    A.rendered = r.rendered; A.depth = r.depth; A.seg = r.seg; A.out = r.out; A.depth_scale = r.depth_scale;
-    A.occl_margin = r.occl_margin;
-    A.h = r.h; A.w = r.w; A.hs = r.hs; A.ws = r.ws; A.c = r.c; A.f = r.h / r.hs; A.channel = r.channel; A.value = r.value;
-    A.fshift = -1;
-    for (int s = 0; s < 30; ++s)
-        if (A.f == (1 << s)) A.fshift = s;
+    A.rendered = r.rendered; A.depth = r.depth; A.object = seg_map(r.seg, r.h, r.hs, r.ws, r.c, r.channel, r.value); A.out = r.out;
+    A.depth_scale = r.depth_scale; A.occl_margin = r.occl_margin; A.h = r.h; A.w = r.w;
     hipStream_t st = (hipStream_t)stream;
     if (r.depth_u16) hipLaunchKernelGGL((sdf_raycast_compare_kernel<unsigned short>), dim3(r.frames), dim3(kCompareLanes), 0, st, A);
     else hipLaunchKernelGGL((sdf_raycast_compare_kernel<float>), dim3(r.frames), dim3(kCompareLanes), 0, st, A);

@@ -12,7 +12,7 @@
 //   3. u = rintf(q_x / q_z * fx + cx),  v = rintf(q_y / q_z * fy + cy)        (a division, a product, a sum; round half to even)
 //      skip unless 0 <= u <= w - 1 and 0 <= v <= h - 1 (compared as floats: a NaN skips)
 //   4. D = depth[v, u], for uint16 counts (float)((double)raw * depth_scale);  skip unless D > 0 and D is finite
-//   5. d = D - q_z;  the pixel is the object's iff seg[v / f, u / f, channel] == value  (f = h / hs, as depth_frame.hip)
+//   5. d = D - q_z;  the pixel is the object's iff seg[v / f, u / f, channel] == value  (f = h / hs: frame_device.h)
 //        object:      skip if d < -trunc;  s = fminf(d, trunc), g = 1
 //        otherwise:   skip unless d > trunc;  s = trunc, g = carve_weight  (hand, background: free space only)
 //      skip if g == 0  (carve_weight = 0: nothing is carved, and no 0 / 0 where the weight is 0 too)
@@ -31,10 +31,8 @@
 // pn2s_tsdf_integrate_batch is the same rule (the one __device__ function below, called by both kernels) for the S volumes of a
 // group of sequences tracked in lockstep, in ONE launch: sequence k integrates its slice of the group's packed frame arrays into
 // its own volume, with the bits pn2s_tsdf_integrate gives for those frames alone.
-#include <hip/hip_fp16.h>
-#include <cmath>
-
-#include "pn2_common.h"
+#include "frame_device.h"
+#include "sdf_device.h"
 #include "../../include/pn2_sdf.h"
 
 namespace pn2 {
@@ -46,26 +44,12 @@ struct Args {
     void *volume;
     float *weight;
     const void *depth;
-    const unsigned char *seg;
     const float *intrinsics, *rotation, *translation;
     double depth_scale;
     float voxel_scale, trunc, carve_weight, max_weight;
-    int res, frames, h, w, ws, hs, c, f, fshift, flip, channel, value;
+    int res, frames, h, w, flip;
+    SegMap object;
 };
-
-__device__ __forceinline__ float decode(float raw, double) { return raw; }
-__device__ __forceinline__ float decode(unsigned short raw, double scale) { return (float)((double)raw * scale); }
-
-template <bool F16>
-__device__ __forceinline__ float ld_vol(const void *vol, int i) {
-    if (F16) return __half2float(reinterpret_cast<const __half *>(vol)[i]);
-    return reinterpret_cast<const float *>(vol)[i];
-}
-template <bool F16>
-__device__ __forceinline__ void st_vol(void *vol, int i, float x) {
-    if (F16) reinterpret_cast<__half *>(vol)[i] = __float2half_rn(x);
-    else reinterpret_cast<float *>(vol)[i] = x;
-}
 
 // The rule, once, for both launches: this lane's kZ voxels (ix, iy, z0 .. z0 + kZ - 1) of `volume` / `weight` over the frames
 // [f0, f1) of A's frame arrays.  iy < res (the caller's duty; z is masked here).
@@ -86,7 +70,7 @@ __device__ __forceinline__ void integrate_voxels(const Args &A, void *volume, fl
         }
     }
     const float px = (float)(ix - half) * A.voxel_scale, py = (float)(iy - half) * A.voxel_scale;
-    const size_t hw = (size_t)A.h * A.w, seg_frame = (size_t)A.hs * A.ws * A.c;
+    const size_t hw = (size_t)A.h * A.w;
     const float umax = (float)(A.w - 1), vmax = (float)(A.h - 1);
     for (int fr = f0; fr < f1; ++fr) {
         const float *R = A.rotation + 9 * fr, *t = A.translation + 3 * fr, *K = A.intrinsics + 4 * fr;
@@ -121,15 +105,14 @@ __device__ __forceinline__ void integrate_voxels(const Args &A, void *volume, fl
         inside &= front;
         if (!__any(inside != 0)) continue;  // the whole wave outside the image
         const D *depth = static_cast<const D *>(A.depth) + (size_t)fr * hw;
-        const unsigned char *seg = A.seg + (size_t)fr * seg_frame;
+        const unsigned char *seg = A.object.frame(fr);
 #pragma unroll
         for (int j = 0; j < kZ; ++j) {
             if (!((inside >> j) & 1u)) continue;
             const int u = (int)uf[j], v = (int)vf[j];  // inside [0, w - 1] x [0, h - 1]
             const float Dz = decode(depth[(size_t)v * A.w + u], A.depth_scale);
             if (!(Dz > 0.f) || Dz == __builtin_inff()) continue;
-            const int us = A.fshift >= 0 ? u >> A.fshift : u / A.f, vs = A.fshift >= 0 ? v >> A.fshift : v / A.f;
-            const bool obj = seg[((size_t)vs * A.ws + us) * A.c + A.channel] == A.value;
+            const bool obj = A.object.is_class(seg, v, u);
             const float d = Dz - qz[j];
             float s, g;
             if (obj) {
@@ -197,23 +180,19 @@ using namespace pn2::tsdf;
 static_assert(sizeof(pn2s_tsdf_frames) == 128, "record layout (pn2_sdf.h)");
 static_assert(sizeof(pn2s_tsdf_group) == 144, "record layout (pn2_sdf.h)");
 
-static inline bool finite_positive(float x) { return std::isfinite(x) && x > 0.f; }
-
-// The checks both records share (their fields carry the same names), in the single entry's order: PN2_EINVAL, then PN2_ERANGE.
-// `frames` is the record's frame count, at least `frames_min`.
+// The checks both records share (their fields carry the same names): PN2_EINVAL before PN2_ERANGE; the observed frames' own
+// are frame_device.h's.  `frames` is the record's frame count, at least `frames_min`.
 template <typename R>
 static int check_record(const R &r, int frames_min) {
-    const bool sizes = r.h >= 1 && r.w >= 1 && r.hs >= 1 && r.ws >= 1;
-    bool inval = r.res < 2 || r.frames < frames_min || !sizes || (r.vol_f16 != 0 && r.vol_f16 != 1) ||
-                 (r.depth_u16 != 0 && r.depth_u16 != 1) || (r.flip_yz != 0 && r.flip_yz != 1) || (r.c != 1 && r.c != 3);
-    inval |= !finite_positive(r.voxel_scale) || !finite_positive(r.trunc) || !finite_positive(r.max_weight) ||
-             !(std::isfinite(r.carve_weight) && r.carve_weight >= 0.f);
-    inval |= sizes && (r.h % r.hs != 0 || r.w % r.ws != 0 || r.h / r.hs != r.w / r.ws);
-    inval |= r.channel < 0 || r.channel >= r.c || r.value < 0 || r.value > 255;
-    inval |= r.depth_u16 == 1 && !(std::isfinite(r.depth_scale) && r.depth_scale > 0.0);
-    if (inval) return PN2_EINVAL;
-    if (r.res > kMaxRes || (long)r.h * r.w >= (1L << 29) || r.frames > 65535) return PN2_ERANGE;
-    return PN2_OK;
+    Faults f;
+    f.inval = r.res < 2 || r.frames < frames_min || (r.vol_f16 != 0 && r.vol_f16 != 1) || (r.flip_yz != 0 && r.flip_yz != 1) ||
+              !finite_positive(r.voxel_scale) || !finite_positive(r.trunc) || !finite_positive(r.max_weight) ||
+              !(std::isfinite(r.carve_weight) && r.carve_weight >= 0.f);
+    f.range = r.res > kMaxRes;
+    check_image_pair(r.frames, r.h, r.w, r.hs, r.ws, r.c, f);
+    check_class(r.channel, r.value, r.c, f);
+    check_depth_encoding(r.depth_u16, r.depth_scale, f);
+    return f.code();
 }
 
 // The kernels' view of a checked record (volume, weight and frames are the single entry's own).
@@ -221,14 +200,10 @@ template <typename R>
 static Args frame_args(const R &r) {
     Args A;
     A.volume = nullptr; A.weight = nullptr; A.frames = 0;
-    A.depth = r.depth; A.seg = r.seg; A.intrinsics = r.intrinsics;
+    A.depth = r.depth; A.object = seg_map(r.seg, r.h, r.hs, r.ws, r.c, r.channel, r.value); A.intrinsics = r.intrinsics;
     A.rotation = r.rotation; A.translation = r.translation; A.depth_scale = r.depth_scale;
     A.voxel_scale = r.voxel_scale; A.trunc = r.trunc; A.carve_weight = r.carve_weight; A.max_weight = r.max_weight;
-    A.res = r.res; A.h = r.h; A.w = r.w; A.ws = r.ws; A.hs = r.hs; A.c = r.c; A.f = r.h / r.hs;
-    A.fshift = -1;
-    for (int s = 0; s < 30; ++s)
-        if (A.f == (1 << s)) A.fshift = s;
-    A.flip = r.flip_yz; A.channel = r.channel; A.value = r.value;
+    A.res = r.res; A.h = r.h; A.w = r.w; A.flip = r.flip_yz;
     return A;
 }
 

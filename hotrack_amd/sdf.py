@@ -419,6 +419,90 @@ def volume_mesh(sdf_volume: torch.Tensor, voxel_scale: float, level: float = 0.0
     return verts, faces
 
 
+# ---- the argument checks the frame entries share; `who` is the caller's name, the prefix of every message -----------------------
+_FRAMES = ("depth", "seg", "intrinsics", "rotation", "translation")   # the per-frame arrays, as the records and the messages name them
+_TSDF_TENSORS, _RAYCAST_TENSORS = ("volume", "weight") + _FRAMES, ("volume",) + _FRAMES[2:]
+_VOLUME_DTYPES, _RAW_DTYPES, _INF = (torch.float16, torch.float32), (torch.uint16, torch.int16), float("inf")
+
+
+def _contiguous_tensors(who, names, tensors):
+    for name, t in zip(names, tensors):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{who}: {name} must be a torch.Tensor, got {type(t).__name__}")
+        if not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be contiguous")
+
+
+def _on_one_gpu(who, module, device, names, tensors):
+    for i, t in enumerate(tensors):
+        if not t.is_cuda or t.device != device:   # (names may be a function: a long list is then named only to say which one)
+            name = (names() if callable(names) else names)[i]
+            if not t.is_cuda:
+                raise RuntimeError(f"{who}: {name} must be a GPU (HIP) tensor -- hotrack_amd has no CPU path (got device {t.device}); "
+                                   f"network/models/{module}.{who}_torch runs anywhere")
+            raise ValueError(f"{who}: tensors on {device} and {t.device}")
+
+
+def _cubic_volume(who, volume, max_res, layout=""):
+    """A (res,res,res) fp16 / fp32 volume in the linear layout with 2 <= res <= max_res -> res."""
+    if volume.dtype not in _VOLUME_DTYPES:
+        raise TypeError(f"{who}: the volume must be float16 or float32, got {volume.dtype}")
+    shape = volume.shape
+    if len(shape) != 3 or not shape[0] == shape[1] == shape[2]:
+        raise ValueError(f"{who}: the volume must be (res,res,res){layout}, got {tuple(shape)}")
+    res = shape[0]
+    if not 2 <= res <= max_res:
+        raise ValueError(f"{who}: res must lie in [2, {max_res}], got {res}")
+    return res
+
+
+def _observed_frames(who, depth, seg, obj_class, depth_scale, rendered=None):
+    """The observed frames as hotrack_amd/csrc/frame_device.h defines them (the depth encoding, the depth / segment image pair, the
+    class), and a rendered image of their size if one is given -> (F, H, W, Hs, Ws, C, f, depth is raw counts)."""
+    if depth.dim() != 3 or depth.shape[0] < 1:
+        raise ValueError(f"{who}: depth must be (F,H,W) with F >= 1, got {tuple(depth.shape)}")
+    F, H, W = depth.shape
+    if rendered is not None and (rendered.dtype != _f32 or rendered.shape != depth.shape):
+        raise ValueError(f"{who}: rendered must be float32 {tuple(depth.shape)}, got {rendered.dtype} {tuple(rendered.shape)}")
+    raw = depth.dtype in _RAW_DTYPES   # (int16: the same 16 bits, for a torch without uint16 arithmetic)
+    if raw == (depth_scale is None) or (not raw and depth.dtype != _f32):
+        raise TypeError(f"{who}: depth is fp32 metres, or uint16 counts with a depth_scale (got {depth.dtype}, "
+                        f"depth_scale = {depth_scale})")
+    if raw and not 0 < float(depth_scale) < _INF:
+        raise ValueError(f"{who}: depth_scale must be finite and > 0, got {depth_scale}")
+    if seg.dtype != torch.uint8 or seg.dim() != 4 or seg.shape[0] != F:
+        raise ValueError(f"{who}: seg must be uint8 (F,Hs,Ws,C) with F = {F}, got {seg.dtype} {tuple(seg.shape)}")
+    _, Hs, Ws, C = seg.shape
+    if min(H, W, Hs, Ws) < 1 or H % Hs or W % Ws or H // Hs != W // Ws or C not in (1, 3) or H * W >= 1 << 29 or F > 65535:
+        raise ValueError(f"{who}: depth {H} x {W}, seg {Hs} x {Ws} x {C}: one integer factor between the two images, "
+                         "C 1 or 3, H W < 2^29, at most 65535 frames")
+    channel, value = int(obj_class[0]), int(obj_class[1])
+    if not (0 <= channel < C and 0 <= value <= 255):
+        raise ValueError(f"{who}: obj_class = (channel, value) with channel in [0, {C}) and value in [0, 255], got {tuple(obj_class)}")
+    return F, H, W, Hs, Ws, C, H // Hs, raw
+
+
+def _pose_frames(who, F, intrinsics, rotation, translation):
+    for name, t, shape in (("intrinsics", intrinsics, (F, 4)), ("rotation", rotation, (F, 3, 3)), ("translation", translation, (F, 3))):
+        if t.dtype != _f32 or t.shape != shape:
+            raise ValueError(f"{who}: {name} must be float32 {shape}, got {t.dtype} {tuple(t.shape)}")
+
+
+def _finite_positive(who, names, values):
+    for name, x in zip(names, values):
+        if not 0 < float(x) < _INF:
+            raise ValueError(f"{who}: {name} must be finite and > 0, got {x}")
+
+
+def _frame_pointers(r, F, depth, seg, sizes, poses):
+    """Fills the record's per-frame pointers: depth and seg (sizes = (H W, Hs Ws C) elements a frame) and poses = (K, R, t), each unless None."""
+    if depth is not None:
+        r.depth, r.seg = _native._ptr(depth, "depth", depth.dtype, F * sizes[0]), _native._ptr(seg, "seg", torch.uint8, F * sizes[1])
+    if poses is not None:
+        r.intrinsics = _native._ptr(poses[0], "intrinsics", _f32, F * 4)
+        r.rotation, r.translation = _native._ptr(poses[1], "rotation", _f32, F * 9), _native._ptr(poses[2], "translation", _f32, F * 3)
+
+
 # ---- depth frames fused into a signed distance volume (hotrack_amd/csrc/tsdf_fuse.hip) ------------------------------------------
 class _TsdfFrames(ctypes.Structure):
     """pn2s_tsdf_frames (128 bytes)."""
@@ -438,49 +522,17 @@ def tsdf_check(volume, weight, voxel_scale, depth, seg, intrinsics, rotation, tr
     """The argument checks of tsdf_integrate, which mirror pn2s_tsdf_integrate's (include/pn2_sdf.h) and raise; shared with the
     torch route (network/models/shape_fusion.py), so both refuse the same calls.  Devices are not looked at here.
     -> (res, F, H, W, Hs, Ws, C, f, depth is raw counts)."""
-    for name, t in (("volume", volume), ("weight", weight), ("depth", depth), ("seg", seg), ("intrinsics", intrinsics),
-                    ("rotation", rotation), ("translation", translation)):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"tsdf_integrate: {name} must be a torch.Tensor, got {type(t).__name__}")
-        if not t.is_contiguous():
-            raise ValueError(f"tsdf_integrate: {name} must be contiguous")
-    if volume.dtype not in (torch.float16, torch.float32):
-        raise TypeError(f"tsdf_integrate: the volume must be float16 or float32, got {volume.dtype}")
-    if volume.dim() != 3 or len(set(volume.shape)) != 1:
-        raise ValueError(f"tsdf_integrate: the volume must be (res,res,res), got {tuple(volume.shape)}")
-    res = volume.shape[0]
-    if not 2 <= res <= TSDF_MAX_RES:
-        raise ValueError(f"tsdf_integrate: res must lie in [2, {TSDF_MAX_RES}], got {res}")
+    who = "tsdf_integrate"
+    _contiguous_tensors(who, _TSDF_TENSORS, (volume, weight, depth, seg, intrinsics, rotation, translation))
+    res = _cubic_volume(who, volume, TSDF_MAX_RES)
     if weight.dtype != _f32 or weight.shape != volume.shape:
         raise ValueError(f"tsdf_integrate: weight must be float32 {tuple(volume.shape)}, got {weight.dtype} {tuple(weight.shape)}")
-    if depth.dim() != 3 or depth.shape[0] < 1:
-        raise ValueError(f"tsdf_integrate: depth must be (F,H,W) with F >= 1, got {tuple(depth.shape)}")
-    F, H, W = depth.shape
-    raw = depth.dtype in (torch.uint16, torch.int16)   # (int16: the same 16 bits, for a torch without uint16 arithmetic)
-    if raw == (depth_scale is None) or (not raw and depth.dtype != _f32):
-        raise TypeError(f"tsdf_integrate: depth is fp32 metres, or uint16 counts with a depth_scale (got {depth.dtype}, "
-                        f"depth_scale = {depth_scale})")
-    if raw and not 0 < float(depth_scale) < float("inf"):
-        raise ValueError(f"tsdf_integrate: depth_scale must be finite and > 0, got {depth_scale}")
-    if seg.dtype != torch.uint8 or seg.dim() != 4 or seg.shape[0] != F:
-        raise ValueError(f"tsdf_integrate: seg must be uint8 (F,Hs,Ws,C) with F = {F}, got {seg.dtype} {tuple(seg.shape)}")
-    _, Hs, Ws, C = seg.shape
-    if min(H, W, Hs, Ws) < 1 or H % Hs or W % Ws or H // Hs != W // Ws or C not in (1, 3) or H * W >= 1 << 29 or F > 65535:
-        raise ValueError(f"tsdf_integrate: depth {H} x {W}, seg {Hs} x {Ws} x {C}: one integer factor between the two images, "
-                         "C 1 or 3, H W < 2^29, at most 65535 frames")
-    channel, value = int(obj_class[0]), int(obj_class[1])
-    if not (0 <= channel < C and 0 <= value <= 255):
-        raise ValueError(f"tsdf_integrate: obj_class = (channel, value) with channel in [0, {C}) and value in [0, 255], got {tuple(obj_class)}")
-    for name, t, shape in (("intrinsics", intrinsics, (F, 4)), ("rotation", rotation, (F, 3, 3)), ("translation", translation, (F, 3))):
-        if t.dtype != _f32 or tuple(t.shape) != shape:
-            raise ValueError(f"tsdf_integrate: {name} must be float32 {shape}, got {t.dtype} {tuple(t.shape)}")
-    inf = float("inf")
-    for name, x in (("trunc", trunc), ("voxel_scale", voxel_scale), ("max_weight", max_weight)):
-        if not 0 < float(x) < inf:
-            raise ValueError(f"tsdf_integrate: {name} must be finite and > 0, got {x}")
-    if not 0 <= float(carve_weight) < inf:
+    frames = _observed_frames(who, depth, seg, obj_class, depth_scale)
+    _pose_frames(who, frames[0], intrinsics, rotation, translation)
+    _finite_positive(who, ("trunc", "voxel_scale", "max_weight"), (trunc, voxel_scale, max_weight))
+    if not 0 <= float(carve_weight) < _INF:
         raise ValueError(f"tsdf_integrate: carve_weight must be finite and >= 0, got {carve_weight}")
-    return res, F, H, W, Hs, Ws, C, H // Hs, raw
+    return (res,) + frames
 
 
 def tsdf_integrate(volume: torch.Tensor, weight: torch.Tensor, voxel_scale: float, depth: torch.Tensor, seg: torch.Tensor,
@@ -496,21 +548,13 @@ def tsdf_integrate(volume: torch.Tensor, weight: torch.Tensor, voxel_scale: floa
     All tensors contiguous on one GPU.  Runs on the current stream, no host sync.  -> (volume, weight), the same tensors."""
     res, F, H, W, Hs, Ws, C, _, raw = tsdf_check(volume, weight, voxel_scale, depth, seg, intrinsics, rotation, translation, trunc,
                                                  obj_class, depth_scale, carve_weight, max_weight)
-    for name, t in (("volume", volume), ("weight", weight), ("depth", depth), ("seg", seg), ("intrinsics", intrinsics),
-                    ("rotation", rotation), ("translation", translation)):
-        if not t.is_cuda:
-            raise RuntimeError(f"tsdf_integrate: {name} must be a GPU (HIP) tensor -- hotrack_amd has no CPU path (got device {t.device}); "
-                               "network/models/shape_fusion.tsdf_integrate_torch runs anywhere")
-        if t.device != volume.device:
-            raise ValueError(f"tsdf_integrate: tensors on {volume.device} and {t.device}")
+    _on_one_gpu("tsdf_integrate", "shape_fusion", volume.device, _TSDF_TENSORS, (volume, weight, depth, seg, intrinsics, rotation, translation))
     r = _TsdfFrames(res=res, vol_f16=int(volume.dtype == torch.float16), frames=F, h=H, w=W, hs=Hs, ws=Ws, c=C, depth_u16=int(raw),
                     flip_yz=int(bool(flip_yz)), channel=int(obj_class[0]), value=int(obj_class[1]),
                     depth_scale=0.0 if depth_scale is None else float(depth_scale), voxel_scale=float(voxel_scale), trunc=float(trunc),
                     carve_weight=float(carve_weight), max_weight=float(max_weight))
     r.volume, r.weight = _native._ptr(volume, "volume", volume.dtype, res ** 3), _native._ptr(weight, "weight", _f32, res ** 3)
-    r.depth, r.seg = _native._ptr(depth, "depth", depth.dtype, F * H * W), _native._ptr(seg, "seg", torch.uint8, F * Hs * Ws * C)
-    r.intrinsics = _native._ptr(intrinsics, "intrinsics", _f32, F * 4)
-    r.rotation, r.translation = _native._ptr(rotation, "rotation", _f32, F * 9), _native._ptr(translation, "translation", _f32, F * 3)
+    _frame_pointers(r, F, depth, seg, (H * W, Hs * Ws * C), (intrinsics, rotation, translation))
     with torch.cuda.device(volume.device):
         rc = _lib.pn2s_tsdf_integrate(ctypes.byref(r), _native._stream(volume))
     _native._check(rc, "sdf.tsdf_integrate")
@@ -603,22 +647,14 @@ def tsdf_integrate_batch(volumes, weights, voxel_scale: float, depth: torch.Tens
                                    obj_class, depth_scale, carve_weight, max_weight)
     if not active:
         return volumes, weights
-    S, F = len(frame_counts), off[-1]
-    device = volumes[active[0]].device
-    named = [(f"volumes[{k}]", volumes[k]) for k in range(S) if volumes[k] is not None]
-    named += [(f"weights[{k}]", weights[k]) for k in range(S) if weights[k] is not None]
-    named += [("depth", depth), ("seg", seg), ("intrinsics", intrinsics), ("rotation", rotation), ("translation", translation)]
-    for name, t in named:
-        if not t.is_cuda:
-            raise RuntimeError(f"tsdf_integrate_batch: {name} must be a GPU (HIP) tensor -- hotrack_amd has no CPU path (got device "
-                               f"{t.device}); network/models/shape_fusion.tsdf_integrate_batch_torch runs anywhere")
-        if t.device != device:
-            raise ValueError(f"tsdf_integrate_batch: tensors on {device} and {t.device}")
-    v0 = volumes[active[0]]
-    res = v0.shape[0]
+    S, F, v0 = len(frame_counts), off[-1], volumes[active[0]]
+    device, res = v0.device, v0.shape[0]
+    given = [k for k in range(S) if volumes[k] is not None]
+    _on_one_gpu("tsdf_integrate_batch", "shape_fusion", device, lambda: [f"{n}[{k}]" for n in ("volumes", "weights") for k in given] + list(_FRAMES),
+                [volumes[k] for k in given] + [weights[k] for k in given] + [depth, seg, intrinsics, rotation, translation])
     _, H, W = depth.shape
     _, Hs, Ws, C = seg.shape
-    raw = depth.dtype in (torch.uint16, torch.int16)
+    raw = depth.dtype in _RAW_DTYPES
     # one table: S volume pointers, S weight pointers, then the S + 1 offsets as int32 (a sitting-out sequence's tensors are not
     # checked beyond res and dtype, and never read: its entries stay NULL)
     key = ("tsdf", str(device), tuple(None if volumes[k] is None else (id(volumes[k]), id(weights[k])) for k in range(S)),
@@ -640,9 +676,7 @@ def tsdf_integrate_batch(volumes, weights, voxel_scale: float, depth: torch.Tens
                    depth_scale=0.0 if depth_scale is None else float(depth_scale), voxel_scale=float(voxel_scale), trunc=float(trunc),
                    carve_weight=float(carve_weight), max_weight=float(max_weight))
     r.volumes, r.weights, r.frame_off = table.data_ptr(), table.data_ptr() + 8 * S, table.data_ptr() + 16 * S
-    r.depth, r.seg = _native._ptr(depth, "depth", depth.dtype, F * H * W), _native._ptr(seg, "seg", torch.uint8, F * Hs * Ws * C)
-    r.intrinsics = _native._ptr(intrinsics, "intrinsics", _f32, F * 4)
-    r.rotation, r.translation = _native._ptr(rotation, "rotation", _f32, F * 9), _native._ptr(translation, "translation", _f32, F * 3)
+    _frame_pointers(r, F, depth, seg, (H * W, Hs * Ws * C), (intrinsics, rotation, translation))
     with torch.cuda.device(device):
         rc = _lib.pn2s_tsdf_integrate_batch(ctypes.byref(r), _native._stream(v0))
     _native._check(rc, "sdf.tsdf_integrate_batch")
@@ -679,31 +713,17 @@ def raycast_check(volume, voxel_scale, intrinsics, rotation, translation, hw, st
     """The argument checks of volume_raycast, which mirror pn2s_volume_raycast's (include/pn2_sdf.h) and raise; shared with the torch
     route (network/models/volume_render.py), so both refuse the same calls.  Devices are not looked at here.
     -> (res, F, H, W, max_steps) with max_steps = 8 * res when None was given."""
-    for name, t in (("volume", volume), ("intrinsics", intrinsics), ("rotation", rotation), ("translation", translation)):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"volume_raycast: {name} must be a torch.Tensor, got {type(t).__name__}")
-        if not t.is_contiguous():
-            raise ValueError(f"volume_raycast: {name} must be contiguous")
-    if volume.dtype not in (torch.float16, torch.float32):
-        raise TypeError(f"volume_raycast: the volume must be float16 or float32, got {volume.dtype}")
-    if volume.dim() != 3 or len(set(volume.shape)) != 1:
-        raise ValueError(f"volume_raycast: the volume must be (res,res,res) in the linear layout, got {tuple(volume.shape)}")
-    res = volume.shape[0]
-    if not 2 <= res <= RAYCAST_MAX_RES:
-        raise ValueError(f"volume_raycast: res must lie in [2, {RAYCAST_MAX_RES}], got {res}")
+    who = "volume_raycast"
+    _contiguous_tensors(who, _RAYCAST_TENSORS, (volume, intrinsics, rotation, translation))
+    res = _cubic_volume(who, volume, RAYCAST_MAX_RES, " in the linear layout")
     if intrinsics.dim() != 2 or intrinsics.shape[0] < 1:
         raise ValueError(f"volume_raycast: intrinsics must be (F,4) with F >= 1, got {tuple(intrinsics.shape)}")
     F = intrinsics.shape[0]
-    for name, t, shape in (("intrinsics", intrinsics, (F, 4)), ("rotation", rotation, (F, 3, 3)), ("translation", translation, (F, 3))):
-        if t.dtype != _f32 or tuple(t.shape) != shape:
-            raise ValueError(f"volume_raycast: {name} must be float32 {shape}, got {t.dtype} {tuple(t.shape)}")
+    _pose_frames(who, F, intrinsics, rotation, translation)
     H, W = int(hw[0]), int(hw[1])
     if H < 1 or W < 1 or H * W >= 1 << 29 or H > 8 * 65535 or F > 65535:
         raise ValueError(f"volume_raycast: an image of {H} x {W}, {F} frames: sizes >= 1, H W < 2^29, H <= 8 * 65535, at most 65535 frames")
-    inf = float("inf")
-    for name, x in (("voxel_scale", voxel_scale), ("step_scale", step_scale), ("min_step", min_step)):
-        if not 0 < float(x) < inf:
-            raise ValueError(f"volume_raycast: {name} must be finite and > 0, got {x}")
+    _finite_positive(who, ("voxel_scale", "step_scale", "min_step"), (voxel_scale, step_scale, min_step))
     if int(refine) != refine or not 0 <= int(refine) <= 16:
         raise ValueError(f"volume_raycast: refine must be an integer in [0, 16], got {refine}")
     max_steps = 8 * res if max_steps is None else max_steps
@@ -724,19 +744,13 @@ def volume_raycast(volume: torch.Tensor, voxel_scale: float, intrinsics: torch.T
     -> (depth (F,H,W) float32, 0 = no hit;  normal (F,H,W,3) float32 unit vectors in the camera frame, or None with normals=False)."""
     res, F, H, W, max_steps = raycast_check(volume, voxel_scale, intrinsics, rotation, translation, hw, step_scale, min_step, refine,
                                             max_steps)
-    for name, t in (("volume", volume), ("intrinsics", intrinsics), ("rotation", rotation), ("translation", translation)):
-        if not t.is_cuda:
-            raise RuntimeError(f"volume_raycast: {name} must be a GPU (HIP) tensor -- hotrack_amd has no CPU path (got device {t.device}); "
-                               "network/models/volume_render.volume_raycast_torch runs anywhere")
-        if t.device != volume.device:
-            raise ValueError(f"volume_raycast: tensors on {volume.device} and {t.device}")
+    _on_one_gpu("volume_raycast", "volume_render", volume.device, _RAYCAST_TENSORS, (volume, intrinsics, rotation, translation))
     depth = torch.empty((F, H, W), dtype=_f32, device=volume.device)
     normal = torch.empty((F, H, W, 3), dtype=_f32, device=volume.device) if normals else None
     r = _Raycast(res=res, vol_f16=int(volume.dtype == torch.float16), frames=F, h=H, w=W, flip_yz=int(bool(flip_yz)), refine=int(refine),
                  max_steps=max_steps, voxel_scale=float(voxel_scale), step_scale=float(step_scale), min_step=float(min_step))
     r.volume = _native._ptr(volume, "volume", volume.dtype, res ** 3)
-    r.intrinsics = _native._ptr(intrinsics, "intrinsics", _f32, F * 4)
-    r.rotation, r.translation = _native._ptr(rotation, "rotation", _f32, F * 9), _native._ptr(translation, "translation", _f32, F * 3)
+    _frame_pointers(r, F, None, None, None, (intrinsics, rotation, translation))
     r.depth, r.normal = depth.data_ptr(), None if normal is None else normal.data_ptr()
     with torch.cuda.device(volume.device):
         rc = _lib.pn2s_volume_raycast(ctypes.byref(r), _native._stream(volume))
@@ -747,34 +761,11 @@ def volume_raycast(volume: torch.Tensor, voxel_scale: float, intrinsics: torch.T
 def raycast_compare_check(rendered, depth, seg, obj_class, depth_scale, occl_margin):
     """The argument checks of raycast_compare (pn2s_raycast_compare's, raised), shared with the torch route.
     -> (F, H, W, Hs, Ws, C, f, depth is raw counts)."""
-    for name, t in (("rendered", rendered), ("depth", depth), ("seg", seg)):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"raycast_compare: {name} must be a torch.Tensor, got {type(t).__name__}")
-        if not t.is_contiguous():
-            raise ValueError(f"raycast_compare: {name} must be contiguous")
-    if depth.dim() != 3 or depth.shape[0] < 1:
-        raise ValueError(f"raycast_compare: depth must be (F,H,W) with F >= 1, got {tuple(depth.shape)}")
-    F, H, W = depth.shape
-    if rendered.dtype != _f32 or rendered.shape != depth.shape:
-        raise ValueError(f"raycast_compare: rendered must be float32 {tuple(depth.shape)}, got {rendered.dtype} {tuple(rendered.shape)}")
-    raw = depth.dtype in (torch.uint16, torch.int16)   # (int16: the same 16 bits, as tsdf_integrate)
-    if raw == (depth_scale is None) or (not raw and depth.dtype != _f32):
-        raise TypeError(f"raycast_compare: depth is fp32 metres, or uint16 counts with a depth_scale (got {depth.dtype}, "
-                        f"depth_scale = {depth_scale})")
-    if raw and not 0 < float(depth_scale) < float("inf"):
-        raise ValueError(f"raycast_compare: depth_scale must be finite and > 0, got {depth_scale}")
-    if seg.dtype != torch.uint8 or seg.dim() != 4 or seg.shape[0] != F:
-        raise ValueError(f"raycast_compare: seg must be uint8 (F,Hs,Ws,C) with F = {F}, got {seg.dtype} {tuple(seg.shape)}")
-    _, Hs, Ws, C = seg.shape
-    if min(H, W, Hs, Ws) < 1 or H % Hs or W % Ws or H // Hs != W // Ws or C not in (1, 3) or H * W >= 1 << 29 or F > 65535:
-        raise ValueError(f"raycast_compare: depth {H} x {W}, seg {Hs} x {Ws} x {C}: one integer factor between the two images, "
-                         "C 1 or 3, H W < 2^29, at most 65535 frames")
-    channel, value = int(obj_class[0]), int(obj_class[1])
-    if not (0 <= channel < C and 0 <= value <= 255):
-        raise ValueError(f"raycast_compare: obj_class = (channel, value) with channel in [0, {C}) and value in [0, 255], got {tuple(obj_class)}")
-    if not 0 <= float(occl_margin) < float("inf"):
+    _contiguous_tensors("raycast_compare", ("rendered", "depth", "seg"), (rendered, depth, seg))
+    frames = _observed_frames("raycast_compare", depth, seg, obj_class, depth_scale, rendered)
+    if not 0 <= float(occl_margin) < _INF:
         raise ValueError(f"raycast_compare: occl_margin must be finite and >= 0, got {occl_margin}")
-    return F, H, W, Hs, Ws, C, H // Hs, raw
+    return frames
 
 
 def raycast_compare(rendered: torch.Tensor, depth: torch.Tensor, seg: torch.Tensor, obj_class=(1, 255), depth_scale: float = None,
@@ -784,18 +775,12 @@ def raycast_compare(rendered: torch.Tensor, depth: torch.Tensor, seg: torch.Tens
     -> (F,4) float32: |A n B|, |A u B|, the sum over A n B of |D - Z| and |Occ|, with A the object's pixels with valid depth, Occ the
     other valid pixels more than occl_margin in front of a model hit, B the model's hits outside Occ.  No host sync."""
     F, H, W, Hs, Ws, C, _, raw = raycast_compare_check(rendered, depth, seg, obj_class, depth_scale, occl_margin)
-    for name, t in (("rendered", rendered), ("depth", depth), ("seg", seg)):
-        if not t.is_cuda:
-            raise RuntimeError(f"raycast_compare: {name} must be a GPU (HIP) tensor -- hotrack_amd has no CPU path (got device {t.device}); "
-                               "network/models/volume_render.raycast_compare_torch runs anywhere")
-        if t.device != rendered.device:
-            raise ValueError(f"raycast_compare: tensors on {rendered.device} and {t.device}")
+    _on_one_gpu("raycast_compare", "volume_render", rendered.device, ("rendered", "depth", "seg"), (rendered, depth, seg))
     out = torch.empty((F, 4), dtype=_f32, device=rendered.device)
     r = _RaycastFrames(frames=F, h=H, w=W, hs=Hs, ws=Ws, c=C, depth_u16=int(raw), channel=int(obj_class[0]), value=int(obj_class[1]),
                        depth_scale=0.0 if depth_scale is None else float(depth_scale), occl_margin=float(occl_margin))
-    r.rendered = _native._ptr(rendered, "rendered", _f32, F * H * W)
-    r.depth, r.seg = _native._ptr(depth, "depth", depth.dtype, F * H * W), _native._ptr(seg, "seg", torch.uint8, F * Hs * Ws * C)
-    r.out = out.data_ptr()
+    r.rendered, r.out = _native._ptr(rendered, "rendered", _f32, F * H * W), out.data_ptr()
+    _frame_pointers(r, F, depth, seg, (H * W, Hs * Ws * C), None)
     with torch.cuda.device(rendered.device):
         rc = _lib.pn2s_raycast_compare(ctypes.byref(r), _native._stream(rendered))
     _native._check(rc, "sdf.raycast_compare")

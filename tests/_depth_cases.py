@@ -195,3 +195,12 @@ def cases():
         # 48 x 64 uint16, not flipped, the segment at 24 x 32 x 1
         make_case("48x64_u16_seg24x32", 5, 1, 48, 64, 2, 1, [[_blob((24, 20), 12), _blob((24, 46), 5)]], u16=True),
     ]
+
+
+def factor_cases():
+    """The two ways a kernel finds a pixel's segment cell, which cases() does not tell apart (its factors are 1 and 2): two frames
+    of 12 x 12 depth, cap 64, three channels, over segments of 12 x 12 (f = 1), 3 x 3 (f = 4, a power of two: the shift) and 4 x 4
+    (f = 3: the division), each with fp32 and with uint16 depth.  Both classes have pixels in every frame."""
+    blobs = [[_blob((4, 4), 4), _blob((7, 8), 4)], [_blob((7, 5), 5), _blob((4, 8), 4)]]
+    return [make_case("12x12_f%d_%s" % (f, "u16" if u16 else "f32"), 20 + 2 * f + u16, 2, 12, 12, f, 3, blobs, flip_yz=bool(u16), u16=u16,
+                      cap=64) for f in (1, 4, 3) for u16 in (False, True)]

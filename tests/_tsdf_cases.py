@@ -66,6 +66,8 @@ CASES = [
     dict(name="res33_close_F3", res=33, scale=0.008, hw=(24, 32), vol="float32", depth="f32", f=1, c=3, flip=False, poses=["close", "front", "close2"], max_w=64.0, carve=0.5, prior_w=1.0),
     dict(name="res5_f16_u16_F3", res=5, scale=0.06, hw=(48, 64), vol="float16", depth="u16", f=1, c=3, flip=False, poses=["close", "side", "front"], max_w=64.0, carve=1.0, prior_w=0.0),
     dict(name="res17_u16_carve0", res=17, scale=0.016, hw=(24, 32), vol="float32", depth="u16", f=1, c=1, flip=False, poses=["close2"], max_w=64.0, carve=0.0, prior_w=1.0),
+    # a segment factor that is no power of two (the kernels divide where the factors 1 and 2 above shift: csrc/frame_device.h)
+    dict(name="res17_u16_seg3_F2", res=17, scale=0.016, hw=(24, 33), vol="float32", depth="u16", f=3, c=3, flip=False, poses=["front", "oblique"], max_w=64.0, carve=1.0, prior_w=1.0),
 ]
 DEPTH_SCALE = 0.001
 MAX_EXCLUDED = 0.02

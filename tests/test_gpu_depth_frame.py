@@ -58,6 +58,20 @@ def test_kernels_match_the_restatement(case):
     assert np.array_equal(_bits(clouds), want["clouds"].view(np.uint32))
 
 
+FACTOR_CASES = D.factor_cases()
+
+
+@pytest.mark.parametrize("case", FACTOR_CASES, ids=[c["name"] for c in FACTOR_CASES])
+def test_segment_cell_by_shift_and_by_division(case):
+    """f = 1 and 4 find a pixel's segment cell with a shift, f = 3 with a division (csrc/frame_device.h); CASES has only 1 and 2."""
+    want = _expected(case)
+    assert (want["counts"] > 0).all()
+    clouds, counts, background = _binding_call(case, _device_frames(case))
+    assert np.array_equal(counts.cpu().numpy(), want["counts"])
+    assert np.array_equal(background.cpu().numpy(), want["background"])
+    assert np.array_equal(_bits(clouds), want["clouds"].view(np.uint32))
+
+
 @pytest.mark.parametrize("case", CASES, ids=[c["name"] for c in CASES])
 def test_front_end_samples_and_gathers(case, oracle):
     want = _expected(case)

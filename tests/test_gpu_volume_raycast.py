@@ -80,7 +80,7 @@ def _observed(name):
     return a, z, depth, t(a["seg"])
 
 
-@pytest.mark.parametrize("name", ["res17_f16_flip_F3", "res33_u16_seg2_F3", "res33_f16_u16_flip"])
+@pytest.mark.parametrize("name", ["res17_f16_flip_F3", "res33_u16_seg2_F3", "res33_f16_u16_flip", "res17_u16_seg3_F2"])
 def test_compare_matches_the_torch_route(name):
     from hotrack_amd import sdf
     from models.volume_render import raycast_compare_torch
