@@ -22,6 +22,10 @@ int three_nn_interp_dispatch(int b, int n, int m, int c, const float *unknown, c
 bool three_nn_interp_rows_supported(long b, long n, long m, long c, long ldp, long ldo);
 int three_nn_interp_rows_dispatch(int b, int n, int m, int c, const float *unknown, const float *known, const float *points, int ldp,
                                   float *out, int ldo, const int *row_list, const int *row_counts, hipStream_t st);
+bool three_nn_interp_rows_act_supported(long b, long n, long m, long c, long ldp, long ldo);
+int three_nn_interp_rows_act_dispatch(int b, int n, int m, int c, const float *unknown, const float *known, const float *points, int ldp,
+                                      float *out, int ldo, const int *row_list, const int *row_counts, const float *wx,
+                                      const float *bias, int relu, hipStream_t st);
 int fps_knn_dispatch(int b, int n, int m, const float *xyz, int *idx, float *radii, int nq, int k, int k2, const float *query,
                      int *kidx, int *kidx2, hipStream_t st);
 int ball_query_dispatch(int b, int n, int m, float radius, int nsample, const float *new_xyz, const float *xyz,
@@ -289,6 +293,22 @@ int pn2x_three_nn_interpolate_pm_rows(int b, int n, int m, int c, const float *u
     PN2_REQ(unknown && known && points && out && row_list && row_counts, PN2_ENULL);
     PN2_REQ(b <= 65535 && fits_int((long)n * 3) && fits_int((long)m * 3), PN2_ERANGE);
     return three_nn_interp_rows_dispatch(b, n, m, c, unknown, known, points, ldp, out, ldo, row_list, row_counts, (hipStream_t)stream);
+}
+
+int pn2x_three_nn_interpolate_pm_rows_act_supported(int b, int n, int m, int c, int ldp, int ldo) {
+    return three_nn_interp_rows_act_supported(b, n, m, c, ldp, ldo) ? 1 : 0;
+}
+
+int pn2x_three_nn_interpolate_pm_rows_act(int b, int n, int m, int c, const float *unknown, const float *known, const float *points,
+                                          int ldp, float *out, int ldo, const int *row_list, const int *row_counts, const float *wx,
+                                          const float *bias, int relu, void *stream) {
+    PN2_REQ(b >= 0 && n >= 0 && m >= 3 && c >= 1 && ldp >= c && ldo >= c, PN2_EINVAL);
+    if (b == 0 || n == 0) return PN2_OK;
+    PN2_REQ(unknown && known && points && out && wx && bias, PN2_ENULL);
+    PN2_REQ((row_list == nullptr) == (row_counts == nullptr), PN2_ENULL);  // both: the listed rows; neither: every row
+    PN2_REQ(b <= 65535 && fits_int((long)n * 3) && fits_int((long)m * 3), PN2_ERANGE);
+    return three_nn_interp_rows_act_dispatch(b, n, m, c, unknown, known, points, ldp, out, ldo, row_list, row_counts, wx, bias, relu,
+                                             (hipStream_t)stream);
 }
 
 int pn2x_three_interpolate_pm(int b, int c, int m, int n, const float *points, int ldp, const int *idx,

@@ -150,17 +150,29 @@ three_nn_split_kernel(int n, int m, const float *__restrict__ unknown_all, const
 // ROWS: the queries of cloud b are the rows row_list[b, 0 : row_counts[b, 1]] (pn2x_row_lists) instead of all n -- workgroup x
 // takes the list entries [64 x, 64 x + 64) and leaves at once when the cloud's count (read on the device) ends before them; each
 // listed row gets the same search, weights and blend at its own place in `out`, no other row is written.
-template <bool ROWS>
-__global__ void __launch_bounds__(256)
-three_nn_interp_kernel(int n, int m, int c4, const float *__restrict__ unknown_all, const float *__restrict__ known_all,
-                       const float *__restrict__ points_all, int ldp, float *__restrict__ out_all, int ldo,
-                       const int *__restrict__ row_list, const int *__restrict__ row_counts) {
-    extern __shared__ __attribute__((aligned(16))) float4 sk[];
+// EPI: the blend is followed by out = act(blend + Wx q_xyz + bias) with Wx (c, 3), bias (c) and q_xyz the query point the row
+// belongs to -- what is left of a per-point layer [features | xyz] -> c once its feature half has been applied to `points` instead
+// of to the blended rows (the blend is a convex combination of rows, so it commutes with the product).  Order of the sum, per
+// channel: the blend in the order above; then fma(Wx[ch][0], x, .), fma(Wx[ch][1], y, .), fma(Wx[ch][2], z, .); then + bias[ch];
+// then max(., 0) when relu is set.  Wx (transposed to one float4 of four channels per coordinate) and bias are staged in LDS behind
+// the known points, so the blend loop adds four ds_read_b128 and no global load.
+struct InterpEpilogue {
+    const float *wx, *bias;
+    int relu;
+};
+
+template <bool ROWS, bool EPI>
+__device__ __forceinline__ void
+three_nn_interp_body(int n, int m, int c4, const float *__restrict__ unknown_all, const float *__restrict__ known_all,
+                     const float *__restrict__ points_all, int ldp, float *__restrict__ out_all, int ldo,
+                     const int *__restrict__ row_list, const int *__restrict__ row_counts, const InterpEpilogue ep) {
+    extern __shared__ __attribute__((aligned(16))) float4 sk[];  // [m] known points; EPI: then [3][c4] Wx columns, [c4] bias
     __shared__ float sd[3][3][64];
     __shared__ int si[3][3][64];
     __shared__ float fw[3][64];
     __shared__ int fi[3][64];
     __shared__ int fq[ROWS ? 64 : 1];  // ROWS: the query row of every entry, -1 = none
+    __shared__ float fx[EPI ? 3 : 1][EPI ? 64 : 4];  // EPI: the query point of every entry
     const int b = blockIdx.y;
     const float *__restrict__ known = known_all + (size_t)b * m * 3;
     const int ql = threadIdx.x & 63, c = threadIdx.x >> 6;  // c is wave-uniform
@@ -178,6 +190,17 @@ three_nn_interp_kernel(int n, int m, int c4, const float *__restrict__ unknown_a
     for (int p = threadIdx.x; p < m; p += 256) {
         const float *src = known + (size_t)3 * p;
         sk[p] = make_float4(src[0], src[1], src[2], 0.f);
+    }
+    float4 *swx = sk + m, *sb = swx + 3 * c4;
+    if constexpr (EPI) {
+        for (int i = threadIdx.x; i < c4; i += 256) {  // rows 4 i .. 4 i + 3 of Wx: 12 consecutive floats
+            const float4 *w = reinterpret_cast<const float4 *>(ep.wx) + 3 * i;
+            const float4 v0 = w[0], v1 = w[1], v2 = w[2], bv = reinterpret_cast<const float4 *>(ep.bias)[i];
+            swx[i] = make_float4(v0.x, v0.w, v1.z, v2.y);
+            swx[c4 + i] = make_float4(v0.y, v1.x, v1.w, v2.z);
+            swx[2 * c4 + i] = make_float4(v0.z, v1.y, v2.x, v2.w);
+            sb[i] = bv;
+        }
     }
     __syncthreads();
     float b1 = __builtin_inff(), b2 = __builtin_inff(), b3 = __builtin_inff();
@@ -213,6 +236,7 @@ three_nn_interp_kernel(int n, int m, int c4, const float *__restrict__ unknown_a
         fw[0][ql] = r1 / norm; fw[1][ql] = r2 / norm; fw[2][ql] = r3 / norm;
         fi[0][ql] = i1; fi[1][ql] = i2; fi[2][ql] = i3;
         if constexpr (ROWS) fq[ql] = q;
+        if constexpr (EPI) { fx[0][ql] = ux; fx[1][ql] = uy; fx[2][ql] = uz; }
     }
     __syncthreads();
     const int rows = min(64, nq - (int)blockIdx.x * 64);
@@ -229,12 +253,41 @@ three_nn_interp_kernel(int n, int m, int c4, const float *__restrict__ unknown_a
         o.y = __builtin_fmaf(w2, a2.y, __builtin_fmaf(w0, a0.y, w1 * a1.y));
         o.z = __builtin_fmaf(w2, a2.z, __builtin_fmaf(w0, a0.z, w1 * a1.z));
         o.w = __builtin_fmaf(w2, a2.w, __builtin_fmaf(w0, a0.w, w1 * a1.w));
+        if constexpr (EPI) {
+            const float x = fx[0][r], y = fx[1][r], z = fx[2][r];
+            const float4 cx = swx[col], cy = swx[c4 + col], cz = swx[2 * c4 + col], bv = sb[col];
+            o.x = __builtin_fmaf(cz.x, z, __builtin_fmaf(cy.x, y, __builtin_fmaf(cx.x, x, o.x))) + bv.x;
+            o.y = __builtin_fmaf(cz.y, z, __builtin_fmaf(cy.y, y, __builtin_fmaf(cx.y, x, o.y))) + bv.y;
+            o.z = __builtin_fmaf(cz.z, z, __builtin_fmaf(cy.z, y, __builtin_fmaf(cx.z, x, o.z))) + bv.z;
+            o.w = __builtin_fmaf(cz.w, z, __builtin_fmaf(cy.w, y, __builtin_fmaf(cx.w, x, o.w))) + bv.w;
+            const bool act = ep.relu != 0;  // a select, not a branch: without ReLU a NaN stays a NaN
+            o.x = act ? fmaxf(o.x, 0.f) : o.x; o.y = act ? fmaxf(o.y, 0.f) : o.y;
+            o.z = act ? fmaxf(o.z, 0.f) : o.z; o.w = act ? fmaxf(o.w, 0.f) : o.w;
+        }
         if constexpr (ROWS) {
             if (fq[r] >= 0) *reinterpret_cast<float4 *>(dst + (size_t)fq[r] * ldo + 4 * col) = o;
         } else {
             *reinterpret_cast<float4 *>(dst + (size_t)r * ldo + 4 * col) = o;
         }
     }
+}
+
+template <bool ROWS>
+__global__ void __launch_bounds__(256)
+three_nn_interp_kernel(int n, int m, int c4, const float *__restrict__ unknown_all, const float *__restrict__ known_all,
+                       const float *__restrict__ points_all, int ldp, float *__restrict__ out_all, int ldo,
+                       const int *__restrict__ row_list, const int *__restrict__ row_counts) {
+    three_nn_interp_body<ROWS, false>(n, m, c4, unknown_all, known_all, points_all, ldp, out_all, ldo, row_list, row_counts,
+                                      InterpEpilogue{nullptr, nullptr, 0});
+}
+
+// either form with the epilogue out = act(blend + Wx q_xyz + bias)
+template <bool ROWS>
+__global__ void __launch_bounds__(256)
+three_nn_interp_act_kernel(int n, int m, int c4, const float *__restrict__ unknown_all, const float *__restrict__ known_all,
+                           const float *__restrict__ points_all, int ldp, float *__restrict__ out_all, int ldo,
+                           const int *__restrict__ row_list, const int *__restrict__ row_counts, InterpEpilogue ep) {
+    three_nn_interp_body<ROWS, true>(n, m, c4, unknown_all, known_all, points_all, ldp, out_all, ldo, row_list, row_counts, ep);
 }
 
 // From 16384 queries up: below that the blend of a workgroup's 64 rows by its own four waves is a longer chain than the
@@ -266,6 +319,29 @@ int three_nn_interp_rows_dispatch(int b, int n, int m, int c, const float *unkno
     dim3 grid((n + 63) / 64, b);
     hipLaunchKernelGGL(three_nn_interp_kernel<true>, grid, dim3(256), (size_t)m * sizeof(float4), st, n, m, c / 4, unknown, known, points,
                        ldp, out, ldo, row_list, row_counts);
+    return check_launch();
+}
+
+// With the epilogue: Wx and the bias join the known points in LDS, which bounds c.
+bool three_nn_interp_rows_act_supported(long b, long n, long m, long c, long ldp, long ldo) {
+    return three_nn_interp_rows_supported(b, n, m, c, ldp, ldo) && c <= 1024;
+}
+
+int three_nn_interp_rows_act_dispatch(int b, int n, int m, int c, const float *unknown, const float *known, const float *points, int ldp,
+                                      float *out, int ldo, const int *row_list, const int *row_counts, const float *wx,
+                                      const float *bias, int relu, hipStream_t st) {
+    if (b == 0 || n == 0) return PN2_OK;
+    if (!three_nn_interp_rows_act_supported(b, n, m, c, ldp, ldo)) return PN2_ERANGE;
+    if ((((uintptr_t)points | (uintptr_t)out | (uintptr_t)wx | (uintptr_t)bias) % 16) != 0) return PN2_ERANGE;
+    dim3 grid((n + 63) / 64, b);
+    const size_t lds = ((size_t)m + (size_t)c) * sizeof(float4);
+    const InterpEpilogue ep{wx, bias, relu ? 1 : 0};
+    if (row_list)  // the listed rows; without a list every row of every cloud (the epilogue has no two-launch counterpart either)
+        hipLaunchKernelGGL(three_nn_interp_act_kernel<true>, grid, dim3(256), lds, st, n, m, c / 4, unknown, known, points, ldp, out, ldo,
+                           row_list, row_counts, ep);
+    else
+        hipLaunchKernelGGL(three_nn_interp_act_kernel<false>, grid, dim3(256), lds, st, n, m, c / 4, unknown, known, points, ldp, out, ldo,
+                           nullptr, nullptr, ep);
     return check_launch();
 }
 

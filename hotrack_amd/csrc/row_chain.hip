@@ -72,26 +72,36 @@ __device__ __forceinline__ int lookup(const ChainArgs &A, const Smem &S, int seq
     return lo * A.N + A.list[(size_t)lo * A.N + off + (e - P[lo])];
 }
 
-// one tile: rows e0 .. e0 + cnt - 1 (cnt <= 16 MT) of list `seq`
-template <int MT>
+// one tile: rows e0 .. e0 + cnt - 1 (cnt <= 16 MT) of list `seq`.  H1IN: the input rows are h1 itself (CH floats, already
+// activated: pn2x_row_chain3) and the tile starts at fp1's second layer.
+template <int MT, bool H1IN>
 __device__ void tile(const ChainArgs &A, const Smem &S, int seq, int e0, int cnt) {
     const int tid = (int)threadIdx.x, lane = tid & 63, w = tid >> 6;
     constexpr int R = MT * 16;
     if (tid < R) S.rows[tid] = tid < cnt ? lookup(A, S, seq, e0 + tid) : -1;
     __syncthreads();
-    // input rows -> LDS, zero past column 131 (the row's pad float may hold anything) and for rows past the end
-    for (int i = tid; i < R * (KX / 4); i += 256) {
-        const int r = i / (KX / 4), q = i - r * (KX / 4);
-        const int g = S.rows[r];
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (g >= 0 && q < XQ) {
-            v = *reinterpret_cast<const f32x4 *>(A.x + (size_t)g * A.ldx + 4 * q);
-            if (q == XQ - 1) v.w = 0.f;
+    if constexpr (H1IN) {
+        // h1 rows -> LDS where layer 1 would have left them, zero for rows past the end (those read row 0: no load in a branch)
+        for (int i = tid; i < R * (CH / 4); i += 256) {
+            const int r = i / (CH / 4), q = i - r * (CH / 4);
+            const int g = S.rows[r];
+            const f32x4 v = *reinterpret_cast<const f32x4 *>(A.x + (size_t)(g < 0 ? 0 : g) * A.ldx + 4 * q);
+            *reinterpret_cast<f32x4 *>(S.r2 + r * LDH + 4 * q) = g < 0 ? (f32x4){0.f, 0.f, 0.f, 0.f} : v;
         }
-        *reinterpret_cast<f32x4 *>(S.r1 + r * LDX + 4 * q) = v;
-    }
-    __syncthreads();
-    {  // fp1 layer 1: 144 -> 128, two n-tiles per wave
+    } else {
+        // input rows -> LDS, zero past column 131 (the row's pad float may hold anything) and for rows past the end
+        for (int i = tid; i < R * (KX / 4); i += 256) {
+            const int r = i / (KX / 4), q = i - r * (KX / 4);
+            const int g = S.rows[r];
+            f32x4 v = {0.f, 0.f, 0.f, 0.f};
+            if (g >= 0 && q < XQ) {
+                v = *reinterpret_cast<const f32x4 *>(A.x + (size_t)g * A.ldx + 4 * q);
+                if (q == XQ - 1) v.w = 0.f;
+            }
+            *reinterpret_cast<f32x4 *>(S.r1 + r * LDX + 4 * q) = v;
+        }
+        __syncthreads();
+        // fp1 layer 1: 144 -> 128, two n-tiles per wave
         f32x4 acc[2][MT];
         init_bias(acc, A.ba, 2 * w, lane);
         mm<2, MT, KX / 16, LDX>(acc, A.wa + (size_t)(2 * w) * (KX / 16) * 256, S.r1, lane);
@@ -138,19 +148,22 @@ __device__ void tile(const ChainArgs &A, const Smem &S, int seq, int e0, int cnt
 }
 
 // run rows [e_lo, e_hi) of list `seq` as tiles of up to 64 rows
+template <bool H1IN>
 __device__ void run_rows(const ChainArgs &A, const Smem &S, int seq, int e_lo, int e_hi) {
     for (int e0 = e_lo; e0 < e_hi; e0 += 64) {
         const int cnt = e_hi - e0 < 64 ? e_hi - e0 : 64;
         switch ((cnt + 15) >> 4) {
-            case 1: tile<1>(A, S, seq, e0, cnt); break;
-            case 2: tile<2>(A, S, seq, e0, cnt); break;
-            case 3: tile<3>(A, S, seq, e0, cnt); break;
-            default: tile<4>(A, S, seq, e0, cnt); break;
+            case 1: tile<1, H1IN>(A, S, seq, e0, cnt); break;
+            case 2: tile<2, H1IN>(A, S, seq, e0, cnt); break;
+            case 3: tile<3, H1IN>(A, S, seq, e0, cnt); break;
+            default: tile<4, H1IN>(A, S, seq, e0, cnt); break;
         }
     }
 }
 
-__global__ __launch_bounds__(256, 1) void row_chain_kernel(ChainArgs A) {
+// the launch: the counts' prefix sums, this workgroup's share of both lists, its tiles
+template <bool H1IN>
+__device__ __forceinline__ void chain(const ChainArgs &A) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = (int)threadIdx.x;
     Smem S;
@@ -194,9 +207,14 @@ __global__ __launch_bounds__(256, 1) void row_chain_kernel(ChainArgs A) {
     long l0 = first_at(lo - cs_end, GROUP_COST_LARGE), l1 = first_at(hi - cs_end, GROUP_COST_LARGE);
     l0 = l0 < g_large ? l0 : g_large; l1 = l1 < g_large ? l1 : g_large;
     auto clip = [](long e, int n) { return (int)(e < n ? e : n); };
-    run_rows(A, S, 0, clip(16 * s0, n_small), clip(16 * s1, n_small));
-    run_rows(A, S, 1, clip(16 * l0, n_large), clip(16 * l1, n_large));
+    run_rows<H1IN>(A, S, 0, clip(16 * s0, n_small), clip(16 * s1, n_small));
+    run_rows<H1IN>(A, S, 1, clip(16 * l0, n_large), clip(16 * l1, n_large));
 }
+
+__global__ __launch_bounds__(256, 1) void row_chain_kernel(ChainArgs A) { chain<false>(A); }
+
+// pn2x_row_chain3: the same lists, shares, tiles and layers from fp1's second layer on, over rows that already hold h1
+__global__ __launch_bounds__(256, 1) void row_chain3_kernel(ChainArgs A) { chain<true>(A); }
 
 // ---- per-cloud row lists -------------------------------------------------------------------------------------------------
 // One workgroup per cloud: bitmaps of the points named by the small-K lists and by either list (LDS, one bit per point),
@@ -275,15 +293,17 @@ extern "C" int pn2x_row_chain_supported(int c_in, int c_h, int c_conv, int c_q) 
     return (c_in == 128 && c_h == 128 && c_conv == 384 && c_q == 512) ? 1 : 0;
 }
 
-extern "C" int pn2x_row_chain(int b, int n, const float *x, int ldx, const int *list, const int *counts, const float *wa,
-                              const float *ba, const float *wb, const float *bb, const float *wc, const float *bc, const float *wq,
-                              float *out, int ldo, int grid, void *stream) {
+// the checks and the launch both entries share; h1in: the three-layer kernel (rows of CH floats, no wa / ba)
+static int launch_chain(void (*kernel)(pn2::rchain::ChainArgs), pn2::PerDeviceOnce &raised, bool h1in, int b, int n, const float *x,
+                        int ldx, const int *list, const int *counts, const float *wa, const float *ba, const float *wb,
+                        const float *bb, const float *wc, const float *bc, const float *wq, float *out, int ldo, int grid,
+                        void *stream) {
     using namespace pn2;
     using namespace pn2::rchain;
-    if (b < 0 || n < 1 || ldx < 132 || ldo < CQ || ldx % 4 || ldo % 4 || grid < 0) return PN2_EINVAL;
+    if (b < 0 || n < 1 || ldx < (h1in ? CH : 132) || ldo < CQ || ldx % 4 || ldo % 4 || grid < 0) return PN2_EINVAL;
     if (b > MAXB || (long)b * n >= (1L << 31) / 2) return PN2_ERANGE;
     if (b == 0) return PN2_OK;
-    if (!x || !list || !counts || !wa || !ba || !wb || !bb || !wc || !bc || !wq || !out) return PN2_ENULL;
+    if (!x || !list || !counts || (!h1in && (!wa || !ba)) || !wb || !bb || !wc || !bc || !wq || !out) return PN2_ENULL;
     if (((uintptr_t)x | (uintptr_t)out | (uintptr_t)wa | (uintptr_t)ba | (uintptr_t)wb | (uintptr_t)bb | (uintptr_t)wc |
          (uintptr_t)bc | (uintptr_t)wq) % 16 != 0)
         return PN2_EINVAL;
@@ -293,11 +313,30 @@ extern "C" int pn2x_row_chain(int b, int n, const float *x, int ldx, const int *
     const size_t lds = lds_bytes(b);
     // the opt-in is made once per device, so it covers the largest batch the entry accepts, not the first call's
     static_assert(lds_bytes(MAXB) <= 160 * 1024, "row_chain's LDS at MAXB clouds exceeds a compute unit's 160 KB");
-    static PerDeviceOnce raised;
     if (raised.first_use())
-        (void)hipFuncSetAttribute((const void *)row_chain_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(MAXB));
+        (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(MAXB));
     const int cus = num_compute_units();
     if (grid == 0 || grid > cus) grid = cus;
-    hipLaunchKernelGGL(row_chain_kernel, dim3(grid), dim3(256), lds, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds, (hipStream_t)stream, a);
     return check_launch();
+}
+
+extern "C" int pn2x_row_chain(int b, int n, const float *x, int ldx, const int *list, const int *counts, const float *wa,
+                              const float *ba, const float *wb, const float *bb, const float *wc, const float *bc, const float *wq,
+                              float *out, int ldo, int grid, void *stream) {
+    static pn2::PerDeviceOnce raised;
+    return launch_chain(pn2::rchain::row_chain_kernel, raised, false, b, n, x, ldx, list, counts, wa, ba, wb, bb, wc, bc, wq, out, ldo,
+                        grid, stream);
+}
+
+extern "C" int pn2x_row_chain3_supported(int c_h, int c_conv, int c_q) {
+    return (c_h == 128 && c_conv == 384 && c_q == 512) ? 1 : 0;
+}
+
+extern "C" int pn2x_row_chain3(int b, int n, const float *h1, int ldh, const int *list, const int *counts, const float *wb,
+                               const float *bb, const float *wc, const float *bc, const float *wq, float *out, int ldo, int grid,
+                               void *stream) {
+    static pn2::PerDeviceOnce raised;
+    return launch_chain(pn2::rchain::row_chain3_kernel, raised, true, b, n, h1, ldh, list, counts, nullptr, nullptr, wb, bb,
+                        wc, bc, wq, out, ldo, grid, stream);
 }

@@ -344,13 +344,23 @@ _lib.pn2x_three_nn_interpolate_pm_rows.argtypes = [_ci, _ci, _ci, _ci, _vp, _vp,
 _lib.pn2x_three_nn_interpolate_pm_rows.restype = _ci
 _lib.pn2x_three_nn_interpolate_pm_rows_supported.argtypes = [_ci] * 6
 _lib.pn2x_three_nn_interpolate_pm_rows_supported.restype = _ci
+_lib.pn2x_three_nn_interpolate_pm_rows_act.argtypes = [_ci, _ci, _ci, _ci, _vp, _vp, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _ci, _vp]
+_lib.pn2x_three_nn_interpolate_pm_rows_act.restype = _ci
+_lib.pn2x_three_nn_interpolate_pm_rows_act_supported.argtypes = [_ci] * 6
+_lib.pn2x_three_nn_interpolate_pm_rows_act_supported.restype = _ci
 
 
-def three_nn_interpolate_pm(unknown: torch.Tensor, known: torch.Tensor, points: torch.Tensor, out: torch.Tensor, rows=None) -> torch.Tensor:
+def three_nn_interpolate_pm(unknown: torch.Tensor, known: torch.Tensor, points: torch.Tensor, out: torch.Tensor, rows=None,
+                            wx: torch.Tensor = None, bias: torch.Tensor = None, relu: bool = False) -> torch.Tensor:
     """out (B,n,C) rows <- three_interpolate_pm(points, *three_nn_weights(unknown, known)[::-1]) -- one launch when the sizes are
     covered (include/pn2_ext.h: pn2x_three_nn_interpolate_pm), the two launches otherwise; same floats either way.
     rows=(lst, counts), the pair row_lists returns: only the rows lst[b, :counts[b, 1]] of cloud b are searched, blended and
-    written (pn2x_three_nn_interpolate_pm_rows, always one launch); every other row of `out` is left as it is."""
+    written (pn2x_three_nn_interpolate_pm_rows, always one launch); every other row of `out` is left as it is.
+    wx (C,3) and bias (C,): the rows get act(blend + wx @ unknown[row] + bias) instead, act = ReLU when `relu`
+    (pn2x_three_nn_interpolate_pm_rows_act: the blend in the same order, then the x, y, z terms as one fma each, then the bias) -- the
+    listed rows with rows=..., every row without; always one launch."""
+    if (wx is None) != (bias is None) or (wx is None and relu):
+        raise ValueError("three_nn_interpolate_pm: wx, bias (and relu) come together")
     if rows is not None:
         if not (isinstance(rows, (tuple, list)) and len(rows) == 2 and all(isinstance(t, torch.Tensor) for t in rows)):
             raise TypeError("three_nn_interpolate_pm: rows must be the (list, counts) pair of row_lists")
@@ -363,12 +373,26 @@ def three_nn_interpolate_pm(unknown: torch.Tensor, known: torch.Tensor, points: 
     pp, ldp = _rows(points, "points", C)
     po, ldo = _rows(out, "out", C)
     f32 = torch.float32
-    if rows is not None:
+    if rows is not None or wx is not None:
         if not (_lib.pn2x_three_nn_interpolate_pm_rows_supported(B, n, m, C, ldp, ldo) and pp % 16 == 0 and po % 16 == 0):
-            raise ValueError("three_nn_interpolate_pm: rows needs 3 <= m <= 2048 known points, C and the row strides multiples of 4 "
-                             "and 16-byte aligned points / out")
-        if rows[0].device != points.device or rows[1].device != points.device:
+            raise ValueError("three_nn_interpolate_pm: rows / wx need 3 <= m <= 2048 known points, C and the row strides multiples "
+                             "of 4 and 16-byte aligned points / out")
+        if rows is not None and (rows[0].device != points.device or rows[1].device != points.device):
             raise ValueError("three_nn_interpolate_pm: rows on another device than points")
+        if wx is not None:
+            if not _lib.pn2x_three_nn_interpolate_pm_rows_act_supported(B, n, m, C, ldp, ldo):
+                raise ValueError("three_nn_interpolate_pm: the wx / bias epilogue covers C <= 1024")
+            pw, pb = _native._ptr(wx, "wx", f32, C * 3), _native._ptr(bias, "bias", f32, C)
+            if tuple(wx.shape) != (C, 3) or tuple(bias.shape) != (C,) or pw % 16 or pb % 16:
+                raise ValueError("three_nn_interpolate_pm: wx must be (C,3) and bias (C,), both 16-byte aligned")
+            pl = None if rows is None else _native._ptr(rows[0], "rows list", torch.int32, B * n)
+            pc = None if rows is None else _native._ptr(rows[1], "rows counts", torch.int32, B * 2)
+            with torch.cuda.device(points.device):
+                _native._check(_native._call(_lib.pn2x_three_nn_interpolate_pm_rows_act, "three_nn_interp_act_kernel", None, B, n, m, C,
+                                             _native._ptr(unknown, "unknown", f32, B * n * 3), _native._ptr(known, "known", f32, B * m * 3),
+                                             pp, ldp, po, ldo, pl, pc, pw, pb, 1 if relu else 0, _native._stream(points)),
+                               "three_nn_interpolate_pm")
+            return out
         with torch.cuda.device(points.device):
             _native._check(_native._call(_lib.pn2x_three_nn_interpolate_pm_rows, "three_nn_interp_kernel", None, B, n, m, C,
                                          _native._ptr(unknown, "unknown", f32, B * n * 3), _native._ptr(known, "known", f32, B * m * 3),
@@ -888,6 +912,10 @@ _lib.pn2x_row_chain_supported.argtypes = [_ci] * 4
 _lib.pn2x_row_chain_supported.restype = _ci
 _lib.pn2x_row_chain.argtypes = [_ci, _ci, _vp, _ci, _vp, _vp] + [_vp] * 7 + [_vp, _ci, _ci, _vp]
 _lib.pn2x_row_chain.restype = _ci
+_lib.pn2x_row_chain3_supported.argtypes = [_ci] * 3
+_lib.pn2x_row_chain3_supported.restype = _ci
+_lib.pn2x_row_chain3.argtypes = [_ci, _ci, _vp, _ci, _vp, _vp] + [_vp] * 5 + [_vp, _ci, _ci, _vp]
+_lib.pn2x_row_chain3.restype = _ci
 ROW_CHAIN_MAX_B = 1024
 
 
@@ -932,9 +960,14 @@ def row_chain(x: torch.Tensor, lst: torch.Tensor, counts: torch.Tensor, wa, ba, 
     """out[b, p, :512] for every listed point p of cloud b (pn2x_row_chain): x (B,N,>=132) [interp | xyz | pad] rows (last dim
     contiguous, row stride a multiple of 4), lst / counts from row_lists, the four weight matrices packed by row_chain_pack
     (wa: fp1 layer 1 as (128, 131) [features | xyz]; wb (128,128); wc (384,128); wq (512,384)) and the biases of the first three.
-    Rows / columns no list asks for are left as they are in `out` (B,N,>=512)."""
+    Rows / columns no list asks for are left as they are in `out` (B,N,>=512).
+    wa = ba = None: x (B,N,>=128) already holds h1 = relu(fp1 layer 1) and the chain starts at its second layer (pn2x_row_chain3)."""
     if x.dim() != 3 or not x.is_cuda or x.dtype != torch.float32 or x.stride(2) != 1 or x.stride(0) != x.shape[1] * x.stride(1):
         raise TypeError("row_chain: x must be a (B,N,C) float32 GPU tensor with contiguous rows")
+    if (wa is None) != (ba is None):
+        raise ValueError("row_chain: wa and ba come together")
+    if wa is None and x.shape[2] < 128:
+        raise ValueError("row_chain: without wa / ba the rows of x hold h1, 128 floats")
     B, N, _ = x.shape
     f32 = torch.float32
     if out is None:
@@ -943,6 +976,14 @@ def row_chain(x: torch.Tensor, lst: torch.Tensor, counts: torch.Tensor, wa, ba, 
         raise ValueError("row_chain: out must be (B,N,>=512) float32 with contiguous rows")
     if lst.shape != (B, N) or counts.shape != (B, 2) or lst.dtype != torch.int32 or counts.dtype != torch.int32:
         raise ValueError("row_chain: list (B,N) / counts (B,2) int32 from row_lists")
+    if wa is None:
+        with torch.cuda.device(x.device):
+            _native._check(_native._call(_lib.pn2x_row_chain3, "row_chain3_kernel", None, B, N, x.data_ptr(), x.stride(1), lst.data_ptr(),
+                                         counts.data_ptr(), _native._ptr(wb, "wb", f32, 128 * 128), _native._ptr(bb, "bb", f32, 128),
+                                         _native._ptr(wc, "wc", f32, 384 * 128), _native._ptr(bc, "bc", f32, 384),
+                                         _native._ptr(wq, "wq", f32, 512 * 384), out.data_ptr(), out.stride(1), int(grid),
+                                         _native._stream(x)), "row_chain")
+        return out
     with torch.cuda.device(x.device):
         _native._check(_native._call(_lib.pn2x_row_chain, "row_chain_kernel", None, B, N, x.data_ptr(), x.stride(1), lst.data_ptr(),
                                      counts.data_ptr(), _native._ptr(wa, "wa", f32, 128 * 144), _native._ptr(ba, "ba", f32, 128),
@@ -951,6 +992,17 @@ def row_chain(x: torch.Tensor, lst: torch.Tensor, counts: torch.Tensor, wa, ba, 
                                      _native._ptr(wq, "wq", f32, 512 * 384), out.data_ptr(), out.stride(1), int(grid),
                                      _native._stream(x)), "row_chain")
     return out
+
+
+def row_chain3_supported(c_h: int, c_conv: int, c_q: int) -> bool:
+    return bool(_lib.pn2x_row_chain3_supported(c_h, c_conv, c_q))
+
+
+def row_chain3(h1: torch.Tensor, lst: torch.Tensor, counts: torch.Tensor, wb, bb, wc, bc, wq, out: torch.Tensor = None,
+               grid: int = 0) -> torch.Tensor:
+    """row_chain from its second layer on (pn2x_row_chain3): h1 (B,N,>=128) rows that already hold relu(fp1 layer 1); lists, packed
+    weights, biases and `out` as in row_chain, which this is without its first layer."""
+    return row_chain(h1, lst, counts, None, None, wb, bb, wc, bc, wq, out=out, grid=grid)
 
 
 # ---- sa3 and fp3 as row-tiled layer chains on the large-batch route (include/pn2_ext.h: pn2x_sa3_chain, pn2x_fp3_chain) ----

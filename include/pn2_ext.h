@@ -166,6 +166,20 @@ int pn2x_three_interpolate_pm(int b, int c, int m, int n, const float *points, i
 int pn2x_three_nn_interpolate_pm_rows_supported(int b, int n, int m, int c, int ldp, int ldo);
 int pn2x_three_nn_interpolate_pm_rows(int b, int n, int m, int c, const float *unknown, const float *known, const float *points,
                                       int ldp, float *out, int ldo, const int *row_list, const int *row_counts, void *stream);
+/*
+ * pn2x_three_nn_interpolate_pm_rows_act: the listed-rows launch with an epilogue,
+ *     out[r, ch] = act(blend[r, ch] + wx[ch, 0] x + wx[ch, 1] y + wx[ch, 2] z + bias[ch]),   (x, y, z) = unknown[r],
+ * act = max(., 0) when relu != 0, the identity otherwise.  It is what remains of a per-point layer over [blend | xyz] rows once the
+ * layer's feature half has been applied to `points` (the blend is a convex combination of rows and commutes with a linear map).
+ * Order of the sum per channel: the blend as pn2x_three_nn_interpolate_pm_rows forms it, then the x, y and z terms as one fma each
+ * in that order, then the bias.  wx (c, 3) and bias (c) contiguous and 16-byte aligned.  row_list and row_counts both NULL: every
+ * row of every cloud gets the search, the blend and the epilogue (the floats the listed launch writes there).  Everything else as
+ * pn2x_three_nn_interpolate_pm_rows; pn2x_three_nn_interpolate_pm_rows_act_supported adds c <= 1024 (wx and bias are held in LDS).
+ */
+int pn2x_three_nn_interpolate_pm_rows_act_supported(int b, int n, int m, int c, int ldp, int ldo);
+int pn2x_three_nn_interpolate_pm_rows_act(int b, int n, int m, int c, const float *unknown, const float *known, const float *points,
+                                          int ldp, float *out, int ldo, const int *row_list, const int *row_counts, const float *wx,
+                                          const float *bias, int relu, void *stream);
 
 /*
  * Two-level furthest point sampling without the second pass.  PointNet++ samples level 2 from level 1's samples
@@ -382,6 +396,15 @@ int pn2x_row_chain_supported(int c_in, int c_h, int c_conv, int c_q);
 int pn2x_row_chain(int b, int n, const float *x, int ldx, const int *list, const int *counts, const float *wa, const float *ba,
                    const float *wb, const float *bb, const float *wc, const float *bc, const float *wq, float *out, int ldo,
                    int grid, void *stream);
+/*
+ * pn2x_row_chain3: pn2x_row_chain from its second layer on, for callers that already hold h1 (c_h = 128 floats per row, activated):
+ *     h2 = relu(Wb h1[r] + bb)   c = relu(Wc h2 + bc)   out[r, :] = Wq c
+ * over the same lists, with the same shares, tiles, grid rule, column rule and weight layout; h1 rows ldh >= 128 floats apart.
+ * Same checks and error codes as pn2x_row_chain.
+ */
+int pn2x_row_chain3_supported(int c_h, int c_conv, int c_q);
+int pn2x_row_chain3(int b, int n, const float *h1, int ldh, const int *list, const int *counts, const float *wb, const float *bb,
+                    const float *wc, const float *bc, const float *wq, float *out, int ldo, int grid, void *stream);
 
 /*
  * sa3 and fp3 of the backbone over the b * s level-2 rows, as row-tiled layer chains (hotrack_amd/csrc/mid_chain.hip).

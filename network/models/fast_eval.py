@@ -46,6 +46,10 @@ class FastEval:
     # (tokens x 5C) GEMMs, as before
     fold_rearrange = True
     fold_r2 = True  # with fold_rearrange, on the large-batch route: False keeps r2 as gather_rows + one GEMM
+    # fp1's interpolation taken after the feature half of fp1's first layer (large-batch route): the product runs on the level-1
+    # rows, the listed-rows interpolation adds the xyz term, the bias and the ReLU, and the row chain starts at fp1's second layer
+    # (ext.row_chain3).  False: interpolate, then ext.row_chain's four layers, as before
+    fold_interp = True
 
     def __init__(self, net):
         self.net = net
@@ -187,6 +191,14 @@ class FastEval:
             P["row_chain"] = dict(wa=ext.row_chain_pack(fp1[0][0]), ba=fp1[0][1].contiguous(),
                                   wb=ext.row_chain_pack(fp1[1][0]), bb=fp1[1][1].contiguous(),
                                   wc=ext.row_chain_pack(Wc), bc=P["conv1"][1].contiguous(), wq=ext.row_chain_pack(P["wq"]))
+        # Interpolation is a convex combination of rows, so it commutes with a linear map: W (sum_i w_i f[n_i]) = sum_i w_i (W f)[n_i].
+        # fp1's first layer [interp | xyz] -> c_a splits into its feature block, applied to l1_out's rows before the blend, and the
+        # xyz block, which joins the bias in the interpolation's epilogue (FastEval.fold_interp); the chain's other three layers are
+        # row_chain's own packed weights
+        P["fold_interp"] = None
+        if P["row_chain"] is not None and ext.row_chain3_supported(fp1[0][0].shape[0], Wc.shape[0], 4 * wq[0].shape[0]):
+            P["fold_interp"] = dict(wa_f=fp1[0][0][:, :c_in].contiguous(), wa_x=fp1[0][0][:, c_in:].contiguous(),
+                                    ba=P["row_chain"]["ba"])
         # sa3 and fp3 as two row-tiled chains over the level-2 rows (ext.sa3_chain / ext.fp3_chain): weights in the kernels' operand
         # layout, fp3's per-cloud half transposed for the tiles' own g product
         P["mid_chain"] = None
@@ -293,10 +305,13 @@ class FastEval:
         # Kabsch (palm template -> jittered palm keypoints) + canonicalisation of cloud and keypoints: one launch
         # fp1's input rows [interp(l1 -> l0) | xyz | pad] exist from the start: the hand-frame kernel drops its xyz copy there
         c_i = P["fp2"][-1][0].shape[0]
-        fp1_in = torch.empty((B, N, c_i + 4), **f32)
+        # ... unless fp1's first layer is taken before the interpolation (fold_interp): the chain then reads rows of h1, and nothing
+        # reads an xyz copy
+        folded = self.fold_interp and self._large_batch(B, N) and P["fold_interp"] is not None
+        fp1_in = torch.empty((B, N, P["fold_interp"]["wa_f"].shape[0] if folded else c_i + 4), **f32)
         nonfinite = torch.empty(B, dtype=torch.int32, device=pts.device)  # per-frame NaN / Inf flag (see prepare())
         R, t, xyz2, xyz1 = ext.hand_frame(palm.contiguous(), kp.contiguous(), palm_idx, pts.contiguous(), 0.2,
-                                          xyz2_copy=fp1_in[:, :, c_i:c_i + 3], nonfinite=nonfinite)
+                                          xyz2_copy=None if folded else fp1_in[:, :, c_i:c_i + 3], nonfinite=nonfinite)
         scale = self._scale(pts.device)
         canon = {"scale": scale, "rotation": R, "translation": t}
         tt = t.transpose(1, 2)
@@ -322,7 +337,7 @@ class FastEval:
                                                                        knn=knn_req, query_counts=True)
         else:
             _, l1_xyz, i_l2, idx1, knn_lists = ext.fps_two_level(xyz2, S1, bh.sa2.npoint, query=(bh.sa1.radius_list[0], K1), knn=knn_req)
-        return dict(cnt1=cnt1, P=P, pts=pts, B=B, N=N, J=J, c_i=c_i, fp1_in=fp1_in, nonfinite=nonfinite, R=R, t=t, xyz2=xyz2, xyz1=xyz1,
+        return dict(folded=folded, cnt1=cnt1, P=P, pts=pts, B=B, N=N, J=J, c_i=c_i, fp1_in=fp1_in, nonfinite=nonfinite, R=R, t=t, xyz2=xyz2, xyz1=xyz1,
                     canon=canon, S1=S1, K1=K1, l1_xyz=l1_xyz, i_l2=i_l2, idx1=idx1, knn_lists=knn_lists)
 
     def _dense(self, G, flag_dict):
@@ -414,10 +429,18 @@ class FastEval:
             # K = 16 list get the columns of both scales, the others only the K = 64 scale's)
             # ... and so does fp1's interpolation: row_chain is the only reader of fp1_in's interpolated columns on this route
             lst, counts = ext.row_lists(gi, gi_small, N)
-            ext.three_nn_interpolate_pm(xyz2, l1_xyz, l1_out, fp1_in[:, :, :c_i], rows=(lst, counts))
             a_all = torch.empty((B, N, 4 * c1q), **f32)
-            ext.row_chain(fp1_in, lst, counts, rc["wa"], rc["ba"], rc["wb"], rc["bb"], rc["wc"], rc["bc"], rc["wq"], out=a_all)
+            if G["folded"]:
+                # the feature half of fp1's first layer on the level-1 rows; the listed rows then get relu(blend + Wx xyz + ba) = h1
+                fi = P["fold_interp"]
+                p1 = _lin(l1_out.view(B * S1, c_i), fi["wa_f"]).view(B, S1, -1)
+                ext.three_nn_interpolate_pm(xyz2, l1_xyz, p1, fp1_in, rows=(lst, counts), wx=fi["wa_x"], bias=fi["ba"], relu=True)
+                ext.row_chain3(fp1_in, lst, counts, rc["wb"], rc["bb"], rc["wc"], rc["bc"], rc["wq"], out=a_all)
+            else:
+                ext.three_nn_interpolate_pm(xyz2, l1_xyz, l1_out, fp1_in[:, :, :c_i], rows=(lst, counts))
+                ext.row_chain(fp1_in, lst, counts, rc["wa"], rc["ba"], rc["wb"], rc["bb"], rc["wc"], rc["bc"], rc["wq"], out=a_all)
         else:
+            assert not G["folded"]  # (P["row_chain"] exists only for two distinct K, which is when _geometry asks for gi_small)
             ext.three_nn_interpolate_pm(xyz2, l1_xyz, l1_out, fp1_in[:, :, :c_i])
             f = P["fp1_fused"]
             if f is not None:  # both fp1 layers in one launch (pn2x_mlp2_rows): rows [interp | xyz | pad] -> 128 -> 128
