@@ -92,7 +92,15 @@ __device__ void kabsch_solve(int num, const float *x, const float *y, int ystrid
                 if (n2 > best) { best = n2; v[0] = sg * w0; v[1] = sg * w1; v[2] = sg * w2; v[3] = sg * w3; }
             }
             const double l3 = lam * lam * lam;
-            if (best > 1e-12 * l3 * l3) {  // product of the three eigenvalue gaps >~ 1e-6 lambda^3: the column carries >= 9 digits
+            // How many digits the column carries: the polynomial's constant term holds ~eps lambda^4 of rounding noise, which moves
+            // the root by that over p'(lambda) = P, the product of the three eigenvalue gaps; the adjugate then mixes in the
+            // neighbouring eigenvector by that shift over the SMALLEST gap, which is >= P / (2 lambda)^2 (no gap exceeds 2 lambda:
+            // N is traceless).  So |dR| <~ c eps lambda^6 / P^2, and P^2 / 4 <= best <= P^2.  Measured over 2000 elongated and
+            // mirrored 6-point fits (fp64 on the host, this code): |dR| <= 2.6e-15 lambda^6 / best.  The fit is kept where that
+            // leaves |dR| <= 2.6e-8 -- well inside the 2e-6 the fit is held to, and below fp32's rounding of R; with the earlier
+            // 1e-12 the kept columns of thin point sets (ratio of extents 1e-3 .. 2e-4) were wrong by up to 1e-3.  An isotropic
+            // or planar palm has best ~ 0.01 .. 1 lambda^6; a set thinner than ~1 : 200 goes to the Jacobi sweep.
+            if (best > 1e-7 * l3 * l3) {
                 q0 = v[0]; q1 = v[1]; q2 = v[2]; q3 = v[3];
                 solved = true;
             }
@@ -221,8 +229,13 @@ __device__ void kabsch_backward_one(int num, const float *x, const float *y, int
     const double A10 = K[1][2] * K[2][0] - K[1][0] * K[2][2], A11 = K[0][0] * K[2][2] - K[0][2] * K[2][0], A12 = K[0][2] * K[1][0] - K[0][0] * K[1][2];
     const double A20 = K[1][0] * K[2][1] - K[1][1] * K[2][0], A21 = K[0][1] * K[2][0] - K[0][0] * K[2][1], A22 = K[0][0] * K[1][1] - K[0][1] * K[1][0];
     const double det = K[0][0] * A00 + K[0][1] * A10 + K[0][2] * A20;
-    const double u0 = (A00 * pv[0] + A01 * pv[1] + A02 * pv[2]) / det, u1 = (A10 * pv[0] + A11 * pv[1] + A12 * pv[2]) / det,
-                 u2 = (A20 * pv[0] + A21 * pv[1] + A22 * pv[2]) / det;
+    // K's eigenvalues are the pairwise sums of w's (signed) singular values.  Collinear or coincident points, or a mirrored
+    // target with s2 = s3, make it singular: the rotation is not unique and has no derivative.  Such a fit passes on dL/dt
+    // alone (u = 0) instead of 0 / 0 (pn2_ext.h); 1e-12 tr^3 is a separation of ~1e-12, far below what the fp64 forward resolves.
+    const bool regular = fabs(det) > 1e-12 * fabs(tr * tr * tr);
+    const double u0 = regular ? (A00 * pv[0] + A01 * pv[1] + A02 * pv[2]) / det : 0.0,
+                 u1 = regular ? (A10 * pv[0] + A11 * pv[1] + A12 * pv[2]) / det : 0.0,
+                 u2 = regular ? (A20 * pv[0] + A21 * pv[1] + A22 * pv[2]) / det : 0.0;
     const double hat[3][3] = {{0, -u2, u1}, {u2, 0, -u0}, {-u1, u0, 0}};
     double dW[3][3];
     for (int a = 0; a < 3; ++a)

@@ -29,6 +29,10 @@ int pn2x_kabsch(int b, int xb, int num, const float *x, const float *y, float *R
  * launch; what autograd computes through torch.svd in the reference's training losses, hand_network.py:186-190 via
  * hand_utils.py:42-66).  R (b,3,3) as returned by pn2x_kabsch; grad_R (b,3,3) / grad_t (b,3) may be NULL (= zero);
  * grad_y (b,num,3) is written.  x carries no gradient (the palm template).
+ * A fit whose points are collinear or coincident (or whose mirrored target has two equal singular values) has no unique
+ * rotation and no derivative of it: the 3x3 system K of the closed form is singular (|det K| <= 1e-12 tr(Sym)^3).  Such a
+ * fit's rows receive the translation term alone, grad_y[i] = grad_t / num -- finite, zero without grad_t -- and never Inf or
+ * NaN.  Every fit is computed by its own thread from its own rows: a singular fit changes no other fit's rows by a bit.
  */
 int pn2x_kabsch_backward(int b, int xb, int num, const float *x, const float *y, const float *R, const float *grad_R,
                          const float *grad_t, float *grad_y, void *stream);
