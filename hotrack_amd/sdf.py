@@ -12,6 +12,7 @@ Mirrors, function for function, the reference methods it replaces:
   tsdf_integrate_batch   the same for the volumes of S sequences tracked in lockstep, one launch
   volume_raycast    no counterpart: a volume rendered to depth and normal maps at tracked poses (the raycast), one launch
   raycast_compare   the rendered frames against the observed ones: overlap counts and depth residual sums, one launch
+  obj_refine / obj_refine_batch   no counterpart: the tracked pose refined by damped Gauss-Newton on the volume, one launch
 """
 from __future__ import annotations
 
@@ -784,4 +785,124 @@ def raycast_compare(rendered: torch.Tensor, depth: torch.Tensor, seg: torch.Tens
     with torch.cuda.device(rendered.device):
         rc = _lib.pn2s_raycast_compare(ctypes.byref(r), _native._stream(rendered))
     _native._check(rc, "sdf.raycast_compare")
+    return out
+
+
+# ---- the tracked pose refined by Gauss-Newton on the volume (hotrack_amd/csrc/sdf_refine.hip) -----------------------------------
+class _Refine(ctypes.Structure):
+    """pn2s_refine (88 bytes)."""
+    _fields_ = ([(n, _vp) for n in ("pcld", "cloud_off", "volume", "vols", "poses", "stats", "trace")] +
+                [(n, _cf) for n in ("bbox_min", "stride", "band")] + [(n, _ci) for n in ("problems", "n", "res", "vol_fmt", "iters")])
+
+
+assert ctypes.sizeof(_Refine) == 88
+for _n in ("pn2s_obj_refine", "pn2s_obj_refine_batch"):
+    getattr(_lib, _n).argtypes = [ctypes.POINTER(_Refine), _vp]
+    getattr(_lib, _n).restype = _ci
+REFINE_MAX_ITERS, REFINE_TRACE_ROW, REFINE_BATCH_MAX = 64, 72, 65535   # PN2S_REFINE_*
+REFINE_ITERS, REFINE_BAND = 8, 0.02   # the band: the reference's inlier distance for the object surface (optimization_obj.py:314)
+
+
+def refine_check(pcld, rotation, translation, iters, band, voxel_scale):
+    """The argument checks of obj_refine, which mirror pn2s_obj_refine's (include/pn2_sdf.h) and raise; shared with the torch route
+    (network/models/pose_refine.py), so both refuse the same calls.  Devices and the volume are not looked at here.  -> n"""
+    who = "obj_refine"
+    for name, x in (("pcld", pcld), ("rotation", rotation), ("translation", translation)):
+        if not isinstance(x, torch.Tensor):
+            raise TypeError(f"{who}: {name} must be a torch.Tensor, got {type(x).__name__}")
+    if pcld.numel() < 3 or pcld.numel() % 3 or pcld.shape[-1] != 3:
+        raise ValueError(f"obj_refine: pcld must be (N,3) or (1,N,3) with N >= 1, got {tuple(pcld.shape)}")
+    if rotation.numel() != 9 or translation.numel() != 3:
+        raise ValueError(f"obj_refine: rotation must hold 9 and translation 3 elements, got {tuple(rotation.shape)} and {tuple(translation.shape)}")
+    if int(iters) != iters or not 0 <= int(iters) <= REFINE_MAX_ITERS:
+        raise ValueError(f"obj_refine: iters must be an integer in [0, {REFINE_MAX_ITERS}], got {iters}")
+    _finite_positive(who, ("band", "voxel_scale"), (band, voxel_scale))
+    return pcld.numel() // 3
+
+
+def _corner_volume(who, volume):
+    if not isinstance(volume, CornerVolume):
+        raise TypeError(f"{who}: the volume must be a hotrack_amd.sdf.CornerVolume (the kernel reads the corner layout), got {type(volume).__name__}")
+    return volume
+
+
+def obj_refine(pcld: torch.Tensor, rotation: torch.Tensor, translation: torch.Tensor, volume: CornerVolume, voxel_scale: float,
+               iters: int = REFINE_ITERS, band: float = REFINE_BAND, trace: bool = False, bbox_min: float = BBOX_MIN):
+    """`iters` damped Gauss-Newton steps on sum_j w_j phi(R^T (p_j - t))^2 from (rotation, translation), ONE launch, no host sync
+    (include/pn2_sdf.h: pn2s_obj_refine; the rule is at the head of hotrack_amd/csrc/sdf_refine.hip).
+    pcld (N,3)|(1,N,3); rotation (3,3)|(1,3,3); translation (3,)|(1,3,1); volume: a CornerVolume.
+    -> (rotation (1,3,3), translation (1,3,1), stats (8,)[, trace (iters + 1, REFINE_TRACE_ROW)]) as new tensors; stats = initial cost,
+    final cost, initial and final weighted count, accepted steps, final lambda, 0, 0.  The final cost is never above the initial."""
+    n = refine_check(pcld, rotation, translation, iters, band, voxel_scale)
+    vol = _corner_volume("obj_refine", volume)
+    _on_one_gpu("obj_refine", "pose_refine", vol.data.device, ("pcld", "rotation", "translation"), (pcld, rotation, translation))
+    pcld = pcld.reshape(-1, 3).contiguous()
+    dev = pcld.device
+    pose = torch.cat([rotation.reshape(9).to(_f32), translation.reshape(3).to(_f32)]).contiguous()
+    stats = torch.empty((8,), dtype=_f32, device=dev)
+    tr = torch.empty((int(iters) + 1, REFINE_TRACE_ROW), dtype=_f32, device=dev) if trace else None
+    r = _Refine(problems=1, n=n, res=vol.res, vol_fmt=2 + vol.f16, iters=int(iters), bbox_min=float(bbox_min), stride=float(voxel_scale),
+                band=float(band))
+    r.pcld, r.volume = _native._ptr(pcld, "pcld", _f32, n * 3), vol.data.data_ptr()
+    r.poses, r.stats, r.trace = pose.data_ptr(), stats.data_ptr(), None if tr is None else tr.data_ptr()
+    with torch.cuda.device(dev):
+        rc = _lib.pn2s_obj_refine(ctypes.byref(r), _native._stream(pcld))
+    _native._check(rc, "sdf.obj_refine")
+    out = (pose[:9].view(1, 3, 3), pose[9:].view(1, 3, 1), stats)
+    return out + (tr,) if trace else out
+
+
+def obj_refine_batch(pclds, rotations, translations, volumes, voxel_scale: float, iters: int = REFINE_ITERS, band: float = REFINE_BAND,
+                     trace: bool = False, bbox_min: float = BBOX_MIN, cache=None):
+    """obj_refine for S independent problems with ONE launch (pn2s_obj_refine_batch); every problem's result is bit for bit what
+    obj_refine returns for it alone.  pclds: a list of S clouds, an empty one or None marking an INACTIVE problem (its pose comes back
+    unchanged, its stats and trace rows are zero);  rotations / translations: two lists of S tensors, or (S,3,3) and (S,3)|(S,3,1);
+    volumes: S CornerVolumes of one dtype and resolution, None allowed for an inactive problem;  cache: as obj_optimize_batch's.
+    -> (rotations (S,3,3), translations (S,3,1), stats (S,8)[, trace (S, iters + 1, REFINE_TRACE_ROW)])."""
+    if isinstance(rotations, (list, tuple)):
+        S = len(rotations)
+        if S == 0 or len(translations) != S:
+            raise ValueError(f"obj_refine_batch: rotations and translations must be two lists of S >= 1 tensors, got {S} and {len(translations)}")
+        pose = torch.cat([x.reshape(1, m).to(_f32) for R, t in zip(rotations, translations) for x, m in ((R, 9), (t, 3))], dim=1).view(S, 12)
+    else:
+        S = rotations.shape[0]
+        if rotations.numel() != 9 * S or translations.numel() != 3 * S:
+            raise ValueError(f"obj_refine_batch: rotations (S,3,3) and translations (S,3), got {tuple(rotations.shape)} and {tuple(translations.shape)}")
+        pose = torch.cat([rotations.reshape(S, 9).to(_f32), translations.reshape(S, 3).to(_f32)], dim=1).contiguous()
+    if len(pclds) != S or len(volumes) != S or S > REFINE_BATCH_MAX:
+        raise ValueError(f"obj_refine_batch: pclds and volumes must hold S = {S} <= {REFINE_BATCH_MAX} entries, got {len(pclds)} and {len(volumes)}")
+    if int(iters) != iters or not 0 <= int(iters) <= REFINE_MAX_ITERS:
+        raise ValueError(f"obj_refine_batch: iters must be an integer in [0, {REFINE_MAX_ITERS}], got {iters}")
+    _finite_positive("obj_refine_batch", ("band", "voxel_scale"), (band, voxel_scale))
+    _native._ptr(pose, "rotations/translations", _f32, 12 * S)
+    dev = pose.device
+    stats = torch.zeros((S, 8), dtype=_f32, device=dev)
+    tr = torch.zeros((S, int(iters) + 1, REFINE_TRACE_ROW), dtype=_f32, device=dev) if trace else None
+    out = (pose[:, :9].view(S, 3, 3), pose[:, 9:].reshape(S, 3, 1), stats)
+    out = out + (tr,) if trace else out
+    clouds = [None if c is None or c.numel() == 0 else c.reshape(-1, 3) for c in pclds]
+    sizes = tuple(0 if c is None else c.shape[0] for c in clouds)
+    active = [k for k, m in enumerate(sizes) if m]
+    if not active:
+        return out
+    for k in active:
+        _corner_volume(f"obj_refine_batch: volumes[{k}]", volumes[k])
+    packed = (clouds[active[0]] if len(active) == 1 else torch.cat([clouds[k] for k in active])).contiguous()
+    _on_one_gpu("obj_refine_batch", "pose_refine", dev, ("pclds", "poses"), (packed, pose))
+    key = ("off", str(dev), sizes)
+    off = None if cache is None else cache.get(key)
+    if off is None:
+        acc = [0]
+        for m in sizes:
+            acc.append(acc[-1] + m)
+        off = torch.tensor(acc, dtype=torch.int32, device=dev)
+        if cache is not None:
+            cache[key] = off
+    table, fmt, res = _volume_table(volumes, active, dev, cache)
+    r = _Refine(problems=S, n=0, res=res, vol_fmt=fmt, iters=int(iters), bbox_min=float(bbox_min), stride=float(voxel_scale), band=float(band))
+    r.pcld, r.cloud_off = _native._ptr(packed, "pclds", _f32, sum(sizes) * 3), _native._ptr(off, "cloud_offsets", torch.int32, S + 1)
+    r.vols, r.poses, r.stats, r.trace = table.data_ptr(), pose.data_ptr(), stats.data_ptr(), None if tr is None else tr.data_ptr()
+    with torch.cuda.device(dev):
+        rc = _lib.pn2s_obj_refine_batch(ctypes.byref(r), _native._stream(pose))
+    _native._check(rc, "sdf.obj_refine_batch")
     return out

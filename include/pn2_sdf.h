@@ -336,6 +336,61 @@ struct pn2s_raycast_frames {
 typedef struct pn2s_raycast_frames pn2s_raycast_frames;
 int pn2s_raycast_compare(const pn2s_raycast_frames *frames, void *stream);
 
+/*
+ * The tracked object pose refined by damped Gauss-Newton on the SDF volume (hotrack_amd/csrc/sdf_refine.hip): `iters`
+ * Levenberg-Marquardt steps on  sum_j w_j phi(R^T (p_j - t))^2  from the pose handed in (the particle optimum of pn2s_obj_optimize),
+ * ONE launch, one workgroup of 256 lanes per problem, no host synchronisation.  The reference has no such step.  pn2s_refine is HOST
+ * memory, read during the call; its pointers are DEVICE memory:
+ *   pcld    (n,3) camera-frame points; the batch entry: the packed clouds (sum_k n_k, 3);
+ *   volume  the CORNER layout of pn2s_build_corner_volume, vol_fmt 2 (fp32) or 3 (fp16); res, bbox_min and stride as pn2s_trilinear;
+ *   poses   in/out (problems,12): rotation (3,3) row-major, then translation (3); the object-frame point is q = R^T (p - t);
+ *   stats   out (problems,8): initial cost, final cost, initial and final count of weighted points, accepted steps, final lambda, 0, 0;
+ *   trace   out (problems, iters + 1, PN2S_REFINE_TRACE_ROW) or NULL: the state after every pass (layout: head of sdf_refine.hip).
+ * The rule, fp32 (every expression, with its fmaf, is at the head of sdf_refine.hip):
+ *   residual  r = the trilinear value at q in Distance's operation order (optimization_obj.py:223-226), NOT clamped to +-0.05;
+ *   gradient  g = the exact derivative of that interpolant inside its cell, from the same eight corner values, divided by stride;
+ *   Jacobian  for  R <- R exp([omega]x),  t <- t + dt:   d r / d omega = g x q,   d r / d dt = -R g;
+ *   weight    0 unless |r| < band, the grid coordinate lies strictly inside (0, res - 1) on every axis (the cell is not on the
+ *             volume's clamped border) and the sample is finite; else Huber's with the knee at band / 2: min(1, (band / 2) / |r|);
+ *   pass      A = sum w J J^T (21 values), b = sum w J r (6), E = sum w r^2, n = the number of weighted points: per lane in point
+ *             order, per wave by xor butterfly, the four waves in order;  cost C = E / max(n, 1);
+ *   decision  a step is accepted when C <= the accepted cost and n >= half the accepted count: lambda = max(lambda / 3, 1e-7);
+ *             otherwise the accepted pose stays and lambda = min(10 lambda, 1e7).  lambda starts at 1e-3;
+ *   step      (A + lambda diag(A) + 1e-5 max(n, 1) I) delta = -b of the ACCEPTED pose by an unrolled 6 x 6 Cholesky;  fewer than 6
+ *             weighted points, a pivot that is not positive, a delta that is not finite or whose predicted gain -b . delta is below
+ *             1e-3 of the accepted E (converged): no step this pass, lambda x 10;
+ *             R' = R exp([omega]x) re-projected by pn2s_obj_optimize's ortho6d rule, t' = t + dt.
+ *   iters steps are iters + 1 passes (the last one evaluates and decides); the result is the accepted pose, so the final cost
+ *   is never above the initial one.  No atomics, no scratch; two runs are bitwise equal; nothing is allocated (capturable).
+ * pn2s_obj_refine: problems == 1, n >= 1 points, `volume`; cloud_off and vols are not read.
+ * pn2s_obj_refine_batch: a grid of `problems` workgroups; cloud_off is a DEVICE array of problems + 1 ints, in points, problem k
+ *   owning rows [cloud_off[k], cloud_off[k+1]) of pcld (inside it: the caller's duty), vols a DEVICE array of `problems` volume
+ *   pointers of one vol_fmt, res, bbox_min and stride: pn2s_obj_optimize_batch's conventions.  A problem with an empty slice is
+ *   INACTIVE: its pose, stats and trace keep every byte and its table entry, which may be NULL, is never dereferenced.  Every
+ *   problem's outputs are bit for bit the single entry's (the same device code).  n and volume are not read; problems == 0 is a
+ *   no-op.
+ * Refused with nothing launched, checked in this order: a NULL record (PN2_ENULL);  PN2_EINVAL for problems < 0 (the single entry:
+ *   != 1, or n < 1), iters < 0, res < 2, vol_fmt not 2 / 3, stride or band not finite and > 0, bbox_min not finite;  PN2_ERANGE for
+ *   iters > PN2S_REFINE_MAX_ITERS, res > 1024, problems > PN2S_REFINE_BATCH_MAX;  PN2_ENULL for a NULL pointer other than `trace`.
+ */
+#define PN2S_REFINE_MAX_ITERS 64
+#define PN2S_REFINE_TRACE_ROW 72
+#define PN2S_REFINE_BATCH_MAX 65535
+struct pn2s_refine {
+    const float *pcld;
+    const int *cloud_off;     /* batch entry only */
+    const void *volume;       /* single entry only */
+    const void *const *vols;  /* batch entry only */
+    float *poses;
+    float *stats;
+    float *trace; /* may be NULL */
+    float bbox_min, stride, band;
+    int problems, n, res, vol_fmt, iters;
+}; /* 88 bytes */
+typedef struct pn2s_refine pn2s_refine;
+int pn2s_obj_refine(const pn2s_refine *refine, void *stream);
+int pn2s_obj_refine_batch(const pn2s_refine *refine, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

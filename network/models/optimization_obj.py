@@ -29,6 +29,9 @@ class gf_optimize_obj:
         self.update_shape_flag = bool(cfg.get("opt", {}).get("updateobjshape", False))
         if self.update_shape_flag:
             raise NotImplementedError("online DeepSDF shape update (optimization_obj.py:345-403) is out of scope")
+        # opt.refine_pose (the tracker's switch): Gauss-Newton steps after the particle search, and the residual band
+        self.refine_iters = int((cfg.get("opt") or {}).get("refine_iters", _sdf.REFINE_ITERS))
+        self.refine_band = float((cfg.get("opt") or {}).get("refine_band", _sdf.REFINE_BAND))
         self.device = torch.device(cfg.get("device", device))
         # pre-sampled particles (:103-107): N(0, I_6), particle 0 is the current pose
         rng = np.random.default_rng(seed) if seed is not None else np.random
@@ -86,6 +89,30 @@ class gf_optimize_obj:
                                  iterations=self.iteration, scaling_coefficient1=self.scaling_coefficient1,
                                  scaling_coefficient2=float(self.scaling_coefficient2), beta=self.beta, work=self._work)
         return {"rotation": R, "translation": t.reshape(1, 3, 1)}
+
+    def refine(self, pcld, pose, route=None):
+        """opt.refine_pose: `refine_iters` damped Gauss-Newton steps on the SDF volume from `pose` (what `optimize` returned) -- one
+        more launch, no host synchronisation (models/pose_refine.py, hotrack_amd/csrc/sdf_refine.hip).  Returns {'rotation' (1,3,3),
+        'translation' (1,3,1), 'refine_stats' (8,)}; the final cost (stats[1]) is never above the initial one (stats[0])."""
+        from . import pose_refine
+        R, t, stats = pose_refine.refine(pcld.float().to(self.device), pose["rotation"].float().to(self.device),
+                                         pose["translation"].float().to(self.device), self._corners, self.voxel_scale,
+                                         iters=self.refine_iters, band=self.refine_band, route=route)
+        return {"rotation": R, "translation": t.reshape(1, 3, 1), "refine_stats": stats}
+
+    def refine_batch(self, pclds, poses, corner_volumes, voxel_scale=None):
+        """`refine` for S problems with one launch (hotrack_amd.sdf.obj_refine_batch), next to `optimize_batch` and with its
+        conventions: an empty cloud or None sits out, its pose comes back unchanged (and its stats are zero).  Returns S dicts,
+        each bit-equal to what `refine` returns for it."""
+        S = len(poses)
+        if S == 0:
+            return []
+        poses = [{k: p[k].float().to(self.device) for k in ("rotation", "translation")} for p in poses]
+        pclds = [None if c is None else c.float().to(self.device) for c in pclds]
+        R, t, stats = _sdf.obj_refine_batch(pclds, [p["rotation"] for p in poses], [p["translation"] for p in poses], list(corner_volumes),
+                                            self.voxel_scale if voxel_scale is None else float(voxel_scale), iters=self.refine_iters,
+                                            band=self.refine_band, cache=self._batch_cache)
+        return [{"rotation": R[k:k + 1], "translation": t[k:k + 1], "refine_stats": stats[k]} for k in range(S)]
 
     def forget_volume_tables(self):
         """Drops optimize_batch's cached volume pointer tables, which keep their volumes alive: for a caller that has just

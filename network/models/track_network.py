@@ -668,6 +668,12 @@ class ObjTrackModel_Optimization(nn.Module):
         self.render_model = bool(opt_cfg.get("render_model", False))
         self.render_occl_margin = float(opt_cfg.get("render_occl_margin", 0.01))
         self.render_route = None
+        # opt.refine_pose: after every frame's particle search, refine_iters damped Gauss-Newton steps on the volume inside a band of
+        # refine_band metres (gf_optimize_obj.refine, hotrack_amd/csrc/sdf_refine.hip): one more launch per frame or group step.  The
+        # refined pose is the frame's pose: the next frame starts from it and every later stage reads it.  refine_route: None (the
+        # kernel for GPU tensors), 'kernel' or 'torch'.  Off: no new code runs
+        self.refine_pose = bool(opt_cfg.get("refine_pose", False))
+        self.refine_route = None
         self.surface_seed = 0  # every sequence draws from a generator of its own with this seed: alone or in a group, the same surface
         self.save_folder = cfg.get("save_dir")
 
@@ -750,6 +756,7 @@ class ObjTrackModel_Optimization(nn.Module):
                                "'obj_mesh_path', into the sequence's first frame")
         last = None
         rets = []
+        refined = []
         surf = None
         fusion = self._new_fusion(input) if getattr(self, "fuse_depth", False) and len(input) else None
         for data in input:
@@ -771,6 +778,9 @@ class ObjTrackModel_Optimization(nn.Module):
                 surf = self._new_surface(cloud0).start(cloud0, data["jittered_obj_pose"])
             ret = self.optimizer.optimize(data["obj_points"], data["jittered_obj_pose"], data["category"][0],
                                           data["file_name"][0], data.get("projection"))
+            if getattr(self, "refine_pose", False):
+                ret = self.optimizer.refine(data["obj_points"], ret, route=getattr(self, "refine_route", None))
+                refined.append(ret.pop("refine_stats"))
             if surf is not None:
                 surf.add(data["obj_points"].float().to(self.device), ret, self.optimizer._corners, self.optimizer.voxel_scale)
             last["prev_translation"], last["prev_rotation"] = last["translation"], last["rotation"]  # last frame's pose
@@ -786,6 +796,8 @@ class ObjTrackModel_Optimization(nn.Module):
                 fusion.push(data, ret)
                 if fusion.due():  # the later frames are tracked against the fused volume (load_volume rebuilds the corner layout)
                     self.optimizer.load_volume(fusion.flush(), fusion.voxel_scale)
+        if refined:
+            rets[0]["obj_refine"] = torch.stack(refined)  # (frames, 8): hotrack_amd.sdf.obj_refine's stats, on the device
         if fusion is not None:
             if fusion.pending:
                 self.optimizer.load_volume(fusion.flush(), fusion.voxel_scale)
@@ -892,6 +904,7 @@ class ObjTrackModel_Optimization(nn.Module):
         last = [None] * S
         rets = [[] for _ in range(S)]
         surfs = [None] * S
+        refined = [[] for _ in range(S)]
         group = self._new_fusion_group(vols, known[0][1]) if fuse and known else None
         for t in range(max((len(seq) for seq in inputs), default=0)):
             live = [k for k in range(S) if t < len(inputs[k])]
@@ -918,6 +931,11 @@ class ObjTrackModel_Optimization(nn.Module):
             out = self.optimizer.optimize_batch([inputs[k][t]["obj_points"] if t < len(inputs[k]) else None for k in range(S)],
                                                 [last[k] if last[k] is not None else last[live[0]] for k in range(S)],
                                                 [vols[k] if t < len(inputs[k]) else None for k in range(S)], known[0][1])
+            if getattr(self, "refine_pose", False):  # one more launch for the group; a sequence that has ended sits it out too
+                out = self.optimizer.refine_batch([inputs[k][t]["obj_points"] if t < len(inputs[k]) else None for k in range(S)], out,
+                                                  [vols[k] if t < len(inputs[k]) else None for k in range(S)], known[0][1])
+                for k in live:
+                    refined[k].append(out[k].pop("refine_stats"))
             for k in live:
                 ret = out[k]
                 if surfs[k] is not None:
@@ -938,6 +956,8 @@ class ObjTrackModel_Optimization(nn.Module):
                         vols[k] = _sdf.CornerVolume(fused)
                     self.optimizer.forget_volume_tables()  # (they hold the corner layouts just replaced)
         for k in range(S):
+            if refined[k]:
+                rets[k][0]["obj_refine"] = torch.stack(refined[k])
             if group is not None and rets[k]:
                 rets[k][0]["obj_fused"] = group.state(k)
             if render and rets[k]:
@@ -979,7 +999,10 @@ class ObjTrackModel_Optimization(nn.Module):
                                                   and the log says so once;
           model_depth_residual(mm), model_silhouette_iou, model_occluded_ratio   with opt.render_model: the sequence's volume
                                                   rendered at the tracked poses against the observed depth frames, means over
-                                                  frames (volume_render.fit_columns); they need no ground truth."""
+                                                  frames (volume_render.fit_columns); they need no ground truth;
+          refine_cost_drop, refine_accepted_steps  with opt.refine_pose: the mean over frames of 1 - final / initial cost of the
+                                                  Gauss-Newton refinement (its own weighted mean squared distance inside the
+                                                  band) and of the steps it accepted (ret_dict_lst[0]['obj_refine'], (frames, 8))."""
         from . import eval_metrics
         r_err = t_err = a_err = 0.0
         gRs, gts, Rs, ts = [], [], [], []
@@ -1037,6 +1060,11 @@ class ObjTrackModel_Optimization(nn.Module):
             from .volume_render import COLUMNS
             keys += list(COLUMNS)
             vals += list(rendered["columns"].unbind())
+        refine = ret_dict_lst[0].get("obj_refine")
+        if refine is not None:  # opt.refine_pose: what the Gauss-Newton steps did to their own cost, means over frames
+            c0, c1 = refine[:, 0], refine[:, 1]
+            keys += ["refine_cost_drop", "refine_accepted_steps"]
+            vals += [torch.where(c0 > 0, 1 - c1 / c0.clamp_min(1e-30), torch.zeros_like(c0)).mean(), refine[:, 4].mean()]
         host = torch.stack([torch.as_tensor(v, dtype=torch.float32, device=self.device).reshape(()) for v in vals]).tolist()  # the one read-back
         out = dict(zip(keys, host))
         for k in keys[:3]:

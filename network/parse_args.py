@@ -88,6 +88,13 @@ def add_args(parser):
     parser.add_argument("--obj_model_radius", type=float, default=None,
                         help="track=obj_opt, synthetic sequences: the radius of the capsule the handed-over SDF volume describes "
                              "(default 0.04, the true one the clouds and depth frames show): another value hands over a wrong model")
+    parser.add_argument("--refine_obj_pose", dest="opt/refine_pose", action="store_const", const=True, default=None,
+                        help="track=obj_opt: after every frame's particle search take opt.refine_iters (8) damped Gauss-Newton steps "
+                             "on the SDF volume, over the points within opt.refine_band (0.02 m) of the surface, in one more launch "
+                             "per frame or group step (gf_optimize_obj.refine, hotrack_amd/csrc/sdf_refine.hip).  The refined pose "
+                             "is the frame's pose: the next frame starts from it, and fusion, rendering, the observed surface and "
+                             "the mesh read it.  Reports refine_cost_drop and refine_accepted_steps; the per-frame figures go into "
+                             "ret_dict_lst[0]['obj_refine'].  Off by default: the poses are then bit for bit what they were")
     parser.add_argument("--obj_mesh", type=str, default=None,
                         help="track the synthetic sequences' clouds against an SDF volume built from this triangle mesh (OBJ or "
                              "PLY, object frame, metres; models/mesh_sdf.py) instead of the analytic capsule volume")
