@@ -7,7 +7,7 @@
 //
 // Arithmetic follows the reference's torch expressions operation for operation (fp32, true division, same
 // association; compiled with -ffp-contract=off), so Distance() is bit-identical to the reference.
-#include "pn2_common.h"
+#include "frame_device.h"
 #include "sdf_device.h"
 #include "../../include/pn2_sdf.h"
 
@@ -28,15 +28,13 @@ struct TriPoint {
 
 __device__ __forceinline__ TriPoint tri_setup(const SdfVol &A, float vx, float vy, float vz) {
     const float top = (float)(A.res - 1);
-    float x = clampf((vx - A.bbox_min) / A.stride, 0.0f, top);
-    float y = clampf((vy - A.bbox_min) / A.stride, 0.0f, top);
-    float z = clampf((vz - A.bbox_min) / A.stride, 0.0f, top);
-    const int xi = (int)x, yi = (int)y, zi = (int)z;  // x >= 0: trunc == floor
+    // torch.clamp: a NaN coordinate stays NaN -- its cell is 0, its fraction and so the value NaN
+    const float x = clampf((vx - A.bbox_min) / A.stride, 0.0f, top);
+    const float y = clampf((vy - A.bbox_min) / A.stride, 0.0f, top);
+    const float z = clampf((vz - A.bbox_min) / A.stride, 0.0f, top);
     TriPoint t;
-    t.x = x - (float)xi;
-    t.y = y - (float)yi;
-    t.z = z - (float)zi;
-    t.i000 = (xi * A.res + yi) * A.res + zi;
+    const int xi = cell_split(x, t.x), yi = cell_split(y, t.y), zi = cell_split(z, t.z);
+    t.i000 = cell_index(xi, yi, zi, A.res);
     return t;
 }
 
@@ -69,21 +67,7 @@ template <int FMT>
 __device__ __forceinline__ void tri_gather(const SdfVol &A, const TriPoint &t, float *d) {
     const int R = A.res, RR = R * R, last = RR * R - 1, i = t.i000;
     if constexpr (FMT >= 2) {
-        // corner layout (pn2s_build_corner_volume): cell i holds the eight values the reference would fetch for
-        // i000 == i, already clamped its way -> ONE 16-byte (fp16) or two 16-byte (fp32) loads per point
-        if constexpr (FMT == 3) {
-            const uint4 w = reinterpret_cast<const uint4 *>(A.p)[i];
-            const unsigned u[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                d[2 * k] = __half2float(__ushort_as_half((unsigned short)(u[k] & 0xffffu)));
-                d[2 * k + 1] = __half2float(__ushort_as_half((unsigned short)(u[k] >> 16)));
-            }
-        } else {
-            const float4 a = reinterpret_cast<const float4 *>(A.p)[2 * (size_t)i], b = reinterpret_cast<const float4 *>(A.p)[2 * (size_t)i + 1];
-            d[0] = a.x; d[1] = a.y; d[2] = a.z; d[3] = a.w;
-            d[4] = b.x; d[5] = b.y; d[6] = b.z; d[7] = b.w;
-        }
+        ld_corner_cell<FMT == 3>(A.p, i, d);
         return;
     }
     if (SDF_PAIR && i + 1 + R + RR <= last) {  // everywhere except the volume's last corner
@@ -102,10 +86,7 @@ __device__ __forceinline__ void tri_gather(const SdfVol &A, const TriPoint &t, f
 }
 
 __device__ __forceinline__ float tri_blend(const SdfVol &A, const TriPoint &t, const float *d) {
-    const float mx = 1.0f - t.x, my = 1.0f - t.y, mz = 1.0f - t.z;
-    const float lo = ((d[0] * mz + d[1] * t.z) * my + (d[2] * mz + d[3] * t.z) * t.y) * mx;  // :223-226, same association
-    const float hi = ((d[4] * mz + d[5] * t.z) * my + (d[6] * mz + d[7] * t.z) * t.y) * t.x;
-    return clampf(lo + hi, A.lo, A.hi);
+    return clampf(cell_blend(d, t.x, t.y, t.z), A.lo, A.hi);  // :223-227
 }
 
 template <int FMT>
@@ -186,42 +167,50 @@ __device__ __forceinline__ void particle_sample(const float *__restrict__ pre, i
     s[0] = sqrtf(1.0f - s[1] * s[1] - s[2] * s[2] - s[3] * s[3]);
 }
 
+// Grid (p, problems): workgroup (i, k) is particle i of problem k.  Problem k owns the work record at work + k * work_stride (the
+// layout above; a batch pads it to a multiple of 16 floats), poses[12k .. 12k+12) and -- in a batch -- its slice of the packed cloud
+// and vols[k] (problem_slice, sdf_device.h).  Nothing is shared between problems but read-only inputs, and the last workgroup of
+// problem k is decided by problem k's own ticket: no workgroup ever waits for another, of its own problem or of any other.
 struct OptArgs {
-    int p, n;
+    int p, n, work_stride;     // n: the single entry's cloud
     const float *pcld, *pre;
+    const int *cloud_off;      // batch: (problems + 1) offsets in points; NULL for the single entry
+    const void *const *vols;   // batch; the single entry's volume is V.p
     SdfVol V;
     float c2, beta, one_minus_beta, carry0;
-    float *pose, *work;
+    float *poses, *work;
 };
 
-__global__ void opt_init_kernel(float *work, float c1) {
+constexpr int opt_work_stride(int p) { return (W_ENERGY + p + 15) / 16 * 16; }
+
+__global__ void opt_init_kernel(float *work, int work_stride, float c1) {
+    float *w = work + (size_t)blockIdx.x * work_stride;
     const int t = threadIdx.x;
-    if (t < 6) work[W_SEARCH + t] = c1;
-    if (t >= 6 && t < 12) work[t] = c1;
-    if (t == 12) work[W_PREV_OK] = 1.0f;
-    if (t == 13) work[W_PREV_SCALAR] = 1.0f;
-    if (t == 14) reinterpret_cast<unsigned *>(work)[W_TICKET] = 0u;
+    if (t < 12) w[t] = c1;  // W_SEARCH, W_PREV
+    if (t == 12) w[W_PREV_OK] = 1.0f;
+    if (t == 13) w[W_PREV_SCALAR] = 1.0f;
+    if (t == 14) reinterpret_cast<unsigned *>(w)[W_TICKET] = 0u;
 }
 
-// One workgroup's share of one iteration of one problem: particle i's evaluation, then -- in the workgroup that draws the
-// problem's last ticket -- the pose / search-size update.  Shared by the single-problem and the batched kernel, so the two
-// accumulate in the same order and agree in every bit.
+// One workgroup's share of one iteration of one problem (its n points at pcld, its volume V.p, its pose and work records):
+// particle i's evaluation, then -- in the workgroup that draws the problem's last ticket -- the pose / search-size update.  The one
+// body of both entries, so a problem of a batch accumulates in the single entry's order and agrees with it in every bit.
 template <int FMT>
-__device__ __forceinline__ void obj_optimize_block(const OptArgs &A, const int i) {
+__device__ __forceinline__ void obj_optimize_block(const OptArgs &A, const int n, const float *__restrict__ pcld, const SdfVol &V,
+                                                   float *pose, float *__restrict__ work, const int i) {
     __shared__ float sm[4];
     __shared__ float red[9 * 4 + 4];
     __shared__ int is_last;
     const int tid = threadIdx.x;
-    float *__restrict__ work = A.work;
     float *__restrict__ energy = work + W_ENERGY;
 
     float search[6], R0[9], t0[3];
 #pragma unroll
     for (int k = 0; k < 6; ++k) search[k] = work[W_SEARCH + k];
 #pragma unroll
-    for (int k = 0; k < 9; ++k) R0[k] = A.pose[k];
+    for (int k = 0; k < 9; ++k) R0[k] = pose[k];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) t0[k] = A.pose[9 + k];
+    for (int k = 0; k < 3; ++k) t0[k] = pose[9 + k];
     {
         float s[7], S[9], R[9], t[3];
         particle_sample(A.pre, i, search, s);
@@ -229,7 +218,7 @@ __device__ __forceinline__ void obj_optimize_block(const OptArgs &A, const int i
         mat3_mul(R0, S, R);  // :263
 #pragma unroll
         for (int k = 0; k < 3; ++k) t[k] = t0[k] + s[4 + k];  // :264
-        const float e = particle_sdf_energy<FMT>(A.n, A.pcld, R, t, A.V, sm);
+        const float e = particle_sdf_energy<FMT>(n, pcld, R, t, V, sm);
         // agent-scope (write-through) store: visible to every XCD without an L2 write-back
         if (tid == 0) __hip_atomic_store(&energy[i], e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
@@ -318,10 +307,10 @@ __device__ __forceinline__ void obj_optimize_block(const OptArgs &A, const int i
         y[0] = z[1] * x[2] - z[2] * x[1]; y[1] = z[2] * x[0] - z[0] * x[2]; y[2] = z[0] * x[1] - z[1] * x[0];
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            A.pose[k] = x[k];
-            A.pose[3 + k] = y[k];
-            A.pose[6 + k] = z[k];
-            A.pose[9 + k] = t0[k] + mt[4 + k];  // :288
+            pose[k] = x[k];
+            pose[3 + k] = y[k];
+            pose[6 + k] = z[k];
+            pose[9 + k] = t0[k] + mt[4 + k];  // :288
         }
     } else {
         mean_sdf = origin_sdf;  // :278
@@ -354,52 +343,12 @@ __device__ __forceinline__ void obj_optimize_block(const OptArgs &A, const int i
 
 template <int FMT>
 __global__ void __launch_bounds__(256) obj_optimize_kernel(const OptArgs A) {
-    obj_optimize_block<FMT>(A, blockIdx.x);
-}
-
-// ---- the same loop for S independent problems per launch (pn2s_obj_optimize_batch) ---------------------------------
-// Grid (p, s): workgroup (i, k) is particle i of problem k.  Problem k owns the work record at work + k * work_stride
-// (the layout above, padded to a multiple of 16 floats), its slice [cloud_off[k], cloud_off[k+1]) of the packed cloud,
-// vols[k] and poses[12k .. 12k+12).  Nothing is shared between problems but read-only inputs, and the last workgroup of
-// problem k is decided by problem k's own ticket: no workgroup ever waits for another, of its own problem or of any other.
-struct OptBatchArgs {
-    int p, work_stride;
-    const float *pcld, *pre;
-    const int *cloud_off;
-    const void *const *vols;
-    SdfVol V;  // .p is unused: every problem has its own volume of this format, size and stride
-    float c2, beta, one_minus_beta, carry0;
-    float *poses, *work;
-};
-
-constexpr int opt_work_stride(int p) { return (W_ENERGY + p + 15) / 16 * 16; }
-
-__global__ void opt_init_batch_kernel(float *work, int work_stride, float c1) {
-    float *w = work + (size_t)blockIdx.x * work_stride;
-    const int t = threadIdx.x;
-    if (t < 12) w[t] = c1;  // W_SEARCH, W_PREV
-    if (t == 12) w[W_PREV_OK] = 1.0f;
-    if (t == 13) w[W_PREV_SCALAR] = 1.0f;
-    if (t == 14) reinterpret_cast<unsigned *>(w)[W_TICKET] = 0u;
-}
-
-template <int FMT>
-__global__ void __launch_bounds__(256) obj_optimize_batch_kernel(const OptBatchArgs B) {
     const int k = blockIdx.y;
-    const int o0 = B.cloud_off[k], o1 = B.cloud_off[k + 1];
-    const void *vol = B.vols[k];  // the table's entry, not the volume: loaded for every problem, dereferenced for active ones only
-    if (o0 < 0 || o1 <= o0) return;  // inactive problem: its pose is left alone and its volume is never read
-    OptArgs A;
-    A.p = B.p;
-    A.n = o1 - o0;
-    A.pcld = B.pcld + 3 * (size_t)o0;
-    A.pre = B.pre;
-    A.V = B.V;
-    A.V.p = vol;
-    A.c2 = B.c2; A.beta = B.beta; A.one_minus_beta = B.one_minus_beta; A.carry0 = B.carry0;
-    A.pose = B.poses + 12 * (size_t)k;
-    A.work = B.work + (size_t)k * B.work_stride;
-    obj_optimize_block<FMT>(A, blockIdx.x);
+    int n = A.n;
+    const float *pcld = A.pcld;
+    SdfVol V = A.V;
+    if (A.cloud_off && !problem_slice(A.cloud_off, A.vols, k, pcld, n, V.p)) return;
+    obj_optimize_block<FMT>(A, n, pcld, V, A.poses + 12 * (size_t)k, A.work + (size_t)k * A.work_stride, blockIdx.x);
 }
 
 // ---- gf_optimize_hand_pose.query_sdf (+ get_penetration_loss) (optimization_hand.py:252-268) -----------------------
@@ -482,7 +431,8 @@ __global__ void __launch_bounds__(256) corner_volume_kernel(const void *__restri
     }
 }
 
-inline bool vol_args_ok(int res, float stride) { return res >= 2 && res <= 1024 && stride > 0.0f; }
+// the trilinear entries' grid: res in [2, 1024] (res^3 fits an int), a finite stride > 0
+inline bool grid_inval(int res, float stride) { return res < 2 || res > 1024 || !finite_positive(stride); }
 
 }  // namespace pn2
 
@@ -512,7 +462,7 @@ extern "C" int pn2s_build_corner_volume(const void *vol, int vol_f16, int res, v
 
 extern "C" int pn2s_trilinear(int m, const float *V, const void *vol, int vol_fmt, int res, float bbox_min, float stride,
                               float clamp_lo, float clamp_hi, float *out, void *stream) {
-    if (m < 0 || !vol_args_ok(res, stride)) return PN2_EINVAL;
+    if (m < 0 || grid_inval(res, stride)) return PN2_EINVAL;
     if (m == 0) return (vol_fmt < 0 || vol_fmt > 3) ? PN2_EINVAL : PN2_OK;
     if (!V || !vol || !out) return PN2_ENULL;
     const SdfVol A{vol, res, bbox_min, stride, clamp_lo, clamp_hi};
@@ -525,7 +475,7 @@ extern "C" int pn2s_trilinear(int m, const float *V, const void *vol, int vol_fm
 extern "C" int pn2s_particle_energy(int p, int n, const float *pcld, const float *rot, const float *trans, const void *vol,
                                     int vol_fmt, int res, float bbox_min, float stride, float clamp_lo, float clamp_hi,
                                     float *sdf_energy, void *stream) {
-    if (p < 0 || n < 1 || !vol_args_ok(res, stride)) return PN2_EINVAL;
+    if (p < 0 || n < 1 || grid_inval(res, stride)) return PN2_EINVAL;
     if (p == 0) return (vol_fmt < 0 || vol_fmt > 3) ? PN2_EINVAL : PN2_OK;
     if (!pcld || !rot || !trans || !vol || !sdf_energy) return PN2_ENULL;
     const SdfVol A{vol, res, bbox_min, stride, clamp_lo, clamp_hi};
@@ -536,56 +486,50 @@ extern "C" int pn2s_particle_energy(int p, int n, const float *pcld, const float
 
 extern "C" int pn2s_obj_optimize_work_floats(int p) { return p < 0 ? PN2_EINVAL : W_ENERGY + p; }
 
-extern "C" int pn2s_obj_optimize(int p, int n, int iterations, const float *pcld, const float *pre_sampled, const void *vol,
-                                 int vol_fmt, int res, float bbox_min, float stride, float clamp_lo, float clamp_hi, float c1,
-                                 float c2, float beta, float *pose, float *work, void *stream) {
-    if (p < 1 || n < 1 || iterations < 0 || !vol_args_ok(res, stride) || vol_fmt < 0 || vol_fmt > 3) return PN2_EINVAL;
-    if (!pcld || !pre_sampled || !vol || !pose || !work) return PN2_ENULL;
-    OptArgs A;
-    A.p = p; A.n = n; A.pcld = pcld; A.pre = pre_sampled;
-    A.V = SdfVol{vol, res, bbox_min, stride, clamp_lo, clamp_hi};
-    A.c2 = c2; A.beta = beta;
-    // the reference mixes a Python double scalar into fp32 tensors here (:295): (1-beta) is rounded to fp32 when it
-    // multiplies a tensor, but (1-beta)*c1 is a double product rounded once while prev_search_size is still c1
-    A.one_minus_beta = (float)(1.0 - (double)beta);
-    A.carry0 = (float)((1.0 - (double)beta) * (double)c1);
-    A.pose = pose; A.work = work;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(opt_init_kernel, dim3(1), dim3(64), 0, st, work, c1);
-    for (int it = 0; it < iterations; ++it) {
-        SDF_FMT_DISPATCH(vol_fmt, hipLaunchKernelGGL(obj_optimize_kernel<FMT>, dim3(p), dim3(256), 0, st, A))
-    }
-    return check_launch();
-}
-
 extern "C" long pn2s_obj_optimize_batch_work_floats(int s, int p) {
     return (s < 0 || p < 0) ? (long)PN2_EINVAL : (long)s * opt_work_stride(p);
 }
 
-extern "C" int pn2s_obj_optimize_batch(int s, int p, int iterations, const float *pcld, const int *cloud_off,
-                                       const float *pre_sampled, const void *const *vols, int vol_fmt, int res, float bbox_min,
-                                       float stride, float clamp_lo, float clamp_hi, float c1, float c2, float beta,
-                                       float *poses, float *work, long work_floats, void *stream) {
-    if (s < 0 || p < 1 || iterations < 0 || !vol_args_ok(res, stride) || vol_fmt < 0 || vol_fmt > 3) return PN2_EINVAL;
-    if (s == 0) return PN2_OK;
-    if (!pcld || !cloud_off || !pre_sampled || !vols || !poses || !work) return PN2_ENULL;
-    if (s > PN2S_OPT_BATCH_MAX || p > (1 << 20) || (long)s * p > (1L << 22)) return PN2_ERANGE;
-    if (work_floats < pn2s_obj_optimize_batch_work_floats(s, p)) return PN2_ESCRATCH;
-    OptBatchArgs B;
-    B.p = p; B.work_stride = opt_work_stride(p);
-    B.pcld = pcld; B.pre = pre_sampled; B.cloud_off = cloud_off; B.vols = vols;
-    B.V = SdfVol{nullptr, res, bbox_min, stride, clamp_lo, clamp_hi};
-    B.c2 = c2; B.beta = beta;
-    B.one_minus_beta = (float)(1.0 - (double)beta);  // as pn2s_obj_optimize
-    B.carry0 = (float)((1.0 - (double)beta) * (double)c1);
-    B.poses = poses; B.work = work;
+static_assert(sizeof(pn2s_obj_opt) == 120, "record layout (pn2_sdf.h)");
+
+// A record pointer is read only if a process can own the address: nothing is mapped below 64 KiB, and the upper half of the
+// address space is the kernel's.  A caller built against the positional entries passes its problem or particle count where the
+// record is now, and is refused (PN2_EINVAL) instead of read (as hand_check.h's is_record).
+static int opt_launch(const pn2s_obj_opt *opt, bool batch, void *stream) {
+    if (!opt) return PN2_ENULL;
+    if ((intptr_t)opt < 65536) return PN2_EINVAL;
+    const pn2s_obj_opt &r = *opt;
+    Faults f;
+    f.inval = r.problems < 0 || (!batch && (r.problems != 1 || r.n < 1)) || r.p < 1 || r.iterations < 0 || grid_inval(r.res, r.stride);
+    f.inval |= r.vol_fmt < 0 || r.vol_fmt > 3;
+    f.range = r.problems > PN2S_OPT_BATCH_MAX || r.p > (1 << 20) || (long)r.problems * r.p > (1L << 22);
+    if (f.code() != PN2_OK) return f.code();
+    if (r.problems == 0) return PN2_OK;
+    f.null = !r.pcld || !r.pre_sampled || !r.poses || !r.work || (batch ? (!r.cloud_off || !r.vols) : !r.volume);
+    if (f.code() != PN2_OK) return f.code();
+    if (r.work_floats < (batch ? pn2s_obj_optimize_batch_work_floats(r.problems, r.p) : (long)pn2s_obj_optimize_work_floats(r.p)))
+        return PN2_ESCRATCH;
+    OptArgs A;
+    A.p = r.p; A.n = r.n; A.work_stride = batch ? opt_work_stride(r.p) : 0;
+    A.pcld = r.pcld; A.pre = r.pre_sampled; A.cloud_off = batch ? r.cloud_off : nullptr; A.vols = batch ? r.vols : nullptr;
+    A.V = SdfVol{batch ? nullptr : r.volume, r.res, r.bbox_min, r.stride, r.clamp_lo, r.clamp_hi};
+    A.c2 = r.c2; A.beta = r.beta;
+    // the reference mixes a Python double scalar into fp32 tensors here (:295): (1-beta) is rounded to fp32 when it
+    // multiplies a tensor, but (1-beta)*c1 is a double product rounded once while prev_search_size is still c1
+    A.one_minus_beta = (float)(1.0 - (double)r.beta);
+    A.carry0 = (float)((1.0 - (double)r.beta) * (double)r.c1);
+    A.poses = r.poses; A.work = r.work;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(opt_init_batch_kernel, dim3(s), dim3(64), 0, st, work, B.work_stride, c1);
-    for (int it = 0; it < iterations; ++it) {
-        SDF_FMT_DISPATCH(vol_fmt, hipLaunchKernelGGL(obj_optimize_batch_kernel<FMT>, dim3(p, s), dim3(256), 0, st, B))
+    hipLaunchKernelGGL(opt_init_kernel, dim3(r.problems), dim3(64), 0, st, r.work, A.work_stride, r.c1);
+    for (int it = 0; it < r.iterations; ++it) {
+        SDF_FMT_DISPATCH(r.vol_fmt, hipLaunchKernelGGL(obj_optimize_kernel<FMT>, dim3(r.p, r.problems), dim3(256), 0, st, A))
     }
     return check_launch();
 }
+
+extern "C" int pn2s_obj_optimize(const pn2s_obj_opt *opt, void *stream) { return opt_launch(opt, false, stream); }
+
+extern "C" int pn2s_obj_optimize_batch(const pn2s_obj_opt *opt, void *stream) { return opt_launch(opt, true, stream); }
 
 extern "C" int pn2s_nearest(int b, int n, const float *hand, const float *obj_r, const float *obj_t, const void *vol,
                             int vol_f16, int res, float voxel_scale, int *out_idx, void *out_sdf, void *out_pen, void *stream) {

@@ -1,7 +1,9 @@
-// sdf_device.h -- device arithmetic shared by the kernels that read an SDF volume (sdf.hip, hand_pose.hip, hand_interact.hip,
-// tsdf_fuse.hip, sdf_raycast.hip, sdf_mesh.hip): the volume-element loader, the object-frame transform, torch's floor division
-// and the nearest-voxel index of gf_optimize_hand_pose.query_sdf, the lookup fused into the hand kernels, and the small rotation
-// helpers of the pose updates.  One definition, so that a lookup fused into another kernel reads the same voxel as pn2s_nearest.
+// sdf_device.h -- device arithmetic shared by the kernels that read an SDF volume (sdf.hip, sdf_refine.hip, sdf_raycast.hip,
+// hand_pose.hip, hand_interact.hip, tsdf_fuse.hip, sdf_mesh.hip): the volume-element loader, the object-frame transform, torch's
+// floor division and the nearest-voxel index of gf_optimize_hand_pose.query_sdf, the lookup fused into the hand kernels, the
+// trilinear cell of gf_optimize_obj.Distance (coordinate split, flat index, corner-layout load, eight-value blend), a batched
+// problem's slice of its packed inputs, and the small rotation helpers of the pose updates.  One definition, so that a lookup
+// fused into another kernel reads the same voxel as pn2s_nearest and blends the same cell as pn2s_trilinear.
 #pragma once
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
@@ -69,6 +71,68 @@ __device__ __forceinline__ float sdf_nearest(const void *vol, float x, float y, 
     float ox, oy, oz;
     to_object_frame(x, y, z, ot, oR, ox, oy, oz);
     return ld_vol<F16>(vol, nearest_voxel(ox, oy, oz, voxel_scale, res));
+}
+
+// ---- one trilinear cell (gf_optimize_obj.Distance, optimization_obj.py:184-228) ---------------------------------------------------
+// How a coordinate is clamped into [0, res - 1], which cell a clamped coordinate on the top face belongs to, and how a linear
+// volume is gathered differ between the callers on purpose and stay with them; what follows is what they share.
+
+// a clamped grid coordinate c in [0, res - 1] -> its cell index and the fraction inside the cell (c >= 0: trunc == floor)
+__device__ __forceinline__ int cell_split(float c, float &frac) {
+    const int i = (int)c;
+    frac = c - (float)i;
+    return i;
+}
+
+__device__ __forceinline__ int cell_index(int ix, int iy, int iz, int res) { return (ix * res + iy) * res + iz; }
+
+// Cell i of the corner layout (pn2s_build_corner_volume): the eight values d000 .. d111 (d_abc: a along x, c along z) that the
+// reference fetches for i000 == i, already clamped its way -> ONE 16-byte (fp16) or two 16-byte (fp32) loads per point
+template <bool F16>
+__device__ __forceinline__ void ld_corner_cell(const void *vol, int i, float *d) {
+    if constexpr (F16) {
+        const uint4 w = reinterpret_cast<const uint4 *>(vol)[i];
+        const unsigned u[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            d[2 * k] = __half2float(__ushort_as_half((unsigned short)(u[k] & 0xffffu)));
+            d[2 * k + 1] = __half2float(__ushort_as_half((unsigned short)(u[k] >> 16)));
+        }
+    } else {
+        const float4 a = reinterpret_cast<const float4 *>(vol)[2 * (size_t)i], b = reinterpret_cast<const float4 *>(vol)[2 * (size_t)i + 1];
+        d[0] = a.x; d[1] = a.y; d[2] = a.z; d[3] = a.w;
+        d[4] = b.x; d[5] = b.y; d[6] = b.z; d[7] = b.w;
+    }
+}
+
+// The cell's value at the fractions (x, y, z) in Distance's association order (:223-226; products and sums, no fmaf), NOT clamped.
+// c[0..3] = c00, c01, c10, c11, the four blends along z, for a caller that differentiates the interpolant.
+__device__ __forceinline__ float cell_blend(const float *d, float x, float y, float z, float *c) {
+    const float mx = 1.0f - x, my = 1.0f - y, mz = 1.0f - z;
+    c[0] = d[0] * mz + d[1] * z;
+    c[1] = d[2] * mz + d[3] * z;
+    c[2] = d[4] * mz + d[5] * z;
+    c[3] = d[6] * mz + d[7] * z;
+    return (c[0] * my + c[1] * y) * mx + (c[2] * my + c[3] * y) * x;
+}
+__device__ __forceinline__ float cell_blend(const float *d, float x, float y, float z) {
+    float c[4];
+    return cell_blend(d, x, y, z, c);
+}
+
+// ---- a batched problem's slice ----------------------------------------------------------------------------------------------------
+// Problem k of a batch owns the rows [cloud_off[k], cloud_off[k+1]) of the packed cloud and the entry vols[k] of the volume table:
+// pcld, n and vol become its own.  false: the slice is empty (or its start negative) and the problem is INACTIVE -- the caller
+// returns at once, so everything the problem owns keeps every byte.  The table's ENTRY is loaded for every problem, the volume it
+// points to is read by active ones only: an inactive problem's entry may be NULL.
+__device__ __forceinline__ bool problem_slice(const int *cloud_off, const void *const *vols, int k, const float *&pcld, int &n,
+                                              const void *&vol) {
+    const int o0 = cloud_off[k], o1 = cloud_off[k + 1];
+    vol = vols[k];
+    if (o0 < 0 || o1 <= o0) return false;
+    n = o1 - o0;
+    pcld += 3 * (size_t)o0;
+    return true;
 }
 
 __device__ __forceinline__ void quat_to_matrix(float w, float x, float y, float z, float *m) {  // rotations.py:105-113

@@ -71,13 +71,12 @@ __device__ __forceinline__ float sample(const Field &G, float px, float py, floa
     const float gz = fminf(fmaxf((pz - G.lo) / G.scale, 0.f), G.top);
     const int ix = min((int)gx, G.res - 2), iy = min((int)gy, G.res - 2), iz = min((int)gz, G.res - 2);
     const float x = gx - (float)ix, y = gy - (float)iy, z = gz - (float)iz;
-    const int i000 = (ix * G.res + iy) * G.res + iz;
-    const float d000 = ld_vol<F16>(G.vol, i000), d001 = ld_vol<F16>(G.vol, i000 + 1);
-    const float d010 = ld_vol<F16>(G.vol, i000 + G.res), d011 = ld_vol<F16>(G.vol, i000 + G.res + 1);
-    const float d100 = ld_vol<F16>(G.vol, i000 + G.rr), d101 = ld_vol<F16>(G.vol, i000 + G.rr + 1);
-    const float d110 = ld_vol<F16>(G.vol, i000 + G.rr + G.res), d111 = ld_vol<F16>(G.vol, i000 + G.rr + G.res + 1);
-    const float mx = 1.f - x, my = 1.f - y, mz = 1.f - z;
-    return ((d000 * mz + d001 * z) * my + (d010 * mz + d011 * z) * y) * mx + ((d100 * mz + d101 * z) * my + (d110 * mz + d111 * z) * y) * x;
+    const int i000 = cell_index(ix, iy, iz, G.res);
+    const float d[8] = {ld_vol<F16>(G.vol, i000),                 ld_vol<F16>(G.vol, i000 + 1),
+                        ld_vol<F16>(G.vol, i000 + G.res),         ld_vol<F16>(G.vol, i000 + G.res + 1),
+                        ld_vol<F16>(G.vol, i000 + G.rr),          ld_vol<F16>(G.vol, i000 + G.rr + 1),
+                        ld_vol<F16>(G.vol, i000 + G.rr + G.res),  ld_vol<F16>(G.vol, i000 + G.rr + G.res + 1)};
+    return cell_blend(d, x, y, z);
 }
 
 template <bool F16, bool NORMALS>

@@ -77,23 +77,6 @@ struct Args {
 
 constexpr int tri(int k, int l) { return k * 6 - k * (k - 1) / 2 + (l - k); }  // k <= l: row-wise upper triangle, 21 entries
 
-template <bool F16>
-__device__ __forceinline__ void load_cell(const void *vol, int i, float *d) {
-    if constexpr (F16) {
-        const uint4 w = reinterpret_cast<const uint4 *>(vol)[i];
-        const unsigned u[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            d[2 * k] = __half2float(__ushort_as_half((unsigned short)(u[k] & 0xffffu)));
-            d[2 * k + 1] = __half2float(__ushort_as_half((unsigned short)(u[k] >> 16)));
-        }
-    } else {
-        const float4 a = reinterpret_cast<const float4 *>(vol)[2 * (size_t)i], b = reinterpret_cast<const float4 *>(vol)[2 * (size_t)i + 1];
-        d[0] = a.x; d[1] = a.y; d[2] = a.z; d[3] = a.w;
-        d[4] = b.x; d[5] = b.y; d[6] = b.z; d[7] = b.w;
-    }
-}
-
 // steps 1-7 for one point, added into the lane's 29 sums
 template <bool F16>
 __device__ __forceinline__ void add_point(const Args &A, const void *vol, float px, float py, float pz, const float *R, const float *t,
@@ -108,15 +91,12 @@ __device__ __forceinline__ void add_point(const Args &A, const void *vol, float 
     for (int a = 0; a < 3; ++a) {
         const float u = (q[a] - A.bbox_min) / A.stride;
         inside = inside && u > 0.f && u < top;
-        const float c = fminf(fmaxf(u, 0.f), top);  // a NaN gives 0: every index formed lies in [0, res^3)
-        i[a] = (int)c;
-        f[a] = c - (float)i[a];
+        i[a] = cell_split(fminf(fmaxf(u, 0.f), top), f[a]);  // a NaN gives 0: every index formed lies in [0, res^3)
     }
-    float d[8];
-    load_cell<F16>(vol, (i[0] * A.res + i[1]) * A.res + i[2], d);
-    const float x = f[0], y = f[1], z = f[2], mx = 1.f - x, my = 1.f - y, mz = 1.f - z;
-    const float c00 = d[0] * mz + d[1] * z, c01 = d[2] * mz + d[3] * z, c10 = d[4] * mz + d[5] * z, c11 = d[6] * mz + d[7] * z;
-    const float r0 = (c00 * my + c01 * y) * mx + (c10 * my + c11 * y) * x;
+    float d[8], c[4];
+    ld_corner_cell<F16>(vol, cell_index(i[0], i[1], i[2], A.res), d);
+    const float x = f[0], y = f[1], mx = 1.f - x, my = 1.f - y;
+    const float r0 = cell_blend(d, x, y, f[2], c), c00 = c[0], c01 = c[1], c10 = c[2], c11 = c[3];
     float g[3];
     g[0] = ((c10 - c00) * my + (c11 - c01) * y) / A.stride;
     g[1] = ((c01 - c00) * mx + (c11 - c10) * x) / A.stride;
@@ -322,13 +302,7 @@ __global__ __launch_bounds__(kLanes) void sdf_refine_kernel(const Args A) {
     int n = A.n;
     const float *pcld = A.pcld;
     const void *vol = A.vol;
-    if (A.cloud_off) {  // a problem of a batch: its slice of the packed cloud, its entry of the volume table
-        const int o0 = A.cloud_off[k], o1 = A.cloud_off[k + 1];
-        vol = A.vols[k];  // the table's entry, not the volume: loaded for every problem, dereferenced for active ones only
-        if (o0 < 0 || o1 <= o0) return;  // inactive: pose, stats and trace keep every byte, the volume is never read
-        n = o1 - o0;
-        pcld += 3 * (size_t)o0;
-    }
+    if (A.cloud_off && !problem_slice(A.cloud_off, A.vols, k, pcld, n, vol)) return;  // inactive: pose, stats and trace keep every byte
     refine_problem<F16>(A, n, pcld, vol, A.poses + 12 * (size_t)k, A.stats + 8 * (size_t)k,
                         A.trace ? A.trace + (size_t)k * (A.iters + 1) * kTraceRow : nullptr);
 }

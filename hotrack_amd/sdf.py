@@ -26,21 +26,30 @@ _lib = _native._lib
 _vp, _ci, _cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
 _lib.pn2s_trilinear.argtypes = [_ci, _vp, _vp, _ci, _ci, _cf, _cf, _cf, _cf, _vp, _vp]
 _lib.pn2s_particle_energy.argtypes = [_ci, _ci, _vp, _vp, _vp, _vp, _ci, _ci, _cf, _cf, _cf, _cf, _vp, _vp]
-_lib.pn2s_obj_optimize.argtypes = [_ci, _ci, _ci, _vp, _vp, _vp, _ci, _ci, _cf, _cf, _cf, _cf, _cf, _cf, _cf, _vp, _vp, _vp]
 _lib.pn2s_obj_optimize_work_floats.argtypes = [_ci]
 _lib.pn2s_nearest.argtypes = [_ci, _ci, _vp, _vp, _vp, _vp, _ci, _ci, _cf, _vp, _vp, _vp, _vp]
-for _n in ("pn2s_trilinear", "pn2s_particle_energy", "pn2s_obj_optimize", "pn2s_obj_optimize_work_floats", "pn2s_nearest"):
+for _n in ("pn2s_trilinear", "pn2s_particle_energy", "pn2s_obj_optimize_work_floats", "pn2s_nearest"):
     getattr(_lib, _n).restype = _ci
 
 _lib.pn2s_build_corner_volume.argtypes = [_vp, _ci, _ci, _vp, _vp]
 _lib.pn2s_build_corner_volume.restype = _ci
 _lib.pn2s_corner_volume_elems.argtypes = [_ci]
 _lib.pn2s_corner_volume_elems.restype = ctypes.c_long
-_lib.pn2s_obj_optimize_batch.argtypes = [_ci, _ci, _ci, _vp, _vp, _vp, _vp, _ci, _ci, _cf, _cf, _cf, _cf, _cf, _cf, _cf, _vp, _vp,
-                                         ctypes.c_long, _vp]
-_lib.pn2s_obj_optimize_batch.restype = _ci
 _lib.pn2s_obj_optimize_batch_work_floats.argtypes = [_ci, _ci]
 _lib.pn2s_obj_optimize_batch_work_floats.restype = ctypes.c_long
+
+
+class _ObjOpt(ctypes.Structure):
+    """pn2s_obj_opt (120 bytes)."""
+    _fields_ = ([(n, _vp) for n in ("pcld", "cloud_off", "pre_sampled", "volume", "vols", "poses", "work")] + [("work_floats", ctypes.c_long)] +
+                [(n, _cf) for n in ("bbox_min", "stride", "clamp_lo", "clamp_hi", "c1", "c2", "beta")] +
+                [(n, _ci) for n in ("problems", "p", "n", "iterations", "res", "vol_fmt", "pad_")])
+
+
+assert ctypes.sizeof(_ObjOpt) == 120
+for _n in ("pn2s_obj_optimize", "pn2s_obj_optimize_batch"):
+    getattr(_lib, _n).argtypes = [ctypes.POINTER(_ObjOpt), _vp]
+    getattr(_lib, _n).restype = _ci
 
 BBOX_MIN = -0.2  # optimization_obj.py:186
 CLAMP = (-0.05, 0.05)  # optimization_obj.py:227
@@ -119,31 +128,86 @@ def particle_energy(pcld: torch.Tensor, r: torch.Tensor, t: torch.Tensor, sdf_vo
     return out
 
 
+def _pose12(rotation, translation):
+    """One pose as the kernels take it: 12 floats, the rotation (3,3) row-major, then the translation (3); a new tensor."""
+    return torch.cat([rotation.reshape(9).to(_f32), translation.reshape(3).to(_f32)]).contiguous()
+
+
+def _pose_rows(who, rotations, translations):
+    """S poses -> (S, (S,12) tensor as _pose12's rows), from two lists of S tensors (3,3)|(1,3,3) and (3,)|(1,3,1) -- a tracker's
+    state, held one by one and assembled by ONE concatenation -- or from (S,3,3) and (S,3)|(S,3,1)."""
+    if isinstance(rotations, (list, tuple)):
+        S = len(rotations)
+        if S == 0 or len(translations) != S:
+            raise ValueError(f"{who}: rotations and translations must be two lists of S >= 1 tensors, got {S} and {len(translations)}")
+        pose = torch.cat([x.reshape(1, n).to(_f32) for R, t in zip(rotations, translations) for x, n in ((R, 9), (t, 3))], dim=1).view(S, 12)
+    else:
+        S = rotations.shape[0]
+        if rotations.numel() != 9 * S or translations.numel() != 3 * S:
+            raise ValueError(f"{who}: rotations (S,3,3) and translations (S,3)|(S,3,1), got {tuple(rotations.shape)} and {tuple(translations.shape)}")
+        pose = torch.cat([rotations.reshape(S, 9).to(_f32), translations.reshape(S, 3).to(_f32)], dim=1).contiguous()
+    _native._ptr(pose, "rotations/translations", _f32, 12 * S)
+    return S, pose
+
+
+def _pack_clouds(who, pclds, S, device, cache):
+    """A list of S clouds (n_k,3)|(1,n_k,3), an empty one or None marking an inactive problem -> (packed (sum n_k,3), sizes, active:
+    the problems with points, the int32 device tensor of the S + 1 offsets).  With a `cache` dict the offsets of a repeated list
+    of sizes are uploaded once.  Nothing active: (None, sizes, [], None)."""
+    if len(pclds) != S:
+        raise ValueError(f"{who}: pclds must hold S = {S} clouds, got {len(pclds)}")
+    clouds = [None if c is None or c.numel() == 0 else c.reshape(-1, 3) for c in pclds]
+    sizes = tuple(0 if c is None else c.shape[0] for c in clouds)
+    active = [k for k, n in enumerate(sizes) if n]
+    if not active:
+        return None, sizes, active, None
+    packed = (clouds[active[0]] if len(active) == 1 else torch.cat([clouds[k] for k in active])).contiguous()
+    key = ("off", str(device), sizes)
+    off = None if cache is None else cache.get(key)
+    if off is None:
+        acc = [0]
+        for n in sizes:
+            acc.append(acc[-1] + n)
+        off = torch.tensor(acc, dtype=torch.int32, device=device)
+        if cache is not None:
+            cache[key] = off
+    return packed, sizes, active, off
+
+
+def _obj_opt(entry, who, pose, pre_sampled_particle, work, need_floats, fmt, res, voxel_scale, iterations, c1, c2, beta, bbox_min, clamp, **own):
+    """What obj_optimize and obj_optimize_batch share: the particles and the work buffer checked, pn2s_obj_opt filled (`own`: the
+    fields that are one entry's own) and `entry` called on the poses' device and stream."""
+    pre = pre_sampled_particle.contiguous()
+    if pre.dim() != 2 or pre.shape[1] != 6:
+        raise ValueError("pre_sampled_particle must be (P,6)")
+    P = pre.shape[0]
+    need = need_floats(P)
+    if work is None:
+        work = torch.empty((need,), dtype=_f32, device=pose.device)
+    elif work.numel() < need or work.dtype != _f32 or not work.is_cuda or not work.is_contiguous():
+        raise ValueError(f"work must be a contiguous float32 GPU tensor of >= {need} elements")
+    r = _ObjOpt(p=P, iterations=iterations, res=res, vol_fmt=fmt, bbox_min=bbox_min, stride=voxel_scale, clamp_lo=clamp[0],
+                clamp_hi=clamp[1], c1=c1, c2=c2, beta=beta, work_floats=work.numel(), **own)
+    r.pre_sampled, r.poses, r.work = _native._ptr(pre, "pre_sampled_particle", _f32, P * 6), pose.data_ptr(), work.data_ptr()
+    with torch.cuda.device(pose.device):
+        rc = entry(ctypes.byref(r), _native._stream(pose))
+    _native._check(rc, who)
+
+
 def obj_optimize(pcld: torch.Tensor, rotation: torch.Tensor, translation: torch.Tensor, pre_sampled_particle: torch.Tensor,
                  sdf_volume: torch.Tensor, voxel_scale: float, iterations: int = 10, scaling_coefficient1: float = 0.02,
                  scaling_coefficient2: float = 2.0, beta: float = 0.9, bbox_min: float = BBOX_MIN, clamp=CLAMP, work=None):
     """The particle loop of gf_optimize_obj.optimize on the device, no host synchronisation.
     pcld (N,3)|(1,N,3); rotation (3,3)|(1,3,3); translation (3,)|(1,3,1); pre_sampled_particle (P,6), row 0 == 0.
     Returns (rotation (1,3,3), translation (1,3,1)) as new tensors."""
-    pv, f16, res = _volume(sdf_volume)
+    pv, fmt, res = _volume(sdf_volume)
     pcld = pcld.reshape(-1, 3).contiguous()
     n = pcld.shape[0]
-    pre = pre_sampled_particle.contiguous()
-    P = pre.shape[0]
-    if pre.dim() != 2 or pre.shape[1] != 6:
-        raise ValueError("pre_sampled_particle must be (P,6)")
-    ptrs = (_native._ptr(pcld, "pcld", _f32, n * 3), _native._ptr(pre, "pre_sampled_particle", _f32, P * 6))
-    pose = torch.cat([rotation.reshape(9).to(_f32), translation.reshape(3).to(_f32)]).contiguous()
+    p_pcld = _native._ptr(pcld, "pcld", _f32, n * 3)
+    pose = _pose12(rotation, translation)
     _native._ptr(pose, "rotation/translation", _f32, 12)
-    need = _lib.pn2s_obj_optimize_work_floats(P)
-    if work is None:
-        work = torch.empty((need,), dtype=_f32, device=pcld.device)
-    elif work.numel() < need or work.dtype != _f32 or not work.is_cuda or not work.is_contiguous():
-        raise ValueError(f"work must be a contiguous float32 GPU tensor of >= {need} elements")
-    with torch.cuda.device(pcld.device):
-        rc = _lib.pn2s_obj_optimize(P, n, iterations, *ptrs, pv, f16, res, bbox_min, voxel_scale, clamp[0], clamp[1], scaling_coefficient1, scaling_coefficient2,
-                                    beta, pose.data_ptr(), work.data_ptr(), _native._stream(pcld))
-    _native._check(rc, "sdf.obj_optimize")
+    _obj_opt(_lib.pn2s_obj_optimize, "sdf.obj_optimize", pose, pre_sampled_particle, work, _lib.pn2s_obj_optimize_work_floats, fmt, res,
+             voxel_scale, iterations, scaling_coefficient1, scaling_coefficient2, beta, bbox_min, clamp, problems=1, n=n, pcld=p_pcld, volume=pv)
     return pose[:9].view(1, 3, 3), pose[9:].view(1, 3, 1)
 
 
@@ -205,70 +269,27 @@ def obj_optimize_batch(pclds, rotations, translations, pre_sampled_particle: tor
     cache: a dict the caller keeps between calls: the offsets of a repeated list of cloud sizes and the pointer table of a
       repeated list of volumes are then uploaded once (a steady-state call uploads nothing; required for graph capture).
     Returns (rotations (S,3,3), translations (S,3,1)) as new tensors."""
-    if isinstance(rotations, (list, tuple)):  # S poses held one by one (a tracker's state): assembled by ONE concatenation
-        S = len(rotations)
-        if S == 0 or len(translations) != S:
-            raise ValueError(f"rotations and translations must be two lists of S >= 1 tensors, got {S} and {len(translations)}")
-        pose = torch.cat([x.reshape(1, n).to(_f32) for R, t in zip(rotations, translations) for x, n in ((R, 9), (t, 3))], dim=1).view(S, 12)
-    else:
-        if rotations.dim() != 3 or tuple(rotations.shape[1:]) != (3, 3):
-            raise ValueError(f"rotations must be (S,3,3), got {tuple(rotations.shape)}")
-        S = rotations.shape[0]
-        if translations.numel() != 3 * S:
-            raise ValueError(f"translations must be (S,3) or (S,3,1) with S = {S}, got {tuple(translations.shape)}")
-        pose = torch.cat([rotations.reshape(S, 9).to(_f32), translations.reshape(S, 3).to(_f32)], dim=1).contiguous()
-    _native._ptr(pose, "rotations/translations", _f32, 12 * S)
+    S, pose = _pose_rows("obj_optimize_batch", rotations, translations)
     device = pose.device
     out = pose[:, :9].view(S, 3, 3), pose[:, 9:].reshape(S, 3, 1)
     if len(volumes) != S:
         raise ValueError(f"volumes must hold S = {S} entries, got {len(volumes)}")
-    pre = pre_sampled_particle.contiguous()
-    if pre.dim() != 2 or pre.shape[1] != 6:
-        raise ValueError("pre_sampled_particle must be (P,6)")
-    P = pre.shape[0]
-    p_pre = _native._ptr(pre, "pre_sampled_particle", _f32, P * 6)
     if cloud_offsets is None:
-        if len(pclds) != S:
-            raise ValueError(f"pclds must hold S = {S} clouds, got {len(pclds)}")
-        clouds = [None if c is None or c.numel() == 0 else c.reshape(-1, 3) for c in pclds]
-        sizes = tuple(0 if c is None else c.shape[0] for c in clouds)
-        active = [k for k, n in enumerate(sizes) if n]
-        if not active:
-            return out
-        packed = clouds[active[0]] if len(active) == 1 else torch.cat([clouds[k] for k in active])
-        packed = packed.contiguous()
-        key = ("off", str(device), sizes)
-        off = None if cache is None else cache.get(key)
-        if off is None:
-            acc = [0]
-            for n in sizes:
-                acc.append(acc[-1] + n)
-            off = torch.tensor(acc, dtype=torch.int32, device=device)
-            if cache is not None:
-                cache[key] = off
+        packed, sizes, active, off = _pack_clouds("obj_optimize_batch", pclds, S, device, cache)
         total = sum(sizes)
     else:
         if not isinstance(pclds, torch.Tensor) or pclds.dim() != 2 or pclds.shape[1] != 3:
             raise ValueError("with cloud_offsets, pclds must be one packed (N,3) tensor")
         packed, off, total = pclds.contiguous(), cloud_offsets, pclds.shape[0]
         active = range(S)  # (which slices are empty is known on the device only: no problem may go without a volume)
-        if total == 0:
-            return out
-    p_pcld = _native._ptr(packed, "pclds", _f32, total * 3)
-    p_off = _native._ptr(off, "cloud_offsets", torch.int32, S + 1)
+    if total == 0:
+        return out
     table, fmt, res = _volume_table(volumes, active, device, cache)
-    if packed.device != device or pre.device != device:
-        raise RuntimeError(f"the clouds, poses and particles are on different devices ({packed.device}, {device}, {pre.device})")
-    need = obj_optimize_batch_work_floats(S, P)
-    if work is None:
-        work = torch.empty((need,), dtype=_f32, device=device)
-    elif work.numel() < need or work.dtype != _f32 or not work.is_cuda or not work.is_contiguous():
-        raise ValueError(f"work must be a contiguous float32 GPU tensor of >= {need} elements")
-    with torch.cuda.device(device):
-        rc = _lib.pn2s_obj_optimize_batch(S, P, iterations, p_pcld, p_off, p_pre, table.data_ptr(), fmt, res, bbox_min, voxel_scale,
-                                          clamp[0], clamp[1], scaling_coefficient1, scaling_coefficient2, beta, pose.data_ptr(),
-                                          work.data_ptr(), work.numel(), _native._stream(pose))
-    _native._check(rc, "sdf.obj_optimize_batch")
+    if packed.device != device or pre_sampled_particle.device != device:
+        raise RuntimeError(f"the clouds, poses and particles are on different devices ({packed.device}, {device}, {pre_sampled_particle.device})")
+    _obj_opt(_lib.pn2s_obj_optimize_batch, "sdf.obj_optimize_batch", pose, pre_sampled_particle, work, lambda P: obj_optimize_batch_work_floats(S, P),
+             fmt, res, voxel_scale, iterations, scaling_coefficient1, scaling_coefficient2, beta, bbox_min, clamp, problems=S, vols=table.data_ptr(),
+             pcld=_native._ptr(packed, "pclds", _f32, total * 3), cloud_off=_native._ptr(off, "cloud_offsets", torch.int32, S + 1))
     return out
 
 
@@ -838,7 +859,7 @@ def obj_refine(pcld: torch.Tensor, rotation: torch.Tensor, translation: torch.Te
     _on_one_gpu("obj_refine", "pose_refine", vol.data.device, ("pcld", "rotation", "translation"), (pcld, rotation, translation))
     pcld = pcld.reshape(-1, 3).contiguous()
     dev = pcld.device
-    pose = torch.cat([rotation.reshape(9).to(_f32), translation.reshape(3).to(_f32)]).contiguous()
+    pose = _pose12(rotation, translation)
     stats = torch.empty((8,), dtype=_f32, device=dev)
     tr = torch.empty((int(iters) + 1, REFINE_TRACE_ROW), dtype=_f32, device=dev) if trace else None
     r = _Refine(problems=1, n=n, res=vol.res, vol_fmt=2 + vol.f16, iters=int(iters), bbox_min=float(bbox_min), stride=float(voxel_scale),
@@ -859,45 +880,23 @@ def obj_refine_batch(pclds, rotations, translations, volumes, voxel_scale: float
     unchanged, its stats and trace rows are zero);  rotations / translations: two lists of S tensors, or (S,3,3) and (S,3)|(S,3,1);
     volumes: S CornerVolumes of one dtype and resolution, None allowed for an inactive problem;  cache: as obj_optimize_batch's.
     -> (rotations (S,3,3), translations (S,3,1), stats (S,8)[, trace (S, iters + 1, REFINE_TRACE_ROW)])."""
-    if isinstance(rotations, (list, tuple)):
-        S = len(rotations)
-        if S == 0 or len(translations) != S:
-            raise ValueError(f"obj_refine_batch: rotations and translations must be two lists of S >= 1 tensors, got {S} and {len(translations)}")
-        pose = torch.cat([x.reshape(1, m).to(_f32) for R, t in zip(rotations, translations) for x, m in ((R, 9), (t, 3))], dim=1).view(S, 12)
-    else:
-        S = rotations.shape[0]
-        if rotations.numel() != 9 * S or translations.numel() != 3 * S:
-            raise ValueError(f"obj_refine_batch: rotations (S,3,3) and translations (S,3), got {tuple(rotations.shape)} and {tuple(translations.shape)}")
-        pose = torch.cat([rotations.reshape(S, 9).to(_f32), translations.reshape(S, 3).to(_f32)], dim=1).contiguous()
+    S, pose = _pose_rows("obj_refine_batch", rotations, translations)
     if len(pclds) != S or len(volumes) != S or S > REFINE_BATCH_MAX:
         raise ValueError(f"obj_refine_batch: pclds and volumes must hold S = {S} <= {REFINE_BATCH_MAX} entries, got {len(pclds)} and {len(volumes)}")
     if int(iters) != iters or not 0 <= int(iters) <= REFINE_MAX_ITERS:
         raise ValueError(f"obj_refine_batch: iters must be an integer in [0, {REFINE_MAX_ITERS}], got {iters}")
     _finite_positive("obj_refine_batch", ("band", "voxel_scale"), (band, voxel_scale))
-    _native._ptr(pose, "rotations/translations", _f32, 12 * S)
     dev = pose.device
     stats = torch.zeros((S, 8), dtype=_f32, device=dev)
     tr = torch.zeros((S, int(iters) + 1, REFINE_TRACE_ROW), dtype=_f32, device=dev) if trace else None
     out = (pose[:, :9].view(S, 3, 3), pose[:, 9:].reshape(S, 3, 1), stats)
     out = out + (tr,) if trace else out
-    clouds = [None if c is None or c.numel() == 0 else c.reshape(-1, 3) for c in pclds]
-    sizes = tuple(0 if c is None else c.shape[0] for c in clouds)
-    active = [k for k, m in enumerate(sizes) if m]
+    packed, sizes, active, off = _pack_clouds("obj_refine_batch", pclds, S, dev, cache)
     if not active:
         return out
     for k in active:
         _corner_volume(f"obj_refine_batch: volumes[{k}]", volumes[k])
-    packed = (clouds[active[0]] if len(active) == 1 else torch.cat([clouds[k] for k in active])).contiguous()
     _on_one_gpu("obj_refine_batch", "pose_refine", dev, ("pclds", "poses"), (packed, pose))
-    key = ("off", str(dev), sizes)
-    off = None if cache is None else cache.get(key)
-    if off is None:
-        acc = [0]
-        for m in sizes:
-            acc.append(acc[-1] + m)
-        off = torch.tensor(acc, dtype=torch.int32, device=dev)
-        if cache is not None:
-            cache[key] = off
     table, fmt, res = _volume_table(volumes, active, dev, cache)
     r = _Refine(problems=S, n=0, res=res, vol_fmt=fmt, iters=int(iters), bbox_min=float(bbox_min), stride=float(voxel_scale), band=float(band))
     r.pcld, r.cloud_off = _native._ptr(packed, "pclds", _f32, sum(sizes) * 3), _native._ptr(off, "cloud_offsets", torch.int32, S + 1)

@@ -45,7 +45,7 @@ int pn2s_build_corner_volume(const void *vol, int vol_f16, int res, void *out, v
  * Distance(V)  (optimization_obj.py:184-228): trilinear SDF at m points.
  *   V (m,3) object-frame coordinates; out (m).  x = clamp((v - bbox_min)/stride, 0, res-1) per axis, the eight
  *   corner indices clamped to [0, res^3-1] exactly as the reference does, result clamped to [clamp_lo, clamp_hi]
- *   (reference constants: bbox_min -0.2, clamps -0.05 / 0.05).
+ *   (reference constants: bbox_min -0.2, clamps -0.05 / 0.05).  res in [2, 1024]; stride finite and > 0 (PN2_EINVAL otherwise).
  */
 int pn2s_trilinear(int m, const float *V, const void *vol, int vol_fmt, int res, float bbox_min, float stride,
                    float clamp_lo, float clamp_hi, float *out, void *stream);
@@ -67,44 +67,55 @@ int pn2s_particle_energy(int p, int n, const float *pcld, const float *rot, cons
  *   R_i = R @ quat2mat(sample_i[0:4]),  t_i = t + sample_i[4:7]
  * and then (last workgroup to finish) the weighted-mean pose update, SO(3) re-projection and search-size update,
  * with no host synchronisation (the reference syncs on `torch.any` every iteration).
- *   pcld (n,3); pre_sampled (p,6) with row 0 == 0 (particle 0 is the current pose);
- *   pose: in/out, 12 floats = rotation (3,3) row-major then translation (3);
- *   work: scratch, at least pn2s_obj_optimize_work_floats(p) floats, contents undefined on return
- *         except work[0..5] = final search size;
+ * pn2s_obj_opt is HOST memory, read during the call; its pointers are DEVICE memory:
+ *   pcld        (n,3) camera-frame points; the batch entry: the packed clouds (sum_k n_k, 3);
+ *   pre_sampled (p,6) with row 0 == 0 (particle 0 is the current pose), shared by all problems;
+ *   volume      of layout `vol_fmt`, with res, bbox_min, stride, clamp_lo and clamp_hi as pn2s_trilinear;
+ *   poses       in/out (problems,12): rotation (3,3) row-major, then translation (3), per problem;
+ *   work        scratch of work_floats floats: at least pn2s_obj_optimize_work_floats(p) (16 header floats and p energies) for the
+ *               single entry, pn2s_obj_optimize_batch_work_floats(problems, p) for the batch = `problems` such records, each padded
+ *               to a multiple of 16 floats.  Contents undefined on return except a record's [0..5] = final search size and its
+ *               ticket, which is zero again;
  *   c1, c2, beta: scaling_coefficient1 (0.02), scaling_coefficient2 (2), beta (0.9).
- */
-int pn2s_obj_optimize(int p, int n, int iterations, const float *pcld, const float *pre_sampled, const void *vol,
-                      int vol_fmt, int res, float bbox_min, float stride, float clamp_lo, float clamp_hi, float c1,
-                      float c2, float beta, float *pose, float *work, void *stream);
-int pn2s_obj_optimize_work_floats(int p);
-
-/*
- * pn2s_obj_optimize for s independent problems at once (one frame step of s object sequences tracked in lockstep): one
- * init launch and `iterations` launches of a (p, s) grid for all of them together, no host synchronisation, capturable in a
- * HIP graph.  Workgroup (i, k) evaluates particle i of problem k; the last workgroup of problem k to finish -- by problem
- * k's own ticket -- does problem k's update.  No workgroup waits for another, and no problem reads what another writes.
- * Every problem's result is bit-for-bit what pn2s_obj_optimize returns for it alone (the same device code, the same
- * accumulation order).
- *   pcld        packed clouds, (sum_k n_k, 3);
- *   cloud_off   DEVICE array of s+1 ints, in points: problem k owns rows [cloud_off[k], cloud_off[k+1]).  The offsets must lie
- *               inside pcld (the caller's duty: they are read on the device only).  A problem with an empty slice
+ * pn2s_obj_optimize: problems == 1, n >= 1 points, `volume`; a grid of p workgroups.  cloud_off and vols are not read.
+ * pn2s_obj_optimize_batch: `problems` independent problems at once (one frame step of that many object sequences tracked in
+ *   lockstep): one init launch and `iterations` launches of a (p, problems) grid for all of them together, capturable in a HIP graph.
+ *   Workgroup (i, k) evaluates particle i of problem k; the last workgroup of problem k to finish -- by problem k's own ticket --
+ *   does problem k's update.  No workgroup waits for another, and no problem reads what another writes.  Every problem's result
+ *   is bit-for-bit what pn2s_obj_optimize returns for it alone (one kernel, the same accumulation order).
+ *   cloud_off   DEVICE array of problems + 1 ints, in points: problem k owns rows [cloud_off[k], cloud_off[k+1]).  The offsets must
+ *               lie inside pcld (the caller's duty: they are read on the device only).  A problem with an empty slice
  *               (cloud_off[k+1] <= cloud_off[k]) is INACTIVE: its pose is left untouched; the entry vols[k] is loaded but
  *               the volume is never read, so the entry may be NULL -- how a sequence that has ended sits out the remaining
  *               frames of its group;
- *   pre_sampled (p,6), row 0 == 0, shared by all problems;
- *   vols        DEVICE array of s volume pointers, all of one vol_fmt, res, bbox_min and stride;
- *   poses       in/out (s,12): rotation (3,3) row-major, then translation (3), per problem;
- *   work        scratch of at least pn2s_obj_optimize_batch_work_floats(s, p) floats = s records of the single entry's
- *               layout, each padded to a multiple of 16 floats; contents undefined on return except the tickets, which are
- *               zero again.
- * s == 0 is a no-op that reads nothing.  Limits (PN2_ERANGE beyond): s <= PN2S_OPT_BATCH_MAX (the grid's second
- * dimension), p <= 2^20, s * p <= 2^22 (workgroups per launch).  PN2_ESCRATCH when work_floats is too small.
+ *   vols        DEVICE array of `problems` volume pointers, all of one vol_fmt, res, bbox_min and stride.
+ *   n and volume are not read; problems == 0 is a no-op that reads nothing.
+ * Refused with nothing launched, checked in this order: a NULL record (PN2_ENULL);  a record pointer no process can own -- below
+ *   64 KiB or in the upper half of the address space, which is what a caller built against the positional entries passes, its
+ *   count -- is PN2_EINVAL and is not read;  PN2_EINVAL for problems < 0 (the single entry: != 1, or n < 1), p < 1, iterations < 0, res outside [2, 1024], vol_fmt outside 0..3, a stride that is not finite and > 0 (an
+ *   infinite stride, which puts every point in cell 0, is refused like a NaN);  PN2_ERANGE for problems > PN2S_OPT_BATCH_MAX (the
+ *   grid's second dimension), p > 2^20, problems * p > 2^22 (workgroups per launch);  PN2_ENULL for a NULL pointer the entry reads;
+ *   PN2_ESCRATCH when work_floats is too small.
  */
 #define PN2S_OPT_BATCH_MAX 65535
-int pn2s_obj_optimize_batch(int s, int p, int iterations, const float *pcld, const int *cloud_off, const float *pre_sampled,
-                            const void *const *vols, int vol_fmt, int res, float bbox_min, float stride, float clamp_lo,
-                            float clamp_hi, float c1, float c2, float beta, float *poses, float *work, long work_floats,
-                            void *stream);
+struct pn2s_obj_opt {
+    const float *pcld;
+    const int *cloud_off;     /* batch entry only */
+    const float *pre_sampled;
+    const void *volume;       /* single entry only */
+    const void *const *vols;  /* batch entry only */
+    float *poses;
+    float *work;
+    long work_floats;
+    float bbox_min, stride, clamp_lo, clamp_hi;
+    float c1, c2, beta;
+    int problems, p, n, iterations, res, vol_fmt;
+    int pad_; /* to 120 bytes; not read */
+}; /* 120 bytes */
+typedef struct pn2s_obj_opt pn2s_obj_opt;
+int pn2s_obj_optimize(const pn2s_obj_opt *opt, void *stream);
+int pn2s_obj_optimize_batch(const pn2s_obj_opt *opt, void *stream);
+int pn2s_obj_optimize_work_floats(int p);
 long pn2s_obj_optimize_batch_work_floats(int s, int p);
 
 /*
@@ -365,7 +376,7 @@ int pn2s_raycast_compare(const pn2s_raycast_frames *frames, void *stream);
  * pn2s_obj_refine: problems == 1, n >= 1 points, `volume`; cloud_off and vols are not read.
  * pn2s_obj_refine_batch: a grid of `problems` workgroups; cloud_off is a DEVICE array of problems + 1 ints, in points, problem k
  *   owning rows [cloud_off[k], cloud_off[k+1]) of pcld (inside it: the caller's duty), vols a DEVICE array of `problems` volume
- *   pointers of one vol_fmt, res, bbox_min and stride: pn2s_obj_optimize_batch's conventions.  A problem with an empty slice is
+ *   pointers of one vol_fmt, res, bbox_min and stride: pn2s_obj_optimize_batch's conventions (one slice rule on the device).  A problem with an empty slice is
  *   INACTIVE: its pose, stats and trace keep every byte and its table entry, which may be NULL, is never dereferenced.  Every
  *   problem's outputs are bit for bit the single entry's (the same device code).  n and volume are not read; problems == 0 is a
  *   no-op.

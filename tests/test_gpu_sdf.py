@@ -251,6 +251,58 @@ def test_corner_layout_is_bit_identical(sdf, S, dt):
     assert torch.equal(Ra, Rb) and torch.equal(ta, tb)
 
 
+def test_trilinear_border_and_non_finite_coordinates(sdf):
+    """Distance() on the box's corners, in its last cells, beyond its faces and at +-inf / NaN coordinates, through all four
+    volume routes (linear / CornerVolume x fp16 / fp32).  The coordinate clamp is torch.clamp: an infinite coordinate is the point a
+    stride beyond that face, bit for bit, and a NaN coordinate stays NaN and gives a NaN; the four routes agree in every bit."""
+    stride, lo, clamp, inf, nan = 0.1, -0.2, (-1e30, 1e30), np.float32(np.inf), np.float32(np.nan)
+    for res in (3, 5):
+        rng = np.random.default_rng(res)
+        hi = lo + (res - 1) * stride
+        inner = lambda m: rng.uniform(lo, hi, (m, 3))                                          # noqa: E731
+        pts = [np.array([[x, y, z] for x in (lo, hi) for y in (lo, hi) for z in (lo, hi)])]    # the eight corners
+        swapped, finite_twin = [], []
+        for a in range(3):
+            last, below, above = inner(4), inner(2), inner(2)
+            last[:, a] = rng.uniform(hi - stride, hi, 4)                                       # in the last cell of this axis
+            below[:, a], above[:, a] = lo - stride, hi + stride                                # a stride beyond each face
+            pts += [last, below, above]
+            for bad, twin in ((inf, hi + stride), (-inf, lo - stride), (nan, None)):
+                p = inner(1)
+                p[0, a] = bad
+                swapped.append(p)
+                q = p.copy()
+                q[0, a] = np.nan if twin is None else twin
+                finite_twin.append(q)
+        n_finite = sum(len(p) for p in pts)
+        V = np.concatenate(pts + swapped).astype(np.float32)
+        twin = np.concatenate(finite_twin).astype(np.float32)
+        vol16 = rng.uniform(-1, 1, res ** 3).astype(np.float16)       # the fp32 volume holds the same values: the routes must agree
+        d16, d32 = _d(vol16), _d(vol16.astype(np.float32))
+        routes = (d16, d32, sdf.CornerVolume(d16), sdf.CornerVolume(d32))
+        got = [sdf.distance(_d(V), r, stride, bbox_min=lo, clamp=clamp).cpu().numpy() for r in routes]
+        ref = got[0]
+        is_nan = np.isnan(V).any(axis=1)
+        assert is_nan.sum() == 3 and np.array_equal(np.isnan(ref), is_nan)                     # a NaN coordinate gives a NaN, nothing else does
+        assert np.abs(ref[~is_nan]).max() <= 1.0 and np.abs(ref[~is_nan]).max() > 0.05         # the +-1e30 clamp let the value show
+        for g in got[1:]:
+            assert np.array_equal(np.isnan(g), is_nan)
+            assert np.array_equal(g[~is_nan].view(np.int32), ref[~is_nan].view(np.int32))
+        want = sdf.distance(_d(twin), d16, stride, bbox_min=lo, clamp=clamp).cpu().numpy()     # the clamp binds: inf == a stride beyond
+        tail, keep = ref[n_finite:], ~np.isnan(twin).any(axis=1)
+        assert keep.sum() == 6 and np.array_equal(tail[keep].view(np.int32), want[keep].view(np.int32))
+        # the same points as a cloud, identity pose, one particle: the fused gather / blend of particle_energy, all four routes
+        eye, zero = _d(np.eye(3, dtype=np.float32)[None]), _d(np.zeros((1, 3), np.float32))
+        for cloud, nan_expected in ((V, True), (V[:n_finite], False)):
+            e = [sdf.particle_energy(_d(cloud), eye, zero, r, stride, bbox_min=lo, clamp=clamp).cpu().numpy() for r in routes]
+            assert e[0].shape == (1,) and bool(np.isnan(e[0][0])) == nan_expected
+            for g in e[1:]:
+                assert np.array_equal(np.isnan(g), np.isnan(e[0]))
+                assert nan_expected or np.array_equal(g.view(np.int32), e[0].view(np.int32))
+        # and the fused value is the mean of |Distance| over the finite points (another summation order: a few ulps)
+        np.testing.assert_allclose(e[0][0], np.abs(ref[:n_finite]).astype(np.float64).mean(), rtol=1e-5)
+
+
 def test_query_sdf_voxel_boundaries_exact(sdf, S):
     """Coordinates on and one ulp either side of every voxel face, huge and tiny values: the kernel's division-based
     floor must give the voxel torch's fmod-based `//` gives (oracle = literal restatement of c10::div_floor_floating)."""
