@@ -82,6 +82,8 @@ class LossDict(dict):
 
 
 class HandTrackNet(nn.Module):
+    fused_loss_weights = None  # (9,) on the device, set by the Trainer: compute_loss's weighted total comes out of the loss launch
+
     def __init__(self, cfg, elide_dead_attention: bool = True):
         super().__init__()
         self.device = cfg["device"]
@@ -302,8 +304,7 @@ class HandTrackNet(nn.Module):
             gt = input["gt_hand_kp"].to(dev).float()
             palm = input["gt_hand_pose"]["palm_template"].to(dev).float()
             s = float(0.2)  # _hand_frame / fast paths: the constant hand-frame scale (hand_network.py:95)
-            # fused_loss_weights (9,), set by the Trainer: the weighted total comes out of the same launch
-            wts = getattr(self, "fused_loss_weights", None)
+            wts = self.fused_loss_weights
             if wts is not None and (wts.device != ret_dict["pred_kp"].device or wts.numel() != 9):
                 wts = None
             res = ext.HandLosses.apply(ret_dict["pred_kp_handframe"], ret_dict["init_kp_handframe"], gt, ret_dict["pred_kp"], canon_pose["rotation"],

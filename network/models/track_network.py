@@ -8,6 +8,8 @@ MANO layer, which needs licensed assets; the tracking logic is otherwise the sam
 (`use_pred_hand_shape`), from the hand model's rest hand at the estimated shape code."""
 from __future__ import annotations
 
+import os
+
 import torch
 import torch.nn as nn
 
@@ -29,6 +31,72 @@ class _FrontEndSlot:
             from .frame_frontend import DepthFrontEnd
             self.front = DepthFrontEnd.from_cfg(self.cfg)
         self.front.fill(data)
+
+
+class _HandSequence:
+    """One hand sequence being tracked: everything HandTrackModel carries from a frame to the next.  `forward` drives one,
+    `forward_batch` one per sequence of its group: `step` runs a frame up to the pose optimiser, the caller runs the optimiser
+    (`optimize`, or one `optimize_batch` for the group), `settle` takes its result.  `volume` / `voxel_scale` (the sequence's
+    own volume), `beta` (the hand model's registered shape) and `history` (the shape optimiser's bone lengths so far) are the
+    group's: `forward` keeps them in the optimisers themselves."""
+
+    def __init__(self, model, frames, flag_dict, graph_ok, ik_graph_ok):
+        self.model, self.flag_dict, self.graph_ok, self.ik_graph_ok = model, flag_dict, graph_ok, ik_graph_ok
+        self.rets = []
+        self.last_kp = self.prev_theta = self.shape_code = self.palm = self.volume = self.voxel_scale = None
+        self.beta = getattr(getattr(model.optimizer, "mano_layer_right", None), "registered_beta", None)
+        self.history = None if model.opt_shape is None else model.opt_shape.old_pred_length
+        if model.opt_shape is not None:  # the zero shape's rest hand until the first estimate (:150-152)
+            self.palm = model._shaped_palm_template(torch.zeros((1, model.opt_shape.optimize_dim), device=model.device))
+        elif len(frames):
+            self.palm = frames[0]["gt_hand_pose"]["palm_template"].to(model.device).float()
+
+    def step(self, i, data):
+        """Frame i up to the pose optimiser -> (ret, the cloud's centre, optimize()'s arguments by name and in its positional
+        order; None where the pose optimiser does not run)."""
+        m = self.model
+        data["pred_palm_template"] = self.palm
+        m._front_end.complete(data, "hand_points")
+        points = data["hand_points"].to(m.device, non_blocking=True).float()
+        centre = points.mean(dim=-2, keepdim=True)
+        if self.last_kp is not None:
+            data["jittered_hand_kp"] = self.last_kp + centre  # stays on the device: no host sync between frames
+        if self.graph_ok:
+            ret = m._graph_step(points, data["jittered_hand_kp"].to(m.device).float(), self.palm, self.flag_dict)
+        else:
+            ret = m.handnet(data, self.flag_dict)
+        if not m.use_optimization and m.IKnet is None:
+            return ret, centre, None
+        ret["baseline_pred_kp"] = ret["pred_kp"].clone()
+        if not m.use_optimization:  # IKNet's pose drives the hand model (track_network.py:196-200, hand_network.py:313-318)
+            m._iknet(ret, data, self.palm, self.ik_graph_ok)
+            ret["pred_kp"] = m.IKnet.pose_keypoints(ret["raw_quat"], ret["global_pose"], data.get("pred_beta"))
+            return ret, centre, None
+        # track_network.py:142-156, :203-211
+        if m.opt_shape is not None:  # :174-193: the template takes effect from the next frame on
+            if m._shape_due(i):
+                self.shape_code = m.opt_shape.optimize(ret["baseline_pred_kp"], use_old=m.shape_mode == 3).clone()
+                self.palm = m._shaped_palm_template(self.shape_code)
+            data["pred_beta"] = self.shape_code
+            ret["pred_beta"] = self.shape_code
+        if m.IKnet is not None:
+            theta0, pose0 = m._iknet(ret, data, self.palm, self.ik_graph_ok)
+        else:  # (without IKNet: the stand-in for its two outputs)
+            theta0, pose0 = m._pose_init(ret["baseline_pred_kp"], self.prev_theta)
+        obj_pose = data["pred_obj_pose"] if (m.use_pred_obj_pose and "pred_obj_pose" in data) else data["gt_obj_pose"]
+        return ret, centre, dict(init_mano=theta0, init_hand_pose=pose0, init_kp=ret["baseline_pred_kp"], last_frame_kp=self.last_kp,
+                                 vis_mask=ret["pred_kp_vis_mask"], init_obj_pose=obj_pose, hand_shape=data.get("pred_beta"),
+                                 projection=data["projection"], background_mask=data["background_mask"])
+
+    def settle(self, ret, centre, optimum):
+        """Ends the frame `step` began.  optimum: the pose optimiser's (keypoints, pose code, rotation, translation), or None."""
+        if optimum is not None:
+            kp, theta, rot, trans = optimum
+            ret["pred_kp"], ret["MANO_theta"] = kp, theta
+            ret["global_pose"] = {"rotation": rot.unsqueeze(0), "translation": trans.unsqueeze(-1)}
+            self.prev_theta = theta
+        self.last_kp = (ret["pred_kp"] - centre).clone()
+        self.rets.append(ret)
 
 
 class HandTrackModel(nn.Module):
@@ -190,73 +258,47 @@ class HandTrackModel(nn.Module):
     def _shape_due(self, i):
         return (self.shape_mode == 1 and i == 0) or (self.shape_mode in (2, 3) and i % 10 == 0)
 
-    def forward(self, input, flag_dict):
+    def _begin_tracking(self, flag_dict):
+        """What a tracking call sets before its first frame -> (graph_ok, ik_graph_ok): may HandTrackNet / IKNet replay graphs."""
         flag_dict["track_flag"] = True
         assert flag_dict["test_flag"]
         flag_dict["opt_flag"] = self.use_optimization
-        if self.opt_shape is not None:  # the zero shape's rest hand until the first estimate (:150-152)
-            palm_template = self._shaped_palm_template(torch.zeros((1, self.opt_shape.optimize_dim), device=self.device))
-            shape_code = None
-        else:
-            palm_template = input[0]["gt_hand_pose"]["palm_template"].to(self.device).float()
-        last_kp = None
-        rets = []
-        graph_ok = (self.use_graph and pointnet_utils.fused_backend() is not None and not self.training
-                    and not torch.is_grad_enabled() and torch.device(self.device).type == "cuda")
-        # (IKNet's graph needs no fused HandTrackNet backend: its own kernels and the device Kabsch)
-        ik_graph_ok = (self.use_graph and not self.training and not torch.is_grad_enabled() and torch.device(self.device).type == "cuda")
         if self.use_optimization or self.IKnet is not None:
             flag_dict["IKNet_flag"] = True  # HandTrackNet also returns the keypoint visibility mask (hand_network.py:149-155)
+        # (IKNet's graph needs no fused HandTrackNet backend: its own kernels and the device Kabsch)
+        ik_graph_ok = self.use_graph and not self.training and not torch.is_grad_enabled() and torch.device(self.device).type == "cuda"
+        return ik_graph_ok and pointnet_utils.fused_backend() is not None, ik_graph_ok
+
+    def _sequence_volume(self, frame0, built):
+        """Loads the volume of a sequence whose first frame is `frame0` into the pose optimiser -> (volume on the device,
+        voxel_scale).  `built` maps id(volume tensor) to its device copy: sequences of a group that hand over one tensor share it
+        (the optimiser then keeps the volume loaded last: optimize_batch reads each call's own)."""
+        opt = self.optimizer
+        if "sdf_volume" in frame0:
+            src, scale = frame0["sdf_volume"], frame0.get("voxel_scale")
+            if id(src) in built:
+                return built[id(src)][1], opt.voxel_scale if scale is None else float(scale)
+            opt.load_volume(src, scale)
+            built[id(src)] = (src, opt.sdf_volume)
+        elif not _load_mesh_volume(opt, frame0, self.device) and opt.sdf_volume is None:
+            raise RuntimeError("use_optimization: no SDF volume (decoding it from a DeepSDF latent needs the checkpoints); "
+                               "put 'sdf_volume' / 'voxel_scale', or the object's mesh as 'obj_mesh' ({'vertices', 'faces'}) "
+                               "or 'obj_mesh_path', into the sequence's first frame")
+        return opt.sdf_volume, opt.voxel_scale
+
+    def forward(self, input, flag_dict):
+        seq = _HandSequence(self, input, flag_dict, *self._begin_tracking(flag_dict))
         if self.use_optimization:
-            if "sdf_volume" in input[0]:
-                self.optimizer.load_volume(input[0]["sdf_volume"], input[0].get("voxel_scale"))
-            elif not _load_mesh_volume(self.optimizer, input[0], self.device) and self.optimizer.sdf_volume is None:
-                raise RuntimeError("use_optimization: no SDF volume (decoding it from a DeepSDF latent needs the checkpoints); "
-                                   "put 'sdf_volume' / 'voxel_scale', or the object's mesh as 'obj_mesh' ({'vertices', 'faces'}) "
-                                   "or 'obj_mesh_path', into the sequence's first frame")
-        prev_theta = None
+            self._sequence_volume(input[0], {})
         for i, data in enumerate(input):
-            data["pred_palm_template"] = palm_template
-            self._front_end.complete(data, "hand_points")
-            points = data["hand_points"].to(self.device, non_blocking=True).float()
-            centre = points.mean(dim=-2, keepdim=True)
-            if last_kp is not None:
-                data["jittered_hand_kp"] = last_kp + centre  # stays on the device: no host sync between frames
-            if graph_ok:
-                ret = self._graph_step(points, data["jittered_hand_kp"].to(self.device).float(), palm_template, flag_dict)
-            else:
-                ret = self.handnet(data, flag_dict)
-            if self.use_optimization or self.IKnet is not None:
-                ret["baseline_pred_kp"] = ret["pred_kp"].clone()
-            if self.use_optimization:  # track_network.py:142-156, :203-211
-                if self.opt_shape is not None:  # :174-193: the template takes effect from the next frame on
-                    if self._shape_due(i):
-                        shape_code = self.opt_shape.optimize(ret["baseline_pred_kp"], use_old=self.shape_mode == 3).clone()
-                        palm_template = self._shaped_palm_template(shape_code)
-                    data["pred_beta"] = shape_code
-                    ret["pred_beta"] = shape_code
-                if self.IKnet is not None:
-                    theta0, pose0 = self._iknet(ret, data, palm_template, ik_graph_ok)
-                else:  # (without IKNet: the stand-in for its two outputs)
-                    theta0, pose0 = self._pose_init(ret["baseline_pred_kp"], prev_theta)
-                obj_pose = data["pred_obj_pose"] if (self.use_pred_obj_pose and "pred_obj_pose" in data) else data["gt_obj_pose"]
-                kp, theta, rot, trans = self.optimizer.optimize(theta0, pose0, ret["baseline_pred_kp"], last_kp, ret["pred_kp_vis_mask"],
-                                                                obj_pose, data.get("pred_beta"), data["projection"], data["background_mask"])
-                ret["pred_kp"], ret["MANO_theta"] = kp, theta
-                ret["global_pose"] = {"rotation": rot.unsqueeze(0), "translation": trans.unsqueeze(-1)}
-                prev_theta = theta
-            elif self.IKnet is not None:  # track_network.py:196-200, hand_network.py:313-318
-                self._iknet(ret, data, palm_template, ik_graph_ok)
-                ret["pred_kp"] = self.IKnet.pose_keypoints(ret["raw_quat"], ret["global_pose"], data.get("pred_beta"))
-            last_kp = (ret["pred_kp"] - centre).clone()
-            rets.append(ret)
-        return rets
+            ret, centre, call = seq.step(i, data)
+            seq.settle(ret, centre, None if call is None else self.optimizer.optimize(*call.values()))
+        return seq.rets
 
     def forward_batch(self, inputs, flag_dict):
         """`forward` for S sequences in lockstep.  At frame index t every sequence that still has a frame t runs its own
-        HandTrackNet step, shape estimate and IKNet / `_pose_init` -- forward()'s calls in forward()'s order, on that sequence's
-        own carried state (last keypoints, previous pose code, palm template, shape code, the shape optimiser's history, the hand
-        model's registered shape, the object's volume) -- and then ONE `gf_optimize_hand_pose.optimize_batch` call serves all of
+        HandTrackNet step, shape estimate and IKNet / `_pose_init` -- `_HandSequence.step`, which is what `forward` runs, on that
+        sequence's own carried state -- and then ONE `gf_optimize_hand_pose.optimize_batch` call serves all of
         them: per iteration one evaluation launch over a (candidates, sequence) grid and one update launch with a workgroup per
         sequence, instead of S times two.  (A hand model with MANO entries runs that call in lockstep only with
         cfg['opt']['lockstep_mano']; without it optimize_batch runs optimize() per sequence.)  Sequences shorter than the longest
@@ -265,91 +307,36 @@ class HandTrackModel(nn.Module):
         sequence alone on a tracker in this one's state at the call.  Without `use_optimization` it is `forward` per sequence."""
         if not self.use_optimization:
             return [self.forward(seq, flag_dict) for seq in inputs]
-        from types import SimpleNamespace
-        flag_dict["track_flag"] = True
-        assert flag_dict["test_flag"]
-        flag_dict["opt_flag"] = True
-        flag_dict["IKNet_flag"] = True
-        graph_ok = (self.use_graph and pointnet_utils.fused_backend() is not None and not self.training
-                    and not torch.is_grad_enabled() and torch.device(self.device).type == "cuda")
-        ik_graph_ok = (self.use_graph and not self.training and not torch.is_grad_enabled() and torch.device(self.device).type == "cuda")
-        opt, hm = self.optimizer, self.optimizer.mano_layer_right
+        graph_flags = self._begin_tracking(flag_dict)
+        opt, shape, hm = self.optimizer, self.opt_shape, self.optimizer.mano_layer_right
         has_reg = hasattr(hm, "registered_beta")
         S = len(inputs)
-        seqs, rets, built = [], [[] for _ in range(S)], {}
-        for seq in inputs:
-            st = SimpleNamespace(last_kp=None, prev_theta=None, shape_code=None, palm=None, volume=None, voxel_scale=None,
-                                 beta=getattr(hm, "registered_beta", None),
-                                 history=None if self.opt_shape is None else self.opt_shape.old_pred_length)
-            seqs.append(st)
-            if not len(seq):
-                continue
-            if self.opt_shape is not None:
-                st.palm = self._shaped_palm_template(torch.zeros((1, self.opt_shape.optimize_dim), device=self.device))
-            else:
-                st.palm = seq[0]["gt_hand_pose"]["palm_template"].to(self.device).float()
-            # the volume forward() would load; sequences that hand over one tensor share its device copy
-            src = seq[0].get("sdf_volume")
-            if src is not None and id(src) in built:
-                st.volume, st.voxel_scale = built[id(src)][1], seq[0].get("voxel_scale")
-                st.voxel_scale = opt.voxel_scale if st.voxel_scale is None else float(st.voxel_scale)
-                continue
-            if src is not None:
-                opt.load_volume(src, seq[0].get("voxel_scale"))
-                built[id(src)] = (src, opt.sdf_volume)
-            elif not _load_mesh_volume(opt, seq[0], self.device) and opt.sdf_volume is None:
-                raise RuntimeError("use_optimization: no SDF volume (decoding it from a DeepSDF latent needs the checkpoints); "
-                                   "put 'sdf_volume' / 'voxel_scale', or the object's mesh as 'obj_mesh' ({'vertices', 'faces'}) "
-                                   "or 'obj_mesh_path', into the sequence's first frame")
-            st.volume, st.voxel_scale = opt.sdf_volume, opt.voxel_scale
+        seqs, built = [_HandSequence(self, seq, flag_dict, *graph_flags) for seq in inputs], {}
+        for st, seq in zip(seqs, inputs):
+            if len(seq):
+                st.volume, st.voxel_scale = self._sequence_volume(seq[0], built)
         for t in range(max((len(seq) for seq in inputs), default=0)):
             live = [k for k in range(S) if t < len(inputs[k])]
-            calls, centres = [None] * S, {}
+            calls, steps = [None] * S, {}
             for k in live:
-                st, data = seqs[k], inputs[k][t]
+                # the hand model's registered shape and the shape optimiser's history belong to shared objects: each sequence
+                # puts its own in for its step and takes the history back
+                st = seqs[k]
                 if has_reg:
                     hm.registered_beta = st.beta
-                if self.opt_shape is not None:
-                    self.opt_shape.old_pred_length = st.history
-                data["pred_palm_template"] = st.palm
-                self._front_end.complete(data, "hand_points")
-                points = data["hand_points"].to(self.device, non_blocking=True).float()
-                centres[k] = centre = points.mean(dim=-2, keepdim=True)
-                if st.last_kp is not None:
-                    data["jittered_hand_kp"] = st.last_kp + centre
-                if graph_ok:
-                    ret = self._graph_step(points, data["jittered_hand_kp"].to(self.device).float(), st.palm, flag_dict)
-                else:
-                    ret = self.handnet(data, flag_dict)
-                ret["baseline_pred_kp"] = ret["pred_kp"].clone()
-                if self.opt_shape is not None:
-                    if self._shape_due(t):
-                        st.shape_code = self.opt_shape.optimize(ret["baseline_pred_kp"], use_old=self.shape_mode == 3).clone()
-                        st.palm = self._shaped_palm_template(st.shape_code)
-                        st.history = self.opt_shape.old_pred_length
-                    data["pred_beta"] = st.shape_code
-                    ret["pred_beta"] = st.shape_code
-                if self.IKnet is not None:
-                    theta0, pose0 = self._iknet(ret, data, st.palm, ik_graph_ok)
-                else:
-                    theta0, pose0 = self._pose_init(ret["baseline_pred_kp"], st.prev_theta)
-                obj_pose = data["pred_obj_pose"] if (self.use_pred_obj_pose and "pred_obj_pose" in data) else data["gt_obj_pose"]
-                calls[k] = dict(init_mano=theta0, init_hand_pose=pose0, init_kp=ret["baseline_pred_kp"], last_frame_kp=st.last_kp,
-                                vis_mask=ret["pred_kp_vis_mask"], init_obj_pose=obj_pose, hand_shape=data.get("pred_beta"),
-                                projection=data["projection"], background_mask=data["background_mask"], sdf_volume=st.volume,
-                                voxel_scale=st.voxel_scale)
-                rets[k].append(ret)
+                if shape is not None:
+                    shape.old_pred_length = st.history
+                ret, centre, call = st.step(t, inputs[k][t])
+                if shape is not None:
+                    st.history = shape.old_pred_length
+                steps[k] = (ret, centre)
+                calls[k] = dict(call, sdf_volume=st.volume, voxel_scale=st.voxel_scale)
             outs = opt.optimize_batch(calls)
             for k in live:
-                st, ret = seqs[k], rets[k][-1]
-                kp, theta, rot, trans = outs[k]
-                ret["pred_kp"], ret["MANO_theta"] = kp, theta
-                ret["global_pose"] = {"rotation": rot.unsqueeze(0), "translation": trans.unsqueeze(-1)}
-                st.prev_theta = theta
-                st.last_kp = (ret["pred_kp"] - centres[k]).clone()
+                seqs[k].settle(*steps[k], outs[k])
                 if calls[k]["hand_shape"] is not None and getattr(hm, "num_betas", 0) > 0:  # what optimize() registers
-                    st.beta = torch.as_tensor(calls[k]["hand_shape"]).reshape(1, -1).to(self.device).float()
-        return rets
+                    seqs[k].beta = torch.as_tensor(calls[k]["hand_shape"]).reshape(1, -1).to(self.device).float()
+        return [st.rets for st in seqs]
 
     def _iknet(self, ret, data, palm_template, graph_ok):
         data["baseline_pred_kp"] = ret["baseline_pred_kp"]
@@ -615,6 +602,83 @@ class HandTrackModel(nn.Module):
         return [(outs[k], ret_dict_lsts[k]) for k in range(S)]
 
 
+class _ObjSequence:
+    """One object sequence being tracked: the pose dict carried from frame to frame (`last`), the results (`rets`), the observed
+    surface (or None) and the refinement's stats.  `forward` drives one, `forward_batch` one per sequence of its group: per frame
+    `begin`, the caller's optimiser call (`optimize`, or one `optimize_batch` for the group), `accept`; `finish` at the end.  The
+    volume is the caller's: `forward` reads the optimiser's, a group keeps one per sequence."""
+
+    def __init__(self, model, frames):
+        self.model, self.frames = model, frames
+        self.last, self.surf = None, None
+        self.rets, self.refined = [], []
+
+    def begin(self, data):
+        """Completes a frame for the optimiser: frame 0 starts from its jittered pose, frame t from frame t-1's result, which is
+        also the pose dict's `prev_*` entries (:353-370)."""
+        m = self.model
+        if m.fuse_depth or m.render_model:  # one upload serves the front end, the fusion and the rendering's comparison
+            for key in ("depth", "seg"):
+                if isinstance(data[key], torch.Tensor):
+                    data[key] = data[key].to(m.device, non_blocking=True)
+        first = self.last is None
+        if first:
+            jp = data["jittered_obj_pose"]
+            jp["translation"] = jp["translation"].float().reshape(1, 3, 1).to(m.device)
+            jp["rotation"] = jp["rotation"].float().reshape(1, 3, 3).to(m.device)
+            jp["prev_translation"], jp["prev_rotation"] = jp["translation"], jp["rotation"]
+            self.last = {"translation": jp["translation"], "rotation": jp["rotation"]}
+        else:
+            data["jittered_obj_pose"] = self.last
+        m._front_end.complete(data, "obj_points")
+        if first and m.accumulate_surface:  # the pose the tracking starts from (load_obj, :153-158)
+            cloud0 = data["obj_points"].float().to(m.device)
+            self.surf = m._new_surface(cloud0).start(cloud0, data["jittered_obj_pose"])
+
+    def accept(self, data, ret, corner_volume, voxel_scale):
+        """Takes the frame's tracked (and, with opt.refine_pose, refined) pose; the volume is the one it was tracked against."""
+        m = self.model
+        if m.refine_pose:
+            self.refined.append(ret.pop("refine_stats"))
+        if self.surf is not None:
+            self.surf.add(data["obj_points"].float().to(m.device), ret, corner_volume, voxel_scale)
+        last = self.last
+        last["prev_translation"], last["prev_rotation"] = last["translation"], last["rotation"]  # last frame's pose
+        last["translation"], last["rotation"] = ret["translation"], ret["rotation"]            # current frame's pose
+        self.rets.append(ret)
+
+    def finish(self, volume, corner_volume, voxel_scale, fused_state, flag_dict, shared_meshes=None):
+        """What the switches attach to rets[0] at the end of a sequence (one that has frames), read off its final volume."""
+        m, rets = self.model, self.rets
+        if self.refined:
+            rets[0]["obj_refine"] = torch.stack(self.refined)  # (frames, 8): hotrack_amd.sdf.obj_refine's stats, on the device
+        if fused_state is not None:
+            rets[0]["obj_fused"] = fused_state
+        if m.render_model:  # every frame with its tracked pose; one launch per sequence (no batched raycast: DESIGN.md 8m)
+            m._attach_render(self.frames, rets, volume, voxel_scale, fused_state is not None, flag_dict)
+        if self.surf is not None:
+            rets[0]["obj_surface"] = m._surface_entry(self.surf, corner_volume, voxel_scale)
+        if m.extract_mesh:
+            m._attach_mesh(self.frames, rets, volume, voxel_scale, flag_dict, shared_meshes)
+
+
+def _require_frame_keys(feature, frames, where):
+    """`feature` (a switch's name) reads every frame's depth image: raises for the first of `frames` that lacks a key it needs.
+    `where` goes in front of the frame's index ('' or 'sequence k, ')."""
+    for t, data in enumerate(frames):
+        missing = [key for key in ("depth", "seg", "intrinsics") if key not in data]
+        if missing:
+            raise KeyError(f"{feature} reads the observed depth frames: the sequence's frames must carry 'depth', 'seg' and "
+                           f"'intrinsics' (as the --from_depth frames do); {where}frame {t} ({data['file_name'][0]}) lacks {missing}")
+
+
+def _sequence_stem(input, save_folder):
+    """<save_folder>/<sequence>, the stem of every file saved for a sequence; makes the folder."""
+    name = os.path.dirname(input[0]["file_name"][0]) or input[0]["file_name"][0]
+    os.makedirs(save_folder, exist_ok=True)
+    return os.path.join(save_folder, name.replace("/", "_"))
+
+
 class ObjTrackModel_Optimization(nn.Module):
     """Per-sequence object-pose tracking by gradient-free particle optimisation against the object's SDF volume
     (counterpart of the reference's ObjTrackModel_Optimization, track_network.py:322-383; BASELINE configs[3], stage 1).
@@ -627,6 +691,15 @@ class ObjTrackModel_Optimization(nn.Module):
     over (`input[0]['sdf_volume']`, `['voxel_scale']`) or hands over the object's triangle mesh (`input[0]['obj_mesh']` =
     {'vertices', 'faces'} or `['obj_mesh_path']`), from which the volume is built once (models/mesh_sdf.py, the reference's
     load_obj_oracle)."""
+
+    # The switches' defaults, for a tracker built without __init__ or with an attribute deleted.  __init__ sets them from cfg['opt']
+    # and cfg['save_dir'] and says there what each one does; a *_route has no config key: None (the kernel for GPU tensors),
+    # 'kernel' or 'torch'
+    extract_mesh, extract_mesh_route = False, None
+    fuse_depth, lockstep_fuse, fuse_route = False, False, None
+    render_model, render_occl_margin, render_route = False, 0.01, None
+    refine_pose, refine_route = False, None
+    save_folder = None
 
     def __init__(self, cfg):
         super().__init__()
@@ -641,7 +714,7 @@ class ObjTrackModel_Optimization(nn.Module):
         # opt.accumulate_surface: keep each sequence's observed surface (models/obs_surface.py); the poses do not depend on it
         self.accumulate_surface = bool((cfg.get("opt") or {}).get("accumulate_surface", False))
         # opt.extract_mesh: at the end of a sequence extract the mesh of its SDF volume (models/mesh_sdf.volume_to_mesh); the poses
-        # do not depend on it.  extract_mesh_route: None (the kernel for a GPU volume), 'kernel' or 'torch'
+        # do not depend on it
         self.extract_mesh = bool((cfg.get("opt") or {}).get("extract_mesh", False))
         self.extract_mesh_route = None
         # opt.fuse_depth: fuse every tracked depth frame into the sequence's own copy of the volume (models/shape_fusion.py,
@@ -655,7 +728,7 @@ class ObjTrackModel_Optimization(nn.Module):
         self.fuse_every = int(opt_cfg.get("fuse_every", 10))
         self.fuse_trunc = float(opt_cfg.get("fuse_trunc", 5.0))
         self.fuse_prior_weight = float(opt_cfg.get("fuse_prior_weight", 8.0))
-        self.fuse_route = None  # None (the kernel for a GPU volume), 'kernel' or 'torch'
+        self.fuse_route = None
         # opt.lockstep_fuse: allow opt.fuse_depth in forward_batch.  Opt-in, for memory: every sequence of a group then owns a copy
         # of the volume and its weights, and from its first flush on a corner layout (201^3 fp16: 49 MB + 130 MB per sequence)
         self.lockstep_fuse = bool(opt_cfg.get("lockstep_fuse", False))
@@ -664,14 +737,13 @@ class ObjTrackModel_Optimization(nn.Module):
         # one launch and compare the maps with the observed frames in a second (models/volume_render.py,
         # hotrack_amd/csrc/sdf_raycast.hip); the poses do not depend on it.  render_occl_margin (metres) is a choice, like
         # contact_threshold: how far in front of the model a non-object pixel must lie to count as an occluder
-        # (hotrack_amd.sdf.OCCL_MARGIN says why 1 cm).  render_route: None (the kernels for a GPU volume), 'kernel' or 'torch'
+        # (hotrack_amd.sdf.OCCL_MARGIN says why 1 cm)
         self.render_model = bool(opt_cfg.get("render_model", False))
         self.render_occl_margin = float(opt_cfg.get("render_occl_margin", 0.01))
         self.render_route = None
         # opt.refine_pose: after every frame's particle search, refine_iters damped Gauss-Newton steps on the volume inside a band of
         # refine_band metres (gf_optimize_obj.refine, hotrack_amd/csrc/sdf_refine.hip): one more launch per frame or group step.  The
-        # refined pose is the frame's pose: the next frame starts from it and every later stage reads it.  refine_route: None (the
-        # kernel for GPU tensors), 'kernel' or 'torch'.  Off: no new code runs
+        # refined pose is the frame's pose: the next frame starts from it and every later stage reads it.  Off: no new code runs
         self.refine_pose = bool(opt_cfg.get("refine_pose", False))
         self.refine_route = None
         self.surface_seed = 0  # every sequence draws from a generator of its own with this seed: alone or in a group, the same surface
@@ -696,133 +768,79 @@ class ObjTrackModel_Optimization(nn.Module):
         the sequence's SDF volume goes into rets[0]['obj_info'] = {'recon_path', 'recon_mesh': {'vertices', 'faces'}}.  With
         --save and a save directory the mesh is written as <sequence>_recon.ply and 'recon_path' names the file (else None).
         `shared` maps id(volume) to a mesh already extracted: sequences of a group that share a volume share one extraction."""
-        import os
         from . import mesh_sdf
         hit = None if shared is None else shared.get(id(volume))
         if hit is None:
-            verts, faces = mesh_sdf.volume_to_mesh(volume, voxel_scale, 0.0, route=getattr(self, "extract_mesh_route", None))
+            verts, faces = mesh_sdf.volume_to_mesh(volume, voxel_scale, 0.0, route=self.extract_mesh_route)
             hit = (volume, {"vertices": verts, "faces": faces})  # (the volume is kept with the mesh: the key's id stays its)
             if shared is not None:
                 shared[id(volume)] = hit
         path = None
-        if flag_dict.get("save_flag") and getattr(self, "save_folder", None):
-            name = os.path.dirname(input[0]["file_name"][0]) or input[0]["file_name"][0]
-            os.makedirs(self.save_folder, exist_ok=True)
-            path = os.path.join(self.save_folder, name.replace("/", "_") + "_recon.ply")
+        if flag_dict.get("save_flag") and self.save_folder:
+            path = _sequence_stem(input, self.save_folder) + "_recon.ply"
             mesh_sdf.save_mesh(path, hit[1]["vertices"], hit[1]["faces"])
         rets[0]["obj_info"] = {"recon_path": path, "recon_mesh": hit[1]}
 
-    def _check_render_frames(self, frame0, where="frame 0"):
-        """opt.render_model, before any work: the frames must carry what the comparison reads."""
-        missing = [k for k in ("depth", "seg", "intrinsics") if k not in frame0]
-        if missing:
-            raise KeyError(f"opt.render_model compares the rendered model with the observed depth frames: the sequence's frames must "
-                           f"carry 'depth', 'seg' and 'intrinsics' (as the --from_depth frames do); {where} "
-                           f"({frame0['file_name'][0]}) lacks {missing}")
-
-    def _attach_render(self, input, rets, kept, volume, voxel_scale, fused, flag_dict):
-        """opt.render_model, at the end of a sequence: `kept` holds every frame and its tracked pose (device references).  All frames
-        are rendered in one launch and compared in a second (volume_render.model_frame_fit); a fused volume is marched with
+    def _attach_render(self, input, rets, volume, voxel_scale, fused, flag_dict):
+        """opt.render_model, at the end of a sequence: `input` holds every frame, `rets` its tracked pose (device references).  All
+        frames are rendered in one launch and compared in a second (volume_render.model_frame_fit); a fused volume is marched with
         step_scale 0.8, because a projective TSDF overestimates the distance at grazing angles.
         rets[0]['obj_render'] = {'depth' (F,H,W), 'normal' (F,H,W,3), 'stats' (F,4), 'columns' (3,), 'skipped' ()}; with --save and
         a save directory the last frame's maps are written as <sequence>_model_depth.png / _model_normal.png."""
-        import os
         from . import volume_render
         fe = self._fuse_frontend
-        out = volume_render.model_frame_fit(volume, voxel_scale, [d for d, _ in kept], [r for _, r in kept],
+        out = volume_render.model_frame_fit(volume, voxel_scale, list(input), list(rets),
                                             obj_class=tuple(fe.get("obj_class", (1, 255))), flip_yz=bool(fe.get("flip_yz", False)),
-                                            step_scale=0.8 if fused else 1.0, occl_margin=getattr(self, "render_occl_margin", 0.01),
-                                            route=getattr(self, "render_route", None))
+                                            step_scale=0.8 if fused else 1.0, occl_margin=self.render_occl_margin,
+                                            route=self.render_route)
         rets[0]["obj_render"] = out
-        if flag_dict.get("save_flag") and getattr(self, "save_folder", None):
-            name = os.path.dirname(input[0]["file_name"][0]) or input[0]["file_name"][0]
-            os.makedirs(self.save_folder, exist_ok=True)
-            stem = os.path.join(self.save_folder, name.replace("/", "_"))
+        if flag_dict.get("save_flag") and self.save_folder:
+            stem = _sequence_stem(input, self.save_folder)
             out["paths"] = (volume_render.save_depth_png(stem + "_model_depth.png", out["depth"][-1]),
                             volume_render.save_normal_png(stem + "_model_normal.png", out["normal"][-1]))
 
-    def forward(self, input, flag_dict):
+    def _begin_tracking(self, sequences, flag_dict):
+        """Before any work: every frame of `sequences` ({where: frames}) must carry what the switches that read the observed depth
+        frames need."""
         flag_dict["track_flag"] = True
         assert flag_dict["test_flag"]
-        render = getattr(self, "render_model", False) and len(input) > 0
-        if render:
-            self._check_render_frames(input[0])
-        kept = []
-        if "sdf_volume" in input[0]:
-            self.optimizer.load_volume(input[0]["sdf_volume"], input[0].get("voxel_scale"))
-        elif not _load_mesh_volume(self.optimizer, input[0], self.device) and self.optimizer.sdf_volume is None:
-            raise RuntimeError("no SDF volume: decoding it from a DeepSDF latent needs the checkpoints (out of scope); "
-                               "put 'sdf_volume' / 'voxel_scale', or the object's mesh as 'obj_mesh' ({'vertices', 'faces'}) or "
-                               "'obj_mesh_path', into the sequence's first frame")
-        last = None
-        rets = []
-        refined = []
-        surf = None
-        fusion = self._new_fusion(input) if getattr(self, "fuse_depth", False) and len(input) else None
+        for feature, on in (("opt.render_model", self.render_model), ("opt.fuse_depth", self.fuse_depth)):
+            if on:
+                for where, frames in sequences.items():
+                    _require_frame_keys(feature, frames, where)
+
+    def forward(self, input, flag_dict):
+        self._begin_tracking({"": input}, flag_dict)
+        opt = self.optimizer
+        self._sequence_volume(input[0], {})
+        seq = _ObjSequence(self, input)
+        fusion = self._new_fusion() if self.fuse_depth else None
         for data in input:
-            if fusion is not None or render:  # one upload serves the front end, the fusion and the rendering's comparison
-                for key in ("depth", "seg"):
-                    if key in data and isinstance(data[key], torch.Tensor):
-                        data[key] = data[key].to(self.device, non_blocking=True)
-            if last is not None:
-                data["jittered_obj_pose"] = last
-            else:
-                jp = data["jittered_obj_pose"]
-                jp["translation"] = jp["translation"].float().reshape(1, 3, 1).to(self.device)
-                jp["rotation"] = jp["rotation"].float().reshape(1, 3, 3).to(self.device)
-                jp["prev_translation"], jp["prev_rotation"] = jp["translation"], jp["rotation"]
-                last = {"translation": jp["translation"], "rotation": jp["rotation"]}
-            self._front_end.complete(data, "obj_points")
-            if self.accumulate_surface and surf is None:  # frame 0, the pose tracking starts from (load_obj, :153-158)
-                cloud0 = data["obj_points"].float().to(self.device)
-                surf = self._new_surface(cloud0).start(cloud0, data["jittered_obj_pose"])
-            ret = self.optimizer.optimize(data["obj_points"], data["jittered_obj_pose"], data["category"][0],
-                                          data["file_name"][0], data.get("projection"))
-            if getattr(self, "refine_pose", False):
-                ret = self.optimizer.refine(data["obj_points"], ret, route=getattr(self, "refine_route", None))
-                refined.append(ret.pop("refine_stats"))
-            if surf is not None:
-                surf.add(data["obj_points"].float().to(self.device), ret, self.optimizer._corners, self.optimizer.voxel_scale)
-            last["prev_translation"], last["prev_rotation"] = last["translation"], last["rotation"]  # last frame's pose
-            last["translation"], last["rotation"] = ret["translation"], ret["rotation"]            # current frame's pose
-            rets.append(ret)
-            if render:
-                self._check_render_frames(data, f"frame {len(rets) - 1}")
-                kept.append((data, ret))
+            seq.begin(data)
+            ret = opt.optimize(data["obj_points"], data["jittered_obj_pose"], data["category"][0], data["file_name"][0],
+                               data.get("projection"))
+            if self.refine_pose:
+                ret = opt.refine(data["obj_points"], ret, route=self.refine_route)
+            seq.accept(data, ret, opt._corners, opt.voxel_scale)
             if fusion is not None:
-                missing = [k for k in ("depth", "seg", "intrinsics") if k not in data]
-                if missing:
-                    raise KeyError(f"opt.fuse_depth: frame {len(rets) - 1} ({data['file_name'][0]}) carries no {missing}")
                 fusion.push(data, ret)
                 if fusion.due():  # the later frames are tracked against the fused volume (load_volume rebuilds the corner layout)
-                    self.optimizer.load_volume(fusion.flush(), fusion.voxel_scale)
-        if refined:
-            rets[0]["obj_refine"] = torch.stack(refined)  # (frames, 8): hotrack_amd.sdf.obj_refine's stats, on the device
-        if fusion is not None:
-            if fusion.pending:
-                self.optimizer.load_volume(fusion.flush(), fusion.voxel_scale)
-            rets[0]["obj_fused"] = fusion.state()
-        if render:  # (after the last flush: the fused volume, else the loaded one)
-            self._attach_render(input, rets, kept, self.optimizer.sdf_volume, self.optimizer.voxel_scale, fusion is not None, flag_dict)
-        if surf is not None:
-            rets[0]["obj_surface"] = self._surface_entry(surf, self.optimizer._corners, self.optimizer.voxel_scale)
-        if getattr(self, "extract_mesh", False) and rets:
-            self._attach_mesh(input, rets, self.optimizer.sdf_volume, self.optimizer.voxel_scale, flag_dict)
-        return rets
+                    opt.load_volume(fusion.flush(), fusion.voxel_scale)
+        if fusion is not None and fusion.pending:
+            opt.load_volume(fusion.flush(), fusion.voxel_scale)
+        # (after the last flush: the fused volume, else the loaded one)
+        seq.finish(opt.sdf_volume, opt._corners, opt.voxel_scale, None if fusion is None else fusion.state(), flag_dict)
+        return seq.rets
 
-    def _new_fusion(self, input):
+    def _new_fusion(self):
         """opt.fuse_depth: the VolumeFusion of a sequence whose volume has just been loaded (a clone: the handed-over tensor,
         which a dataset may share between sequences, and a cached mesh volume are never written)."""
         from .shape_fusion import VolumeFusion
-        missing = [k for k in ("depth", "seg", "intrinsics") if k not in input[0]]
-        if missing:
-            raise KeyError(f"opt.fuse_depth fuses depth frames into the object's volume: the sequence's frames must carry 'depth', 'seg' "
-                           f"and 'intrinsics' (as the --from_depth frames do); frame 0 ({input[0]['file_name'][0]}) lacks {missing}")
         fe = self._fuse_frontend
         scale = float(self.optimizer.voxel_scale)
         return VolumeFusion(self.optimizer.sdf_volume, scale, self.fuse_prior_weight, self.fuse_trunc * scale, self.fuse_every,
                             obj_class=tuple(fe.get("obj_class", (1, 255))), flip_yz=bool(fe.get("flip_yz", False)),
-                            route=getattr(self, "fuse_route", None), device=self.device)
+                            route=self.fuse_route, device=self.device)
 
     def _new_fusion_group(self, corner_volumes, voxel_scale):
         """opt.fuse_depth with opt.lockstep_fuse: the VolumeFusionGroup of a lockstep group whose volumes have just been loaded --
@@ -832,7 +850,7 @@ class ObjTrackModel_Optimization(nn.Module):
         scale = float(voxel_scale)
         return VolumeFusionGroup([None if c is None else c.source for c in corner_volumes], scale, self.fuse_prior_weight,
                                  self.fuse_trunc * scale, self.fuse_every, obj_class=tuple(fe.get("obj_class", (1, 255))),
-                                 flip_yz=bool(fe.get("flip_yz", False)), route=getattr(self, "fuse_route", None), device=self.device)
+                                 flip_yz=bool(fe.get("flip_yz", False)), route=self.fuse_route, device=self.device)
 
     def _sequence_volume(self, frame0, built):
         """The volume `forward` would load for a sequence whose first frame is `frame0`, in its lookup layout ->
@@ -851,7 +869,7 @@ class ObjTrackModel_Optimization(nn.Module):
                     raise RuntimeError("no SDF volume: decoding it from a DeepSDF latent needs the checkpoints (out of scope); "
                                        "put 'sdf_volume' / 'voxel_scale', or the object's mesh as 'obj_mesh' ({'vertices', 'faces'}) or "
                                        "'obj_mesh_path', into the sequence's first frame")
-                return opt._corners, opt.voxel_scale  # (as forward: the volume loaded last stays)
+                return opt._corners, opt.voxel_scale  # (the volume loaded last stays)
         hit = built.get(id(src))
         if hit is None:
             opt.load_volume(src, scale)
@@ -869,28 +887,13 @@ class ObjTrackModel_Optimization(nn.Module):
         once per sequence.  inputs: a list of S sequences, each what `forward` takes; sequences shorter than the longest sit
         out once they have ended.  All volumes must share one resolution, dtype and voxel_scale (one launch reads them all).
         Returns a list of S `ret_dict_lst`, bit-equal to S `forward` calls."""
-        fuse = getattr(self, "fuse_depth", False)
-        if fuse and not getattr(self, "lockstep_fuse", False):
+        if self.fuse_depth and not self.lockstep_fuse:
             raise ValueError("opt.fuse_depth for sequences tracked in lockstep needs opt.lockstep_fuse (--lockstep_fuse) as well: a group's "
                              "sequences share volumes, a fused volume belongs to one sequence, so every sequence of the group then owns "
                              "a copy of the volume, its weights and, from its first flush on, the corner layout; or track with "
                              "--seq_batch 1")
-        flag_dict["track_flag"] = True
-        assert flag_dict["test_flag"]
-        render = getattr(self, "render_model", False)
-        if render:  # before any work, as `forward`
-            for k, seq in enumerate(inputs):
-                for t, data in enumerate(seq):
-                    self._check_render_frames(data, f"sequence {k}, frame {t}")
-        if fuse:  # before any work: every frame must carry what the fusion reads
-            for k, seq in enumerate(inputs):
-                for t, data in enumerate(seq):
-                    missing = [key for key in ("depth", "seg", "intrinsics") if key not in data]
-                    if missing:
-                        raise KeyError(f"opt.fuse_depth fuses depth frames into the object's volume: the frames must carry 'depth', 'seg' "
-                                       f"and 'intrinsics' (as the --from_depth frames do); sequence {k}, frame {t} "
-                                       f"({data['file_name'][0]}) lacks {missing}")
-        built, vols, scales = {}, [], []
+        self._begin_tracking({f"sequence {k}, ": seq for k, seq in enumerate(inputs)}, flag_dict)
+        opt, built, vols, scales = self.optimizer, {}, [], []
         for seq in inputs:
             v, s = self._sequence_volume(seq[0], built) if len(seq) else (None, None)
             vols.append(v)
@@ -900,49 +903,24 @@ class ObjTrackModel_Optimization(nn.Module):
             if s != known[0][1]:
                 raise ValueError(f"sequences {known[0][0]} and {k} differ in voxel_scale ({known[0][1]}, {s}): a group tracked in "
                                  "lockstep shares one; track them in separate groups")
+        scale = known[0][1] if known else None
         S = len(inputs)
-        last = [None] * S
-        rets = [[] for _ in range(S)]
-        surfs = [None] * S
-        refined = [[] for _ in range(S)]
-        group = self._new_fusion_group(vols, known[0][1]) if fuse and known else None
+        seqs = [_ObjSequence(self, seq) for seq in inputs]
+        group = self._new_fusion_group(vols, scale) if self.fuse_depth and known else None
         for t in range(max((len(seq) for seq in inputs), default=0)):
             live = [k for k in range(S) if t < len(inputs[k])]
             for k in live:
-                data = inputs[k][t]
-                if group is not None or render:  # one upload serves the front end, the fusion and the rendering's comparison
-                    for key in ("depth", "seg"):
-                        if isinstance(data[key], torch.Tensor):
-                            data[key] = data[key].to(self.device, non_blocking=True)
-                self._front_end.complete(data, "obj_points")
-                if last[k] is not None:
-                    data["jittered_obj_pose"] = last[k]
-                else:
-                    jp = data["jittered_obj_pose"]
-                    jp["translation"] = jp["translation"].float().reshape(1, 3, 1).to(self.device)
-                    jp["rotation"] = jp["rotation"].float().reshape(1, 3, 3).to(self.device)
-                    jp["prev_translation"], jp["prev_rotation"] = jp["translation"], jp["rotation"]
-                    last[k] = {"translation": jp["translation"], "rotation": jp["rotation"]}
-                    if self.accumulate_surface:
-                        cloud0 = data["obj_points"].float().to(self.device)
-                        surfs[k] = self._new_surface(cloud0).start(cloud0, jp)
+                seqs[k].begin(inputs[k][t])
             # (a sequence that has ended keeps its slot, with no cloud and no volume: the launch skips it; an EMPTY sequence
             # has no pose either and borrows a live one's, which comes back unchanged and is dropped)
-            out = self.optimizer.optimize_batch([inputs[k][t]["obj_points"] if t < len(inputs[k]) else None for k in range(S)],
-                                                [last[k] if last[k] is not None else last[live[0]] for k in range(S)],
-                                                [vols[k] if t < len(inputs[k]) else None for k in range(S)], known[0][1])
-            if getattr(self, "refine_pose", False):  # one more launch for the group; a sequence that has ended sits it out too
-                out = self.optimizer.refine_batch([inputs[k][t]["obj_points"] if t < len(inputs[k]) else None for k in range(S)], out,
-                                                  [vols[k] if t < len(inputs[k]) else None for k in range(S)], known[0][1])
-                for k in live:
-                    refined[k].append(out[k].pop("refine_stats"))
+            clouds = [inputs[k][t]["obj_points"] if t < len(inputs[k]) else None for k in range(S)]
+            step_vols = [vols[k] if t < len(inputs[k]) else None for k in range(S)]
+            poses = [inputs[k][t]["jittered_obj_pose"] if t < len(inputs[k]) else seqs[k].last for k in range(S)]
+            out = opt.optimize_batch(clouds, [p if p is not None else poses[live[0]] for p in poses], step_vols, scale)
+            if self.refine_pose:  # one more launch for the group; a sequence that has ended sits it out too
+                out = opt.refine_batch(clouds, out, step_vols, scale)
             for k in live:
-                ret = out[k]
-                if surfs[k] is not None:
-                    surfs[k].add(inputs[k][t]["obj_points"].float().to(self.device), ret, vols[k], known[0][1])
-                last[k]["prev_translation"], last[k]["prev_rotation"] = last[k]["translation"], last[k]["rotation"]
-                last[k]["translation"], last[k]["rotation"] = ret["translation"], ret["rotation"]
-                rets[k].append(ret)
+                seqs[k].accept(inputs[k][t], out[k], vols[k], scale)
             if group is not None:
                 # as `forward`: the frame is pushed with the pose just found; a sequence whose pending frames reach fuse_every, or
                 # whose last frame this was, is flushed -- all of them in ONE launch -- and tracked against its own fused volume
@@ -954,25 +932,12 @@ class ObjTrackModel_Optimization(nn.Module):
                     from hotrack_amd import sdf as _sdf
                     for k, fused in zip(flush, group.flush(flush)):
                         vols[k] = _sdf.CornerVolume(fused)
-                    self.optimizer.forget_volume_tables()  # (they hold the corner layouts just replaced)
-        for k in range(S):
-            if refined[k]:
-                rets[k][0]["obj_refine"] = torch.stack(refined[k])
-            if group is not None and rets[k]:
-                rets[k][0]["obj_fused"] = group.state(k)
-            if render and rets[k]:
-                # every sequence after the group has finished, one launch per sequence as `forward` (a batched, multi-volume
-                # raycast is not built: DESIGN.md 8m); vols[k].source is the sequence's volume, fused if it was
-                self._attach_render(inputs[k], rets[k], list(zip(inputs[k], rets[k])), vols[k].source, known[0][1], group is not None,
-                                    flag_dict)
-            if surfs[k] is not None:
-                rets[k][0]["obj_surface"] = self._surface_entry(surfs[k], vols[k], known[0][1])
-        if getattr(self, "extract_mesh", False):
-            meshes = {}
-            for k in range(S):
-                if rets[k]:
-                    self._attach_mesh(inputs[k], rets[k], vols[k].source, known[0][1], flag_dict, meshes)
-        return rets
+                    opt.forget_volume_tables()  # (they hold the corner layouts just replaced)
+        meshes = {}
+        for k, st in enumerate(seqs):
+            if st.rets:  # vols[k].source is the sequence's volume, fused if it was
+                st.finish(vols[k].source, vols[k], scale, None if group is None else group.state(k), flag_dict, meshes)
+        return [st.rets for st in seqs]
 
     def compute_loss(self, input, ret_dict_lst, flag_dict):
         """The reference's evaluation of a tracked sequence (track_network.py:385-434) next to this project's three figures,
@@ -1076,12 +1041,9 @@ class ObjTrackModel_Optimization(nn.Module):
     def _save_surface(self, input, ret_dict_lst, surface):
         """--save with opt.accumulate_surface: the sequence's pickle (named as the reference names it, track_network.py:446-451)
         with the tracked poses and the observed surface."""
-        import os
         import pickle
-        name = os.path.dirname(input[0]["file_name"][0]) or input[0]["file_name"][0]
-        os.makedirs(self.save_folder, exist_ok=True)
         cpu = lambda v: v.detach().cpu().numpy() if torch.is_tensor(v) else v
-        with open(os.path.join(self.save_folder, name.replace("/", "_") + ".pkl"), "wb") as f:
+        with open(_sequence_stem(input, self.save_folder) + ".pkl", "wb") as f:
             pickle.dump({"CAD_ID": input[0]["category"][0],
                          "pred_obj_poses": [{k: cpu(r[k]) for k in ("rotation", "translation")} for r in ret_dict_lst],
                          "obj_surface": {k: cpu(v) for k, v in surface.items()}}, f)
