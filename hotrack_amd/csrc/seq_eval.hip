@@ -114,9 +114,11 @@ posed_chamfer_sum_kernel(int T, int N, int M, int tilesA, int tilesB, const floa
     out[t] = sa / (float)N + sb / (float)M;
 }
 
-__device__ __forceinline__ float pm_angle(float trace) {
-    return acosf(fminf(fmaxf((trace - 1.f) / 2.f, -1.f), 1.f));
-}
+// clamp to [-1, 1] that keeps a NaN: fminf / fmaxf return the bound instead, and a NaN rotation would read as an angle (0
+// degrees under |cos|, so both accuracy flags set); the reference's torch.clamp keeps it and the flags' comparisons fail
+__device__ __forceinline__ float pm_clamp(float c) { return c < -1.f ? -1.f : (c > 1.f ? 1.f : c); }
+
+__device__ __forceinline__ float pm_angle(float trace) { return acosf(pm_clamp((trace - 1.f) / 2.f)); }
 
 // One thread per frame: out[t] = {tdiff, rdiff (degrees), 5deg5cm, 10deg10cm}.  rot_diff_rad's branches (metrics.py:6-136):
 // axis 0..2 the angle between the chosen columns (|cos| when up/down symmetric), 3 the minimum over identity and the three
@@ -136,7 +138,7 @@ obj_pose_metrics_kernel(int T, const float *__restrict__ gR, const float *__rest
         float d = (c == 0 ? a[0] * b[0] : c == 1 ? a[1] * b[1] : a[2] * b[2]);
         d += (c == 0 ? a[3] * b[3] : c == 1 ? a[4] * b[4] : a[5] * b[5]);
         d += (c == 0 ? a[6] * b[6] : c == 1 ? a[7] * b[7] : a[8] * b[8]);
-        d = fminf(fmaxf(d, -1.f), 1.f);
+        d = pm_clamp(d);
         if (sym) d = fabsf(d);
         rad = acosf(d);
     } else {
