@@ -30,6 +30,7 @@ _lib.pn2x_tail_pose_head_fwd.restype = _ci
 _lib.pn2x_tail_pose_head_bwd.argtypes = [_ci, _ci, _ci] + [_vp] * 6 + [_ci] + [_vp] * 4
 _lib.pn2x_tail_pose_head_bwd.restype = _ci
 _f32 = torch.float32
+LN_BWD_MAX_C = 512  # pn2x_tail_ln_bwd: 8 elements per lane at the most (the forward takes 1024)
 
 
 def _p(t):
@@ -97,8 +98,12 @@ class _Ln(torch.autograd.Function):
 
 
 def ln(x, norm_a, norm_b, grads, y=None, bias=None, p=0.0, site=0, seed_in=None, seed_dev=None, seed_out=None):
-    """LN_b(LN_a(x + dropout(y + bias))) on rows (R, C); norm_a / norm_b: torch.nn.LayerNorm modules (norm_b may be None)."""
+    """LN_b(LN_a(x + dropout(y + bias))) on rows (R, C); norm_a / norm_b: torch.nn.LayerNorm modules (norm_b may be None).
+    C <= 1024; above LN_BWD_MAX_C there is no backward, and a call that would record one is refused here."""
     gb, bb, eps_b = (None, None, 0.0) if norm_b is None else (norm_b.weight, norm_b.bias, norm_b.eps)
+    if x.shape[1] > LN_BWD_MAX_C and torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, y, bias, norm_a.weight, norm_a.bias, gb, bb)):
+        raise _native.Pn2Error(f"tail_ln: rows of {x.shape[1]} channels have a forward only (the backward kernel holds at most {LN_BWD_MAX_C} "
+                               "per row); call under torch.no_grad() or with inputs that need no gradient")
     return _Ln.apply(x, y, bias, norm_a.weight, norm_a.bias, gb, bb, norm_a.eps, eps_b, p, site, seed_in, seed_dev, seed_out, grads)
 
 
