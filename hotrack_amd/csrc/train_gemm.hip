@@ -14,7 +14,7 @@
 //                                                                    from (G_i, Y_i); epilogue: ReLU mask of layer i-1 from Y_{i-1},
 //                                                                    sum(g), sum(g xhat) of layer i-1 (its BatchNorm backward sums)
 //             tg_wgrad   dW_i = dY_i^T H_{i-1}                       both operands transformed on load; split over the rows, partial
-//                                                                    tiles reduced by tg_reduce (which also emits dgamma / dbeta)
+//                                                                    tiles reduced by tg_reduce_multi (also emits dgamma / dbeta)
 //
 // so a hidden activation is written once and read once forward (as pre-activation), and neither the normalised activations
 // H nor the pre-activation gradients dY ever exist in HBM.  The top of a stack (max over the K neighbours, or the
@@ -477,7 +477,7 @@ struct WgradArgs {
     const float *mean_p, *invstd_p, *gamma_p, *beta_p;
     float *partial;             // [gridDim.x * KG][N][K]
     long rows_per_split;        // multiple of RC
-    float *dW;                  // zeroed here (row split 0) for tg_reduce's atomic accumulation
+    float *dW;                  // zeroed here (row split 0) for tg_reduce_multi's atomic accumulation
 };
 
 template <int MT, int NT, int GMODE>
@@ -592,46 +592,8 @@ tg_wgrad_kernel(WgradArgs a) {
             const int n = m0 + strip * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
             out[(size_t)n * a.K + j0 + nb * 32 + (lane & 31)] = acc[nb][r];
         }
-    if (blockIdx.x == 0) {  // this (m, j) tile of dW starts from zero: tg_reduce accumulates its slices of the partials into it
+    if (blockIdx.x == 0) {  // this (m, j) tile of dW starts from zero: tg_reduce_multi accumulates its slices of the partials into it
         for (int e = tid; e < MT * NT; e += kT) a.dW[(size_t)(m0 + e / NT) * a.K + j0 + e % NT] = 0.f;
-    }
-}
-
-// dW += sum of a slice of the partial tiles (grid.y slices, 64 elements x 4 partial lanes per workgroup: the partials of a
-// narrow layer are few elements deep and thousands of tiles long, so the sum is spread over the partial axis as well);
-// dgamma / dbeta of the layer from its backward sums; the conv bias in front of a BatchNorm has an identically zero gradient
-__global__ void __launch_bounds__(kT)
-tg_reduce_kernel(const float *__restrict__ partial, int P, int numel, float *__restrict__ dW, const double *__restrict__ sums_bwd, int N,
-                 float *__restrict__ dgamma, float *__restrict__ dbeta, float *__restrict__ dbias) {
-    __shared__ float red[4][64];
-    const int el = threadIdx.x & 63, pl = threadIdx.x >> 6;
-    const int e = blockIdx.x * 64 + el;
-    const int per = (P + gridDim.y - 1) / gridDim.y;
-    const int p0 = blockIdx.y * per, p1 = (p0 + per) < P ? (p0 + per) : P;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    if (e < numel) {
-        int p = p0 + pl;
-        for (; p + 12 < p1; p += 16) {
-            s0 += partial[(size_t)p * numel + e];
-            s1 += partial[(size_t)(p + 4) * numel + e];
-            s2 += partial[(size_t)(p + 8) * numel + e];
-            s3 += partial[(size_t)(p + 12) * numel + e];
-        }
-        for (; p < p1; p += 4) s0 += partial[(size_t)p * numel + e];
-    }
-    red[pl][el] = (s0 + s1) + (s2 + s3);
-    __syncthreads();
-    if (pl == 0 && e < numel) atomicAdd(dW + e, (red[0][el] + red[1][el]) + (red[2][el] + red[3][el]));
-    const int c = blockIdx.x * kT + threadIdx.x;
-    if (blockIdx.y == 0 && c < N && sums_bwd) {
-        double sa = 0.0, sb = 0.0;
-        for (int r = 0; r < kBnRep; ++r) {
-            sa += sums_bwd[(size_t)r * 2 * N + c];
-            sb += sums_bwd[(size_t)r * 2 * N + N + c];
-        }
-        dbeta[c] = (float)sa;
-        dgamma[c] = (float)sb;
-        if (dbias) dbias[c] = 0.f;
     }
 }
 
@@ -846,13 +808,8 @@ extern "C" int pn2x_tg_wgrad(long rows, int n, int k, int gmode, const float *g,
     if (int rc = check_launch()) return rc;
     const int numel = n * k, P = splits * kg;
     if (n_partials) { *n_partials = P; return PN2_OK; }
-    int ps = P / 32;  // >= 32 partial tiles per slice (8 per lane)
-    if (ps < 1) ps = 1;
-    if (ps > 64) ps = 64;
-    // (numel + 63) / 64 >= (n + 255) / 256 workgroups along x: the dgamma / dbeta tail covers every channel
-    hipLaunchKernelGGL(tg_reduce_kernel, dim3((numel + 63) / 64, ps), dim3(kT), 0, st, partial, P, numel, dw, sums_bwd_i, n,
-                       dgamma, dbeta, dbias);
-    return check_launch();
+    // the immediate reduction is the deferred one's launch for this layer alone: same slices, same order, same bits
+    return pn2x_tg_reduce_multi(1, &partial, &P, &numel, &dw, &sums_bwd_i, &n, nullptr, &dgamma, &dbeta, &dbias, stream);
 }
 
 // sums_ld (may be NULL: = channels): entry j is a column slice of a layer with sums_ld[j] channels (sums_bwd[j], dgamma[j], dbeta[j],
